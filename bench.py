@@ -10,12 +10,16 @@ independent batches, no data-path collective => "weak" scaling).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up (model, autotune), warms up, times exactly K steps and prints the line;
+`ms_per_step` = wall ms of one timed step.  `--dump-outputs DIR` writes what the last timed call returned as DIR/<name>.npy
+(float32; inputs are seeded, so two builds can be compared output for output).  `--full` adds the extra objects:
   roofline     : the implicit-GEMM convolution kernel family (dominant: ~95 % of evaluation time), algorithmic
                  FLOPs (2*M*Cout*K) / summed launch durations measured with HIP events on the launch
                  stream, against the fp32 matrix/vector peak (157.3 TFLOP/s, MI355X_MICROARCH.md).
   cpu_baseline : the CPU oracle (oracle/torch_ref.py, kind "port") timed on this box's host cores on a bounded
                  sample of the same workload.
+  secondary    : the other BASELINE configurations (training step, 256x256 predictor-corrector, full domain, 64x64, untuned).
+  config.repeat_ms_per_step : the same K-step loop timed twice more.
 """
 import argparse
 import ctypes as C
@@ -35,6 +39,31 @@ PEAK_HBM_GBS = 8000.0
 FLOP_PER_SAMPLE_128 = 5.146e9     # SURVEY.md §8d, 128x128, C_in = 2
 CLOCK_WARM_S = 0.15               # continuous sampling the device needs before its clocks are steady (measured, tools/micro/call_seq.py)
 BYTES_PER_EVAL = lambda b, hw: 76.2e6 + 29.2e6 * b * (hw / 128.0) ** 2   # noqa: E731  layer-fused model, SURVEY §8d
+DUMP_BYTES = 64 << 20             # --dump-outputs: at most this many bytes in all
+
+
+def host_outputs(outputs, budget):
+    """What a timed call returned, copied to the host for --dump-outputs: name -> float32 (float64 stays float64) numpy array.
+    The arrays share `budget` bytes; one larger than its share is replaced by a fixed, seeded sample of its elements (flattened,
+    in index order)."""
+    share = budget // max(1, len(outputs))
+    res = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        t = (t if t.dtype == torch.float64 else t.float()).cpu()
+        k = share // t.element_size()
+        if t.numel() > k:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t.reshape(-1)[idx]
+        res[name] = t.numpy()
+    return res
+
+
+def write_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
 
 
 def spawn_ranks(n, argv):
@@ -519,6 +548,8 @@ def train_bench(a):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:                             # the last step's loss (every rank its own noise: loss[_rank<r>].npy)
+        write_outputs(a.dump_outputs, host_outputs({"loss" if world == 1 else f"loss_rank{rank}": loss}, DUMP_BYTES // world))
     if world > 1:
         tt = torch.tensor([dt], device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -565,6 +596,8 @@ def domain_bench(a):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert out.shape == (1, 589, 789) and torch.isfinite(out).all()
+    if a.dump_outputs and rank == 0:               # the stitched field (the same on every rank)
+        write_outputs(a.dump_outputs, host_outputs({"field": out}, DUMP_BYTES))
     if world > 1:
         tt = torch.tensor([dt], device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -592,16 +625,22 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-clock-warm", action="store_true", help="do not run extra untimed steps when the warm-up is shorter than 0.15 s of sampling")
     ap.add_argument("--no-autotune", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3 training-step measurement appended to the default line")
+    ap.add_argument("--full", action="store_true", help="besides the headline: repeated timed loops, roofline, secondary "
+                                                         "configurations and CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed call "
+                                                                         "returned as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary configurations appended to the line")
     ap.add_argument("--tune-cache", default=None, help="tile-table file: loaded when present, else written after autotuning "
                                                        "(lets the rocprofv3 passes replay exactly the benchmarked kernels)")
-    ap.add_argument("--profile-csv", default=None, help="write the per-convolution event timings here")
+    ap.add_argument("--profile-csv", default=None, help="--full: write the per-convolution event timings of the roofline here")
     ap.add_argument("--sync-bn", action="store_true", help="train mode: SyncBatchNorm (statistics summed over the ranks), eager launches")
     ap.add_argument("--mode", choices=["sample", "train", "domain"], default="sample",
                     help="sample = BASELINE configs[1] (the headline metric); train = configs[2] optimizer steps; domain = "
                          "configs[4] full-domain tiled sampling (secondary lines)")
     a = ap.parse_args()
+    if a.profile_csv and not a.full:
+        ap.error("--profile-csv is written by the roofline, which runs with --full")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:      # plain `python bench.py --gpus N`: be our own launcher
         sys.exit(spawn_ranks(a.gpus, sys.argv[1:]))
     if os.environ.get("SBGM_BENCH_DRYRUN"):                # launcher self-test (tests/test_cpu_host.py): no GPU work
@@ -663,14 +702,17 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     assert torch.isfinite(out).all()
+    dump = None
+    if a.dump_outputs:                                     # every rank its own batch: samples[_rank<r>].npy
+        dump = host_outputs({"samples" if world == 1 else f"samples_rank{rank}": out}, DUMP_BYTES // world)
     if world > 1:
         tt = torch.tensor([dt], device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
-    # the same K-step loop twice more (reported beside the headline, which stays the FIRST timed loop): at K = 20 the timed region is
-    # ~35 ms, so one number alone says little about its own spread
+    # --full: the same K-step loop twice more (reported beside the headline, which stays the FIRST timed loop): at K = 20 the timed
+    # region is ~35 ms, so one number alone says little about its own spread
     repeats = [dt]
-    for _ in range(2):
+    for _ in range(2 if a.full else 0):
         barrier()
         t1 = time.perf_counter()
         sampler(net, S.marginal_prob_std_fn, S.diffusion_coeff_fn, num_steps=a.steps, **kw)
@@ -678,10 +720,10 @@ def main():
         repeats.append(time.perf_counter() - t1)
 
     roof, cpu = None, None
-    if rank == 0:
+    if rank == 0 and a.full:
         roof = conv_roofline(net, cond, B, HW, a.sampler, dt / (a.steps * evals_per_step) * 1e3, dev, a.profile_csv)
     secondary = None
-    if rank == 0 and world == 1 and not a.no_secondary and B == 32 and HW == 128:
+    if rank == 0 and world == 1 and a.full and not a.no_secondary and B == 32 and HW == 128:
         # the other BASELINE configurations beside the headline, driver-timed too (each in a try: never lose the headline line):
         # configs[2] per-GPU training step, configs[3] 256x256 predictor-corrector, configs[4] full-domain tiles, configs[0] 64x64
         del net, out, cond
@@ -697,7 +739,7 @@ def main():
             except Exception as e:
                 secondary[name] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
-    if rank == 0 and not a.no_cpu_baseline and world == 1:         # the CPU reference leg is reported at N=1 only; it runs LAST: its
+    if rank == 0 and a.full and not a.no_cpu_baseline and world == 1:   # the CPU reference leg is reported at N=1 only; it runs LAST: its
         cpu = cpu_baseline(B, HW)                                  # OpenMP workers keep spinning on the host cores the GPU legs launch from
         if secondary is not None:                                   # CPU evals/s for the other configurations as well
             for name, args in (("c1_em", dict(batch=1, hw=64, budget_s=4.0, sampler="em", n_cond=0, max_steps=50)),
@@ -717,12 +759,16 @@ def main():
                                        f"{'Euler-Maruyama' if a.sampler == 'em' else 'predictor-corrector'} sampling, "
                                        f"{evals_per_step} network eval/step, hipGraph={'off' if a.no_graph else 'on'}",
                            "global_batch": B * world, "sampler": a.sampler, "network_evals_per_s": value * evals_per_step,
-                           "clock_warm_steps": clock_warm_steps,
-                           "repeat_ms_per_step": {"runs": [r / a.steps * 1e3 for r in repeats], "min": min(repeats) / a.steps * 1e3,
-                                                  "median": sorted(repeats)[1] / a.steps * 1e3,
-                                                  "note": "3 consecutive timed loops of the same K steps; ms_per_step / value are the first"},
+                           "clock_warm_steps": clock_warm_steps, "full": a.full,
                            "parallelism": f"dp{world} (independent batches, no collective)"},
                 "roofline": roof, "cpu_baseline": cpu, "secondary": secondary}
+        if a.full:
+            line["config"]["repeat_ms_per_step"] = {"runs": [r / a.steps * 1e3 for r in repeats], "min": min(repeats) / a.steps * 1e3,
+                                                    "median": sorted(repeats)[1] / a.steps * 1e3,
+                                                    "note": "3 consecutive timed loops of the same K steps; ms_per_step / value are the first"}
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

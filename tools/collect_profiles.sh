@@ -5,7 +5,7 @@
 # 1. bench.py autotune -> tile table saved
 # 2. rocprofv3 --kernel-trace --stats of the same command (same tile table)          -> <tag>_<wl>_kernel_stats.csv, _step_breakdown.txt
 # 3. two PMC passes (FETCH_SIZE, WRITE_SIZE; never combined with other trace domains) -> <tag>_pmc_traffic_<wl>.json (+ source hash)
-# 4. bench.py: the JSON line (roofline.traffic from 3) and the per-convolution HIP-event timings
+# 4. bench.py --full: the JSON line (roofline.traffic from 3) and the per-convolution HIP-event timings
 # then the C3 training step (kernel trace -> <tag>_train_step_breakdown.txt, bench line).
 # Everything lands in gpurun_out/profiles_<tag>/ ; copy what should be judged into profiles/.
 set -eo pipefail
@@ -35,7 +35,7 @@ one_workload () {   # name  workload-key  steps  extra bench args...
     rm -rf $OUT/pmc_fetch $OUT/pmc_write $OUT/*.log
     # the bench line last: it reads the traffic file measured above (same kernel sources, same tile table) from profiles/
     cp $OUT/${TAG}_pmc_traffic_${WL}.json profiles/
-    python3 bench.py --steps $STEPS --warmup 10 --tune-cache $T --profile-csv $OUT/${TAG}_${NAME}_conv_launches_hip_events.csv "$@" \
+    python3 bench.py --full --steps $STEPS --warmup 10 --tune-cache $T --profile-csv $OUT/${TAG}_${NAME}_conv_launches_hip_events.csv "$@" \
         > $OUT/${TAG}_${NAME}_bench_line.json 2> $OUT/${NAME}_bench.err
     echo "== $NAME"; cut -c1-260 $OUT/${TAG}_${NAME}_bench_line.json; head -3 $OUT/${TAG}_${NAME}_step_breakdown.txt
 }
