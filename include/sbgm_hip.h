@@ -378,6 +378,18 @@ int sbgm_adam_step_blocks(int64_t numel);
  * replicas: the averaging of reference-style data parallelism without a pass of its own). */
 int sbgm_adam_step_batched(const sbgm_adam_desc* desc_dev, int n, int total_blocks, const float* step, float lr, float beta1,
                            float beta2, float eps, float weight_decay, int decoupled, float grad_scale, void* stream);
+/* The same step with an exponential moving average of the parameters in the same launch (training.with_ema).  ema: DEVICE array
+ * of n shadow pointers, parallel to desc.  After the update each shadow moves towards its parameter, e += ema_rate * (p - e),
+ * ema_rate = 1 - decay of this step; p, m and v come out bit-identical to the launch without the average.  A descriptor with
+ * g == NULL takes no optimizer step (m, v unused): only its shadow moves towards p, or, with reserved == 1, receives a bit copy of
+ * p, numel then counting 32-bit words (integer buffers such as num_batches_tracked).  Shadows follow the 16-byte alignment rule
+ * of the other pointers (aligned tensors take the vector path, the rest the scalar one). */
+int sbgm_adam_ema_step_batched(const sbgm_adam_desc* desc_dev, float* const* ema, int n, int total_blocks, const float* step, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, int decoupled, float grad_scale, float ema_rate,
+                               void* stream);
+/* EMA only, for optimizers whose step is not the launch above: every descriptor is treated as g == NULL (g, m, v are never read).
+ * Blocks per descriptor: sbgm_adam_step_blocks(numel). */
+int sbgm_ema_update_batched(const sbgm_adam_desc* desc_dev, float* const* ema, int n, int total_blocks, float ema_rate, void* stream);
 int sbgm_colsum(const float* x, const float* y /* NULL or multiplied elementwise */, float* out, int M, int C, void* stream);
 int sbgm_samplesum(const float* x, float* out /* [B,C] */, int B, int HW, int C, void* stream);
 /* ws: >= 8*B*C bytes */

@@ -87,6 +87,15 @@ int sbgm_adam_step_batched(const sbgm_adam_desc* desc_dev, int n, int total_bloc
                            float beta2, float eps, float weight_decay, int decoupled, float grad_scale, void* stream) {
     return sbgm_launch_adam_batched(desc_dev, n, total_blocks, step, lr, beta1, beta2, eps, weight_decay, decoupled, grad_scale, ST);
 }
+int sbgm_adam_ema_step_batched(const sbgm_adam_desc* desc_dev, float* const* ema, int n, int total_blocks, const float* step, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, int decoupled, float grad_scale, float ema_rate,
+                               void* stream) {
+    return sbgm_launch_adam_ema_batched(desc_dev, ema, n, total_blocks, step, lr, beta1, beta2, eps, weight_decay, decoupled, grad_scale,
+                                        ema_rate, ST);
+}
+int sbgm_ema_update_batched(const sbgm_adam_desc* desc_dev, float* const* ema, int n, int total_blocks, float ema_rate, void* stream) {
+    return sbgm_launch_ema_batched(desc_dev, ema, n, total_blocks, ema_rate, ST);
+}
 int sbgm_batchnorm_train_stats(const float* x, int B, int HW, int C, void* stats_ws, void* stream) {
     return sbgm_launch_batchnorm_stats(x, B, HW, C, static_cast<double*>(stats_ws), ST);
 }

@@ -1,5 +1,5 @@
 """`generation_main(cfg)` — reference sbgm/evaluate_sbgm/generation_main.py:47-181: seed, model, checkpoint
-(`network_params`), generation loader, `SampleGenerator`, then every `cfg.evaluation.gen_type`."""
+(`network_params`, or `ema_network_params` with training.load_ema), generation loader, `SampleGenerator`, then every `cfg.evaluation.gen_type`."""
 from __future__ import annotations
 
 import os
@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from .. import parallel
+from ..ema import pick_network_params
 from ..training_utils import get_gen_dataloader, get_model, setup_logger
 from ..utils import get_model_string
 from .generation import SampleGenerator
@@ -29,8 +30,9 @@ def generation_main(cfg, dataloader=None, back_transforms=None):
     device = torch.device("cuda", local) if dev == "cuda" and torch.cuda.is_available() else torch.device("cpu")
     model, ckpt_dir, ckpt_name = get_model(cfg)
     model = model.to(device)
-    state = torch.load(os.path.join(ckpt_dir, ckpt_name), map_location=device, weights_only=True)["network_params"]
-    model.load_state_dict(state)
+    ckpt = torch.load(os.path.join(ckpt_dir, ckpt_name), map_location=device, weights_only=True)
+    # training.load_ema: sample from the exponential moving average of the weights when the checkpoint has it
+    model.load_state_dict(pick_network_params(ckpt, bool(cfg["training"].get("load_ema", False)), f"{ckpt_dir}/{ckpt_name}"))
     log.info(f"[INFO] Model checkpoint loaded from: {ckpt_dir}/{ckpt_name}")
     if back_transforms is None and cfg["evaluation"].get("transform_back", False):
         # reference generation_main.py:93-108: inverse transforms from the saved global statistics (device-side classes)

@@ -17,9 +17,15 @@ class _NativeStep:
 
     `grad_scale` (default 1.0) multiplies every gradient as the step reads it.  The data-parallel pipeline sets it to 1 / world
     and leaves the all-reduced SUM in `.grad`: the division of gradient averaging then costs nothing (a `flat.div_(world)` is a
-    76 MB read + write pass per step).  Groups that fall back to torch's own step get their gradients scaled in place first."""
+    76 MB read + write pass per step).  Groups that fall back to torch's own step get their gradients scaled in place first.
+
+    `ema` (default None) is an ema.ModelEMA the pipeline attaches with `training.with_ema`: every step() then makes exactly one
+    EMA update.  The native groups' launches carry it as an epilogue, and the tensors they do not step (buffers, parameters
+    without a gradient) ride on the last one as EMA-only descriptors; when some group takes torch's own step, that remainder is
+    one EMA-only launch after it instead."""
     _decoupled = 0
     grad_scale = 1.0
+    ema = None
 
     def _native_ok(self, group, params):
         return (params and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and not p.grad.is_sparse
@@ -34,6 +40,7 @@ class _NativeStep:
             with torch.enable_grad():
                 loss = closure()
         leftovers = False
+        plan = []
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
             if not params:
@@ -41,7 +48,17 @@ class _NativeStep:
             if not self._native_ok(group, params):
                 leftovers = True
                 continue
-            self._step_group(gi, group, params)
+            plan.append((gi, group, params))
+        ema = self.ema if self.ema is not None and self.ema.shadow is not None else None
+        if ema is None:
+            for gi, group, params in plan:
+                self._step_group(gi, group, params)
+        else:
+            rate = ema.advance()
+            covered = {p.data_ptr() for _, _, params in plan for p in params}
+            for k, (gi, group, params) in enumerate(plan):
+                rest = ema.rest_rows(covered) if not leftovers and k == len(plan) - 1 else []
+                self._step_group_ema(gi, group, params, rate, rest)
         if leftovers:                                  # torch's own step for the groups the launch does not cover
             saved = [(g, g["params"]) for g in self.param_groups]
             try:
@@ -55,6 +72,8 @@ class _NativeStep:
             finally:
                 for g, ps in saved:
                     g["params"] = ps
+        if ema is not None and (leftovers or not plan):    # the remainder after torch's own step (or a step without gradients)
+            ema.launch_rest(rate, covered)
         return loss
 
     def state_dict(self):
@@ -65,7 +84,8 @@ class _NativeStep:
         sd["state"] = {k: ({**v, "step": v["step"].clone()} if torch.is_tensor(v.get("step")) else v) for k, v in sd["state"].items()}
         return sd
 
-    def _step_group(self, gi, group, params):
+    def _group_state(self, params):
+        """(device step counter of the group, contiguous gradients); creates exp_avg / exp_avg_sq on first use"""
         dev = params[0].device
         first = self.state[params[0]]
         master = first.get("step")
@@ -77,7 +97,24 @@ class _NativeStep:
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             st["step"] = master                        # one device counter per group; every parameter's entry refers to it
-        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
+        return master, [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
+
+    def _step_group_ema(self, gi, group, params, rate, rest):
+        """the group's step with the EMA epilogue (rate = 1 - d_n), plus the EMA-only descriptor rows `rest`, in one launch"""
+        master, grads = self._group_state(params)
+        rows = [(p.data_ptr(), g.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
+                 self.ema.shadow_ptr(p), p.numel(), 0) for p, g in zip(params, grads)] + rest
+        d_dev, e_dev, n, blk = self.ema.table(("adam", gi), rows, params[0].device)
+        master += 1
+        b1, b2 = group["betas"]
+        N.check(N.lib().sbgm_adam_ema_step_batched(d_dev.data_ptr(), e_dev.data_ptr(), n, blk, master.data_ptr(), float(group["lr"]), float(b1),
+                                                   float(b2), float(group["eps"]), float(group["weight_decay"]), self._decoupled,
+                                                   float(self.grad_scale), float(rate), N.stream()))
+        N.bump_generation()                            # parameters and shadow were written through raw pointers
+
+    def _step_group(self, gi, group, params):
+        dev = params[0].device
+        master, grads = self._group_state(params)
         key = tuple((p.data_ptr(), g.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(), p.numel())
                     for p, g in zip(params, grads))
         cache = self.__dict__.setdefault("_native_tables", {})

@@ -14,6 +14,7 @@ libsbgm_hip.so raises.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import functools
 import logging
@@ -337,6 +338,18 @@ class ScoreNet(nn.Module):
         self.sigma = _sigma_of(marginal_prob_std)
         self._engines = {}
         self.to(self.device)
+
+    def __deepcopy__(self, memo):
+        # an _Engine owns a raw native model handle that its __del__ destroys: a copy starts without engines (and without the
+        # gradient arena, whose flat buffer and pointer index belong to this model's parameters) and builds its own on first use
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k == "_engines":
+                new.__dict__[k] = {}
+            elif k != "_grad_arena":
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
 
     # -- engine plumbing -----------------------------------------------------------------------------------
     def _engine(self, lsm_cond, topo_cond, cond_img) -> _Engine:

@@ -3,7 +3,9 @@ __init__ :41-117, xavier_init_weights :188-201, load_checkpoint :203-222, save_m
 train :424-508, validate_batches :510-609, generate_and_plot_samples :611-786).
 
 Same constructor signature, same per-batch order (zero_grad -> loss_fn -> backward -> step -> .item()), same checkpoint
-dict (`network_params`, `optimizer_params`), best-validation checkpointing, per-epoch pickled losses.  Kept out:
+dict (`network_params`, `optimizer_params`), best-validation checkpointing, per-epoch pickled losses.  `training.with_ema` (which
+the reference reads but never implements) keeps an exponential moving average of the weights in `ema_model` (ema.py): validation,
+the per-epoch preview and `load_ema` then use it, and checkpoints gain `ema_network_params` / `ema_num_updates`.  Kept out:
 matplotlib plotting (`generate_and_plot_samples` only generates and returns the samples) and the precipitation
 back-transform of the sentinel.  New relative to the reference: when a process group exists
 the gradients are all-reduced (one flattened bucket, RCCL) between backward and step.
@@ -18,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import parallel
+from .ema import EMA_COUNT_KEY, EMA_KEY, ModelEMA, pick_network_params
 from .score_sampling import Euler_Maruyama_sampler, ode_sampler, pc_sampler
 from .utils import (draw_condition_dropout, extract_samples, extract_samples_device, get_model_string,
                     report_precip_extremes)
@@ -27,6 +30,8 @@ _SAMPLERS = {"pc_sampler": pc_sampler, "Euler_Maruyama_sampler": Euler_Maruyama_
 
 
 class TrainingPipeline_general:
+    ema = None                          # ema.ModelEMA with training.with_ema
+
     def __init__(self, model, loss_fn, marginal_prob_std_fn, diffusion_coeff_fn, optimizer, device, lr_scheduler, cfg):
         self.model, self.loss_fn, self.optimizer, self.lr_scheduler, self.cfg = model, loss_fn, optimizer, lr_scheduler, cfg
         self.marginal_prob_std_fn, self.diffusion_coeff_fn = marginal_prob_std_fn, diffusion_coeff_fn
@@ -54,6 +59,18 @@ class TrainingPipeline_general:
         for d in (self.checkpoint_dir, self.path_losses):
             os.makedirs(d, exist_ok=True)
         self._bucket = None
+        # the shadow is built from the live weights when training starts (train_batches), not here: training_main broadcasts the
+        # parameters and may load a checkpoint after constructing the pipeline
+        self.ema = ModelEMA(self.model, float(t.get("ema_decay", 0.9999))) if self.with_ema else None
+
+    @property
+    def ema_model(self):
+        """the EMA shadow ScoreNet (None without training.with_ema, or before training has started / a checkpoint has restored it)"""
+        return self.ema.shadow if self.ema is not None else None
+
+    def _eval_model(self):
+        """the weights validation and sampling run on: the EMA shadow when there is one, else the live model"""
+        return self.ema.shadow if self.ema is not None and self.ema.shadow is not None else self.model
 
     @staticmethod
     def _build_back_transforms(cfg):
@@ -83,13 +100,20 @@ class TrainingPipeline_general:
                 m.bias.data.fill_(0.01)
 
     def load_checkpoint(self, checkpoint_path, load_ema=False, device=None):
-        state = torch.load(checkpoint_path, map_location=device or self.device, weights_only=True)["network_params"]
-        self.model.load_state_dict(state)
+        """`network_params` into the model, or with load_ema the checkpoint's EMA weights (reference training.py:205-207); with
+        training.with_ema the shadow and its update counter are restored too whenever the file has them."""
+        ck = torch.load(checkpoint_path, map_location=device or self.device, weights_only=True)
+        self.model.load_state_dict(pick_network_params(ck, load_ema, checkpoint_path))
+        if self.ema is not None and EMA_KEY in ck:
+            self.ema.load_state_dict({"network_params": ck[EMA_KEY], "num_updates": int(ck.get(EMA_COUNT_KEY, 0))})
 
     def save_model(self, dirname="./model_params", filename="SBGM.pth"):
         os.makedirs(dirname, exist_ok=True)
-        return torch.save({"network_params": self.model.state_dict(), "optimizer_params": self.optimizer.state_dict()},
-                          os.path.join(dirname, filename))
+        ck = {"network_params": self.model.state_dict(), "optimizer_params": self.optimizer.state_dict()}
+        if self.ema is not None:
+            ema = self.ema.state_dict()
+            ck[EMA_KEY], ck[EMA_COUNT_KEY] = ema["network_params"], ema["num_updates"]
+        return torch.save(ck, os.path.join(dirname, filename))
 
     def _extract(self, samples, split):
         """Batch dict -> tensors on the device.  Raw batches (1-channel geo fields) and batches that need the
@@ -102,9 +126,9 @@ class TrainingPipeline_general:
             return extract_samples_device(samples, self.device, dropped)
         return extract_samples(samples, self.device)
 
-    def _loss(self, samples, split="train"):
+    def _loss(self, samples, split="train", model=None):
         x, seasons, cond, _lsm_hr, lsm, sdf, topo, _hp, _lp = self._extract(samples, split)
-        return x, self.loss_fn(self.model, x, self.marginal_prob_std_fn, y=seasons, cond_img=cond, lsm_cond=lsm,
+        return x, self.loss_fn(model if model is not None else self.model, x, self.marginal_prob_std_fn, y=seasons, cond_img=cond, lsm_cond=lsm,
                                topo_cond=topo, sdf_cond=sdf if self.sdf_weighted_loss else None)
 
     def _graph_step(self, samples, soft=False):
@@ -222,6 +246,15 @@ class TrainingPipeline_general:
         fold = self._bucket is not None and hasattr(self.optimizer, "grad_scale")
         if fold:
             self.optimizer.grad_scale = 1.0 / world
+        # training.with_ema: native Adam / AdamW average inside their own launch (optim._NativeStep.ema); other optimizers get one
+        # EMA-only launch after their step.  Either way exactly one update per optimizer step, eager or replayed.
+        ema_after_step = False
+        if self.ema is not None:
+            self.ema.start()
+            if hasattr(self.optimizer, "ema"):
+                self.optimizer.ema = self.ema
+            else:
+                ema_after_step = True
         meter = self._LossMeter(self.device)
         from . import train_graph
         # training.use_hip_graph: true / false / auto (default, also when the key is absent as in the reference's YAML files): auto
@@ -254,6 +287,8 @@ class TrainingPipeline_general:
             if self._bucket is not None:
                 self._bucket.all_reduce_(average=not fold)   # the exchange step of the path (its decoder part started inside backward)
             self.optimizer.step()
+            if ema_after_step:
+                self.ema.update()
             meter.add(batch_loss)
         train_graph.set_overlap_bucket(prev_overlap)
         avg = meter.flush() / max(1, len(dataloader))
@@ -263,10 +298,11 @@ class TrainingPipeline_general:
 
     def validate_batches(self, dataloader, verbose=True):
         self.model.eval()
+        model = self._eval_model()        # with training.with_ema the EMA weights: best-checkpoint selection follows their loss
         meter = self._LossMeter(self.device)
         with torch.inference_mode():
             for samples in dataloader:
-                meter.add(self._loss(samples, "valid")[1])
+                meter.add(self._loss(samples, "valid", model)[1])
         avg = meter.flush() / max(1, len(dataloader))
         if verbose:
             logger.info(f"→ Validation Loss: {avg:.4f}")
@@ -297,14 +333,15 @@ class TrainingPipeline_general:
         """Per-epoch preview: first generation batch through cfg.sampler.sampler_type with the reference's kwargs
         (training.py:683-695).  Returns the generated tensor [B,1,H,W] (plotting is out of scope)."""
         if os.path.exists(self.checkpoint_path):
-            self.load_checkpoint(self.checkpoint_path)
+            self.load_checkpoint(self.checkpoint_path)       # network_params -> model; with training.with_ema the EMA weights -> shadow
         self.model.eval()
+        model = self._eval_model()
         sampler = _SAMPLERS.get(cfg["sampler"]["sampler_type"])
         if sampler is None:
             raise ValueError(f"Sampler type {cfg['sampler']['sampler_type']} not recognized.")
         samples = next(iter(gen_dataloader))
         x, seasons, cond, _lsm_hr, lsm, _sdf, topo, _hp, _lp = extract_samples(samples, self.device)
-        kw = dict(score_model=self.model, marginal_prob_std=self.marginal_prob_std_fn, diffusion_coeff=self.diffusion_coeff_fn,
+        kw = dict(score_model=model, marginal_prob_std=self.marginal_prob_std_fn, diffusion_coeff=self.diffusion_coeff_fn,
                   batch_size=x.shape[0], num_steps=cfg["sampler"]["n_timesteps"], device=self.device,
                   img_size=cfg["highres"]["data_size"][0])
         if sampler is not ode_sampler:
