@@ -26,7 +26,7 @@ int sbgm_abi_version(void);
 
 enum { SBGM_NONE = 0, SBGM_RELU = 1, SBGM_SILU = 2, SBGM_GELU = 3 };   /* activation codes */
 enum { SBGM_NORM_INSTANCE = 0, SBGM_NORM_GROUP = 1 };
-enum { SBGM_SAMPLER_EM = 0, SBGM_SAMPLER_PC = 1 };
+enum { SBGM_SAMPLER_EM = 0, SBGM_SAMPLER_PC = 1, SBGM_SAMPLER_EDM_HEUN = 2 };
 
 /* ------------------------------------------------------------------------------------------------------------
  * Model handle.  Replaces: training_utils.get_model -> Encoder/Decoder/ScoreNet construction
@@ -126,6 +126,21 @@ typedef struct sbgm_sampler_args {
  * the old graph is still executing, and guided runs (cfg_enabled), which free per-call condition copies at their end.  The handle's
  * workspace is the engine's: the caller passes no scratch memory. */
 int sbgm_sampler_run(sbgm_model* m, const sbgm_sampler_args* a, void* stream);
+
+/* Deterministic few-step sampler: second-order Heun solver of the probability-flow ODE on the Karras sigma ladder
+ * (Karras et al. 2022, Alg. 2), for the same VE-SDE score network (no retraining).  a->kind must be SBGM_SAMPLER_EDM_HEUN;
+ * a->snr and a->cfg_scale_corrector are ignored (with guidance both evaluations of a step use cfg_scale); a->bn_train must be 0.
+ *   ladder: sigma_i = (smax^(1/rho) + i/(N-1) (smin^(1/rho) - smax^(1/rho)))^rho, i < N = num_steps, sigma_N = 0.
+ *           sigma_min / sigma_max <= 0 mean the trained range [std(eps), std(1)] of the model's sigma; other values are clipped to it.
+ *   step i: gamma_i = min(s_churn/N, sqrt2-1) if s_tmin <= sigma_i <= s_tmax else 0, capped so sigma_hat = sigma_i (1+gamma_i) <= sigma_0;
+ *           x_hat = x + s_noise sqrt(sigma_hat^2 - sigma_i^2) z_i (only when s_churn > 0); d = -sigma_hat score(x_hat, t(sigma_hat));
+ *           x' = x_hat + (sigma_{i+1} - sigma_hat) d; then for i < N-1 the Heun correction with score(x', t(sigma_{i+1})), and for
+ *           i = N-1 x = x' (one evaluation).  2N-1 network evaluations; out = x after the last step, NCHW [B,1,H,W].
+ *   noise:  init x = sigma_0 z_0, then z_{1+i} per step when s_churn > 0: 1 draw, or 1 + N.
+ * With use_graph one full Heun step is captured and replayed N-1 times on `stream`; the final Euler-only step is enqueued
+ * eagerly.  Blocking behaviour is that of sbgm_sampler_run. */
+int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
+                         float s_tmin, float s_tmax, float s_noise, void* stream);
 
 /* Conv autotuning: time the tile / split-K candidates of every convolution of the (B,H,W) plan once and keep the
  * fastest.  Synchronises the stream.  Optional; without it a static heuristic is used. */
@@ -457,13 +472,20 @@ int sbgm_dsm_loss_bwd(const float* score, const float* z, const float* std, cons
  * z NULL -> Philox draw keyed by (seed, draw_index).
  *   em:       x_mean = x + (g2*score)*dt ; x = x_mean + noise_coef*z            score_sampling.py:124-125, :224-227
  *   langevin: eps = 2*(snr_noise_norm / mean_b||score_b||)^2 ; x += eps*score + sqrt(2 eps)*z      :200-204
- *   cfg:      out = (1+w)*s_cond - w*s_uncond                                                        :55      */
+ *   cfg:      out = (1+w)*s_cond - w*s_uncond                                                        :55
+ *   edm churn: x += churn_coef*z                     (EDM Heun, sbgm_sampler_run_edm)
+ *   edm euler: d = -sigma_hat*score ; x_next = x_hat + (sigma_next - sigma_hat)*d
+ *   edm heun:  x = x + (sigma_next - sigma_hat)*0.5*(d - sigma_next*score)   (x holds x_hat on entry)              */
 int sbgm_em_step(float* x, float* x_mean, const float* score, const float* z, float g2, float dt, float noise_coef,
                  uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
 int sbgm_langevin_step(float* x, const float* score, const float* z, float snr_noise_norm, void* sumsq_ws /* >= 8*B B */,
                        uint64_t seed, uint64_t draw_index, int B, int64_t per_sample, void* stream);
 int sbgm_cfg_combine(float* out, const float* s_cond, const float* s_uncond, float scale, int64_t n, void* stream);
 int sbgm_randn_scaled(float* x, float scale, uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
+int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
+int sbgm_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, float sigma_hat, float sigma_next, int64_t n,
+                   void* stream);
+int sbgm_edm_heun(float* x, const float* d, const float* score, float sigma_hat, float sigma_next, int64_t n, void* stream);
 
 /* ---- after the sampler -------------------------------------------------------------------------
  * sbgm_pointwise_chain: y[i] = program(x[i]); the program is at most SBGM_CHAIN_MAX_OPS scalar steps, each rounded to fp32

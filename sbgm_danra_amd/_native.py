@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libsbgm_hip.so")
 
 NONE, RELU, SILU, GELU = 0, 1, 2, 3
 NORM_INSTANCE, NORM_GROUP = 0, 1
-SAMPLER_EM, SAMPLER_PC = 0, 1
+SAMPLER_EM, SAMPLER_PC, SAMPLER_EDM_HEUN = 0, 1, 2
 
 _vp, _i, _f, _i64, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 
@@ -78,6 +78,7 @@ SIGNATURES = {
     "sbgm_model_workspace_bytes": (_i64, [_vp]),
     "sbgm_model_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "sbgm_sampler_run": (_i, [_vp, C.POINTER(SamplerArgs), _vp]),
+    "sbgm_sampler_run_edm": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _vp]),
     "sbgm_pointwise_chain": (_i, [_vp, _vp, _i64, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     "sbgm_sample_extremes": (_i, [_vp, _i, _i64, _f, _vp, _vp, _vp]),
     "sbgm_assemble_conditions": (_i, [C.POINTER(AssembleArgs), _vp]),
@@ -167,6 +168,9 @@ SIGNATURES = {
     "sbgm_langevin_step": (_i, [_vp, _vp, _vp, _f, _vp, _u64, _u64, _i, _i64, _vp]),
     "sbgm_cfg_combine": (_i, [_vp, _vp, _vp, _f, _i64, _vp]),
     "sbgm_randn_scaled": (_i, [_vp, _f, _u64, _u64, _i64, _vp]),
+    "sbgm_edm_churn": (_i, [_vp, _vp, _f, _u64, _u64, _i64, _vp]),
+    "sbgm_edm_euler": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i64, _vp]),
+    "sbgm_edm_heun": (_i, [_vp, _vp, _vp, _f, _f, _i64, _vp]),
 }
 
 ABI_VERSION = 4          # include/sbgm_hip.h: sbgm_abi_version()

@@ -366,5 +366,18 @@ int sbgm_cfg_combine(float* out, const float* s_cond, const float* s_uncond, flo
 int sbgm_randn_scaled(float* x, float scale, uint64_t seed, uint64_t draw_index, int64_t n, void* stream) {
     return sbgm_launch_init_noise(x, scale, nullptr, seed, nullptr, draw_index, (size_t)n, ST);
 }
+int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, uint64_t draw_index, int64_t n, void* stream) {
+    const EdmStep sc{0.f, 0.f, 0.f, 0.f, 0.f, churn_coef};
+    return sbgm_launch_edm_churn(x, nullptr, z, nullptr, nullptr, &sc, draw_index, seed, (size_t)n, ST);
+}
+int sbgm_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, float sigma_hat, float sigma_next, int64_t n,
+                   void* stream) {
+    const EdmStep sc{0.f, sigma_hat, sigma_next, 0.f, 0.f, 0.f};
+    return sbgm_launch_edm_euler(x_hat, score, d, x_next, nullptr, nullptr, &sc, nullptr, 0, (size_t)n, ST);
+}
+int sbgm_edm_heun(float* x, const float* d, const float* score, float sigma_hat, float sigma_next, int64_t n, void* stream) {
+    const EdmStep sc{0.f, sigma_hat, sigma_next, 0.f, 0.f, 0.f};
+    return sbgm_launch_edm_heun(x, nullptr, d, score, nullptr, nullptr, &sc, nullptr, 0, 1, (size_t)n, ST);
+}
 
 }  // extern "C"

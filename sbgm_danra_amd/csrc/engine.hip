@@ -93,6 +93,8 @@ struct sbgm_model {
     SamplerState* d_state = nullptr;
     StepScalars* d_table = nullptr;
     int table_cap = 0;
+    EdmStep* d_edm_table = nullptr;          // step table of the EDM Heun sampler (its own rows; same counter / RNG state)
+    int edm_table_cap = 0;
     // pinned host staging of a run's step table + initial state: the upload is a true asynchronous copy, so sbgm_sampler_run does not
     // have to wait for it (or for anything enqueued before it); ev_stage guards the buffer against the next call's rewrite
     char* h_stage = nullptr;
@@ -111,7 +113,7 @@ struct sbgm_model {
     // two steps.  Everything a step bakes in is in the key (shapes, sampler kind, caller tensors, scalar arguments, workspace,
     // tile-table generation); what changes between runs lives in device memory (step table, step counter, RNG offset AND seed).
     struct StepGraphKey {
-        int B, H, W, kind, guided, bn_train, domain_w;
+        int B, H, W, kind, guided, bn_train, domain_w, churn;
         const void *y, *cond, *lsm, *topo, *origins, *ws, *table;
         size_t ws_bytes;
         float cfg, cfg_corr, snr_nn;
@@ -135,6 +137,7 @@ struct sbgm_model {
         if (ws) (void)hipFree(ws);
         if (d_state) (void)hipFree(d_state);
         if (d_table) (void)hipFree(d_table);
+        if (d_edm_table) (void)hipFree(d_edm_table);
         if (h_stage) (void)hipHostFree(h_stage);
         if (ev_stage) (void)hipEventDestroy(ev_stage);
         if (graph_stream) (void)hipStreamDestroy(graph_stream);
@@ -181,7 +184,7 @@ struct sbgm_model {
     int build(const sbgm_model_config& c);
     int ensure_ws(size_t bytes);
     int dummy_forward(int B, int H, int W, bool tune, hipStream_t st);
-    int prepare_ws(int B, int H, int W, int bn_train, size_t factor, hipStream_t st);
+    int prepare_ws(int B, int H, int W, int bn_train, size_t factor, hipStream_t st, int kind = SBGM_SAMPLER_EM);
     float* wsalloc(size_t floats) {     // bump allocator over the activation workspace; nullptr (+ error text) when full
         const size_t bytes = align_up(floats * 4, 256);
         if (ws_used + bytes > ws_bytes) {
@@ -201,11 +204,14 @@ struct sbgm_model {
     std::map<std::array<int, 4>, size_t> ws_peak;
     size_t ws_target = 0;                   // largest measured total need (forward + sampler slabs) of any shape seen so far
     size_t fwd_need(int B, int H, int W, int bn_train = 0) const;
-    size_t sampler_keep(int B, int H, int W) const {
+    // persistent sampler slabs: x, score, x_mean (+ the Heun derivative d for SBGM_SAMPLER_EDM_HEUN), time vector, norm partials
+    size_t sampler_keep(int B, int H, int W, int kind = SBGM_SAMPLER_EM) const {
         const size_t n = (size_t)B * H * W;
-        return align_up(n * 4, 256) * 3 + align_up((size_t)B * 4, 256) + align_up((size_t)B * 8, 256);
+        return align_up(n * 4, 256) * (kind == SBGM_SAMPLER_EDM_HEUN ? 4 : 3) + align_up((size_t)B * 4, 256) + align_up((size_t)B * 8, 256);
     }
-    size_t ws_need(int B, int H, int W, int bn_train = 0) const { return fwd_need(B, H, W, bn_train) + sampler_keep(B, H, W); }
+    size_t ws_need(int B, int H, int W, int bn_train = 0, int kind = SBGM_SAMPLER_EM) const {
+        return fwd_need(B, H, W, bn_train) + sampler_keep(B, H, W, kind);
+    }
     int fold_bn(hipStream_t st);
     ConvTile pick_tile(const ConvGeom& g, const ConvParams& p);
     int conv(const ConvGeom& g, ConvParams p, hipStream_t st);
@@ -223,7 +229,8 @@ struct sbgm_model {
         }
         return rc;
     }
-    int sampler(const sbgm_sampler_args& a, hipStream_t st);
+    struct EdmArgs { float sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise; };
+    int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr);
 };
 
 int sbgm_model::build(const sbgm_model_config& c) {
@@ -931,7 +938,33 @@ static std::vector<float> linspace_f32(float start, float end, int n) {
     return v;
 }
 
-int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
+// EDM Heun step table (Karras et al. 2022, Alg. 2) for the VE SDE std(t) = sqrt((sigma^2t - 1) / (2 ln sigma)): the Karras ladder between
+// sigma_min and sigma_max (<= 0: the trained range [std(eps), std(1)]; other values are clipped to it), churn gamma_i, t(sigma) =
+// log1p(2 ln sigma * s^2) / (2 ln sigma) clamped to [eps, 1].  float64 throughout, stored as fp32: score_sampling.edm_heun_schedule.
+static void edm_table(EdmStep* tab, int N, double sig, double eps, const sbgm_model::EdmArgs& e) {
+    const double ls = std::log(sig);
+    auto std_of = [&](double t) { return std::sqrt(std::expm1(2.0 * t * ls) / (2.0 * ls)); };
+    const double lo = std_of(eps), hi = std_of(1.0);
+    auto t_of = [&](double s) {                            // clamped in sigma too: sigma >= std(1) is t = 1 exactly
+        return s >= hi ? 1.0 : s <= lo ? eps : std::min(1.0, std::max(eps, std::log1p(2.0 * ls * s * s) / (2.0 * ls)));
+    };
+    const double smin = e.sigma_min > 0 ? std::min(hi, std::max(lo, (double)e.sigma_min)) : lo;
+    const double smax = e.sigma_max > 0 ? std::min(hi, std::max(lo, (double)e.sigma_max)) : hi;
+    const double rho = e.rho, a0 = std::pow(smax, 1.0 / rho), a1 = std::pow(smin, 1.0 / rho);
+    std::vector<double> sg(N + 1);
+    for (int i = 0; i < N; ++i) sg[i] = std::pow(a0 + (double)i / (double)(N - 1) * (a1 - a0), rho);
+    sg[0] = smax; sg[N - 1] = smin; sg[N] = 0.0;           // the ends exactly (the power round trip is off by an ulp)
+    const double gmax = std::min((double)e.s_churn / (double)N, std::sqrt(2.0) - 1.0);
+    for (int i = 0; i < N; ++i) {
+        double g = (e.s_tmin <= sg[i] && sg[i] <= e.s_tmax) ? gmax : 0.0;
+        g = std::min(g, sg[0] / sg[i] - 1.0);
+        const double sh = sg[i] * (1.0 + g);
+        tab[i] = EdmStep{(float)sg[i], (float)sh, (float)sg[i + 1], (float)t_of(sh), (float)t_of(sg[i + 1]),
+                         (float)((double)e.s_noise * std::sqrt(std::max(0.0, sh * sh - sg[i] * sg[i])))};
+    }
+}
+
+int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm) {
     // Graph CAPTURE is illegal on the legacy default stream, so the step is captured on a private stream (capture records, it runs
     // nothing); the REPLAYS, the uploads and the final copy go to the caller's stream, so the run is ordinary stream-ordered work of the
     // caller.  (Round 2 also replayed on the private stream, fenced with events on both sides: measured 1.639 vs 1.589 ms per C2 step —
@@ -952,16 +985,18 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
             st = graph_stream;
         }
     }
-    SBGM_CHECK(a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC, "sampler: unknown kind %d", a.kind);
+    const bool heun = edm != nullptr;                      // only sbgm_sampler_run_edm passes EDM arguments
+    SBGM_CHECK(heun ? a.kind == SBGM_SAMPLER_EDM_HEUN : (a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC),
+               "sampler: unknown kind %d", a.kind);
     SBGM_CHECK(a.num_steps >= 2, "sampler: num_steps=%d must be >= 2 (step size = t0 - t1)", a.num_steps);
     SBGM_CHECK(a.out != nullptr, "sampler: out is required");
     const int B = a.B, H = a.H, W = a.W, N = a.num_steps;
     const bool guided = a.cfg_enabled != 0;
     const int BE = guided ? 2 * B : B;                     // samples per network evaluation
     const size_t per = (size_t)H * W, n = (size_t)B * per;
-    SBGM_CHECK(ws_need(BE, H, W, a.bn_train) <= ws_bytes, "sampler: workspace not prepared for B=%d H=%d W=%d", BE, H, W);
+    SBGM_CHECK(ws_need(BE, H, W, a.bn_train, a.kind) <= ws_bytes, "sampler: workspace not prepared for B=%d H=%d W=%d", BE, H, W);
     // ---- per-step scalars on the host, in the reference's precision, written into the pinned staging buffer ---------------------
-    const size_t stage_need = sizeof(StepScalars) * (size_t)N + sizeof(SamplerState);
+    const size_t stage_need = (heun ? sizeof(EdmStep) : sizeof(StepScalars)) * (size_t)N + sizeof(SamplerState);
     if (stage_pending) {                                   // the previous call's upload still reads the buffer (normally long done)
         SBGM_HIP(hipEventSynchronize(ev_stage));
         stage_pending = false;
@@ -974,8 +1009,11 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
     }
     if (!ev_stage) SBGM_HIP(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming));
     StepScalars* tab = reinterpret_cast<StepScalars*>(h_stage);
+    EdmStep* etab = reinterpret_cast<EdmStep*>(h_stage);
     const float sig = cfg.sigma;
-    if (a.kind == SBGM_SAMPLER_EM) {                       // score_sampling.py:96-97, :102-103, :124-125
+    if (heun) {
+        edm_table(etab, N, (double)sig, (double)a.eps, *edm);
+    } else if (a.kind == SBGM_SAMPLER_EM) {                       // score_sampling.py:96-97, :102-103, :124-125
         const std::vector<float> ts = linspace_f32(1.0f, a.eps, N);
         const float dt = ts[0] - ts[1];
         for (int i = 0; i < N; ++i) {
@@ -994,24 +1032,34 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
             tab[i] = StepScalars{tf, g * g, dt, sqrtf((g * g) * dt), (float)ts[std::min(i + 1, N - 1)]};
         }
     }
-    const float t_first = tab[0].t;
-    if (table_cap < N) {
+    const float t_first = heun ? etab[0].t_hat : tab[0].t;
+    if (!heun && table_cap < N) {
         if (d_table) SBGM_HIP(hipFree(d_table));
         d_table = nullptr;
         const int cap = std::max(N, 4096);                   // roomy: a new table address invalidates the cached step graph
         SBGM_HIP(hipMalloc(&d_table, sizeof(StepScalars) * cap));
         table_cap = cap;
     }
-    SamplerState* state0 = reinterpret_cast<SamplerState*>(h_stage + sizeof(StepScalars) * (size_t)N);
+    if (heun && edm_table_cap < N) {
+        if (d_edm_table) SBGM_HIP(hipFree(d_edm_table));
+        d_edm_table = nullptr;
+        const int cap = std::max(N, 1024);
+        SBGM_HIP(hipMalloc(&d_edm_table, sizeof(EdmStep) * cap));
+        edm_table_cap = cap;
+    }
+    const size_t tab_bytes = (heun ? sizeof(EdmStep) : sizeof(StepScalars)) * (size_t)N;
+    SamplerState* state0 = reinterpret_cast<SamplerState*>(h_stage + tab_bytes);
     *state0 = SamplerState{0ull, 0ull, (unsigned long long)a.seed, (unsigned long long)N};
-    SBGM_HIP(hipMemcpyAsync(d_table, tab, sizeof(StepScalars) * N, hipMemcpyHostToDevice, st));
+    if (heun) SBGM_HIP(hipMemcpyAsync(d_edm_table, etab, tab_bytes, hipMemcpyHostToDevice, st));
+    else SBGM_HIP(hipMemcpyAsync(d_table, tab, sizeof(StepScalars) * N, hipMemcpyHostToDevice, st));
     SBGM_HIP(hipMemcpyAsync(d_state, state0, sizeof(SamplerState), hipMemcpyHostToDevice, st));
     SBGM_HIP(hipEventRecord(ev_stage, st));               // no host wait: the copies read pinned memory this handle owns
     stage_pending = true;
 
     // persistent sampler buffers live at the top of the workspace, the forward uses the rest
     // layout (BE = B, or 2B with guidance): x [BE*per] (rows B.. mirror rows 0..B-1), score [BE*per], x_mean [B*per]
-    const size_t keep = sampler_keep(BE, H, W);
+    // EDM Heun: x is the network input, x_mean holds the state x / x_hat, and a fourth slab after the others holds d
+    const size_t keep = sampler_keep(BE, H, W, a.kind);
     const size_t slab = align_up((size_t)BE * per * 4, 256);
     char* top = ws + ws_bytes - keep;
     float* xs = reinterpret_cast<float*>(top);
@@ -1019,6 +1067,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
     float* xmean = reinterpret_cast<float*>(top + 2 * slab);
     float* t_dev = reinterpret_cast<float*>(top + 3 * slab);
     double* sumsq = reinterpret_cast<double*>(top + 3 * slab + align_up((size_t)BE * 4, 256));
+    float* dheun = heun ? reinterpret_cast<float*>(top + sampler_keep(BE, H, W)) : nullptr;
     const size_t fwd_bytes = ws_bytes - keep;
     if (bn_dirty && fold_bn(st)) return 1;              // keep the fold out of the captured step
 
@@ -1068,7 +1117,12 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
                    a.domain_w);
         nm = NoiseMap{a.tile_origins, H, W / 4, (a.domain_w + 3) / 4};
     }
-    if (sbgm_launch_init_noise(xs, std1, next_z(), a.seed, d_state, 0, n, st, nm)) return 1;
+    if (heun) {                                            // x = sigma_0 z into the state slab, copied to the network input
+        if (sbgm_launch_init_noise(xmean, etab[0].sigma, next_z(), a.seed, d_state, 0, n, st, nm)) return 1;
+        SBGM_HIP(hipMemcpyAsync(xs, xmean, n * 4, hipMemcpyDeviceToDevice, st));
+    } else if (sbgm_launch_init_noise(xs, std1, next_z(), a.seed, d_state, 0, n, st, nm)) {
+        return 1;
+    }
     if (sbgm_launch_fill_t(t_dev, t_first, BE, st)) return 1;
     const float snr_nn = (float)((double)a.snr * std::sqrt((double)per));     // snr * sqrt(prod(x.shape[1:])) (:202-203)
 
@@ -1078,7 +1132,19 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
         if (forward(xs, t_dev, y_e, cond_e, lsm_e, topo_e, score, nullptr, BE, H, W, a.bn_train, st)) return 1;
         return guided ? sbgm_launch_cfg_combine(score, score, score + n, w, n, st) : 0;
     };
+    const bool churn = heun && edm->s_churn > 0.f;
+    // one Heun step: (churn) -> eval -> euler -> eval -> heun + advance; the last step (sigma_N = 0) is Euler only, into `out`
+    auto heun_step = [&](bool with_noise_ptrs, bool last) -> int {
+        if (churn && sbgm_launch_edm_churn(xmean, xs, with_noise_ptrs ? next_z() : nullptr, d_edm_table, d_state, nullptr, 0, a.seed,
+                                           n, st, nm)) return 1;
+        if (evaluate(a.cfg_scale)) return 1;
+        if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, d_edm_table, d_state, nullptr, t_dev, BE, n, st)) return 1;
+        if (last) return 0;
+        if (evaluate(a.cfg_scale)) return 1;
+        return sbgm_launch_edm_heun(xmean, xs, dheun, score, d_edm_table, d_state, nullptr, t_dev, BE, N, n, st);
+    };
     auto one_step = [&](bool with_noise_ptrs) -> int {
+        if (heun) return heun_step(with_noise_ptrs, false);
         if (a.kind == SBGM_SAMPLER_PC) {
             if (evaluate(a.cfg_scale_corrector)) return 1;
             if (sbgm_launch_langevin(xs, score, with_noise_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, nm)) return 1;
@@ -1093,9 +1159,11 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
     int rc = 0;
     if (graphed) {
         StepGraphKey key{};                                  // (value-initialised: the padding bytes compare equal)
-        key.B = B; key.H = H; key.W = W; key.kind = a.kind; key.guided = guided; key.bn_train = a.bn_train; key.table = d_table;
+        key.B = B; key.H = H; key.W = W; key.kind = a.kind; key.guided = guided; key.bn_train = a.bn_train;
+        key.table = heun ? (const void*)d_edm_table : (const void*)d_table; key.churn = churn;
         key.domain_w = a.domain_w; key.y = y_e; key.cond = cond_e; key.lsm = lsm_e; key.topo = topo_e; key.origins = a.tile_origins;
-        key.ws = ws; key.ws_bytes = saved_ws; key.cfg = a.cfg_scale; key.cfg_corr = a.cfg_scale_corrector; key.snr_nn = snr_nn;
+        key.ws = ws; key.ws_bytes = saved_ws; key.cfg = a.cfg_scale; key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector;
+        key.snr_nn = heun ? 0.f : snr_nn;
         key.plan_gen = plan_gen;
         const bool reuse = step_exec != nullptr && !guided && std::memcmp(&key, &step_key, sizeof key) == 0;
         if (!reuse) {
@@ -1119,18 +1187,22 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller) {
                 rc = 2;
             }
         }
-        for (int i = 0; i < N && rc == 0; ++i)
+        const int replays = heun ? N - 1 : N;                // EDM: the final Euler-only step is enqueued eagerly below
+        for (int i = 0; i < replays && rc == 0; ++i)
             if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
+        if (heun && rc == 0) rc = heun_step(false, true);
         if (guided) {                                        // its condition copies are freed when this call returns
             (void)hipStreamSynchronize(st);
             drop_step_graph();
         }
+    } else if (heun) {
+        for (int i = 0; i < N && rc == 0; ++i) rc = heun_step(z != nullptr, i == N - 1);
     } else {
         for (int i = 0; i < N && rc == 0; ++i) rc = one_step(z != nullptr);
     }
     ws_bytes = saved_ws;
     if (rc) return rc;
-    SBGM_HIP(hipMemcpyAsync(a.out, xmean, n * 4, hipMemcpyDeviceToDevice, st));
+    if (!heun) SBGM_HIP(hipMemcpyAsync(a.out, xmean, n * 4, hipMemcpyDeviceToDevice, st));
     if (graphed && !replay_on_caller) {
         SBGM_HIP(hipEventRecord(ev_out, st));
         SBGM_HIP(hipStreamWaitEvent(caller, ev_out, 0));
@@ -1229,6 +1301,19 @@ int sbgm_sampler_run(sbgm_model* m, const sbgm_sampler_args* a, void* stream) {
     return m->sampler(*a, (hipStream_t)stream);
 }
 
+int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
+                         float s_tmin, float s_tmax, float s_noise, void* stream) {
+    SBGM_CHECK(a, "sampler_run_edm: null args");
+    SBGM_CHECK(a->kind == SBGM_SAMPLER_EDM_HEUN, "sampler_run_edm: kind %d is not SBGM_SAMPLER_EDM_HEUN", a->kind);
+    SBGM_CHECK(!a->bn_train, "sampler_run_edm: serves eval-mode BatchNorm only (bn_train must be 0)");
+    SBGM_CHECK(rho > 0.f && s_churn >= 0.f && s_noise >= 0.f, "sampler_run_edm: need rho > 0, s_churn >= 0, s_noise >= 0");
+    SBGM_CHECK(!(sigma_min > 0.f && sigma_max > 0.f && sigma_min >= sigma_max), "sampler_run_edm: sigma_min %g >= sigma_max %g",
+               sigma_min, sigma_max);
+    if (m->prepare_ws(a->cfg_enabled ? 2 * a->B : a->B, a->H, a->W, 0, 1, (hipStream_t)stream, SBGM_SAMPLER_EDM_HEUN)) return 1;
+    const sbgm_model::EdmArgs e{sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise};
+    return m->sampler(*a, (hipStream_t)stream, &e);
+}
+
 // One evaluation of the (B, H, W) plan on zero inputs placed at the top of the workspace.  tune = true: every convolution times its tile
 // candidates; tune = false: a plain evaluation whose only purpose is the bump allocator's high-water mark (ws_peak).
 int sbgm_model::dummy_forward(int B, int H, int W, bool tune, hipStream_t st) {
@@ -1255,13 +1340,13 @@ int sbgm_model::dummy_forward(int B, int H, int W, bool tune, hipStream_t st) {
 // BEFORE the caller's work, so the slab has its final size (and address) from the first real call on: a sampler's captured step graph
 // is then captured once, not again after a later call has trimmed the slab.  Train-mode BatchNorm shapes are not pre-measured (an
 // evaluation would move the running statistics): they run on the generous bound first and are trimmed by a later call.
-int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, size_t factor, hipStream_t st) {
+int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, size_t factor, hipStream_t st, int kind) {
     if (!bn_train && ws_peak.find(std::array<int, 4>{B, H, W, 0}) == ws_peak.end() && sbgm_model_check_complete(this) == 0) {
-        if (ensure_ws(ws_need(B, H, W) + ((size_t)B * H * W * 16 + 1024) * 4 + 4096)) return 1;
+        if (ensure_ws(ws_need(B, H, W, 0, kind) + ((size_t)B * H * W * 16 + 1024) * 4 + 4096)) return 1;
         if (bn_dirty && fold_bn(st)) return 1;
         if (dummy_forward(B, H, W, false, st)) return 1;
     }
-    return ensure_ws(factor * ws_need(B, H, W, bn_train));
+    return ensure_ws(factor * ws_need(B, H, W, bn_train, kind));
 }
 
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {

@@ -229,6 +229,28 @@ int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr
                          size_t per_sample, hipStream_t st, NoiseMap nm = NoiseMap{});
 int sbgm_launch_cfg_combine(float* out, const float* s_cond, const float* s_uncond, float scale, size_t n, hipStream_t st);
 
+// EDM Heun sampler (Karras et al. 2022, Alg. 2) on the probability-flow ODE of the VE SDE: one row per step i of the
+// Karras sigma ladder, built in float64 on the host and stored as fp32 (score_sampling.edm_heun_schedule is the same table)
+struct EdmStep {
+    float sigma;           // sigma_i
+    float sigma_hat;       // sigma_i (1 + gamma_i): the noise level the step starts from after churn
+    float sigma_next;      // sigma_{i+1} (0 after the last step)
+    float t_hat;           // t(sigma_hat), the time of the step's first evaluation
+    float t_next;          // t(sigma_{i+1}), the time of its second evaluation (unused on the last step)
+    float churn_coef;      // s_noise * sqrt(sigma_hat^2 - sigma_i^2)
+};
+// churn: x += churn_coef * z (z null: Philox draw at the run's RNG offset / draw_index); x_copy (may be null) receives x too
+int sbgm_launch_edm_churn(float* x, float* x_copy, const float* z, const EdmStep* table, const SamplerState* state,
+                          const EdmStep* sc_val, unsigned long long draw_index, unsigned long long seed, size_t n, hipStream_t st,
+                          NoiseMap nm = NoiseMap{});
+// euler: d = -sigma_hat * score ; x_next = x_hat + (sigma_next - sigma_hat) * d ; t_dev[0 .. t_entries) = t_next
+int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, const EdmStep* table,
+                          const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st);
+// heun: x = x_hat + (sigma_next - sigma_hat) * 0.5 (d - sigma_next * score), in place over x_hat (x_copy may be null);
+// with a state: t_dev = t_hat of the next step, then the step counter / RNG offset advance
+int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* score, const EdmStep* table, SamplerState* state,
+                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st);
+
 // ---- dsm_loss.hip (the loss around the network) -----------------------------------------------------------------------
 int sbgm_dsm_nblk(int64_t per_sample);
 int sbgm_launch_dsm_perturb(const float* x, const float* z_in, const float* t_in, const unsigned long long* rng,

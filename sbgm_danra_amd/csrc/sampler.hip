@@ -1,6 +1,6 @@
 // K25 / K26 / K27: per-step state updates of the reverse-SDE samplers, fused with the Gaussian draw.
 // reference sbgm/score_sampling.py:124-125 (Euler-Maruyama), :200-204 (Langevin corrector), :224-227 (predictor),
-// :55 (classifier-free-guidance combine).
+// :55 (classifier-free-guidance combine).  Beyond the reference: the EDM Heun updates of edm_heun_sampler (churn / euler / heun).
 //
 // Noise: when `z` is null the kernels draw N(0,1) themselves (Philox4x32-10 counter RNG + Box-Muller, keyed by
 // (seed, running offset, element index)), so the sampler loop never round-trips noise through HBM; when `z`
@@ -136,6 +136,67 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(float* __restrict__ ou
     }
 }
 
+// EDM Heun step, split around its two network evaluations (the step table row is picked by the device step counter when
+// a state is given, so one captured graph serves every step; by value otherwise).
+// churn: x_hat = x + churn_coef * z, written to x and to the network-input slab
+__global__ __launch_bounds__(256) void edm_churn_kernel(float* __restrict__ x, float* __restrict__ x_copy,
+                                                        const float* __restrict__ z, const EdmStep* __restrict__ table,
+                                                        const SamplerState* __restrict__ state, EdmStep sc_val,
+                                                        unsigned long long off_val, unsigned long long seed, size_t n4,
+                                                        NoiseMap nm) {
+    const float c = (state ? table[state->step] : sc_val).churn_coef;
+    const unsigned long long off = state ? state->rng_offset : off_val;
+    if (state) seed = state->seed;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
+        const f32x4 v = reinterpret_cast<const f32x4*>(x)[i] + c * n;
+        reinterpret_cast<f32x4*>(x)[i] = v;
+        if (x_copy) reinterpret_cast<f32x4*>(x_copy)[i] = v;
+    }
+}
+
+// Euler predictor: d = dx/dsigma = -sigma_hat * score ; x' = x_hat + (sigma_next - sigma_hat) * d.  The time vector of the
+// second evaluation (t_next) is published by the same launch: nothing reads it until the next kernel.
+__global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict__ x_hat, const float* __restrict__ score,
+                                                        float* __restrict__ d, float* __restrict__ x_next,
+                                                        const EdmStep* __restrict__ table, const SamplerState* __restrict__ state,
+                                                        EdmStep sc_val, float* __restrict__ t_dev, int t_entries, size_t n4) {
+    const EdmStep sc = state ? table[state->step] : sc_val;
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    if (t_dev)
+        for (size_t j = gid; j < (size_t)t_entries; j += stride) t_dev[j] = sc.t_next;
+    const float h = sc.sigma_next - sc.sigma_hat;
+    for (size_t i = gid; i < n4; i += stride) {
+        const f32x4 dv = (-sc.sigma_hat) * reinterpret_cast<const f32x4*>(score)[i];
+        reinterpret_cast<f32x4*>(d)[i] = dv;
+        reinterpret_cast<f32x4*>(x_next)[i] = reinterpret_cast<const f32x4*>(x_hat)[i] + h * dv;
+    }
+}
+
+// Heun corrector: x = x_hat + (sigma_next - sigma_hat) * 0.5 (d + d'), d' = -sigma_next * score(x', sigma_next); in place over
+// x_hat, mirrored into the network-input slab.  Publishes the first evaluation time of the next step (the advance follows).
+__global__ __launch_bounds__(256) void edm_heun_kernel(float* __restrict__ x, float* __restrict__ x_copy,
+                                                       const float* __restrict__ d, const float* __restrict__ score,
+                                                       const EdmStep* __restrict__ table, const SamplerState* __restrict__ state,
+                                                       EdmStep sc_val, float* __restrict__ t_dev, int t_entries, int n_steps,
+                                                       size_t n4) {
+    const unsigned long long s = state ? state->step : 0ull;
+    const EdmStep sc = state ? table[s] : sc_val;
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    if (state && t_dev) {
+        const unsigned long long ns = state->n_steps ? state->n_steps : (unsigned long long)n_steps;
+        const float tn = table[s + 1 < ns ? s + 1 : s].t_hat;
+        for (size_t j = gid; j < (size_t)t_entries; j += stride) t_dev[j] = tn;
+    }
+    const float h = sc.sigma_next - sc.sigma_hat;
+    for (size_t i = gid; i < n4; i += stride) {
+        const f32x4 d2 = (-sc.sigma_next) * reinterpret_cast<const f32x4*>(score)[i];
+        const f32x4 v = reinterpret_cast<const f32x4*>(x)[i] + (h * 0.5f) * (reinterpret_cast<const f32x4*>(d)[i] + d2);
+        reinterpret_cast<f32x4*>(x)[i] = v;
+        if (x_copy) reinterpret_cast<f32x4*>(x_copy)[i] = v;
+    }
+}
+
 inline int stream_blocks(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 2048); }
 
 }  // namespace
@@ -193,6 +254,44 @@ int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr
     SBGM_LAUNCH_CHECK();
     if (state) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0);
+        SBGM_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int sbgm_launch_edm_churn(float* x, float* x_copy, const float* z, const EdmStep* table, const SamplerState* state,
+                          const EdmStep* sc_val, unsigned long long draw_index, unsigned long long seed, size_t n, hipStream_t st,
+                          NoiseMap nm) {
+    SBGM_CHECK(n % 4 == 0, "edm_churn: element count must be a multiple of 4");
+    SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_churn: need a device table or explicit scalars");
+    const EdmStep v = sc_val ? *sc_val : EdmStep{};
+    hipLaunchKernelGGL(edm_churn_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x, x_copy, z, table, state, v, draw_index,
+                       seed, n / 4, nm);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, const EdmStep* table,
+                          const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st) {
+    SBGM_CHECK(n % 4 == 0, "edm_euler: element count must be a multiple of 4");
+    SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_euler: need a device table or explicit scalars");
+    const EdmStep v = sc_val ? *sc_val : EdmStep{};
+    hipLaunchKernelGGL(edm_euler_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x_hat, score, d, x_next, table, state, v,
+                       t_dev, t_dev ? t_entries : 0, n / 4);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* score, const EdmStep* table, SamplerState* state,
+                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st) {
+    SBGM_CHECK(n % 4 == 0, "edm_heun: element count must be a multiple of 4");
+    SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_heun: need a device table or explicit scalars");
+    const EdmStep v = sc_val ? *sc_val : EdmStep{};
+    hipLaunchKernelGGL(edm_heun_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x, x_copy, d, score, table, state, v, t_dev,
+                       t_dev ? t_entries : 0, n_steps, n / 4);
+    SBGM_LAUNCH_CHECK();
+    if (state) {                     // step counter and RNG offset: the EM mechanism, without its StepScalars time publish
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 1, n_steps);
         SBGM_LAUNCH_CHECK();
     }
     return 0;

@@ -21,12 +21,13 @@ import torch.nn as nn
 
 from . import parallel
 from .ema import EMA_COUNT_KEY, EMA_KEY, ModelEMA, pick_network_params
-from .score_sampling import Euler_Maruyama_sampler, ode_sampler, pc_sampler
+from .score_sampling import Euler_Maruyama_sampler, edm_heun_sampler, edm_sampler_kwargs, ode_sampler, pc_sampler
 from .utils import (draw_condition_dropout, extract_samples, extract_samples_device, get_model_string,
                     report_precip_extremes)
 
 logger = logging.getLogger(__name__)
-_SAMPLERS = {"pc_sampler": pc_sampler, "Euler_Maruyama_sampler": Euler_Maruyama_sampler, "ode_sampler": ode_sampler}
+_SAMPLERS = {"pc_sampler": pc_sampler, "Euler_Maruyama_sampler": Euler_Maruyama_sampler, "ode_sampler": ode_sampler,
+             "edm_heun_sampler": edm_heun_sampler}
 
 
 class TrainingPipeline_general:
@@ -346,6 +347,8 @@ class TrainingPipeline_general:
                   img_size=cfg["highres"]["data_size"][0])
         if sampler is not ode_sampler:
             kw.update(y=seasons, cond_img=cond, lsm_cond=lsm, topo_cond=topo)
+        if sampler is edm_heun_sampler:                      # n_timesteps is the Heun step count N (2N-1 evaluations)
+            kw.update(edm_sampler_kwargs(cfg))
         gen = sampler(**kw)
         gen, self.last_generation_check = self.monitor_generated(gen, cfg)
         return gen
