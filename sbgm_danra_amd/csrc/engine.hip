@@ -91,10 +91,8 @@ struct sbgm_model {
     size_t ws_bytes = 0, ws_used = 0;
     // sampler state
     SamplerState* d_state = nullptr;
-    StepScalars* d_table = nullptr;
-    int table_cap = 0;
-    EdmStep* d_edm_table = nullptr;          // step table of the EDM Heun sampler (its own rows; same counter / RNG state)
-    int edm_table_cap = 0;
+    void* d_table = nullptr;                // step table of the current run: StepScalars rows (EM, PC) or EdmStep rows (EDM Heun)
+    size_t table_bytes = 0;                 // its capacity
     // pinned host staging of a run's step table + initial state: the upload is a true asynchronous copy, so sbgm_sampler_run does not
     // have to wait for it (or for anything enqueued before it); ev_stage guards the buffer against the next call's rewrite
     char* h_stage = nullptr;
@@ -108,7 +106,7 @@ struct sbgm_model {
     std::vector<ConvRec>* prof = nullptr;   // when set, conv() brackets every launch with events
     static constexpr int PROF_REPS = 4;
     hipStream_t graph_stream = nullptr;     // private capture stream (the caller's may be the legacy default stream)
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    hipEvent_t ev_replayed = nullptr;       // recorded on the caller's stream after a run's last replay of step_exec
     // The captured SDE step is kept across sampler calls: capture + instantiation of its ~75 kernel nodes cost ~3 ms, as much as
     // two steps.  Everything a step bakes in is in the key (shapes, sampler kind, caller tensors, scalar arguments, workspace,
     // tile-table generation); what changes between runs lives in device memory (step table, step counter, RNG offset AND seed).
@@ -124,7 +122,7 @@ struct sbgm_model {
     hipGraphExec_t step_exec = nullptr;
     unsigned long long plan_gen = 0;         // bumped whenever the tile table changes (the captured launches embed tile choices)
     void drop_step_graph() {
-        if (step_exec && graph_stream) (void)hipStreamSynchronize(graph_stream);      // a replay of it may still be executing
+        if (step_exec && ev_replayed) (void)hipEventSynchronize(ev_replayed);        // a replay of it may still be executing
         if (step_exec) (void)hipGraphExecDestroy(step_exec);
         if (step_graph) (void)hipGraphDestroy(step_graph);
         step_exec = nullptr;
@@ -137,12 +135,10 @@ struct sbgm_model {
         if (ws) (void)hipFree(ws);
         if (d_state) (void)hipFree(d_state);
         if (d_table) (void)hipFree(d_table);
-        if (d_edm_table) (void)hipFree(d_edm_table);
         if (h_stage) (void)hipHostFree(h_stage);
         if (ev_stage) (void)hipEventDestroy(ev_stage);
         if (graph_stream) (void)hipStreamDestroy(graph_stream);
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_out) (void)hipEventDestroy(ev_out);
+        if (ev_replayed) (void)hipEventDestroy(ev_replayed);
     }
 
     Param* add(const std::string& name, ParamKind kind, int64_t numel) {
@@ -184,7 +180,7 @@ struct sbgm_model {
     int build(const sbgm_model_config& c);
     int ensure_ws(size_t bytes);
     int dummy_forward(int B, int H, int W, bool tune, hipStream_t st);
-    int prepare_ws(int B, int H, int W, int bn_train, size_t factor, hipStream_t st, int kind = SBGM_SAMPLER_EM);
+    int prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, int slabs);
     float* wsalloc(size_t floats) {     // bump allocator over the activation workspace; nullptr (+ error text) when full
         const size_t bytes = align_up(floats * 4, 256);
         if (ws_used + bytes > ws_bytes) {
@@ -204,13 +200,15 @@ struct sbgm_model {
     std::map<std::array<int, 4>, size_t> ws_peak;
     size_t ws_target = 0;                   // largest measured total need (forward + sampler slabs) of any shape seen so far
     size_t fwd_need(int B, int H, int W, int bn_train = 0) const;
-    // persistent sampler slabs: x, score, x_mean (+ the Heun derivative d for SBGM_SAMPLER_EDM_HEUN), time vector, norm partials
-    size_t sampler_keep(int B, int H, int W, int kind = SBGM_SAMPLER_EM) const {
+    // persistent sampler slabs: x, score, x_mean (+ the Heun derivative d for SBGM_SAMPLER_EDM_HEUN), then time vector, norm partials.
+    // Evaluations and autotuning reserve the three slabs of EM / PC, so that such a sampler finds its workspace settled.
+    static int sampler_slabs(int kind) { return kind == SBGM_SAMPLER_EDM_HEUN ? 4 : 3; }
+    size_t sampler_keep(int B, int H, int W, int slabs) const {
         const size_t n = (size_t)B * H * W;
-        return align_up(n * 4, 256) * (kind == SBGM_SAMPLER_EDM_HEUN ? 4 : 3) + align_up((size_t)B * 4, 256) + align_up((size_t)B * 8, 256);
+        return align_up(n * 4, 256) * slabs + align_up((size_t)B * 4, 256) + align_up((size_t)B * 8, 256);
     }
-    size_t ws_need(int B, int H, int W, int bn_train = 0, int kind = SBGM_SAMPLER_EM) const {
-        return fwd_need(B, H, W, bn_train) + sampler_keep(B, H, W, kind);
+    size_t ws_need(int B, int H, int W, int bn_train = 0, int slabs = 3) const {
+        return fwd_need(B, H, W, bn_train) + sampler_keep(B, H, W, slabs);
     }
     int fold_bn(hipStream_t st);
     ConvTile pick_tile(const ConvGeom& g, const ConvParams& p);
@@ -225,7 +223,7 @@ struct sbgm_model {
         if (!rc && !tuning) {                                // the evaluation's high-water mark sizes every later call of this shape
             size_t& pk = ws_peak[std::array<int, 4>{B, H, W, bn_train != 0}];
             pk = std::max(pk, ws_used);
-            ws_target = std::max(ws_target, pk + ((size_t)8 << 20) + sampler_keep(B, H, W));
+            ws_target = std::max(ws_target, pk + ((size_t)8 << 20) + sampler_keep(B, H, W, 3));
         }
         return rc;
     }
@@ -938,10 +936,43 @@ static std::vector<float> linspace_f32(float start, float end, int n) {
     return v;
 }
 
+// Step tables, in the reference's precision.  Each builder writes the N rows of its kind into the staging buffer and returns the row
+// size and the time of the run's first evaluation.
+struct StepTable { size_t row_bytes; float t_first; };
+
+// Euler-Maruyama: torch.linspace times in fp32 (score_sampling.py:96-97, :102-103, :124-125)
+static StepTable em_table(void* stage, int N, float sig, float eps) {
+    StepScalars* tab = static_cast<StepScalars*>(stage);
+    const std::vector<float> ts = linspace_f32(1.0f, eps, N);
+    const float dt = ts[0] - ts[1];
+    for (int i = 0; i < N; ++i) {
+        const float g = powf(sig, ts[i]);
+        tab[i] = StepScalars{ts[i], g * g, dt, sqrtf(dt) * g, ts[std::min(i + 1, N - 1)]};
+    }
+    return {sizeof(StepScalars), tab[0].t};
+}
+
+// predictor-corrector: np.linspace times in float64, stored as fp32 (score_sampling.py:169-170, :176, :207, :224-227)
+static StepTable pc_table(void* stage, int N, float sig, float eps) {
+    StepScalars* tab = static_cast<StepScalars*>(stage);
+    std::vector<double> ts(N);
+    const double step = ((double)eps - 1.0) / (double)(N - 1);
+    for (int i = 0; i < N; ++i) ts[i] = 1.0 + (double)i * step;
+    ts[N - 1] = (double)eps;
+    const float dt = (float)(ts[0] - ts[1]);
+    for (int i = 0; i < N; ++i) {
+        const float tf = (float)ts[i];
+        const float g = powf(sig, tf);
+        tab[i] = StepScalars{tf, g * g, dt, sqrtf((g * g) * dt), (float)ts[std::min(i + 1, N - 1)]};
+    }
+    return {sizeof(StepScalars), tab[0].t};
+}
+
 // EDM Heun step table (Karras et al. 2022, Alg. 2) for the VE SDE std(t) = sqrt((sigma^2t - 1) / (2 ln sigma)): the Karras ladder between
 // sigma_min and sigma_max (<= 0: the trained range [std(eps), std(1)]; other values are clipped to it), churn gamma_i, t(sigma) =
 // log1p(2 ln sigma * s^2) / (2 ln sigma) clamped to [eps, 1].  float64 throughout, stored as fp32: score_sampling.edm_heun_schedule.
-static void edm_table(EdmStep* tab, int N, double sig, double eps, const sbgm_model::EdmArgs& e) {
+static StepTable edm_table(void* stage, int N, double sig, double eps, const sbgm_model::EdmArgs& e) {
+    EdmStep* tab = static_cast<EdmStep*>(stage);
     const double ls = std::log(sig);
     auto std_of = [&](double t) { return std::sqrt(std::expm1(2.0 * t * ls) / (2.0 * ls)); };
     const double lo = std_of(eps), hi = std_of(1.0);
@@ -962,29 +993,48 @@ static void edm_table(EdmStep* tab, int N, double sig, double eps, const sbgm_mo
         tab[i] = EdmStep{(float)sg[i], (float)sh, (float)sg[i + 1], (float)t_of(sh), (float)t_of(sg[i + 1]),
                          (float)((double)e.s_noise * std::sqrt(std::max(0.0, sh * sh - sg[i] * sg[i])))};
     }
+    return {sizeof(EdmStep), tab[0].t_hat};
 }
 
-int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm) {
-    // Graph CAPTURE is illegal on the legacy default stream, so the step is captured on a private stream (capture records, it runs
-    // nothing); the REPLAYS, the uploads and the final copy go to the caller's stream, so the run is ordinary stream-ordered work of the
-    // caller.  (Round 2 also replayed on the private stream, fenced with events on both sides: measured 1.639 vs 1.589 ms per C2 step —
-    // the same kernels dispatch 0.7 us apart closer on the caller's stream; SBGM_GRAPH_PRIVATE_STREAM=1 restores that form for A/B runs.)
-    hipStream_t st = caller;
-    const bool graphed = a.use_graph && !a.noise;
-    static const bool private_replay = getenv("SBGM_GRAPH_PRIVATE_STREAM") != nullptr;
-    const bool replay_on_caller = graphed && !private_replay;
-    if (graphed) {
-        if (!graph_stream) {
-            SBGM_HIP(hipStreamCreateWithFlags(&graph_stream, hipStreamNonBlocking));
-            SBGM_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-            SBGM_HIP(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
-        }
-        if (!replay_on_caller) {
-            SBGM_HIP(hipEventRecord(ev_in, caller));
-            SBGM_HIP(hipStreamWaitEvent(graph_stream, ev_in, 0));
-            st = graph_stream;
-        }
+// Condition tensors of a run's network evaluations: the caller's, or with guidance (guided_score_fn :27-43) per-call copies of 2B rows
+// whose second half is the unconditional input (null class 0, zero cond_img, geo fields with their mask channel zeroed).  The copies
+// are freed on every exit path, after the stream has drained.
+struct SamplerConds {
+    const int64_t* y;
+    const float *cond, *lsm, *topo;
+    hipStream_t st;
+    std::vector<void*> bufs;
+    SamplerConds(const sbgm_sampler_args& a, hipStream_t s) : y(a.y), cond(a.cond_img), lsm(a.lsm_cond), topo(a.topo_cond), st(s) {}
+    SamplerConds(const SamplerConds&) = delete;
+    ~SamplerConds() {
+        if (bufs.empty()) return;
+        (void)hipStreamSynchronize(st);
+        for (void* p : bufs) (void)hipFree(p);
     }
+    int add_unconditional(const sbgm_sampler_args& a, const sbgm_model_config& c) {
+        const size_t per = (size_t)a.H * a.W, n = (size_t)a.B * per;
+        // p -> [p; unconditional half]: zeros, or for a geo field with geo_ch channels a copy, with channel 1 (the mask) zeroed if 2
+        auto dup = [&](auto& p, size_t bytes_half, int geo_ch) -> bool {
+            void* d = nullptr;
+            if (p == nullptr) return true;
+            if (hipMalloc(&d, 2 * bytes_half) != hipSuccess) return false;
+            bufs.push_back(d);
+            (void)hipMemcpyAsync(d, p, bytes_half, hipMemcpyDeviceToDevice, st);
+            char* lo = static_cast<char*>(d) + bytes_half;
+            if (geo_ch == 0) (void)hipMemsetAsync(lo, 0, bytes_half, st);
+            else (void)hipMemcpyAsync(lo, p, bytes_half, hipMemcpyDeviceToDevice, st);
+            if (geo_ch == 2) (void)hipMemset2DAsync(lo + per * 4, 2 * per * 4, 0, per * 4, a.B, st);   // NCHW [B][2][H][W]
+            p = static_cast<std::remove_reference_t<decltype(p)>>(d);
+            return true;
+        };
+        SBGM_CHECK(dup(y, (size_t)a.B * 8, 0) && dup(cond, n * 4 * c.n_cond_channels, 0) &&
+                   dup(lsm, n * 4 * c.n_lsm_channels, c.n_lsm_channels) && dup(topo, n * 4 * c.n_topo_channels, c.n_topo_channels) &&
+                   hipGetLastError() == hipSuccess, "sampler: could not allocate the unconditional condition tensors");
+        return 0;
+    }
+};
+
+int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm) {
     const bool heun = edm != nullptr;                      // only sbgm_sampler_run_edm passes EDM arguments
     SBGM_CHECK(heun ? a.kind == SBGM_SAMPLER_EDM_HEUN : (a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC),
                "sampler: unknown kind %d", a.kind);
@@ -992,11 +1042,24 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     SBGM_CHECK(a.out != nullptr, "sampler: out is required");
     const int B = a.B, H = a.H, W = a.W, N = a.num_steps;
     const bool guided = a.cfg_enabled != 0;
+    SBGM_CHECK(!(guided && a.bn_train), "sampler: guidance with train-mode BatchNorm would couple the two halves of the batch");
     const int BE = guided ? 2 * B : B;                     // samples per network evaluation
     const size_t per = (size_t)H * W, n = (size_t)B * per;
-    SBGM_CHECK(ws_need(BE, H, W, a.bn_train, a.kind) <= ws_bytes, "sampler: workspace not prepared for B=%d H=%d W=%d", BE, H, W);
-    // ---- per-step scalars on the host, in the reference's precision, written into the pinned staging buffer ---------------------
-    const size_t stage_need = (heun ? sizeof(EdmStep) : sizeof(StepScalars)) * (size_t)N + sizeof(SamplerState);
+    const int slabs = sampler_slabs(a.kind);
+    if (prepare_ws(BE, H, W, a.bn_train, caller, slabs)) return 1;
+    // Graph CAPTURE is illegal on the legacy default stream, so the step is captured on a private stream (capture records, it runs
+    // nothing); the replays, the uploads and the final copy go to the caller's stream, so the run is ordinary stream-ordered work of
+    // the caller.
+    const bool graphed = a.use_graph && !a.noise;
+    if (graphed && !graph_stream) {
+        SBGM_HIP(hipStreamCreateWithFlags(&graph_stream, hipStreamNonBlocking));
+        SBGM_HIP(hipEventCreateWithFlags(&ev_replayed, hipEventDisableTiming));
+    }
+    hipStream_t st = caller;
+
+    // ---- step table and initial state, written into the pinned staging buffer and uploaded from there --------------------------
+    static_assert(sizeof(EdmStep) >= sizeof(StepScalars), "the staging buffer is sized for the larger row");
+    const size_t stage_need = sizeof(EdmStep) * (size_t)N + sizeof(SamplerState);
     if (stage_pending) {                                   // the previous call's upload still reads the buffer (normally long done)
         SBGM_HIP(hipEventSynchronize(ev_stage));
         stage_pending = false;
@@ -1004,62 +1067,34 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     if (h_stage_bytes < stage_need) {
         if (h_stage) SBGM_HIP(hipHostFree(h_stage));
         h_stage = nullptr;
-        h_stage_bytes = std::max(stage_need, sizeof(StepScalars) * (size_t)4096 + sizeof(SamplerState));
+        h_stage_bytes = std::max(stage_need, sizeof(EdmStep) * (size_t)4096 + sizeof(SamplerState));
         SBGM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_stage), h_stage_bytes, hipHostMallocDefault));
     }
     if (!ev_stage) SBGM_HIP(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming));
-    StepScalars* tab = reinterpret_cast<StepScalars*>(h_stage);
-    EdmStep* etab = reinterpret_cast<EdmStep*>(h_stage);
     const float sig = cfg.sigma;
-    if (heun) {
-        edm_table(etab, N, (double)sig, (double)a.eps, *edm);
-    } else if (a.kind == SBGM_SAMPLER_EM) {                       // score_sampling.py:96-97, :102-103, :124-125
-        const std::vector<float> ts = linspace_f32(1.0f, a.eps, N);
-        const float dt = ts[0] - ts[1];
-        for (int i = 0; i < N; ++i) {
-            const float g = powf(sig, ts[i]);
-            tab[i] = StepScalars{ts[i], g * g, dt, sqrtf(dt) * g, ts[std::min(i + 1, N - 1)]};
-        }
-    } else {                                               // score_sampling.py:169-170, :176, :207, :224-227
-        std::vector<double> ts(N);
-        const double step = ((double)a.eps - 1.0) / (double)(N - 1);
-        for (int i = 0; i < N; ++i) ts[i] = 1.0 + (double)i * step;
-        ts[N - 1] = (double)a.eps;
-        const float dt = (float)(ts[0] - ts[1]);
-        for (int i = 0; i < N; ++i) {
-            const float tf = (float)ts[i];
-            const float g = powf(sig, tf);
-            tab[i] = StepScalars{tf, g * g, dt, sqrtf((g * g) * dt), (float)ts[std::min(i + 1, N - 1)]};
-        }
-    }
-    const float t_first = heun ? etab[0].t_hat : tab[0].t;
-    if (!heun && table_cap < N) {
+    const StepTable tab = heun ? edm_table(h_stage, N, (double)sig, (double)a.eps, *edm)
+                        : a.kind == SBGM_SAMPLER_EM ? em_table(h_stage, N, sig, a.eps) : pc_table(h_stage, N, sig, a.eps);
+    const size_t tab_bytes = tab.row_bytes * (size_t)N;
+    if (table_bytes < tab_bytes) {                         // roomy: a new table address invalidates the cached step graph
         if (d_table) SBGM_HIP(hipFree(d_table));
         d_table = nullptr;
-        const int cap = std::max(N, 4096);                   // roomy: a new table address invalidates the cached step graph
-        SBGM_HIP(hipMalloc(&d_table, sizeof(StepScalars) * cap));
-        table_cap = cap;
+        const size_t cap = std::max(tab_bytes, sizeof(StepScalars) * 4096);
+        SBGM_HIP(hipMalloc(&d_table, cap));
+        table_bytes = cap;
     }
-    if (heun && edm_table_cap < N) {
-        if (d_edm_table) SBGM_HIP(hipFree(d_edm_table));
-        d_edm_table = nullptr;
-        const int cap = std::max(N, 1024);
-        SBGM_HIP(hipMalloc(&d_edm_table, sizeof(EdmStep) * cap));
-        edm_table_cap = cap;
-    }
-    const size_t tab_bytes = (heun ? sizeof(EdmStep) : sizeof(StepScalars)) * (size_t)N;
     SamplerState* state0 = reinterpret_cast<SamplerState*>(h_stage + tab_bytes);
     *state0 = SamplerState{0ull, 0ull, (unsigned long long)a.seed, (unsigned long long)N};
-    if (heun) SBGM_HIP(hipMemcpyAsync(d_edm_table, etab, tab_bytes, hipMemcpyHostToDevice, st));
-    else SBGM_HIP(hipMemcpyAsync(d_table, tab, sizeof(StepScalars) * N, hipMemcpyHostToDevice, st));
+    SBGM_HIP(hipMemcpyAsync(d_table, h_stage, tab_bytes, hipMemcpyHostToDevice, st));
     SBGM_HIP(hipMemcpyAsync(d_state, state0, sizeof(SamplerState), hipMemcpyHostToDevice, st));
     SBGM_HIP(hipEventRecord(ev_stage, st));               // no host wait: the copies read pinned memory this handle owns
     stage_pending = true;
+    const StepScalars* sde_tab = static_cast<const StepScalars*>(d_table);
+    const EdmStep* edm_tab = static_cast<const EdmStep*>(d_table);
 
     // persistent sampler buffers live at the top of the workspace, the forward uses the rest
-    // layout (BE = B, or 2B with guidance): x [BE*per] (rows B.. mirror rows 0..B-1), score [BE*per], x_mean [B*per]
-    // EDM Heun: x is the network input, x_mean holds the state x / x_hat, and a fourth slab after the others holds d
-    const size_t keep = sampler_keep(BE, H, W, a.kind);
+    // layout (BE = B, or 2B with guidance): x [BE*per] (rows B.. mirror rows 0..B-1), score [BE*per], x_mean [B*per], time vector,
+    // norm partials, and for EDM Heun the derivative d after them.  EDM Heun: x is the network input, x_mean holds the state x / x_hat.
+    const size_t keep = sampler_keep(BE, H, W, slabs);
     const size_t slab = align_up((size_t)BE * per * 4, 256);
     char* top = ws + ws_bytes - keep;
     float* xs = reinterpret_cast<float*>(top);
@@ -1067,45 +1102,13 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     float* xmean = reinterpret_cast<float*>(top + 2 * slab);
     float* t_dev = reinterpret_cast<float*>(top + 3 * slab);
     double* sumsq = reinterpret_cast<double*>(top + 3 * slab + align_up((size_t)BE * 4, 256));
-    float* dheun = heun ? reinterpret_cast<float*>(top + sampler_keep(BE, H, W)) : nullptr;
+    float* dheun = heun ? reinterpret_cast<float*>(top + sampler_keep(BE, H, W, 3)) : nullptr;
     const size_t fwd_bytes = ws_bytes - keep;
     if (bn_dirty && fold_bn(st)) return 1;              // keep the fold out of the captured step
+    SamplerConds conds(a, st);                           // guidance: the unconditional half is built once per run
+    if (guided && conds.add_unconditional(a, cfg)) return 1;
 
-    // guidance: the unconditional half of the condition tensors is built once per run (guided_score_fn :27-43)
-    const int64_t* y_e = a.y;
-    const float *cond_e = a.cond_img, *lsm_e = a.lsm_cond, *topo_e = a.topo_cond;
-    struct Scratch {                                       // freed on every exit path, after the stream has drained
-        std::vector<void*> v;
-        hipStream_t st;
-        ~Scratch() {
-            if (v.empty()) return;
-            (void)hipStreamSynchronize(st);
-            for (void* p : v) (void)hipFree(p);
-        }
-    } guided_bufs{{}, st};
-    if (guided) {
-        SBGM_CHECK(!a.bn_train, "sampler: guidance with train-mode BatchNorm would couple the two halves of the batch");
-        auto dup = [&](const void* src, size_t bytes_half, int mode, int channels) -> void* {   // mode 0 zero, 1 copy, 2 strip mask
-            void* p = nullptr;
-            if (hipMalloc(&p, 2 * bytes_half) != hipSuccess) return nullptr;
-            guided_bufs.v.push_back(p);
-            (void)hipMemcpyAsync(p, src, bytes_half, hipMemcpyDeviceToDevice, st);
-            char* lo = static_cast<char*>(p) + bytes_half;
-            if (mode == 0) (void)hipMemsetAsync(lo, 0, bytes_half, st);
-            else (void)hipMemcpyAsync(lo, src, bytes_half, hipMemcpyDeviceToDevice, st);
-            if (mode == 2 && channels == 2)                  // NCHW [B][2][H][W]: zero channel 1 of every sample
-                (void)hipMemset2DAsync(lo + per * 4, 2 * per * 4, 0, per * 4, B, st);
-            return p;
-        };
-        bool ok = true;
-        if (a.y) ok = ok && (y_e = static_cast<const int64_t*>(dup(a.y, (size_t)B * 8, 0, 0)));          // null token 0
-        if (a.cond_img) ok = ok && (cond_e = static_cast<const float*>(dup(a.cond_img, n * 4 * cfg.n_cond_channels, 0, 0)));
-        if (a.lsm_cond) ok = ok && (lsm_e = static_cast<const float*>(dup(a.lsm_cond, n * 4 * cfg.n_lsm_channels, 2, cfg.n_lsm_channels)));
-        if (a.topo_cond) ok = ok && (topo_e = static_cast<const float*>(dup(a.topo_cond, n * 4 * cfg.n_topo_channels, 2, cfg.n_topo_channels)));
-        SBGM_CHECK(ok && hipGetLastError() == hipSuccess, "sampler: could not allocate the unconditional condition tensors");
-    }
-
-    // x0 = randn * marginal_prob_std(1)
+    // x0 = randn * marginal_prob_std(1); EDM Heun: sigma_0 z into its state slab, copied to the network input
     const float ls = logf(sig);
     const float std1 = fmaxf(sqrtf((expf((2.f * 1.0f) * ls) - 1.f) / (2.f * ls)), 1e-5f);
     const float* z = a.noise;
@@ -1117,96 +1120,81 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
                    a.domain_w);
         nm = NoiseMap{a.tile_origins, H, W / 4, (a.domain_w + 3) / 4};
     }
-    if (heun) {                                            // x = sigma_0 z into the state slab, copied to the network input
-        if (sbgm_launch_init_noise(xmean, etab[0].sigma, next_z(), a.seed, d_state, 0, n, st, nm)) return 1;
-        SBGM_HIP(hipMemcpyAsync(xs, xmean, n * 4, hipMemcpyDeviceToDevice, st));
-    } else if (sbgm_launch_init_noise(xs, std1, next_z(), a.seed, d_state, 0, n, st, nm)) {
-        return 1;
-    }
-    if (sbgm_launch_fill_t(t_dev, t_first, BE, st)) return 1;
+    const float x0_scale = heun ? reinterpret_cast<const EdmStep*>(h_stage)->sigma : std1;
+    if (sbgm_launch_init_noise(heun ? xmean : xs, x0_scale, next_z(), a.seed, d_state, 0, n, st, nm)) return 1;
+    if (heun) SBGM_HIP(hipMemcpyAsync(xs, xmean, n * 4, hipMemcpyDeviceToDevice, st));
+    if (sbgm_launch_fill_t(t_dev, tab.t_first, BE, st)) return 1;
     const float snr_nn = (float)((double)a.snr * std::sqrt((double)per));     // snr * sqrt(prod(x.shape[1:])) (:202-203)
 
     // one (possibly guided) score evaluation of the current x into score[0 .. n)
     auto evaluate = [&](float w) -> int {
         if (guided) SBGM_HIP(hipMemcpyAsync(xs + n, xs, n * 4, hipMemcpyDeviceToDevice, st));
-        if (forward(xs, t_dev, y_e, cond_e, lsm_e, topo_e, score, nullptr, BE, H, W, a.bn_train, st)) return 1;
+        if (forward(xs, t_dev, conds.y, conds.cond, conds.lsm, conds.topo, score, nullptr, BE, H, W, a.bn_train, st)) return 1;
         return guided ? sbgm_launch_cfg_combine(score, score, score + n, w, n, st) : 0;
     };
     const bool churn = heun && edm->s_churn > 0.f;
-    // one Heun step: (churn) -> eval -> euler -> eval -> heun + advance; the last step (sigma_N = 0) is Euler only, into `out`
-    auto heun_step = [&](bool with_noise_ptrs, bool last) -> int {
-        if (churn && sbgm_launch_edm_churn(xmean, xs, with_noise_ptrs ? next_z() : nullptr, d_edm_table, d_state, nullptr, 0, a.seed,
-                                           n, st, nm)) return 1;
-        if (evaluate(a.cfg_scale)) return 1;
-        if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, d_edm_table, d_state, nullptr, t_dev, BE, n, st)) return 1;
-        if (last) return 0;
-        if (evaluate(a.cfg_scale)) return 1;
-        return sbgm_launch_edm_heun(xmean, xs, dheun, score, d_edm_table, d_state, nullptr, t_dev, BE, N, n, st);
-    };
-    auto one_step = [&](bool with_noise_ptrs) -> int {
-        if (heun) return heun_step(with_noise_ptrs, false);
+    // One step of the run's kind; z_ptrs: read the caller's noise draws (eager runs).
+    //   EM:  eval -> predictor + advance          PC: eval -> Langevin corrector -> eval -> predictor + advance
+    //   EDM: (churn) -> eval -> euler -> eval -> heun + advance; `last` (sigma_N = 0) is Euler only, into `out`
+    auto step = [&](bool z_ptrs, bool last) -> int {
+        if (heun) {
+            if (churn && sbgm_launch_edm_churn(xmean, xs, z_ptrs ? next_z() : nullptr, edm_tab, d_state, nullptr, 0, a.seed, n, st, nm))
+                return 1;
+            if (evaluate(a.cfg_scale)) return 1;
+            if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, edm_tab, d_state, nullptr, t_dev, BE, n, st)) return 1;
+            if (last) return 0;
+            if (evaluate(a.cfg_scale)) return 1;
+            return sbgm_launch_edm_heun(xmean, xs, dheun, score, edm_tab, d_state, nullptr, t_dev, BE, N, n, st);
+        }
         if (a.kind == SBGM_SAMPLER_PC) {
             if (evaluate(a.cfg_scale_corrector)) return 1;
-            if (sbgm_launch_langevin(xs, score, with_noise_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, nm)) return 1;
+            if (sbgm_launch_langevin(xs, score, z_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, nm)) return 1;
         }
         if (evaluate(a.cfg_scale)) return 1;
-        return sbgm_launch_em_update(xs, xmean, score, with_noise_ptrs ? next_z() : nullptr, d_table, d_state, nullptr, 0, t_dev,
-                                     a.seed, B, per, N, st, BE, nm);
+        return sbgm_launch_em_update(xs, xmean, score, z_ptrs ? next_z() : nullptr, sde_tab, d_state, nullptr, 0, t_dev, a.seed, B,
+                                     per, N, st, BE, nm);
     };
+    // The run: N - tail steps (replays of the captured step, or eager launches), then `tail` eager last steps.  EM / PC: no tail,
+    // the result is the x_mean slab, copied to `out`; EDM Heun: the tail is its Euler-only last step, which writes `out` itself.
+    const int tail = heun ? 1 : 0;
 
     const size_t saved_ws = ws_bytes;
     ws_bytes = fwd_bytes;            // forward() must not touch the sampler slabs
     int rc = 0;
     if (graphed) {
         StepGraphKey key{};                                  // (value-initialised: the padding bytes compare equal)
-        key.B = B; key.H = H; key.W = W; key.kind = a.kind; key.guided = guided; key.bn_train = a.bn_train;
-        key.table = heun ? (const void*)d_edm_table : (const void*)d_table; key.churn = churn;
-        key.domain_w = a.domain_w; key.y = y_e; key.cond = cond_e; key.lsm = lsm_e; key.topo = topo_e; key.origins = a.tile_origins;
-        key.ws = ws; key.ws_bytes = saved_ws; key.cfg = a.cfg_scale; key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector;
-        key.snr_nn = heun ? 0.f : snr_nn;
-        key.plan_gen = plan_gen;
-        const bool reuse = step_exec != nullptr && !guided && std::memcmp(&key, &step_key, sizeof key) == 0;
-        if (!reuse) {
+        key.B = B; key.H = H; key.W = W; key.kind = a.kind; key.guided = guided; key.bn_train = a.bn_train; key.churn = churn;
+        key.domain_w = a.domain_w; key.y = conds.y; key.cond = conds.cond; key.lsm = conds.lsm; key.topo = conds.topo;
+        key.origins = a.tile_origins; key.ws = ws; key.table = d_table; key.ws_bytes = saved_ws; key.cfg = a.cfg_scale;
+        key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn; key.plan_gen = plan_gen;
+        if (step_exec == nullptr || guided || std::memcmp(&key, &step_key, sizeof key) != 0) {
             drop_step_graph();
-            const hipStream_t run_st = st;
-            if (replay_on_caller) st = graph_stream;          // capture (records, runs nothing) on the private stream; replay on the caller's
+            st = graph_stream;                                // capture records, it runs nothing
             hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                rc = one_step(false);
-                hipError_t e2 = hipStreamEndCapture(st, &step_graph);
-                st = run_st;
-                if (rc == 0 && (e2 != hipSuccess || hipGraphInstantiate(&step_exec, step_graph, nullptr, nullptr, 0) != hipSuccess)) {
-                    sbgm_set_error("hipGraph capture/instantiate failed: %s", hipGetErrorString(e2));
+            if (e != hipSuccess) { sbgm_set_error("hipStreamBeginCapture failed: %s", hipGetErrorString(e)); rc = 2; }
+            if (rc == 0) {
+                rc = step(false, false);
+                e = hipStreamEndCapture(st, &step_graph);
+                if (rc == 0 && (e != hipSuccess || hipGraphInstantiate(&step_exec, step_graph, nullptr, nullptr, 0) != hipSuccess)) {
+                    sbgm_set_error("hipGraph capture/instantiate failed: %s", hipGetErrorString(e));
                     rc = 2;
                 }
                 if (rc) drop_step_graph();
                 else step_key = key;
-            } else {
-                st = run_st;
-                sbgm_set_error("hipStreamBeginCapture failed: %s", hipGetErrorString(e));
-                rc = 2;
             }
+            st = caller;
         }
-        const int replays = heun ? N - 1 : N;                // EDM: the final Euler-only step is enqueued eagerly below
-        for (int i = 0; i < replays && rc == 0; ++i)
+        for (int i = 0; i < N - tail && rc == 0; ++i)
             if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
-        if (heun && rc == 0) rc = heun_step(false, true);
-        if (guided) {                                        // its condition copies are freed when this call returns
-            (void)hipStreamSynchronize(st);
-            drop_step_graph();
-        }
-    } else if (heun) {
-        for (int i = 0; i < N && rc == 0; ++i) rc = heun_step(z != nullptr, i == N - 1);
+        if (step_exec && hipEventRecord(ev_replayed, st) != hipSuccess && !rc) { sbgm_set_error("hipEventRecord failed"); rc = 2; }
     } else {
-        for (int i = 0; i < N && rc == 0; ++i) rc = one_step(z != nullptr);
+        for (int i = 0; i < N - tail && rc == 0; ++i) rc = step(z != nullptr, false);
     }
+    if (tail && rc == 0) rc = step(z != nullptr, true);
+    if (graphed && guided) drop_step_graph();          // its condition copies are freed when this call returns
     ws_bytes = saved_ws;
     if (rc) return rc;
-    if (!heun) SBGM_HIP(hipMemcpyAsync(a.out, xmean, n * 4, hipMemcpyDeviceToDevice, st));
-    if (graphed && !replay_on_caller) {
-        SBGM_HIP(hipEventRecord(ev_out, st));
-        SBGM_HIP(hipStreamWaitEvent(caller, ev_out, 0));
-    }
+    if (!tail) SBGM_HIP(hipMemcpyAsync(a.out, xmean, n * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
@@ -1297,7 +1285,6 @@ int sbgm_model_forward(sbgm_model* m, const float* x, const float* t, const int6
 
 int sbgm_sampler_run(sbgm_model* m, const sbgm_sampler_args* a, void* stream) {
     SBGM_CHECK(a, "sampler_run: null args");
-    if (m->prepare_ws(a->cfg_enabled ? 2 * a->B : a->B, a->H, a->W, a->bn_train, 1, (hipStream_t)stream)) return 1;
     return m->sampler(*a, (hipStream_t)stream);
 }
 
@@ -1309,7 +1296,6 @@ int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_
     SBGM_CHECK(rho > 0.f && s_churn >= 0.f && s_noise >= 0.f, "sampler_run_edm: need rho > 0, s_churn >= 0, s_noise >= 0");
     SBGM_CHECK(!(sigma_min > 0.f && sigma_max > 0.f && sigma_min >= sigma_max), "sampler_run_edm: sigma_min %g >= sigma_max %g",
                sigma_min, sigma_max);
-    if (m->prepare_ws(a->cfg_enabled ? 2 * a->B : a->B, a->H, a->W, 0, 1, (hipStream_t)stream, SBGM_SAMPLER_EDM_HEUN)) return 1;
     const sbgm_model::EdmArgs e{sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise};
     return m->sampler(*a, (hipStream_t)stream, &e);
 }
@@ -1340,13 +1326,13 @@ int sbgm_model::dummy_forward(int B, int H, int W, bool tune, hipStream_t st) {
 // BEFORE the caller's work, so the slab has its final size (and address) from the first real call on: a sampler's captured step graph
 // is then captured once, not again after a later call has trimmed the slab.  Train-mode BatchNorm shapes are not pre-measured (an
 // evaluation would move the running statistics): they run on the generous bound first and are trimmed by a later call.
-int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, size_t factor, hipStream_t st, int kind) {
+int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, int slabs) {
     if (!bn_train && ws_peak.find(std::array<int, 4>{B, H, W, 0}) == ws_peak.end() && sbgm_model_check_complete(this) == 0) {
-        if (ensure_ws(ws_need(B, H, W, 0, kind) + ((size_t)B * H * W * 16 + 1024) * 4 + 4096)) return 1;
+        if (ensure_ws(ws_need(B, H, W, 0, slabs) + ((size_t)B * H * W * 16 + 1024) * 4 + 4096)) return 1;
         if (bn_dirty && fold_bn(st)) return 1;
         if (dummy_forward(B, H, W, false, st)) return 1;
     }
-    return ensure_ws(factor * ws_need(B, H, W, bn_train, kind));
+    return ensure_ws(ws_need(B, H, W, bn_train, slabs));
 }
 
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {

@@ -87,8 +87,17 @@ def _guidance(cfg):
     return 1, scale, corr
 
 
+def _counts(kind, num_steps, churn=False):
+    """(network evaluations per step, noise draws of a run) of a sampler kind: draw 0 is the initial state; then one draw per
+    evaluation of an SDE step (PC: corrector and predictor), or one per EDM Heun step with churn"""
+    if kind == N.SAMPLER_EDM_HEUN:
+        return 2, 1 + (int(num_steps) if churn else 0)
+    per_step = 2 if kind == N.SAMPLER_PC else 1
+    return per_step, 1 + int(num_steps) * per_step
+
+
 def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw, y, cond_img, lsm_cond, topo_cond,
-                noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm=None):
+                noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm_args=None):
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if dev.type != "cuda":
         raise N.NativeError(f"the native samplers run on a ROCm device, got device={device!r}")
@@ -100,7 +109,7 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
     nz = None
     if noise is not None:
         nz = noise if torch.is_tensor(noise) else torch.stack(list(noise))
-        need = edm["draws"] if edm is not None else 1 + num_steps * (2 if kind == N.SAMPLER_PC else 1)
+        need = _counts(kind, num_steps, edm_args is not None and edm_args[3] > 0)[1]          # edm_args[3]: s_churn
         if nz.shape[0] < need:
             raise ValueError(f"noise holds {nz.shape[0]} draws, the sampler consumes {need}")
         nz = N.f32c(nz.to(dev))
@@ -113,13 +122,31 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
             raise ValueError("tile_origins must be a contiguous int32 [batch, 2] device tensor of (y0, x0)")
         if noise is not None:
             raise ValueError("tile_origins keys the in-kernel noise; it cannot be combined with injected noise")
-    if edm is not None:
-        N.check(eng.lib.sbgm_sampler_run_edm(eng.h, C.byref(a), *edm["args"], N.stream()))
+    if edm_args is not None:
+        N.check(eng.lib.sbgm_sampler_run_edm(eng.h, C.byref(a), *edm_args, N.stream()))
         return out
     N.check(eng.lib.sbgm_sampler_run(eng.h, C.byref(a), N.stream()))
     if score_model.training:
-        eng.download_bn_stats(score_model, n_forwards=int(num_steps) * (2 if kind == N.SAMPLER_PC else 1))
+        eng.download_bn_stats(score_model, n_forwards=int(num_steps) * _counts(kind, num_steps)[0])
     return out
+
+
+def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scale, tile_origins, churn=False):
+    """Setup of the host-driven loops: refuses `tile_origins`, checks that `noise` holds the run's draws, and returns the initial
+    x = scale * (draw 0) and z(i), the i-th noise draw (None: the kernels draw in-kernel Philox noise)."""
+    if tile_origins is not None:
+        raise N.NativeError("domain-keyed noise (tile_origins) needs the native sampler loop (a ScoreNet in eval mode)")
+    if noise is not None:
+        noise = noise if torch.is_tensor(noise) else list(noise)
+        need = _counts(kind, num_steps, churn)[1]
+        if len(noise) < need:
+            raise ValueError(f"noise holds {len(noise)} draws, the sampler consumes {need}")
+    x = torch.empty(batch_size, 1, img_size, img_size, device=device)
+    if noise is None:
+        N.check(N.lib().sbgm_randn_scaled(x.data_ptr(), scale, seed, 0, x.numel(), N.stream()))
+    else:
+        x.copy_(noise[0].to(x) * scale)
+    return x, lambda i: None if noise is None else N.f32c(noise[i].to(x))
 
 
 def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=500, device="cuda",
@@ -130,29 +157,19 @@ def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batc
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_EM, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
                            topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width)
-    if tile_origins is not None:
-        raise N.NativeError("domain-keyed noise (tile_origins) needs the native sampler loop (a ScoreNet in eval mode)")
     lib, st = N.lib(), N.stream
-    noise = iter(noise) if noise is not None else None
     ones = torch.ones(batch_size, device=device)
-    std1 = float(marginal_prob_std(ones)[0])
-    x = torch.empty(batch_size, 1, img_size, img_size, device=device)
-    draw = 0
-    if noise is None:
-        N.check(lib.sbgm_randn_scaled(x.data_ptr(), std1, seed, draw, x.numel(), st()))
-    else:
-        x.copy_(next(noise).to(x) * std1)
+    x, z = _host_start(N.SAMPLER_EM, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
+                       tile_origins)
     time_steps = torch.linspace(1.0, eps, num_steps, device=device)
     step_size = float(time_steps[0] - time_steps[1])
     mean_x = torch.empty_like(x)
     with torch.no_grad():
-        for ts in time_steps.tolist():
+        for draw, ts in enumerate(time_steps.tolist(), 1):
             bt = ones * ts
             g = float(diffusion_coeff(bt)[0])
             score = N.f32c(_score(score_model, cfg, x, bt, y, cond_img, lsm_cond, topo_cond))
-            draw += 1
-            z = None if noise is None else N.f32c(next(noise).to(x))
-            N.check(lib.sbgm_em_step(x.data_ptr(), mean_x.data_ptr(), score.data_ptr(), N.ptr(z), g * g, step_size,
+            N.check(lib.sbgm_em_step(x.data_ptr(), mean_x.data_ptr(), score.data_ptr(), N.ptr(z(draw)), g * g, step_size,
                                      math.sqrt(step_size) * g, seed, draw, x.numel(), st()))
     return mean_x
 
@@ -166,18 +183,10 @@ def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, n
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_PC, score_model, batch_size, num_steps, snr, eps, img_size, y, cond_img, lsm_cond,
                            topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width)
-    if tile_origins is not None:
-        raise N.NativeError("domain-keyed noise (tile_origins) needs the native sampler loop (a ScoreNet in eval mode)")
     lib, st = N.lib(), N.stream
-    noise = iter(noise) if noise is not None else None
     ones = torch.ones(batch_size, device=device)
-    std1 = float(marginal_prob_std(ones)[0])
-    x = torch.empty(batch_size, 1, img_size, img_size, device=device)
-    draw = 0
-    if noise is None:
-        N.check(lib.sbgm_randn_scaled(x.data_ptr(), std1, seed, draw, x.numel(), st()))
-    else:
-        x.copy_(next(noise).to(x) * std1)
+    x, z = _host_start(N.SAMPLER_PC, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
+                       tile_origins)
     time_steps = np.linspace(1.0, eps, num_steps)
     step_size = float(time_steps[0] - time_steps[1])
     x_mean = torch.empty_like(x)
@@ -185,19 +194,15 @@ def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, n
     per = x[0].numel()
     snr_nn = float(snr * np.sqrt(per))
     with torch.no_grad():
-        for ts in time_steps:
+        for i, ts in enumerate(time_steps):
             bt = ones * ts
             grad = N.f32c(_score(score_model, cfg, x, bt, y, cond_img, lsm_cond, topo_cond, clamp=True))
-            draw += 1
-            z = None if noise is None else N.f32c(next(noise).to(x))
-            N.check(lib.sbgm_langevin_step(x.data_ptr(), grad.data_ptr(), N.ptr(z), snr_nn, sumsq.data_ptr(), seed, draw,
-                                           batch_size, per, st()))
+            N.check(lib.sbgm_langevin_step(x.data_ptr(), grad.data_ptr(), N.ptr(z(1 + 2 * i)), snr_nn, sumsq.data_ptr(), seed,
+                                           1 + 2 * i, batch_size, per, st()))
             g = float(diffusion_coeff(bt)[0])
             score = N.f32c(_score(score_model, cfg, x, bt, y, cond_img, lsm_cond, topo_cond))
-            draw += 1
-            z = None if noise is None else N.f32c(next(noise).to(x))
-            N.check(lib.sbgm_em_step(x.data_ptr(), x_mean.data_ptr(), score.data_ptr(), N.ptr(z), g * g, step_size,
-                                     math.sqrt(g * g * step_size), seed, draw, x.numel(), st()))
+            N.check(lib.sbgm_em_step(x.data_ptr(), x_mean.data_ptr(), score.data_ptr(), N.ptr(z(2 + 2 * i)), g * g, step_size,
+                                     math.sqrt(g * g * step_size), seed, 2 + 2 * i, x.numel(), st()))
     return x_mean
 
 
@@ -290,7 +295,7 @@ def edm_heun_schedule(num_steps, sigma_sde=25.0, eps=1e-3, sigma_min=None, sigma
         return np.where(v >= hi, 1.0, np.where(v <= lo, eps, t))
     return {"sigma": sigma, "gamma": gamma, "sigma_hat": sigma_hat, "t_hat": t_of(sigma_hat), "t_next": t_of(sigma[1:]),
             "churn_coef": s_noise * np.sqrt(np.maximum(0.0, sigma_hat ** 2 - s ** 2)), "nfe": 2 * N_ - 1,
-            "draws": 1 + (N_ if s_churn > 0 else 0), "sigma_min": smin, "sigma_max": smax}
+            "draws": _counts(N.SAMPLER_EDM_HEUN, N_, s_churn > 0)[1], "sigma_min": smin, "sigma_max": smax}
 
 
 def edm_sampler_kwargs(cfg) -> dict:
@@ -317,33 +322,22 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     sch = edm_heun_schedule(num_steps, sig, eps, sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise)
     seed = _fresh_seed() if seed is None else seed
     if isinstance(score_model, ScoreNet) and not score_model.training:
-        edm = {"draws": sch["draws"], "args": (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"],
-                                               float(rho), float(s_churn), float(s_tmin), float(s_tmax), float(s_noise))}
+        edm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
+                    float(s_churn), float(s_tmin), float(s_tmax), float(s_noise))
         return _native_run(N.SAMPLER_EDM_HEUN, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
-                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, edm=edm)
-    if tile_origins is not None:
-        raise N.NativeError("domain-keyed noise (tile_origins) needs the native sampler loop (a ScoreNet in eval mode)")
+                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, edm_args=edm_args)
     lib, st = N.lib(), N.stream
-    if noise is not None:
-        noise = noise if torch.is_tensor(noise) else list(noise)
-        if len(noise) < sch["draws"]:
-            raise ValueError(f"noise holds {len(noise)} draws, the sampler consumes {sch['draws']}")
-    x = torch.empty(batch_size, 1, img_size, img_size, device=device)
+    churn = s_churn > 0
+    x, z = _host_start(N.SAMPLER_EDM_HEUN, batch_size, num_steps, img_size, device, noise, seed, float(np.float32(sch["sigma"][0])),
+                       tile_origins, churn)
     n = x.numel()
-    sigma0 = float(np.float32(sch["sigma"][0]))
-    if noise is None:
-        N.check(lib.sbgm_randn_scaled(x.data_ptr(), sigma0, seed, 0, n, st()))
-    else:
-        x.copy_(N.f32c(noise[0].to(x)) * sigma0)
     xp, d, out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     ones = torch.ones(batch_size, device=device)
-    churn = s_churn > 0
     with torch.no_grad():
         for i in range(int(num_steps)):
             sh, sn = float(sch["sigma_hat"][i]), float(sch["sigma"][i + 1])
             if churn:
-                z = None if noise is None else N.f32c(noise[1 + i].to(x))
-                N.check(lib.sbgm_edm_churn(x.data_ptr(), N.ptr(z), float(sch["churn_coef"][i]), seed, 1 + i, n, st()))
+                N.check(lib.sbgm_edm_churn(x.data_ptr(), N.ptr(z(1 + i)), float(sch["churn_coef"][i]), seed, 1 + i, n, st()))
             s1 = N.f32c(_score(score_model, cfg, x, ones * float(np.float32(sch["t_hat"][i])), y, cond_img, lsm_cond, topo_cond))
             last = i == int(num_steps) - 1
             N.check(lib.sbgm_edm_euler(x.data_ptr(), s1.data_ptr(), d.data_ptr(), (out if last else xp).data_ptr(), sh, sn, n, st()))

@@ -158,6 +158,20 @@ def test_python_loop_sampler_equals_native_loop():
     assert maxrel(a.cpu(), b.cpu()) <= 1e-4
 
 
+def test_short_noise_is_refused_before_any_step():
+    """every sampler loop, native or host-driven, checks up front that `noise` holds all the draws the run consumes"""
+    import sbgm_danra_amd as S
+    _, net, _ = build_pair(1)
+    net.eval()
+    f = lambda x, t, y=None, c=None, l=None, tp=None: net(x, t, y, c, l, tp)  # noqa: E731  (a plain callable, not a ScoreNet)
+    noise = torch.randn(4, 2, 1, 32, 32)           # 4 steps: EM needs 5 draws, PC 9, EDM Heun with churn 5
+    kw = dict(batch_size=2, num_steps=4, device="cuda", img_size=32, cond_img=torch.randn(2, 1, 32, 32).cuda())
+    for sampler, extra in ((S.Euler_Maruyama_sampler, {}), (S.pc_sampler, {}), (S.edm_heun_sampler, {"s_churn": 1.0})):
+        for model in (net, f):
+            with pytest.raises(ValueError, match="noise holds 4 draws"):
+                sampler(model, S.marginal_prob_std_fn, S.diffusion_coeff_fn, noise=noise, **kw, **extra)
+
+
 def test_graph_replay_equals_eager_and_seed_reproducible():
     import sbgm_danra_amd as S
     _, net, _ = build_pair(1)
