@@ -501,6 +501,46 @@ int sbgm_pointwise_chain(const float* x, float* y, int64_t n, int n_ops, const i
  * the two statistics report_precip_extremes needs (utils.py:1647-1649).  out_max, out_q: device [B]. */
 int sbgm_sample_extremes(const float* x, int B, int64_t per_sample, float q, float* out_max, float* out_q, void* stream);
 
+/* ---- verification statistics (verify.hip) -------------------------------------------------------------
+ * Inputs are fp32 [rows][HW] on the device, HW = H*W of any size.  A pixel of row n is VALID when gen/x is not NaN, obs/ref is
+ * not NaN and the mask admits it (mask_is_u8: uint8 != 0; else fp32 > 0.5); every statistic uses valid pixels only (nanmean).
+ * obs / ref / mask rows are 1 (broadcast) or one per row.  Float sums are fp64 per-wave partials added in a fixed order and
+ * histograms are integer, so every output is bitwise reproducible.  `workspace` holds the partials; size it with the
+ * *_workspace_bytes query.  Empty sets give NaN statistics.
+ *
+ * sbgm_error_stats: gen [N][HW] against obs [No][HW], mask [Nm][HW] or NULL.  Per pixel over samples: pix_count int32 [HW],
+ * pix_mae, pix_rmse, pix_bias = mean(gen) - mean(obs) fp32 [HW].  Per sample over pixels: sample_stats fp64 [N][3] =
+ * (count, MAE, RMSE).  global_stats fp64 [10] = (count, mean gen, mean obs, bias, MAE, RMSE, min gen, max gen, min obs,
+ * max obs). */
+int64_t sbgm_error_stats_workspace_bytes(int N, int64_t HW);
+int sbgm_error_stats(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int64_t HW,
+                     int* pix_count, float* pix_mae, float* pix_rmse, float* pix_bias, double* sample_stats, double* global_stats,
+                     void* workspace, void* stream);
+/* sbgm_histogram: counts int64 [bins] (overwritten) of v = x, or |x - ref| when absdiff, over the valid pixels of x [N][HW]
+ * (ref [Nr][HW] or NULL, mask [Nm][HW] or NULL).  Equal bins on [lo, hi] with numpy.histogram's range and closed-last-bin
+ * convention and the floor rule: v is kept iff lo <= v <= hi and idx = floor(((double)v - lo) * bins / (hi - lo)) in fp64,
+ * clamped to bins - 1 (v == hi falls in the last bin).  numpy also corrects indices against its linspace edges, so a value
+ * within rounding of an interior edge can land one bin away from numpy's choice.  1 <= bins <= 8192. */
+int sbgm_histogram(const float* x, const float* ref, const void* mask, int mask_is_u8, int N, int Nr, int Nm, int64_t HW,
+                   int absdiff, double lo, double hi, int bins, int64_t* counts, void* stream);
+/* sbgm_ensemble_scores: members ens [M][HW] (2 <= M <= 8191), truth obs [HW], mask [HW] or NULL.  A pixel with any NaN member
+ * is invalid: its maps are NaN and its rank -1.  Per pixel: mean, var (ddof 1), crps (fair: (1/M) sum|x_i - y| -
+ * sum_ij|x_i - x_j| / (2M(M-1))) fp32 [HW]; rank int32 [HW] of obs among the members, uniform on [#{x_i < y}, #{x_i <= y}]
+ * from a Philox draw keyed by (seed, pixel).  rank_hist int64 [M+1] (overwritten).  scores fp64 [6] = (count, mean fair
+ * CRPS, mean standard CRPS (c = 1/(2M^2)), skill = RMSE of the ensemble mean, spread = sqrt(mean var),
+ * spread / skill * sqrt((M+1)/M)). */
+int64_t sbgm_ensemble_scores_workspace_bytes(int64_t HW);
+int sbgm_ensemble_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
+                         uint64_t seed, float* mean, float* var, float* crps, int* rank, int64_t* rank_hist, double* scores,
+                         void* workspace, void* stream);
+/* sbgm_radial_spectrum: power [F][H][W] = |fft2|^2 of mean-removed fields; fields with field_ok[f] == 0 (uint8 [F]) are
+ * skipped.  With L = max(H, W) and fy, fx = numpy.fft.fftfreq (cycles per pixel), pixel (iy, ix) is in bin
+ * k = rint(L * sqrt(fy^2 + fx^2)); bins 0..L/2 are kept, the corners dropped.  psd fp64 [L/2+1] = mean power per bin over
+ * the kept fields, bin_count int64 [L/2+1] = pixels per bin, n_fields int64 [1] = fields used.  2 <= H, W <= 2048. */
+int64_t sbgm_radial_spectrum_workspace_bytes(int H, int W);
+int sbgm_radial_spectrum(const float* power, const unsigned char* field_ok, int F, int H, int W, double* psd, int64_t* bin_count,
+                         int64_t* n_fields, void* workspace, void* stream);
+
 /* ---- before the network ------------------------------------------------------------------------
  * Batch-level condition assembly: channel concatenation of the sorted *_lr fields (utils.py:441-447), classifier-free-
  * guidance condition dropout (data_modules.py:957-983: LR fields -> 0, class label -> NULL token 0) and the value||mask

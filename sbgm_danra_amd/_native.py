@@ -171,6 +171,13 @@ SIGNATURES = {
     "sbgm_edm_churn": (_i, [_vp, _vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_edm_euler": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i64, _vp]),
     "sbgm_edm_heun": (_i, [_vp, _vp, _vp, _f, _f, _i64, _vp]),
+    "sbgm_error_stats_workspace_bytes": (_i64, [_i, _i64]),
+    "sbgm_error_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64] + [_vp] * 8),
+    "sbgm_histogram": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, C.c_double, C.c_double, _i, _vp, _vp]),
+    "sbgm_ensemble_scores_workspace_bytes": (_i64, [_i64]),
+    "sbgm_ensemble_scores": (_i, [_vp, _vp, _vp, _i, _i, _i64, _u64] + [_vp] * 8),
+    "sbgm_radial_spectrum_workspace_bytes": (_i64, [_i, _i]),
+    "sbgm_radial_spectrum": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 4          # include/sbgm_hip.h: sbgm_abi_version()

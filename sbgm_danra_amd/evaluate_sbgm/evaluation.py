@@ -1,0 +1,241 @@
+"""`Evaluation` — the statistics half of reference sbgm/evaluate_sbgm/evaluation.py:15-444, on the device.  Reads the npz
+files `SampleGenerator` writes, moves them to the GPU once, and computes every statistic with the verification kernels
+(csrc/verify.hip via `..verification`): the reference's pixel, spatial and daily statistics plus ensemble scores (CRPS, rank
+histogram, spread/skill) and radially averaged power spectra.  Only scalars, maps and histograms come back to the host.
+Plots are out of scope: the plotting keys are accepted and logged as skipped.
+
+Files are found by name: `gen_samples_*`, `eval_samples_*` and `lsm_samples_*` with the suffixes `multi_n_<B>`, `single`,
+`repeated_n_<n>` (this package) or `repeated_<n>` (the reference), each optionally followed by `_rank<r>`.  Rank files of
+`multiple` / `single` are concatenated along the sample axis; each rank's `repeated` file is its own unit (every rank
+conditions on a different sample), selected with `rank=`."""
+from __future__ import annotations
+
+import json
+import logging
+import os
+import re
+
+import numpy as np
+import torch
+
+from .. import verification as V
+from ..utils import get_model_string
+
+logger = logging.getLogger(__name__)
+
+GEN_TYPES = ("multiple", "single", "repeated")
+PREFIXES = ("gen_samples", "eval_samples", "lsm_samples")
+_SUFFIX = {"multiple": r"multi_n_(?P<n>\d+)", "single": r"single(?P<n>)", "repeated": r"repeated_(?:n_)?(?P<n>\d+)"}
+PIXEL_BINS = 150                      # the reference's pixel-value histograms (evaluation.py:320)
+CRPS_DEFINITIONS = {"crps_fair": "(1/M) sum_i |x_i - y| - sum_ij |x_i - x_j| / (2 M (M - 1))",
+                    "crps_standard": "(1/M) sum_i |x_i - y| - sum_ij |x_i - x_j| / (2 M^2)"}
+
+
+def sample_units(sample_dir, gen_type, n_samples=None):
+    """the evaluation units of one generation type in `sample_dir`: a list of (rank or None, {prefix: [paths in rank order]}).
+    `multiple` / `single` give one unit (rank files concatenated); `repeated` gives one unit per rank file.  When files of
+    several sizes exist, the one of size `n_samples` is taken."""
+    if gen_type not in GEN_TYPES:
+        raise ValueError(f"Unknown generated sample type: {gen_type}. Choose from: {list(GEN_TYPES)}")
+    pat = re.compile(rf"^(?P<prefix>{'|'.join(PREFIXES)})_{_SUFFIX[gen_type]}(?:_rank(?P<rank>\d+))?\.npz$")
+    found = {}                                         # (rank, n) -> {prefix: path}
+    for f in sorted(os.listdir(sample_dir)) if os.path.isdir(sample_dir) else []:
+        m = pat.match(f)
+        if m:
+            r = None if m.group("rank") is None else int(m.group("rank"))
+            found.setdefault((r, m.group("n")), {})[m.group("prefix")] = os.path.join(sample_dir, f)
+    found = {k: v for k, v in found.items() if "gen_samples" in v}
+    if not found:
+        raise FileNotFoundError(f"no gen_samples_* file of type '{gen_type}' in {sample_dir}")
+    plain = {k: v for k, v in found.items() if k[0] is None}
+    pool = plain or found                               # an unranked file wins over rank files
+    if plain and len(plain) != len(found):
+        ranked = sorted({k[0] for k in found if k[0] is not None})
+        logger.warning(f"[WARN] {sample_dir} holds both single-process '{gen_type}' files and rank files (ranks {ranked}); "
+                       f"evaluating the single-process files. Remove the ones that are stale.")
+    by_rank = {}
+    for (r, n), files in pool.items():
+        by_rank.setdefault(r, {})[n] = files
+    chosen = {}
+    for r, sizes in by_rank.items():
+        if len(sizes) == 1:
+            chosen[r] = next(iter(sizes.values()))
+        elif n_samples is not None and str(n_samples) in sizes:
+            chosen[r] = sizes[str(n_samples)]
+        else:
+            raise ValueError(f"several '{gen_type}' sample sizes {sorted(sizes)} in {sample_dir}"
+                             f"{'' if r is None else f' for rank {r}'}; none matches n_samples={n_samples}")
+    ranks = sorted(chosen, key=lambda r: -1 if r is None else r)
+    for r in ranks:
+        if "eval_samples" not in chosen[r]:
+            raise FileNotFoundError(f"gen_samples of type '{gen_type}' (rank {r}) have no matching eval_samples file in {sample_dir}")
+    if gen_type == "repeated":
+        return [(r, {p: [chosen[r][p]] for p in chosen[r]}) for r in ranks]
+    merged = {p: [chosen[r][p] for r in ranks] for p in PREFIXES if all(p in chosen[r] for r in ranks)}
+    return [(None, merged)]
+
+
+def _fields3(a):
+    """[N,H,W] from the saved layouts: [N,H,W], [N,C,H,W] (channel 0) or [H,W]"""
+    a = np.asarray(a)
+    if a.ndim == 4:
+        a = a[:, 0]
+    elif a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError(f"unexpected sample array shape {a.shape}")
+    return a
+
+
+def _load(paths):
+    return np.concatenate([_fields3(np.load(p)["arr_0"]) for p in paths], axis=0).astype(np.float32, copy=False)
+
+
+def statistics_dir(cfg):
+    """<paths.evaluation_dir>/<model string>/statistics, or <paths.sample_dir>/evaluation/<model string>/statistics"""
+    paths = cfg["paths"]
+    base = paths.get("evaluation_dir") or os.path.join(paths["sample_dir"], "evaluation")
+    return os.path.join(base, get_model_string(cfg), "statistics")
+
+
+class Evaluation:
+    def __init__(self, cfg, generated_sample_type="repeated", n_samples=4, rank=None, device=None):
+        self.cfg = cfg
+        self.generated_sample_type = generated_sample_type
+        self.model_name_str = get_model_string(cfg)
+        self.generated_sample_path = os.path.join(cfg["paths"]["sample_dir"], "generation", self.model_name_str, "generated_samples")
+        self.evaluation_stats_path = statistics_dir(cfg)
+        os.makedirs(self.evaluation_stats_path, exist_ok=True)
+        units = sample_units(self.generated_sample_path, generated_sample_type, n_samples)
+        if rank is None and len(units) > 1:
+            raise ValueError(f"'{generated_sample_type}' files of ranks {[u[0] for u in units]}: pick one with rank=")
+        match = [u for u in units if rank is None or u[0] == rank]
+        if not match:
+            raise FileNotFoundError(f"no '{generated_sample_type}' files of rank {rank} in {self.generated_sample_path}")
+        self.rank, files = match[0]
+        self.label = generated_sample_type + ("" if self.rank is None else f"_rank{self.rank}")
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        logger.info(f"[INFO] Evaluating {self.label} from {files['gen_samples']}")
+        self.gen_imgs = torch.from_numpy(_load(files["gen_samples"])).to(self.device)
+        self.eval_imgs = torch.from_numpy(_load(files["eval_samples"])).to(self.device)
+        n, no = self.gen_imgs.shape[0], self.eval_imgs.shape[0]
+        if self.eval_imgs.shape[1:] != self.gen_imgs.shape[1:] or no not in (1, n):
+            raise ValueError(f"eval_samples {tuple(self.eval_imgs.shape)} do not match gen_samples {tuple(self.gen_imgs.shape)}")
+        self.mask = None
+        if cfg["evaluation"].get("mask_stats", False):
+            if "lsm_samples" not in files:
+                raise FileNotFoundError(f"evaluation.mask_stats is set but there is no lsm_samples file for {self.label} in "
+                                        f"{self.generated_sample_path}")
+            lsm = torch.from_numpy(_load(files["lsm_samples"])).to(self.device)
+            if lsm.shape[1:] != self.gen_imgs.shape[1:] or lsm.shape[0] not in (1, n):
+                raise ValueError(f"lsm_samples {tuple(lsm.shape)} do not match gen_samples {tuple(self.gen_imgs.shape)}")
+            self.mask = (lsm > 0.5).to(torch.uint8)         # land pixels (channel 0)
+        self.n_samples = n
+        self.metrics = {"gen_type": generated_sample_type, "rank": self.rank, "n_samples": n, "n_obs": no,
+                        "shape": list(self.gen_imgs.shape[1:]), "mask_stats": self.mask is not None}
+        self.fields = {}
+        self._err = None
+
+    def _error_stats(self):
+        if self._err is None:
+            self._err = V.error_stats(self.gen_imgs, self.eval_imgs, self.mask)
+        return self._err
+
+    def _valid(self):
+        """host copies of the valid (gen, obs) pixel values, flattened — only for the reference's save_stats files"""
+        g = self.gen_imgs
+        o = self.eval_imgs.expand_as(g)
+        v = ~(torch.isnan(g) | torch.isnan(o))
+        if self.mask is not None:
+            v &= self.mask.expand_as(g).bool()
+        return g[v].cpu().numpy(), o[v].cpu().numpy()
+
+    def full_pixel_statistics(self, show_figs=False, save_figs=False, save_stats=False, save_path=None, n_samples=None):
+        """global count / means / bias / MAE / RMSE / extremes, 150-bin histograms of gen and obs over their joint range and of
+        |gen - obs| over [0, its bound] (reference evaluation.py:266-389)"""
+        if show_figs or save_figs:
+            logger.info("[INFO] full_pixel_statistics: figures are not produced (plotting is out of scope)")
+        g = self._error_stats()["global"].cpu().numpy()
+        out = dict(zip(V.GLOBAL_KEYS, (float(v) for v in g)))
+        out["count"] = int(g[0])
+        res = {"metrics": out}
+        if out["count"] > 0:
+            lo, hi = min(out["min_gen"], out["min_obs"]), max(out["max_gen"], out["max_obs"])
+            hi = hi if hi > lo else lo + 1.0
+            dmax = max(out["max_gen"] - out["min_obs"], out["max_obs"] - out["min_gen"], 0.0)
+            dmax = dmax if dmax > 0 else 1.0
+            res["hist_gen"] = V.histogram(self.gen_imgs, PIXEL_BINS, lo, hi, ref=self.eval_imgs, mask=self.mask).cpu().numpy()
+            res["hist_obs"] = V.histogram(self.eval_imgs.expand_as(self.gen_imgs), PIXEL_BINS, lo, hi, ref=self.gen_imgs,
+                                          mask=self.mask).cpu().numpy()
+            res["hist_value_edges"] = V.histogram_edges(PIXEL_BINS, lo, hi).numpy()
+            res["hist_absdiff"] = V.histogram(self.gen_imgs, PIXEL_BINS, 0.0, dmax, ref=self.eval_imgs, mask=self.mask,
+                                              absdiff=True).cpu().numpy()
+            res["hist_absdiff_edges"] = V.histogram_edges(PIXEL_BINS, 0.0, dmax).numpy()
+        self.metrics["pixel_stats"] = out
+        self.fields.update({f"pixel_{k}": v for k, v in res.items() if k != "metrics"})
+        if save_stats:
+            n = self.n_samples if n_samples is None else n_samples
+            gf, of = self._valid()
+            np.savez(os.path.join(self.evaluation_stats_path, f"n_samples_{n}_pixel_statistics.npz"), gen_imgs_flat=gf, eval_imgs_flat=of)
+            d = np.abs(gf.astype(np.float32) - of.astype(np.float32))
+            np.savez(os.path.join(self.evaluation_stats_path, f"n_samples_{n}_RMSE_MAE_statistics.npz"), mae_all=d, rmse_all=d)
+        return res
+
+    def spatial_statistics(self, show_figs=False, save_figs=False, save_stats=False, save_path=None, n_samples=None):
+        """per-pixel count, MAE, RMSE and bias = nanmean(gen) - nanmean(obs) over the samples (reference evaluation.py:414-444)"""
+        if show_figs or save_figs:
+            logger.info("[INFO] spatial_statistics: figures are not produced (plotting is out of scope)")
+        e = self._error_stats()
+        res = {k: e[k].cpu().numpy() for k in ("count", "mae", "rmse", "bias")}
+        self.metrics["spatial_stats"] = {"mean_mae_per_pixel": float(np.nanmean(res["mae"])) if (res["count"] > 0).any() else float("nan")}
+        self.fields.update({f"spatial_{k}_per_pixel": v for k, v in res.items()})
+        return res
+
+    def daily_statistics(self, plot_stats=False, save_plots=False, save_stats=False, save_path=None):
+        """per-sample MAE and RMSE over the valid pixels (reference evaluation.py:393-410)"""
+        e = self._error_stats()
+        res = {k: e[f"sample_{k}"].cpu().numpy() for k in ("count", "mae", "rmse")}
+        res["count"] = res["count"].astype(np.int64)
+        self.metrics["daily_stats"] = {"n_days": int(res["count"].shape[0])}
+        self.fields.update({f"daily_{k}": v for k, v in res.items()})
+        return res
+
+    def ensemble_statistics(self, seed=None):
+        """CRPS (fair map, fair and standard means), rank histogram, skill, spread and spread/skill ratio of the `repeated`
+        samples as an ensemble of M members against their one truth"""
+        if self.generated_sample_type != "repeated":
+            raise ValueError(f"ensemble_statistics needs 'repeated' samples (an ensemble for one condition), not "
+                             f"'{self.generated_sample_type}'")
+        if self.n_samples < 2:
+            raise ValueError(f"ensemble_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        seed = int(self.cfg["evaluation"].get("seed", 0)) if seed is None else int(seed)
+        mask = None if self.mask is None else self.mask[0]
+        r = V.ensemble_scores(self.gen_imgs, self.eval_imgs[0], mask=mask, seed=seed)
+        s = r["scores"].cpu().numpy()
+        out = dict(zip(V.ENSEMBLE_KEYS, (float(v) for v in s)))
+        out.update(count=int(s[0]), M=self.n_samples, crps_map="crps_fair", crps_definitions=CRPS_DEFINITIONS, rank_seed=seed)
+        res = {k: r[k].cpu().numpy() for k in ("mean", "var", "crps", "rank", "rank_hist")}
+        self.metrics["ensemble_stats"] = out
+        self.fields.update({f"ensemble_{k}": v for k, v in res.items()})
+        return dict(res, metrics=out)
+
+    def spectral_statistics(self):
+        """radially averaged power spectral density of the generated and the true fields (each field mean-removed; a field
+        with a NaN is skipped and counted).  Spectra need whole rectangles, so mask_stats does not apply here."""
+        k, pg, sg = V.rapsd(self.gen_imgs)
+        _, po, so = V.rapsd(self.eval_imgs)
+        res = {"wavenumber": k.cpu().numpy(), "psd_gen": pg.cpu().numpy(), "psd_obs": po.cpu().numpy()}
+        out = {"skipped_gen": int(sg), "skipped_obs": int(so), "n_wavenumbers": int(res["wavenumber"].shape[0])}
+        self.metrics["spectral_stats"] = out
+        self.fields.update({f"spectral_{k}": v for k, v in res.items()})
+        return dict(res, metrics=out)
+
+    def save(self):
+        """<label>_metrics.json and <label>_fields.npz under the statistics directory; returns their paths"""
+        mpath = os.path.join(self.evaluation_stats_path, f"{self.label}_metrics.json")
+        fpath = os.path.join(self.evaluation_stats_path, f"{self.label}_fields.npz")
+        with open(mpath, "w") as f:
+            json.dump(self.metrics, f, indent=2, default=float)
+        np.savez(fpath, **self.fields)
+        logger.info(f"[INFO] Saved {mpath} and {fpath}")
+        return mpath, fpath

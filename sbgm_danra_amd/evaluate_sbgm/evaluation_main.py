@@ -1,0 +1,73 @@
+"""`evaluation_main(cfg)` — reference sbgm/evaluate_sbgm/evaluation_main.py:45-111: seed from evaluation.seed, then for every
+generation type in evaluation.eval_gen_type (default: evaluation.gen_type, then ['multiple']) run the methods of
+evaluation.eval_stat_methods (default ['pixel_stats', 'spatial_stats'], as in the reference) and write each unit's
+`<type>[_rank<r>]_metrics.json` / `_fields.npz`.  Plotting keys are accepted and logged as skipped."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from ..training_utils import setup_logger
+from ..utils import get_model_string
+from .evaluation import GEN_TYPES, Evaluation, sample_units
+
+METHODS = {"pixel_stats": "full_pixel_statistics", "spatial_stats": "spatial_statistics", "daily_stats": "daily_statistics",
+           "ensemble_stats": "ensemble_statistics", "spectral_stats": "spectral_statistics"}
+PLOT_KEYS = ("plot_examples", "save_figs", "show_plots", "show_figs", "mask_plots", "plot_w_cond", "plot_w_lsm")
+
+
+def eval_gen_types(cfg):
+    ev = cfg["evaluation"]
+    types = list(ev.get("eval_gen_type") or ev.get("gen_type") or ["multiple"])
+    for t in types:
+        if t not in GEN_TYPES:
+            raise ValueError(f"Invalid generated sample type: {t}. Must be one of {list(GEN_TYPES)}")
+    return types
+
+
+def eval_stat_methods(cfg):
+    methods = list(cfg["evaluation"].get("eval_stat_methods") or ["pixel_stats", "spatial_stats"])
+    for m in methods:
+        if m not in METHODS:
+            raise ValueError(f"Invalid evaluation method: {m}. Must be one of {list(METHODS)}")
+    return methods
+
+
+def n_samples_of(cfg, gen_type):
+    ev = cfg["evaluation"]
+    return {"multiple": ev.get("batch_size"), "single": 1, "repeated": ev.get("n_repeats")}[gen_type]
+
+
+def evaluation_main(cfg):
+    """returns {unit label: metrics dict}"""
+    ev = cfg["evaluation"]
+    seed = int(ev.get("seed", 0))
+    torch.manual_seed(seed)
+    torch.cuda.manual_seed(seed)
+    np.random.seed(seed)
+    types, methods = eval_gen_types(cfg), eval_stat_methods(cfg)       # both validated before any file is read
+    model_name_str = get_model_string(cfg)
+    log = setup_logger(os.path.join(cfg["paths"]["sample_dir"], "generation", model_name_str, "logs"), name="eval_log")
+    skipped = [k for k in PLOT_KEYS if ev.get(k, False)]
+    if skipped:
+        log.info(f"[INFO] Plotting is not part of this evaluation; skipped: {skipped}")
+    sample_dir = os.path.join(cfg["paths"]["sample_dir"], "generation", model_name_str, "generated_samples")
+    out = {}
+    for gen_type in types:
+        n = n_samples_of(cfg, gen_type)
+        for rank, _ in sample_units(sample_dir, gen_type, n):
+            runner = Evaluation(cfg, generated_sample_type=gen_type, n_samples=n, rank=rank)
+            log.info(f"[INFO] Running evaluation for {runner.label}")
+            for method in methods:
+                log.info(f"[INFO] Running evaluation method: {method}")
+                fn = getattr(runner, METHODS[method])
+                if method in ("pixel_stats", "spatial_stats"):
+                    fn(save_stats=bool(ev.get("save_stats", False)), n_samples=n if n is not None else runner.n_samples)
+                else:
+                    fn()
+            runner.save()
+            out[runner.label] = runner.metrics
+    log.info("[INFO] Evaluation completed for all generated sample types")
+    return out
