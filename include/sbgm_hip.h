@@ -202,7 +202,10 @@ typedef struct sbgm_conv_args {
     int winograd;            /* bit 0: Winograd F(2,3) weights/kernel (3x3/s1/p1; w_packed from sbgm_conv_wino_pack_weight;
                                 tile_px counts 32-pixel fragments: {4,1} {2,2} {2,1} {4,2});
                                 bit 1: LDS-staged kernel (W %% 16 == 0; tile_px = tile rows per wave, 2x that with bit 0);
-                                bit 2 (with bit 1): two LDS stage buffers, one barrier per stage */
+                                bit 2 (with bit 1): two LDS stage buffers, one barrier per stage;
+                                bit 5 (32, alone): 8x8/s2/p3 as a space-to-depth Winograd F(2x2,4x4), LDS-staged (w_packed from
+                                sbgm_conv8x8s2_wino_pack_weight; c_pad %% 16 == 0; tile_co in {1, 2} = 16 / 32 output channels per
+                                workgroup, 0 = 2; tile_px / splits / waves_per_tile ignored; no in_mode, no in_dil) */
     int in_dil;              /* 0/1, or 2: read x through a zero-inserted grid (data gradient of a stride-2 conv) */
     int out_h, out_w;        /* explicit output size (required with in_dil = 2), else 0 */
     float* ws;
@@ -276,6 +279,11 @@ int sbgm_conv_wino_pack_weight(const float* w_oihw, float* packed, int Cout, int
 /* Winograd F(2x2,3x3) weight transform for 3x3 kernels: OIHW -> U[c/16][xi*4+eta][Cout][16], U = G g G^T */
 int64_t sbgm_conv_wino2d_packed_numel(int Cout, int c_pad);
 int sbgm_conv_wino2d_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int c_pad, void* stream);
+/* 8x8 stride-2 pad-3 weight OIHW [Cout][Cin][8][8] -> the space-to-depth F(2x2,4x4) image that sbgm_conv2d_fwd reads with
+ * winograd bit 5: U = G g G^T (in fp64) of every 4x4 phase sub-filter, [4 * c_pad / 16 stages][25][Cout][16].  c_pad %% 16 == 0,
+ * Cout %% 16 == 0. */
+int64_t sbgm_conv8x8s2_wino_packed_numel(int Cout, int c_pad);
+int sbgm_conv8x8s2_wino_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int c_pad, void* stream);
 
 /* ConvTranspose2d(k=2,s=2) = one 1x1 convolution to 4C channels (weights from sbgm_tconv_weight_to_oihw, bias repeated
  * 4x) followed by depth->space; its backward is space->depth followed by the 1x1 convolution's backward. */

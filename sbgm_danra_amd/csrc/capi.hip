@@ -33,6 +33,10 @@ int64_t sbgm_conv_wino2d_packed_numel(int Cout, int c_pad) { return (int64_t)sbg
 int sbgm_conv_wino2d_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int c_pad, void* stream) {
     return sbgm_launch_pack_w2d_weight(w_oihw, packed, Cout, Cin, c_pad, ST);
 }
+int64_t sbgm_conv8x8s2_wino_packed_numel(int Cout, int c_pad) { return (int64_t)sbgm_s2w_packed_floats(Cout, c_pad); }
+int sbgm_conv8x8s2_wino_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int c_pad, void* stream) {
+    return sbgm_launch_pack_s2w_weight(w_oihw, packed, Cout, Cin, c_pad, ST);
+}
 int sbgm_conv_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int KH, int KW, int c_pad, void* stream) {
     return sbgm_launch_pack_conv_weight(w_oihw, packed, Cout, Cin, KH, KW, c_pad, ST);
 }
@@ -47,6 +51,12 @@ int sbgm_conv2d_fwd(const sbgm_conv_args* a, void* stream) {
     p.tbias_after_act = a->tbias_after_act;
     p.in_dil = a->in_dil; p.out_h = a->out_h; p.out_w = a->out_w;
     p.in_mode = a->in_mode; p.in_affine = a->in_affine; p.in_skip = a->in_skip; p.in_act = a->in_act;
+    if (a->winograd & 32) {                  // 8x8/s2/p3 as space-to-depth Winograd F(2x2,4x4) (conv_s2w.hip): weights from sbgm_conv8x8s2_wino_pack_weight
+        SBGM_CHECK((a->winograd & ~32) == 0 && a->in_mode == 0, "conv2d: winograd bit 5 stands alone and takes no in_mode");
+        SBGM_CHECK(a->KH == 8 && a->KW == 8 && a->stride == 2 && a->pad == 3 && a->in_dil <= 1, "conv2d: the F(2x2,4x4) path is 8x8 stride 2 pad 3 only");
+        SBGM_CHECK(a->tile_co == 0 || a->tile_co == 1 || a->tile_co == 2, "conv2d: winograd bit 5 takes tile_co 1 or 2");
+        return sbgm_launch_conv_s2w(p, ConvTile{a->tile_co ? a->tile_co : 2, 1, 1, 1, 3, 1}, ST);
+    }
     SBGM_CHECK(a->in_mode == 0 || (a->winograd & 3) == 3 || (a->winograd & 8), "conv2d: in_mode %d needs an LDS-staged Winograd kernel (winograd bits 0 and 1, or bit 3)", a->in_mode);
     if (a->winograd & 8) {                   // 2-D Winograd F(2x2,3x3), LDS-staged (conv_w2d.hip): weights from sbgm_conv_wino2d_pack_weight
         SBGM_CHECK(a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->in_dil <= 1, "conv2d: the 2-D Winograd path is 3x3 stride 1 pad 1 only");

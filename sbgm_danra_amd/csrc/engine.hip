@@ -40,6 +40,8 @@ struct Param {
     size_t wino_floats = 0;
     float* dev_w2d = nullptr;   // ... and a 2-D Winograd F(2x2,3x3) packed copy (conv_w2d.hip)
     size_t w2d_floats = 0;
+    float* dev_s2w = nullptr;   // 8x8 conv with Cin padded to 16: a space-to-depth F(2x2,4x4) packed copy (conv_s2w.hip)
+    size_t s2w_floats = 0;
     bool filled = false;
 };
 
@@ -52,12 +54,18 @@ struct DecW { ConvW up, conv; Param *n1g, *n1b, *n2g, *n2b, *freq, *tpw, *tpb; A
 // one launch of a tuned tile: picks the kernel family and the weight image it reads
 int launch_tile(const ConvGeom& g, ConvParams p, const ConvTile& ct, float* partial, hipStream_t st) {
     if (ct.wino == 2) { p.wp = p.wp_w2d; return sbgm_launch_conv_w2d(p, ct, st); }
+    if (ct.wino == 3) {
+        SBGM_CHECK(g.kh == 8 && g.kw == 8 && g.stride == 2 && g.pad == 3, "launch_tile: the F(2x2,4x4) kernel is 8x8 stride 2 pad 3 only");
+        p.wp = p.wp_s2w;
+        return sbgm_launch_conv_s2w(p, ct, st);
+    }
     if (!ct.wino && !ct.lds) return sbgm_launch_conv(g, p, ct, partial, st);
     if (ct.wino) p.wp = p.wp_wino;
     return ct.lds ? sbgm_launch_conv_lds(p, ct, st) : sbgm_launch_conv_wino(p, ct, st);
 }
 // GroupNorm statistics the launch above leaves in p.gn_stats (chunks per sample), 0 = none
 int tile_gn_chunks(const ConvParams& p, const ConvTile& ct) {
+    if (ct.wino == 3) return 0;
     return ct.wino == 2 ? sbgm_conv_w2d_gn_chunks(p, ct) : sbgm_conv_lds_gn_chunks(p, ct);
 }
 
@@ -335,7 +343,9 @@ int sbgm_model::build(const sbgm_model_config& c) {
         else p->dev_floats = (size_t)p->numel;
         if (p->wino) p->wino_floats = sbgm_wino_packed_floats(p->cout, p->cs);
         if (p->wino && getenv("SBGM_NO_WINOGRAD2D") == nullptr) p->w2d_floats = sbgm_w2d_packed_floats(p->cout, p->cs);
-        total += align_up(p->dev_floats, 64) + align_up(p->wino_floats, 64) + align_up(p->w2d_floats, 64);
+        if (p->kind == P_CONV && p->kh == 8 && p->kw == 8 && p->cs % 16 == 0 && p->cout % 16 == 0 && getenv("SBGM_NO_WINOGRAD") == nullptr)
+            p->s2w_floats = sbgm_s2w_packed_floats(p->cout, p->cs);
+        total += align_up(p->dev_floats, 64) + align_up(p->wino_floats, 64) + align_up(p->w2d_floats, 64) + align_up(p->s2w_floats, 64);
     }
     // folded BN scale/bias
     size_t bn_floats = 0;
@@ -352,6 +362,7 @@ int sbgm_model::build(const sbgm_model_config& c) {
         if (p->dev_floats) { p->dev = arena + off; off += align_up(p->dev_floats, 64); }
         if (p->wino_floats) { p->dev_wino = arena + off; off += align_up(p->wino_floats, 64); }
         if (p->w2d_floats) { p->dev_w2d = arena + off; off += align_up(p->w2d_floats, 64); }
+        if (p->s2w_floats) { p->dev_s2w = arena + off; off += align_up(p->s2w_floats, 64); }
         if (p->kind == P_IGNORE) p->filled = true;
     }
     auto place_bn = [&](BNW& b, int c_) {
@@ -413,7 +424,13 @@ int sbgm_model::fold_bn(hipStream_t st) {
 //     tile that still gives >= 256 workgroups, the K loop split over 4 or 8 waves;
 //   small problems of any geometry (< 1024 tiles of 32 channels x 16 pixels): that smallest wave tile, K split over the 4 waves of
 //     a workgroup and over up to 8 workgroups;
+//   8x8 stride 2 pad 3 on a 16-channel-padded input (the stem's second convolution) with >= 256 workgroups: space-to-depth Winograd
+//     F(2x2,4x4) (conv_s2w.hip), 32-channel workgroups while they still fill 256 CUs, 16-channel ones below;
 //   everything else (strided, 1x1, the stem): wave tiles that fill ~2 waves per SIMD.
+static bool s2w_ok(const ConvGeom& g, const ConvParams& p) {
+    return p.wp_s2w != nullptr && g.kh == 8 && g.kw == 8 && g.stride == 2 && g.pad == 3 && p.in_dil <= 1 && p.in_mode == 0 &&
+           p.proj_w == nullptr && p.c_real == 0 && p.Cs % 16 == 0 && p.Cout % 16 == 0 && p.out_h == 0 && p.out_w == 0;
+}
 ConvTile sbgm_model::pick_tile(const ConvGeom& g, const ConvParams& p) {
     const int OH = (p.H + 2 * g.pad - g.kh) / g.stride + 1, OW = (p.W + 2 * g.pad - g.kw) / g.stride + 1;
     ConvOpKey key{g.kh, g.kw, g.stride, g.pad, p.B, p.H, p.W, p.Cs, p.Cout, p.proj_w != nullptr, p.in_mode};
@@ -424,6 +441,11 @@ ConvTile sbgm_model::pick_tile(const ConvGeom& g, const ConvParams& p) {
     const bool s1 = g.kh == 3 && g.kw == 3 && g.stride == 1 && g.pad == 1 && p.in_dil <= 1;
     const int M = p.B * OH * OW;
     const int nsteps = sbgm_conv_nsteps(g.kh, g.kw, p.c_real == 2 ? 2 : p.Cs);
+    if (s2w_ok(g, p) && !round1) {
+        const long tiles = (long)p.B * ((OH + 15) / 16) * ((OW + 15) / 16);
+        if (p.Cout % 32 == 0 && tiles * (p.Cout / 32) >= 256) return ConvTile{2, 1, 1, 1, 3, 1};
+        if (tiles * (p.Cout / 16) >= 256) return ConvTile{1, 1, 1, 1, 3, 1};
+    }
     if (lds_ok && s1 && p.W % 16 == 0 && p.H % 2 == 0 && p.Cs % 16 == 0) {
         const long tiles16 = (long)p.B * (p.W / 16) * ((p.H + 15) / 16) * (p.Cout / 16);
         if (p.wp_w2d != nullptr && (tiles16 >= 512 || p.proj_w)) {
@@ -556,6 +578,10 @@ int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, float* partial, size_
                 }
             cands.push_back(ConvTile{fco, 1, 1, 2, 2, 3});       // persistent workgroups, LDS-DMA slab (two per CU)
         }
+    // 8x8 stride 2 pad 3 as space-to-depth Winograd F(2x2,4x4): 16x16-output tiles, 16 or 32 channels per workgroup
+    if (s2w_ok(g, p))
+        for (int fco : {2, 1})
+            if (p.Cout % (16 * fco) == 0) cands.push_back(ConvTile{fco, 1, 1, 1, 3, 1});
     hipEvent_t e0, e1;
     SBGM_HIP(hipEventCreate(&e0));
     SBGM_HIP(hipEventCreate(&e1));
@@ -735,7 +761,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     auto conv_bn = [&](const ConvGeom& g, const float* in, int h, int w, int cs, const ConvW& cw, BNW& bnw, int cout,
                        const float* res, bool relu, const float* tb_after, float* o) -> int {
         ConvParams p{};
-        p.x = in; p.wp = cw.w->dev; p.wp_wino = cw.w->dev_wino; p.wp_w2d = cw.w->dev_w2d; p.B = B; p.H = h; p.W = w; p.Cs = cs; p.Cout = cout;
+        p.x = in; p.wp = cw.w->dev; p.wp_wino = cw.w->dev_wino; p.wp_w2d = cw.w->dev_w2d; p.wp_s2w = cw.w->dev_s2w; p.B = B; p.H = h; p.W = w; p.Cs = cs; p.Cout = cout;
         if (!bn_train) {
             p.out = o; p.scale = bnw.scale; p.bias = bnw.bias; p.res = res; p.act = relu ? SBGM_ACT_RELU : SBGM_ACT_NONE;
             p.tbias = tb_after; p.tbias_after_act = 1;
@@ -1241,6 +1267,7 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
         if (sbgm_launch_pack_conv_weight(src, p->dev, p->cout, p->cin, p->kh, p->kw, p->cs, st)) return 1;
         if (p->wino && sbgm_launch_pack_wino_weight(src, p->dev_wino, p->cout, p->cin, p->cs, st)) return 1;
         if (p->dev_w2d && sbgm_launch_pack_w2d_weight(src, p->dev_w2d, p->cout, p->cin, p->cs, st)) return 1;
+        if (p->dev_s2w && sbgm_launch_pack_s2w_weight(src, p->dev_s2w, p->cout, p->cin, p->cs, st)) return 1;
     } else if (p->kind == P_TCONV) {             // [Cin][Cout][2][2] -> OIHW [4*Cout][Cin][1][1] (scratch) -> packed
         float* tmp = nullptr;
         SBGM_HIP(hipMalloc(&tmp, (size_t)numel * 4));
@@ -1348,7 +1375,8 @@ int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {
 extern "C++" {
 static std::string conv_kernel_name(const sbgm_model::ConvRec& r) {
     char b[96];
-    if (r.t.wino == 2 && r.t.lds == 3) snprintf(b, sizeof b, "conv3x3_w2dp_kernel<%d; %d; %s>", r.t.fco, r.in_mode, r.proj ? "true" : "false");
+    if (r.t.wino == 3) snprintf(b, sizeof b, "conv8x8s2_s2w_kernel<%d>", r.t.fco);
+    else if (r.t.wino == 2 && r.t.lds == 3) snprintf(b, sizeof b, "conv3x3_w2dp_kernel<%d; %d; %s>", r.t.fco, r.in_mode, r.proj ? "true" : "false");
     else if (r.t.wino == 2) snprintf(b, sizeof b, "conv3x3_w2d_kernel<%d; %d; %s; %d>", r.t.fco, r.t.ws == 2 ? 2 : 1, r.t.lds == 2 ? "true" : "false", r.in_mode);
     else if (r.t.lds) snprintf(b, sizeof b, "conv3x3_lds_kernel<%d; %d; %s; %s; %d>", r.t.fco, r.t.fpx, r.t.wino ? "true" : "false", r.t.lds == 2 ? "true" : "false", r.in_mode);
     else if (r.t.wino) snprintf(b, sizeof b, "conv3x3_wino_kernel<%d; %d; %d>", r.t.fco, r.t.fpx, r.t.ws);
@@ -1390,7 +1418,8 @@ int sbgm_model_tune_load(sbgm_model* m, const char* path) {
                              &k.Cs, &k.Cout, &k.proj, &k.in_mode, &t[0], &t[1], &t[2], &t[3], &t[4], &t[5]);
         // the launchers reject tiles they do not instantiate; here only the ranges that index memory are checked
         const bool ok = n == 17 && k.in_mode >= 0 && k.in_mode <= 2 && (t[0] == 1 || t[0] == 2 || t[0] == 4) && (t[1] == 1 || t[1] == 2 || t[1] == 4) && t[2] >= 1 &&
-                        t[2] <= 64 && (t[3] == 1 || t[3] == 2 || t[3] == 4 || t[3] == 8) && t[4] >= 0 && t[4] <= 2 && (t[4] != 2 || t[5] >= 1) && t[5] >= 0 && t[5] <= (t[4] == 2 ? 3 : 2) &&
+                        t[2] <= 64 && (t[3] == 1 || t[3] == 2 || t[3] == 4 || t[3] == 8) && t[4] >= 0 && t[4] <= 3 && (t[4] < 2 || t[5] >= 1) && t[5] >= 0 && t[5] <= (t[4] == 2 ? 3 : 2) &&
+                        (t[4] != 3 || (k.kh == 8 && k.kw == 8 && k.s == 2 && k.p == 3 && t[0] <= 2)) &&
                         k.Cout % (16 * t[0]) == 0;
         if (!ok) {
             fclose(f);
@@ -1437,7 +1466,7 @@ int sbgm_model_profile_forward(sbgm_model* m, const float* x, const float* t, co
         s.n_conv += 1;
         if (r.ms > s.ms_conv_max) { s.ms_conv_max = r.ms; s.flops_conv_max = r.flops; }
         if (f) fprintf(f, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%.2f,%s\n", i, r.g.kh, r.g.kw, r.g.stride, r.B, r.H, r.W,
-                       r.Cs, r.Cout, r.M, r.nsteps, 16 * r.t.fco, r.t.wino == 2 ? 256 : r.t.lds ? 64 * r.t.fpx * (r.t.wino ? 2 : 1) : (r.t.wino ? 32 : 16) * r.t.fpx, r.t.splits, r.t.wino == 2 ? -40 : r.t.lds ? (r.t.wino ? -20 : 20) : (r.t.wino ? -r.t.ws : r.t.ws), r.flops * 1e-9, r.ms,
+                       r.Cs, r.Cout, r.M, r.nsteps, 16 * r.t.fco, r.t.wino >= 2 ? 256 : r.t.lds ? 64 * r.t.fpx * (r.t.wino ? 2 : 1) : (r.t.wino ? 32 : 16) * r.t.fpx, r.t.splits, r.t.wino == 3 ? -25 : r.t.wino == 2 ? -40 : r.t.lds ? (r.t.wino ? -20 : 20) : (r.t.wino ? -r.t.ws : r.t.ws), r.flops * 1e-9, r.ms,
                        r.flops / (r.ms * 1e-3) * 1e-12, conv_kernel_name(r).c_str());
         ++i;
     }

@@ -13,7 +13,8 @@ struct ConvTile {
     int splits;     // split-K over gridDim.y (partials + reduce kernel)
     int ws;         // waves of a workgroup cooperating on one tile (in-workgroup split-K through LDS): 1, 2 or 4
     int wino;       // 1 = 3x3/s1 Winograd F(2,3) kernel (conv_wino.hip): fpx then counts PAIR fragments, weights = wino pack;
-                    // 2 = 2-D Winograd F(2x2,3x3), LDS-staged only (conv_w2d.hip): 16x16-pixel tiles, fpx unused, weights = w2d pack
+                    // 2 = 2-D Winograd F(2x2,3x3), LDS-staged only (conv_w2d.hip): 16x16-pixel tiles, fpx unused, weights = w2d pack;
+                    // 3 = 8x8/s2/p3 as space-to-depth Winograd F(2x2,4x4), LDS-staged (conv_s2w.hip): 16x16-output tiles, weights = s2w pack
     int lds;        // 1 = LDS-staged 3x3/s1 kernel (conv_lds.hip): fpx = tile rows per wave (Winograd: 2*fpx rows)
 };
 struct ConvParams {
@@ -30,6 +31,7 @@ struct ConvParams {
     float* proj_out;      // [9][M] planar tap sums (then `out` is not written)
     const float* wp_wino; // host-side only: Winograd-packed copy of the weights (3x3 stride-1 layers), or null
     const float* wp_w2d;  // host-side only: F(2x2,3x3)-packed copy of the weights (3x3 stride-1 layers), or null
+    const float* wp_s2w;  // host-side only: space-to-depth F(2x2,4x4)-packed copy of the weights (8x8 stride-2 pad-3 layers), or null
     double* gn_stats;     // conv_lds only, or null: per-workgroup GroupNorm partial sums of the OUTPUT (sum, sum of squares per
                           // group) in the [b][chunk][G][2] layout groupnorm_apply reads -> no separate statistics pass
     int gn_groups;        // G of that GroupNorm (channels per group must divide or be a multiple of the tile's channel slice)
@@ -92,6 +94,12 @@ size_t sbgm_conv_w2d_bytes(const ConvTile& cfg, int in_mode);
 int sbgm_conv_w2d_gn_chunks(const ConvParams& p, const ConvTile& cfg);
 // co tiles of a tap-projection launch: each writes its own partial plane [tile][9][M], sbgm_launch_tap_stencil sums `parts` planes
 int sbgm_conv_w2d_proj_parts(const ConvParams& p, const ConvTile& cfg);
+
+// ---- conv_s2w.hip: 8x8 stride-2 pad-3 convolution as a space-to-depth Winograd F(2x2,4x4), LDS-staged (ConvTile.wino == 3) -----
+size_t sbgm_s2w_packed_floats(int Cout, int cs);
+int sbgm_launch_pack_s2w_weight(const float* w_oihw, float* up, int Cout, int Cin, int cs, hipStream_t st);
+int sbgm_launch_conv_s2w(ConvParams p, const ConvTile& cfg, hipStream_t st);    // p.wp = F(2x2,4x4) space-to-depth weights
+size_t sbgm_conv_s2w_bytes(const ConvTile& cfg);
 
 // ---- pointwise.hip ---------------------------------------------------------------------------------
 struct PackSrc {
