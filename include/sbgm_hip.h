@@ -26,7 +26,7 @@ int sbgm_abi_version(void);
 
 enum { SBGM_NONE = 0, SBGM_RELU = 1, SBGM_SILU = 2, SBGM_GELU = 3 };   /* activation codes */
 enum { SBGM_NORM_INSTANCE = 0, SBGM_NORM_GROUP = 1 };
-enum { SBGM_SAMPLER_EM = 0, SBGM_SAMPLER_PC = 1, SBGM_SAMPLER_EDM_HEUN = 2 };
+enum { SBGM_SAMPLER_EM = 0, SBGM_SAMPLER_PC = 1, SBGM_SAMPLER_EDM_HEUN = 2, SBGM_SAMPLER_RK45 = 3 };
 
 /* ------------------------------------------------------------------------------------------------------------
  * Model handle.  Replaces: training_utils.get_model -> Encoder/Decoder/ScoreNet construction
@@ -141,6 +141,27 @@ int sbgm_sampler_run(sbgm_model* m, const sbgm_sampler_args* a, void* stream);
  * eagerly.  Blocking behaviour is that of sbgm_sampler_run. */
 int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
                          float s_tmin, float s_tmax, float s_noise, void* stream);
+
+/* Adaptive deterministic sampler: the probability-flow ODE dx/dt = -1/2 g(t)^2 score(x, t) integrated from t0 to t1 by
+ * Dormand-Prince 5(4) with the step controller of scipy.integrate.RK45 (select_initial_step, FSAL, accept when the RMS error
+ * norm is < 1, factor min(10, 0.9 err^-0.2), max(0.2, .) on rejection), entirely on the device.  a->kind must be
+ * SBGM_SAMPLER_RK45; a->num_steps, a->snr, a->eps and a->cfg_scale_corrector are ignored (with guidance every evaluation uses
+ * cfg_scale); a->bn_train must be 0.  t0 > t1 samples (1 -> eps), t0 < t1 encodes data into the latent; both in [0, 1].
+ *   x0:         start state [B,1,H,W], or NULL: marginal_prob_std(t0) times draw 0 of the run's Philox stream (a->seed; a->noise, when
+ *               given, holds that one draw; tile_origins key it by domain position).
+ *   per_sample: 0 = one controller over all B*H*W values (scipy's semantics); 1 = B independent controllers, each with its own t, h,
+ *               error norm over its H*W values, accept / reject and counters; a finished or failed sample is frozen.  Required with
+ *               tile_origins.
+ *   max_steps:  attempts (accepted + rejected) a controller may use.
+ *   stats_i:    int64 [4 G + 2], G = per_sample ? B : 1: per controller nfev, n_accepted, n_rejected, status (1 finished, 2 step size
+ *               below 10 ulp of t after a rejection, 3 non-finite error norm, 4 max_steps used up), then the surplus attempts (enqueued
+ *               after the run was done; at most 1) and the attempts enqueued.  stats_d: double [G] final t (may be NULL).
+ * A status other than 1 is not a failure of the call (it returns 0); out then holds the state where the controller stopped.
+ * With use_graph one attempt (6 evaluations, their stage kernels, norm, controller, commit) is captured once and replayed on `stream`
+ * until the device reports done; the host reads a 4-byte word in pinned memory and stays at most one attempt ahead of it.  Unlike the
+ * other samplers the call returns only when the run is complete. */
+int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, double t1, double rtol, double atol, int per_sample,
+                         int64_t max_steps, const float* x0, int64_t* stats_i, double* stats_d, void* stream);
 
 /* Conv autotuning: time the tile / split-K candidates of every convolution of the (B,H,W) plan once and keep the
  * fastest.  Synchronises the stream.  Optional; without it a static heuristic is used. */
@@ -494,6 +515,32 @@ int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, ui
 int sbgm_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, float sigma_hat, float sigma_next, int64_t n,
                    void* stream);
 int sbgm_edm_heun(float* x, const float* d, const float* score, float sigma_hat, float sigma_next, int64_t n, void* stream);
+
+/* The pieces of the RK45 solver above, for callers that run the network evaluations themselves (rk45_sampler's Python loop).
+ * `state` is an opaque device block of sbgm_rk45_state_bytes bytes for `groups` controllers (1, or B with per_sample); K holds the seven
+ * fp32 stage scores, slab s at K + s * k_stride (k_stride >= B * per, a multiple of 4); y, y_new are float64 [B * per]; partials is
+ * a float64 scratch of sbgm_rk45_partials_bytes bytes.
+ *   init:    resets the block for a run from t0 to t_bound.     load / store: y = float64(x) / x = fp32(y).
+ *   stage:   writes the network input xs (fp32) and the time vector t_dev[B] of the evaluation that `phase` leads to, whose score the
+ *            caller then puts into slab: phase 7 -> slab 0 (f at t0), 8 -> slab 1 (the probe of the initial step), s = 1..5 -> slab s
+ *            (Runge-Kutta stage s), 6 -> slab 6 (f at y_new, which it also stores).
+ *   control: what = 0 after slab 0, 1 after slab 1 (the two halves of the initial step), 2 after slab 6: error norm and decision.
+ *   commit:  after control 2: moves y_new and slab 6 into place if the attempt was accepted.
+ *   read:    synchronises and returns stats_i [4 groups + 2] (per controller nfev, n_accepted, n_rejected, status; then the done word
+ *            and the attempts that found a controller running) and stats_d [groups] (current t; may be NULL). */
+int64_t sbgm_rk45_state_bytes(int groups);
+int64_t sbgm_rk45_partials_bytes(int B, int64_t per);
+int sbgm_rk45_init(void* state, int groups, double t0, double t_bound, double rtol, double atol, float sigma, int64_t max_steps,
+                   void* stream);
+int sbgm_rk45_load(double* y, const float* x, int64_t n, void* stream);
+int sbgm_rk45_store(float* x, const double* y, int64_t n, void* stream);
+int sbgm_rk45_stage(void* state, int phase, const double* y, double* y_new, const float* K, int64_t k_stride, float* xs, float* t_dev,
+                    int B, int64_t per, int per_sample, void* stream);
+int sbgm_rk45_control(void* state, int what, const double* y, const double* y_new, const float* K, int64_t k_stride, double* partials,
+                      int B, int64_t per, int per_sample, void* stream);
+int sbgm_rk45_commit(const void* state, double* y, const double* y_new, float* K, int64_t k_stride, int B, int64_t per, int per_sample,
+                     void* stream);
+int sbgm_rk45_read(const void* state, int groups, int64_t* stats_i, double* stats_d, void* stream);
 
 /* ---- after the sampler -------------------------------------------------------------------------
  * sbgm_pointwise_chain: y[i] = program(x[i]); the program is at most SBGM_CHAIN_MAX_OPS scalar steps, each rounded to fp32

@@ -16,9 +16,11 @@ LIB_PATH = os.path.join(_HERE, "libsbgm_hip.so")
 
 NONE, RELU, SILU, GELU = 0, 1, 2, 3
 NORM_INSTANCE, NORM_GROUP = 0, 1
-SAMPLER_EM, SAMPLER_PC, SAMPLER_EDM_HEUN = 0, 1, 2
+SAMPLER_EM, SAMPLER_PC, SAMPLER_EDM_HEUN, SAMPLER_RK45 = 0, 1, 2, 3
+ODE_FINISHED, ODE_TOO_SMALL_STEP, ODE_NONFINITE, ODE_MAX_STEPS = 1, 2, 3, 4      # controller status of the RK45 solver
+ODE_PHASE_F0, ODE_PHASE_F1 = 7, 8                                              # sbgm_rk45_stage phases besides stages 1..6
 
-_vp, _i, _f, _i64, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
+_vp, _i, _f, _i64, _u64, _d = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64, C.c_double
 
 
 class ModelConfig(C.Structure):
@@ -79,6 +81,7 @@ SIGNATURES = {
     "sbgm_model_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "sbgm_sampler_run": (_i, [_vp, C.POINTER(SamplerArgs), _vp]),
     "sbgm_sampler_run_edm": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _vp]),
+    "sbgm_sampler_run_ode": (_i, [_vp, C.POINTER(SamplerArgs), _d, _d, _d, _d, _i, _i64, _vp, _vp, _vp, _vp]),
     "sbgm_pointwise_chain": (_i, [_vp, _vp, _i64, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     "sbgm_sample_extremes": (_i, [_vp, _i, _i64, _f, _vp, _vp, _vp]),
     "sbgm_assemble_conditions": (_i, [C.POINTER(AssembleArgs), _vp]),
@@ -173,6 +176,15 @@ SIGNATURES = {
     "sbgm_edm_churn": (_i, [_vp, _vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_edm_euler": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i64, _vp]),
     "sbgm_edm_heun": (_i, [_vp, _vp, _vp, _f, _f, _i64, _vp]),
+    "sbgm_rk45_state_bytes": (_i64, [_i]),
+    "sbgm_rk45_partials_bytes": (_i64, [_i, _i64]),
+    "sbgm_rk45_init": (_i, [_vp, _i, _d, _d, _d, _d, _f, _i64, _vp]),
+    "sbgm_rk45_load": (_i, [_vp, _vp, _i64, _vp]),
+    "sbgm_rk45_store": (_i, [_vp, _vp, _i64, _vp]),
+    "sbgm_rk45_stage": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i, _vp]),
+    "sbgm_rk45_control": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _vp, _i, _i64, _i, _vp]),
+    "sbgm_rk45_commit": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _vp]),
+    "sbgm_rk45_read": (_i, [_vp, _i, _vp, _vp, _vp]),
     "sbgm_error_stats_workspace_bytes": (_i64, [_i, _i64]),
     "sbgm_error_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64] + [_vp] * 8),
     "sbgm_histogram": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, C.c_double, C.c_double, _i, _vp, _vp]),

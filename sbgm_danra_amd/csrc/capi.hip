@@ -390,4 +390,28 @@ int sbgm_edm_heun(float* x, const float* d, const float* score, float sigma_hat,
     return sbgm_launch_edm_heun(x, nullptr, d, score, nullptr, nullptr, &sc, nullptr, 0, 1, (size_t)n, ST);
 }
 
+int64_t sbgm_rk45_state_bytes(int groups) { return (int64_t)sbgm_ode_state_bytes(groups); }
+int64_t sbgm_rk45_partials_bytes(int B, int64_t per) { return (int64_t)sbgm_ode_partials_bytes(B, (size_t)per); }
+int sbgm_rk45_init(void* state, int groups, double t0, double t_bound, double rtol, double atol, float sigma, int64_t max_steps,
+                   void* stream) {
+    return sbgm_launch_ode_init(state, groups, t0, t_bound, rtol, atol, sigma, (long long)max_steps, ST);
+}
+int sbgm_rk45_load(double* y, const float* x, int64_t n, void* stream) { return sbgm_launch_ode_load(y, x, (size_t)n, ST); }
+int sbgm_rk45_store(float* x, const double* y, int64_t n, void* stream) { return sbgm_launch_ode_store(x, y, (size_t)n, ST); }
+int sbgm_rk45_stage(void* state, int phase, const double* y, double* y_new, const float* K, int64_t k_stride, float* xs, float* t_dev,
+                    int B, int64_t per, int per_sample, void* stream) {
+    return sbgm_launch_ode_stage(state, phase, y, y_new, K, (size_t)k_stride, xs, t_dev, 1, B, (size_t)per, per_sample, ST);
+}
+int sbgm_rk45_control(void* state, int what, const double* y, const double* y_new, const float* K, int64_t k_stride, double* partials,
+                      int B, int64_t per, int per_sample, void* stream) {
+    return sbgm_launch_ode_control(state, what, y, y_new, K, (size_t)k_stride, partials, B, (size_t)per, per_sample, ST);
+}
+int sbgm_rk45_commit(const void* state, double* y, const double* y_new, float* K, int64_t k_stride, int B, int64_t per, int per_sample,
+                     void* stream) {
+    return sbgm_launch_ode_commit(state, y, y_new, K, (size_t)k_stride, B, (size_t)per, per_sample, ST);
+}
+int sbgm_rk45_read(const void* state, int groups, int64_t* stats_i, double* stats_d, void* stream) {
+    return sbgm_ode_read_state(state, groups, stats_i, stats_d, ST);
+}
+
 }  // extern "C"

@@ -115,11 +115,13 @@ struct sbgm_model {
     static constexpr int PROF_REPS = 4;
     hipStream_t graph_stream = nullptr;     // private capture stream (the caller's may be the legacy default stream)
     hipEvent_t ev_replayed = nullptr;       // recorded on the caller's stream after a run's last replay of step_exec
+    int* h_done = nullptr;                  // pinned copy of an RK45 run's done word, written by a copy node after each controller
+    hipEvent_t ev_poll[2] = {nullptr, nullptr};   // recorded after attempt k (slot k & 1): the host reads h_done behind them
     // The captured SDE step is kept across sampler calls: capture + instantiation of its ~75 kernel nodes cost ~3 ms, as much as
     // two steps.  Everything a step bakes in is in the key (shapes, sampler kind, caller tensors, scalar arguments, workspace,
     // tile-table generation); what changes between runs lives in device memory (step table, step counter, RNG offset AND seed).
     struct StepGraphKey {
-        int B, H, W, kind, guided, bn_train, domain_w, churn;
+        int B, H, W, kind, guided, bn_train, domain_w, churn, ode_norm;
         const void *y, *cond, *lsm, *topo, *origins, *ws, *table;
         size_t ws_bytes;
         float cfg, cfg_corr, snr_nn;
@@ -136,6 +138,29 @@ struct sbgm_model {
         step_exec = nullptr;
         step_graph = nullptr;
     }
+    // Makes step_exec the captured form of `body` under `key`: reused when the cached graph has that key (and `recapture` is not set),
+    // else `body`, which enqueues on `st`, is recorded on the private stream (`st` points there meanwhile; capture runs nothing).
+    int ensure_step_graph(const StepGraphKey& key, bool recapture, hipStream_t& st, const std::function<int()>& body) {
+        if (step_exec != nullptr && !recapture && std::memcmp(&key, &step_key, sizeof key) == 0) return 0;
+        drop_step_graph();
+        const hipStream_t caller = st;
+        st = graph_stream;
+        int rc = 0;
+        hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+        if (e != hipSuccess) { sbgm_set_error("hipStreamBeginCapture failed: %s", hipGetErrorString(e)); rc = 2; }
+        if (rc == 0) {
+            rc = body();
+            e = hipStreamEndCapture(st, &step_graph);
+            if (rc == 0 && (e != hipSuccess || hipGraphInstantiate(&step_exec, step_graph, nullptr, nullptr, 0) != hipSuccess)) {
+                sbgm_set_error("hipGraph capture/instantiate failed: %s", hipGetErrorString(e));
+                rc = 2;
+            }
+            if (rc) drop_step_graph();
+            else step_key = key;
+        }
+        st = caller;
+        return rc;
+    }
 
     ~sbgm_model() {
         drop_step_graph();
@@ -147,6 +172,8 @@ struct sbgm_model {
         if (ev_stage) (void)hipEventDestroy(ev_stage);
         if (graph_stream) (void)hipStreamDestroy(graph_stream);
         if (ev_replayed) (void)hipEventDestroy(ev_replayed);
+        if (h_done) (void)hipHostFree(h_done);
+        for (hipEvent_t e : ev_poll) if (e) (void)hipEventDestroy(e);
     }
 
     Param* add(const std::string& name, ParamKind kind, int64_t numel) {
@@ -210,7 +237,10 @@ struct sbgm_model {
     size_t fwd_need(int B, int H, int W, int bn_train = 0) const;
     // persistent sampler slabs: x, score, x_mean (+ the Heun derivative d for SBGM_SAMPLER_EDM_HEUN), then time vector, norm partials.
     // Evaluations and autotuning reserve the three slabs of EM / PC, so that such a sampler finds its workspace settled.
-    static int sampler_slabs(int kind) { return kind == SBGM_SAMPLER_EDM_HEUN ? 4 : 3; }
+    // SBGM_SAMPLER_RK45: network input, the 2B score of a guided evaluation, seven stage scores, y and y_new in float64 (two slabs
+    // each), one slab for the state block and the norm partials.
+    static constexpr int ODE_SLABS = 14;
+    static int sampler_slabs(int kind) { return kind == SBGM_SAMPLER_RK45 ? ODE_SLABS : kind == SBGM_SAMPLER_EDM_HEUN ? 4 : 3; }
     size_t sampler_keep(int B, int H, int W, int slabs) const {
         const size_t n = (size_t)B * H * W;
         return align_up(n * 4, 256) * slabs + align_up((size_t)B * 4, 256) + align_up((size_t)B * 8, 256);
@@ -237,6 +267,8 @@ struct sbgm_model {
     }
     struct EdmArgs { float sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise; };
     int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr);
+    struct OdeArgs { double t0, t1, rtol, atol; int per_sample; long long max_steps; const float* x0; int64_t* stats_i; double* stats_d; };
+    int sampler_ode(const sbgm_sampler_args& a, hipStream_t st, const OdeArgs& o);
 };
 
 int sbgm_model::build(const sbgm_model_config& c) {
@@ -1193,23 +1225,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         key.domain_w = a.domain_w; key.y = conds.y; key.cond = conds.cond; key.lsm = conds.lsm; key.topo = conds.topo;
         key.origins = a.tile_origins; key.ws = ws; key.table = d_table; key.ws_bytes = saved_ws; key.cfg = a.cfg_scale;
         key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn; key.plan_gen = plan_gen;
-        if (step_exec == nullptr || guided || std::memcmp(&key, &step_key, sizeof key) != 0) {
-            drop_step_graph();
-            st = graph_stream;                                // capture records, it runs nothing
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e != hipSuccess) { sbgm_set_error("hipStreamBeginCapture failed: %s", hipGetErrorString(e)); rc = 2; }
-            if (rc == 0) {
-                rc = step(false, false);
-                e = hipStreamEndCapture(st, &step_graph);
-                if (rc == 0 && (e != hipSuccess || hipGraphInstantiate(&step_exec, step_graph, nullptr, nullptr, 0) != hipSuccess)) {
-                    sbgm_set_error("hipGraph capture/instantiate failed: %s", hipGetErrorString(e));
-                    rc = 2;
-                }
-                if (rc) drop_step_graph();
-                else step_key = key;
-            }
-            st = caller;
-        }
+        rc = ensure_step_graph(key, guided, st, [&] { return step(false, false); });
         for (int i = 0; i < N - tail && rc == 0; ++i)
             if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
         if (step_exec && hipEventRecord(ev_replayed, st) != hipSuccess && !rc) { sbgm_set_error("hipEventRecord failed"); rc = 2; }
@@ -1221,6 +1237,145 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     ws_bytes = saved_ws;
     if (rc) return rc;
     if (!tail) SBGM_HIP(hipMemcpyAsync(a.out, xmean, n * 4, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// rk45_sampler: the adaptive probability-flow ODE solver (ode.hip).  The fourth kind of the driver above shares its workspace rule,
+// its condition handling and its cached step graph; what differs is the loop: its length is decided on the device.  One ATTEMPT is
+// captured (six stage kernels with their evaluations, the norm, the controller, a 4-byte copy of the done word to pinned memory, the
+// commit): a linear chain that depends on nothing that changes between attempts or runs, because t, h, tolerances, flags and counters
+// live in the device state block.  The host replays it on the caller's stream and stays at most one attempt ahead of the done word it
+// waits for, so the device does not idle on the poll; an attempt that runs after done finds every controller frozen and changes
+// nothing.
+int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, const OdeArgs& o) {
+    SBGM_CHECK(a.kind == SBGM_SAMPLER_RK45, "sampler_ode: kind %d is not SBGM_SAMPLER_RK45", a.kind);
+    SBGM_CHECK(a.out != nullptr && o.stats_i != nullptr, "sampler_ode: out and stats_i are required");
+    SBGM_CHECK(!a.bn_train, "sampler_ode: serves eval-mode BatchNorm only (bn_train must be 0)");
+    SBGM_CHECK(o.rtol > 0 && o.atol >= 0 && o.max_steps >= 1, "sampler_ode: need rtol > 0, atol >= 0, max_steps >= 1");
+    SBGM_CHECK(o.t0 != o.t1 && std::min(o.t0, o.t1) >= 0.0 && std::max(o.t0, o.t1) <= 1.0, "sampler_ode: t_span (%g, %g) must be two "
+               "different times in [0, 1]", o.t0, o.t1);
+    SBGM_CHECK(!(a.tile_origins && !o.per_sample), "sampler_ode: tiles need one controller per sample (a shared step would couple them)");
+    const int B = a.B, H = a.H, W = a.W;
+    const bool guided = a.cfg_enabled != 0;
+    const int BE = guided ? 2 * B : B;
+    const size_t per = (size_t)H * W, n = (size_t)B * per;
+    const int G = o.per_sample ? B : 1;
+    if (prepare_ws(BE, H, W, 0, caller, ODE_SLABS)) return 1;
+    const bool graphed = a.use_graph != 0;
+    if (graphed && !graph_stream) {
+        SBGM_HIP(hipStreamCreateWithFlags(&graph_stream, hipStreamNonBlocking));
+        SBGM_HIP(hipEventCreateWithFlags(&ev_replayed, hipEventDisableTiming));
+    }
+    if (!h_done) {
+        SBGM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_done), 64, hipHostMallocDefault));
+        for (hipEvent_t& e : ev_poll) SBGM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    hipStream_t st = caller;
+
+    // workspace: 14 slabs at the top (xs | score2 | K[0..6] | y, y | y_new, y_new | state + partials), then the time vector
+    const size_t keep = sampler_keep(BE, H, W, ODE_SLABS);
+    const size_t slab = align_up((size_t)BE * per * 4, 256);
+    char* top = ws + ws_bytes - keep;
+    float* xs = reinterpret_cast<float*>(top);
+    float* score2 = reinterpret_cast<float*>(top + slab);
+    float* K = reinterpret_cast<float*>(top + 2 * slab);
+    const size_t ks = slab / 4;
+    double* y = reinterpret_cast<double*>(top + 9 * slab);
+    double* y_new = reinterpret_cast<double*>(top + 11 * slab);
+    char* state = top + 13 * slab;
+    const size_t state_bytes = align_up(sbgm_ode_state_bytes(G), 256);
+    double* partials = reinterpret_cast<double*>(state + state_bytes);
+    SBGM_CHECK(state_bytes + sbgm_ode_partials_bytes(B, per) <= slab, "sampler_ode: %d x %d samples are too small for the solver's state slab", H, W);
+    float* t_dev = reinterpret_cast<float*>(top + ODE_SLABS * slab);
+    const size_t fwd_bytes = ws_bytes - keep;
+    if (bn_dirty && fold_bn(st)) return 1;
+    SamplerConds conds(a, st);
+    if (guided && conds.add_unconditional(a, cfg)) return 1;
+
+    // start: the caller's state, or marginal_prob_std(t0) * draw 0 of the run's Philox stream (domain-keyed on tiles)
+    if (sbgm_launch_ode_init(state, G, o.t0, o.t1, o.rtol, o.atol, cfg.sigma, o.max_steps, st)) return 1;
+    if (o.x0) {
+        if (sbgm_launch_ode_load(y, o.x0, n, st)) return 1;
+    } else {
+        NoiseMap nm{};
+        if (a.tile_origins) {
+            SBGM_CHECK(W % 4 == 0 && a.domain_w >= W, "sampler_ode: tiled noise needs W %% 4 == 0 and domain_w >= W (W=%d, domain_w=%d)", W,
+                       a.domain_w);
+            nm = NoiseMap{a.tile_origins, H, W / 4, (a.domain_w + 3) / 4};
+        }
+        const float ls = logf(cfg.sigma), t0f = (float)o.t0;
+        const float std0 = fmaxf(sqrtf((expf((2.f * t0f) * ls) - 1.f) / (2.f * ls)), 1e-5f);
+        if (sbgm_launch_init_noise(xs, std0, a.noise, a.seed, nullptr, 0, n, st, nm)) return 1;
+        if (sbgm_launch_ode_load(y, xs, n, st)) return 1;
+    }
+
+    auto evaluate = [&](float* dst) -> int {
+        if (guided) SBGM_HIP(hipMemcpyAsync(xs + n, xs, n * 4, hipMemcpyDeviceToDevice, st));
+        if (forward(xs, t_dev, conds.y, conds.cond, conds.lsm, conds.topo, guided ? score2 : dst, nullptr, BE, H, W, 0, st)) return 1;
+        return guided ? sbgm_launch_cfg_combine(dst, score2, score2 + n, a.cfg_scale, n, st) : 0;
+    };
+    auto stage = [&](int phase) -> int {
+        return sbgm_launch_ode_stage(state, phase, y, y_new, K, ks, xs, t_dev, guided ? 2 : 1, B, per, o.per_sample, st);
+    };
+    auto control = [&](int what) -> int {
+        if (sbgm_launch_ode_control(state, what, y, y_new, K, ks, partials, B, per, o.per_sample, st)) return 1;
+        SBGM_HIP(hipMemcpyAsync(h_done, state + offsetof(OdeHeader, done), 4, hipMemcpyDeviceToHost, st));
+        return 0;
+    };
+    auto attempt = [&]() -> int {
+        for (int s = 1; s <= 6; ++s)
+            if (stage(s) || evaluate(K + (size_t)s * ks)) return 1;
+        if (control(2)) return 1;
+        return sbgm_launch_ode_commit(state, y, y_new, K, ks, B, per, o.per_sample, st);
+    };
+
+    const size_t saved_ws = ws_bytes;
+    ws_bytes = fwd_bytes;            // forward() must not touch the solver's slabs
+    int rc = 0;
+    long long enqueued = 0;
+    // select_initial_step: f0, the two norms, f1 at t0 + h0, the third norm; then the first attempt is prepared
+    rc = stage(SBGM_ODE_PHASE_F0) || evaluate(K) || control(0) || stage(SBGM_ODE_PHASE_F1) || evaluate(K + ks) || control(1);
+    if (rc == 0 && (hipEventRecord(ev_poll[0], st) != hipSuccess || hipEventSynchronize(ev_poll[0]) != hipSuccess)) {
+        sbgm_set_error("sampler_ode: waiting for the initial step failed: %s", hipGetErrorString(hipGetLastError()));
+        rc = 2;
+    }
+    volatile int* done = h_done;
+    if (rc == 0 && !*done) {
+        if (graphed) {
+            StepGraphKey key{};
+            key.B = B; key.H = H; key.W = W; key.kind = a.kind; key.guided = guided; key.ode_norm = o.per_sample;
+            key.y = conds.y; key.cond = conds.cond; key.lsm = conds.lsm; key.topo = conds.topo; key.ws = ws; key.ws_bytes = saved_ws;
+            key.cfg = a.cfg_scale; key.plan_gen = plan_gen;
+            rc = ensure_step_graph(key, guided, st, attempt);
+        }
+        auto launch = [&]() -> int {
+            if (graphed) {
+                if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at attempt %lld", enqueued); return 2; }
+            } else if (attempt()) {
+                return 1;
+            }
+            if (hipEventRecord(ev_poll[enqueued & 1], st) != hipSuccess) { sbgm_set_error("hipEventRecord failed"); return 2; }
+            ++enqueued;
+            return 0;
+        };
+        // every controller stops within max_steps attempts, so max_steps + 1 enqueued attempts always reach done
+        const long long cap = o.max_steps + 1;
+        for (long long k = 0; rc == 0; ++k) {                    // k: the attempt whose done word the host waits for
+            while (rc == 0 && enqueued <= k + 1 && enqueued < cap) rc = launch();     // at most one attempt ahead of it
+            if (rc) break;
+            if (hipEventSynchronize(ev_poll[k & 1]) != hipSuccess) { sbgm_set_error("sampler_ode: waiting for attempt %lld failed", k); rc = 2; }
+            if (rc || *done) break;
+            if (k + 1 >= cap) { sbgm_set_error("sampler_ode: %lld attempts did not finish the run", cap); rc = 2; }
+        }
+        if (graphed && step_exec && hipEventRecord(ev_replayed, st) != hipSuccess && !rc) { sbgm_set_error("hipEventRecord failed"); rc = 2; }
+    }
+    if (graphed && guided) drop_step_graph();          // its condition copies are freed when this call returns
+    ws_bytes = saved_ws;
+    if (rc) return rc;
+    if (sbgm_launch_ode_store(a.out, y, n, st)) return 1;
+    if (sbgm_ode_read_state(state, G, o.stats_i, o.stats_d, st)) return 1;       // synchronises: the run is complete on return
+    o.stats_i[4 * G] = enqueued - o.stats_i[4 * G + 1];                            // surplus attempts: enqueued, found nothing to do
+    o.stats_i[4 * G + 1] = enqueued;
     return 0;
 }
 
@@ -1325,6 +1480,13 @@ int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_
                sigma_min, sigma_max);
     const sbgm_model::EdmArgs e{sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise};
     return m->sampler(*a, (hipStream_t)stream, &e);
+}
+
+int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, double t1, double rtol, double atol, int per_sample,
+                         int64_t max_steps, const float* x0, int64_t* stats_i, double* stats_d, void* stream) {
+    SBGM_CHECK(a, "sampler_run_ode: null args");
+    const sbgm_model::OdeArgs o{t0, t1, rtol, atol, per_sample != 0, (long long)max_steps, x0, stats_i, stats_d};
+    return m->sampler_ode(*a, (hipStream_t)stream, o);
 }
 
 // One evaluation of the (B, H, W) plan on zero inputs placed at the top of the workspace.  tune = true: every convolution times its tile

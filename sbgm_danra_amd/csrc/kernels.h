@@ -259,6 +259,45 @@ int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, floa
 int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* score, const EdmStep* table, SamplerState* state,
                          const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st);
 
+// ---- ode.hip (rk45_sampler: Dormand-Prince 5(4) with scipy's step controller, on the device) -----------------------------------
+enum { SBGM_ODE_RUNNING = 0, SBGM_ODE_FINISHED = 1, SBGM_ODE_TOO_SMALL_STEP = 2, SBGM_ODE_NONFINITE = 3, SBGM_ODE_MAX_STEPS = 4 };
+enum { SBGM_ODE_PHASE_F0 = 7, SBGM_ODE_PHASE_F1 = 8 };     // stage phases besides the Runge-Kutta stages 1..6
+struct OdeHeader {         // head of the device state block of a run; `groups` OdeGroup follow it
+    double t0, t_bound, rtol, atol, dir;
+    long long max_steps;   // attempts (accepted + rejected) a controller may use
+    long long live_attempts;   // attempts during which at least one controller was still running
+    float sigma;
+    int groups;            // controllers: 1 (error_norm = batch) or B (error_norm = sample)
+    int done;              // 1 once no controller is running; the host polls a copy of this word
+    int pad_;
+};
+struct OdeGroup {          // one step controller
+    double t, h_abs, h, t_new;     // current time, |step| to try next, signed step and end time of the attempt in flight
+    double h0, d1;                 // select_initial_step carry-over
+    double c[7];                   // f_s = c[s] * K[s]: the float64 coefficient of each fp32 score slab
+    long long nfev, n_accepted, n_rejected;
+    int status;            // SBGM_ODE_*
+    int rejected;          // a rejection has occurred within the current step
+    int accept;            // the last attempt was accepted: the commit kernel moves y_new, K[6] into place
+    int pad_;
+};
+int sbgm_ode_blocks_per_sample(size_t per);
+size_t sbgm_ode_state_bytes(int groups);
+size_t sbgm_ode_partials_bytes(int B, size_t per);
+int sbgm_launch_ode_init(void* state, int groups, double t0, double t_bound, double rtol, double atol, float sigma,
+                         long long max_steps, hipStream_t st);
+int sbgm_launch_ode_load(double* y, const float* x, size_t n, hipStream_t st);       // y = float64(x)
+int sbgm_launch_ode_store(float* x, const double* y, size_t n, hipStream_t st);      // x = fp32(y)
+// network input xs, evaluation time(s) t_dev[r * B + b] (r < t_copies) and the coefficient of the evaluation `phase` leads to
+int sbgm_launch_ode_stage(void* state, int phase, const double* y, double* y_new, const float* K, size_t k_stride, float* xs,
+                          float* t_dev, int t_copies, int B, size_t per, int per_sample, hipStream_t st);
+// norm partials + the one-block controller; what = 0 / 1: the two halves of select_initial_step, 2: an attempt's decision
+int sbgm_launch_ode_control(void* state, int what, const double* y, const double* y_new, const float* K, size_t k_stride,
+                            double* partials, int B, size_t per, int per_sample, hipStream_t st);
+int sbgm_launch_ode_commit(const void* state, double* y, const double* y_new, float* K, size_t k_stride, int B, size_t per,
+                           int per_sample, hipStream_t st);
+int sbgm_ode_read_state(const void* state, int groups, int64_t* stats_i, double* stats_d, hipStream_t st);
+
 // ---- dsm_loss.hip (the loss around the network) -----------------------------------------------------------------------
 int sbgm_dsm_nblk(int64_t per_sample);
 int sbgm_launch_dsm_perturb(const float* x, const float* z_in, const float* t_in, const unsigned long long* rng,

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import parallel
-from ..score_sampling import edm_heun_sampler, edm_sampler_kwargs, pc_sampler
+from ..score_sampling import edm_heun_sampler, edm_sampler_kwargs, ode_sampler_kwargs, pc_sampler, rk45_sampler
 from ..score_unet import diffusion_coeff_fn, marginal_prob_std_fn
 from ..utils import extract_samples, get_model_string
 
@@ -41,12 +41,17 @@ class SampleGenerator:
     def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond):
         """the sampler output as [B,H,W] still on the device (what _run_sampler returns after .cpu()).  pc_sampler, as in the
         reference, unless cfg.sampler.sampler_type is "edm_heun_sampler": then n_timesteps is its Heun step count N (2N-1
-        network evaluations; 18-64 is the intended range) and the optional `edm:` section sets the sigma ladder."""
+        network evaluations; 18-64 is the intended range) and the optional `edm:` section sets the sigma ladder; or "rk45_sampler":
+        the adaptive ODE solver, which ignores n_timesteps and reads its tolerances from the optional `ode:` section."""
         if self.cfg["sampler"].get("sampler_type") == "edm_heun_sampler":
             gen = edm_heun_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                                    batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,
                                    img_size=self.cfg["highres"]["data_size"][0], y=y, cond_img=cond_img, lsm_cond=lsm_cond,
                                    topo_cond=topo_cond, **edm_sampler_kwargs(self.cfg))
+        elif self.cfg["sampler"].get("sampler_type") == "rk45_sampler":
+            gen = rk45_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
+                               batch_size=batch_size, device=self.device, img_size=self.cfg["highres"]["data_size"][0], y=y,
+                               cond_img=cond_img, lsm_cond=lsm_cond, topo_cond=topo_cond, **ode_sampler_kwargs(self.cfg))
         else:
             gen = pc_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                              batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,

@@ -15,6 +15,9 @@ Deviation kept explicit: the reference's Euler-Maruyama sampler ignores `img_siz
 
 Beyond the reference: `edm_heun_sampler`, a deterministic few-step Heun solver of the probability-flow ODE on the Karras
 sigma ladder (Karras et al. 2022, Alg. 2) for the same VE-trained network; `edm_heun_schedule` is its one host definition.
+`rk45_sampler`, the adaptive probability-flow ODE solver on the device (Dormand-Prince 5(4) with scipy's RK45 step controller):
+conditioned, guided, tileable, in both directions of the flow, with one controller per batch or per sample; `rk45_host_solve` is
+its definition in numpy.
 """
 from __future__ import annotations
 
@@ -92,6 +95,8 @@ def _counts(kind, num_steps, churn=False):
     evaluation of an SDE step (PC: corrector and predictor), or one per EDM Heun step with churn"""
     if kind == N.SAMPLER_EDM_HEUN:
         return 2, 1 + (int(num_steps) if churn else 0)
+    if kind == N.SAMPLER_RK45:                                # six evaluations per attempt; the only draw is the start
+        return 6, 1
     per_step = 2 if kind == N.SAMPLER_PC else 1
     return per_step, 1 + int(num_steps) * per_step
 
@@ -346,3 +351,306 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
             s2 = N.f32c(_score(score_model, cfg, xp, ones * float(np.float32(sch["t_next"][i])), y, cond_img, lsm_cond, topo_cond))
             N.check(lib.sbgm_edm_heun(x.data_ptr(), d.data_ptr(), s2.data_ptr(), sh, sn, n, st()))
     return out
+
+
+# ---- rk45_sampler: Dormand-Prince 5(4) with the step controller of scipy.integrate.RK45 -------------------------------------------
+_RK_C = np.array([0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1])
+_RK_A = np.array([[0, 0, 0, 0, 0], [1 / 5, 0, 0, 0, 0], [3 / 40, 9 / 40, 0, 0, 0], [44 / 45, -56 / 15, 32 / 9, 0, 0],
+                  [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729, 0],
+                  [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656]])
+_RK_B = np.array([35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84])
+_RK_E = np.array([-71 / 57600, 0, 71 / 16695, -71 / 1920, 17253 / 339200, -22 / 525, 1 / 40])
+_RK_SAFETY, _RK_MIN_FACTOR, _RK_MAX_FACTOR = 0.9, 0.2, 10.0
+_ODE_FAILURES = {N.ODE_TOO_SMALL_STEP: "the step size fell below the minimal step (10 ulp of t) after a rejection",
+                 N.ODE_NONFINITE: "non-finite error norm (the right-hand side returned NaN or inf)",
+                 N.ODE_MAX_STEPS: "the step budget (max_steps={max_steps}) was used up before t reached the end of t_span"}
+
+
+class OdeSolverError(RuntimeError):
+    """the adaptive solver stopped before the end of its time span; the message names the cause"""
+
+
+def _rms(x):
+    return np.linalg.norm(x) / x.size ** 0.5
+
+
+def _check_tolerances(rtol, atol, error_norm, max_steps):
+    if error_norm not in ("batch", "sample"):
+        raise ValueError(f"rk45: error_norm={error_norm!r} must be 'batch' or 'sample'")
+    if not rtol > 0:
+        raise ValueError(f"rk45: rtol={rtol} must be > 0")
+    if not atol >= 0:
+        raise ValueError(f"rk45: atol={atol} must be >= 0")
+    if not int(max_steps) >= 1:
+        raise ValueError(f"rk45: max_steps={max_steps} must be >= 1")
+
+
+def rk45_host_solve(f, t0, t_bound, y0, rtol, atol, error_norm="batch", batch=None, max_steps=10000):
+    """The solver of `rk45_sampler`, restated in numpy: Dormand-Prince 5(4) with FSAL, `select_initial_step` and the step
+    controller of scipy.integrate.RK45 (scipy 1.15), float64 throughout.  The stage sums are the same `np.dot` expressions as
+    scipy's, so for `error_norm="batch"` the endpoint and the evaluation count equal `solve_ivp(f, (t0, t_bound), y0,
+    method="RK45", rtol=rtol, atol=atol)` (rtol is not raised to 100 eps here; rtol <= 0 is an error).
+
+    error_norm="batch": `y0` is one vector, `f(t, y)` with a float `t`; one controller, scipy's semantics.
+    error_norm="sample": `y0` is [batch, m] (or flat, with `batch` given) and `f(t, y)` takes t [batch] and y [batch, m], row b being
+    a function of (t[b], y[b]) alone.  Every row has its own controller (t, h, error norm over its m values, initial step, accept /
+    reject, counters); a finished row is frozen: `f` still sees it, at its final (t, y), and the result is ignored.
+
+    Returns (y, stats); stats holds nfev, n_accepted, n_rejected and t_final (ints / a float, or arrays of `batch` in sample mode).
+    Raises OdeSolverError, naming the cause, on a non-finite error norm (at once), when a controller has used `max_steps` attempts,
+    or when the step falls below 10 ulp of t after a rejection."""
+    _check_tolerances(rtol, atol, error_norm, max_steps)
+    per_sample = error_norm == "sample"
+    y0 = np.asarray(y0, dtype=np.float64)
+    shape = y0.shape
+    if per_sample:
+        G = int(batch) if batch is not None else int(shape[0])
+        ys = [np.ascontiguousarray(r) for r in y0.reshape(G, -1)]
+    else:
+        G = 1
+        ys = [y0.reshape(-1).copy()]
+    t0, t_bound = float(t0), float(t_bound)
+    if t0 == t_bound:
+        raise ValueError("rk45: t0 and t_bound must differ")
+    direction = float(np.sign(t_bound - t0))
+    m = ys[0].size
+    ts = [t0] * G
+
+    def call(tt, yy):                                  # one evaluation of every row, frozen ones included
+        if per_sample:
+            return list(np.asarray(f(np.asarray(tt, dtype=np.float64), np.stack(yy)), dtype=np.float64).reshape(G, m))
+        return [np.asarray(f(tt[0], yy[0]), dtype=np.float64).reshape(m)]
+
+    def fail(code, g):
+        who = f" (sample {g})" if per_sample else ""
+        raise OdeSolverError("rk45" + who + ": " + _ODE_FAILURES[code].format(max_steps=max_steps))
+
+    def finite(v, g):
+        if not np.isfinite(v):
+            fail(N.ODE_NONFINITE, g)
+
+    # ---- select_initial_step (order 4) --------------------------------------------------------------------------------------------
+    K = [np.empty((7, m)) for _ in range(G)]
+    fs = call(ts, ys)
+    nfev = np.full(G, 2, dtype=np.int64)
+    h0s, d1s, scales = [0.0] * G, [0.0] * G, [None] * G
+    interval = abs(t_bound - t0)
+    for g in range(G):
+        scales[g] = atol + np.abs(ys[g]) * rtol
+        d0, d1 = _rms(ys[g] / scales[g]), _rms(fs[g] / scales[g])
+        finite(d0, g), finite(d1, g)
+        h0s[g] = min(1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1, interval)
+        d1s[g] = d1
+    f1s = call([t0 + h0s[g] * direction for g in range(G)], [ys[g] + h0s[g] * direction * fs[g] for g in range(G)])
+    h_abs = [0.0] * G
+    for g in range(G):
+        d2 = _rms((f1s[g] - fs[g]) / scales[g]) / h0s[g]
+        finite(d2, g)
+        h1 = max(1e-6, h0s[g] * 1e-3) if d1s[g] <= 1e-15 and d2 <= 1e-15 else (0.01 / max(d1s[g], d2)) ** (1 / 5)
+        h_abs[g] = min(100 * h0s[g], h1, interval)
+    # ---- the attempts -------------------------------------------------------------------------------------------------------------
+    running = [True] * G
+    rejected = [False] * G
+    n_acc, n_rej = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
+    hs, t_news = [0.0] * G, [0.0] * G
+    while any(running):
+        live = [g for g in range(G) if running[g]]
+        for g in live:
+            t = ts[g]
+            min_step = 10 * np.abs(np.nextafter(t, direction * np.inf) - t)
+            if not rejected[g]:
+                h_abs[g] = max(h_abs[g], min_step)
+            elif h_abs[g] < min_step:
+                fail(N.ODE_TOO_SMALL_STEP, g)
+            h = h_abs[g] * direction
+            t_new = t + h
+            if direction * (t_new - t_bound) > 0:
+                t_new = t_bound
+            hs[g], t_news[g] = t_new - t, t_new
+            h_abs[g] = np.abs(hs[g])
+            K[g][0] = fs[g]
+        y_new = list(ys)
+        for s in range(1, 7):
+            tt, yy = list(ts), list(ys)
+            for g in live:
+                if s < 6:
+                    yy[g] = ys[g] + np.dot(K[g][:s].T, _RK_A[s, :s]) * hs[g]
+                    tt[g] = ts[g] + _RK_C[s] * hs[g]
+                else:
+                    yy[g] = y_new[g] = ys[g] + hs[g] * np.dot(K[g][:-1].T, _RK_B)
+                    tt[g] = ts[g] + hs[g]
+            out = call(tt, yy)
+            for g in live:
+                K[g][s] = out[g]
+        for g in live:
+            nfev[g] += 6
+            scale = atol + np.maximum(np.abs(ys[g]), np.abs(y_new[g])) * rtol
+            err = _rms(np.dot(K[g].T, _RK_E) * hs[g] / scale)
+            finite(err, g)
+            if err < 1:
+                factor = _RK_MAX_FACTOR if err == 0 else min(_RK_MAX_FACTOR, _RK_SAFETY * err ** -0.2)
+                if rejected[g]:
+                    factor = min(1, factor)
+                h_abs[g] *= factor
+                ts[g] = t_news[g]
+                ys[g], fs[g] = y_new[g], K[g][6].copy()
+                rejected[g] = False
+                n_acc[g] += 1
+                if direction * (ts[g] - t_bound) >= 0:
+                    running[g] = False
+            else:
+                h_abs[g] *= max(_RK_MIN_FACTOR, _RK_SAFETY * err ** -0.2)
+                rejected[g] = True
+                n_rej[g] += 1
+            if running[g] and n_acc[g] + n_rej[g] >= int(max_steps):
+                fail(N.ODE_MAX_STEPS, g)
+    if per_sample:
+        return np.stack(ys).reshape(shape), {"nfev": nfev, "n_accepted": n_acc, "n_rejected": n_rej, "t_final": np.asarray(ts)}
+    return ys[0].reshape(shape), {"nfev": int(nfev[0]), "n_accepted": int(n_acc[0]), "n_rejected": int(n_rej[0]), "t_final": ts[0]}
+
+
+def ode_sampler_kwargs(cfg) -> dict:
+    """keyword arguments of `rk45_sampler` from the optional `ode:` section of a config (rtol, atol, error_norm, max_steps); a
+    missing section or key keeps the sampler's default.  `sampler.sampler_type: rk45_sampler` selects the sampler; `n_timesteps`
+    is not read by it (the tolerances decide the number of steps)."""
+    sec = (cfg or {}).get("ode") or {}
+    kw = {k: float(sec[k]) for k in ("rtol", "atol") if sec.get(k) is not None}
+    if sec.get("error_norm") is not None:
+        kw["error_norm"] = str(sec["error_norm"])
+    if sec.get("max_steps") is not None:
+        kw["max_steps"] = int(sec["max_steps"])
+    return kw
+
+
+def _ode_stats(raw_i, raw_d, G, per_sample, max_steps, surplus):
+    """statistics dict of a run from the solver's read-back; raises OdeSolverError when a controller did not finish"""
+    grp = raw_i[:4 * G].reshape(G, 4)
+    for g in range(G):
+        code = int(grp[g, 3])
+        if code != N.ODE_FINISHED:
+            who = f" (sample {g})" if per_sample else ""
+            why = _ODE_FAILURES.get(code, f"controller status {code}").format(max_steps=max_steps)
+            raise OdeSolverError(f"rk45_sampler{who}: {why}; stopped at t = {raw_d[g]:.6g} after {int(grp[g, 1])} accepted and "
+                                 f"{int(grp[g, 2])} rejected steps")
+    one = (lambda a: a.copy()) if per_sample else (lambda a: a[0].item())
+    return {"nfev": one(grp[:, 0]), "n_accepted": one(grp[:, 1]), "n_rejected": one(grp[:, 2]), "t_final": one(raw_d[:G]),
+            "surplus_attempts": int(surplus)}
+
+
+def rk45_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, device="cuda", eps=1e-3, img_size=64, y=None,
+                 cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, rtol=1e-5, atol=1e-5, error_norm="batch", t_span=None,
+                 z=None, noise=None, seed=None, use_graph=True, max_steps=10000, tile_origins=None, domain_width=0,
+                 return_stats=False):
+    """Adaptive solver of the probability-flow ODE dx/dt = -1/2 g(t)^2 score(x, t) on the device: Dormand-Prince 5(4) with FSAL and
+    the step controller of scipy.integrate.RK45 (`rk45_host_solve` is the definition), with the right-hand side in the precision of
+    `ode_sampler` (network input and time in fp32, g(t)^2 squared in fp32, state and stage sums in float64).  `rtol` / `atol` take
+    the place of a step count.  Unlike `ode_sampler` it is conditioned (`y`, `cond_img`, `lsm_cond`, `topo_cond`), guided (`cfg`:
+    every evaluation uses guidance_scale) and tileable, and it honours `img_size`.
+
+    t_span      (t0, t1), both in [eps, 1]; None is (1.0, eps), i.e. sampling.  (eps, 1.0) encodes data into the latent and needs `z`.
+    z           start state [B,1,H,W] (its shape then sets the batch and image size).  Without it the run starts from
+                marginal_prob_std(t0) times draw 0 of the run's Philox stream (`seed`), or times `noise[0]` when `noise` is given.
+    error_norm  "batch": one step size and error norm over the whole batch (scipy's semantics).  "sample": one controller per sample,
+                so a sample's trajectory does not depend on its batch-mates; required with `tile_origins`.
+    max_steps   attempts (accepted + rejected) a controller may use; OdeSolverError when they run out, on a non-finite error norm, or
+                when the step size underflows.
+    `seed`, `use_graph`, `tile_origins`, `domain_width` as in `edm_heun_sampler`; `diffusion_coeff` is accepted for signature
+    compatibility and unused (g(t) = sigma^t of the model).  An eval-mode ScoreNet runs the native loop (`sbgm_sampler_run_ode`:
+    one captured attempt replayed until the device reports done); any other callable, or a train-mode model, runs a Python loop over
+    the same kernels.  Returns fp32 [B,1,H,W]; with `return_stats` also a dict with nfev (network evaluations that counted, the two of
+    the initial step included), n_accepted, n_rejected, t_final (arrays per sample with error_norm="sample") and surplus_attempts
+    (attempts enqueued after the run was done: at most 1 for the native loop, 0 for the Python loop)."""
+    _check_tolerances(rtol, atol, error_norm, max_steps)
+    per_sample = error_norm == "sample"
+    t0, t1 = (1.0, float(eps)) if t_span is None else (float(t_span[0]), float(t_span[1]))
+    if not (eps <= t0 <= 1.0 and eps <= t1 <= 1.0) or t0 == t1:
+        raise ValueError(f"rk45_sampler: t_span=({t0:g}, {t1:g}) must be two different times in [eps, 1] = [{eps:g}, 1]")
+    if t0 < t1 and z is None:
+        raise ValueError("rk45_sampler: encoding (t_span[0] < t_span[1]) starts from data: pass it as z")
+    if z is not None and noise is not None:
+        raise ValueError("rk45_sampler: pass either z (the start state) or noise (its N(0,1) draw), not both")
+    if tile_origins is not None and not per_sample:
+        raise ValueError("rk45_sampler: tile_origins needs error_norm='sample' (a step size shared by the batch would couple the tiles)")
+    if z is not None:
+        if z.dim() != 4 or z.shape[1] != 1 or z.shape[2] != z.shape[3]:
+            raise ValueError(f"rk45_sampler: z must be [B, 1, H, H], got {tuple(z.shape)}")
+        batch_size, img_size = int(z.shape[0]), int(z.shape[-1])
+    B, hw = int(batch_size), int(img_size)
+    G = B if per_sample else 1
+    sig = float(score_model.sigma) if isinstance(score_model, ScoreNet) else _sigma_of(marginal_prob_std)
+    seed = _fresh_seed() if seed is None else seed
+    dev = torch.device(device) if not isinstance(device, torch.device) else device
+    raw_i, raw_d = np.zeros(4 * G + 2, dtype=np.int64), np.zeros(G, dtype=np.float64)
+
+    if isinstance(score_model, ScoreNet) and not score_model.training:
+        if dev.type != "cuda":
+            raise N.NativeError(f"the native samplers run on a ROCm device, got device={device!r}")
+        x_dummy, t_dummy = torch.empty(B, 1, hw, hw, device=dev), torch.empty(B, device=dev)
+        _, _, y, cond_img, lsm_cond, topo_cond = score_model._prep(x_dummy, t_dummy, y, cond_img, lsm_cond, topo_cond)
+        eng = score_model._engine(lsm_cond, topo_cond, cond_img)
+        out = torch.empty(B, 1, hw, hw, device=dev)
+        x0 = None if z is None else N.f32c(z.to(dev))
+        nz = None
+        if noise is not None:
+            nz = N.f32c((noise if torch.is_tensor(noise) else torch.stack(list(noise)))[0].to(dev))
+            if tuple(nz.shape) != (B, 1, hw, hw):
+                raise ValueError(f"noise[0] must be [{B}, 1, {hw}, {hw}], got {tuple(nz.shape)}")
+        if tile_origins is not None:
+            N.require_device(tile_origins)
+            if tile_origins.dtype != torch.int32 or tuple(tile_origins.shape) != (B, 2) or not tile_origins.is_contiguous():
+                raise ValueError("tile_origins must be a contiguous int32 [batch, 2] device tensor of (y0, x0)")
+            if noise is not None or z is not None:
+                raise ValueError("tile_origins keys the in-kernel noise; it cannot be combined with z or injected noise")
+        a = N.SamplerArgs(N.SAMPLER_RK45, B, hw, hw, 0, float(eps), 0.0, int(seed), int(bool(use_graph)), 0, N.ptr(y), N.ptr(cond_img),
+                          N.ptr(lsm_cond), N.ptr(topo_cond), N.ptr(nz), out.data_ptr(), *_guidance(cfg), N.ptr(tile_origins),
+                          int(domain_width or 0))
+        N.check(eng.lib.sbgm_sampler_run_ode(eng.h, C.byref(a), t0, t1, float(rtol), float(atol), int(per_sample), int(max_steps),
+                                             N.ptr(x0), raw_i.ctypes.data, raw_d.ctypes.data, N.stream()))
+        stats = _ode_stats(raw_i, raw_d, G, per_sample, max_steps, raw_i[4 * G])
+        return (out, stats) if return_stats else out
+
+    # ---- Python loop over the same kernels (any callable, or a train-mode model): also the definition the native loop is tested against
+    lib, st = N.lib(), N.stream
+    if z is not None:
+        if tile_origins is not None:
+            raise N.NativeError("domain-keyed noise (tile_origins) needs the native sampler loop (a ScoreNet in eval mode)")
+        x = N.f32c(z.to(dev)).clone()
+    else:
+        std0 = float(marginal_prob_std(torch.full((B,), t0, device=dev))[0])
+        x, _ = _host_start(N.SAMPLER_RK45, B, 0, hw, dev, noise, seed, std0, tile_origins)
+    N.require_device(x)
+    per, n = hw * hw, B * hw * hw
+    state = torch.empty(int(lib.sbgm_rk45_state_bytes(G)), dtype=torch.uint8, device=dev)
+    partials = torch.empty(int(lib.sbgm_rk45_partials_bytes(B, per)) // 8, dtype=torch.float64, device=dev)
+    K = torch.empty(7, n, device=dev)
+    yy, y_new = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    xs, t_dev = torch.empty(B, 1, hw, hw, device=dev), torch.empty(B, device=dev)
+    ptrs = (yy.data_ptr(), y_new.data_ptr(), K.data_ptr(), n)
+
+    def evaluate(phase, slot):
+        N.check(lib.sbgm_rk45_stage(state.data_ptr(), phase, *ptrs, xs.data_ptr(), t_dev.data_ptr(), B, per, int(per_sample), st()))
+        K[slot].copy_(N.f32c(_score(score_model, cfg, xs, t_dev, y, cond_img, lsm_cond, topo_cond)).reshape(-1))
+
+    def control(what):
+        N.check(lib.sbgm_rk45_control(state.data_ptr(), what, *ptrs, partials.data_ptr(), B, per, int(per_sample), st()))
+
+    def done():
+        N.check(lib.sbgm_rk45_read(state.data_ptr(), G, raw_i.ctypes.data, raw_d.ctypes.data, st()))
+        return bool(raw_i[4 * G])
+
+    with torch.no_grad():
+        N.check(lib.sbgm_rk45_init(state.data_ptr(), G, t0, t1, float(rtol), float(atol), sig, int(max_steps), st()))
+        N.check(lib.sbgm_rk45_load(yy.data_ptr(), x.data_ptr(), n, st()))
+        evaluate(N.ODE_PHASE_F0, 0)
+        control(0)
+        evaluate(N.ODE_PHASE_F1, 1)
+        control(1)
+        while not done():
+            for s in range(1, 7):
+                evaluate(s, s)
+            control(2)
+            N.check(lib.sbgm_rk45_commit(state.data_ptr(), *ptrs, B, per, int(per_sample), st()))
+        out = torch.empty(B, 1, hw, hw, device=dev)
+        N.check(lib.sbgm_rk45_store(out.data_ptr(), yy.data_ptr(), n, st()))
+    stats = _ode_stats(raw_i, raw_d, G, per_sample, max_steps, 0)
+    return (out, stats) if return_stats else out

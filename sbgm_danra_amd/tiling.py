@@ -120,7 +120,8 @@ class FullDomainTiler:
         def run_batch(idx):
             cut = lambda f: None if f is None else self.extract(f, idx)   # noqa: E731
             yb = None if y is None else torch.full((len(idx),), int(y), dtype=torch.int64, device=self.device)
-            return sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=len(idx), num_steps=num_steps,
+            steps = {} if num_steps is None else {"num_steps": num_steps}      # None: an adaptive sampler (rk45_sampler) has no step count
+            return sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=len(idx), **steps,
                            device=self.device, img_size=self.tile, y=yb, cond_img=cut(cond_img), lsm_cond=cut(lsm_cond),
                            topo_cond=cut(topo_cond), seed=seed, tile_origins=self.origins_dev[idx].contiguous(),
                            domain_width=self.Wd_pad, **sampler_kw)
