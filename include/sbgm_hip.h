@@ -306,6 +306,20 @@ int sbgm_conv_wino2d_pack_weight(const float* w_oihw, float* packed, int Cout, i
 int64_t sbgm_conv8x8s2_wino_packed_numel(int Cout, int c_pad);
 int sbgm_conv8x8s2_wino_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int c_pad, void* stream);
 
+/* The stem's two 8x8 / stride-2 / pad-3 convolutions as ONE 22x22 / stride-4 correlation (samplers only; conv_stem22.hip):
+ *   conv2(conv1(in) + tb0[:, :, None, None]) = sum_cin Wc[class] * in[cin] + S[class] . tb0,  64 -> 64 channels in between.
+ * conv2 zero-pads conv1's output, so the composed filter depends on the output's border class (5 per axis: o = 0, 1, interior,
+ * O - 2, O - 1).  pack: w1 OIHW [64][Cin][8][8], w2 OIHW [64][64][8][8] -> wc (sbgm_stem22_packed_numel(Cin) floats) and s
+ * (sbgm_stem22_bias_numel() floats), summed in fp64, rounded once.
+ * fwd: out [B][H/4][W/4][64] (NHWC) = act(scale * (sum over the weight channels first_channel .. first_channel + n_channels - 1 of
+ * the composed correlation of src [B][n_channels][H][W] (NCHW) + S . tb0 + addend) + bias).  tb0 [B][64], addend (out's layout; may
+ * be out itself), scale, bias [64] may be NULL; relu != 0 applies ReLU.  H, W >= 32 and multiples of 4; Cin <= 16. */
+int64_t sbgm_stem22_packed_numel(int Cin);
+int64_t sbgm_stem22_bias_numel(void);
+int sbgm_stem22_pack_weight(const float* w1_oihw, const float* w2_oihw, float* wc, float* s, int Cin, void* stream);
+int sbgm_stem22_fwd(const float* src, int n_channels, int first_channel, int Cin, const float* wc, const float* s, const float* tb0,
+                    const float* addend, const float* scale, const float* bias, int relu, float* out, int B, int H, int W, void* stream);
+
 /* ConvTranspose2d(k=2,s=2) = one 1x1 convolution to 4C channels (weights from sbgm_tconv_weight_to_oihw, bias repeated
  * 4x) followed by depth->space; its backward is space->depth followed by the 1x1 convolution's backward. */
 int sbgm_depth_to_space2(const float* x /* [B,H,W,4C] */, float* y /* [B,2H,2W,C] */, int B, int H, int W, int C, void* stream);

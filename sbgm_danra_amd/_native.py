@@ -109,6 +109,10 @@ SIGNATURES = {
     "sbgm_conv_wino2d_pack_weight": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sbgm_conv8x8s2_wino_packed_numel": (_i64, [_i, _i]),
     "sbgm_conv8x8s2_wino_pack_weight": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "sbgm_stem22_packed_numel": (_i64, [_i]),
+    "sbgm_stem22_bias_numel": (_i64, []),
+    "sbgm_stem22_pack_weight": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "sbgm_stem22_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "sbgm_conv2d_fwd": (_i, [C.POINTER(ConvArgs), _vp]),
     "sbgm_conv2d_tune": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int), _vp]),
     "sbgm_conv_pack_weights_batched": (_i, [_vp, _i, _i, _vp]),

@@ -37,6 +37,16 @@ int64_t sbgm_conv8x8s2_wino_packed_numel(int Cout, int c_pad) { return (int64_t)
 int sbgm_conv8x8s2_wino_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int c_pad, void* stream) {
     return sbgm_launch_pack_s2w_weight(w_oihw, packed, Cout, Cin, c_pad, ST);
 }
+int64_t sbgm_stem22_packed_numel(int Cin) { return (int64_t)sbgm_stem22_packed_floats(Cin); }
+int64_t sbgm_stem22_bias_numel(void) { return (int64_t)sbgm_stem22_bias_floats(); }
+int sbgm_stem22_pack_weight(const float* w1_oihw, const float* w2_oihw, float* wc, float* s, int Cin, void* stream) {
+    SBGM_CHECK(w1_oihw && w2_oihw && wc && s, "stem22_pack_weight: null tensor");
+    return sbgm_launch_pack_stem22(w1_oihw, w2_oihw, wc, s, Cin, ST);
+}
+int sbgm_stem22_fwd(const float* src, int n_channels, int first_channel, int Cin, const float* wc, const float* s, const float* tb0,
+                    const float* addend, const float* scale, const float* bias, int relu, float* out, int B, int H, int W, void* stream) {
+    return sbgm_launch_conv_stem22(src, n_channels, first_channel, Cin, wc, s, tb0, addend, scale, bias, relu, out, B, H, W, ST);
+}
 int sbgm_conv_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin, int KH, int KW, int c_pad, void* stream) {
     return sbgm_launch_pack_conv_weight(w_oihw, packed, Cout, Cin, KH, KW, c_pad, ST);
 }

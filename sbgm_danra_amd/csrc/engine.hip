@@ -94,6 +94,57 @@ struct sbgm_model {
     DecW dec[4];
     ConvW fin_up, fin_conv;
     bool bn_dirty = true;
+    // Composed stem of the samplers (conv_stem22.hip): conv2(conv1(.) + tb0) as one 22x22 / stride-4 kernel.  OIHW copies of the two
+    // weights are kept at upload; the composed image is built lazily (stem_dirty) before a sampler run, never by a training upload.
+    float *stem_w1 = nullptr, *stem_w2 = nullptr;          // OIHW encoder.conv1 / conv2 as uploaded
+    float *stem_wc = nullptr, *stem_sb = nullptr;          // composed weights and time-bias sums of the 25 border classes
+    bool stem_dirty = true;
+    const float* stem_T = nullptr;           // during a sampler run: the run's condition term [BE][H/4][W/4][64] (null: no condition channels)
+    bool stem_run = false;                   // set by the sampler drivers for the duration of a run: forward_impl composes the stem
+    static bool stem_enabled() { static const bool on = getenv("SBGM_NO_STEM_COMPOSE") == nullptr; return on; }
+    int stem_keep(const float* src, Param* p, float*& copy, hipStream_t st) {
+        if (!stem_enabled()) return 0;
+        if (!copy) SBGM_HIP(hipMalloc(&copy, (size_t)p->numel * 4));
+        SBGM_HIP(hipMemcpyAsync(copy, src, (size_t)p->numel * 4, hipMemcpyDeviceToDevice, st));
+        stem_dirty = true;
+        return 0;
+    }
+    int stem_prepare(hipStream_t st) {       // outside any captured step
+        if (!stem_dirty) return 0;
+        SBGM_CHECK(stem_w1 && stem_w2, "sampler: encoder.conv1 / conv2 weights were never uploaded");
+        if (!stem_wc) SBGM_HIP(hipMalloc(&stem_wc, sbgm_stem22_packed_floats(cin_total) * 4));
+        if (!stem_sb) SBGM_HIP(hipMalloc(&stem_sb, sbgm_stem22_bias_floats() * 4));
+        if (sbgm_launch_pack_stem22(stem_w1, stem_w2, stem_wc, stem_sb, cin_total, st)) return 1;
+        stem_dirty = false;
+        return 0;
+    }
+    // The run's condition term T = composed filter over the channels that do not change from step to step (lsm, topo, cond_img, in
+    // conv1's concatenation order after x), into `T`; then forward_impl routes the stem through the composed kernel until stem_end().
+    int stem_begin(const float* lsm, const float* topo, const float* cond, float* T, int B, int H, int W, hipStream_t st) {
+        if (!stem_enabled()) return 0;
+        if (stem_prepare(st)) return 1;
+        const float* srcs[3] = {lsm, topo, cond};
+        const int chs[3] = {cfg.n_lsm_channels, cfg.n_topo_channels, cfg.n_cond_channels};
+        int c0 = 1;
+        bool any = false;
+        for (int i = 0; i < 3; ++i) {
+            if (!chs[i]) continue;
+            if (sbgm_launch_conv_stem22(srcs[i], chs[i], c0, cin_total, stem_wc, nullptr, nullptr, any ? T : nullptr, nullptr, nullptr, 0,
+                                        T, B, H, W, st)) return 1;
+            c0 += chs[i];
+            any = true;
+        }
+        stem_T = any ? T : nullptr;
+        stem_run = true;
+        return 0;
+    }
+    struct StemRun {                         // ends the routing on every exit path of a sampler driver
+        sbgm_model* m;
+        ~StemRun() { m->stem_run = false; m->stem_T = nullptr; }
+    };
+    size_t stem_t_bytes(int B, int H, int W) const {
+        return stem_enabled() && cin_total > 1 ? align_up((size_t)B * H * W * 4 * 4, 256) : 0;
+    }
     // workspace
     char* ws = nullptr;
     size_t ws_bytes = 0, ws_used = 0;
@@ -165,6 +216,7 @@ struct sbgm_model {
     ~sbgm_model() {
         drop_step_graph();
         if (arena) (void)hipFree(arena);
+        for (float* q : {stem_w1, stem_w2, stem_wc, stem_sb}) if (q) (void)hipFree(q);
         if (ws) (void)hipFree(ws);
         if (d_state) (void)hipFree(d_state);
         if (d_table) (void)hipFree(d_table);
@@ -241,10 +293,12 @@ struct sbgm_model {
     // each), one slab for the state block and the norm partials.
     static constexpr int ODE_SLABS = 14;
     static int sampler_slabs(int kind) { return kind == SBGM_SAMPLER_RK45 ? ODE_SLABS : kind == SBGM_SAMPLER_EDM_HEUN ? 4 : 3; }
-    size_t sampler_keep(int B, int H, int W, int slabs) const {
+    // After them (run-persistent as well): the composed stem's condition term T [B][H/4][W/4][64].
+    size_t slabs_keep(int B, int H, int W, int slabs) const {
         const size_t n = (size_t)B * H * W;
         return align_up(n * 4, 256) * slabs + align_up((size_t)B * 4, 256) + align_up((size_t)B * 8, 256);
     }
+    size_t sampler_keep(int B, int H, int W, int slabs) const { return slabs_keep(B, H, W, slabs) + stem_t_bytes(B, H, W); }
     size_t ws_need(int B, int H, int W, int bn_train = 0, int slabs = 3) const {
         return fwd_need(B, H, W, bn_train) + sampler_keep(B, H, W, slabs);
     }
@@ -823,7 +877,19 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     int ch = H / 4, cw_ = W / 4;
     float* cur = wsalloc((size_t)B * ch * cw_ * 64);
     if (!cur) return 1;
-    if (conv_bn(ConvGeom{8, 8, 2, 3}, fm[0], fh[0], fw[0], 64, conv2, bn1, 64, nullptr, true, nullptr, cur)) return 1;   // :321-325
+    if (stem_run && !prof && !tuning) {
+        // sampler runs: conv2(fm[0]) + bn1 + ReLU straight from x, the run's condition term and tb[0] (conv_stem22.hip); conv1 above
+        // still writes fm[0], the decoder's last skip
+        float* o = cur;
+        if (bn_train) {
+            o = wsalloc((size_t)B * ch * cw_ * 64);
+            if (!o) return 1;
+        }
+        if (sbgm_launch_conv_stem22(x, 1, 0, cin_total, stem_wc, stem_sb, tb[0], stem_T, bn_train ? nullptr : bn1.scale,
+                                    bn_train ? nullptr : bn1.bias, bn_train ? 0 : 1, o, B, H, W, st)) return 1;
+        if (bn_train && sbgm_launch_batchnorm_train(o, cur, bn1.g->dev, bn1.b->dev, bn1.rm->dev, bn1.rv->dev, nullptr, nullptr, true, B,
+                                                    ch * cw_, 64, BN_EPS, BN_MOMENTUM, stats, st)) return 1;
+    } else if (conv_bn(ConvGeom{8, 8, 2, 3}, fm[0], fh[0], fw[0], 64, conv2, bn1, 64, nullptr, true, nullptr, cur)) return 1;   // :321-325
     int cc = 64;
     for (int li = 0; li < 4; ++li) {
         const int nb = (int)layers[li].size();
@@ -1160,11 +1226,15 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     float* xmean = reinterpret_cast<float*>(top + 2 * slab);
     float* t_dev = reinterpret_cast<float*>(top + 3 * slab);
     double* sumsq = reinterpret_cast<double*>(top + 3 * slab + align_up((size_t)BE * 4, 256));
-    float* dheun = heun ? reinterpret_cast<float*>(top + sampler_keep(BE, H, W, 3)) : nullptr;
+    float* dheun = heun ? reinterpret_cast<float*>(top + slabs_keep(BE, H, W, 3)) : nullptr;
+    float* stemT = reinterpret_cast<float*>(top + slabs_keep(BE, H, W, slabs));
     const size_t fwd_bytes = ws_bytes - keep;
     if (bn_dirty && fold_bn(st)) return 1;              // keep the fold out of the captured step
     SamplerConds conds(a, st);                           // guidance: the unconditional half is built once per run
     if (guided && conds.add_unconditional(a, cfg)) return 1;
+    // once per run, outside the captured step: a cached step graph is replayed on new condition contents at the same addresses
+    StemRun stem_guard{this};
+    if (stem_begin(conds.lsm, conds.topo, conds.cond, stemT, BE, H, W, st)) return 1;
 
     // x0 = randn * marginal_prob_std(1); EDM Heun: sigma_0 z into its state slab, copied to the network input
     const float ls = logf(sig);
@@ -1291,6 +1361,9 @@ int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, cons
     if (bn_dirty && fold_bn(st)) return 1;
     SamplerConds conds(a, st);
     if (guided && conds.add_unconditional(a, cfg)) return 1;
+    // The composed stem (stem_begin) is NOT used here: rk45_sampler's Python loop evaluates the network through the plain forward and
+    // must take the same accept / reject decisions as this loop (one computation, bit for bit); a stem that rounds differently flips a
+    // decision whose error norm lies within rounding of 1.
 
     // start: the caller's state, or marginal_prob_std(t0) * draw 0 of the run's Philox stream (domain-keyed on tiles)
     if (sbgm_launch_ode_init(state, G, o.t0, o.t1, o.rtol, o.atol, cfg.sigma, o.max_steps, st)) return 1;
@@ -1423,6 +1496,8 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
         if (p->wino && sbgm_launch_pack_wino_weight(src, p->dev_wino, p->cout, p->cin, p->cs, st)) return 1;
         if (p->dev_w2d && sbgm_launch_pack_w2d_weight(src, p->dev_w2d, p->cout, p->cin, p->cs, st)) return 1;
         if (p->dev_s2w && sbgm_launch_pack_s2w_weight(src, p->dev_s2w, p->cout, p->cin, p->cs, st)) return 1;
+        if (p == m->conv1.w && m->stem_keep(src, p, m->stem_w1, st)) return 1;
+        if (p == m->conv2.w && m->stem_keep(src, p, m->stem_w2, st)) return 1;
     } else if (p->kind == P_TCONV) {             // [Cin][Cout][2][2] -> OIHW [4*Cout][Cin][1][1] (scratch) -> packed
         float* tmp = nullptr;
         SBGM_HIP(hipMalloc(&tmp, (size_t)numel * 4));

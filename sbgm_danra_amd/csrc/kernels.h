@@ -101,6 +101,15 @@ int sbgm_launch_pack_s2w_weight(const float* w_oihw, float* up, int Cout, int Ci
 int sbgm_launch_conv_s2w(ConvParams p, const ConvTile& cfg, hipStream_t st);    // p.wp = F(2x2,4x4) space-to-depth weights
 size_t sbgm_conv_s2w_bytes(const ConvTile& cfg);
 
+// ---- conv_stem22.hip: the stem's conv2(conv1(.) + tb0) composed into one 22x22 stride-4 correlation (samplers only) --------------
+size_t sbgm_stem22_packed_floats(int Cin);      // Wc[25 classes][Cin][33][64][4][4]
+size_t sbgm_stem22_bias_floats();               // S[25 classes][4][64][4][4]
+int sbgm_launch_pack_stem22(const float* w1_oihw, const float* w2_oihw, float* wc, float* sb, int Cin, hipStream_t st);
+// channels c0 .. c0 + nch - 1 of the composed filter over src [B][nch][H][W] (+ S . tb0, + addend, folded BN, ReLU) -> out NHWC
+int sbgm_launch_conv_stem22(const float* src, int nch, int c0, int Cin, const float* wc, const float* sb, const float* tb0,
+                            const float* addend, const float* scale, const float* bias, int relu, float* out, int B, int H, int W,
+                            hipStream_t st);
+
 // ---- pointwise.hip ---------------------------------------------------------------------------------
 struct PackSrc {
     const float* ptr[4];   // NCHW sources, concatenated along C in this order
