@@ -320,6 +320,23 @@ int sbgm_stem22_pack_weight(const float* w1_oihw, const float* w2_oihw, float* w
 int sbgm_stem22_fwd(const float* src, int n_channels, int first_channel, int Cin, const float* wc, const float* s, const float* tb0,
                     const float* addend, const float* scale, const float* bias, int relu, float* out, int B, int H, int W, void* stream);
 
+/* The final DecoderBlock (identity norms, no skip, no time term, identity activation: score_unet.py:713-730, :757) as ONE 3x3
+ * convolution (conv_final.hip): conv(conv_up(up(x))) = gather(Wc * up(x) + bc), Wc[tap][ci][v][b] = sum_co w2[0][co][tap] w1[co][ci][v][b],
+ * bc[tap] = sum_co w2[0][co][tap] b1[co], out[o] = b2 + sum_tap d[tap][o + tap - 1] with d = 0 outside the image.
+ * pack: w1 OIHW [C][C][3][3] and b1 [C] (conv_up), w2 OIHW [1][C][3][3] (conv) -> wc OIHW [16][C][3][3] (rows 9..15 zero) and bc [16],
+ * summed in fp64 and rounded once; pack wc with sbgm_conv_pack_weight, sbgm_conv_wino_pack_weight, sbgm_conv_wino2d_pack_weight (Cout 16).
+ * fwd: x = the LOW-resolution NHWC input [B,H/2,W/2,C], optionally act(x*scale + shift + in_skip) on load (in_affine / in_skip / in_act
+ * as in sbgm_conv_args, fused route only); out [B,1,H,W] = the block's output, divided by sigma(t) when t [B] is given.  W >= 32 runs
+ * the bilinear x2 inside the convolution (in_mode 2) as the decoder does, narrower maps upsample into ws first.  ws: 16*B*H*W floats
+ * (+ C*B*H*W for the narrow route).  tile: NULL = the engine's static choice, else one of sbgm_final_block_tiles' candidates
+ * {tile_co, tile_px, splits, waves_per_tile, winograd kind, LDS kind}; w_wino2d may be NULL when no such tile is used.
+ * sbgm_final_block_tiles writes up to `cap` candidates (6 ints each), the ones the autotuner times for this op, and returns their number. */
+int sbgm_final_compose_pack(const float* w1_oihw, const float* b1, const float* w2_oihw, float* wc_oihw, float* bc, int C, void* stream);
+int sbgm_final_block_tiles(int B, int H, int W, int C, int* tiles, int cap);
+int sbgm_final_block_fwd(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* w_packed,
+                         const float* w_wino, const float* w_wino2d, const float* bc, const float* b2, const float* t, float sigma,
+                         float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, const int* tile, void* stream);
+
 /* ConvTranspose2d(k=2,s=2) = one 1x1 convolution to 4C channels (weights from sbgm_tconv_weight_to_oihw, bias repeated
  * 4x) followed by depth->space; its backward is space->depth followed by the 1x1 convolution's backward. */
 int sbgm_depth_to_space2(const float* x /* [B,H,W,4C] */, float* y /* [B,2H,2W,C] */, int B, int H, int W, int C, void* stream);

@@ -113,6 +113,10 @@ SIGNATURES = {
     "sbgm_stem22_bias_numel": (_i64, []),
     "sbgm_stem22_pack_weight": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "sbgm_stem22_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "sbgm_final_compose_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sbgm_final_block_tiles": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), _i]),
+    "sbgm_final_block_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i,
+                                  C.POINTER(C.c_int), _vp]),
     "sbgm_conv2d_fwd": (_i, [C.POINTER(ConvArgs), _vp]),
     "sbgm_conv2d_tune": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int), _vp]),
     "sbgm_conv_pack_weights_batched": (_i, [_vp, _i, _i, _vp]),

@@ -140,10 +140,72 @@ struct sbgm_model {
     }
     struct StemRun {                         // ends the routing on every exit path of a sampler driver
         sbgm_model* m;
-        ~StemRun() { m->stem_run = false; m->stem_T = nullptr; }
+        ~StemRun() { m->stem_run = false; m->stem_T = nullptr; m->fin_run = false; }
     };
     size_t stem_t_bytes(int B, int H, int W) const {
         return stem_enabled() && cin_total > 1 ? align_up((size_t)B * H * W * 4 * 4, 256) : 0;
+    }
+    // Composed final block (conv_final.hip): final_layer.conv(final_layer.conv_up(.)) as one 3x3 convolution to 16 channels, the 9 taps
+    // of `conv` first.  fin_comp is no Param (not in the state_dict, the gradient arena or Adam): its images live in fin_img at fixed
+    // addresses and are rebuilt lazily (fin_dirty) from OIHW copies kept at upload, outside any captured step.
+    float *fin_w1 = nullptr, *fin_w2 = nullptr;            // OIHW final_layer.conv_up.weight / final_layer.conv.weight as uploaded
+    float *fin_img = nullptr, *fin_wc = nullptr;           // one allocation: Wc OIHW [16][ci][3][3], bc [16], then the three packed images
+    Param fin_cw, fin_cb;
+    ConvW fin_comp;
+    bool fin_route = false, fin_dirty = true;
+    // Who takes the route: the EM / PC / EDM Heun drivers (fin_run, for the duration of a run), profile_forward and a tuning evaluation.
+    // The plain forward and the RK45 driver keep the projection path: rk45_sampler's Python loop and SciPy's solver behind ode_sampler
+    // evaluate the network through the plain forward, and at rtol 1e-4 their accept / reject decisions are within rounding of the
+    // native loop's -- with the composed block's rounding one run of tests/test_gpu_rk45_sampler.py took 452 evaluations under SciPy
+    // against 464 natively (bound 9), where the projection path gives 464 / 464.
+    bool fin_run = false;
+    static bool fin_enabled() { static const bool on = getenv("SBGM_NO_FINAL_COMPOSE") == nullptr; return on; }
+    int fin_build(int ci) {
+        // the 16-channel op runs on the LDS-staged Winograd kernels only, so the switches that take those away keep the projection path
+        fin_route = fin_enabled() && !cfg.decoder_transpose && ci % 16 == 0 && fin_up.w->wino && getenv("SBGM_NO_LDS_CONV") == nullptr &&
+                    getenv("SBGM_STATIC_ROUND1") == nullptr;
+        if (!fin_route) return 0;
+        fin_cw.name = "final_layer.composed.weight"; fin_cw.kind = P_CONV; fin_cw.numel = (int64_t)16 * ci * 9;
+        fin_cw.cout = 16; fin_cw.cin = ci; fin_cw.kh = fin_cw.kw = 3; fin_cw.cs = ci; fin_cw.wino = true;
+        fin_cw.dev_floats = (size_t)sbgm_conv_nsteps(3, 3, ci) * 16 * 16;
+        fin_cw.wino_floats = sbgm_wino_packed_floats(16, ci);
+        fin_cw.w2d_floats = fin_up.w->w2d_floats ? sbgm_w2d_packed_floats(16, ci) : 0;
+        fin_cb.name = "final_layer.composed.bias"; fin_cb.numel = fin_cb.dev_floats = 16;
+        const size_t wc_floats = align_up((size_t)fin_cw.numel, 64);
+        const size_t total = wc_floats + 64 + align_up(fin_cw.dev_floats, 64) + align_up(fin_cw.wino_floats, 64) + align_up(fin_cw.w2d_floats, 64);
+        SBGM_HIP(hipMalloc(&fin_img, total * 4));
+        SBGM_HIP(hipMemset(fin_img, 0, total * 4));
+        float* q = fin_img;
+        fin_wc = q; q += wc_floats;
+        fin_cb.dev = q; q += 64;
+        fin_cw.dev = q; q += align_up(fin_cw.dev_floats, 64);
+        fin_cw.dev_wino = q; q += align_up(fin_cw.wino_floats, 64);
+        if (fin_cw.w2d_floats) fin_cw.dev_w2d = q;
+        fin_cw.filled = fin_cb.filled = true;
+        fin_comp = ConvW{&fin_cw, &fin_cb};
+        return 0;
+    }
+    int fin_keep(const float* src, const Param* p, float*& copy, hipStream_t st) {
+        if (!copy) SBGM_HIP(hipMalloc(&copy, (size_t)p->numel * 4));
+        SBGM_HIP(hipMemcpyAsync(copy, src, (size_t)p->numel * 4, hipMemcpyDeviceToDevice, st));
+        fin_dirty = true;
+        return 0;
+    }
+    int fin_prepare(hipStream_t st) {        // outside any captured step
+        if (!fin_route || !fin_dirty) return 0;
+        SBGM_CHECK(fin_w1 && fin_w2 && fin_up.b->filled, "final block: final_layer.conv_up / conv weights were never uploaded");
+        const int ci = fin_cw.cin;
+        if (sbgm_launch_final_compose(fin_w1, fin_up.b->dev, fin_w2, fin_wc, fin_cb.dev, ci, st)) return 1;
+        if (sbgm_launch_pack_conv_weight(fin_wc, fin_cw.dev, 16, ci, 3, 3, ci, st)) return 1;
+        if (sbgm_launch_pack_wino_weight(fin_wc, fin_cw.dev_wino, 16, ci, ci, st)) return 1;
+        if (fin_cw.dev_w2d && sbgm_launch_pack_w2d_weight(fin_wc, fin_cw.dev_w2d, 16, ci, ci, st)) return 1;
+        fin_dirty = false;
+        return 0;
+    }
+    // what an evaluation reads besides the uploaded parameters: folded BatchNorm, the composed final block
+    int refresh_derived(hipStream_t st) {
+        if (bn_dirty && fold_bn(st)) return 1;
+        return fin_prepare(st);
     }
     // workspace
     char* ws = nullptr;
@@ -216,7 +278,7 @@ struct sbgm_model {
     ~sbgm_model() {
         drop_step_graph();
         if (arena) (void)hipFree(arena);
-        for (float* q : {stem_w1, stem_w2, stem_wc, stem_sb}) if (q) (void)hipFree(q);
+        for (float* q : {stem_w1, stem_w2, stem_wc, stem_sb, fin_w1, fin_w2, fin_img}) if (q) (void)hipFree(q);
         if (ws) (void)hipFree(ws);
         if (d_state) (void)hipFree(d_state);
         if (d_table) (void)hipFree(d_table);
@@ -459,7 +521,7 @@ int sbgm_model::build(const sbgm_model_config& c) {
     for (int li = 0; li < 4; ++li)
         for (auto& b : layers[li]) { place_bn(b.bn1, b.cout); place_bn(b.bn2, b.cout); if (b.has_ds) place_bn(b.dsbn, b.cout); }
     SBGM_HIP(hipMalloc(&d_state, sizeof(SamplerState)));
-    return 0;
+    return fin_build(dec[3].cout);           // after the loop above: it mirrors which images final_layer.conv_up has
 }
 
 int sbgm_model::ensure_ws(size_t bytes) {
@@ -517,6 +579,15 @@ static bool s2w_ok(const ConvGeom& g, const ConvParams& p) {
     return p.wp_s2w != nullptr && g.kh == 8 && g.kw == 8 && g.stride == 2 && g.pad == 3 && p.in_dil <= 1 && p.in_mode == 0 &&
            p.proj_w == nullptr && p.c_real == 0 && p.Cs % 16 == 0 && p.Cout % 16 == 0 && p.out_h == 0 && p.out_w == 0;
 }
+// 16 output channels (the composed final block): only the one-co-tile LDS-staged Winograd kernels serve it.  Timed alone at batch
+// 32 x 128^2 / batch 16 x 256^2 (convolution + gather, inputs evicted): 2-D Winograd one-tile with one stage buffer 89 / 162 us,
+// persistent 90 / 174 us, row-only 1-D Winograd 97-100 / 172 us, every double-buffered form 113-127 / 200-237 us.  The autotuner
+// picks the same one-tile kernel inside the network (profiles/r06_c2_tiles.txt, r06_c4_tiles.txt: 81 / 154 us per launch).
+static ConvTile cout16_tile(const ConvParams& p) {
+    const ConvTile w2d{1, 1, 1, 1, 2, 1}, row{1, 1, 1, 1, 1, 1};
+    if (p.wp_w2d != nullptr && p.H % 2 == 0 && sbgm_conv_w2d_bytes(w2d, p.in_mode) <= 160 * 1024) return w2d;
+    return row;
+}
 ConvTile sbgm_model::pick_tile(const ConvGeom& g, const ConvParams& p) {
     const int OH = (p.H + 2 * g.pad - g.kh) / g.stride + 1, OW = (p.W + 2 * g.pad - g.kw) / g.stride + 1;
     ConvOpKey key{g.kh, g.kw, g.stride, g.pad, p.B, p.H, p.W, p.Cs, p.Cout, p.proj_w != nullptr, p.in_mode};
@@ -534,6 +605,7 @@ ConvTile sbgm_model::pick_tile(const ConvGeom& g, const ConvParams& p) {
     }
     if (lds_ok && s1 && p.W % 16 == 0 && p.H % 2 == 0 && p.Cs % 16 == 0) {
         const long tiles16 = (long)p.B * (p.W / 16) * ((p.H + 15) / 16) * (p.Cout / 16);
+        if (p.Cout == 16 && !p.proj_w && p.wp_wino != nullptr) return cout16_tile(p);
         if (p.wp_w2d != nullptr && (tiles16 >= 512 || p.proj_w)) {
             const ConvTile big{2, 1, 1, 2, 2, 3}, mid{1, 1, 1, 2, 2, 3};
             if (p.Cout % 32 == 0 && tiles16 >= 1024 && sbgm_conv_w2d_bytes(big, p.in_mode) <= 160 * 1024) return big;
@@ -595,14 +667,11 @@ ConvTile sbgm_model::pick_tile(const ConvGeom& g, const ConvParams& p) {
     return ConvTile{fco, fpx, splits, ws, 0, 0};
 }
 
-// Times the tile candidates (template x tile x waves-per-tile x split-K) of ONE convolution on its real operands and returns
-// the fastest in *best (in: the fallback).  A launch never reads what it writes, so repeating it is harmless.  Synchronises.
-int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, float* partial, size_t partial_floats, hipStream_t st, ConvTile* best) {
+// The tile candidates (template x tile x waves-per-tile x split-K) of one convolution; split-K ones only with a partial buffer.
+static std::vector<ConvTile> conv_candidates(const ConvGeom& g, const ConvParams& p, bool partial) {
     const int OH = p.out_h > 0 ? p.out_h : (p.H + 2 * g.pad - g.kh) / g.stride + 1;
     const int OW = p.out_w > 0 ? p.out_w : (p.W + 2 * g.pad - g.kw) / g.stride + 1;
-    const size_t mc = (size_t)p.B * OH * OW * p.Cout;
     const int nsteps = sbgm_conv_nsteps(g.kh, g.kw, p.c_real == 2 ? 2 : p.Cs);
-    auto launch = [&](const ConvTile& ct) -> int { return launch_tile(g, p, ct, partial, st); };
     std::vector<ConvTile> cands;
     const int tiles[6][2] = {{4, 4}, {4, 2}, {4, 1}, {2, 4}, {2, 2}, {2, 1}};
     for (auto& t : tiles) {
@@ -668,6 +737,17 @@ int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, float* partial, size_
     if (s2w_ok(g, p))
         for (int fco : {2, 1})
             if (p.Cout % (16 * fco) == 0) cands.push_back(ConvTile{fco, 1, 1, 1, 3, 1});
+    return cands;
+}
+
+// Times the tile candidates (template x tile x waves-per-tile x split-K) of ONE convolution on its real operands and returns
+// the fastest in *best (in: the fallback).  A launch never reads what it writes, so repeating it is harmless.  Synchronises.
+int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, float* partial, size_t partial_floats, hipStream_t st, ConvTile* best) {
+    const int OH = p.out_h > 0 ? p.out_h : (p.H + 2 * g.pad - g.kh) / g.stride + 1;
+    const int OW = p.out_w > 0 ? p.out_w : (p.W + 2 * g.pad - g.kw) / g.stride + 1;
+    const size_t mc = (size_t)p.B * OH * OW * p.Cout;
+    auto launch = [&](const ConvTile& ct) -> int { return launch_tile(g, p, ct, partial, st); };
+    const std::vector<ConvTile> cands = conv_candidates(g, p, partial != nullptr);
     hipEvent_t e0, e1;
     SBGM_HIP(hipEventCreate(&e0));
     SBGM_HIP(hipEventCreate(&e1));
@@ -804,7 +884,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
         SBGM_CHECK(fwd_need(B, H, W, bn_train) <= ws_bytes, "forward: workspace not prepared for B=%d H=%d W=%d", B, H, W);
         ws_used = 0;
     }
-    if (bn_dirty && fold_bn(st)) return 1;
+    if (refresh_derived(st)) return 1;
     partial = wsalloc(PARTIAL_FLOATS);
     if (!partial) return 1;
 
@@ -1028,6 +1108,18 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             if (sbgm_launch_depth_space2(up, a, B, ch, cw_, ci, 1, st)) return 1;
             return sbgm_launch_conv3x3_cout1(a, fin_conv.w->dev, fin_conv.b->dev, t, cfg.sigma, out, B, H, W, ci, st);
         }
+        if (fin_route && (fin_run || prof != nullptr || tuning)) {
+            // conv(conv_up(.)) composed: one 3x3 convolution from ci to the 9 taps (16 channels stored), rows [M][16], then the gather
+            const Pending pend0 = pend;
+            if (conv_up(fin_comp, cur, ci, H, W, p, nullptr)) return 1;
+            float* d = wsalloc((size_t)16 * B * H * W);
+            if (!d) return 1;
+            p.Cout = 16; p.out = d;
+            if (conv(ConvGeom{3, 3, 1, 1}, p, st)) return 1;
+            if (sbgm_launch_tap_gather_rows(d, fin_conv.b->dev, t, cfg.sigma, out, B, H, W, st)) return 1;
+            if (!tuning) return 0;
+            pend = pend0;                        // a tuning evaluation also times the projection form below (plain forward, RK45)
+        }
         if (conv_up(fin_up, cur, ci, H, W, p, nullptr)) return 1;
         if (ci == 64) {
             // conv_up's 64-channel output feeds only the linear 3x3 Cout=1 conv: project onto its 9 taps in the epilogue
@@ -1229,11 +1321,12 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     float* dheun = heun ? reinterpret_cast<float*>(top + slabs_keep(BE, H, W, 3)) : nullptr;
     float* stemT = reinterpret_cast<float*>(top + slabs_keep(BE, H, W, slabs));
     const size_t fwd_bytes = ws_bytes - keep;
-    if (bn_dirty && fold_bn(st)) return 1;              // keep the fold out of the captured step
+    if (refresh_derived(st)) return 1;                  // keep the fold and the final block's rebuild out of the captured step
     SamplerConds conds(a, st);                           // guidance: the unconditional half is built once per run
     if (guided && conds.add_unconditional(a, cfg)) return 1;
     // once per run, outside the captured step: a cached step graph is replayed on new condition contents at the same addresses
     StemRun stem_guard{this};
+    fin_run = fin_route;
     if (stem_begin(conds.lsm, conds.topo, conds.cond, stemT, BE, H, W, st)) return 1;
 
     // x0 = randn * marginal_prob_std(1); EDM Heun: sigma_0 z into its state slab, copied to the network input
@@ -1358,7 +1451,7 @@ int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, cons
     SBGM_CHECK(state_bytes + sbgm_ode_partials_bytes(B, per) <= slab, "sampler_ode: %d x %d samples are too small for the solver's state slab", H, W);
     float* t_dev = reinterpret_cast<float*>(top + ODE_SLABS * slab);
     const size_t fwd_bytes = ws_bytes - keep;
-    if (bn_dirty && fold_bn(st)) return 1;
+    if (refresh_derived(st)) return 1;
     SamplerConds conds(a, st);
     if (guided && conds.add_unconditional(a, cfg)) return 1;
     // The composed stem (stem_begin) is NOT used here: rk45_sampler's Python loop evaluates the network through the plain forward and
@@ -1491,6 +1584,7 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
     const float* src = static_cast<const float*>(data);
     if (p->kind == P_VEC) {
         SBGM_HIP(hipMemcpyAsync(p->dev, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
+        if (p == m->fin_up.b) m->fin_dirty = true;
     } else if (p->kind == P_CONV) {
         if (sbgm_launch_pack_conv_weight(src, p->dev, p->cout, p->cin, p->kh, p->kw, p->cs, st)) return 1;
         if (p->wino && sbgm_launch_pack_wino_weight(src, p->dev_wino, p->cout, p->cin, p->cs, st)) return 1;
@@ -1498,6 +1592,7 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
         if (p->dev_s2w && sbgm_launch_pack_s2w_weight(src, p->dev_s2w, p->cout, p->cin, p->cs, st)) return 1;
         if (p == m->conv1.w && m->stem_keep(src, p, m->stem_w1, st)) return 1;
         if (p == m->conv2.w && m->stem_keep(src, p, m->stem_w2, st)) return 1;
+        if (m->fin_route && p == m->fin_up.w && m->fin_keep(src, p, m->fin_w1, st)) return 1;
     } else if (p->kind == P_TCONV) {             // [Cin][Cout][2][2] -> OIHW [4*Cout][Cin][1][1] (scratch) -> packed
         float* tmp = nullptr;
         SBGM_HIP(hipMalloc(&tmp, (size_t)numel * 4));
@@ -1511,6 +1606,7 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
             SBGM_HIP(hipMemcpyAsync(p->dev + (size_t)r * numel, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
     } else {
         if (sbgm_launch_pack_cout1_weight(src, p->dev, p->cin, st)) return 1;
+        if (m->fin_route && p == m->fin_conv.w && m->fin_keep(src, p, m->fin_w2, st)) return 1;
     }
     p->filled = true;
     m->bn_dirty = true;
@@ -1593,7 +1689,7 @@ int sbgm_model::dummy_forward(int B, int H, int W, bool tune, hipStream_t st) {
 int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, int slabs) {
     if (!bn_train && ws_peak.find(std::array<int, 4>{B, H, W, 0}) == ws_peak.end() && sbgm_model_check_complete(this) == 0) {
         if (ensure_ws(ws_need(B, H, W, 0, slabs) + ((size_t)B * H * W * 16 + 1024) * 4 + 4096)) return 1;
-        if (bn_dirty && fold_bn(st)) return 1;
+        if (refresh_derived(st)) return 1;
         if (dummy_forward(B, H, W, false, st)) return 1;
     }
     return ensure_ws(ws_need(B, H, W, bn_train, slabs));
@@ -1602,7 +1698,7 @@ int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, in
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (m->ensure_ws(2 * m->ws_need(B, H, W))) return 1;
-    if (m->bn_dirty && m->fold_bn(st)) return 1;
+    if (m->refresh_derived(st)) return 1;
     if (m->dummy_forward(B, H, W, true, st)) return 1;
     // the tuned plan's high-water mark, then the slab at its final size: what runs next (a sampler capturing its step) finds both settled
     if (m->dummy_forward(B, H, W, false, st)) return 1;
@@ -1712,6 +1808,61 @@ int sbgm_model_profile_forward(sbgm_model* m, const float* x, const float* t, co
     (void)hipEventDestroy(t1);
     if (summary) *summary = s;
     return 0;
+}
+
+// ---- the composed final block on its own (conv_final.hip; the engine's route in forward_impl, without a network) -------------------
+int sbgm_final_compose_pack(const float* w1_oihw, const float* b1, const float* w2_oihw, float* wc_oihw, float* bc, int C, void* stream) {
+    return sbgm_launch_final_compose(w1_oihw, b1, w2_oihw, wc_oihw, bc, C, (hipStream_t)stream);
+}
+
+extern "C++" {
+// the block's convolution: bilinear x2 on load where the decoder fuses it (width >= 32), else a plain one on an upsampled copy
+static bool final_block_fused(int W) { return W >= 32; }
+static ConvParams final_block_conv(int B, int H, int W, int C) {
+    ConvParams p{};
+    p.B = B; p.H = H; p.W = W; p.Cs = C; p.Cout = 16;
+    p.in_mode = final_block_fused(W) ? 2 : 0;
+    return p;
+}
+}  // extern "C++"
+
+int sbgm_final_block_tiles(int B, int H, int W, int C, int* tiles, int cap) {
+    static const float present = 0.f;                 // the candidate list only asks which weight images exist
+    ConvParams p = final_block_conv(B, H, W, C);
+    p.wp = p.wp_wino = p.wp_w2d = &present;
+    const std::vector<ConvTile> c = conv_candidates(ConvGeom{3, 3, 1, 1}, p, false);
+    for (int i = 0; i < (int)c.size() && i < cap; ++i) {
+        const int v[6] = {c[i].fco, c[i].fpx, c[i].splits, c[i].ws, c[i].wino, c[i].lds};
+        std::memcpy(tiles + 6 * i, v, sizeof v);
+    }
+    return (int)c.size();
+}
+
+int sbgm_final_block_fwd(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* w_packed,
+                         const float* w_wino, const float* w_wino2d, const float* bc, const float* b2, const float* t, float sigma,
+                         float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, const int* tile, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(x && w_packed && w_wino && bc && b2 && out && ws, "final_block_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 2 && H % 2 == 0 && W >= 16 && W % 16 == 0 && C >= 16 && C % 16 == 0,
+               "final_block_fwd: needs an even H, W %% 16 == 0 and C %% 16 == 0 (B=%d H=%d W=%d C=%d)", B, H, W, C);
+    const size_t M = (size_t)B * H * W;
+    const bool fused = final_block_fused(W);
+    SBGM_CHECK(fused || (!in_affine && !in_skip && in_act == SBGM_ACT_NONE), "final_block_fwd: affine / skip / activation on load need the fused route (W >= 32)");
+    SBGM_CHECK((size_t)ws_floats >= M * (fused ? 16 : 16 + (size_t)C), "final_block_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    ConvParams p = final_block_conv(B, H, W, C);
+    p.wp = w_packed; p.wp_wino = w_wino; p.wp_w2d = w_wino2d; p.bias = bc; p.out = ws;
+    if (fused) {
+        p.x = x; p.in_affine = in_affine; p.in_skip = in_skip; p.in_act = in_act;
+    } else {
+        float* up = ws + M * 16;
+        if (sbgm_launch_upsample2x(x, up, B, H / 2, W / 2, C, st)) return 1;
+        p.x = up;
+    }
+    const ConvTile ct = tile ? ConvTile{tile[0], tile[1], tile[2], tile[3], tile[4], tile[5]} : cout16_tile(p);
+    SBGM_CHECK(ct.fco == 1 && ct.splits == 1 && ct.lds >= 1 && (ct.wino == 1 || (ct.wino == 2 && w_wino2d)),
+               "final_block_fwd: tile {%d,%d,%d,%d,%d,%d} is no 16-channel LDS-staged Winograd kernel", ct.fco, ct.fpx, ct.splits, ct.ws, ct.wino, ct.lds);
+    if (launch_tile(ConvGeom{3, 3, 1, 1}, p, ct, nullptr, st)) return 1;
+    return sbgm_launch_tap_gather_rows(ws, b2, t, sigma, out, B, H, W, st);
 }
 
 int sbgm_event_create(void** ev) { hipEvent_t e; SBGM_HIP(hipEventCreate(&e)); *ev = e; return 0; }

@@ -110,6 +110,14 @@ int sbgm_launch_conv_stem22(const float* src, int nch, int c0, int Cin, const fl
                             const float* addend, const float* scale, const float* bias, int relu, float* out, int B, int H, int W,
                             hipStream_t st);
 
+// ---- conv_final.hip: the final DecoderBlock's conv(conv_up(.)) composed into one 3x3 convolution to the 9 taps of `conv` -------------
+// w1 OIHW [C][C][3][3], b1 [C] (conv_up), w2 OIHW [1][C][3][3] (conv) -> wc OIHW [16][C][3][3] (rows 9..15 zero), bc [16]
+int sbgm_launch_final_compose(const float* w1_oihw, const float* b1, const float* w2_oihw, float* wc_oihw, float* bc, int C,
+                              hipStream_t st);
+// sbgm_launch_tap_stencil over the pixel-major rows d [B][H][W][16] a 16-channel convolution writes (floats 0..8 of a row = the taps)
+int sbgm_launch_tap_gather_rows(const float* d, const float* bias, const float* t, float sigma, float* out, int B, int H, int W,
+                                hipStream_t st);
+
 // ---- pointwise.hip ---------------------------------------------------------------------------------
 struct PackSrc {
     const float* ptr[4];   // NCHW sources, concatenated along C in this order
