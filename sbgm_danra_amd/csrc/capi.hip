@@ -52,50 +52,12 @@ int sbgm_conv_pack_weight(const float* w_oihw, float* packed, int Cout, int Cin,
 }
 
 int sbgm_conv2d_fwd(const sbgm_conv_args* a, void* stream) {
-    SBGM_CHECK(a && a->x && a->w_packed && a->out, "conv2d: null tensor");
-    ConvParams p{};
-    p.x = a->x; p.wp = a->w_packed; p.out = a->out; p.scale = a->scale; p.bias = a->bias; p.tbias = a->tbias;
-    p.res = a->residual; p.B = a->B; p.H = a->H; p.W = a->W; p.Cs = a->c_pad; p.Cout = a->Cout;
-    p.act = a->act;
-    SBGM_CHECK(a->act == SBGM_NONE || a->act == SBGM_RELU || a->act == SBGM_GELU, "conv2d: act must be none, relu or gelu");
-    p.tbias_after_act = a->tbias_after_act;
-    p.in_dil = a->in_dil; p.out_h = a->out_h; p.out_w = a->out_w;
-    p.in_mode = a->in_mode; p.in_affine = a->in_affine; p.in_skip = a->in_skip; p.in_act = a->in_act;
-    if (a->winograd & 32) {                  // 8x8/s2/p3 as space-to-depth Winograd F(2x2,4x4) (conv_s2w.hip): weights from sbgm_conv8x8s2_wino_pack_weight
-        SBGM_CHECK((a->winograd & ~32) == 0 && a->in_mode == 0, "conv2d: winograd bit 5 stands alone and takes no in_mode");
-        SBGM_CHECK(a->KH == 8 && a->KW == 8 && a->stride == 2 && a->pad == 3 && a->in_dil <= 1, "conv2d: the F(2x2,4x4) path is 8x8 stride 2 pad 3 only");
-        SBGM_CHECK(a->tile_co == 0 || a->tile_co == 1 || a->tile_co == 2, "conv2d: winograd bit 5 takes tile_co 1 or 2");
-        return sbgm_launch_conv_s2w(p, ConvTile{a->tile_co ? a->tile_co : 2, 1, 1, 1, 3, 1}, ST);
-    }
-    SBGM_CHECK(a->in_mode == 0 || (a->winograd & 3) == 3 || (a->winograd & 8), "conv2d: in_mode %d needs an LDS-staged Winograd kernel (winograd bits 0 and 1, or bit 3)", a->in_mode);
-    if (a->winograd & 8) {                   // 2-D Winograd F(2x2,3x3), LDS-staged (conv_w2d.hip): weights from sbgm_conv_wino2d_pack_weight
-        SBGM_CHECK(a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->in_dil <= 1, "conv2d: the 2-D Winograd path is 3x3 stride 1 pad 1 only");
-        SBGM_CHECK(a->w_wino2d || !(a->winograd & 3), "conv2d: winograd bit 3 beside bits 0/1 needs w_wino2d");
-        if (a->w_wino2d) p.wp = a->w_wino2d;
-        const ConvTile t2{a->tile_co ? a->tile_co : 2, 1, 1, (a->winograd & 16) ? 2 : (a->waves_per_tile == 2 ? 2 : 1), 2,
-                          (a->winograd & 16) ? 3 : (a->winograd & 4) ? 2 : 1};
-        return sbgm_launch_conv_w2d(p, t2, ST);
-    }
-    if ((a->winograd & 1) && a->w_wino) p.wp = a->w_wino;
-    ConvTile t{a->tile_co ? a->tile_co : (a->Cout % 64 == 0 ? 4 : 2), a->tile_px ? a->tile_px : 2, a->splits ? a->splits : 1,
-               a->waves_per_tile ? a->waves_per_tile : 1, a->winograd & 1, (a->winograd & 2) ? ((a->winograd & 4) ? 2 : 1) : 0};
-    if (a->winograd & 2) {
-        SBGM_CHECK(a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->in_dil <= 1, "conv2d: the LDS path is 3x3 stride 1 pad 1 only");
-        if (!a->tile_px) t.fpx = 1;
-        return sbgm_launch_conv_lds(p, t, ST);
-    }
-    if (a->winograd & 1) {
-        SBGM_CHECK(a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad == 1 && a->in_dil <= 1, "conv2d: Winograd path is 3x3 stride 1 pad 1 only");
-        if (!a->tile_px) t.fpx = 1;
-        return sbgm_launch_conv_wino(p, t, ST);
-    }
-    SBGM_CHECK(a->Cout % 32 == 0, "conv2d: Cout=%d must be a multiple of 32", a->Cout);
-    if (t.splits > 1) {
-        const int OH = a->out_h > 0 ? a->out_h : (a->H + 2 * a->pad - a->KH) / a->stride + 1;
-        const int OW = a->out_w > 0 ? a->out_w : (a->W + 2 * a->pad - a->KW) / a->stride + 1;
-        SBGM_CHECK(a->ws && a->ws_floats >= (int64_t)t.splits * a->B * OH * OW * a->Cout, "conv2d: split-K workspace too small");
-    }
-    return sbgm_launch_conv(ConvGeom{a->KH, a->KW, a->stride, a->pad}, p, t, a->ws, ST);
+    ConvGeom g;
+    ConvParams p;
+    ConvImages w;
+    ConvTile t;
+    if (sbgm_conv_from_args(a, &g, &p, &w, &t)) return 1;
+    return sbgm_launch_tile(g, p, w, t, a->ws, ST);
 }
 
 int sbgm_conv_pack_weights_batched_blocks(int Cout, int KH, int KW, int c_pad) { return sbgm_conv_pack_blocks(Cout, KH, KW, c_pad); }
@@ -177,18 +139,16 @@ int sbgm_wgrad_flush_pending(void) { return sbgm_wgrad_pending(); }
 int sbgm_wgrad_discard(void) { const int n = sbgm_wgrad_pending(); sbgm_wgrad_discard_queue(); return n; }
 
 int sbgm_conv2d_tune(const sbgm_conv_args* a, int* tile, void* stream) {
-    SBGM_CHECK(a && tile && a->x && a->w_packed && a->out, "conv2d_tune: null argument");
+    SBGM_CHECK(a && tile, "conv2d_tune: null argument");
+    SBGM_CHECK(a->winograd == 0, "conv2d_tune: winograd must be 0 (the search decides the kernel; w_wino / w_wino2d say which images exist)");
     SBGM_CHECK(a->Cout % 32 == 0, "conv2d_tune: Cout=%d must be a multiple of 32", a->Cout);
-    ConvParams p{};
-    p.x = a->x; p.wp = a->w_packed; p.out = a->out; p.scale = a->scale; p.bias = a->bias; p.tbias = a->tbias;
-    p.res = a->residual; p.B = a->B; p.H = a->H; p.W = a->W; p.Cs = a->c_pad; p.Cout = a->Cout;
-    p.act = a->act; p.tbias_after_act = a->tbias_after_act;
-    p.in_dil = a->in_dil; p.out_h = a->out_h; p.out_w = a->out_w;
-    p.wp_wino = a->w_wino;
-    p.wp_w2d = a->w_wino2d;
-    ConvTile best{a->Cout % 64 == 0 ? 4 : 2, 2, 1, 1, 0, 0};
-    if (sbgm_tune_conv(ConvGeom{a->KH, a->KW, a->stride, a->pad}, p, a->ws, a->ws ? (size_t)a->ws_floats : 0, ST, &best)) return 1;
-    tile[0] = best.fco; tile[1] = best.fpx; tile[2] = best.splits; tile[3] = best.ws; tile[4] = best.wino; tile[5] = best.lds;
+    ConvGeom g;
+    ConvParams p;
+    ConvImages w;
+    ConvTile best;                      // the call's own tile (the default one when its tile fields are zero) is the fallback
+    if (sbgm_conv_from_args(a, &g, &p, &w, &best)) return 1;
+    if (sbgm_tune_conv(g, p, w, a->ws, a->ws ? (size_t)a->ws_floats : 0, ST, &best)) return 1;
+    best.to_ints(tile);
     return 0;
 }
 

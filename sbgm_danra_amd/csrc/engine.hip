@@ -33,16 +33,22 @@ struct Param {
     ParamKind kind = P_VEC;
     int64_t numel = 0;          // element count in reference layout
     int cout = 0, cin = 0, kh = 1, kw = 1, cs = 0;   // P_CONV geometry (cs = padded Cin)
-    float* dev = nullptr;       // engine storage (packed for P_CONV / P_COUT1)
-    size_t dev_floats = 0;
-    bool wino = false;          // 3x3 stride-1 conv: keep a Winograd F(2,3) packed copy as well
-    float* dev_wino = nullptr;
-    size_t wino_floats = 0;
-    float* dev_w2d = nullptr;   // ... and a 2-D Winograd F(2x2,3x3) packed copy (conv_w2d.hip)
-    size_t w2d_floats = 0;
-    float* dev_s2w = nullptr;   // 8x8 conv with Cin padded to 16: a space-to-depth F(2x2,4x4) packed copy (conv_s2w.hip)
-    size_t s2w_floats = 0;
+    bool want_wino = false;     // P_CONV: keep the Winograd images the geometry has as well (sbgm_conv_image_floats)
+    float* img[CONV_IMAGES] = {};      // engine storage: the packed images of a convolution weight; index 0 alone for every other kind
+    size_t floats[CONV_IMAGES] = {};
     bool filled = false;
+    float* dev() const { return img[IMG_IGEMM]; }
+    ConvImages images() const { ConvImages w; std::copy(img, img + CONV_IMAGES, w.img); return w; }
+    size_t storage_floats() const {
+        size_t n = 0;
+        for (size_t f : floats) n += align_up(f, 64);
+        return n;
+    }
+    float* place(float* at) {   // lays the images out from `at`, returns the end
+        for (int i = 0; i < CONV_IMAGES; ++i)
+            if (floats[i]) { img[i] = at; at += align_up(floats[i], 64); }
+        return at;
+    }
 };
 
 struct ConvW { Param* w = nullptr; Param* b = nullptr; };          // weight (+ optional bias)
@@ -50,29 +56,6 @@ struct BNW { Param *g, *b, *rm, *rv; float *scale, *bias; };       // + folded e
 struct AttnW { Param *ln1g, *ln1b, *ln2g, *ln2b, *inw, *inb, *outw, *outb, *f1w, *f1b, *f2w, *f2b; int C; };
 struct BlockW { ConvW c1, c2, ds; BNW bn1, bn2, dsbn; bool has_ds; int cin, cout, stride; };
 struct DecW { ConvW up, conv; Param *n1g, *n1b, *n2g, *n2b, *freq, *tpw, *tpb; AttnW attn; bool has_attn; int cin, cout; };
-
-// one launch of a tuned tile: picks the kernel family and the weight image it reads
-int launch_tile(const ConvGeom& g, ConvParams p, const ConvTile& ct, float* partial, hipStream_t st) {
-    if (ct.wino == 2) { p.wp = p.wp_w2d; return sbgm_launch_conv_w2d(p, ct, st); }
-    if (ct.wino == 3) {
-        SBGM_CHECK(g.kh == 8 && g.kw == 8 && g.stride == 2 && g.pad == 3, "launch_tile: the F(2x2,4x4) kernel is 8x8 stride 2 pad 3 only");
-        p.wp = p.wp_s2w;
-        return sbgm_launch_conv_s2w(p, ct, st);
-    }
-    if (!ct.wino && !ct.lds) return sbgm_launch_conv(g, p, ct, partial, st);
-    if (ct.wino) p.wp = p.wp_wino;
-    return ct.lds ? sbgm_launch_conv_lds(p, ct, st) : sbgm_launch_conv_wino(p, ct, st);
-}
-// GroupNorm statistics the launch above leaves in p.gn_stats (chunks per sample), 0 = none
-int tile_gn_chunks(const ConvParams& p, const ConvTile& ct) {
-    if (ct.wino == 3) return 0;
-    return ct.wino == 2 ? sbgm_conv_w2d_gn_chunks(p, ct) : sbgm_conv_lds_gn_chunks(p, ct);
-}
-
-struct ConvOpKey {
-    int kh, kw, s, p, B, H, W, Cs, Cout, proj, in_mode;
-    bool operator<(const ConvOpKey& o) const { return std::memcmp(this, &o, sizeof(*this)) < 0; }
-};
 
 }  // namespace
 
@@ -162,25 +145,19 @@ struct sbgm_model {
     static bool fin_enabled() { static const bool on = getenv("SBGM_NO_FINAL_COMPOSE") == nullptr; return on; }
     int fin_build(int ci) {
         // the 16-channel op runs on the LDS-staged Winograd kernels only, so the switches that take those away keep the projection path
-        fin_route = fin_enabled() && !cfg.decoder_transpose && ci % 16 == 0 && fin_up.w->wino && getenv("SBGM_NO_LDS_CONV") == nullptr &&
-                    getenv("SBGM_STATIC_ROUND1") == nullptr;
+        fin_route = fin_enabled() && !cfg.decoder_transpose && ci % 16 == 0 && fin_up.w->img[IMG_WINO] != nullptr &&
+                    !sbgm_conv_switches().no_lds && !sbgm_conv_switches().round1;
         if (!fin_route) return 0;
         fin_cw.name = "final_layer.composed.weight"; fin_cw.kind = P_CONV; fin_cw.numel = (int64_t)16 * ci * 9;
-        fin_cw.cout = 16; fin_cw.cin = ci; fin_cw.kh = fin_cw.kw = 3; fin_cw.cs = ci; fin_cw.wino = true;
-        fin_cw.dev_floats = (size_t)sbgm_conv_nsteps(3, 3, ci) * 16 * 16;
-        fin_cw.wino_floats = sbgm_wino_packed_floats(16, ci);
-        fin_cw.w2d_floats = fin_up.w->w2d_floats ? sbgm_w2d_packed_floats(16, ci) : 0;
-        fin_cb.name = "final_layer.composed.bias"; fin_cb.numel = fin_cb.dev_floats = 16;
+        fin_cw.cout = 16; fin_cw.cin = ci; fin_cw.kh = fin_cw.kw = 3; fin_cw.cs = ci; fin_cw.want_wino = true;
+        sbgm_conv_image_floats(3, 3, ci, 16, true, fin_cw.floats);
+        fin_cb.name = "final_layer.composed.bias"; fin_cb.numel = fin_cb.floats[0] = 16;
         const size_t wc_floats = align_up((size_t)fin_cw.numel, 64);
-        const size_t total = wc_floats + 64 + align_up(fin_cw.dev_floats, 64) + align_up(fin_cw.wino_floats, 64) + align_up(fin_cw.w2d_floats, 64);
+        const size_t total = wc_floats + fin_cb.storage_floats() + fin_cw.storage_floats();
         SBGM_HIP(hipMalloc(&fin_img, total * 4));
         SBGM_HIP(hipMemset(fin_img, 0, total * 4));
-        float* q = fin_img;
-        fin_wc = q; q += wc_floats;
-        fin_cb.dev = q; q += 64;
-        fin_cw.dev = q; q += align_up(fin_cw.dev_floats, 64);
-        fin_cw.dev_wino = q; q += align_up(fin_cw.wino_floats, 64);
-        if (fin_cw.w2d_floats) fin_cw.dev_w2d = q;
+        fin_wc = fin_img;
+        fin_cw.place(fin_cb.place(fin_img + wc_floats));
         fin_cw.filled = fin_cb.filled = true;
         fin_comp = ConvW{&fin_cw, &fin_cb};
         return 0;
@@ -195,10 +172,8 @@ struct sbgm_model {
         if (!fin_route || !fin_dirty) return 0;
         SBGM_CHECK(fin_w1 && fin_w2 && fin_up.b->filled, "final block: final_layer.conv_up / conv weights were never uploaded");
         const int ci = fin_cw.cin;
-        if (sbgm_launch_final_compose(fin_w1, fin_up.b->dev, fin_w2, fin_wc, fin_cb.dev, ci, st)) return 1;
-        if (sbgm_launch_pack_conv_weight(fin_wc, fin_cw.dev, 16, ci, 3, 3, ci, st)) return 1;
-        if (sbgm_launch_pack_wino_weight(fin_wc, fin_cw.dev_wino, 16, ci, ci, st)) return 1;
-        if (fin_cw.dev_w2d && sbgm_launch_pack_w2d_weight(fin_wc, fin_cw.dev_w2d, 16, ci, ci, st)) return 1;
+        if (sbgm_launch_final_compose(fin_w1, fin_up.b->dev(), fin_w2, fin_wc, fin_cb.dev(), ci, st)) return 1;
+        if (sbgm_pack_conv_images(fin_wc, fin_cw.img, 16, ci, 3, 3, ci, st)) return 1;
         fin_dirty = false;
         return 0;
     }
@@ -220,7 +195,7 @@ struct sbgm_model {
     size_t h_stage_bytes = 0;
     hipEvent_t ev_stage = nullptr;
     bool stage_pending = false;
-    std::map<ConvOpKey, ConvTile> tuned;
+    ConvTileTable tuned;
     ConvTile last_tile{};                   // tile of the most recent conv() (tells the caller whether GroupNorm statistics were fused)
     bool tuning = false;
     struct ConvRec { ConvGeom g; int B, H, W, Cs, Cout, M, nsteps; ConvTile t; double flops; hipEvent_t e0, e1; float ms; int c_real; int in_mode; int proj; };
@@ -302,7 +277,7 @@ struct sbgm_model {
         Param* p = add(n, P_CONV, (int64_t)cout * cin * kh * kw);
         p->cout = cout; p->cin = cin; p->kh = kh; p->kw = kw;
         p->cs = cs ? cs : (int)align_up(cin, 16);
-        p->wino = wino && kh == 3 && kw == 3 && p->cs % 16 == 0 && getenv("SBGM_NO_WINOGRAD") == nullptr;
+        p->want_wino = wino;
         return p;
     }
     BNW bn(const std::string& pre, int c) {
@@ -365,9 +340,11 @@ struct sbgm_model {
         return fwd_need(B, H, W, bn_train) + sampler_keep(B, H, W, slabs);
     }
     int fold_bn(hipStream_t st);
-    ConvTile pick_tile(const ConvGeom& g, const ConvParams& p);
-    int conv(const ConvGeom& g, ConvParams p, hipStream_t st);
-    int launch_any(const ConvGeom& g, ConvParams p, const ConvTile& ct, hipStream_t st) { return launch_tile(g, p, ct, partial, st); }
+    ConvTile pick_tile(const ConvGeom& g, const ConvParams& p, const ConvImages& im) const {      // the tuned tile, else the static choice
+        const auto it = tuned.find(sbgm_conv_op_key(g, p));
+        return it != tuned.end() ? it->second : sbgm_static_tile(g, p, im);
+    }
+    int conv(const ConvGeom& g, ConvParams p, const Param& w, hipStream_t st);
     int attention(const AttnW& a, float* x, int B, int S, hipStream_t st);
     int forward_impl(const float* x, const float* t, const int64_t* y, const float* cond, const float* lsm, const float* topo,
                      float* out, float* const* fmaps_out, int B, int H, int W, int bn_train, hipStream_t st);
@@ -435,7 +412,7 @@ int sbgm_model::build(const sbgm_model_config& c) {
             enc_attn[i] = attn("encoder.attention_layers." + std::to_string(i), FMAP_CH[i]);
         }
     }
-    conv2.w = convw("encoder.conv2.weight", 64, 64, 8, 8);
+    conv2.w = convw("encoder.conv2.weight", 64, 64, 8, 8, 0, true);       // conv1 keeps the implicit-GEMM kernels alone
     if (c.num_classes > 0) label_emb = vec("encoder.label_emb.weight", (int64_t)(c.num_classes + 1) * D);
     // ---- decoder ---------------------------------------------------------------------------------------------------
     int dc = c.last_fmap_channels;
@@ -485,15 +462,11 @@ int sbgm_model::build(const sbgm_model_config& c) {
     size_t total = 0;
     for (auto& up : params) {
         Param* p = up.get();
-        if (p->kind == P_CONV || p->kind == P_TCONV) p->dev_floats = (size_t)sbgm_conv_nsteps(p->kh, p->kw, p->cs) * p->cout * 16;
-        else if (p->kind == P_VEC4) p->dev_floats = (size_t)p->numel * 4;
-        else if (p->kind == P_IGNORE) p->dev_floats = 0;
-        else p->dev_floats = (size_t)p->numel;
-        if (p->wino) p->wino_floats = sbgm_wino_packed_floats(p->cout, p->cs);
-        if (p->wino && getenv("SBGM_NO_WINOGRAD2D") == nullptr) p->w2d_floats = sbgm_w2d_packed_floats(p->cout, p->cs);
-        if (p->kind == P_CONV && p->kh == 8 && p->kw == 8 && p->cs % 16 == 0 && p->cout % 16 == 0 && getenv("SBGM_NO_WINOGRAD") == nullptr)
-            p->s2w_floats = sbgm_s2w_packed_floats(p->cout, p->cs);
-        total += align_up(p->dev_floats, 64) + align_up(p->wino_floats, 64) + align_up(p->w2d_floats, 64) + align_up(p->s2w_floats, 64);
+        if (p->kind == P_CONV || p->kind == P_TCONV) sbgm_conv_image_floats(p->kh, p->kw, p->cs, p->cout, p->want_wino, p->floats);
+        else if (p->kind == P_VEC4) p->floats[0] = (size_t)p->numel * 4;
+        else if (p->kind == P_IGNORE) p->floats[0] = 0;
+        else p->floats[0] = (size_t)p->numel;
+        total += p->storage_floats();
     }
     // folded BN scale/bias
     size_t bn_floats = 0;
@@ -507,10 +480,7 @@ int sbgm_model::build(const sbgm_model_config& c) {
     size_t off = 0;
     for (auto& up : params) {
         Param* p = up.get();
-        if (p->dev_floats) { p->dev = arena + off; off += align_up(p->dev_floats, 64); }
-        if (p->wino_floats) { p->dev_wino = arena + off; off += align_up(p->wino_floats, 64); }
-        if (p->w2d_floats) { p->dev_w2d = arena + off; off += align_up(p->w2d_floats, 64); }
-        if (p->s2w_floats) { p->dev_s2w = arena + off; off += align_up(p->s2w_floats, 64); }
+        off = p->place(arena + off) - arena;
         if (p->kind == P_IGNORE) p->filled = true;
     }
     auto place_bn = [&](BNW& b, int c_) {
@@ -521,7 +491,7 @@ int sbgm_model::build(const sbgm_model_config& c) {
     for (int li = 0; li < 4; ++li)
         for (auto& b : layers[li]) { place_bn(b.bn1, b.cout); place_bn(b.bn2, b.cout); if (b.has_ds) place_bn(b.dsbn, b.cout); }
     SBGM_HIP(hipMalloc(&d_state, sizeof(SamplerState)));
-    return fin_build(dec[3].cout);           // after the loop above: it mirrors which images final_layer.conv_up has
+    return fin_build(dec[3].cout);           // after the loop above: the route needs final_layer.conv_up to have its Winograd image
 }
 
 int sbgm_model::ensure_ws(size_t bytes) {
@@ -550,7 +520,7 @@ size_t sbgm_model::fwd_need(int B, int H, int W, int bn_train) const {
 
 int sbgm_model::fold_bn(hipStream_t st) {
     auto f = [&](BNW& b, int c) {
-        return sbgm_launch_bn_fold(b.g->dev, b.b->dev, b.rm->dev, b.rv->dev, BN_EPS, b.scale, b.bias, c, st);
+        return sbgm_launch_bn_fold(b.g->dev(), b.b->dev(), b.rm->dev(), b.rv->dev(), BN_EPS, b.scale, b.bias, c, st);
     };
     if (f(bn1, 64)) return 1;
     for (int li = 0; li < 4; ++li)
@@ -562,252 +532,24 @@ int sbgm_model::fold_bn(hipStream_t st) {
     return 0;
 }
 
-// Static choice for a convolution the autotuner has not timed.  It follows what the tuner picks on the BASELINE shapes and on
-// small batches (profiles/r03_c2_tiles.txt, r03_c4_tiles.txt; B = 1, 2, 8 tables in DESIGN.md 3.2), so a sampler that never called
-// sbgm_model_autotune runs within a few per cent of a tuned one instead of on the round-1 kernels:
-//   3x3 stride 1, >= 512 tiles of 16x16 pixels x 16 channels (or the final projection): 2-D Winograd F(2x2,3x3) (conv_w2d.hip) — the
-//     persistent 32-channel kernel once there are >= 512 such tiles (two per CU), 16-channel double-buffered workgroups below;
-//   fewer tiles, or a fused input mode: the LDS-staged 1-D Winograd kernel on 16-channel slices (conv_lds.hip);
-//   3x3 stride 1 with >= 2048 pixels of >= 128 channels (the 8x8 / 4x4 maps of a full batch): 1-D Winograd (conv_wino.hip), the largest
-//     tile that still gives >= 256 workgroups, the K loop split over 4 or 8 waves;
-//   small problems of any geometry (< 1024 tiles of 32 channels x 16 pixels): that smallest wave tile, K split over the 4 waves of
-//     a workgroup and over up to 8 workgroups;
-//   8x8 stride 2 pad 3 on a 16-channel-padded input (the stem's second convolution) with >= 256 workgroups: space-to-depth Winograd
-//     F(2x2,4x4) (conv_s2w.hip), 32-channel workgroups while they still fill 256 CUs, 16-channel ones below;
-//   everything else (strided, 1x1, the stem): wave tiles that fill ~2 waves per SIMD.
-static bool s2w_ok(const ConvGeom& g, const ConvParams& p) {
-    return p.wp_s2w != nullptr && g.kh == 8 && g.kw == 8 && g.stride == 2 && g.pad == 3 && p.in_dil <= 1 && p.in_mode == 0 &&
-           p.proj_w == nullptr && p.c_real == 0 && p.Cs % 16 == 0 && p.Cout % 16 == 0 && p.out_h == 0 && p.out_w == 0;
-}
-// 16 output channels (the composed final block): only the one-co-tile LDS-staged Winograd kernels serve it.  Timed alone at batch
-// 32 x 128^2 / batch 16 x 256^2 (convolution + gather, inputs evicted): 2-D Winograd one-tile with one stage buffer 89 / 162 us,
-// persistent 90 / 174 us, row-only 1-D Winograd 97-100 / 172 us, every double-buffered form 113-127 / 200-237 us.  The autotuner
-// picks the same one-tile kernel inside the network (profiles/r06_c2_tiles.txt, r06_c4_tiles.txt: 81 / 154 us per launch).
-static ConvTile cout16_tile(const ConvParams& p) {
-    const ConvTile w2d{1, 1, 1, 1, 2, 1}, row{1, 1, 1, 1, 1, 1};
-    if (p.wp_w2d != nullptr && p.H % 2 == 0 && sbgm_conv_w2d_bytes(w2d, p.in_mode) <= 160 * 1024) return w2d;
-    return row;
-}
-ConvTile sbgm_model::pick_tile(const ConvGeom& g, const ConvParams& p) {
-    const int OH = (p.H + 2 * g.pad - g.kh) / g.stride + 1, OW = (p.W + 2 * g.pad - g.kw) / g.stride + 1;
-    ConvOpKey key{g.kh, g.kw, g.stride, g.pad, p.B, p.H, p.W, p.Cs, p.Cout, p.proj_w != nullptr, p.in_mode};
-    auto it = tuned.find(key);
-    if (it != tuned.end()) return it->second;
-    static const bool round1 = getenv("SBGM_STATIC_ROUND1") != nullptr;      // the round-1 table (A/B of this function)
-    static const bool lds_ok = getenv("SBGM_NO_LDS_CONV") == nullptr && !round1;
-    const bool s1 = g.kh == 3 && g.kw == 3 && g.stride == 1 && g.pad == 1 && p.in_dil <= 1;
-    const int M = p.B * OH * OW;
-    const int nsteps = sbgm_conv_nsteps(g.kh, g.kw, p.c_real == 2 ? 2 : p.Cs);
-    if (s2w_ok(g, p) && !round1) {
-        const long tiles = (long)p.B * ((OH + 15) / 16) * ((OW + 15) / 16);
-        if (p.Cout % 32 == 0 && tiles * (p.Cout / 32) >= 256) return ConvTile{2, 1, 1, 1, 3, 1};
-        if (tiles * (p.Cout / 16) >= 256) return ConvTile{1, 1, 1, 1, 3, 1};
-    }
-    if (lds_ok && s1 && p.W % 16 == 0 && p.H % 2 == 0 && p.Cs % 16 == 0) {
-        const long tiles16 = (long)p.B * (p.W / 16) * ((p.H + 15) / 16) * (p.Cout / 16);
-        if (p.Cout == 16 && !p.proj_w && p.wp_wino != nullptr) return cout16_tile(p);
-        if (p.wp_w2d != nullptr && (tiles16 >= 512 || p.proj_w)) {
-            const ConvTile big{2, 1, 1, 2, 2, 3}, mid{1, 1, 1, 2, 2, 3};
-            if (p.Cout % 32 == 0 && tiles16 >= 1024 && sbgm_conv_w2d_bytes(big, p.in_mode) <= 160 * 1024) return big;
-            if (p.proj_w && sbgm_conv_w2d_bytes(mid, p.in_mode) <= 160 * 1024) return mid;
-            for (int lds : {2, 1}) {
-                const ConvTile small{1, 1, 1, 1, 2, lds};
-                if (!p.proj_w && sbgm_conv_w2d_bytes(small, p.in_mode) <= 160 * 1024) return small;
-            }
-        }
-        if (p.wp_wino != nullptr && !p.proj_w && (p.in_mode != 0 || tiles16 >= 256 || (tiles16 >= 128 && p.W >= 32)))
-            for (int lds : {2, 1}) {
-                const ConvTile t{1, 1, 1, 1, 1, lds};
-                if (sbgm_conv_lds_bytes(t, p.in_mode) <= 160 * 1024) return t;
-            }
-    }
-    if (p.in_mode != 0) return ConvTile{p.Cout % 64 == 0 ? 4 : 2, 1, 1, 1, 1, 1};     // fused input modes: LDS-staged Winograd tiles only
-    const bool wino_ok = p.wp_wino != nullptr && s1 && p.W % 2 == 0;
-    if (wino_ok && p.proj_w) return ConvTile{p.Cout / 16, 1, 1, 1, 1, 0};
-    if (wino_ok && !round1 && ((M >= 2048 && p.Cs >= 128) || (M >= 512 && p.Cs >= 512 && p.Cout >= 512))) {
-        const int ns = 3 * (p.Cs / 16);
-        const int wt[3][2] = {{4, 2}, {4, 1}, {2, 1}};
-        for (auto& t : wt) {
-            if (p.Cout % (16 * t[0])) continue;
-            const long wgs = (long)((M + 32 * t[1] - 1) / (32 * t[1])) * (p.Cout / (16 * t[0]));
-            if (wgs >= 256 || (t[0] == 2 && t[1] == 1)) {
-                int ws = t[1] == 2 ? 4 : ((p.Cs >= 512 || wgs < 512) ? 8 : 4);
-                while (ws > 1 && ns / ws < 2) ws >>= 1;
-                return ConvTile{t[0], t[1], 1, ws, 1, 0};
-            }
-        }
-    }
-    if (wino_ok && round1) {                          // Winograd F(2,3): 1.5x fewer MFMAs; pick waves-per-tile to fill the chip
-        const int Mp = p.B * OH * OW / 2, ns = 3 * (p.Cs / 16);
-        const long tiles = (long)((Mp + 31) / 32) * (p.Cout / 32);          // (2,2) tiles: 32 channels x 64 pixels
-        const int ws = tiles >= 2048 ? 1 : (tiles >= 1024 || ns < 8) ? 2 : 4;
-        return ConvTile{2, 2, 1, ws, 1, 0};
-    }
-    if (p.proj_w) return ConvTile{p.Cout / 16, 2, 1, 1, 0, 0};
-    const long t21 = (long)((M + 15) / 16) * (p.Cout / 32);
-    if (!round1 && p.Cout % 32 == 0 && t21 < 1024) {
-        const int ws = nsteps >= 8 ? 4 : nsteps >= 4 ? 2 : 1;
-        int splits = 1;
-        while (splits < 8 && t21 * splits * 2 <= 256 && nsteps / (splits * 2 * ws) >= 4) splits *= 2;
-        return ConvTile{2, 1, splits, ws, 0, 0};
-    }
-    const int target = 2048;                 // ~2 waves per SIMD
-    const int cand[3][2] = {{4, 4}, {4, 2}, {2, 2}};
-    for (auto& c : cand) {
-        if (p.Cout % (16 * c[0])) continue;
-        const long tiles = (long)((M + 16 * c[1] - 1) / (16 * c[1])) * (p.Cout / (16 * c[0]));
-        for (int ws : {1, 2, 4})
-            if (tiles * ws >= target && nsteps / ws >= 2) return ConvTile{c[0], c[1], 1, ws, 0, 0};
-    }
-    // tiny problem: 64x32 (or 32x32) tiles, 4 waves per tile, plus split-K over the grid (>= 2 K-steps per wave)
-    const int fco = p.Cout % 64 == 0 ? 4 : 2, fpx = 2;
-    const long tiles = (long)((M + 16 * fpx - 1) / (16 * fpx)) * (p.Cout / (16 * fco));
-    const int ws = nsteps >= 8 ? 4 : nsteps >= 4 ? 2 : 1;
-    const int splits = (int)std::min<long>(std::max<long>(1, target / std::max<long>(1, tiles * ws)), std::max(1, nsteps / (2 * ws)));
-    return ConvTile{fco, fpx, splits, ws, 0, 0};
-}
-
-// The tile candidates (template x tile x waves-per-tile x split-K) of one convolution; split-K ones only with a partial buffer.
-static std::vector<ConvTile> conv_candidates(const ConvGeom& g, const ConvParams& p, bool partial) {
-    const int OH = p.out_h > 0 ? p.out_h : (p.H + 2 * g.pad - g.kh) / g.stride + 1;
-    const int OW = p.out_w > 0 ? p.out_w : (p.W + 2 * g.pad - g.kw) / g.stride + 1;
-    const int nsteps = sbgm_conv_nsteps(g.kh, g.kw, p.c_real == 2 ? 2 : p.Cs);
-    std::vector<ConvTile> cands;
-    const int tiles[6][2] = {{4, 4}, {4, 2}, {4, 1}, {2, 4}, {2, 2}, {2, 1}};
-    for (auto& t : tiles) {
-        if (p.in_mode != 0) break;                    // the fused input modes exist in the LDS-staged Winograd kernel only
-        if (p.Cout % (16 * t[0])) continue;
-        if (p.proj_w && 16 * t[0] != p.Cout) continue;
-        const long ntile = (long)(((size_t)p.B * OH * OW + 16 * t[1] - 1) / (16 * t[1])) * (p.Cout / (16 * t[0]));
-        for (int ws : {1, 2, 4}) {
-            if (ws > 1 && (nsteps / ws < 2 || ntile * ws > 32768)) continue;
-            for (int sp : {1, 2, 4, 8, 16}) {
-                if (sp > 1 && (p.proj_w || !partial || nsteps / (sp * ws) < 2 || ntile * ws >= 4096)) continue;   // already enough waves
-                cands.push_back(ConvTile{t[0], t[1], sp, ws, 0, 0});
-            }
-        }
-    }
-    const bool s1 = g.kh == 3 && g.kw == 3 && g.stride == 1 && g.pad == 1 && p.in_dil <= 1 &&
-                    (p.out_h == 0 || (p.out_h == p.H && p.out_w == p.W));
-    if (p.wp_wino != nullptr && s1 && p.W % 2 == 0 && p.in_mode == 0) {
-        const int wt[4][2] = {{4, 1}, {2, 2}, {2, 1}, {4, 2}};
-        const int nsw = 3 * (p.Cs / 16);
-        for (auto& t : wt) {
-            if (p.Cout % (16 * t[0])) continue;
-            if (p.proj_w && 16 * t[0] != p.Cout) continue;
-            for (int ws : {1, 2, 4, 8}) {
-                if (ws > 1 && nsw / ws < 2) continue;
-                cands.push_back(ConvTile{t[0], t[1], 1, ws, 1, 0});
-            }
-        }
-    }
-    if (s1 && p.W % 16 == 0 && p.Cs % 16 == 0 && getenv("SBGM_NO_LDS_CONV") == nullptr) {
-        const int dt[6][2] = {{4, 1}, {4, 2}, {4, 4}, {2, 2}, {2, 4}, {2, 1}};
-        auto lds_bytes = [](int fco, int rows_per_wave, bool wino) {
-            return ((size_t)(wino ? 12 : 9) * 16 * fco * 4 + (size_t)(4 * rows_per_wave + 2) * (wino ? 19 : 18) * 4) * 16;
-        };
-        for (auto& t : dt) {
-            if (p.in_mode != 0) break;
-            if (p.Cout % (16 * t[0]) || (p.proj_w && 16 * t[0] != p.Cout)) continue;
-            cands.push_back(ConvTile{t[0], t[1], 1, 1, 0, 1});
-            if (2 * lds_bytes(t[0], t[1], false) <= 160 * 1024) cands.push_back(ConvTile{t[0], t[1], 1, 1, 0, 2});   // double-buffered
-        }
-        const int wt2[6][2] = {{4, 1}, {4, 2}, {2, 1}, {2, 2}, {1, 1}, {1, 2}};   // 16-channel slices double the workgroup count of small layers
-        if (p.wp_wino)
-            for (auto& t : wt2) {
-                if (p.Cout % (16 * t[0]) || (p.proj_w && 16 * t[0] != p.Cout)) continue;
-                if (sbgm_conv_lds_bytes(ConvTile{t[0], t[1], 1, 1, 1, 1}, p.in_mode) <= 160 * 1024) cands.push_back(ConvTile{t[0], t[1], 1, 1, 1, 1});
-                if (sbgm_conv_lds_bytes(ConvTile{t[0], t[1], 1, 1, 1, 2}, p.in_mode) <= 160 * 1024) cands.push_back(ConvTile{t[0], t[1], 1, 1, 1, 2});
-            }
-    }
-    // 2-D Winograd F(2x2,3x3), LDS-staged: 16x16-pixel tiles, 16 or 32 channels per workgroup; a tap projection may span several
-    // channel tiles (partial planes).  ws = 2 selects the build that is held to two waves per SIMD.
-    if (p.wp_w2d != nullptr && s1 && p.W % 16 == 0 && p.H % 2 == 0 && p.Cs % 16 == 0 && getenv("SBGM_NO_LDS_CONV") == nullptr)
-        for (int fco : {2, 1}) {
-            if (p.Cout % (16 * fco)) continue;
-            for (int lds : {1, 2})
-                for (int ws : {1, 2}) {
-                    const ConvTile ct{fco, 1, 1, ws, 2, lds};
-                    if (fco == 1 && ws == 2) continue;
-                    if (sbgm_conv_w2d_bytes(ct, p.in_mode) <= 160 * 1024) cands.push_back(ct);
-                }
-            cands.push_back(ConvTile{fco, 1, 1, 2, 2, 3});       // persistent workgroups, LDS-DMA slab (two per CU)
-        }
-    // 8x8 stride 2 pad 3 as space-to-depth Winograd F(2x2,4x4): 16x16-output tiles, 16 or 32 channels per workgroup
-    if (s2w_ok(g, p))
-        for (int fco : {2, 1})
-            if (p.Cout % (16 * fco) == 0) cands.push_back(ConvTile{fco, 1, 1, 1, 3, 1});
-    return cands;
-}
-
-// Times the tile candidates (template x tile x waves-per-tile x split-K) of ONE convolution on its real operands and returns
-// the fastest in *best (in: the fallback).  A launch never reads what it writes, so repeating it is harmless.  Synchronises.
-int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, float* partial, size_t partial_floats, hipStream_t st, ConvTile* best) {
-    const int OH = p.out_h > 0 ? p.out_h : (p.H + 2 * g.pad - g.kh) / g.stride + 1;
-    const int OW = p.out_w > 0 ? p.out_w : (p.W + 2 * g.pad - g.kw) / g.stride + 1;
-    const size_t mc = (size_t)p.B * OH * OW * p.Cout;
-    auto launch = [&](const ConvTile& ct) -> int { return launch_tile(g, p, ct, partial, st); };
-    const std::vector<ConvTile> cands = conv_candidates(g, p, partial != nullptr);
-    hipEvent_t e0, e1;
-    SBGM_HIP(hipEventCreate(&e0));
-    SBGM_HIP(hipEventCreate(&e1));
-    const bool cold = getenv("SBGM_TUNE_WARM") == nullptr;
-    float best_ms = 1e30f;
-    int rc = 0;
-    for (int round = 0; round < 3 && !rc; ++round)          // three interleaved rounds, keep each candidate's best (DVFS / noise)
-        for (auto& ct : cands) {
-            if (ct.splits > 1 && mc * ct.splits > partial_floats) continue;
-            constexpr int REPS = 6;
-            float ms = 0.f;
-            if (cold && partial) {
-                // In the network a convolution finds its weights cold (the layers in between have streamed hundreds of MB
-                // through L2 / Infinity Cache), so every timed launch is preceded by an untimed 48 MiB fill that evicts them:
-                // ranking the candidates warm (back-to-back repeats) picked tiles that were 3 % slower per sampling step.
-                for (int rep = 0; rep < 3 && !rc; ++rep) {
-                    (void)hipMemsetAsync(partial, 0, std::min<size_t>(partial_floats * 4, (size_t)48 << 20), st);
-                    (void)hipEventRecord(e0, st);
-                    rc = launch(ct);
-                    (void)hipEventRecord(e1, st);
-                    (void)hipEventSynchronize(e1);
-                    float m1 = 0.f;
-                    (void)hipEventElapsedTime(&m1, e0, e1);
-                    ms += m1;
-                }
-                if (rc) break;
-            } else {
-                for (int rep = 0; rep <= REPS && !rc; ++rep) {
-                    if (rep == 1) (void)hipEventRecord(e0, st);
-                    rc = launch(ct);
-                }
-                if (rc) break;
-                (void)hipEventRecord(e1, st);
-                (void)hipEventSynchronize(e1);
-                (void)hipEventElapsedTime(&ms, e0, e1);
-            }
-            if (ms < best_ms) { best_ms = ms; *best = ct; }
-        }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-}
-
-int sbgm_model::conv(const ConvGeom& g, ConvParams p, hipStream_t st) {
+int sbgm_model::conv(const ConvGeom& g, ConvParams p, const Param& w, hipStream_t st) {
+    const ConvImages im = w.images();
     const int OH = (p.H + 2 * g.pad - g.kh) / g.stride + 1, OW = (p.W + 2 * g.pad - g.kw) / g.stride + 1;
     const size_t mc = (size_t)p.B * OH * OW * p.Cout;
     if (tuning) {
         // time every candidate on this op, keep the fastest
-        ConvOpKey key{g.kh, g.kw, g.stride, g.pad, p.B, p.H, p.W, p.Cs, p.Cout, p.proj_w != nullptr, p.in_mode};
+        const ConvOpKey key = sbgm_conv_op_key(g, p);
         if (tuned.find(key) == tuned.end()) {
-            ConvTile best_t = pick_tile(g, p);
-            if (sbgm_tune_conv(g, p, partial, PARTIAL_FLOATS, st, &best_t)) return 1;
+            ConvTile best_t = pick_tile(g, p, im);
+            if (sbgm_tune_conv(g, p, im, partial, PARTIAL_FLOATS, st, &best_t)) return 1;
             tuned[key] = best_t;
             ++plan_gen;
         }
     }
-    ConvTile ct = pick_tile(g, p);
+    ConvTile ct = pick_tile(g, p, im);
     if (ct.splits > 1 && mc * ct.splits > PARTIAL_FLOATS) ct.splits = (int)std::max<size_t>(1, PARTIAL_FLOATS / mc);
     last_tile = ct;
-    if (!prof) return launch_any(g, p, ct, st);
+    if (!prof) return sbgm_launch_tile(g, p, im, ct, partial, st);
     ConvRec r{g, p.B, p.H, p.W, p.Cs, p.Cout, p.B * OH * OW, sbgm_conv_nsteps(g.kh, g.kw, p.c_real == 2 ? 2 : p.Cs), ct, 0.0, nullptr, nullptr, 0.f, p.c_real, p.in_mode, p.proj_w != nullptr};
     // algorithmic FLOPs: 2 * M * Cout * (KH*KW*Cin_real); Cs may be padded (only the stem conv), count real K there
     const int cin_real = (g.kh == 8 && p.Cs <= 16) ? cin_total : p.Cs;
@@ -818,7 +560,7 @@ int sbgm_model::conv(const ConvGeom& g, ConvParams p, hipStream_t st) {
     // dominated by execution time rather than by the event packets and the host's launch gaps
     SBGM_HIP(hipEventRecord(r.e0, st));
     int rc = 0;
-    for (int rep = 0; rep < PROF_REPS && !rc; ++rep) rc = launch_any(g, p, ct, st);
+    for (int rep = 0; rep < PROF_REPS && !rc; ++rep) rc = sbgm_launch_tile(g, p, im, ct, partial, st);
     SBGM_HIP(hipEventRecord(r.e1, st));
     prof->push_back(r);
     return rc;
@@ -838,10 +580,10 @@ int sbgm_model::attention(const AttnW& a, float* x, int B, int S, hipStream_t st
         if (!qkv) return 1;
         float* att = wsalloc((size_t)M * C);
         if (!att) return 1;
-        if (sbgm_launch_attn_in(x, a.ln1g->dev, a.ln1b->dev, a.inw->dev, a.inb->dev, qkv, M, C, LN_EPS, st)) return 1;
+        if (sbgm_launch_attn_in(x, a.ln1g->dev(), a.ln1b->dev(), a.inw->dev(), a.inb->dev(), qkv, M, C, LN_EPS, st)) return 1;
         if (sbgm_launch_mha_core(qkv, att, B, S, C, cfg.n_heads, st)) return 1;
-        return sbgm_launch_attn_out(att, x, a.outw->dev, a.outb->dev, a.ln2g->dev, a.ln2b->dev, a.f1w->dev, a.f1b->dev, a.f2w->dev,
-                                    a.f2b->dev, x, M, C, LN_EPS, st);
+        return sbgm_launch_attn_out(att, x, a.outw->dev(), a.outb->dev(), a.ln2g->dev(), a.ln2b->dev(), a.f1w->dev(), a.f1b->dev(), a.f2w->dev(),
+                                    a.f2b->dev(), x, M, C, LN_EPS, st);
     }
     float* n1 = wsalloc((size_t)M * C);
     if (!n1) return 1;
@@ -854,19 +596,19 @@ int sbgm_model::attention(const AttnW& a, float* x, int B, int S, hipStream_t st
     float* f1 = wsalloc((size_t)M * C);
     if (!f1) return 1;
     const ConvGeom lin{1, 1, 1, 0};
-    if (sbgm_launch_layernorm(x, n1, a.ln1g->dev, a.ln1b->dev, M, C, LN_EPS, st)) return 1;
+    if (sbgm_launch_layernorm(x, n1, a.ln1g->dev(), a.ln1b->dev(), M, C, LN_EPS, st)) return 1;
     ConvParams p{};
     p.B = 1; p.H = 1; p.W = M; p.Cs = C;
-    p.x = n1; p.wp = a.inw->dev; p.out = qkv; p.bias = a.inb->dev; p.Cout = 3 * C;
-    if (conv(lin, p, st)) return 1;
+    p.x = n1; p.out = qkv; p.bias = a.inb->dev(); p.Cout = 3 * C;
+    if (conv(lin, p, *a.inw, st)) return 1;
     if (sbgm_launch_mha_core(qkv, att, B, S, C, cfg.n_heads, st)) return 1;
-    p.x = att; p.wp = a.outw->dev; p.out = h; p.bias = a.outb->dev; p.Cout = C; p.res = x;
-    if (conv(lin, p, st)) return 1;
-    if (sbgm_launch_layernorm(h, n1, a.ln2g->dev, a.ln2b->dev, M, C, LN_EPS, st)) return 1;
-    p.x = n1; p.wp = a.f1w->dev; p.out = f1; p.bias = a.f1b->dev; p.res = nullptr; p.act = SBGM_ACT_GELU;   // :131-132
-    if (conv(lin, p, st)) return 1;
-    p.x = f1; p.wp = a.f2w->dev; p.out = x; p.bias = a.f2b->dev; p.res = h; p.act = SBGM_ACT_NONE;
-    return conv(lin, p, st);
+    p.x = att; p.out = h; p.bias = a.outb->dev(); p.Cout = C; p.res = x;
+    if (conv(lin, p, *a.outw, st)) return 1;
+    if (sbgm_launch_layernorm(h, n1, a.ln2g->dev(), a.ln2b->dev(), M, C, LN_EPS, st)) return 1;
+    p.x = n1; p.out = f1; p.bias = a.f1b->dev(); p.res = nullptr; p.act = SBGM_ACT_GELU;   // :131-132
+    if (conv(lin, p, *a.f1w, st)) return 1;
+    p.x = f1; p.out = x; p.bias = a.f2b->dev(); p.res = h; p.act = SBGM_ACT_NONE;
+    return conv(lin, p, *a.f2w, st);
 }
 
 int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, const float* cond, const float* lsm,
@@ -897,11 +639,11 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     if (sbgm_launch_pack_input(src, x0, B, H, W, cs_in, st)) return 1;
 
     TimeEmbedArgs te{};
-    te.t = t; te.y = y; te.label_emb = (y && label_emb) ? label_emb->dev : nullptr;
+    te.t = t; te.y = y; te.label_emb = (y && label_emb) ? label_emb->dev() : nullptr;
     te.B = B; te.D = D;
     te.n_emb = 5;
-    te.freqs[0] = enc_freq->dev;
-    for (int i = 0; i < 4; ++i) te.freqs[1 + i] = dec[i].freq->dev;
+    te.freqs[0] = enc_freq->dev();
+    for (int i = 0; i < 4; ++i) te.freqs[1 + i] = dec[i].freq->dev();
     te.emb_ws = wsalloc((size_t)5 * B * D);
     if (!te.emb_ws) return 1;
     float* tb[9];
@@ -909,12 +651,12 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     for (int i = 0; i < 5; ++i) {
         tb[i] = wsalloc((size_t)B * FMAP_CH[i]);
         if (!tb[i]) return 1;
-        te.proj[i] = TimeProj{enc_tpw[i]->dev, enc_tpb[i]->dev, tb[i], FMAP_CH[i], 0};
+        te.proj[i] = TimeProj{enc_tpw[i]->dev(), enc_tpb[i]->dev(), tb[i], FMAP_CH[i], 0};
     }
     for (int i = 0; i < 4; ++i) {
         tb[5 + i] = wsalloc((size_t)B * dec[i].cout);
         if (!tb[5 + i]) return 1;
-        te.proj[5 + i] = TimeProj{dec[i].tpw->dev, dec[i].tpb->dev, tb[5 + i], dec[i].cout, 1 + i};
+        te.proj[5 + i] = TimeProj{dec[i].tpw->dev(), dec[i].tpb->dev(), tb[5 + i], dec[i].cout, 1 + i};
     }
     if (sbgm_launch_time_embed(te, st)) return 1;
 
@@ -927,18 +669,18 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     auto conv_bn = [&](const ConvGeom& g, const float* in, int h, int w, int cs, const ConvW& cw, BNW& bnw, int cout,
                        const float* res, bool relu, const float* tb_after, float* o) -> int {
         ConvParams p{};
-        p.x = in; p.wp = cw.w->dev; p.wp_wino = cw.w->dev_wino; p.wp_w2d = cw.w->dev_w2d; p.wp_s2w = cw.w->dev_s2w; p.B = B; p.H = h; p.W = w; p.Cs = cs; p.Cout = cout;
+        p.x = in; p.B = B; p.H = h; p.W = w; p.Cs = cs; p.Cout = cout;
         if (!bn_train) {
             p.out = o; p.scale = bnw.scale; p.bias = bnw.bias; p.res = res; p.act = relu ? SBGM_ACT_RELU : SBGM_ACT_NONE;
             p.tbias = tb_after; p.tbias_after_act = 1;
-            return conv(g, p, st);
+            return conv(g, p, *cw.w, st);
         }
         const int oh = (h + 2 * g.pad - g.kh) / g.stride + 1, ow = (w + 2 * g.pad - g.kw) / g.stride + 1;
         float* raw = wsalloc((size_t)B * oh * ow * cout);
         if (!raw) return 1;
         p.out = raw;
-        if (conv(g, p, st)) return 1;
-        return sbgm_launch_batchnorm_train(raw, o, bnw.g->dev, bnw.b->dev, bnw.rm->dev, bnw.rv->dev, res, tb_after, relu, B,
+        if (conv(g, p, *cw.w, st)) return 1;
+        return sbgm_launch_batchnorm_train(raw, o, bnw.g->dev(), bnw.b->dev(), bnw.rm->dev(), bnw.rv->dev(), res, tb_after, relu, B,
                                            oh * ow, cout, BN_EPS, BN_MOMENTUM, stats, st);
     };
 
@@ -950,9 +692,9 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     if (!fm[0]) return 1;
     {
         ConvParams p{};
-        p.x = x0; p.wp = conv1.w->dev; p.out = fm[0]; p.tbias = tb[0]; p.B = B; p.H = H; p.W = W; p.Cs = cs_in; p.Cout = 64;
+        p.x = x0; p.out = fm[0]; p.tbias = tb[0]; p.B = B; p.H = H; p.W = W; p.Cs = cs_in; p.Cout = 64;
         p.c_real = cin_total == 2 ? 2 : 0;
-        if (conv(ConvGeom{8, 8, 2, 3}, p, st)) return 1;                                        // score_unet.py:312-316
+        if (conv(ConvGeom{8, 8, 2, 3}, p, *conv1.w, st)) return 1;                                        // score_unet.py:312-316
     }
     int ch = H / 4, cw_ = W / 4;
     float* cur = wsalloc((size_t)B * ch * cw_ * 64);
@@ -967,7 +709,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
         }
         if (sbgm_launch_conv_stem22(x, 1, 0, cin_total, stem_wc, stem_sb, tb[0], stem_T, bn_train ? nullptr : bn1.scale,
                                     bn_train ? nullptr : bn1.bias, bn_train ? 0 : 1, o, B, H, W, st)) return 1;
-        if (bn_train && sbgm_launch_batchnorm_train(o, cur, bn1.g->dev, bn1.b->dev, bn1.rm->dev, bn1.rv->dev, nullptr, nullptr, true, B,
+        if (bn_train && sbgm_launch_batchnorm_train(o, cur, bn1.g->dev(), bn1.b->dev(), bn1.rm->dev(), bn1.rv->dev(), nullptr, nullptr, true, B,
                                                     ch * cw_, 64, BN_EPS, BN_MOMENTUM, stats, st)) return 1;
     } else if (conv_bn(ConvGeom{8, 8, 2, 3}, fm[0], fh[0], fw[0], 64, conv2, bn1, 64, nullptr, true, nullptr, cur)) return 1;   // :321-325
     int cc = 64;
@@ -1013,9 +755,9 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     // passes everywhere.
     const int G_of = cfg.gn_groups;
     auto groups = [&](int c) { return cfg.decoder_norm == SBGM_NORM_GROUP ? std::max(1, std::min(G_of, c)) : c; };
-    static const bool fused_ok = getenv("SBGM_NO_FUSED_DECODER") == nullptr && getenv("SBGM_NO_LDS_CONV") == nullptr && getenv("SBGM_NO_WINOGRAD") == nullptr;
+    static const bool fused_ok = getenv("SBGM_NO_FUSED_DECODER") == nullptr && !sbgm_conv_switches().no_lds && !sbgm_conv_switches().no_wino;
     auto can_fuse = [&](const ConvW& cw, int c_in, int w_out) {
-        return fused_ok && !cfg.decoder_transpose && w_out >= 32 && w_out % 16 == 0 && c_in % 16 == 0 && cw.w->dev_wino != nullptr;
+        return fused_ok && !cfg.decoder_transpose && w_out >= 32 && w_out % 16 == 0 && c_in % 16 == 0 && cw.w->img[IMG_WINO] != nullptr;
     };
     struct Pending { const float* raw; const float* affine; const float* skip; int act; bool live; } pend{nullptr, nullptr, nullptr, SBGM_ACT_NONE, false};
     // statistics of `t` [B][hw][c] for its GroupNorm: from the convolution epilogue (chunks > 0) or a separate partial pass
@@ -1026,7 +768,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     // conv_up of a block: input `in` [B][ch][cw_][ci] (or the pending raw map), output raw [B][2ch][2cw_][ci] (+ bias)
     auto conv_up = [&](const ConvW& cw, const float* in, int ci, int oh, int ow, ConvParams& p, float* out_raw) -> int {
         p = ConvParams{};
-        p.wp = cw.w->dev; p.wp_wino = cw.w->dev_wino; p.wp_w2d = cw.w->dev_w2d; p.out = out_raw; p.bias = cw.b->dev; p.B = B; p.H = oh; p.W = ow; p.Cs = ci; p.Cout = ci;
+        p.out = out_raw; p.bias = cw.b->dev(); p.B = B; p.H = oh; p.W = ow; p.Cs = ci; p.Cout = ci;
         if (can_fuse(cw, ci, ow)) {
             p.in_mode = 2;
             p.x = pend.live ? pend.raw : in;
@@ -1053,43 +795,43 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
         if (cfg.decoder_transpose) {                 // ConvTranspose2d: 1x1 conv to 4*cin phase-major channels, then depth -> space
             float* up = wsalloc((size_t)B * oh * ow * d.cin);
             if (!up) return 1;
-            p.x = cur; p.wp = d.up.w->dev; p.out = up; p.bias = d.up.b->dev; p.B = B; p.H = ch; p.W = cw_; p.Cs = d.cin; p.Cout = 4 * d.cin;
-            if (conv(ConvGeom{1, 1, 1, 0}, p, st)) return 1;
+            p.x = cur; p.out = up; p.bias = d.up.b->dev(); p.B = B; p.H = ch; p.W = cw_; p.Cs = d.cin; p.Cout = 4 * d.cin;
+            if (conv(ConvGeom{1, 1, 1, 0}, p, *d.up.w, st)) return 1;
             if (sbgm_launch_depth_space2(up, a, B, ch, cw_, d.cin, 1, st)) return 1;
         } else {
             if (conv_up(d.up, cur, d.cin, oh, ow, p, a)) return 1;
             p.gn_stats = stats; p.gn_groups = groups(d.cin);        // GroupNorm statistics in the epilogue when the LDS kernel runs
-            if (conv(ConvGeom{3, 3, 1, 1}, p, st)) return 1;
-            gn1_chunks = tile_gn_chunks(p, last_tile);
+            if (conv(ConvGeom{3, 3, 1, 1}, p, *d.up.w, st)) return 1;
+            gn1_chunks = sbgm_tile_gn_chunks(p, last_tile);
         }
         float* c2 = wsalloc((size_t)B * oh * ow * d.cout);
         if (!c2) return 1;
         if (ensure_stats(a, oh * ow, d.cin, gn1_chunks)) return 1;
         p = ConvParams{};
         p.B = B; p.H = oh; p.W = ow; p.Cs = d.cin;
-        p.x = a; p.wp = d.conv.w->dev; p.wp_wino = d.conv.w->dev_wino; p.wp_w2d = d.conv.w->dev_w2d; p.out = c2; p.bias = d.conv.b->dev; p.Cout = d.cout;
+        p.x = a; p.out = c2; p.bias = d.conv.b->dev(); p.Cout = d.cout;
         if (can_fuse(d.conv, d.cin, ow)) {           // norm1 applied while `conv` stages its patch
             float* aff1 = wsalloc((size_t)B * d.cin * 2);
             if (!aff1) return 1;
-            if (sbgm_launch_gn_finalize(stats, gn1_chunks, d.n1g ? d.n1g->dev : nullptr, d.n1b ? d.n1b->dev : nullptr, nullptr, aff1, B, oh * ow,
+            if (sbgm_launch_gn_finalize(stats, gn1_chunks, d.n1g ? d.n1g->dev() : nullptr, d.n1b ? d.n1b->dev() : nullptr, nullptr, aff1, B, oh * ow,
                                         d.cin, groups(d.cin), GN_EPS, st)) return 1;
             p.in_mode = 1; p.in_affine = aff1;
-        } else if (sbgm_launch_groupnorm_apply(a, a, d.n1g ? d.n1g->dev : nullptr, d.n1b ? d.n1b->dev : nullptr, nullptr, nullptr,
+        } else if (sbgm_launch_groupnorm_apply(a, a, d.n1g ? d.n1g->dev() : nullptr, d.n1b ? d.n1b->dev() : nullptr, nullptr, nullptr,
                                                SBGM_ACT_NONE, B, oh * ow, d.cin, groups(d.cin), GN_EPS, stats, gn1_chunks, st)) return 1;
         p.gn_stats = stats; p.gn_groups = groups(d.cout);
-        if (conv(ConvGeom{3, 3, 1, 1}, p, st)) return 1;
-        int gn2_chunks = tile_gn_chunks(p, last_tile);
+        if (conv(ConvGeom{3, 3, 1, 1}, p, *d.conv.w, st)) return 1;
+        int gn2_chunks = sbgm_tile_gn_chunks(p, last_tile);
         if (ensure_stats(c2, oh * ow, d.cout, gn2_chunks)) return 1;
         const ConvW& next_up = i < 3 ? dec[i + 1].up : fin_up;
         if (!d.has_attn && can_fuse(next_up, d.cout, 2 * ow)) {
             // norm2 + skip + time bias + activation stay pending: the next conv_up applies them to the low-res pixels it loads
             float* aff2 = wsalloc((size_t)B * d.cout * 2);
             if (!aff2) return 1;
-            if (sbgm_launch_gn_finalize(stats, gn2_chunks, d.n2g ? d.n2g->dev : nullptr, d.n2b ? d.n2b->dev : nullptr, tb[5 + i], aff2, B, oh * ow,
+            if (sbgm_launch_gn_finalize(stats, gn2_chunks, d.n2g ? d.n2g->dev() : nullptr, d.n2b ? d.n2b->dev() : nullptr, tb[5 + i], aff2, B, oh * ow,
                                         d.cout, groups(d.cout), GN_EPS, st)) return 1;
             pend = Pending{c2, aff2, fm[3 - i], cfg.decoder_activation, true};
         } else {
-            if (sbgm_launch_groupnorm_apply(c2, c2, d.n2g ? d.n2g->dev : nullptr, d.n2b ? d.n2b->dev : nullptr, fm[3 - i], tb[5 + i],
+            if (sbgm_launch_groupnorm_apply(c2, c2, d.n2g ? d.n2g->dev() : nullptr, d.n2b ? d.n2b->dev() : nullptr, fm[3 - i], tb[5 + i],
                                             cfg.decoder_activation, B, oh * ow, d.cout, groups(d.cout), GN_EPS, stats, gn2_chunks, st)) return 1;
             if (d.has_attn && attention(d.attn, c2, B, oh * ow, st)) return 1;
         }
@@ -1103,10 +845,10 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             if (!up) return 1;
             float* a = wsalloc((size_t)B * H * W * ci);
             if (!a) return 1;
-            p.x = cur; p.wp = fin_up.w->dev; p.out = up; p.bias = fin_up.b->dev; p.B = B; p.H = ch; p.W = cw_; p.Cs = ci; p.Cout = 4 * ci;
-            if (conv(ConvGeom{1, 1, 1, 0}, p, st)) return 1;
+            p.x = cur; p.out = up; p.bias = fin_up.b->dev(); p.B = B; p.H = ch; p.W = cw_; p.Cs = ci; p.Cout = 4 * ci;
+            if (conv(ConvGeom{1, 1, 1, 0}, p, *fin_up.w, st)) return 1;
             if (sbgm_launch_depth_space2(up, a, B, ch, cw_, ci, 1, st)) return 1;
-            return sbgm_launch_conv3x3_cout1(a, fin_conv.w->dev, fin_conv.b->dev, t, cfg.sigma, out, B, H, W, ci, st);
+            return sbgm_launch_conv3x3_cout1(a, fin_conv.w->dev(), fin_conv.b->dev(), t, cfg.sigma, out, B, H, W, ci, st);
         }
         if (fin_route && (fin_run || prof != nullptr || tuning)) {
             // conv(conv_up(.)) composed: one 3x3 convolution from ci to the 9 taps (16 channels stored), rows [M][16], then the gather
@@ -1115,8 +857,8 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             float* d = wsalloc((size_t)16 * B * H * W);
             if (!d) return 1;
             p.Cout = 16; p.out = d;
-            if (conv(ConvGeom{3, 3, 1, 1}, p, st)) return 1;
-            if (sbgm_launch_tap_gather_rows(d, fin_conv.b->dev, t, cfg.sigma, out, B, H, W, st)) return 1;
+            if (conv(ConvGeom{3, 3, 1, 1}, p, *fin_comp.w, st)) return 1;
+            if (sbgm_launch_tap_gather_rows(d, fin_conv.b->dev(), t, cfg.sigma, out, B, H, W, st)) return 1;
             if (!tuning) return 0;
             pend = pend0;                        // a tuning evaluation also times the projection form below (plain forward, RK45)
         }
@@ -1124,19 +866,18 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
         if (ci == 64) {
             // conv_up's 64-channel output feeds only the linear 3x3 Cout=1 conv: project onto its 9 taps in the epilogue
             // (9 floats per pixel instead of 64) and finish with a 9-point gather.
-            p.proj_w = fin_conv.w->dev;
+            p.proj_w = fin_conv.w->dev();
             float* d = wsalloc((size_t)9 * B * H * W * 4);      // up to 4 partial planes (2-D Winograd tiles of 16 channels)
             if (!d) return 1;
             p.out = d; p.proj_out = d;
-            if (conv(ConvGeom{3, 3, 1, 1}, p, st)) return 1;
-            const int parts = last_tile.wino == 2 ? sbgm_conv_w2d_proj_parts(p, last_tile) : 1;
-            if (sbgm_launch_tap_stencil(d, fin_conv.b->dev, t, cfg.sigma, out, B, H, W, st, parts)) return 1;
+            if (conv(ConvGeom{3, 3, 1, 1}, p, *fin_up.w, st)) return 1;
+            if (sbgm_launch_tap_stencil(d, fin_conv.b->dev(), t, cfg.sigma, out, B, H, W, st, sbgm_tile_proj_parts(p, last_tile))) return 1;
         } else {
             float* a = wsalloc((size_t)B * H * W * ci);
             if (!a) return 1;
             p.out = a;
-            if (conv(ConvGeom{3, 3, 1, 1}, p, st)) return 1;
-            if (sbgm_launch_conv3x3_cout1(a, fin_conv.w->dev, fin_conv.b->dev, t, cfg.sigma, out, B, H, W, ci, st)) return 1;
+            if (conv(ConvGeom{3, 3, 1, 1}, p, *fin_up.w, st)) return 1;
+            if (sbgm_launch_conv3x3_cout1(a, fin_conv.w->dev(), fin_conv.b->dev(), t, cfg.sigma, out, B, H, W, ci, st)) return 1;
         }
     }
     return 0;
@@ -1583,13 +1324,10 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
     SBGM_CHECK(numel == p->numel, "set_param: '%s' has %lld elements, expected %lld", name, (long long)numel, (long long)p->numel);
     const float* src = static_cast<const float*>(data);
     if (p->kind == P_VEC) {
-        SBGM_HIP(hipMemcpyAsync(p->dev, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
+        SBGM_HIP(hipMemcpyAsync(p->dev(), src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
         if (p == m->fin_up.b) m->fin_dirty = true;
     } else if (p->kind == P_CONV) {
-        if (sbgm_launch_pack_conv_weight(src, p->dev, p->cout, p->cin, p->kh, p->kw, p->cs, st)) return 1;
-        if (p->wino && sbgm_launch_pack_wino_weight(src, p->dev_wino, p->cout, p->cin, p->cs, st)) return 1;
-        if (p->dev_w2d && sbgm_launch_pack_w2d_weight(src, p->dev_w2d, p->cout, p->cin, p->cs, st)) return 1;
-        if (p->dev_s2w && sbgm_launch_pack_s2w_weight(src, p->dev_s2w, p->cout, p->cin, p->cs, st)) return 1;
+        if (sbgm_pack_conv_images(src, p->img, p->cout, p->cin, p->kh, p->kw, p->cs, st)) return 1;
         if (p == m->conv1.w && m->stem_keep(src, p, m->stem_w1, st)) return 1;
         if (p == m->conv2.w && m->stem_keep(src, p, m->stem_w2, st)) return 1;
         if (m->fin_route && p == m->fin_up.w && m->fin_keep(src, p, m->fin_w1, st)) return 1;
@@ -1597,15 +1335,15 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
         float* tmp = nullptr;
         SBGM_HIP(hipMalloc(&tmp, (size_t)numel * 4));
         int rc = sbgm_launch_tconv_weight(src, tmp, p->cin, p->cout / 4, st);
-        if (!rc) rc = sbgm_launch_pack_conv_weight(tmp, p->dev, p->cout, p->cin, 1, 1, p->cs, st);
+        if (!rc) rc = sbgm_launch_pack_conv_weight(tmp, p->dev(), p->cout, p->cin, 1, 1, p->cs, st);
         (void)hipStreamSynchronize(st);
         (void)hipFree(tmp);
         if (rc) return rc;
     } else if (p->kind == P_VEC4) {
         for (int r = 0; r < 4; ++r)
-            SBGM_HIP(hipMemcpyAsync(p->dev + (size_t)r * numel, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
+            SBGM_HIP(hipMemcpyAsync(p->dev() + (size_t)r * numel, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
     } else {
-        if (sbgm_launch_pack_cout1_weight(src, p->dev, p->cin, st)) return 1;
+        if (sbgm_launch_pack_cout1_weight(src, p->dev(), p->cin, st)) return 1;
         if (m->fin_route && p == m->fin_conv.w && m->fin_keep(src, p, m->fin_w2, st)) return 1;
     }
     p->filled = true;
@@ -1618,7 +1356,7 @@ int sbgm_model_get_param(sbgm_model* m, const char* name, float* dst, int64_t nu
     SBGM_CHECK(it != m->by_name.end(), "get_param: unknown key '%s'", name);
     Param* p = it->second;
     SBGM_CHECK(p->kind == P_VEC && numel == p->numel, "get_param: '%s' is not a plain vector of %lld elements", name, (long long)numel);
-    SBGM_HIP(hipMemcpyAsync(dst, p->dev, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    SBGM_HIP(hipMemcpyAsync(dst, p->dev(), (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
@@ -1705,63 +1443,11 @@ int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {
     return m->ensure_ws(m->ws_need(B, H, W));
 }
 
-extern "C++" {
-static std::string conv_kernel_name(const sbgm_model::ConvRec& r) {
-    char b[96];
-    if (r.t.wino == 3) snprintf(b, sizeof b, "conv8x8s2_s2w_kernel<%d>", r.t.fco);
-    else if (r.t.wino == 2 && r.t.lds == 3) snprintf(b, sizeof b, "conv3x3_w2dp_kernel<%d; %d; %s>", r.t.fco, r.in_mode, r.proj ? "true" : "false");
-    else if (r.t.wino == 2) snprintf(b, sizeof b, "conv3x3_w2d_kernel<%d; %d; %s; %d>", r.t.fco, r.t.ws == 2 ? 2 : 1, r.t.lds == 2 ? "true" : "false", r.in_mode);
-    else if (r.t.lds) snprintf(b, sizeof b, "conv3x3_lds_kernel<%d; %d; %s; %s; %d>", r.t.fco, r.t.fpx, r.t.wino ? "true" : "false", r.t.lds == 2 ? "true" : "false", r.in_mode);
-    else if (r.t.wino) snprintf(b, sizeof b, "conv3x3_wino_kernel<%d; %d; %d>", r.t.fco, r.t.fpx, r.t.ws);
-    else snprintf(b, sizeof b, "conv_igemm_kernel<%d; %d; %d; %d; %d; %d; %d; %d>", r.g.kh, r.g.kw, r.g.stride, r.g.pad, r.t.fco,
-                  r.t.fpx, r.c_real == 2 ? 2 : (r.Cs >= 16 ? 0 : r.Cs), r.t.ws);
-    return b;
-}
-}  // extern "C++"
-
-// Tile table <-> text file: one line per tuned convolution, "kh kw stride pad B H W Cin_pad Cout proj in_mode | fco fpx splits ws wino lds".
-int sbgm_model_tune_save(sbgm_model* m, const char* path) {
-    SBGM_CHECK(path, "tune_save: null path");
-    FILE* f = fopen(path, "w");
-    SBGM_CHECK(f, "tune_save: cannot open %s", path);
-    fprintf(f, "# sbgm conv tile table v2\n");
-    for (auto& kv : m->tuned) {
-        const ConvOpKey& k = kv.first;
-        const ConvTile& t = kv.second;
-        fprintf(f, "%d %d %d %d %d %d %d %d %d %d %d | %d %d %d %d %d %d\n", k.kh, k.kw, k.s, k.p, k.B, k.H, k.W, k.Cs, k.Cout, k.proj,
-                k.in_mode, t.fco, t.fpx, t.splits, t.ws, t.wino, t.lds);
-    }
-    fclose(f);
-    return 0;
-}
+// Tile table <-> text file (conv_plan.hip: one line per tuned convolution)
+int sbgm_model_tune_save(sbgm_model* m, const char* path) { return sbgm_tile_table_save(m->tuned, path); }
 
 int sbgm_model_tune_load(sbgm_model* m, const char* path) {
-    SBGM_CHECK(path, "tune_load: null path");
-    FILE* f = fopen(path, "r");
-    SBGM_CHECK(f, "tune_load: cannot open %s", path);
-    char line[256];
-    std::map<ConvOpKey, ConvTile> table;
-    int lineno = 0;
-    while (fgets(line, sizeof line, f)) {
-        ++lineno;
-        if (line[0] == '#' || line[0] == '\n') continue;
-        ConvOpKey k{};
-        int t[6];
-        const int n = sscanf(line, "%d %d %d %d %d %d %d %d %d %d %d | %d %d %d %d %d %d", &k.kh, &k.kw, &k.s, &k.p, &k.B, &k.H, &k.W,
-                             &k.Cs, &k.Cout, &k.proj, &k.in_mode, &t[0], &t[1], &t[2], &t[3], &t[4], &t[5]);
-        // the launchers reject tiles they do not instantiate; here only the ranges that index memory are checked
-        const bool ok = n == 17 && k.in_mode >= 0 && k.in_mode <= 2 && (t[0] == 1 || t[0] == 2 || t[0] == 4) && (t[1] == 1 || t[1] == 2 || t[1] == 4) && t[2] >= 1 &&
-                        t[2] <= 64 && (t[3] == 1 || t[3] == 2 || t[3] == 4 || t[3] == 8) && t[4] >= 0 && t[4] <= 3 && (t[4] < 2 || t[5] >= 1) && t[5] >= 0 && t[5] <= (t[4] == 2 ? 3 : 2) &&
-                        (t[4] != 3 || (k.kh == 8 && k.kw == 8 && k.s == 2 && k.p == 3 && t[0] <= 2)) &&
-                        k.Cout % (16 * t[0]) == 0;
-        if (!ok) {
-            fclose(f);
-            SBGM_CHECK(false, "tune_load: %s line %d is malformed", path, lineno);
-        }
-        table[k] = ConvTile{t[0], t[1], t[2], t[3], t[4], t[5]};
-    }
-    fclose(f);
-    for (auto& kv : table) m->tuned[kv.first] = kv.second;
+    if (sbgm_tile_table_load(&m->tuned, path)) return 1;
     ++m->plan_gen;
     return 0;
 }
@@ -1799,8 +1485,8 @@ int sbgm_model_profile_forward(sbgm_model* m, const float* x, const float* t, co
         s.n_conv += 1;
         if (r.ms > s.ms_conv_max) { s.ms_conv_max = r.ms; s.flops_conv_max = r.flops; }
         if (f) fprintf(f, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%.2f,%s\n", i, r.g.kh, r.g.kw, r.g.stride, r.B, r.H, r.W,
-                       r.Cs, r.Cout, r.M, r.nsteps, 16 * r.t.fco, r.t.wino >= 2 ? 256 : r.t.lds ? 64 * r.t.fpx * (r.t.wino ? 2 : 1) : (r.t.wino ? 32 : 16) * r.t.fpx, r.t.splits, r.t.wino == 3 ? -25 : r.t.wino == 2 ? -40 : r.t.lds ? (r.t.wino ? -20 : 20) : (r.t.wino ? -r.t.ws : r.t.ws), r.flops * 1e-9, r.ms,
-                       r.flops / (r.ms * 1e-3) * 1e-12, conv_kernel_name(r).c_str());
+                       r.Cs, r.Cout, r.M, r.nsteps, 16 * r.t.fco, sbgm_tile_csv_px(r.t), r.t.splits, sbgm_tile_csv_ws(r.t), r.flops * 1e-9, r.ms,
+                       r.flops / (r.ms * 1e-3) * 1e-12, sbgm_tile_kernel_name(r.g, r.t, r.Cs, r.c_real, r.in_mode, r.proj != 0).c_str());
         ++i;
     }
     if (f) fclose(f);
@@ -1828,13 +1514,9 @@ static ConvParams final_block_conv(int B, int H, int W, int C) {
 
 int sbgm_final_block_tiles(int B, int H, int W, int C, int* tiles, int cap) {
     static const float present = 0.f;                 // the candidate list only asks which weight images exist
-    ConvParams p = final_block_conv(B, H, W, C);
-    p.wp = p.wp_wino = p.wp_w2d = &present;
-    const std::vector<ConvTile> c = conv_candidates(ConvGeom{3, 3, 1, 1}, p, false);
-    for (int i = 0; i < (int)c.size() && i < cap; ++i) {
-        const int v[6] = {c[i].fco, c[i].fpx, c[i].splits, c[i].ws, c[i].wino, c[i].lds};
-        std::memcpy(tiles + 6 * i, v, sizeof v);
-    }
+    const ConvImages im{{&present, &present, &present, nullptr}};
+    const std::vector<ConvTile> c = sbgm_conv_candidates(ConvGeom{3, 3, 1, 1}, final_block_conv(B, H, W, C), im, false);
+    for (int i = 0; i < (int)c.size() && i < cap; ++i) c[i].to_ints(tiles + 6 * i);
     return (int)c.size();
 }
 
@@ -1850,7 +1532,8 @@ int sbgm_final_block_fwd(const float* x, const float* in_affine, const float* in
     SBGM_CHECK(fused || (!in_affine && !in_skip && in_act == SBGM_ACT_NONE), "final_block_fwd: affine / skip / activation on load need the fused route (W >= 32)");
     SBGM_CHECK((size_t)ws_floats >= M * (fused ? 16 : 16 + (size_t)C), "final_block_fwd: workspace of %lld floats is too small", (long long)ws_floats);
     ConvParams p = final_block_conv(B, H, W, C);
-    p.wp = w_packed; p.wp_wino = w_wino; p.wp_w2d = w_wino2d; p.bias = bc; p.out = ws;
+    const ConvImages im{{w_packed, w_wino, w_wino2d, nullptr}};
+    p.bias = bc; p.out = ws;
     if (fused) {
         p.x = x; p.in_affine = in_affine; p.in_skip = in_skip; p.in_act = in_act;
     } else {
@@ -1858,10 +1541,13 @@ int sbgm_final_block_fwd(const float* x, const float* in_affine, const float* in
         if (sbgm_launch_upsample2x(x, up, B, H / 2, W / 2, C, st)) return 1;
         p.x = up;
     }
-    const ConvTile ct = tile ? ConvTile{tile[0], tile[1], tile[2], tile[3], tile[4], tile[5]} : cout16_tile(p);
-    SBGM_CHECK(ct.fco == 1 && ct.splits == 1 && ct.lds >= 1 && (ct.wino == 1 || (ct.wino == 2 && w_wino2d)),
-               "final_block_fwd: tile {%d,%d,%d,%d,%d,%d} is no 16-channel LDS-staged Winograd kernel", ct.fco, ct.fpx, ct.splits, ct.ws, ct.wino, ct.lds);
-    if (launch_tile(ConvGeom{3, 3, 1, 1}, p, ct, nullptr, st)) return 1;
+    const ConvTile ct = tile ? ConvTile::from_ints(tile) : sbgm_cout16_tile(p, im);
+    const ConvFamily fam = ct.well_formed() ? ct.family() : FAM_IGEMM;
+    int v[6];
+    ct.to_ints(v);
+    SBGM_CHECK(ct.fco == 1 && ct.splits == 1 && (fam == FAM_LDS_WINO || ((fam == FAM_W2D || fam == FAM_W2DP) && w_wino2d)),
+               "final_block_fwd: tile {%d,%d,%d,%d,%d,%d} is no 16-channel LDS-staged Winograd kernel", v[0], v[1], v[2], v[3], v[4], v[5]);
+    if (sbgm_launch_tile(ConvGeom{3, 3, 1, 1}, p, im, ct, nullptr, st)) return 1;
     return sbgm_launch_tap_gather_rows(ws, b2, t, sigma, out, B, H, W, st);
 }
 

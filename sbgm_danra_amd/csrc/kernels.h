@@ -4,52 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
-
-struct ConvGeom {
-    int kh, kw, stride, pad;
-};
-struct ConvTile {
-    int fco, fpx;   // wave tile = (16*fco) output channels x (16*fpx) pixels
-    int splits;     // split-K over gridDim.y (partials + reduce kernel)
-    int ws;         // waves of a workgroup cooperating on one tile (in-workgroup split-K through LDS): 1, 2 or 4
-    int wino;       // 1 = 3x3/s1 Winograd F(2,3) kernel (conv_wino.hip): fpx then counts PAIR fragments, weights = wino pack;
-                    // 2 = 2-D Winograd F(2x2,3x3), LDS-staged only (conv_w2d.hip): 16x16-pixel tiles, fpx unused, weights = w2d pack;
-                    // 3 = 8x8/s2/p3 as space-to-depth Winograd F(2x2,4x4), LDS-staged (conv_s2w.hip): 16x16-output tiles, weights = s2w pack
-    int lds;        // 1 = LDS-staged 3x3/s1 kernel (conv_lds.hip): fpx = tile rows per wave (Winograd: 2*fpx rows)
-};
-struct ConvParams {
-    const float* x;       // NHWC [B][H][W][Cs]
-    const float* wp;      // packed weights [nsteps][Cout][16]
-    float* out;           // NHWC [M][Cout]
-    const float* scale;   // [Cout] or null   (folded BatchNorm gamma/sqrt(var+eps))
-    const float* bias;    // [Cout] or null
-    const float* tbias;   // [B][Cout] or null (time-projection bias, broadcast over pixels)
-    const float* res;     // [M][Cout] or null (residual / skip)
-    int B, H, W, Cs, Cout;
-    int act, tbias_after_act;
-    const float* proj_w;  // [9][Cout] or null: fuse the following 3x3 Cout=1 conv's per-tap channel dot products
-    float* proj_out;      // [9][M] planar tap sums (then `out` is not written)
-    const float* wp_wino; // host-side only: Winograd-packed copy of the weights (3x3 stride-1 layers), or null
-    const float* wp_w2d;  // host-side only: F(2x2,3x3)-packed copy of the weights (3x3 stride-1 layers), or null
-    const float* wp_s2w;  // host-side only: space-to-depth F(2x2,4x4)-packed copy of the weights (8x8 stride-2 pad-3 layers), or null
-    double* gn_stats;     // conv_lds only, or null: per-workgroup GroupNorm partial sums of the OUTPUT (sum, sum of squares per
-                          // group) in the [b][chunk][G][2] layout groupnorm_apply reads -> no separate statistics pass
-    int gn_groups;        // G of that GroupNorm (channels per group must divide or be a multiple of the tile's channel slice)
-    int c_real;           // 0, or 2 with Cs == 4: only 2 of the 4 stored channels are real (the 2-channel stem): a K step is then
-                          // 8 taps x 2 channels (weights packed with cs = 2) instead of 4 taps x 4 slots, halving the MFMA work
-    int in_dil;           // 1, or 2: read the input through a zero-inserted grid (data-gradient of a stride-2 conv)
-    int out_h, out_w;     // explicit output size (required with in_dil == 2), else 0
-    // conv_lds only — what happens to the input while the halo patch is staged (conv_lds.hip, "Input modes"):
-    int in_mode;          // 0 plain; 1 affine on load (x*scale + shift per (sample, channel), zero padding kept); 2 bilinear x2 on
-                          // load: x is the LOW-resolution map [B][H/2][W/2][Cs] (H, W stay the convolution's own size), optionally
-                          // transformed act(x*scale + shift + skip) before the interpolation
-    const float* in_affine;  // [B][Cs/4][2][4] (scale quad, shift quad) from sbgm_launch_gn_finalize, or null
-    const float* in_skip;    // mode 2: [B][H/2][W/2][Cs] added before the activation, or null
-    int in_act;              // mode 2: SBGM_ACT_* applied to the low-res value
-    // filled by sbgm_launch_conv:
-    int OH, OW, M, cb_per_tap, nsteps, steps_per_split, n_px_tiles, n_co_tiles;
-    uint32_t x_bytes, w_bytes;
-};
+#include "conv_plan.h"   // ConvGeom, ConvTile, ConvParams, the weight images and the planner
 
 int sbgm_conv_nsteps(int KH, int KW, int cs);
 int sbgm_conv_pack_blocks(int Cout, int KH, int KW, int cs);   // workgroups one weight takes in the batched pack launch
@@ -86,7 +41,7 @@ size_t sbgm_conv_lds_bytes(const ConvTile& cfg, int in_mode);
 // chunks per sample the launch above writes into p.gn_stats for this tile, or 0 if that tile cannot produce them
 int sbgm_conv_lds_gn_chunks(const ConvParams& p, const ConvTile& cfg);
 
-// ---- conv_w2d.hip: the same convolution as a 2-D Winograd F(2x2,3x3), LDS-staged (ConvTile.wino == 2) -----------------------
+// ---- conv_w2d.hip: the same convolution as a 2-D Winograd F(2x2,3x3), LDS-staged (FAM_W2D, FAM_W2DP) -----------------------
 size_t sbgm_w2d_packed_floats(int Cout, int cs);
 int sbgm_launch_pack_w2d_weight(const float* w_oihw, float* up, int Cout, int Cin, int cs, hipStream_t st);
 int sbgm_launch_conv_w2d(ConvParams p, const ConvTile& cfg, hipStream_t st);    // p.wp = F(2x2,3x3)-packed weights
@@ -95,7 +50,7 @@ int sbgm_conv_w2d_gn_chunks(const ConvParams& p, const ConvTile& cfg);
 // co tiles of a tap-projection launch: each writes its own partial plane [tile][9][M], sbgm_launch_tap_stencil sums `parts` planes
 int sbgm_conv_w2d_proj_parts(const ConvParams& p, const ConvTile& cfg);
 
-// ---- conv_s2w.hip: 8x8 stride-2 pad-3 convolution as a space-to-depth Winograd F(2x2,4x4), LDS-staged (ConvTile.wino == 3) -----
+// ---- conv_s2w.hip: 8x8 stride-2 pad-3 convolution as a space-to-depth Winograd F(2x2,4x4), LDS-staged (FAM_S2W) -----
 size_t sbgm_s2w_packed_floats(int Cout, int cs);
 int sbgm_launch_pack_s2w_weight(const float* w_oihw, float* up, int Cout, int Cin, int cs, hipStream_t st);
 int sbgm_launch_conv_s2w(ConvParams p, const ConvTile& cfg, hipStream_t st);    // p.wp = F(2x2,4x4) space-to-depth weights
@@ -327,9 +282,6 @@ int sbgm_launch_dsm_loss_bwd(const float* score, const float* z, const float* st
 // ---- batch_pack.hip (before the network) ------------------------------------------------------------------------------
 struct sbgm_assemble_args;
 int sbgm_launch_assemble_conditions(const sbgm_assemble_args& a, hipStream_t st);
-
-// ---- engine.hip: tile search for one convolution (used by the model's autotuner and by sbgm_conv2d_tune) -------------------
-int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, float* partial, size_t partial_floats, hipStream_t st, ConvTile* best);
 
 // ---- tiling.hip (full-domain tiles) -----------------------------------------------------------------------------------
 int sbgm_launch_extract_tiles(const float* dom, const int* origins, float* tiles, int T, int C, int Hd, int Wd, int th, int tw,

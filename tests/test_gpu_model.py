@@ -205,9 +205,125 @@ def test_tile_table_save_load_roundtrip(tmp_path):
         b.autotune(2, 64, 64, cache=bad)
 
 
+# tile columns "fco fpx splits ws wino lds" of every kernel family a 3x3 / stride 1 / 64 -> 64 convolution on 16x16 maps admits
+# and the kernel each names in the profile CSV
+FAMILY_TILES_3X3 = {"lds_direct": ("2 1 1 1 0 1", "conv3x3_lds_kernel<2; 1; false; false; 0>"),
+                    "lds_winograd": ("1 1 1 1 1 2", "conv3x3_lds_kernel<1; 1; true; true; 0>"),
+                    "winograd_1d": ("2 1 1 2 1 0", "conv3x3_wino_kernel<2; 1; 2>"),
+                    "winograd_2d": ("1 1 1 1 2 1", "conv3x3_w2d_kernel<1; 1; false; 0>"),
+                    "winograd_2d_two_buffers": ("1 1 1 1 2 2", "conv3x3_w2d_kernel<1; 1; true; 0>"),
+                    "winograd_2d_persistent": ("2 1 1 2 2 3", "conv3x3_w2dp_kernel<2; 0; false>")}
+
+
+def test_every_kernel_family_runs_from_a_loaded_tile_table(tmp_path):
+    """Every kernel family through the engine by table: the tuned table of B = 2, 64x64 is rewritten so that the stem's second 8x8
+    convolution runs as space-to-depth Winograd, the 1x1 convolutions as implicit GEMM and layer1's 3x3 64 -> 64 convolutions on
+    16x16 maps (in_mode 0) in turn as each of the six 3x3 families; a fresh model that loads the table agrees with the tuned model to
+    2e-5 max-rel (the bound between two plans of one network, as in the test below), launches the kernels the table names
+    (kernel column of the profile CSV) and saves the lines it loaded.  A table holds one tile per convolution key and this shape
+    has one 64 -> 64 key on 16x16 maps, so the six 3x3 families come from six tables loaded in turn into the same model, each holding
+    three families, not from a single table with all seven."""
+    import csv
+    import ctypes as C
+    from sbgm_danra_amd import _native as N
+    _, a, _ = build_pair(1)
+    _, b, _ = build_pair(1)
+    a.eval(), b.eval()
+    tuned = str(tmp_path / "tuned.txt")
+    a.autotune(2, 64, 64, cache=tuned)
+    g = torch.Generator().manual_seed(11)
+    x, c = torch.randn(2, 1, 64, 64, generator=g).cuda(), torch.randn(2, 1, 64, 64, generator=g).cuda()
+    t = torch.tensor([0.2, 0.7]).cuda()
+    with torch.no_grad():
+        want = a(x, t, cond_img=c).cpu()
+    lines = open(tuned).read().splitlines()
+    site, stem2 = "3 3 1 1 2 16 16 64 64 0 0 |", "8 8 2 3 2 32 32 64 64 0 0 |"
+    assert sum(ln.startswith(site) for ln in lines) == 1 and sum(ln.startswith(stem2) for ln in lines) == 1
+    assert any(ln.startswith("1 1 ") for ln in lines)
+    eng = b._engine(None, None, torch.empty(1, 1, 1, 1))
+    for name, (tile, kernel) in FAMILY_TILES_3X3.items():
+        out = []
+        for ln in lines:
+            key = ln.split("|")[0] + "|"
+            if ln.startswith(site):
+                ln = f"{key} {tile}"
+            elif ln.startswith(stem2):
+                ln = f"{key} 2 1 1 1 3 1"
+            elif ln.startswith("1 1 "):
+                ln = f"{key} 2 1 1 1 0 0"
+            out.append(ln)
+        text = "\n".join(out) + "\n"
+        path, again = str(tmp_path / f"{name}.txt"), str(tmp_path / f"{name}_saved.txt")
+        open(path, "w").write(text)
+        N.check(eng.lib.sbgm_model_tune_load(eng.h, os.fsencode(path)))
+        with torch.no_grad():
+            got = b(x, t, cond_img=c).cpu()
+        err = maxrel(got, want)
+        print(f"{name}: max-rel {err:.3e} against the tuned plan")
+        assert err <= 2e-5, (name, err)
+        prof, o, rows = N.Profile(), torch.empty_like(x), str(tmp_path / f"{name}.csv")
+        N.check(eng.lib.sbgm_model_profile_forward(eng.h, x.data_ptr(), t.data_ptr(), None, c.data_ptr(), None, None, o.data_ptr(), 2, 64, 64,
+                                                   C.byref(prof), rows.encode(), N.stream()))
+        rows = list(csv.DictReader(open(rows)))
+        layer1 = [r["kernel"] for r in rows if (r["kh"], r["stride"], r["H"], r["Cin_pad"], r["Cout"]) == ("3", "1", "16", "64", "64")]
+        assert layer1 == [kernel] * 4, (name, layer1)
+        assert [r["kernel"] for r in rows if r["kh"] == "8" and r["Cin_pad"] == "64"] == ["conv8x8s2_s2w_kernel<2>"]
+        linear = [r["kernel"] for r in rows if r["kh"] == "1"]
+        assert linear and all(k.startswith("conv_igemm_kernel<1; 1; ") and k.endswith("; 2; 1; 0; 1>") for k in linear), linear
+        N.check(eng.lib.sbgm_model_tune_save(eng.h, os.fsencode(again)))
+        assert open(again).read() == text, name
+
+
+def test_stem_conv1_stays_on_implicit_gemm_with_sixteen_channel_slots(tmp_path):
+    """9 to 16 input channels pad to 16 slots, the geometry the space-to-depth Winograd kernel takes; that kernel serves the stem's
+    second convolution only, also at a size (B = 8, 128x128: 256 workgroups of 32 channels) at which the static choice would take it"""
+    import csv
+    import ctypes as C
+    from sbgm_danra_amd import _native as N
+    _, net, _ = build_pair(8)
+    net.eval()
+    g = torch.Generator().manual_seed(4)
+    B, HW = 8, 128
+    x, c = torch.randn(B, 1, HW, HW, generator=g).cuda(), torch.randn(B, 8, HW, HW, generator=g).cuda()
+    t = (torch.rand(B, generator=g) * 0.9 + 0.05).cuda()
+    eng = net._engine(None, None, c)
+    prof, o, path = N.Profile(), torch.empty_like(x), str(tmp_path / "convs.csv")
+    N.check(N.lib().sbgm_model_profile_forward(eng.h, x.data_ptr(), t.data_ptr(), None, c.data_ptr(), None, None, o.data_ptr(), B, HW, HW,
+                                               C.byref(prof), path.encode(), N.stream()))
+    stem = [r for r in csv.DictReader(open(path)) if r["kh"] == "8"]
+    assert [(r["Cin_pad"], r["H"]) for r in stem] == [("16", "128"), ("64", "64")] and stem[0]["kernel"].startswith("conv_igemm_kernel<"), stem
+
+
+@pytest.fixture(scope="module")
+def untuned_net():
+    _, net, _ = build_pair(1)
+    return net.eval()
+
+
+GOOD_LINE = "3 3 1 1 2 16 16 64 64 0 0 | 2 1 1 1 1 0"
+MALFORMED = {"wino_3_on_a_3x3_key": "3 3 1 1 2 16 16 64 64 0 0 | 2 1 1 1 3 1",
+             "lds_3_with_wino_1": "3 3 1 1 2 16 16 64 64 0 0 | 2 1 1 1 1 3",
+             "fco_4_with_wino_3": "8 8 2 3 2 32 32 64 64 0 0 | 4 1 1 1 3 1",
+             "lds_0_with_wino_2": "3 3 1 1 2 16 16 64 64 0 0 | 2 1 1 1 2 0",
+             "cout_no_multiple_of_the_tile": "3 3 1 1 2 16 16 64 48 0 0 | 2 1 1 1 1 0",
+             "in_mode_3": "3 3 1 1 2 16 16 64 64 0 3 | 2 1 1 1 1 0"}
+
+
+@pytest.mark.parametrize("fault", list(MALFORMED))
+def test_malformed_tile_table_lines_are_rejected(tmp_path, untuned_net, fault):
+    """a 17-field line with one field out of its family's range is an error, beside the 10-field line of the round-trip test"""
+    from sbgm_danra_amd._native import NativeError
+    good, bad = str(tmp_path / "good.txt"), str(tmp_path / "bad.txt")
+    open(good, "w").write(GOOD_LINE + "\n")
+    untuned_net.autotune(2, 64, 64, cache=good)        # the unspoilt line loads
+    open(bad, "w").write(MALFORMED[fault] + "\n")
+    with pytest.raises(NativeError):
+        untuned_net.autotune(2, 64, 64, cache=bad)
+
+
 def test_static_plan_uses_the_current_kernels_and_agrees_with_the_tuned_plan(tmp_path):
     """A sampler or forward call that never ran the autotuner must not fall back to the first-generation kernels: at the C2 shape
-    the static choice (engine.hip pick_tile) puts the large 3x3 layers on the 2-D Winograd kernels and the 8x8 / 4x4 maps on the
+    the static choice (conv_plan.hip sbgm_static_tile) puts the large 3x3 layers on the 2-D Winograd kernels and the 8x8 / 4x4 maps on the
     1-D Winograd kernel, and its output equals the tuned plan's up to the kernels' rounding."""
     import csv
     import ctypes as C

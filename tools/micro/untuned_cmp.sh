@@ -1,5 +1,5 @@
 #!/bin/bash
-# static tile choice (engine.hip pick_tile) against the autotuned plan: ms per SDE step, EM sampler unless noted
+# static tile choice (conv_plan.hip sbgm_static_tile) against the autotuned plan: ms per SDE step, EM sampler unless noted
 # usage: bash tools/micro/untuned_cmp.sh [tuned]   -> gpurun_out/untuned_cmp.txt
 out=gpurun_out/untuned_cmp.txt; mkdir -p gpurun_out; : > $out
 run() { # label batch size sampler steps extra

@@ -69,7 +69,7 @@ int main(int argc, char** argv) {
 #endif
     // db: 0 single buffer, 1 double buffer, 3 persistent kernel (minw = workgroups per CU).  fco 9 (with -DEXP_W2X and KFILE w2x.hip):
     // the experimental 32x32x2 tiling
-    ConvTile ct{fco, 1, 1, minw, 2, db == 3 ? 3 : (db ? 2 : 1)};
+    const ConvTile ct = db == 3 ? ConvTile::w2d_persistent(fco, minw) : ConvTile::w2d(fco, minw, db != 0);
 #ifdef EXP_W2X
     auto launch = [&]() { return fco == 9 ? (db == 3 ? launch_w2xp(p, minw, nullptr) : launch_w2x(p, minw, db, nullptr)) : sbgm_launch_conv_w2d(p, ct, nullptr); };
 #else
