@@ -37,6 +37,8 @@ struct Param {
     float* img[CONV_IMAGES] = {};      // engine storage: the packed images of a convolution weight; index 0 alone for every other kind
     size_t floats[CONV_IMAGES] = {};
     bool filled = false;
+    struct Derived* feeds = nullptr;   // the derived image this tensor is a source of (set in build()), told of every upload
+    bool keep_oihw = false; float* oihw = nullptr;   // ... which then keeps the tensor as uploaded (OIHW) to rebuild from
     float* dev() const { return img[IMG_IGEMM]; }
     ConvImages images() const { ConvImages w; std::copy(img, img + CONV_IMAGES, w.img); return w; }
     size_t storage_floats() const {
@@ -57,6 +59,87 @@ struct AttnW { Param *ln1g, *ln1b, *ln2g, *ln2b, *inw, *inb, *outw, *outb, *f1w,
 struct BlockW { ConvW c1, c2, ds; BNW bn1, bn2, dsbn; bool has_ds; int cin, cout, stride; };
 struct DecW { ConvW up, conv; Param *n1g, *n1b, *n2g, *n2b, *freq, *tpw, *tpb; AttnW attn; bool has_attn; int cin, cout; };
 
+// ---- weights derived from uploaded weights ---------------------------------------------------------------------
+// Three images are computed from uploaded tensors, lazily and outside any captured step (who rebuilds which: refresh_derived).  The
+// folded BatchNorm (sbgm_model::bn_dirty) is raised by EVERY upload of any tensor.  The composed stem and the composed final block each
+// decide once whether they are active (`on`), are raised by an upload of one of their sources (Param::feeds, all the upload path knows
+// of them) and own every allocation behind them.
+struct Derived {
+    bool on = false, dirty = true;
+    std::vector<float*> owned;              // the image's own buffers and the OIHW copies of its sources
+    ~Derived() { for (float* q : owned) (void)hipFree(q); }
+    int alloc(float*& q, size_t floats) {
+        if (!q) { SBGM_HIP(hipMalloc(&q, floats * 4)); owned.push_back(q); }
+        return 0;
+    }
+    int source_uploaded(Param* p, const float* src, hipStream_t st) {
+        if (!on) return 0;
+        if (p->keep_oihw) {
+            if (alloc(p->oihw, (size_t)p->numel)) return 1;
+            SBGM_HIP(hipMemcpyAsync(p->oihw, src, (size_t)p->numel * 4, hipMemcpyDeviceToDevice, st));
+        }
+        dirty = true;
+        return 0;
+    }
+};
+
+// Composed stem of the samplers (conv_stem22.hip): conv2(conv1(.) + tb0) as one 22x22 / stride-4 kernel, built before an EM / PC / EDM
+// Heun run, never by a training upload or a plain forward.
+struct Stem : Derived {
+    float *wc = nullptr, *sb = nullptr;                    // composed weights and time-bias sums of the 25 border classes
+    static bool env_on() { static const bool v = getenv("SBGM_NO_STEM_COMPOSE") == nullptr; return v; }
+    void build(Param* w1, Param* w2) {                     // encoder.conv1 / conv2 weights
+        on = env_on();
+        w1->feeds = w2->feeds = this; w1->keep_oihw = w2->keep_oihw = true;
+    }
+    int prepare(const Param& w1, const Param& w2, int cin_total, hipStream_t st) {
+        if (!on || !dirty) return 0;
+        SBGM_CHECK(w1.oihw && w2.oihw, "sampler: encoder.conv1 / conv2 weights were never uploaded");
+        if (alloc(wc, sbgm_stem22_packed_floats(cin_total)) || alloc(sb, sbgm_stem22_bias_floats())) return 1;
+        if (sbgm_launch_pack_stem22(w1.oihw, w2.oihw, wc, sb, cin_total, st)) return 1;
+        dirty = false;
+        return 0;
+    }
+};
+
+// Composed final block (conv_final.hip): final_layer.conv(final_layer.conv_up(.)) as one 3x3 convolution to 16 channels, the 9 taps
+// of `conv` first.  cw / cb are no Params of the model (not in the state_dict, the gradient arena or Adam): their images live in one
+// allocation at fixed addresses (Wc OIHW [16][ci][3][3], bc [16], then the three packed images), so a cached step graph stays valid.
+struct FinalBlock : Derived {                                  // up: final_layer.conv_up.weight / .bias, w2: final_layer.conv.weight
+    float* wc = nullptr;
+    Param cw, cb;                                              // the composed weight and bias
+    static bool env_on() { static const bool v = getenv("SBGM_NO_FINAL_COMPOSE") == nullptr; return v; }
+    int build(const ConvW& up, Param* w2, int ci, bool resize_conv) {
+        // the 16-channel op runs on the LDS-staged Winograd kernels only, so the switches that take those away keep the projection path
+        on = env_on() && resize_conv && ci % 16 == 0 && up.w->img[IMG_WINO] != nullptr && !sbgm_conv_switches().no_lds &&
+             !sbgm_conv_switches().round1;
+        if (!on) return 0;
+        up.w->feeds = up.b->feeds = w2->feeds = this; up.w->keep_oihw = w2->keep_oihw = true;
+        cw.name = "final_layer.composed.weight"; cw.kind = P_CONV; cw.numel = (int64_t)16 * ci * 9;
+        cw.cout = 16; cw.cin = ci; cw.kh = cw.kw = 3; cw.cs = ci; cw.want_wino = true;
+        sbgm_conv_image_floats(3, 3, ci, 16, true, cw.floats);
+        cb.name = "final_layer.composed.bias"; cb.numel = cb.floats[0] = 16;
+        const size_t wc_floats = align_up((size_t)cw.numel, 64), total = wc_floats + cb.storage_floats() + cw.storage_floats();
+        if (alloc(wc, total)) return 1;
+        SBGM_HIP(hipMemset(wc, 0, total * 4));
+        cw.place(cb.place(wc + wc_floats));
+        cw.filled = cb.filled = true;
+        return 0;
+    }
+    int prepare(const ConvW& up, const Param& w2, hipStream_t st) {
+        if (!on || !dirty) return 0;
+        SBGM_CHECK(up.w->oihw && w2.oihw && up.b->filled, "final block: final_layer.conv_up / conv weights were never uploaded");
+        if (sbgm_launch_final_compose(up.w->oihw, up.b->dev(), w2.oihw, wc, cb.dev(), cw.cin, st)) return 1;
+        if (sbgm_pack_conv_images(wc, cw.img, 16, cw.cin, 3, 3, cw.cin, st)) return 1;
+        dirty = false;
+        return 0;
+    }
+};
+
+// Which evaluations take the composed stem (+ the run's condition term, null without condition channels) and the composed final block
+struct Routes { bool stem = false, fin = false; const float* stem_T = nullptr; };
+enum Caller { CALL_PLAIN, CALL_SDE_RUN, CALL_MEASURE };
+
 }  // namespace
 
 struct sbgm_model {
@@ -76,112 +159,27 @@ struct sbgm_model {
     bool enc_has_attn[5];
     DecW dec[4];
     ConvW fin_up, fin_conv;
-    bool bn_dirty = true;
-    // Composed stem of the samplers (conv_stem22.hip): conv2(conv1(.) + tb0) as one 22x22 / stride-4 kernel.  OIHW copies of the two
-    // weights are kept at upload; the composed image is built lazily (stem_dirty) before a sampler run, never by a training upload.
-    float *stem_w1 = nullptr, *stem_w2 = nullptr;          // OIHW encoder.conv1 / conv2 as uploaded
-    float *stem_wc = nullptr, *stem_sb = nullptr;          // composed weights and time-bias sums of the 25 border classes
-    bool stem_dirty = true;
-    const float* stem_T = nullptr;           // during a sampler run: the run's condition term [BE][H/4][W/4][64] (null: no condition channels)
-    bool stem_run = false;                   // set by the sampler drivers for the duration of a run: forward_impl composes the stem
-    static bool stem_enabled() { static const bool on = getenv("SBGM_NO_STEM_COMPOSE") == nullptr; return on; }
-    int stem_keep(const float* src, Param* p, float*& copy, hipStream_t st) {
-        if (!stem_enabled()) return 0;
-        if (!copy) SBGM_HIP(hipMalloc(&copy, (size_t)p->numel * 4));
-        SBGM_HIP(hipMemcpyAsync(copy, src, (size_t)p->numel * 4, hipMemcpyDeviceToDevice, st));
-        stem_dirty = true;
-        return 0;
-    }
-    int stem_prepare(hipStream_t st) {       // outside any captured step
-        if (!stem_dirty) return 0;
-        SBGM_CHECK(stem_w1 && stem_w2, "sampler: encoder.conv1 / conv2 weights were never uploaded");
-        if (!stem_wc) SBGM_HIP(hipMalloc(&stem_wc, sbgm_stem22_packed_floats(cin_total) * 4));
-        if (!stem_sb) SBGM_HIP(hipMalloc(&stem_sb, sbgm_stem22_bias_floats() * 4));
-        if (sbgm_launch_pack_stem22(stem_w1, stem_w2, stem_wc, stem_sb, cin_total, st)) return 1;
-        stem_dirty = false;
-        return 0;
-    }
-    // The run's condition term T = composed filter over the channels that do not change from step to step (lsm, topo, cond_img, in
-    // conv1's concatenation order after x), into `T`; then forward_impl routes the stem through the composed kernel until stem_end().
-    int stem_begin(const float* lsm, const float* topo, const float* cond, float* T, int B, int H, int W, hipStream_t st) {
-        if (!stem_enabled()) return 0;
-        if (stem_prepare(st)) return 1;
-        const float* srcs[3] = {lsm, topo, cond};
-        const int chs[3] = {cfg.n_lsm_channels, cfg.n_topo_channels, cfg.n_cond_channels};
-        int c0 = 1;
-        bool any = false;
-        for (int i = 0; i < 3; ++i) {
-            if (!chs[i]) continue;
-            if (sbgm_launch_conv_stem22(srcs[i], chs[i], c0, cin_total, stem_wc, nullptr, nullptr, any ? T : nullptr, nullptr, nullptr, 0,
-                                        T, B, H, W, st)) return 1;
-            c0 += chs[i];
-            any = true;
-        }
-        stem_T = any ? T : nullptr;
-        stem_run = true;
-        return 0;
-    }
-    struct StemRun {                         // ends the routing on every exit path of a sampler driver
-        sbgm_model* m;
-        ~StemRun() { m->stem_run = false; m->stem_T = nullptr; m->fin_run = false; }
-    };
-    size_t stem_t_bytes(int B, int H, int W) const {
-        return stem_enabled() && cin_total > 1 ? align_up((size_t)B * H * W * 4 * 4, 256) : 0;
-    }
-    // Composed final block (conv_final.hip): final_layer.conv(final_layer.conv_up(.)) as one 3x3 convolution to 16 channels, the 9 taps
-    // of `conv` first.  fin_comp is no Param (not in the state_dict, the gradient arena or Adam): its images live in fin_img at fixed
-    // addresses and are rebuilt lazily (fin_dirty) from OIHW copies kept at upload, outside any captured step.
-    float *fin_w1 = nullptr, *fin_w2 = nullptr;            // OIHW final_layer.conv_up.weight / final_layer.conv.weight as uploaded
-    float *fin_img = nullptr, *fin_wc = nullptr;           // one allocation: Wc OIHW [16][ci][3][3], bc [16], then the three packed images
-    Param fin_cw, fin_cb;
-    ConvW fin_comp;
-    bool fin_route = false, fin_dirty = true;
-    // Who takes the route: the EM / PC / EDM Heun drivers (fin_run, for the duration of a run), profile_forward and a tuning evaluation.
-    // The plain forward and the RK45 driver keep the projection path: rk45_sampler's Python loop and SciPy's solver behind ode_sampler
-    // evaluate the network through the plain forward, and at rtol 1e-4 their accept / reject decisions are within rounding of the
-    // native loop's -- with the composed block's rounding one run of tests/test_gpu_rk45_sampler.py took 452 evaluations under SciPy
-    // against 464 natively (bound 9), where the projection path gives 464 / 464.
-    bool fin_run = false;
-    static bool fin_enabled() { static const bool on = getenv("SBGM_NO_FINAL_COMPOSE") == nullptr; return on; }
-    int fin_build(int ci) {
-        // the 16-channel op runs on the LDS-staged Winograd kernels only, so the switches that take those away keep the projection path
-        fin_route = fin_enabled() && !cfg.decoder_transpose && ci % 16 == 0 && fin_up.w->img[IMG_WINO] != nullptr &&
-                    !sbgm_conv_switches().no_lds && !sbgm_conv_switches().round1;
-        if (!fin_route) return 0;
-        fin_cw.name = "final_layer.composed.weight"; fin_cw.kind = P_CONV; fin_cw.numel = (int64_t)16 * ci * 9;
-        fin_cw.cout = 16; fin_cw.cin = ci; fin_cw.kh = fin_cw.kw = 3; fin_cw.cs = ci; fin_cw.want_wino = true;
-        sbgm_conv_image_floats(3, 3, ci, 16, true, fin_cw.floats);
-        fin_cb.name = "final_layer.composed.bias"; fin_cb.numel = fin_cb.floats[0] = 16;
-        const size_t wc_floats = align_up((size_t)fin_cw.numel, 64);
-        const size_t total = wc_floats + fin_cb.storage_floats() + fin_cw.storage_floats();
-        SBGM_HIP(hipMalloc(&fin_img, total * 4));
-        SBGM_HIP(hipMemset(fin_img, 0, total * 4));
-        fin_wc = fin_img;
-        fin_cw.place(fin_cb.place(fin_img + wc_floats));
-        fin_cw.filled = fin_cb.filled = true;
-        fin_comp = ConvW{&fin_cw, &fin_cb};
-        return 0;
-    }
-    int fin_keep(const float* src, const Param* p, float*& copy, hipStream_t st) {
-        if (!copy) SBGM_HIP(hipMalloc(&copy, (size_t)p->numel * 4));
-        SBGM_HIP(hipMemcpyAsync(copy, src, (size_t)p->numel * 4, hipMemcpyDeviceToDevice, st));
-        fin_dirty = true;
-        return 0;
-    }
-    int fin_prepare(hipStream_t st) {        // outside any captured step
-        if (!fin_route || !fin_dirty) return 0;
-        SBGM_CHECK(fin_w1 && fin_w2 && fin_up.b->filled, "final block: final_layer.conv_up / conv weights were never uploaded");
-        const int ci = fin_cw.cin;
-        if (sbgm_launch_final_compose(fin_w1, fin_up.b->dev(), fin_w2, fin_wc, fin_cb.dev(), ci, st)) return 1;
-        if (sbgm_pack_conv_images(fin_wc, fin_cw.img, 16, ci, 3, 3, ci, st)) return 1;
-        fin_dirty = false;
-        return 0;
-    }
-    // what an evaluation reads besides the uploaded parameters: folded BatchNorm, the composed final block
+    bool bn_dirty = true;                    // folded BatchNorm (see Derived)
+    Stem stem; FinalBlock fin;
+    // What every evaluation reads besides the uploaded parameters: the BatchNorm fold and the final block, refreshed from forward_impl
+    // for eager calls and from SamplerRun, prepare_ws and autotune ahead of a capture.  The composed stem is NOT refreshed here but only
+    // where an EM / PC / EDM Heun run begins: a plain forward or a training-time evaluation must not start packing a 22x22 image.
     int refresh_derived(hipStream_t st) {
         if (bn_dirty && fold_bn(st)) return 1;
-        return fin_prepare(st);
+        return fin.prepare(fin_up, *fin_conv.w, st);
     }
+    // The one place that decides who evaluates through which form of the network, from the kind of caller:
+    //   the EM / PC / EDM Heun driver: composed stem and composed final block, for the duration of a run (~SamplerRun ends them);
+    //   profile_forward and a tuning evaluation: the final block only (the roofline and the tile table describe the two-convolution stem);
+    //   the plain forward and the RK45 driver: neither.  rk45_sampler's Python loop and SciPy's solver behind ode_sampler evaluate the
+    //   network through the plain forward, and at rtol 1e-4 their accept / reject decisions are within rounding of the native loop's: with
+    //   the composed block's rounding one run of tests/test_gpu_rk45_sampler.py took 452 evaluations under SciPy against 464 natively
+    //   (bound 9), where the projection path gives 464 / 464; a stem that rounds differently flips such decisions too.
+    Routes routes;
+    void set_routes(Caller c, const float* stem_T = nullptr) {
+        routes = Routes{c == CALL_SDE_RUN && stem.on, c != CALL_PLAIN && fin.on, c == CALL_SDE_RUN ? stem_T : nullptr};
+    }
+    size_t stem_t_bytes(int B, int H, int W) const { return stem.on && cin_total > 1 ? align_up((size_t)B * H * W * 4 * 4, 256) : 0; }
     // workspace
     char* ws = nullptr;
     size_t ws_bytes = 0, ws_used = 0;
@@ -253,7 +251,6 @@ struct sbgm_model {
     ~sbgm_model() {
         drop_step_graph();
         if (arena) (void)hipFree(arena);
-        for (float* q : {stem_w1, stem_w2, stem_wc, stem_sb, fin_w1, fin_w2, fin_img}) if (q) (void)hipFree(q);
         if (ws) (void)hipFree(ws);
         if (d_state) (void)hipFree(d_state);
         if (d_table) (void)hipFree(d_table);
@@ -452,11 +449,11 @@ int sbgm_model::build(const sbgm_model_config& c) {
         if (dec_block("decoder.residual_layers." + std::to_string(i), dec[i], dc, co, true, i < 2)) return 1;
         dc = co;
     }
-    DecW fin;
-    if (dec_block("decoder.final_layer", fin, dec[3].cin, 1, false, false)) return 1;
+    DecW fl;
+    if (dec_block("decoder.final_layer", fl, dec[3].cin, 1, false, false)) return 1;
     // final layer: its time-embedding tensors exist in the state_dict but are never used (score_unet.py:757)
-    fin.freq->kind = fin.tpw->kind = fin.tpb->kind = P_IGNORE;
-    fin_up = fin.up; fin_conv = fin.conv;
+    fl.freq->kind = fl.tpw->kind = fl.tpb->kind = P_IGNORE;
+    fin_up = fl.up; fin_conv = fl.conv;
 
     // ---- storage ----------------------------------------------------------------------------------------------------
     size_t total = 0;
@@ -491,7 +488,8 @@ int sbgm_model::build(const sbgm_model_config& c) {
     for (int li = 0; li < 4; ++li)
         for (auto& b : layers[li]) { place_bn(b.bn1, b.cout); place_bn(b.bn2, b.cout); if (b.has_ds) place_bn(b.dsbn, b.cout); }
     SBGM_HIP(hipMalloc(&d_state, sizeof(SamplerState)));
-    return fin_build(dec[3].cout);           // after the loop above: the route needs final_layer.conv_up to have its Winograd image
+    stem.build(conv1.w, conv2.w);
+    return fin.build(fin_up, fin_conv.w, dec[3].cout, !c.decoder_transpose);   // after place(): the route needs conv_up's Winograd image
 }
 
 int sbgm_model::ensure_ws(size_t bytes) {
@@ -699,7 +697,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     int ch = H / 4, cw_ = W / 4;
     float* cur = wsalloc((size_t)B * ch * cw_ * 64);
     if (!cur) return 1;
-    if (stem_run && !prof && !tuning) {
+    if (routes.stem) {
         // sampler runs: conv2(fm[0]) + bn1 + ReLU straight from x, the run's condition term and tb[0] (conv_stem22.hip); conv1 above
         // still writes fm[0], the decoder's last skip
         float* o = cur;
@@ -707,7 +705,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             o = wsalloc((size_t)B * ch * cw_ * 64);
             if (!o) return 1;
         }
-        if (sbgm_launch_conv_stem22(x, 1, 0, cin_total, stem_wc, stem_sb, tb[0], stem_T, bn_train ? nullptr : bn1.scale,
+        if (sbgm_launch_conv_stem22(x, 1, 0, cin_total, stem.wc, stem.sb, tb[0], routes.stem_T, bn_train ? nullptr : bn1.scale,
                                     bn_train ? nullptr : bn1.bias, bn_train ? 0 : 1, o, B, H, W, st)) return 1;
         if (bn_train && sbgm_launch_batchnorm_train(o, cur, bn1.g->dev(), bn1.b->dev(), bn1.rm->dev(), bn1.rv->dev(), nullptr, nullptr, true, B,
                                                     ch * cw_, 64, BN_EPS, BN_MOMENTUM, stats, st)) return 1;
@@ -850,14 +848,14 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             if (sbgm_launch_depth_space2(up, a, B, ch, cw_, ci, 1, st)) return 1;
             return sbgm_launch_conv3x3_cout1(a, fin_conv.w->dev(), fin_conv.b->dev(), t, cfg.sigma, out, B, H, W, ci, st);
         }
-        if (fin_route && (fin_run || prof != nullptr || tuning)) {
+        if (routes.fin) {
             // conv(conv_up(.)) composed: one 3x3 convolution from ci to the 9 taps (16 channels stored), rows [M][16], then the gather
             const Pending pend0 = pend;
-            if (conv_up(fin_comp, cur, ci, H, W, p, nullptr)) return 1;
+            if (conv_up(ConvW{&fin.cw, &fin.cb}, cur, ci, H, W, p, nullptr)) return 1;
             float* d = wsalloc((size_t)16 * B * H * W);
             if (!d) return 1;
             p.Cout = 16; p.out = d;
-            if (conv(ConvGeom{3, 3, 1, 1}, p, *fin_comp.w, st)) return 1;
+            if (conv(ConvGeom{3, 3, 1, 1}, p, fin.cw, st)) return 1;
             if (sbgm_launch_tap_gather_rows(d, fin_conv.b->dev(), t, cfg.sigma, out, B, H, W, st)) return 1;
             if (!tuning) return 0;
             pend = pend0;                        // a tuning evaluation also times the projection form below (plain forward, RK45)
@@ -991,28 +989,102 @@ struct SamplerConds {
     }
 };
 
+// What the drivers below share, done once: one sampler call's hold on the model.  open() validates the call and settles the workspace;
+// begin() carves the run's persistent buffers off its top (the forward uses the rest), refreshes the derived weights ahead of any
+// capture, builds the conditions, the routes and the tiled noise map and takes the buffers out of the forward's reach.  The destructor
+// gives the workspace back and ends the routes on every exit path.  Layout from `top` (BE = B, or 2B with guidance): `lead` slabs of
+// BE*per floats (slab 0: the network input, rows B.. mirror rows 0..B-1), the time vector [BE], double partials [BE], the kind's
+// further slabs, the composed stem's condition term.
+struct SamplerRun {
+    sbgm_model* m;
+    const sbgm_sampler_args& a;
+    hipStream_t st;                  // the caller's stream (ensure_step_graph points it at the capture stream meanwhile)
+    const char* who;                 // the driver's name in error texts
+    const bool graphed;
+    const int B = a.B, H = a.H, W = a.W, slabs = sbgm_model::sampler_slabs(a.kind), lead = a.kind == SBGM_SAMPLER_RK45 ? slabs : 3;
+    const bool guided = a.cfg_enabled != 0;
+    const int BE = guided ? 2 * B : B;                     // samples per network evaluation
+    const size_t per = (size_t)H * W, n = (size_t)B * per, slab = align_up((size_t)BE * per * 4, 256);
+    char* top = nullptr;
+    size_t saved_ws = 0;             // the model's ws_bytes while the run holds its slabs (0: not held)
+    SamplerConds conds{a, st};       // guidance: the unconditional half is built once per run
+    NoiseMap nm{};
+    ~SamplerRun() { if (saved_ws) m->ws_bytes = saved_ws; m->set_routes(CALL_PLAIN); }
+    size_t keep() const { return m->sampler_keep(BE, H, W, slabs); }
+    float* slab_at(int i) const { return reinterpret_cast<float*>(top + (i < lead ? i * slab : m->slabs_keep(BE, H, W, lead) + (i - lead) * slab)); }
+    float* t_vec() const { return reinterpret_cast<float*>(top + lead * slab); }
+    double* partials() const { return reinterpret_cast<double*>(top + lead * slab + align_up((size_t)BE * 4, 256)); }
+    float* stem_T() const { return reinterpret_cast<float*>(top + m->slabs_keep(BE, H, W, slabs)); }
+    int open() {
+        SBGM_CHECK(B >= 1 && H >= 32 && W >= 32, "%s: needs B >= 1 and H, W >= 32, got B=%d H=%d W=%d", who, B, H, W);
+        SBGM_CHECK(!(guided && a.bn_train), "%s: guidance with train-mode BatchNorm would couple the two halves of the batch", who);
+        return m->prepare_ws(BE, H, W, a.bn_train, st, slabs);
+    }
+    int begin(bool draws_noise = true) {
+        // Graph CAPTURE is illegal on the legacy default stream, so the step is captured on a private stream (capture records, it runs
+        // nothing); the replays, the uploads and the final copy go to the caller's stream: ordinary stream-ordered work of the caller.
+        if (graphed && !m->graph_stream) {
+            SBGM_HIP(hipStreamCreateWithFlags(&m->graph_stream, hipStreamNonBlocking));
+            SBGM_HIP(hipEventCreateWithFlags(&m->ev_replayed, hipEventDisableTiming));
+        }
+        top = m->ws + m->ws_bytes - keep();
+        if (m->refresh_derived(st)) return 1;
+        if (guided && conds.add_unconditional(a, m->cfg)) return 1;
+        if (a.kind != SBGM_SAMPLER_RK45) {
+            // The run's condition term T: the composed filter over the channels that do not change from step to step (lsm, topo, cond_img,
+            // in conv1's order after x).  On every call, outside the captured step: a cached step graph is replayed on new condition
+            // contents at the same addresses.
+            if (m->stem.prepare(*m->conv1.w, *m->conv2.w, m->cin_total, st)) return 1;
+            const float *srcs[3] = {conds.lsm, conds.topo, conds.cond}, *term = nullptr;
+            const int chs[3] = {m->cfg.n_lsm_channels, m->cfg.n_topo_channels, m->cfg.n_cond_channels};
+            for (int i = 0, c0 = 1; i < 3 && m->stem.on; c0 += chs[i++]) {
+                if (!chs[i]) continue;
+                if (sbgm_launch_conv_stem22(srcs[i], chs[i], c0, m->cin_total, m->stem.wc, nullptr, nullptr, term, nullptr, nullptr, 0, stem_T(), BE, H, W, st)) return 1;
+                term = stem_T();
+            }
+            m->set_routes(CALL_SDE_RUN, term);
+        }
+        if (a.tile_origins && draws_noise) {
+            SBGM_CHECK(W % 4 == 0 && a.domain_w >= W, "%s: tiled noise needs W %% 4 == 0 and domain_w >= W (W=%d, domain_w=%d)", who, W, a.domain_w);
+            nm = NoiseMap{a.tile_origins, H, W / 4, (a.domain_w + 3) / 4};
+        }
+        saved_ws = m->ws_bytes;
+        m->ws_bytes -= keep();       // forward() must not touch the run's slabs
+        return 0;
+    }
+    // One (possibly guided) score evaluation of slab 0 at t_vec() into dst[0 .. n), with guidance through scratch[0 .. 2n): in place for
+    // the SDE steps (dst = scratch = the score slab), from a scratch slab into the stage's own for the ODE.
+    int evaluate(float* dst, float* scratch, float w) {
+        float* xs = slab_at(0);
+        if (guided) SBGM_HIP(hipMemcpyAsync(xs + n, xs, n * 4, hipMemcpyDeviceToDevice, st));
+        if (m->forward(xs, t_vec(), conds.y, conds.cond, conds.lsm, conds.topo, guided ? scratch : dst, nullptr, BE, H, W, a.bn_train, st)) return 1;
+        return guided ? sbgm_launch_cfg_combine(dst, scratch, scratch + n, w, n, st) : 0;
+    }
+    // ensure_step_graph under k = value-initialised (the padding bytes compare equal) + the kind's own fields + what every kind bakes in
+    int capture(sbgm_model::StepGraphKey& k, const std::function<int()>& body) {
+        k.B = B; k.H = H; k.W = W; k.kind = a.kind; k.guided = guided; k.bn_train = a.bn_train;
+        k.y = conds.y; k.cond = conds.cond; k.lsm = conds.lsm; k.topo = conds.topo;
+        k.ws = m->ws; k.ws_bytes = saved_ws; k.cfg = a.cfg_scale; k.plan_gen = m->plan_gen;
+        return m->ensure_step_graph(k, guided, st, body);
+    }
+    int replay_done(int rc) {        // after the last replay; a guided graph goes: its condition copies are freed when the call returns
+        if (graphed && m->step_exec && hipEventRecord(m->ev_replayed, st) != hipSuccess && !rc) { sbgm_set_error("hipEventRecord failed"); rc = 2; }
+        if (graphed && guided) m->drop_step_graph();
+        return rc;
+    }
+};
+
 int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm) {
     const bool heun = edm != nullptr;                      // only sbgm_sampler_run_edm passes EDM arguments
     SBGM_CHECK(heun ? a.kind == SBGM_SAMPLER_EDM_HEUN : (a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC),
                "sampler: unknown kind %d", a.kind);
     SBGM_CHECK(a.num_steps >= 2, "sampler: num_steps=%d must be >= 2 (step size = t0 - t1)", a.num_steps);
     SBGM_CHECK(a.out != nullptr, "sampler: out is required");
-    const int B = a.B, H = a.H, W = a.W, N = a.num_steps;
-    const bool guided = a.cfg_enabled != 0;
-    SBGM_CHECK(!(guided && a.bn_train), "sampler: guidance with train-mode BatchNorm would couple the two halves of the batch");
-    const int BE = guided ? 2 * B : B;                     // samples per network evaluation
-    const size_t per = (size_t)H * W, n = (size_t)B * per;
-    const int slabs = sampler_slabs(a.kind);
-    if (prepare_ws(BE, H, W, a.bn_train, caller, slabs)) return 1;
-    // Graph CAPTURE is illegal on the legacy default stream, so the step is captured on a private stream (capture records, it runs
-    // nothing); the replays, the uploads and the final copy go to the caller's stream, so the run is ordinary stream-ordered work of
-    // the caller.
-    const bool graphed = a.use_graph && !a.noise;
-    if (graphed && !graph_stream) {
-        SBGM_HIP(hipStreamCreateWithFlags(&graph_stream, hipStreamNonBlocking));
-        SBGM_HIP(hipEventCreateWithFlags(&ev_replayed, hipEventDisableTiming));
-    }
-    hipStream_t st = caller;
+    SamplerRun run{this, a, caller, "sampler", a.use_graph && !a.noise};
+    if (run.open()) return 1;
+    const int B = a.B, N = a.num_steps, BE = run.BE;
+    const size_t per = run.per, n = run.n;
+    hipStream_t& st = run.st;
 
     // ---- step table and initial state, written into the pinned staging buffer and uploaded from there --------------------------
     static_assert(sizeof(EdmStep) >= sizeof(StepScalars), "the staging buffer is sized for the larger row");
@@ -1048,27 +1120,11 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     const StepScalars* sde_tab = static_cast<const StepScalars*>(d_table);
     const EdmStep* edm_tab = static_cast<const EdmStep*>(d_table);
 
-    // persistent sampler buffers live at the top of the workspace, the forward uses the rest
-    // layout (BE = B, or 2B with guidance): x [BE*per] (rows B.. mirror rows 0..B-1), score [BE*per], x_mean [B*per], time vector,
-    // norm partials, and for EDM Heun the derivative d after them.  EDM Heun: x is the network input, x_mean holds the state x / x_hat.
-    const size_t keep = sampler_keep(BE, H, W, slabs);
-    const size_t slab = align_up((size_t)BE * per * 4, 256);
-    char* top = ws + ws_bytes - keep;
-    float* xs = reinterpret_cast<float*>(top);
-    float* score = reinterpret_cast<float*>(top + slab);
-    float* xmean = reinterpret_cast<float*>(top + 2 * slab);
-    float* t_dev = reinterpret_cast<float*>(top + 3 * slab);
-    double* sumsq = reinterpret_cast<double*>(top + 3 * slab + align_up((size_t)BE * 4, 256));
-    float* dheun = heun ? reinterpret_cast<float*>(top + slabs_keep(BE, H, W, 3)) : nullptr;
-    float* stemT = reinterpret_cast<float*>(top + slabs_keep(BE, H, W, slabs));
-    const size_t fwd_bytes = ws_bytes - keep;
-    if (refresh_derived(st)) return 1;                  // keep the fold and the final block's rebuild out of the captured step
-    SamplerConds conds(a, st);                           // guidance: the unconditional half is built once per run
-    if (guided && conds.add_unconditional(a, cfg)) return 1;
-    // once per run, outside the captured step: a cached step graph is replayed on new condition contents at the same addresses
-    StemRun stem_guard{this};
-    fin_run = fin_route;
-    if (stem_begin(conds.lsm, conds.topo, conds.cond, stemT, BE, H, W, st)) return 1;
+    if (run.begin()) return 1;
+    // slabs: x (the network input), score, x_mean, and for EDM Heun the derivative d; EDM Heun keeps its state x / x_hat in x_mean
+    float *xs = run.slab_at(0), *score = run.slab_at(1), *xmean = run.slab_at(2), *dheun = heun ? run.slab_at(3) : nullptr;
+    float* t_dev = run.t_vec();
+    double* sumsq = run.partials();                          // the Langevin corrector's norm partials
 
     // x0 = randn * marginal_prob_std(1); EDM Heun: sigma_0 z into its state slab, copied to the network input
     const float ls = logf(sig);
@@ -1076,31 +1132,20 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     const float* z = a.noise;
     size_t draw = 0;
     auto next_z = [&]() -> const float* { const float* p = z ? z + draw * n : nullptr; ++draw; return p; };
-    NoiseMap nm{};
-    if (a.tile_origins) {
-        SBGM_CHECK(W % 4 == 0 && a.domain_w >= W, "sampler: tiled noise needs W %% 4 == 0 and domain_w >= W (W=%d, domain_w=%d)", W,
-                   a.domain_w);
-        nm = NoiseMap{a.tile_origins, H, W / 4, (a.domain_w + 3) / 4};
-    }
     const float x0_scale = heun ? reinterpret_cast<const EdmStep*>(h_stage)->sigma : std1;
-    if (sbgm_launch_init_noise(heun ? xmean : xs, x0_scale, next_z(), a.seed, d_state, 0, n, st, nm)) return 1;
+    if (sbgm_launch_init_noise(heun ? xmean : xs, x0_scale, next_z(), a.seed, d_state, 0, n, st, run.nm)) return 1;
     if (heun) SBGM_HIP(hipMemcpyAsync(xs, xmean, n * 4, hipMemcpyDeviceToDevice, st));
     if (sbgm_launch_fill_t(t_dev, tab.t_first, BE, st)) return 1;
     const float snr_nn = (float)((double)a.snr * std::sqrt((double)per));     // snr * sqrt(prod(x.shape[1:])) (:202-203)
 
-    // one (possibly guided) score evaluation of the current x into score[0 .. n)
-    auto evaluate = [&](float w) -> int {
-        if (guided) SBGM_HIP(hipMemcpyAsync(xs + n, xs, n * 4, hipMemcpyDeviceToDevice, st));
-        if (forward(xs, t_dev, conds.y, conds.cond, conds.lsm, conds.topo, score, nullptr, BE, H, W, a.bn_train, st)) return 1;
-        return guided ? sbgm_launch_cfg_combine(score, score, score + n, w, n, st) : 0;
-    };
+    auto evaluate = [&](float w) { return run.evaluate(score, score, w); };
     const bool churn = heun && edm->s_churn > 0.f;
     // One step of the run's kind; z_ptrs: read the caller's noise draws (eager runs).
     //   EM:  eval -> predictor + advance          PC: eval -> Langevin corrector -> eval -> predictor + advance
     //   EDM: (churn) -> eval -> euler -> eval -> heun + advance; `last` (sigma_N = 0) is Euler only, into `out`
     auto step = [&](bool z_ptrs, bool last) -> int {
         if (heun) {
-            if (churn && sbgm_launch_edm_churn(xmean, xs, z_ptrs ? next_z() : nullptr, edm_tab, d_state, nullptr, 0, a.seed, n, st, nm))
+            if (churn && sbgm_launch_edm_churn(xmean, xs, z_ptrs ? next_z() : nullptr, edm_tab, d_state, nullptr, 0, a.seed, n, st, run.nm))
                 return 1;
             if (evaluate(a.cfg_scale)) return 1;
             if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, edm_tab, d_state, nullptr, t_dev, BE, n, st)) return 1;
@@ -1110,47 +1155,39 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         }
         if (a.kind == SBGM_SAMPLER_PC) {
             if (evaluate(a.cfg_scale_corrector)) return 1;
-            if (sbgm_launch_langevin(xs, score, z_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, nm)) return 1;
+            if (sbgm_launch_langevin(xs, score, z_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, run.nm)) return 1;
         }
         if (evaluate(a.cfg_scale)) return 1;
         return sbgm_launch_em_update(xs, xmean, score, z_ptrs ? next_z() : nullptr, sde_tab, d_state, nullptr, 0, t_dev, a.seed, B,
-                                     per, N, st, BE, nm);
+                                     per, N, st, BE, run.nm);
     };
     // The run: N - tail steps (replays of the captured step, or eager launches), then `tail` eager last steps.  EM / PC: no tail,
     // the result is the x_mean slab, copied to `out`; EDM Heun: the tail is its Euler-only last step, which writes `out` itself.
     const int tail = heun ? 1 : 0;
-
-    const size_t saved_ws = ws_bytes;
-    ws_bytes = fwd_bytes;            // forward() must not touch the sampler slabs
     int rc = 0;
-    if (graphed) {
-        StepGraphKey key{};                                  // (value-initialised: the padding bytes compare equal)
-        key.B = B; key.H = H; key.W = W; key.kind = a.kind; key.guided = guided; key.bn_train = a.bn_train; key.churn = churn;
-        key.domain_w = a.domain_w; key.y = conds.y; key.cond = conds.cond; key.lsm = conds.lsm; key.topo = conds.topo;
-        key.origins = a.tile_origins; key.ws = ws; key.table = d_table; key.ws_bytes = saved_ws; key.cfg = a.cfg_scale;
-        key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn; key.plan_gen = plan_gen;
-        rc = ensure_step_graph(key, guided, st, [&] { return step(false, false); });
+    if (run.graphed) {
+        StepGraphKey key{};
+        key.churn = churn; key.domain_w = a.domain_w; key.origins = a.tile_origins; key.table = d_table;
+        key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn;
+        rc = run.capture(key, [&] { return step(false, false); });
         for (int i = 0; i < N - tail && rc == 0; ++i)
             if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
-        if (step_exec && hipEventRecord(ev_replayed, st) != hipSuccess && !rc) { sbgm_set_error("hipEventRecord failed"); rc = 2; }
     } else {
         for (int i = 0; i < N - tail && rc == 0; ++i) rc = step(z != nullptr, false);
     }
     if (tail && rc == 0) rc = step(z != nullptr, true);
-    if (graphed && guided) drop_step_graph();          // its condition copies are freed when this call returns
-    ws_bytes = saved_ws;
-    if (rc) return rc;
+    if ((rc = run.replay_done(rc))) return rc;
     if (!tail) SBGM_HIP(hipMemcpyAsync(a.out, xmean, n * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
-// rk45_sampler: the adaptive probability-flow ODE solver (ode.hip).  The fourth kind of the driver above shares its workspace rule,
-// its condition handling and its cached step graph; what differs is the loop: its length is decided on the device.  One ATTEMPT is
+// rk45_sampler: the adaptive probability-flow ODE solver (ode.hip).  The fourth kind shares the run context above (workspace rule,
+// condition handling, cached step graph); what differs is the loop: its length is decided on the device.  One ATTEMPT is
 // captured (six stage kernels with their evaluations, the norm, the controller, a 4-byte copy of the done word to pinned memory, the
 // commit): a linear chain that depends on nothing that changes between attempts or runs, because t, h, tolerances, flags and counters
 // live in the device state block.  The host replays it on the caller's stream and stays at most one attempt ahead of the done word it
 // waits for, so the device does not idle on the poll; an attempt that runs after done finds every controller frozen and changes
-// nothing.
+// nothing.  It sets no route (set_routes).
 int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, const OdeArgs& o) {
     SBGM_CHECK(a.kind == SBGM_SAMPLER_RK45, "sampler_ode: kind %d is not SBGM_SAMPLER_RK45", a.kind);
     SBGM_CHECK(a.out != nullptr && o.stats_i != nullptr, "sampler_ode: out and stats_i are required");
@@ -1159,70 +1196,40 @@ int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, cons
     SBGM_CHECK(o.t0 != o.t1 && std::min(o.t0, o.t1) >= 0.0 && std::max(o.t0, o.t1) <= 1.0, "sampler_ode: t_span (%g, %g) must be two "
                "different times in [0, 1]", o.t0, o.t1);
     SBGM_CHECK(!(a.tile_origins && !o.per_sample), "sampler_ode: tiles need one controller per sample (a shared step would couple them)");
-    const int B = a.B, H = a.H, W = a.W;
-    const bool guided = a.cfg_enabled != 0;
-    const int BE = guided ? 2 * B : B;
-    const size_t per = (size_t)H * W, n = (size_t)B * per;
-    const int G = o.per_sample ? B : 1;
-    if (prepare_ws(BE, H, W, 0, caller, ODE_SLABS)) return 1;
-    const bool graphed = a.use_graph != 0;
-    if (graphed && !graph_stream) {
-        SBGM_HIP(hipStreamCreateWithFlags(&graph_stream, hipStreamNonBlocking));
-        SBGM_HIP(hipEventCreateWithFlags(&ev_replayed, hipEventDisableTiming));
-    }
+    SamplerRun run{this, a, caller, "sampler_ode", a.use_graph != 0};
+    if (run.open()) return 1;
+    const int B = a.B, G = o.per_sample ? B : 1;
+    const size_t per = run.per, n = run.n;
+    hipStream_t& st = run.st;
     if (!h_done) {
         SBGM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_done), 64, hipHostMallocDefault));
         for (hipEvent_t& e : ev_poll) SBGM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    hipStream_t st = caller;
 
-    // workspace: 14 slabs at the top (xs | score2 | K[0..6] | y, y | y_new, y_new | state + partials), then the time vector
-    const size_t keep = sampler_keep(BE, H, W, ODE_SLABS);
-    const size_t slab = align_up((size_t)BE * per * 4, 256);
-    char* top = ws + ws_bytes - keep;
-    float* xs = reinterpret_cast<float*>(top);
-    float* score2 = reinterpret_cast<float*>(top + slab);
-    float* K = reinterpret_cast<float*>(top + 2 * slab);
-    const size_t ks = slab / 4;
-    double* y = reinterpret_cast<double*>(top + 9 * slab);
-    double* y_new = reinterpret_cast<double*>(top + 11 * slab);
-    char* state = top + 13 * slab;
+    if (run.begin(o.x0 == nullptr)) return 1;
+    // the 14 slabs: xs | score2 | K[0..6] | y, y | y_new, y_new | state + partials
+    float *xs = run.slab_at(0), *score2 = run.slab_at(1), *K = run.slab_at(2), *t_dev = run.t_vec();
+    const size_t ks = run.slab / 4;
+    double *y = reinterpret_cast<double*>(run.slab_at(9)), *y_new = reinterpret_cast<double*>(run.slab_at(11));
+    char* state = reinterpret_cast<char*>(run.slab_at(13));
     const size_t state_bytes = align_up(sbgm_ode_state_bytes(G), 256);
     double* partials = reinterpret_cast<double*>(state + state_bytes);
-    SBGM_CHECK(state_bytes + sbgm_ode_partials_bytes(B, per) <= slab, "sampler_ode: %d x %d samples are too small for the solver's state slab", H, W);
-    float* t_dev = reinterpret_cast<float*>(top + ODE_SLABS * slab);
-    const size_t fwd_bytes = ws_bytes - keep;
-    if (refresh_derived(st)) return 1;
-    SamplerConds conds(a, st);
-    if (guided && conds.add_unconditional(a, cfg)) return 1;
-    // The composed stem (stem_begin) is NOT used here: rk45_sampler's Python loop evaluates the network through the plain forward and
-    // must take the same accept / reject decisions as this loop (one computation, bit for bit); a stem that rounds differently flips a
-    // decision whose error norm lies within rounding of 1.
+    SBGM_CHECK(state_bytes + sbgm_ode_partials_bytes(B, per) <= run.slab, "sampler_ode: %d x %d samples are too small for the solver's state slab", a.H, a.W);
 
     // start: the caller's state, or marginal_prob_std(t0) * draw 0 of the run's Philox stream (domain-keyed on tiles)
     if (sbgm_launch_ode_init(state, G, o.t0, o.t1, o.rtol, o.atol, cfg.sigma, o.max_steps, st)) return 1;
     if (o.x0) {
         if (sbgm_launch_ode_load(y, o.x0, n, st)) return 1;
     } else {
-        NoiseMap nm{};
-        if (a.tile_origins) {
-            SBGM_CHECK(W % 4 == 0 && a.domain_w >= W, "sampler_ode: tiled noise needs W %% 4 == 0 and domain_w >= W (W=%d, domain_w=%d)", W,
-                       a.domain_w);
-            nm = NoiseMap{a.tile_origins, H, W / 4, (a.domain_w + 3) / 4};
-        }
         const float ls = logf(cfg.sigma), t0f = (float)o.t0;
         const float std0 = fmaxf(sqrtf((expf((2.f * t0f) * ls) - 1.f) / (2.f * ls)), 1e-5f);
-        if (sbgm_launch_init_noise(xs, std0, a.noise, a.seed, nullptr, 0, n, st, nm)) return 1;
+        if (sbgm_launch_init_noise(xs, std0, a.noise, a.seed, nullptr, 0, n, st, run.nm)) return 1;
         if (sbgm_launch_ode_load(y, xs, n, st)) return 1;
     }
 
-    auto evaluate = [&](float* dst) -> int {
-        if (guided) SBGM_HIP(hipMemcpyAsync(xs + n, xs, n * 4, hipMemcpyDeviceToDevice, st));
-        if (forward(xs, t_dev, conds.y, conds.cond, conds.lsm, conds.topo, guided ? score2 : dst, nullptr, BE, H, W, 0, st)) return 1;
-        return guided ? sbgm_launch_cfg_combine(dst, score2, score2 + n, a.cfg_scale, n, st) : 0;
-    };
+    auto evaluate = [&](float* dst) { return run.evaluate(dst, score2, a.cfg_scale); };
     auto stage = [&](int phase) -> int {
-        return sbgm_launch_ode_stage(state, phase, y, y_new, K, ks, xs, t_dev, guided ? 2 : 1, B, per, o.per_sample, st);
+        return sbgm_launch_ode_stage(state, phase, y, y_new, K, ks, xs, t_dev, run.guided ? 2 : 1, B, per, o.per_sample, st);
     };
     auto control = [&](int what) -> int {
         if (sbgm_launch_ode_control(state, what, y, y_new, K, ks, partials, B, per, o.per_sample, st)) return 1;
@@ -1236,27 +1243,22 @@ int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, cons
         return sbgm_launch_ode_commit(state, y, y_new, K, ks, B, per, o.per_sample, st);
     };
 
-    const size_t saved_ws = ws_bytes;
-    ws_bytes = fwd_bytes;            // forward() must not touch the solver's slabs
-    int rc = 0;
     long long enqueued = 0;
     // select_initial_step: f0, the two norms, f1 at t0 + h0, the third norm; then the first attempt is prepared
-    rc = stage(SBGM_ODE_PHASE_F0) || evaluate(K) || control(0) || stage(SBGM_ODE_PHASE_F1) || evaluate(K + ks) || control(1);
+    int rc = stage(SBGM_ODE_PHASE_F0) || evaluate(K) || control(0) || stage(SBGM_ODE_PHASE_F1) || evaluate(K + ks) || control(1);
     if (rc == 0 && (hipEventRecord(ev_poll[0], st) != hipSuccess || hipEventSynchronize(ev_poll[0]) != hipSuccess)) {
         sbgm_set_error("sampler_ode: waiting for the initial step failed: %s", hipGetErrorString(hipGetLastError()));
         rc = 2;
     }
     volatile int* done = h_done;
     if (rc == 0 && !*done) {
-        if (graphed) {
+        if (run.graphed) {
             StepGraphKey key{};
-            key.B = B; key.H = H; key.W = W; key.kind = a.kind; key.guided = guided; key.ode_norm = o.per_sample;
-            key.y = conds.y; key.cond = conds.cond; key.lsm = conds.lsm; key.topo = conds.topo; key.ws = ws; key.ws_bytes = saved_ws;
-            key.cfg = a.cfg_scale; key.plan_gen = plan_gen;
-            rc = ensure_step_graph(key, guided, st, attempt);
+            key.ode_norm = o.per_sample;
+            rc = run.capture(key, attempt);
         }
         auto launch = [&]() -> int {
-            if (graphed) {
+            if (run.graphed) {
                 if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at attempt %lld", enqueued); return 2; }
             } else if (attempt()) {
                 return 1;
@@ -1274,11 +1276,8 @@ int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, cons
             if (rc || *done) break;
             if (k + 1 >= cap) { sbgm_set_error("sampler_ode: %lld attempts did not finish the run", cap); rc = 2; }
         }
-        if (graphed && step_exec && hipEventRecord(ev_replayed, st) != hipSuccess && !rc) { sbgm_set_error("hipEventRecord failed"); rc = 2; }
     }
-    if (graphed && guided) drop_step_graph();          // its condition copies are freed when this call returns
-    ws_bytes = saved_ws;
-    if (rc) return rc;
+    if ((rc = run.replay_done(rc))) return rc;
     if (sbgm_launch_ode_store(a.out, y, n, st)) return 1;
     if (sbgm_ode_read_state(state, G, o.stats_i, o.stats_d, st)) return 1;       // synchronises: the run is complete on return
     o.stats_i[4 * G] = enqueued - o.stats_i[4 * G + 1];                            // surplus attempts: enqueued, found nothing to do
@@ -1325,12 +1324,8 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
     const float* src = static_cast<const float*>(data);
     if (p->kind == P_VEC) {
         SBGM_HIP(hipMemcpyAsync(p->dev(), src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
-        if (p == m->fin_up.b) m->fin_dirty = true;
     } else if (p->kind == P_CONV) {
         if (sbgm_pack_conv_images(src, p->img, p->cout, p->cin, p->kh, p->kw, p->cs, st)) return 1;
-        if (p == m->conv1.w && m->stem_keep(src, p, m->stem_w1, st)) return 1;
-        if (p == m->conv2.w && m->stem_keep(src, p, m->stem_w2, st)) return 1;
-        if (m->fin_route && p == m->fin_up.w && m->fin_keep(src, p, m->fin_w1, st)) return 1;
     } else if (p->kind == P_TCONV) {             // [Cin][Cout][2][2] -> OIHW [4*Cout][Cin][1][1] (scratch) -> packed
         float* tmp = nullptr;
         SBGM_HIP(hipMalloc(&tmp, (size_t)numel * 4));
@@ -1344,8 +1339,8 @@ int sbgm_model_set_param(sbgm_model* m, const char* name, const void* data, int6
             SBGM_HIP(hipMemcpyAsync(p->dev() + (size_t)r * numel, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, st));
     } else {
         if (sbgm_launch_pack_cout1_weight(src, p->dev(), p->cin, st)) return 1;
-        if (m->fin_route && p == m->fin_conv.w && m->fin_keep(src, p, m->fin_w2, st)) return 1;
     }
+    if (p->feeds && p->feeds->source_uploaded(p, src, st)) return 1;
     p->filled = true;
     m->bn_dirty = true;
     return 0;
@@ -1410,11 +1405,11 @@ int sbgm_model::dummy_forward(int B, int H, int W, bool tune, hipStream_t st) {
     if (sbgm_launch_fill_t(t, 0.5f, B, st)) return 1;
     const size_t saved = ws_bytes;
     ws_bytes -= align_up(in_floats * 4, 256);
-    tuning = tune;
+    tuning = tune; set_routes(tune ? CALL_MEASURE : CALL_PLAIN);
     ws_used = 0;
     const int rc = forward(x, t, nullptr, cfg.n_cond_channels ? cond : nullptr, cfg.n_lsm_channels ? lsm : nullptr,
                            cfg.n_topo_channels ? topo : nullptr, out, nullptr, B, H, W, 0, st);
-    tuning = false;
+    tuning = false; set_routes(CALL_PLAIN);
     ws_bytes = saved;
     SBGM_HIP(hipStreamSynchronize(st));
     return rc;
@@ -1465,7 +1460,9 @@ int sbgm_model_profile_forward(sbgm_model* m, const float* x, const float* t, co
     SBGM_HIP(hipEventCreate(&t1));
     m->prof = &recs;
     SBGM_HIP(hipEventRecord(t0, st));
+    m->set_routes(CALL_MEASURE);
     const int rc = m->forward(x, t, y, cond_img, lsm_cond, topo_cond, out, nullptr, B, H, W, 0, st);
+    m->set_routes(CALL_PLAIN);
     SBGM_HIP(hipEventRecord(t1, st));
     m->prof = nullptr;
     if (rc) return rc;

@@ -226,3 +226,29 @@ def test_weight_updates_reach_the_composed_stem(which):
     assert torch.equal(after, want)
     net.load_state_dict(sd)                                   # and back, through load_state_dict
     assert torch.equal(_em(net, c), before)
+
+
+def test_a_run_leaves_nothing_behind():
+    """a plain eval-mode forward gives the same bits before and after a graphed EM run and a sampler call the engine refuses once its
+    routes are set (tile origins with a domain narrower than the tile): neither leaves the composed routes or a truncated workspace
+    on the model"""
+    import sbgm_danra_amd as S
+    _, net, _ = build_pair(1)
+    net.eval()
+    g = torch.Generator().manual_seed(41)
+    x, c = torch.randn(2, 1, 32, 32, generator=g).cuda(), torch.randn(2, 1, 32, 32, generator=g).cuda()
+    t = (torch.rand(2, generator=g) * 0.9 + 0.05).cuda()
+
+    def forward():
+        with torch.no_grad():
+            return net(x, t, cond_img=c).cpu()
+
+    first = forward()
+    assert torch.isfinite(_em(net, c)).all()
+    handle = net._engine(None, None, c).h
+    ws_bytes = N.lib().sbgm_model_workspace_bytes(handle)
+    with pytest.raises(N.NativeError):
+        S.Euler_Maruyama_sampler(net, S.marginal_prob_std_fn, S.diffusion_coeff_fn, batch_size=2, num_steps=3, device=DEV, img_size=32,
+                                 cond_img=c, seed=11, tile_origins=torch.zeros(2, 2, dtype=torch.int32).cuda(), domain_width=16)
+    assert N.lib().sbgm_model_workspace_bytes(handle) == ws_bytes
+    assert torch.equal(forward(), first)
