@@ -142,6 +142,23 @@ int sbgm_sampler_run(sbgm_model* m, const sbgm_sampler_args* a, void* stream);
 int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
                          float s_tmin, float s_tmax, float s_noise, void* stream);
 
+/* Constrained sampling (imputation / inpainting, Song et al. 2021 App. I.2): sbgm_sampler_run and sbgm_sampler_run_edm with known pixels
+ * held.  known, known_mask: device fp32 [B][1][H][W], both required, used in place (no copy: new contents at the same addresses are read
+ * by a cached step graph's replays, as the conditions are); known_mask is clamped to [0,1] in the kernels, known may hold anything (NaN
+ * included) where the mask is 0.  hold(v, target, m) = v if m == 0, target if m == 1 (both bit-exactly), else (1-m) v + m target; std =
+ * marginal_prob_std in double at the step table's fp32 times, rounded to fp32.
+ *   start:      x0 = scale z0 + m known (where m > 0), scale = std(1), or sigma_0 for EDM Heun.
+ *   EM / PC predictor, step i, draw z:  x_mean = hold(mean, known, m); x = hold(mean + noise z, known + std(t_{i+1}) z, m), level 0 on
+ *               the last step, so out equals known where the mask is 1.
+ *   PC corrector, step i, draw z:       x = hold(x + eps score + sqrt(2 eps) z, known + std(t_i) z, m); the score norm is unchanged.
+ *   EDM Heun:   both the Euler and the Heun output of step i are hold(., known + sigma_{i+1} z0, m) with the run's draw 0 (read from
+ *               noise[0], or recomputed from the seed): the trajectory of a point mass, deterministic.  The churn is not constrained.
+ * No extra noise draw is consumed (a held pixel reuses the draw of its update kernel), no launch is added, guidance acts on the
+ * evaluations only, and the captured step's key holds the two pointers.  Everything else is as in the unconstrained entry points. */
+int sbgm_sampler_run_held(sbgm_model* m, const sbgm_sampler_args* a, const float* known, const float* known_mask, void* stream);
+int sbgm_sampler_run_edm_held(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
+                              float s_tmin, float s_tmax, float s_noise, const float* known, const float* known_mask, void* stream);
+
 /* Adaptive deterministic sampler: the probability-flow ODE dx/dt = -1/2 g(t)^2 score(x, t) integrated from t0 to t1 by
  * Dormand-Prince 5(4) with the step controller of scipy.integrate.RK45 (select_initial_step, FSAL, accept when the RMS error
  * norm is < 1, factor min(10, 0.9 err^-0.2), max(0.2, .) on rejection), entirely on the device.  a->kind must be
@@ -546,6 +563,11 @@ int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, ui
 int sbgm_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, float sigma_hat, float sigma_next, int64_t n,
                    void* stream);
 int sbgm_edm_heun(float* x, const float* d, const float* score, float sigma_hat, float sigma_next, int64_t n, void* stream);
+/* The hold of constrained sampling as an op of its own, called after a step op above by loops that run the network themselves:
+ * x = hold(x, known + level*z, m) and, when x_mean is not NULL, x_mean = hold(x_mean, known, m).  z NULL -> the Philox draw
+ * (seed, draw_index), i.e. the draw the step op just consumed. */
+int sbgm_hold_known(float* x, float* x_mean, const float* known, const float* known_mask, const float* z, float level, uint64_t seed,
+                    uint64_t draw_index, int64_t n, void* stream);
 
 /* The pieces of the RK45 solver above, for callers that run the network evaluations themselves (rk45_sampler's Python loop).
  * `state` is an opaque device block of sbgm_rk45_state_bytes bytes for `groups` controllers (1, or B with per_sample); K holds the seven

@@ -81,6 +81,8 @@ SIGNATURES = {
     "sbgm_model_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "sbgm_sampler_run": (_i, [_vp, C.POINTER(SamplerArgs), _vp]),
     "sbgm_sampler_run_edm": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _vp]),
+    "sbgm_sampler_run_held": (_i, [_vp, C.POINTER(SamplerArgs), _vp, _vp, _vp]),
+    "sbgm_sampler_run_edm_held": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
     "sbgm_sampler_run_ode": (_i, [_vp, C.POINTER(SamplerArgs), _d, _d, _d, _d, _i, _i64, _vp, _vp, _vp, _vp]),
     "sbgm_pointwise_chain": (_i, [_vp, _vp, _i64, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     "sbgm_sample_extremes": (_i, [_vp, _i, _i64, _f, _vp, _vp, _vp]),
@@ -184,6 +186,7 @@ SIGNATURES = {
     "sbgm_edm_churn": (_i, [_vp, _vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_edm_euler": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i64, _vp]),
     "sbgm_edm_heun": (_i, [_vp, _vp, _vp, _f, _f, _i64, _vp]),
+    "sbgm_hold_known": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_rk45_state_bytes": (_i64, [_i]),
     "sbgm_rk45_partials_bytes": (_i64, [_i, _i64]),
     "sbgm_rk45_init": (_i, [_vp, _i, _d, _d, _d, _d, _f, _i64, _vp]),

@@ -340,6 +340,13 @@ int sbgm_langevin_step(float* x, const float* score, const float* z, float snr_n
                        uint64_t draw_index, int B, int64_t per_sample, void* stream) {
     return sbgm_launch_langevin(x, score, z, snr_noise_norm, (double*)sumsq_ws, nullptr, draw_index, seed, B, (size_t)per_sample, ST);
 }
+int sbgm_hold_known(float* x, float* x_mean, const float* known, const float* known_mask, const float* z, float level, uint64_t seed,
+                    uint64_t draw_index, int64_t n, void* stream) {
+    Hold h{};
+    h.known = known;
+    h.mask = known_mask;
+    return sbgm_launch_hold_known(x, x_mean, z, level, seed, draw_index, (size_t)n, ST, h);
+}
 int sbgm_cfg_combine(float* out, const float* s_cond, const float* s_uncond, float scale, int64_t n, void* stream) {
     return sbgm_launch_cfg_combine(out, s_cond, s_uncond, scale, (size_t)n, ST);
 }

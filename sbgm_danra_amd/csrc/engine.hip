@@ -187,6 +187,8 @@ struct sbgm_model {
     SamplerState* d_state = nullptr;
     void* d_table = nullptr;                // step table of the current run: StepScalars rows (EM, PC) or EdmStep rows (EDM Heun)
     size_t table_bytes = 0;                 // its capacity
+    HoldLevels* d_levels = nullptr;         // hold levels of a constrained EM / PC run, one row per step (allocated by the first such run)
+    size_t levels_rows = 0;                 // its capacity
     // pinned host staging of a run's step table + initial state: the upload is a true asynchronous copy, so sbgm_sampler_run does not
     // have to wait for it (or for anything enqueued before it); ev_stage guards the buffer against the next call's rewrite
     char* h_stage = nullptr;
@@ -209,6 +211,7 @@ struct sbgm_model {
     struct StepGraphKey {
         int B, H, W, kind, guided, bn_train, domain_w, churn, ode_norm;
         const void *y, *cond, *lsm, *topo, *origins, *ws, *table;
+        const void *known, *known_mask, *levels;   // constrained runs (null otherwise): a held and an unheld step never share a graph
         size_t ws_bytes;
         float cfg, cfg_corr, snr_nn;
         unsigned long long plan_gen;
@@ -254,6 +257,7 @@ struct sbgm_model {
         if (ws) (void)hipFree(ws);
         if (d_state) (void)hipFree(d_state);
         if (d_table) (void)hipFree(d_table);
+        if (d_levels) (void)hipFree(d_levels);
         if (h_stage) (void)hipHostFree(h_stage);
         if (ev_stage) (void)hipEventDestroy(ev_stage);
         if (graph_stream) (void)hipStreamDestroy(graph_stream);
@@ -356,7 +360,8 @@ struct sbgm_model {
         return rc;
     }
     struct EdmArgs { float sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise; };
-    int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr);
+    struct HeldArgs { const float *known, *mask; };        // constrained sampling: both device [B][1][H][W], used in place
+    int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr, const HeldArgs* held = nullptr);
     struct OdeArgs { double t0, t1, rtol, atol; int per_sample; long long max_steps; const float* x0; int64_t* stats_i; double* stats_d; };
     int sampler_ode(const sbgm_sampler_args& a, hipStream_t st, const OdeArgs& o);
 };
@@ -1074,8 +1079,9 @@ struct SamplerRun {
     }
 };
 
-int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm) {
+int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm, const HeldArgs* held) {
     const bool heun = edm != nullptr;                      // only sbgm_sampler_run_edm passes EDM arguments
+    SBGM_CHECK(!held || (held->known && held->mask), "sampler: a constrained run needs both known and known_mask");
     SBGM_CHECK(heun ? a.kind == SBGM_SAMPLER_EDM_HEUN : (a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC),
                "sampler: unknown kind %d", a.kind);
     SBGM_CHECK(a.num_steps >= 2, "sampler: num_steps=%d must be >= 2 (step size = t0 - t1)", a.num_steps);
@@ -1088,7 +1094,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
 
     // ---- step table and initial state, written into the pinned staging buffer and uploaded from there --------------------------
     static_assert(sizeof(EdmStep) >= sizeof(StepScalars), "the staging buffer is sized for the larger row");
-    const size_t stage_need = sizeof(EdmStep) * (size_t)N + sizeof(SamplerState);
+    const size_t stage_need = (sizeof(EdmStep) + sizeof(HoldLevels)) * (size_t)N + sizeof(SamplerState);
     if (stage_pending) {                                   // the previous call's upload still reads the buffer (normally long done)
         SBGM_HIP(hipEventSynchronize(ev_stage));
         stage_pending = false;
@@ -1096,7 +1102,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     if (h_stage_bytes < stage_need) {
         if (h_stage) SBGM_HIP(hipHostFree(h_stage));
         h_stage = nullptr;
-        h_stage_bytes = std::max(stage_need, sizeof(EdmStep) * (size_t)4096 + sizeof(SamplerState));
+        h_stage_bytes = std::max(stage_need, (sizeof(EdmStep) + sizeof(HoldLevels)) * (size_t)4096 + sizeof(SamplerState));
         SBGM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_stage), h_stage_bytes, hipHostMallocDefault));
     }
     if (!ev_stage) SBGM_HIP(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming));
@@ -1115,12 +1121,37 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     *state0 = SamplerState{0ull, 0ull, (unsigned long long)a.seed, (unsigned long long)N};
     SBGM_HIP(hipMemcpyAsync(d_table, h_stage, tab_bytes, hipMemcpyHostToDevice, st));
     SBGM_HIP(hipMemcpyAsync(d_state, state0, sizeof(SamplerState), hipMemcpyHostToDevice, st));
+    // Constrained EM / PC run: the levels its held pixels are re-noised to, std(t_i) and std(t_{i+1}) (0 after the last step) with std =
+    // marginal_prob_std in double at the table's fp32 times, as a table parallel to the step table (EDM Heun: EdmStep has sigma_next).
+    Hold hold{};
+    if (held) {
+        hold.known = held->known;
+        hold.mask = held->mask;
+        hold.z0 = heun ? a.noise : nullptr;
+        hold.seed = a.seed;
+    }
+    if (held && !heun) {
+        if (levels_rows < (size_t)N) {
+            if (d_levels) SBGM_HIP(hipFree(d_levels));
+            d_levels = nullptr;
+            levels_rows = std::max<size_t>(N, 4096);
+            SBGM_HIP(hipMalloc(reinterpret_cast<void**>(&d_levels), levels_rows * sizeof(HoldLevels)));
+        }
+        HoldLevels* lv = reinterpret_cast<HoldLevels*>(h_stage + tab_bytes + sizeof(SamplerState));
+        const StepScalars* rows = reinterpret_cast<const StepScalars*>(h_stage);
+        const double lsd = std::log((double)sig);
+        for (int i = 0; i < N; ++i) lv[i].cur = (float)std::max(std::sqrt(std::expm1(2.0 * (double)rows[i].t * lsd) / (2.0 * lsd)), 1e-5);
+        for (int i = 0; i < N; ++i) lv[i].next = i + 1 < N ? lv[i + 1].cur : 0.f;
+        SBGM_HIP(hipMemcpyAsync(d_levels, lv, sizeof(HoldLevels) * (size_t)N, hipMemcpyHostToDevice, st));
+        hold.levels = d_levels;
+    }
     SBGM_HIP(hipEventRecord(ev_stage, st));               // no host wait: the copies read pinned memory this handle owns
     stage_pending = true;
     const StepScalars* sde_tab = static_cast<const StepScalars*>(d_table);
     const EdmStep* edm_tab = static_cast<const EdmStep*>(d_table);
 
     if (run.begin()) return 1;
+    hold.nm = run.nm;
     // slabs: x (the network input), score, x_mean, and for EDM Heun the derivative d; EDM Heun keeps its state x / x_hat in x_mean
     float *xs = run.slab_at(0), *score = run.slab_at(1), *xmean = run.slab_at(2), *dheun = heun ? run.slab_at(3) : nullptr;
     float* t_dev = run.t_vec();
@@ -1133,7 +1164,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     size_t draw = 0;
     auto next_z = [&]() -> const float* { const float* p = z ? z + draw * n : nullptr; ++draw; return p; };
     const float x0_scale = heun ? reinterpret_cast<const EdmStep*>(h_stage)->sigma : std1;
-    if (sbgm_launch_init_noise(heun ? xmean : xs, x0_scale, next_z(), a.seed, d_state, 0, n, st, run.nm)) return 1;
+    if (sbgm_launch_init_noise(heun ? xmean : xs, x0_scale, next_z(), a.seed, d_state, 0, n, st, run.nm, hold)) return 1;
     if (heun) SBGM_HIP(hipMemcpyAsync(xs, xmean, n * 4, hipMemcpyDeviceToDevice, st));
     if (sbgm_launch_fill_t(t_dev, tab.t_first, BE, st)) return 1;
     const float snr_nn = (float)((double)a.snr * std::sqrt((double)per));     // snr * sqrt(prod(x.shape[1:])) (:202-203)
@@ -1148,18 +1179,18 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
             if (churn && sbgm_launch_edm_churn(xmean, xs, z_ptrs ? next_z() : nullptr, edm_tab, d_state, nullptr, 0, a.seed, n, st, run.nm))
                 return 1;
             if (evaluate(a.cfg_scale)) return 1;
-            if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, edm_tab, d_state, nullptr, t_dev, BE, n, st)) return 1;
+            if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, edm_tab, d_state, nullptr, t_dev, BE, n, st, hold)) return 1;
             if (last) return 0;
             if (evaluate(a.cfg_scale)) return 1;
-            return sbgm_launch_edm_heun(xmean, xs, dheun, score, edm_tab, d_state, nullptr, t_dev, BE, N, n, st);
+            return sbgm_launch_edm_heun(xmean, xs, dheun, score, edm_tab, d_state, nullptr, t_dev, BE, N, n, st, hold);
         }
         if (a.kind == SBGM_SAMPLER_PC) {
             if (evaluate(a.cfg_scale_corrector)) return 1;
-            if (sbgm_launch_langevin(xs, score, z_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, run.nm)) return 1;
+            if (sbgm_launch_langevin(xs, score, z_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, run.nm, hold)) return 1;
         }
         if (evaluate(a.cfg_scale)) return 1;
         return sbgm_launch_em_update(xs, xmean, score, z_ptrs ? next_z() : nullptr, sde_tab, d_state, nullptr, 0, t_dev, a.seed, B,
-                                     per, N, st, BE, run.nm);
+                                     per, N, st, BE, run.nm, hold);
     };
     // The run: N - tail steps (replays of the captured step, or eager launches), then `tail` eager last steps.  EM / PC: no tail,
     // the result is the x_mean slab, copied to `out`; EDM Heun: the tail is its Euler-only last step, which writes `out` itself.
@@ -1169,6 +1200,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         StepGraphKey key{};
         key.churn = churn; key.domain_w = a.domain_w; key.origins = a.tile_origins; key.table = d_table;
         key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn;
+        key.known = hold.known; key.known_mask = hold.mask; key.levels = hold.levels;
         rc = run.capture(key, [&] { return step(false, false); });
         for (int i = 0; i < N - tail && rc == 0; ++i)
             if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
@@ -1374,16 +1406,39 @@ int sbgm_sampler_run(sbgm_model* m, const sbgm_sampler_args* a, void* stream) {
     return m->sampler(*a, (hipStream_t)stream);
 }
 
-int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
-                         float s_tmin, float s_tmax, float s_noise, void* stream) {
-    SBGM_CHECK(a, "sampler_run_edm: null args");
+static int edm_args_check(const sbgm_sampler_args* a, float rho, float s_churn, float s_noise, float sigma_min, float sigma_max) {
     SBGM_CHECK(a->kind == SBGM_SAMPLER_EDM_HEUN, "sampler_run_edm: kind %d is not SBGM_SAMPLER_EDM_HEUN", a->kind);
     SBGM_CHECK(!a->bn_train, "sampler_run_edm: serves eval-mode BatchNorm only (bn_train must be 0)");
     SBGM_CHECK(rho > 0.f && s_churn >= 0.f && s_noise >= 0.f, "sampler_run_edm: need rho > 0, s_churn >= 0, s_noise >= 0");
     SBGM_CHECK(!(sigma_min > 0.f && sigma_max > 0.f && sigma_min >= sigma_max), "sampler_run_edm: sigma_min %g >= sigma_max %g",
                sigma_min, sigma_max);
+    return 0;
+}
+
+int sbgm_sampler_run_edm(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
+                         float s_tmin, float s_tmax, float s_noise, void* stream) {
+    SBGM_CHECK(a, "sampler_run_edm: null args");
+    if (edm_args_check(a, rho, s_churn, s_noise, sigma_min, sigma_max)) return 1;
     const sbgm_model::EdmArgs e{sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise};
     return m->sampler(*a, (hipStream_t)stream, &e);
+}
+
+// The two drivers above with a constraint (constrained sampling): the same sbgm_model::sampler, the held kernels.
+int sbgm_sampler_run_held(sbgm_model* m, const sbgm_sampler_args* a, const float* known, const float* known_mask, void* stream) {
+    SBGM_CHECK(a, "sampler_run_held: null args");
+    SBGM_CHECK(known && known_mask, "sampler_run_held: known and known_mask are required");
+    const sbgm_model::HeldArgs h{known, known_mask};
+    return m->sampler(*a, (hipStream_t)stream, nullptr, &h);
+}
+
+int sbgm_sampler_run_edm_held(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
+                              float s_tmin, float s_tmax, float s_noise, const float* known, const float* known_mask, void* stream) {
+    SBGM_CHECK(a, "sampler_run_edm_held: null args");
+    SBGM_CHECK(known && known_mask, "sampler_run_edm_held: known and known_mask are required");
+    if (edm_args_check(a, rho, s_churn, s_noise, sigma_min, sigma_max)) return 1;
+    const sbgm_model::EdmArgs e{sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise};
+    const sbgm_model::HeldArgs h{known, known_mask};
+    return m->sampler(*a, (hipStream_t)stream, &e, &h);
 }
 
 int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, double t1, double rtol, double atol, int per_sample,

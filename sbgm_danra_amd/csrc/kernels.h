@@ -194,19 +194,39 @@ struct NoiseMap {
     int tile_h, tile_w4;  // tile rows, tile width / 4
     int dom_w4;           // ceil(domain width / 4)
 };
+// Constrained sampling: pixels with mask > 0 are held at known + level * z after each state update, in the update
+// kernel's own epilogue.  known == null (the default) is the unconstrained kernel.
+struct HoldLevels {        // noise levels a held pixel is re-noised to in an SDE step: one row per step, parallel to the step table
+    float cur;             // std(t_i): the Langevin corrector's output
+    float next;            // std(t_{i+1}), 0 after the last step: the predictor's output
+};
+struct Hold {
+    const float* known;        // [B][H][W] model-space values (anything, NaN included, where mask == 0)
+    const float* mask;         // [B][H][W], clamped to [0,1] in the kernel
+    const HoldLevels* levels;  // device table indexed by the step counter (with a state), else `lv` by value
+    HoldLevels lv;
+    // EDM Heun only: its held pixels carry the run's draw 0, read from z0 or (null) recomputed from (seed, offset 0, nm)
+    const float* z0;
+    unsigned long long seed;   // used without a state (the state's seed otherwise)
+    NoiseMap nm;
+};
 int sbgm_launch_fill_t(float* t, float value, int B, hipStream_t st);
 // `state` != null: scalars / RNG offset come from device memory (graph-replayable) and the state is advanced after
 // the update; `state` == null: explicit by-value scalars and draw index.
 int sbgm_launch_init_noise(float* x, float scale, const float* z, unsigned long long seed, SamplerState* state,
-                           unsigned long long draw_index, size_t n, hipStream_t st, NoiseMap nm = NoiseMap{});
+                           unsigned long long draw_index, size_t n, hipStream_t st, NoiseMap nm = NoiseMap{},
+                           const Hold& hold = Hold{});       // held: x = scale z + m known
 int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const float* z, const StepScalars* table,
                           SamplerState* state, const StepScalars* sc_val, unsigned long long draw_index, float* t_dev,
                           unsigned long long seed, int B, size_t per_sample, int n_steps, hipStream_t st,
                           int t_entries = 0,    // entries of t_dev to refresh (0 -> B; 2B for the batched guidance pass)
-                          NoiseMap nm = NoiseMap{});
+                          NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{});
 int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr_noise_norm, double* sumsq_ws,
                          SamplerState* state, unsigned long long draw_index, unsigned long long seed, int B,
-                         size_t per_sample, hipStream_t st, NoiseMap nm = NoiseMap{});
+                         size_t per_sample, hipStream_t st, NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{});
+// x = hold(x, known + level z, m), x_mean (may be null) = hold(x_mean, known, m); z null: the Philox draw (seed, draw_index)
+int sbgm_launch_hold_known(float* x, float* x_mean, const float* z, float level, unsigned long long seed, unsigned long long draw_index,
+                           size_t n, hipStream_t st, const Hold& hold);
 int sbgm_launch_cfg_combine(float* out, const float* s_cond, const float* s_uncond, float scale, size_t n, hipStream_t st);
 
 // EDM Heun sampler (Karras et al. 2022, Alg. 2) on the probability-flow ODE of the VE SDE: one row per step i of the
@@ -225,11 +245,13 @@ int sbgm_launch_edm_churn(float* x, float* x_copy, const float* z, const EdmStep
                           NoiseMap nm = NoiseMap{});
 // euler: d = -sigma_hat * score ; x_next = x_hat + (sigma_next - sigma_hat) * d ; t_dev[0 .. t_entries) = t_next
 int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, const EdmStep* table,
-                          const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st);
+                          const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st,
+                          const Hold& hold = Hold{});
 // heun: x = x_hat + (sigma_next - sigma_hat) * 0.5 (d - sigma_next * score), in place over x_hat (x_copy may be null);
 // with a state: t_dev = t_hat of the next step, then the step counter / RNG offset advance
 int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* score, const EdmStep* table, SamplerState* state,
-                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st);
+                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st,
+                         const Hold& hold = Hold{});
 
 // ---- ode.hip (rk45_sampler: Dormand-Prince 5(4) with scipy's step controller, on the device) -----------------------------------
 enum { SBGM_ODE_RUNNING = 0, SBGM_ODE_FINISHED = 1, SBGM_ODE_TOO_SMALL_STEP = 2, SBGM_ODE_NONFINITE = 3, SBGM_ODE_MAX_STEPS = 4 };

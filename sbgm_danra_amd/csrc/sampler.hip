@@ -24,31 +24,59 @@ __device__ __forceinline__ unsigned long long noise_index(const NoiseMap& m, siz
     return ((unsigned long long)(m.origins[2 * b] + y)) * m.dom_w4 + (unsigned long long)(m.origins[2 * b + 1] >> 2) + x4;
 }
 
+// Constrained sampling: hold(v, target, m) is a select with a soft edge.  m <= 0 keeps v and m >= 1 takes target, both
+// bit-exactly (the other operand is never combined arithmetically, so `known` may hold anything where the mask is 0); in between
+// (1-m) v + m target.  The mask is clamped to [0,1] here; a NaN mask counts as 0.
+__device__ __forceinline__ f32x4 clamp_mask(f32x4 m) {
+    for (int k = 0; k < 4; ++k) m[k] = fminf(fmaxf(m[k], 0.f), 1.f);
+    return m;
+}
+__device__ __forceinline__ f32x4 hold4(f32x4 v, f32x4 target, f32x4 m) {
+    f32x4 r;
+    for (int k = 0; k < 4; ++k) r[k] = m[k] <= 0.f ? v[k] : m[k] >= 1.f ? target[k] : (1.f - m[k]) * v[k] + m[k] * target[k];
+    return r;
+}
+__device__ __forceinline__ f32x4 load_mask(const Hold& h, size_t i) { return clamp_mask(reinterpret_cast<const f32x4*>(h.mask)[i]); }
+__device__ __forceinline__ f32x4 load_known(const Hold& h, size_t i) { return reinterpret_cast<const f32x4*>(h.known)[i]; }
+// draw 0 of the run (the initial state's noise) at quad i: the injected one, or recomputed from (seed, offset 0, counter)
+__device__ __forceinline__ f32x4 draw0(const Hold& h, unsigned long long seed, size_t i) {
+    return h.z0 ? reinterpret_cast<const f32x4*>(h.z0)[i] : philox_normal4(seed, 0ull, noise_index(h.nm, i));
+}
+
 __global__ void fill_kernel(float* t, float v, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) t[i] = v;
 }
 
-// x = scale * N(0,1)   (sampler start: randn * marginal_prob_std(1), score_sampling.py:94-95, :168)
+// x = scale * N(0,1)   (sampler start: randn * marginal_prob_std(1), score_sampling.py:94-95, :168);  HELD: + m * known where m > 0
+template <bool HELD>
 __global__ __launch_bounds__(256) void init_noise_kernel(float* __restrict__ x, float scale, const float* __restrict__ z,
                                                          unsigned long long seed, const SamplerState* __restrict__ state,
-                                                         unsigned long long off_val, size_t n4, NoiseMap nm) {
+                                                         unsigned long long off_val, size_t n4, NoiseMap nm, Hold hold) {
     const unsigned long long off = state ? state->rng_offset : off_val;
     if (state) seed = state->seed;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
-        reinterpret_cast<f32x4*>(x)[i] = n * scale;
+        f32x4 v = n * scale;
+        if (HELD) {
+            const f32x4 m = load_mask(hold, i), kn = load_known(hold, i);
+            for (int k = 0; k < 4; ++k) v[k] = m[k] <= 0.f ? v[k] : v[k] + m[k] * kn[k];
+        }
+        reinterpret_cast<f32x4*>(x)[i] = v;
     }
 }
 
-// x_mean = x + g^2 dt * score ;  x = x_mean + noise_coef * N(0,1)
+// x_mean = x + g^2 dt * score ;  x = x_mean + noise_coef * N(0,1);  HELD: x_mean = hold(., known), x = hold(., known + std(t_next) z)
+// with the step's own draw z (the unheld branch discards it on a held pixel, so it is a fresh draw there)
+template <bool HELD>
 __global__ __launch_bounds__(256) void em_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
                                                         const float* __restrict__ score, const float* __restrict__ z,
                                                         const StepScalars* __restrict__ table,
                                                         const SamplerState* __restrict__ state, StepScalars sc_val,
                                                         unsigned long long off_val, unsigned long long seed, size_t n4,
-                                                        NoiseMap nm) {
+                                                        NoiseMap nm, Hold hold) {
     const StepScalars sc = state ? table[state->step] : sc_val;
+    const float s_next = !HELD ? 0.f : (state ? hold.levels[state->step] : hold.lv).next;
     const unsigned long long off = state ? state->rng_offset : off_val;
     if (state) seed = state->seed;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
@@ -56,8 +84,14 @@ __global__ __launch_bounds__(256) void em_update_kernel(float* __restrict__ x, f
         const f32x4 sv = reinterpret_cast<const f32x4*>(score)[i];
         const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
         const f32x4 mean = xv + (sc.g2 * sv) * sc.dt;   // association of score_sampling.py:124/:224
-        reinterpret_cast<f32x4*>(x_mean)[i] = mean;
-        reinterpret_cast<f32x4*>(x)[i] = mean + sc.noise * n;
+        if (HELD) {
+            const f32x4 m = load_mask(hold, i), kn = load_known(hold, i);
+            reinterpret_cast<f32x4*>(x_mean)[i] = hold4(mean, kn, m);
+            reinterpret_cast<f32x4*>(x)[i] = hold4(mean + sc.noise * n, kn + s_next * n, m);
+        } else {
+            reinterpret_cast<f32x4*>(x_mean)[i] = mean;
+            reinterpret_cast<f32x4*>(x)[i] = mean + sc.noise * n;
+        }
     }
 }
 
@@ -98,12 +132,15 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ sc
 // Tile mode (nm.origins set: the samples are tiles of one domain): the step size of a tile uses that tile's OWN score norm
 // instead of the batch mean, so a tile's trajectory does not depend on which other tiles share its batch or its GPU
 // (the reference has no tiler, its batch-mean rule :201 applies to batches of independent samples).
+// HELD: x = hold(., known + std(t_i) z); the score norm stays over the whole sample.
+template <bool HELD>
 __global__ __launch_bounds__(256) void langevin_kernel(float* __restrict__ x, const float* __restrict__ score,
                                                        const float* __restrict__ z, float snr_noise_norm,
                                                        const double* __restrict__ sumsq,
                                                        const SamplerState* __restrict__ state,
                                                        unsigned long long off_val, unsigned long long seed, int B,
-                                                       size_t n4, NoiseMap nm) {
+                                                       size_t n4, NoiseMap nm, Hold hold) {
+    const float s_cur = !HELD ? 0.f : (state ? hold.levels[state->step] : hold.lv).cur;
     float gn = 0.f;
     for (int b = 0; b < B; ++b) gn += (float)sqrt(sumsq[b]);
     gn /= (float)B;
@@ -124,7 +161,8 @@ __global__ __launch_bounds__(256) void langevin_kernel(float* __restrict__ x, co
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
         const f32x4 sv = reinterpret_cast<const f32x4*>(score)[i];
         const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
-        reinterpret_cast<f32x4*>(x)[i] = xv + eps * sv + nz * n;
+        const f32x4 v = xv + eps * sv + nz * n;
+        reinterpret_cast<f32x4*>(x)[i] = HELD ? hold4(v, load_known(hold, i) + s_cur * n, load_mask(hold, i)) : v;
     }
 }
 
@@ -157,11 +195,16 @@ __global__ __launch_bounds__(256) void edm_churn_kernel(float* __restrict__ x, f
 
 // Euler predictor: d = dx/dsigma = -sigma_hat * score ; x' = x_hat + (sigma_next - sigma_hat) * d.  The time vector of the
 // second evaluation (t_next) is published by the same launch: nothing reads it until the next kernel.
+// HELD (here and in the Heun corrector): a held pixel follows the probability-flow trajectory of a point mass, known + sigma z0 with
+// the run's own draw 0, so the output is hold(., known + sigma_next z0): deterministic, and `known` itself after the last step.
+template <bool HELD>
 __global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict__ x_hat, const float* __restrict__ score,
                                                         float* __restrict__ d, float* __restrict__ x_next,
                                                         const EdmStep* __restrict__ table, const SamplerState* __restrict__ state,
-                                                        EdmStep sc_val, float* __restrict__ t_dev, int t_entries, size_t n4) {
+                                                        EdmStep sc_val, float* __restrict__ t_dev, int t_entries, size_t n4,
+                                                        Hold hold) {
     const EdmStep sc = state ? table[state->step] : sc_val;
+    const unsigned long long seed = state ? state->seed : hold.seed;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
     if (t_dev)
         for (size_t j = gid; j < (size_t)t_entries; j += stride) t_dev[j] = sc.t_next;
@@ -169,18 +212,22 @@ __global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict_
     for (size_t i = gid; i < n4; i += stride) {
         const f32x4 dv = (-sc.sigma_hat) * reinterpret_cast<const f32x4*>(score)[i];
         reinterpret_cast<f32x4*>(d)[i] = dv;
-        reinterpret_cast<f32x4*>(x_next)[i] = reinterpret_cast<const f32x4*>(x_hat)[i] + h * dv;
+        const f32x4 v = reinterpret_cast<const f32x4*>(x_hat)[i] + h * dv;
+        reinterpret_cast<f32x4*>(x_next)[i] =
+            HELD ? hold4(v, load_known(hold, i) + sc.sigma_next * draw0(hold, seed, i), load_mask(hold, i)) : v;
     }
 }
 
 // Heun corrector: x = x_hat + (sigma_next - sigma_hat) * 0.5 (d + d'), d' = -sigma_next * score(x', sigma_next); in place over
 // x_hat, mirrored into the network-input slab.  Publishes the first evaluation time of the next step (the advance follows).
+template <bool HELD>
 __global__ __launch_bounds__(256) void edm_heun_kernel(float* __restrict__ x, float* __restrict__ x_copy,
                                                        const float* __restrict__ d, const float* __restrict__ score,
                                                        const EdmStep* __restrict__ table, const SamplerState* __restrict__ state,
                                                        EdmStep sc_val, float* __restrict__ t_dev, int t_entries, int n_steps,
-                                                       size_t n4) {
+                                                       size_t n4, Hold hold) {
     const unsigned long long s = state ? state->step : 0ull;
+    const unsigned long long seed = state ? state->seed : hold.seed;
     const EdmStep sc = state ? table[s] : sc_val;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
     if (state && t_dev) {
@@ -191,10 +238,35 @@ __global__ __launch_bounds__(256) void edm_heun_kernel(float* __restrict__ x, fl
     const float h = sc.sigma_next - sc.sigma_hat;
     for (size_t i = gid; i < n4; i += stride) {
         const f32x4 d2 = (-sc.sigma_next) * reinterpret_cast<const f32x4*>(score)[i];
-        const f32x4 v = reinterpret_cast<const f32x4*>(x)[i] + (h * 0.5f) * (reinterpret_cast<const f32x4*>(d)[i] + d2);
+        f32x4 v = reinterpret_cast<const f32x4*>(x)[i] + (h * 0.5f) * (reinterpret_cast<const f32x4*>(d)[i] + d2);
+        if (HELD) v = hold4(v, load_known(hold, i) + sc.sigma_next * draw0(hold, seed, i), load_mask(hold, i));
         reinterpret_cast<f32x4*>(x)[i] = v;
         if (x_copy) reinterpret_cast<f32x4*>(x_copy)[i] = v;
     }
+}
+
+// The hold as an op of its own, for loops that run the network themselves: x = hold(x, known + level z, m) and, when given,
+// x_mean = hold(x_mean, known, m); z null -> the Philox draw (seed, draw_index) the preceding step op consumed.
+__global__ __launch_bounds__(256) void hold_known_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ z,
+                                                         float level, unsigned long long seed, unsigned long long off, size_t n4,
+                                                         Hold hold) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, i);
+        const f32x4 m = load_mask(hold, i), kn = load_known(hold, i);
+        reinterpret_cast<f32x4*>(x)[i] = hold4(reinterpret_cast<const f32x4*>(x)[i], kn + level * n, m);
+        if (x_mean) reinterpret_cast<f32x4*>(x_mean)[i] = hold4(reinterpret_cast<const f32x4*>(x_mean)[i], kn, m);
+    }
+}
+
+// the held or the plain instantiation of a kernel template, by whether the call carries a constraint
+#define SBGM_LAUNCH_HELD(kernel, held, grid, st, ...)                                                   \
+    do {                                                                                                \
+        if (held) hipLaunchKernelGGL((kernel<true>), grid, dim3(256), 0, st, __VA_ARGS__);              \
+        else hipLaunchKernelGGL((kernel<false>), grid, dim3(256), 0, st, __VA_ARGS__);                  \
+    } while (0)
+inline int check_hold(const Hold& h, const char* who) {
+    SBGM_CHECK((h.known == nullptr) == (h.mask == nullptr), "%s: known and known_mask must be given together", who);
+    return 0;
 }
 
 inline int stream_blocks(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 2048); }
@@ -208,10 +280,11 @@ int sbgm_launch_fill_t(float* t, float value, int B, hipStream_t st) {
 }
 
 int sbgm_launch_init_noise(float* x, float scale, const float* z, unsigned long long seed, SamplerState* state,
-                           unsigned long long draw_index, size_t n, hipStream_t st, NoiseMap nm) {
+                           unsigned long long draw_index, size_t n, hipStream_t st, NoiseMap nm, const Hold& hold) {
     SBGM_CHECK(n % 4 == 0, "init_noise: element count must be a multiple of 4");
-    hipLaunchKernelGGL(init_noise_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x, scale, z, seed, state, draw_index,
-                       n / 4, nm);
+    if (check_hold(hold, "init_noise")) return 1;
+    SBGM_LAUNCH_HELD(init_noise_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x, scale, z, seed, state, draw_index,
+                     n / 4, nm, hold);
     SBGM_LAUNCH_CHECK();
     if (state) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0);
@@ -223,15 +296,17 @@ int sbgm_launch_init_noise(float* x, float scale, const float* z, unsigned long 
 int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const float* z, const StepScalars* table,
                           SamplerState* state, const StepScalars* sc_val, unsigned long long draw_index, float* t_dev,
                           unsigned long long seed, int B, size_t per_sample, int n_steps, hipStream_t st, int t_entries,
-                          NoiseMap nm) {
+                          NoiseMap nm, const Hold& hold) {
     const size_t n = (size_t)B * per_sample;
     if (t_entries <= 0) t_entries = B;
     SBGM_CHECK(n % 4 == 0, "em_update: element count must be a multiple of 4");
     SBGM_CHECK(t_entries <= 1024, "em_update: %d time entries > 1024", t_entries);
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "em_update: need a device table or explicit scalars");
+    SBGM_CHECK(!(hold.known && state && !hold.levels), "em_update: a held run with a device state needs the hold-level table");
+    if (check_hold(hold, "em_update")) return 1;
     const StepScalars v = sc_val ? *sc_val : StepScalars{};
-    hipLaunchKernelGGL(em_update_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x, x_mean, score, z, table, state, v,
-                       draw_index, seed, n / 4, nm);
+    SBGM_LAUNCH_HELD(em_update_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x, x_mean, score, z, table, state, v,
+                     draw_index, seed, n / 4, nm, hold);
     SBGM_LAUNCH_CHECK();
     if (state) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1024), 0, st, state, table, t_dev, t_entries, 1, n_steps);
@@ -242,15 +317,17 @@ int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const flo
 
 int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr_noise_norm, double* sumsq_ws,
                          SamplerState* state, unsigned long long draw_index, unsigned long long seed, int B,
-                         size_t per_sample, hipStream_t st, NoiseMap nm) {
+                         size_t per_sample, hipStream_t st, NoiseMap nm, const Hold& hold) {
     SBGM_CHECK(per_sample % 4 == 0, "langevin: per-sample element count must be a multiple of 4");
+    SBGM_CHECK(!(hold.known && state && !hold.levels), "langevin: a held run with a device state needs the hold-level table");
+    if (check_hold(hold, "langevin")) return 1;
     { if (sbgm_zero_async(sumsq_ws, sizeof(double) * B, st)) return 1; }
     const int bx = (int)std::min<size_t>((per_sample / 4 + 255) / 256, B >= 64 ? 4 : 16);
     hipLaunchKernelGGL(sumsq_kernel, dim3(bx, B), dim3(256), 0, st, score, sumsq_ws, per_sample / 4);
     SBGM_LAUNCH_CHECK();
     const size_t n4 = (size_t)B * per_sample / 4;
-    hipLaunchKernelGGL(langevin_kernel, dim3(stream_blocks(n4)), dim3(256), 0, st, x, score, z, snr_noise_norm, sumsq_ws,
-                       state, draw_index, seed, B, n4, nm);
+    SBGM_LAUNCH_HELD(langevin_kernel, hold.known != nullptr, dim3(stream_blocks(n4)), st, x, score, z, snr_noise_norm, sumsq_ws,
+                     state, draw_index, seed, B, n4, nm, hold);
     SBGM_LAUNCH_CHECK();
     if (state) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0);
@@ -272,28 +349,41 @@ int sbgm_launch_edm_churn(float* x, float* x_copy, const float* z, const EdmStep
 }
 
 int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, const EdmStep* table,
-                          const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st) {
+                          const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st,
+                          const Hold& hold) {
     SBGM_CHECK(n % 4 == 0, "edm_euler: element count must be a multiple of 4");
+    if (check_hold(hold, "edm_euler")) return 1;
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_euler: need a device table or explicit scalars");
     const EdmStep v = sc_val ? *sc_val : EdmStep{};
-    hipLaunchKernelGGL(edm_euler_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x_hat, score, d, x_next, table, state, v,
-                       t_dev, t_dev ? t_entries : 0, n / 4);
+    SBGM_LAUNCH_HELD(edm_euler_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x_hat, score, d, x_next, table, state, v,
+                     t_dev, t_dev ? t_entries : 0, n / 4, hold);
     SBGM_LAUNCH_CHECK();
     return 0;
 }
 
 int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* score, const EdmStep* table, SamplerState* state,
-                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st) {
+                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st, const Hold& hold) {
     SBGM_CHECK(n % 4 == 0, "edm_heun: element count must be a multiple of 4");
+    if (check_hold(hold, "edm_heun")) return 1;
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_heun: need a device table or explicit scalars");
     const EdmStep v = sc_val ? *sc_val : EdmStep{};
-    hipLaunchKernelGGL(edm_heun_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x, x_copy, d, score, table, state, v, t_dev,
-                       t_dev ? t_entries : 0, n_steps, n / 4);
+    SBGM_LAUNCH_HELD(edm_heun_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x, x_copy, d, score, table, state, v, t_dev,
+                     t_dev ? t_entries : 0, n_steps, n / 4, hold);
     SBGM_LAUNCH_CHECK();
     if (state) {                     // step counter and RNG offset: the EM mechanism, without its StepScalars time publish
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 1, n_steps);
         SBGM_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+int sbgm_launch_hold_known(float* x, float* x_mean, const float* z, float level, unsigned long long seed, unsigned long long draw_index,
+                           size_t n, hipStream_t st, const Hold& hold) {
+    SBGM_CHECK(n % 4 == 0, "hold_known: element count must be a multiple of 4");
+    SBGM_CHECK(x && hold.known && hold.mask, "hold_known: x, known and known_mask are required");
+    hipLaunchKernelGGL(hold_known_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x, x_mean, z, level, seed, draw_index, n / 4,
+                       hold);
+    SBGM_LAUNCH_CHECK();
     return 0;
 }
 

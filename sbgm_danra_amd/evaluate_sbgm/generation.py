@@ -22,6 +22,27 @@ from ..utils import extract_samples, get_model_string
 logger = logging.getLogger(__name__)
 
 
+def constraint_mask(cfg, hw):
+    """The [H,W] float32 mask of the optional top-level `constraint:` section, or None when it is absent or `enabled` is false.
+    `mask_file`: an .npy file of shape [H,W] (values in [0,1]); else `station_fraction` (default 0.01) with `seed` (default 0): a
+    seeded Bernoulli mask, the same for every sample of a run.  The batch's true high-resolution field is held where it is set."""
+    sec = (cfg.get("constraint") if hasattr(cfg, "get") else None) or {}
+    if not sec.get("enabled", False):
+        return None
+    if cfg["sampler"].get("sampler_type") == "rk45_sampler":
+        raise ValueError("constraint.enabled: rk45_sampler does not take known pixels (use pc_sampler or edm_heun_sampler)")
+    H, W = int(hw[0]), int(hw[1])
+    if sec.get("mask_file"):
+        mask = np.load(sec["mask_file"]).astype(np.float32)
+        if mask.shape != (H, W):
+            raise ValueError(f"constraint.mask_file holds {mask.shape}, the samples are {(H, W)}")
+        return mask
+    frac = float(sec.get("station_fraction", 0.01))
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError(f"constraint.station_fraction={frac} must be in [0, 1]")
+    return (np.random.default_rng(int(sec.get("seed", 0))).random((H, W)) < frac).astype(np.float32)
+
+
 def maybe_inverse_transform(k, arr, back_transforms):
     """reference generation.py:26-35"""
     if back_transforms and k in back_transforms:
@@ -37,17 +58,24 @@ class SampleGenerator:
         self.output_dir = os.path.join(cfg["paths"]["sample_dir"], "generation", self.model_name_str)
         self.sample_path = os.path.join(self.output_dir, "generated_samples")
         os.makedirs(self.sample_path, exist_ok=True)
+        hw = cfg["highres"]["data_size"]
+        self.constraint = constraint_mask(cfg, (hw[0], hw[0]))       # raises here, at start, on a sampler that cannot hold pixels
 
-    def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond):
+    def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond, known=None):
         """the sampler output as [B,H,W] still on the device (what _run_sampler returns after .cpu()).  pc_sampler, as in the
         reference, unless cfg.sampler.sampler_type is "edm_heun_sampler": then n_timesteps is its Heun step count N (2N-1
         network evaluations; 18-64 is the intended range) and the optional `edm:` section sets the sigma ladder; or "rk45_sampler":
-        the adaptive ODE solver, which ignores n_timesteps and reads its tolerances from the optional `ode:` section."""
+        the adaptive ODE solver, which ignores n_timesteps and reads its tolerances from the optional `ode:` section.
+        With a `constraint:` section, `known` (the batch's true field, model space) is held on the section's mask."""
+        held = {}
+        if self.constraint is not None and known is not None:
+            held = {"known": known.reshape(-1, 1, *known.shape[-2:]).expand(batch_size, -1, -1, -1),
+                    "known_mask": torch.from_numpy(self.constraint)}
         if self.cfg["sampler"].get("sampler_type") == "edm_heun_sampler":
             gen = edm_heun_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                                    batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,
                                    img_size=self.cfg["highres"]["data_size"][0], y=y, cond_img=cond_img, lsm_cond=lsm_cond,
-                                   topo_cond=topo_cond, **edm_sampler_kwargs(self.cfg))
+                                   topo_cond=topo_cond, **edm_sampler_kwargs(self.cfg), **held)
         elif self.cfg["sampler"].get("sampler_type") == "rk45_sampler":
             gen = rk45_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                                batch_size=batch_size, device=self.device, img_size=self.cfg["highres"]["data_size"][0], y=y,
@@ -56,7 +84,7 @@ class SampleGenerator:
             gen = pc_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                              batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,
                              img_size=self.cfg["highres"]["data_size"][0], y=y, cond_img=cond_img, lsm_cond=lsm_cond,
-                             topo_cond=topo_cond)
+                             topo_cond=topo_cond, **held)
         gen = gen.squeeze().detach()
         if gen.ndim == 4:
             gen = gen.squeeze(1)
@@ -86,12 +114,13 @@ class SampleGenerator:
         return x, generated, cond_images
 
     def _generate(self, x, seasons, cond, lsm, topo, suffix, batch=None):
-        gen = self._sample_device(x.shape[0] if batch is None else batch, seasons, cond, lsm, topo)
+        gen = self._sample_device(x.shape[0] if batch is None else batch, seasons, cond, lsm, topo, known=x)
         cond_out = cond
         if self.cfg["evaluation"].get("transform_back", False):
             x, gen, cond_out = self._apply_backtransforms(x, gen, cond, seasons)
         gen = gen.cpu()
-        self._save_npz({"gen_samples": gen, "eval_samples": x, "lsm_samples": lsm, "seasons": seasons}, suffix)
+        self._save_npz({"gen_samples": gen, "eval_samples": x, "lsm_samples": lsm, "seasons": seasons,
+                        "constraint_mask": self.constraint}, suffix)
         if cond_out is not None and isinstance(cond_out, list):
             for i, k in enumerate(self.cfg["lowres"]["condition_variables"] or []):
                 self._save_npz({f"cond_samples_{k}": torch.stack([im[i] for im in cond_out])}, suffix)

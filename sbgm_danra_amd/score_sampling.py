@@ -13,6 +13,10 @@ reference's RNG order (init, then per step [corrector,] predictor) for parity ru
 Deviation kept explicit: the reference's Euler-Maruyama sampler ignores `img_size` and always starts from
 32x32 (score_sampling.py:94); here `img_size` is honoured (pass 32 to reproduce the reference literally).
 
+Constrained sampling (imputation, Song et al. 2021 App. I.2): `Euler_Maruyama_sampler`, `pc_sampler` and
+`edm_heun_sampler` take keyword-only `known` / `known_mask` and hold the masked pixels at `known`, re-noised after every state update to
+the level the state is at, in the epilogue of the update kernels; `sde_hold_levels` is the host definition of those levels.
+
 Beyond the reference: `edm_heun_sampler`, a deterministic few-step Heun solver of the probability-flow ODE on the Karras
 sigma ladder (Karras et al. 2022, Alg. 2) for the same VE-trained network; `edm_heun_schedule` is its one host definition.
 `rk45_sampler`, the adaptive probability-flow ODE solver on the device (Dormand-Prince 5(4) with scipy's RK45 step controller):
@@ -101,8 +105,51 @@ def _counts(kind, num_steps, churn=False):
     return per_step, 1 + int(num_steps) * per_step
 
 
+def _prep_known(known, known_mask, batch_size, hw, device, who):
+    """(known, known_mask) as contiguous fp32 [B,1,H,W] device tensors, or (None, None).  known: [B,1,H,W] or [B,H,W]; known_mask also
+    [H,W] or [1,1,H,W] (one mask for the whole batch).  Shapes are checked, values are not (no device sync): the kernels clamp the mask."""
+    if known is None and known_mask is None:
+        return None, None
+    if known is None or known_mask is None:
+        raise ValueError(f"{who}: known and known_mask must be given together")
+    B, full = int(batch_size), (int(batch_size), 1, int(hw), int(hw))
+    dev = torch.device(device) if not isinstance(device, torch.device) else device
+
+    def view_of(t, name, shared):                          # the shape to view `t` as before it is expanded over the batch
+        ok = {full: full, (B, hw, hw): full}
+        if shared:
+            ok.update({(hw, hw): (1, 1, hw, hw), (1, 1, hw, hw): (1, 1, hw, hw)})
+        if tuple(t.shape) not in ok:
+            raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected one of {sorted(ok, key=len)}")
+        return ok[tuple(t.shape)]
+    known, known_mask = torch.as_tensor(known), torch.as_tensor(known_mask)
+    views = view_of(known, "known", False), view_of(known_mask, "known_mask", True)        # both checked before anything moves
+    return tuple(N.f32c(t.to(dev).reshape(v).expand(full)) for t, v in zip((known, known_mask), views))
+
+
+def _held_start(x, known, mask):
+    """x0 = scale z0 + m known of a constrained run (the native loop's init kernel), for the Python loops"""
+    m = mask.clamp(0.0, 1.0)
+    return torch.where(m > 0, x + m * known, x)
+
+
+def sde_hold_levels(kind, num_steps, sigma_sde=25.0, eps=1e-3):
+    """Noise levels a constrained Euler-Maruyama (`kind="em"`) or predictor-corrector (`kind="pc"`) run re-noises its held pixels to,
+    as the engine builds them beside its step table: `t` [N] the table's fp32 times (torch.linspace in fp32 for EM, np.linspace in
+    float64 rounded to fp32 for PC), `s_cur` [N] = fp32(marginal_prob_std(t_i)) evaluated in float64 (floored at 1e-5 like the model's) --
+    the corrector's level -- and `s_next` [N] = s_cur shifted by one step with a final 0 -- the predictor's level."""
+    if kind in ("em", N.SAMPLER_EM):
+        t = torch.linspace(1.0, eps, int(num_steps)).numpy().astype(np.float64)
+    elif kind in ("pc", N.SAMPLER_PC):
+        t = np.linspace(1.0, eps, int(num_steps)).astype(np.float32).astype(np.float64)
+    else:
+        raise ValueError(f"sde_hold_levels: kind={kind!r} must be 'em' or 'pc'")
+    s_cur = np.maximum(_ve_std(t, sigma_sde), 1e-5).astype(np.float32)
+    return {"t": t, "s_cur": s_cur, "s_next": np.append(s_cur[1:], np.float32(0.0))}
+
+
 def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw, y, cond_img, lsm_cond, topo_cond,
-                noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm_args=None):
+                noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm_args=None, held=(None, None)):
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if dev.type != "cuda":
         raise N.NativeError(f"the native samplers run on a ROCm device, got device={device!r}")
@@ -127,10 +174,17 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
             raise ValueError("tile_origins must be a contiguous int32 [batch, 2] device tensor of (y0, x0)")
         if noise is not None:
             raise ValueError("tile_origins keys the in-kernel noise; it cannot be combined with injected noise")
+    known, mask = held
     if edm_args is not None:
-        N.check(eng.lib.sbgm_sampler_run_edm(eng.h, C.byref(a), *edm_args, N.stream()))
+        if known is not None:
+            N.check(eng.lib.sbgm_sampler_run_edm_held(eng.h, C.byref(a), *edm_args, known.data_ptr(), mask.data_ptr(), N.stream()))
+        else:
+            N.check(eng.lib.sbgm_sampler_run_edm(eng.h, C.byref(a), *edm_args, N.stream()))
         return out
-    N.check(eng.lib.sbgm_sampler_run(eng.h, C.byref(a), N.stream()))
+    if known is not None:
+        N.check(eng.lib.sbgm_sampler_run_held(eng.h, C.byref(a), known.data_ptr(), mask.data_ptr(), N.stream()))
+    else:
+        N.check(eng.lib.sbgm_sampler_run(eng.h, C.byref(a), N.stream()))
     if score_model.training:
         eng.download_bn_stats(score_model, n_forwards=int(num_steps) * _counts(kind, num_steps)[0])
     return out
@@ -156,12 +210,14 @@ def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scal
 
 def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=500, device="cuda",
                            eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
-                           noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0):
-    """Euler-Maruyama reverse-SDE sampler (reference score_sampling.py:63-127).  Returns the last `mean_x`."""
+                           noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None):
+    """Euler-Maruyama reverse-SDE sampler (reference score_sampling.py:63-127).  Returns the last `mean_x`.
+    `known` / `known_mask` (not in the reference): hold the masked pixels at `known`, see `pc_sampler`."""
     seed = _fresh_seed() if seed is None else seed
+    known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "Euler_Maruyama_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_EM, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
-                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width)
+                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask))
     lib, st = N.lib(), N.stream
     ones = torch.ones(batch_size, device=device)
     x, z = _host_start(N.SAMPLER_EM, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
@@ -169,6 +225,9 @@ def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batc
     time_steps = torch.linspace(1.0, eps, num_steps, device=device)
     step_size = float(time_steps[0] - time_steps[1])
     mean_x = torch.empty_like(x)
+    if known is not None:
+        x = _held_start(x, known, known_mask)
+        s_next = sde_hold_levels("em", num_steps, _sigma_of(marginal_prob_std), eps)["s_next"]
     with torch.no_grad():
         for draw, ts in enumerate(time_steps.tolist(), 1):
             bt = ones * ts
@@ -176,18 +235,29 @@ def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batc
             score = N.f32c(_score(score_model, cfg, x, bt, y, cond_img, lsm_cond, topo_cond))
             N.check(lib.sbgm_em_step(x.data_ptr(), mean_x.data_ptr(), score.data_ptr(), N.ptr(z(draw)), g * g, step_size,
                                      math.sqrt(step_size) * g, seed, draw, x.numel(), st()))
+            if known is not None:
+                N.check(lib.sbgm_hold_known(x.data_ptr(), mean_x.data_ptr(), known.data_ptr(), known_mask.data_ptr(), N.ptr(z(draw)),
+                                            float(s_next[draw - 1]), seed, draw, x.numel(), st()))
     return mean_x
 
 
 def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=800, snr=signal_to_noise_ratio,
                device="cuda", eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
-               noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0):
+               noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None):
     """Predictor-corrector sampler: Langevin corrector with the batch-mean gradient norm, then an Euler-Maruyama
-    predictor (reference score_sampling.py:136-230).  Returns the last `x_mean`."""
+    predictor (reference score_sampling.py:136-230).  Returns the last `x_mean`.
+
+    Constrained sampling (not in the reference; Song et al. 2021, App. I.2): `known` [B,1,H,W] or [B,H,W], model space, and `known_mask`
+    of the same shape, or [H,W] / [1,1,H,W] for one mask shared by the batch, values in [0,1] (clamped on the device; CPU tensors are
+    moved).  Pixels with mask 1 are held: after every state update they are overwritten with `known` plus noise of the level the state
+    is at (reusing that update's own draw: no extra draw, `noise=` keeps its layout), so the result equals `known` there bit for bit and
+    the free pixels are sampled consistently with them.  Mask 0 leaves a pixel exactly as without the arguments (`known` may be NaN
+    there); values in between blend.  Both or neither must be given (ValueError)."""
     seed = _fresh_seed() if seed is None else seed
+    known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "pc_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_PC, score_model, batch_size, num_steps, snr, eps, img_size, y, cond_img, lsm_cond,
-                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width)
+                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask))
     lib, st = N.lib(), N.stream
     ones = torch.ones(batch_size, device=device)
     x, z = _host_start(N.SAMPLER_PC, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
@@ -198,16 +268,26 @@ def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, n
     sumsq = torch.empty(batch_size, dtype=torch.float64, device=device)
     per = x[0].numel()
     snr_nn = float(snr * np.sqrt(per))
+    if known is not None:
+        x = _held_start(x, known, known_mask)
+        lv = sde_hold_levels("pc", num_steps, _sigma_of(marginal_prob_std), eps)
+
+    def hold(x_mean_ptr, level, i, draw):                  # after a step op, with that op's draw
+        if known is not None:
+            N.check(lib.sbgm_hold_known(x.data_ptr(), x_mean_ptr, known.data_ptr(), known_mask.data_ptr(), N.ptr(z(draw)),
+                                        float(lv[level][i]), seed, draw, x.numel(), st()))
     with torch.no_grad():
         for i, ts in enumerate(time_steps):
             bt = ones * ts
             grad = N.f32c(_score(score_model, cfg, x, bt, y, cond_img, lsm_cond, topo_cond, clamp=True))
             N.check(lib.sbgm_langevin_step(x.data_ptr(), grad.data_ptr(), N.ptr(z(1 + 2 * i)), snr_nn, sumsq.data_ptr(), seed,
                                            1 + 2 * i, batch_size, per, st()))
+            hold(None, "s_cur", i, 1 + 2 * i)
             g = float(diffusion_coeff(bt)[0])
             score = N.f32c(_score(score_model, cfg, x, bt, y, cond_img, lsm_cond, topo_cond))
             N.check(lib.sbgm_em_step(x.data_ptr(), x_mean.data_ptr(), score.data_ptr(), N.ptr(z(2 + 2 * i)), g * g, step_size,
                                      math.sqrt(g * g * step_size), seed, 2 + 2 * i, x.numel(), st()))
+            hold(x_mean.data_ptr(), "s_next", i, 2 + 2 * i)
     return x_mean
 
 
@@ -315,22 +395,26 @@ def edm_sampler_kwargs(cfg) -> dict:
 def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=32, device="cuda", eps=1e-3,
                      img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, sigma_min=None, sigma_max=None,
                      rho=7.0, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, noise=None, use_graph=True, seed=None,
-                     tile_origins=None, domain_width=0):
+                     tile_origins=None, domain_width=0, known=None, known_mask=None):
     """Heun (2nd-order) solver of the probability-flow ODE dx/dsigma = -sigma * score on the Karras sigma ladder, with optional
     stochastic churn (Karras et al. 2022, Alg. 2); works with the VE-SDE score network as trained.  `num_steps` N costs 2N-1
     network evaluations (18-64 is the intended range).  Conditions, guidance (`cfg`: both evaluations of a step use
     guidance_scale), `noise` (draw 0 = initial state, draw 1+i = churn of step i when s_churn > 0), `seed`, `use_graph` and
     `tile_origins` behave as in `pc_sampler`.  `diffusion_coeff` is accepted for signature compatibility and unused.
+    `known` / `known_mask` as in `pc_sampler`; here a held pixel follows known + sigma * (draw 0), the exact trajectory of a point mass,
+    so the sampler stays deterministic in its seed.
     Returns x after the last step, [B,1,H,W] (no noise added at the end).  Sample quality against `pc_sampler` at 1000 steps
     has not been measured."""
     sig = float(score_model.sigma) if isinstance(score_model, ScoreNet) else _sigma_of(marginal_prob_std)
     sch = edm_heun_schedule(num_steps, sig, eps, sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise)
     seed = _fresh_seed() if seed is None else seed
+    known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "edm_heun_sampler")
     if isinstance(score_model, ScoreNet) and not score_model.training:
         edm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
                     float(s_churn), float(s_tmin), float(s_tmax), float(s_noise))
         return _native_run(N.SAMPLER_EDM_HEUN, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
-                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, edm_args=edm_args)
+                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, edm_args=edm_args,
+                           held=(known, known_mask))
     lib, st = N.lib(), N.stream
     churn = s_churn > 0
     x, z = _host_start(N.SAMPLER_EDM_HEUN, batch_size, num_steps, img_size, device, noise, seed, float(np.float32(sch["sigma"][0])),
@@ -338,6 +422,12 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     n = x.numel()
     xp, d, out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     ones = torch.ones(batch_size, device=device)
+    if known is not None:
+        x = _held_start(x, known, known_mask)
+
+    def hold(v, level):                                    # held pixels: known + sigma_{i+1} * (draw 0)
+        if known is not None:
+            N.check(lib.sbgm_hold_known(v.data_ptr(), None, known.data_ptr(), known_mask.data_ptr(), N.ptr(z(0)), level, seed, 0, n, st()))
     with torch.no_grad():
         for i in range(int(num_steps)):
             sh, sn = float(sch["sigma_hat"][i]), float(sch["sigma"][i + 1])
@@ -346,10 +436,12 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
             s1 = N.f32c(_score(score_model, cfg, x, ones * float(np.float32(sch["t_hat"][i])), y, cond_img, lsm_cond, topo_cond))
             last = i == int(num_steps) - 1
             N.check(lib.sbgm_edm_euler(x.data_ptr(), s1.data_ptr(), d.data_ptr(), (out if last else xp).data_ptr(), sh, sn, n, st()))
+            hold(out if last else xp, sn)
             if last:
                 break
             s2 = N.f32c(_score(score_model, cfg, xp, ones * float(np.float32(sch["t_next"][i])), y, cond_img, lsm_cond, topo_cond))
             N.check(lib.sbgm_edm_heun(x.data_ptr(), d.data_ptr(), s2.data_ptr(), sh, sn, n, st()))
+            hold(x, sn)
     return out
 
 

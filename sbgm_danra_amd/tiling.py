@@ -105,11 +105,26 @@ class FullDomainTiler:
         return dom[:, :, : self.Wd].contiguous() if self.Wd_pad != self.Wd else dom
 
     def sample(self, score_model, sampler, marginal_prob_std, diffusion_coeff, num_steps, cond_img=None, lsm_cond=None,
-               topo_cond=None, y=None, seed=None, tiles_per_batch=None, **sampler_kw) -> torch.Tensor:
+               topo_cond=None, y=None, seed=None, tiles_per_batch=None, known=None, known_mask=None, **sampler_kw) -> torch.Tensor:
         """Sample the whole domain: cond_img [C,Hd,Wd] / lsm_cond, topo_cond [2,Hd,Wd] / y scalar class -> [1,Hd,Wd].
         Tiles are sharded over the ranks of the process group (if any) and, per rank, run in batches of
-        `tiles_per_batch`; every batch shares `seed`, so the domain-keyed noise is identical wherever tiles overlap."""
+        `tiles_per_batch`; every batch shares `seed`, so the domain-keyed noise is identical wherever tiles overlap.
+        `known`, `known_mask` [1,Hd,Wd] (constrained sampling, see `pc_sampler`): cut into tiles like the conditions and passed to
+        the sampler; after the stitch the hold is applied once more against the domain fields, so the result equals `known` on the
+        mask bit for bit and not just to the rounding of the blend."""
+        import inspect
         from .score_sampling import _fresh_seed
+        if (known is None) != (known_mask is None):
+            raise ValueError("FullDomainTiler.sample: known and known_mask must be given together")
+        held = {}
+        if known is not None:
+            if "known" not in inspect.signature(sampler).parameters:
+                raise ValueError(f"FullDomainTiler.sample: {getattr(sampler, '__name__', sampler)} does not take known / known_mask")
+            known, known_mask = (N.f32c(torch.as_tensor(f).to(self.device)) for f in (known, known_mask))
+            for f, name in ((known, "known"), (known_mask, "known_mask")):
+                if tuple(f.shape) != (1, self.Hd, self.Wd):
+                    raise ValueError(f"FullDomainTiler.sample: {name} {tuple(f.shape)} must be [1, {self.Hd}, {self.Wd}]")
+            held = {"known": known, "known_mask": known_mask}
         _, world = parallel.world()
         seed = _fresh_seed() if seed is None else seed
         if world > 1:                                  # one seed for the whole domain
@@ -124,9 +139,13 @@ class FullDomainTiler:
             return sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=len(idx), **steps,
                            device=self.device, img_size=self.tile, y=yb, cond_img=cut(cond_img), lsm_cond=cut(lsm_cond),
                            topo_cond=cut(topo_cond), seed=seed, tile_origins=self.origins_dev[idx].contiguous(),
-                           domain_width=self.Wd_pad, **sampler_kw)
+                           domain_width=self.Wd_pad, **{k: cut(f) for k, f in held.items()}, **sampler_kw)
         out = sample_tiles_sharded(len(self), run_batch, (1, self.tile, self.tile), self.device, tiles_per_batch)
-        return self.stitch(out)
+        dom = self.stitch(out)
+        if known is not None:                          # hold(dom, known, m): a select where m is 0 or 1
+            m = known_mask.clamp(0.0, 1.0)
+            dom = torch.where(m <= 0, dom, torch.where(m >= 1, known, (1.0 - m) * dom + m * known))
+        return dom
 
 
 def sample_tiles_sharded(n_tiles: int, run_batch, tile_shape, device, tiles_per_batch=None) -> torch.Tensor:
