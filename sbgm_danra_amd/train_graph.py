@@ -36,9 +36,18 @@ _TILES = {}            # conv geometry -> (tile_co, tile_px, splits, waves_per_t
 _SPLITK = {}           # device -> split-K scratch (16 Mi floats), shared by every convolution (stream-ordered)
 _SPLITK_FLOATS = 16 << 20
 
+# debugging switches
+_USE_ARENA = [True]    # False = every gradient in a fresh tensor (the pre-arena behaviour)
+_USE_SLOTS = [True]    # False = every fork summed by autograd (the pre-slot behaviour)
+_USE_WINO = [True]     # False = the training convolutions never use the Winograd kernels
+_BATCH_WGRAD = [True]  # queue the small weight-gradient GEMMs of a backward sweep for one batched launch (sbgm_wgrad_defer bit 1)
+_DEFER_UNPACK = [True]  # queue the slab -> OIHW layout passes of a backward sweep for one launch at its end (sbgm_wgrad_defer bit 0)
+
 
 def _zero_(t):
-    """t.zero_() with the library's own kernel (no at::native fill on the hot path; capture-safe)"""
+    """t.zero_() with the library's own kernel (no at::native fill on the hot path; capture-safe); host tensors: t.zero_()"""
+    if not t.is_cuda:
+        return t.zero_()
     if t.numel():
         N.check(_L().sbgm_fill_zero(t.data_ptr(), t.numel() * t.element_size(), _st()))
     return t
@@ -53,38 +62,55 @@ def _splitk_ws(dev):
 
 # ---- per-step pools --------------------------------------------------------------------------------------------------------
 # Backward scratch that is accumulated with atomics (weight-gradient slabs, norm-backward sums) comes out of ONE buffer that
-# forward_train zeroes once per step; slices are handed out sequentially and never reused before the next forward, so every
+# is zeroed once per step; slices are handed out sequentially and never reused before the next forward, so every
 # slice is still zero when its kernel runs (a second backward through the same graph simply takes fresh slices).
 # Only the part that was handed out is re-zeroed: everything past the step's offset is still zero from the allocation.  Under
 # stream capture the zeroing is recorded with a fixed extent (the high-water mark of earlier steps); slices past it come from
 # fresh tensors, so a replay never sees a stale slab.
+# Gradients that are accumulated with atomics and RETURNED to autograd (conv biases, LayerNorm gamma/beta, time-bias sums, the
+# weights of 1x1 convolutions / linears) are slices of a second pool: a fresh zeroed tensor per step, so a slice that lives on as
+# some parameter's .grad is never touched by a later step (unlike the scratch pool, which is re-zeroed in place).
 _ZERO_FLOATS = 32 << 20
-_ZERO = {}             # device -> [buffer, offset, high-water mark, usable extent of this step]
+_GRAD_FLOATS = 4 << 20
 
 
-def _zero_reset(dev):
-    if _L().sbgm_wgrad_flush_pending():           # a backward pass that raised before its end-of-pass callback: its queued layout
-        _L().sbgm_wgrad_discard()                 # passes point at gradient tensors that may be freed by now — drop them unrun
-    _DEFER_KEEP.clear()
-    _FLUSH_QUEUED[0] = False
-    z = _ZERO.get(dev)
-    if z is None:
-        z = _ZERO[dev] = [torch.zeros(_ZERO_FLOATS, device=dev), 0, 0, _ZERO_FLOATS, False]
-    capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
-    z[4] = z[4] or capturing               # replays of captured steps dirty the pool behind Python's back: from then on the
-    dirty = z[2] if z[4] else z[1]         # whole high-water prefix is re-zeroed, not just this process's last step
-    if dirty:
-        _zero_(z[0][:dirty])
-    z[3] = z[2] if capturing else _ZERO_FLOATS
-    z[1] = 0
-    _GRAD[dev] = [_zero_(torch.empty(_GRAD_FLOATS, device=dev)), 0]
+class _Pool:
+    """bump allocator over one zeroed fp32 tensor, slices aligned to 64 floats"""
+    __slots__ = ("buf", "off", "high_water", "extent", "replayed")
+
+    def __init__(self, buf):
+        self.buf, self.off, self.high_water, self.extent, self.replayed = buf, 0, 0, buf.numel(), False
+
+    def take(self, n):
+        """n zeroed floats: (a slice of the pool, True -> the launcher may skip its own memset) or (a fresh tensor, False)"""
+        end = self.off + (n + 63) // 64 * 64
+        if end > self.extent:
+            return torch.zeros(n, device=self.buf.device), False
+        out = self.buf[self.off: self.off + n]
+        self.off = end
+        if end > self.high_water:
+            self.high_water = end
+        return out, True
+
+    def rezero(self, capturing):
+        """the scratch pool's step: same buffer (captured steps hold its address), dirty prefix zeroed in place"""
+        self.replayed = self.replayed or capturing      # replays of captured steps dirty the pool behind Python's back: from then on
+        dirty = self.high_water if self.replayed else self.off      # the whole high-water prefix is re-zeroed, not just the last step's
+        if dirty:
+            _zero_(self.buf[:dirty])
+        self.extent = self.high_water if capturing else self.buf.numel()
+        self.off = 0
+
+    def renew(self):
+        """the returned-gradient pool's step: a new zeroed tensor (slices of the old one may live on as .grad)"""
+        self.buf, self.off = _zero_(torch.empty_like(self.buf)), 0
 
 
 # ---- gradient arena ------------------------------------------------------------------------------------------------------
 # Every parameter gradient of a model lives in ONE flat fp32 tensor: the backward kernels write (or atomically accumulate) a
 # parameter's gradient straight into its slice, `p.grad` ends up as a view of that slice, so the data-parallel exchange is ONE
 # all-reduce over the flat tensor with no gather / scatter copies (parallel.GradientBucket adopts it) and the native Adam step
-# reads the same memory.  The arena is zeroed once per step by forward_train.  It is used when every `p.grad` is None at the start
+# reads the same memory.  The arena is zeroed once per step by _Step.begin.  It is used when every `p.grad` is None at the start
 # of the step (`optimizer.zero_grad()` default); with live gradients (accumulation over several backward calls) the kernels
 # write fresh tensors and autograd adds them, exactly as before.
 class GradArena:
@@ -121,8 +147,6 @@ class GradArena:
 
 
 _WGRAD_LOG = [None]             # bench.py: when a list, ConvFn.backward appends the geometry of every weight gradient it launches
-_ACTIVE_ARENA = [None]
-_USE_ARENA = [True]             # debugging switch: False = every gradient in a fresh tensor (the pre-arena behaviour)
 
 
 def arena_for(net, create=True):
@@ -134,9 +158,6 @@ def arena_for(net, create=True):
         a = GradArena(net)
         object.__setattr__(net, "_grad_arena", a)
     return a
-
-
-_BATCH_WGRAD = [True]  # queue the small weight-gradient GEMMs of a backward sweep for one batched launch (sbgm_wgrad_defer bit 1)
 
 
 def _in_arena(arena, t):
@@ -154,7 +175,7 @@ def _pgrad(arena, like, zeroed):
         if v is not None:
             return v, True
     if zeroed:
-        g, z = _grad_zeros(like.numel(), like.device)
+        g, z = _STEP.zeros(like.numel(), like.device, True)
         return g.view(like.shape), z
     return torch.empty_like(like), False
 
@@ -184,7 +205,7 @@ class _GradSlot:
         return a if (a is None or like is None) else a.view(like.shape)
 
     def give(self, g):
-        _queue_slot_check()
+        _STEP.at_backward_end()                              # the incomplete-slot check
         self.left -= 1
         if self.left > 0:
             self.acc = g
@@ -193,52 +214,26 @@ class _GradSlot:
         return g
 
 
-_SLOTS = []
-_SLOT_CHECK_QUEUED = [False]
-
-
-def _queue_slot_check():
-    if not _SLOT_CHECK_QUEUED[0]:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_check_slots)
-            _SLOT_CHECK_QUEUED[0] = True
-        except RuntimeError:                                 # not inside a backward pass
-            pass
-_USE_SLOTS = [True]            # debugging switch: False = every fork summed by autograd (the pre-slot behaviour)
-
-
 def _slot(n):
     if not _USE_SLOTS[0] or n < 2:
         return None
     sl = _GradSlot(n)
-    _SLOTS.append(sl)
+    _STEP.slots.append(sl)
     return sl
 
 
-def _check_slots():
-    _SLOT_CHECK_QUEUED[0] = False
-    bad = [sl for sl in _SLOTS if sl.left != sl.n]           # untouched (no consumer needed the gradient) or completed: fine
-    for sl in bad:
-        sl.left, sl.acc = sl.n, None
-    if bad:
-        raise RuntimeError(f"{len(bad)} gradient slot(s) were left incomplete by the backward pass: a consumer of a shared tensor did not "
-                           f"run its backward (partial graph?); set train_graph._USE_SLOTS[0] = False")
-
-
-def _fold(slot, g, fused=False):
-    """hand gradient `g` of a slotted input to the slot; `fused`: the pending partial sum was already added by the kernel"""
+def _fold(slot, g):
+    """hand gradient `g` of a slotted input to the slot, from a consumer whose kernel has no fused-add path"""
     if slot is None:
         return g
-    if not fused:
-        extra = slot.take(g)
-        if extra is not None:
-            g = g + extra                                    # consumer without a fused-add path ran late: one torch add
+    extra = slot.take(g)
+    if extra is not None:
+        g = g + extra                                        # ran late: one torch add
     return slot.give(g)
 
 
 # SyncBatchNorm (DESIGN.md 7): statistics summed over the ranks of the process group, see BNTrainFn
 _SYNC_BN = [False]
-_SYNC_COUNT = [None]            # total batch size over the ranks for the current forward (device-independent python int)
 
 
 def set_sync_batchnorm(on: bool):
@@ -254,55 +249,89 @@ def _sync_world():
     return None
 
 
-# Gradients that are accumulated with atomics and RETURNED to autograd (conv biases, LayerNorm gamma/beta, time-bias sums,
-# the weights of 1x1 convolutions / linears) are slices of one tensor that forward_train allocates zeroed — a fresh tensor per step, so a slice that lives on as
-# some parameter's .grad is never touched by a later step (unlike the scratch pool above, which is re-zeroed in place).
-_GRAD_FLOATS = 4 << 20
-_GRAD = {}             # device -> [tensor, offset]
+# ---- the step ------------------------------------------------------------------------------------------------------------
+class _Step:
+    """Everything that lives for one forward + backward.  `begin` is the only place that resets it; forward_train, the stand-alone
+    sub-module calls and tests that drive single ops all start there.  Deliberately older than a step: the scratch pool's buffer
+    (captured steps hold its address), a model's _PackPlan and GradArena, the tile cache _TILES and the split-K scratch."""
+
+    def __init__(self):
+        self.pools = {}            # device -> (scratch pool, returned-gradient pool)
+        self.arena = None          # the GradArena the gradients of this step go to, or None
+        self.plan = None           # the _PackPlan whose images this step's convolutions read, or None
+        self.slots = []            # every _GradSlot of this step
+        self.queued = False        # the end-of-backward callback is queued
+        self.keep = []             # (dy, x) of the weight-gradient GEMMs queued for the batched launch: alive until the flush has enqueued them
+        self.nbt = []              # num_batches_tracked of every train-mode BatchNorm of the forward: one increment at its end, not 20
+        self.sync_count = None     # SyncBatchNorm: total batch size over the ranks (a python int)
+
+    def begin(self, dev, net=None):
+        """start a step on `dev`; net: the model whose whole forward this is (its plan and, when every p.grad is None, its arena
+        become active), None: a stand-alone call, neither"""
+        if _L().sbgm_wgrad_flush_pending():           # a backward pass that raised before its end-of-pass callback: its queued layout
+            _L().sbgm_wgrad_discard()                 # passes point at gradient tensors that may be freed by now -- drop them unrun
+        self.slots.clear()
+        self.keep.clear()
+        self.nbt.clear()
+        self.queued = False                           # (autograd drops the queued callback of a backward pass that raised)
+        self.plan = self.arena = self.sync_count = None
+        pools = self.pools.get(dev)
+        if pools is None:
+            pools = self.pools[dev] = (_Pool(torch.zeros(_ZERO_FLOATS, device=dev)), _Pool(torch.empty(_GRAD_FLOATS, device=dev)))
+        pools[0].rezero(dev.type == "cuda" and torch.cuda.is_current_stream_capturing())
+        pools[1].renew()
+        if net is not None:
+            self.plan = _plan_for(net)
+            if _USE_ARENA[0] and all(p.grad is None for p in net.parameters()):      # fresh step: gradients go straight into the model's flat arena
+                self.arena = arena_for(net)
+                self.arena.begin_step()
+
+    def zeros(self, n, dev, returned=False):
+        """n zeroed floats of backward scratch, or (returned) for a gradient that is handed to autograd; see _Pool.take"""
+        pools = self.pools.get(dev)
+        return pools[returned].take(n) if pools is not None else (torch.zeros(n, device=dev), False)
+
+    def bump_nbt(self):
+        if self.nbt:
+            with torch.no_grad():
+                torch._foreach_add_(list(self.nbt), 1)
+            self.nbt.clear()
+
+    def flush_wgrad(self):
+        """run the weight-gradient work queued so far (also called mid-pass by _BucketBoundary)"""
+        try:
+            if _L().sbgm_wgrad_flush_pending():
+                N.check(_L().sbgm_wgrad_flush(_st()))
+        finally:
+            self.keep.clear()
+
+    def at_backward_end(self):
+        """queue the end-of-backward work (once per pass)"""
+        if not self.queued:
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(self._backward_end)
+                self.queued = True
+            except RuntimeError:                             # not inside a backward pass (a direct .backward() call on the Function):
+                self.flush_wgrad()                           # nothing to wait for, and no pass whose slots could be checked
+
+    def _backward_end(self):
+        self.queued = False
+        self.flush_wgrad()
+        bad = [sl for sl in self.slots if sl.left != sl.n]   # untouched (no consumer needed the gradient) or completed: fine
+        for sl in bad:
+            sl.left, sl.acc = sl.n, None
+        if bad:
+            raise RuntimeError(f"{len(bad)} gradient slot(s) were left incomplete by the backward pass: a consumer of a shared tensor did not "
+                               f"run its backward (partial graph?); set train_graph._USE_SLOTS[0] = False")
 
 
-def _grad_zeros(n, dev):
-    """n zeroed floats for a returned gradient (second value True -> came from the step's tensor, already zero)"""
-    g = _GRAD.get(dev)
-    n_al = (n + 63) // 64 * 64
-    if g is None or g[1] + n_al > _GRAD_FLOATS:
-        return torch.zeros(n, device=dev), False
-    out = g[0][g[1]: g[1] + n]
-    g[1] += n_al
-    return out, True
-
-
-def _zeros(n, dev):
-    """n zeroed floats: a slice of the step's pool (second value True -> the launcher may skip its own memset) or a fresh tensor"""
-    z = _ZERO.get(dev)
-    n_al = (n + 63) // 64 * 64
-    if z is None or z[1] + n_al > z[3]:
-        return torch.zeros(n, device=dev), False
-    out = z[0][z[1]: z[1] + n]
-    z[1] += n_al
-    z[2] = max(z[2], z[1])
-    return out, True
+_STEP = _Step()
+_zero_reset = _STEP.begin      # the name tests that drive single ops know for "begin a stand-alone step on `dev`"
 
 
 # Slab -> OIHW layout passes of the weight gradients are queued during a backward pass and run as one launch at its end
 # (autograd's end-of-pass callback).  Only slabs from the step's pool are queued: they stay alive and untouched until the next
 # forward.  Until the callback has run, the affected `.grad` views hold zeros (gradient hooks on conv weights would see that).
-_DEFER_UNPACK = [True]
-_FLUSH_QUEUED = [False]
-
-
-_DEFER_KEEP = []       # (dy, x) of the weight-gradient GEMMs queued for the batched launch: alive until the flush has enqueued them
-
-
-def _flush_wgrad():
-    _FLUSH_QUEUED[0] = False
-    try:
-        if _L().sbgm_wgrad_flush_pending():
-            N.check(_L().sbgm_wgrad_flush(_st()))
-    finally:
-        _DEFER_KEEP.clear()
-
-
 class _deferred_unpack:
     """`on`: the slab -> OIHW pass of this call may wait for the end of the backward sweep; `gemm`: so may the weight-gradient GEMM itself
     (sbgm_wgrad_defer bit 1: the small per-tap GEMMs of a sweep run as one batched launch) — `keep` = the tensors it reads, held until then"""
@@ -315,17 +344,13 @@ class _deferred_unpack:
         if self.on:
             self.prev = _L().sbgm_wgrad_defer(self.mask)
             if self.keep:
-                _DEFER_KEEP.append(self.keep)
+                _STEP.keep.append(self.keep)
 
     def __exit__(self, *exc):
         if self.on:
             _L().sbgm_wgrad_defer(self.prev)
-            if not _FLUSH_QUEUED[0] and _L().sbgm_wgrad_flush_pending():
-                try:
-                    torch.autograd.Variable._execution_engine.queue_callback(_flush_wgrad)
-                    _FLUSH_QUEUED[0] = True
-                except RuntimeError:                       # not inside a backward pass (a direct .backward() call on the Function)
-                    _flush_wgrad()
+            if not _STEP.queued and _L().sbgm_wgrad_flush_pending():
+                _STEP.at_backward_end()
 
 
 class _prezeroed:
@@ -429,8 +454,16 @@ class _PackPlan:
 
 
 _PLANS = {}            # id(net) -> _PackPlan
-_ACTIVE_PLAN = [None]
-_USE_WINO = [True]     # debugging switch: False = the training convolutions never use the Winograd kernels
+
+
+def _plan_for(net):
+    plan = _PLANS.get(id(net))
+    if plan is None or plan.owner() is not net:           # ids are recycled: a plan belongs to one live model object
+        plan = _PLANS[id(net)] = _PackPlan()
+        plan.owner = weakref.ref(net)
+        for k in [k for k, v in _PLANS.items() if v.owner() is None]:
+            del _PLANS[k]
+    return plan
 
 
 def _wino_ok(k, stride, pad, in_dil, cs, cout, W):
@@ -506,6 +539,40 @@ def _pack_single(w, cout, cin, k, cs, flags):
     return dst
 
 
+def _conv_with_images(x, w, out, imgs, dgrad, cs, cout, k, stride, pad, **epilogue):
+    """One convolution with whatever images weight `w` has.  dgrad False: the forward operator (w is [cout, cin <= cs, k, k]);
+    True: the data-gradient operator (w is [cs, cout, k, k], read transposed and flipped).  imgs: the plan's ('g', 'w', 'd') images
+    for this role, or None.  When they do not hold what the geometry's tile reads (first step; another batch shape of the same weight
+    wants another layout) the implicit-GEMM image and every Winograd image the geometry admits are packed on the spot.
+    Returns (layout read, True if packed here): the caller tells its plan."""
+    if imgs is not None and any(im is not None for im in imgs):
+        try:
+            return _conv_launch(x, imgs[0], out, cs, cout, k, stride, pad, wino=imgs[1], w2d=imgs[2], on_missing="raise", **epilogue), False
+        except _MissingImage:
+            pass
+    packed = torch.empty(_L().sbgm_conv_packed_numel(cout, k, k, cs), device=x.device)
+    if dgrad:
+        N.check(_L().sbgm_conv_pack_weight_dgrad(w.data_ptr(), packed.data_ptr(), cs, cout, k, k, _st()))
+    else:
+        N.check(_L().sbgm_conv_pack_weight(w.data_ptr(), packed.data_ptr(), cout, w.shape[1], k, k, cs, _st()))
+    pw = pd = None
+    if _USE_WINO[0] and not torch.cuda.is_current_stream_capturing():
+        cin, in_dil = w.shape[0 if dgrad else 1], epilogue.get("in_dil", 0)
+        if _wino_ok(k, stride, pad, in_dil, cs, cout, x.shape[2]):
+            pw = _pack_single(w, cout, cin, k, cs, 2 | dgrad)
+        if _w2d_ok(k, stride, pad, in_dil, cs, cout, x.shape[1], x.shape[2]):
+            pd = _pack_single(w, cout, cin, k, cs, 4 | dgrad)
+    return _conv_launch(x, packed, out, cs, cout, k, stride, pad, wino=pw, w2d=pd, **epilogue), True
+
+
+def _samplesum(dy, B, Cc):
+    """gradient of a per-sample bias [B, Cc] broadcast over the pixels of dy"""
+    dtb, zeroed = _STEP.zeros(B * Cc, dy.device, True)
+    with _prezeroed(zeroed):
+        N.check(_L().sbgm_samplesum(dy.data_ptr(), dtb.data_ptr(), B, dy.numel() // (B * Cc), Cc, _st()))
+    return dtb.view(B, Cc)
+
+
 class ConvFn(torch.autograd.Function):
     """y = conv2d(x, w, stride, pad) [+ bias] [+ tbias[b] broadcast over pixels] [+ res]   (NHWC x, OIHW w).
     Also serves nn.Linear as a 1x1 conv."""
@@ -514,37 +581,23 @@ class ConvFn(torch.autograd.Function):
     def forward(ctx, x, w, bias, res, tbias, stride, pad, xslot=None, rslot=None):
         B, H, W, cs = x.shape
         cout, cin, k, _ = w.shape
-        plan = _ACTIVE_PLAN[0]
+        plan = _STEP.plan
         e = plan.lookup(w, cs) if plan is not None else None
+        fwd_imgs = ctx.packed_bwd = None
+        if e is not None:                                    # packed by the step's batched launch, in the layout(s) its tiles read
+            fwd_imgs, ctx.packed_bwd = (tuple(e["img"][(role, l)] for l in "gwd") for role in ("fwd", "bwd"))
         oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
         y = torch.empty(B, oh, ow, cout, device=x.device)
-        used = None
-        if e is not None:                                    # packed by the step's batched launch, in the layout(s) its tiles read
-            try:
-                used = _conv_launch(x, e["img"][("fwd", "g")], y, cs, cout, k, stride, pad, bias, res, tbias, wino=e["img"][("fwd", "w")],
-                                    w2d=e["img"][("fwd", "d")], on_missing="raise")
-            except _MissingImage:                            # another batch shape of the same weight wants the other layout
-                used = None
-        if used is None:
-            packed = torch.empty(_L().sbgm_conv_packed_numel(cout, k, k, cs), device=x.device)
-            N.check(_L().sbgm_conv_pack_weight(w.data_ptr(), packed.data_ptr(), cout, cin, k, k, cs, _st()))
-            pw = pd = None
-            if _USE_WINO[0] and not torch.cuda.is_current_stream_capturing():
-                if _wino_ok(k, stride, pad, 0, cs, cout, W):
-                    pw = _pack_single(w, cout, cin, k, cs, 2)
-                if _w2d_ok(k, stride, pad, 0, cs, cout, H, W):
-                    pd = _pack_single(w, cout, cin, k, cs, 4)
-            used = _conv_launch(x, packed, y, cs, cout, k, stride, pad, bias, res, tbias, wino=pw, w2d=pd)
-            base = w._base if w._base is not None else w
-            if plan is not None and base.is_leaf and base.data_ptr() == w.data_ptr() and base.numel() == w.numel():
-                # a parameter or a reshaped view of one (nn.Linear weights), not a derived tensor: batch-pack it from the next step on
-                plan.note(w, cs, dgrad=x.requires_grad and cs == cin and cs % 32 == 0, layout=used)
+        used, packed_here = _conv_with_images(x, w, y, fwd_imgs, False, cs, cout, k, stride, pad, bias=bias, res=res, tbias=tbias)
+        base = w._base if w._base is not None else w
+        if packed_here and plan is not None and base.is_leaf and base.data_ptr() == w.data_ptr() and base.numel() == w.numel():
+            # a parameter or a reshaped view of one (nn.Linear weights), not a derived tensor: batch-pack it from the next step on
+            plan.note(w, cs, dgrad=x.requires_grad and cs == cin and cs % 32 == 0, layout=used)
         ctx.save_for_backward(x, w, bias)
         ctx.geom = (stride, pad, bias is not None, res is not None, tbias is not None)
         ctx.slots = (xslot, rslot)
-        ctx.packed_bwd = (e["img"][("bwd", "g")], e["img"][("bwd", "w")], e["img"][("bwd", "d")]) if e is not None else None
         ctx.plan = plan
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return y
 
     @staticmethod
@@ -575,26 +628,10 @@ class ConvFn(torch.autograd.Function):
             if cs != cin or cs % 32:
                 raise NotImplementedError("data gradient w.r.t. a channel-padded input is not needed on this path")
             dx = torch.empty_like(x)
-            dil = 2 if stride == 2 else 0
-            used = None
-            if ctx.packed_bwd is not None and any(im is not None for im in ctx.packed_bwd):
-                try:
-                    used = _conv_launch(dy, ctx.packed_bwd[0], dx, cout, cin, k, 1, k - 1 - pad, res=extra, in_dil=dil, out_hw=(H, W),
-                                        wino=ctx.packed_bwd[1], w2d=ctx.packed_bwd[2], on_missing="raise")
-                except _MissingImage:
-                    used = None
-            if used is None:
-                packed = torch.empty(_L().sbgm_conv_packed_numel(cin, k, k, cout), device=x.device)
-                N.check(_L().sbgm_conv_pack_weight_dgrad(w.data_ptr(), packed.data_ptr(), cout, cin, k, k, _st()))
-                pw = pd = None
-                if _USE_WINO[0] and cout % 16 == 0 and not torch.cuda.is_current_stream_capturing():
-                    if _wino_ok(k, 1, k - 1 - pad, dil, cout, cin, dy.shape[2]):
-                        pw = _pack_single(w, cin, cout, k, cout, 3)
-                    if _w2d_ok(k, 1, k - 1 - pad, dil, cout, cin, dy.shape[1], dy.shape[2]):
-                        pd = _pack_single(w, cin, cout, k, cout, 5)
-                used = _conv_launch(dy, packed, dx, cout, cin, k, 1, k - 1 - pad, res=extra, in_dil=dil, out_hw=(H, W), wino=pw, w2d=pd)
-                if ctx.plan is not None:
-                    ctx.plan.note_bwd(w, cs, used)
+            used, packed_here = _conv_with_images(dy, w, dx, ctx.packed_bwd, True, cout, cin, k, 1, k - 1 - pad, res=extra,
+                                                  in_dil=2 if stride == 2 else 0, out_hw=(H, W))
+            if packed_here and ctx.plan is not None:
+                ctx.plan.note_bwd(w, cs, used)
             fused = True                                         # the convolution's epilogue added the pending partial sum
         want_db = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
@@ -606,7 +643,7 @@ class ConvFn(torch.autograd.Function):
                 ws, defer = dw, False
             else:
                 dw, in_arena = _pgrad(arena, w, False)
-                ws, pooled = _zeros(k * k * cout * cs, x.device)
+                ws, pooled = _STEP.zeros(k * k * cout * cs, x.device)
                 # the layout pass may run at the end of the backward sweep only when nothing consumes dw before that: an arena
                 # slice becomes p.grad as it is; a fresh tensor may be added to a live .grad by AccumulateGrad right away
                 defer = pooled and in_arena
@@ -625,12 +662,7 @@ class ConvFn(torch.autograd.Function):
         if want_db:
             db, _ = _pgrad(arena, bias, False)
             N.check(_L().sbgm_colsum(dy.data_ptr(), None, db.data_ptr(), dy.numel() // cout, cout, _st()))
-        dtb = None
-        if has_tb and ctx.needs_input_grad[4]:
-            dtb, zeroed = _grad_zeros(B * cout, x.device)
-            dtb = dtb.view(B, cout)
-            with _prezeroed(zeroed):
-                N.check(_L().sbgm_samplesum(dy.data_ptr(), dtb.data_ptr(), B, dy.numel() // (B * cout), cout, _st()))
+        dtb = _samplesum(dy, B, cout) if has_tb and ctx.needs_input_grad[4] else None
         if xslot is not None and ctx.needs_input_grad[0]:
             if not fused and extra is not None:
                 dx = dx + extra                                  # stem convolution (phase-decomposed data gradient): no residual epilogue
@@ -661,7 +693,7 @@ class BNTrainFn(torch.autograd.Function):
         ctx.rslot = rslot
         y = torch.empty_like(x)
         mr = torch.empty(Cc, 2, device=x.device)         # (mean, rstd) per channel, kept for the backward
-        sums, pooled = _zeros(4 * Cc, x.device)          # 2C fp64 sums: scratch of this launch only
+        sums, pooled = _STEP.zeros(4 * Cc, x.device)          # 2C fp64 sums: scratch of this launch only
         dist = _sync_world()
         n_total = None
         with _prezeroed(pooled):
@@ -670,7 +702,7 @@ class BNTrainFn(torch.autograd.Function):
                                                       rv.data_ptr(), N.ptr(res), N.ptr(tb_after), int(relu), B, H * W, Cc, eps, momentum,
                                                       sums.data_ptr(), mr.data_ptr(), _st()))
             else:
-                n_total = float(_SYNC_COUNT[0] * H * W)
+                n_total = float(_STEP.sync_count * H * W)
                 N.check(_L().sbgm_batchnorm_train_stats(x.data_ptr(), B, H * W, Cc, sums.data_ptr(), _st()))
                 dist.all_reduce(sums.view(torch.float64))
                 N.check(_L().sbgm_batchnorm_train_apply(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(),
@@ -680,7 +712,7 @@ class BNTrainFn(torch.autograd.Function):
             _RELU_TRACE[0].append(((y - tb_after.view(B, 1, 1, Cc)) if tb_after is not None else y) > 0)
         ctx.save_for_backward(x, y, gamma, beta, tb_after, mr)
         ctx.cfg = (relu, res is not None, tb_after is not None, n_total)
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return y
 
     @staticmethod
@@ -692,7 +724,7 @@ class BNTrainFn(torch.autograd.Function):
         dx, dres = torch.empty_like(x), (torch.empty_like(x) if has_res else None)
         dg, _ = _pgrad(ctx.arena, gamma, False)
         db, _ = _pgrad(ctx.arena, beta, False)
-        s12, pooled = _zeros(B * Cc * 2, x.device)
+        s12, pooled = _STEP.zeros(B * Cc * 2, x.device)
         with _prezeroed(pooled):
             if n_total is None:
                 N.check(_L().sbgm_batchnorm_bwd(x.data_ptr(), dy.data_ptr(), y.data_ptr(), gamma.data_ptr(), N.ptr(tb_after), mr.data_ptr(),
@@ -709,12 +741,7 @@ class BNTrainFn(torch.autograd.Function):
                 N.check(_L().sbgm_batchnorm_bwd_apply(x.data_ptr(), dy.data_ptr(), y.data_ptr(), gamma.data_ptr(), N.ptr(tb_after),
                                                       mr.data_ptr(), int(relu), dx.data_ptr(), N.ptr(dres), dg.data_ptr(), db.data_ptr(),
                                                       s12.data_ptr(), tot.data_ptr(), n_total, B, H * W, Cc, _st()))
-        dtb = None
-        if has_tb:
-            dtb, zeroed = _grad_zeros(B * Cc, x.device)
-            dtb = dtb.view(B, Cc)
-            with _prezeroed(zeroed):
-                N.check(_L().sbgm_samplesum(dy.data_ptr(), dtb.data_ptr(), B, H * W, Cc, _st()))
+        dtb = _samplesum(dy, B, Cc) if has_tb else None
         return dx, dg, db, None, None, (_fold(ctx.rslot, dres) if dres is not None else None), dtb, None, None, None, None
 
 
@@ -732,7 +759,7 @@ class GroupNormFn(torch.autograd.Function):
                                         Cc, G, eps, ws.data_ptr(), mr.data_ptr(), _st()))
         ctx.save_for_backward(x, gamma, beta, skip, tbias, mr)
         ctx.cfg = (act, G)
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return y
 
     @staticmethod
@@ -747,7 +774,7 @@ class GroupNormFn(torch.autograd.Function):
         dg = _pgrad(ctx.arena, gamma, False)[0] if gamma is not None else None
         db = _pgrad(ctx.arena, beta, False)[0] if gamma is not None else None
         dtb = torch.empty(B, Cc, device=dev) if tbias is not None else None
-        s12, pooled = _zeros(B * Cc * 2, dev)
+        s12, pooled = _STEP.zeros(B * Cc * 2, dev)
         with _prezeroed(pooled):
             N.check(_L().sbgm_groupnorm_bwd(x.data_ptr(), dy.data_ptr(), N.ptr(gamma), N.ptr(beta), N.ptr(skip), N.ptr(tbias), mr.data_ptr(),
                                             act, dx.data_ptr(), N.ptr(dskip), N.ptr(dg), N.ptr(db), N.ptr(dtb), s12.data_ptr(), B, H * W, Cc,
@@ -764,7 +791,7 @@ class LayerNormFn(torch.autograd.Function):
         ctx.save_for_backward(x, gamma, beta)
         ctx.xslot = xslot
         ctx.eps = eps
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return y
 
     @staticmethod
@@ -802,7 +829,7 @@ class MHACoreFn(torch.autograd.Function):
         (qkv,) = ctx.saved_tensors
         B, S, Cc, heads = ctx.dims
         dout = dout.contiguous()
-        dqkv, zeroed = _grad_zeros(qkv.numel(), qkv.device)       # dK / dV are accumulated with atomics: a slice of the step's zeroed pool
+        dqkv, zeroed = _STEP.zeros(qkv.numel(), qkv.device, True)       # dK / dV are accumulated with atomics: a slice of the step's zeroed pool
         dqkv = dqkv.view(qkv.shape)                              # saves the launcher's own memset (4 per step)
         with _prezeroed(zeroed):
             N.check(_L().sbgm_mha_core_bwd(qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), B, S, Cc, heads, _st()))
@@ -825,7 +852,7 @@ class MHACoreDropoutFn(torch.autograd.Function):
         (qkv,) = ctx.saved_tensors
         B, S, Cc, heads, p, seed = ctx.dims
         dout = dout.contiguous()
-        dqkv, zeroed = _grad_zeros(qkv.numel(), qkv.device)
+        dqkv, zeroed = _STEP.zeros(qkv.numel(), qkv.device, True)
         dqkv = dqkv.view(qkv.shape)
         with _prezeroed(zeroed):
             N.check(_L().sbgm_mha_core_dropout_bwd(qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), B, S, Cc, heads, p, seed, 0, _st()))
@@ -923,7 +950,7 @@ class TimeProjFn(torch.autograd.Function):
                                         _st()))
         ctx.save_for_backward(weight, bias, semb, raw, y if y is not None else torch.empty(0), table if table is not None else torch.empty(0))
         ctx.has_y = y is not None
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return out
 
     @staticmethod
@@ -963,7 +990,7 @@ class TimeProjMultiFn(torch.autograd.Function):
         ctx.save_for_backward(semb, raw, y if y is not None else torch.empty(0), table if table is not None else torch.empty(0),
                               *weights, *biases)
         ctx.meta = (tuple(emb_index), n_emb, n_proj, y is not None)
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return tuple(outs)
 
     @staticmethod
@@ -1011,7 +1038,7 @@ class Cout1Fn(torch.autograd.Function):
                                             _st()))
         ctx.save_for_backward(a, wp, t, w, bias)
         ctx.sigma = sigma
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return out
 
     @staticmethod
@@ -1040,14 +1067,11 @@ def _pack_inputs(x, lsm, topo, cond, cs):
     return out
 
 
-_NBT = []
-
-
 def _bn(x, bn, res=None, tb_after=None, relu=True, rslot=None):
     if not bn.training:
         return _bn_eval(x, bn, res, tb_after, relu, rslot)
     y = BNTrainFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, res, tb_after, relu, bn.eps, bn.momentum, rslot)
-    _NBT.append(bn.num_batches_tracked)                  # incremented together at the end of forward_train (one launch, not 20)
+    _STEP.nbt.append(bn.num_batches_tracked)
     return y
 
 
@@ -1074,7 +1098,7 @@ class BNEvalFn(torch.autograd.Function):
             _RELU_TRACE[0].append(((y - tb_after.view(B, 1, 1, Cc)) if tb_after is not None else y) > 0)
         ctx.save_for_backward(x, y, gamma, beta, tb_after, mr)
         ctx.cfg = (relu, res is not None, tb_after is not None)
-        ctx.arena = _ACTIVE_ARENA[0]
+        ctx.arena = _STEP.arena
         return y
 
     @staticmethod
@@ -1086,7 +1110,7 @@ class BNEvalFn(torch.autograd.Function):
         dx, dres = torch.empty_like(x), (torch.empty_like(x) if has_res else None)
         dg, _ = _pgrad(ctx.arena, gamma, False)
         db, _ = _pgrad(ctx.arena, beta, False)
-        s12, pooled = _zeros(B * Cc * 2, x.device)
+        s12, pooled = _STEP.zeros(B * Cc * 2, x.device)
         with _prezeroed(pooled):
             N.check(_L().sbgm_batchnorm_bwd_reduce(x.data_ptr(), dy.data_ptr(), y.data_ptr(), N.ptr(tb_after), mr.data_ptr(), int(relu),
                                                    s12.data_ptr(), B, H * W, Cc, _st()))
@@ -1094,12 +1118,7 @@ class BNEvalFn(torch.autograd.Function):
         N.check(_L().sbgm_batchnorm_bwd_apply(x.data_ptr(), dy.data_ptr(), y.data_ptr(), gamma.data_ptr(), N.ptr(tb_after), mr.data_ptr(),
                                               int(relu), dx.data_ptr(), N.ptr(dres), dg.data_ptr(), db.data_ptr(), s12.data_ptr(),
                                               zero.data_ptr(), float(B * H * W), B, H * W, Cc, _st()))
-        dtb = None
-        if has_tb:
-            dtb, zeroed = _grad_zeros(B * Cc, x.device)
-            dtb = dtb.view(B, Cc)
-            with _prezeroed(zeroed):
-                N.check(_L().sbgm_samplesum(dy.data_ptr(), dtb.data_ptr(), B, H * W, Cc, _st()))
+        dtb = _samplesum(dy, B, Cc) if has_tb else None
         return dx, dg, db, None, None, (_fold(ctx.rslot, dres) if dres is not None else None), dtb, None, None, None
 
 
@@ -1133,44 +1152,22 @@ def _attention(mod, x):                               # x: [B, H, W, C] -> same 
 
 
 def forward_train(net, x, t, y, cond, lsm, topo):
-    plan = _PLANS.get(id(net))
-    if plan is None or plan.owner() is not net:           # ids are recycled: a plan belongs to one live model object
-        plan = _PLANS[id(net)] = _PackPlan()
-        plan.owner = weakref.ref(net)
-        for k in [k for k, v in _PLANS.items() if v.owner() is None]:
-            del _PLANS[k]
-    _ACTIVE_PLAN[0] = plan
-    _NBT.clear()
-    _SLOTS.clear()
-    _zero_reset(x.device)
-    arena = None
-    if _USE_ARENA[0] and all(p.grad is None for p in net.parameters()):      # fresh step: gradients go straight into the model's flat arena
-        arena = arena_for(net)
-        arena.begin_step()
-    _ACTIVE_ARENA[0] = arena
-    dist = _sync_world()
-    if dist is not None:                                    # SyncBatchNorm: total batch over the ranks (ragged last batches allowed)
-        cnt = torch.tensor([float(x.shape[0])], device=x.device)
-        dist.all_reduce(cnt)
-        _SYNC_COUNT[0] = int(round(float(cnt.item())))
-    plan.run(x.device)
+    _STEP.begin(x.device, net)
     try:
+        dist = _sync_world()
+        if dist is not None:                                # SyncBatchNorm: total batch over the ranks (ragged last batches allowed)
+            cnt = torch.tensor([float(x.shape[0])], device=x.device)
+            dist.all_reduce(cnt)
+            _STEP.sync_count = int(round(float(cnt.item())))
+        _STEP.plan.run(x.device)
         skip_slots = []
         fmaps = encoder_forward(net.encoder, x, t, y, cond, lsm, topo, skip_slots)
         a = decoder_forward(net.decoder, fmaps, t, skip_slots)
         fin = net.decoder.final_layer
-        _bump_nbt()
+        _STEP.bump_nbt()
         return Cout1Fn.apply(a, fin.conv.weight, fin.conv.bias, t, float(net.sigma))
     finally:
-        _ACTIVE_PLAN[0] = None
-        _ACTIVE_ARENA[0] = None
-
-
-def _bump_nbt():
-    if _NBT:
-        with torch.no_grad():
-            torch._foreach_add_(list(_NBT), 1)
-        _NBT.clear()
+        _STEP.plan = _STEP.arena = None                     # active while the forward records its ops, not for single ops run after it
 
 
 def _tproj(t, y, tlabel, freq_mod, seq):
@@ -1272,7 +1269,7 @@ class _BucketBoundary(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         if not (dy.is_cuda and torch.cuda.is_current_stream_capturing()):      # a captured step exchanges after the replay
-            _flush_wgrad()                                   # decoder weight gradients: slab -> OIHW slices of the arena, now
+            _STEP.flush_wgrad()                              # decoder weight gradients: slab -> OIHW slices of the arena, now
             ctx.bucket.begin_early([p for p in ctx.dec.parameters() if p.requires_grad])
         return dy, None, None
 
@@ -1325,16 +1322,12 @@ class _ToNHWC(torch.autograd.Function):
         return _ToNCHW.apply(dy.contiguous())
 
 
-def _standalone(fn):
-    """run `fn` with the per-step scratch pools reset, as forward_train does for the whole network"""
-    def wrapped(dev, *a, **k):
-        _NBT.clear()
-        _zero_reset(dev)
-        _ACTIVE_ARENA[0] = None
-        out = fn(*a, **k)
-        _bump_nbt()
-        return out
-    return wrapped
+def _standalone(dev, fn, *a):
+    """run `fn` as a step of its own on `dev`: no plan, no arena"""
+    _STEP.begin(dev)
+    out = fn(*a)
+    _STEP.bump_nbt()
+    return out
 
 
 def encoder_call(enc, x, t, y=None, cond_img=None, lsm_cond=None, topo_cond=None):
@@ -1345,7 +1338,7 @@ def encoder_call(enc, x, t, y=None, cond_img=None, lsm_cond=None, topo_cond=None
     f = lambda v: None if v is None else N.f32c(v.to(x.device))   # noqa: E731
     t = N.f32c(t.to(x.device).view(-1))
     yl = None if y is None else y.to(x.device).long().contiguous()
-    fm = _standalone(encoder_forward)(x.device, enc, f(x), t, yl, f(cond_img), f(lsm_cond), f(topo_cond))
+    fm = _standalone(x.device, encoder_forward, enc, f(x), t, yl, f(cond_img), f(lsm_cond), f(topo_cond))
     return tuple(_ToNCHW.apply(v) for v in fm)
 
 
@@ -1390,7 +1383,7 @@ def decoder_block_call(blk, fmap, prev_fmap=None, t=None):
                 out = _attention(blk.attention, out)
             return _ToNCHW.apply(out)
         return _ToNCHW.apply(decoder_block_forward(blk, cur, skip, tt, tbd))
-    return _standalone(run)(fmap.device)
+    return _standalone(fmap.device, run)
 
 
 def decoder_call(dec, *fmaps, t=None):
@@ -1403,4 +1396,4 @@ def decoder_call(dec, *fmaps, t=None):
         a = decoder_forward(dec, nh, tt)
         fin = dec.final_layer
         return Cout1Fn.apply(a, fin.conv.weight, fin.conv.bias, None, 0.0)
-    return _standalone(run)(fmaps[0].device)
+    return _standalone(fmaps[0].device, run)

@@ -136,7 +136,8 @@ class TrainingPipeline_general:
     def _graph_step(self, samples, soft=False):
         """`training.use_hip_graph: true` — loss_fn + backward of one step replayed as a hipGraph (torch.cuda.graphs over the
         C-ABI launches): the ~700 launches of a step cost one host call.  The batch is copied into static input tensors; the
-        first batch of a new shape runs 2 eager warm-up steps' worth of launches (tile tuning, weight-pack plan) and captures.
+        first batch of a new shape runs 3 eager warm-up steps (tile tuning, then the weight-pack plan settles; 1 more on auto
+        mode's retry) and captures.
         Gradients land in the parameters' (static) .grad tensors exactly as after loss.backward()."""
         x, seasons, cond, _lsm_hr, lsm, sdf, topo, _hp, _lp = self._extract(samples, "train")
         live = [x, seasons, cond, lsm, topo, sdf if self.sdf_weighted_loss else None]
@@ -275,24 +276,26 @@ class TrainingPipeline_general:
             raise ValueError("training.sync_batchnorm needs host-driven collectives between kernel halves and cannot run inside a captured "
                              "step: set training.use_hip_graph: false (or sync_batchnorm: false)")
         prev_overlap = train_graph.set_overlap_bucket(self._bucket if not use_graph else None)
-        for idx, samples in enumerate(dataloader):
-            step = self._graph_step(samples, soft=auto) if use_graph else None
-            if step is not None:
-                x, batch_loss = step
-            else:
-                use_graph = False                           # (auto mode: a failed capture switches the rest of the run to eager steps)
-                self.optimizer.zero_grad()
-                x, batch_loss = self._loss(samples)
-                batch_loss.backward()
-            if self.extreme_enabled and idx % self.extreme_every_step == 0:
-                self._check_ground_truth(x)
-            if self._bucket is not None:
-                self._bucket.all_reduce_(average=not fold)   # the exchange step of the path (its decoder part started inside backward)
-            self.optimizer.step()
-            if ema_after_step:
-                self.ema.update()
-            meter.add(batch_loss)
-        train_graph.set_overlap_bucket(prev_overlap)
+        try:
+            for idx, samples in enumerate(dataloader):
+                step = self._graph_step(samples, soft=auto) if use_graph else None
+                if step is not None:
+                    x, batch_loss = step
+                else:
+                    use_graph = False                           # (auto mode: a failed capture switches the rest of the run to eager steps)
+                    self.optimizer.zero_grad()
+                    x, batch_loss = self._loss(samples)
+                    batch_loss.backward()
+                if self.extreme_enabled and idx % self.extreme_every_step == 0:
+                    self._check_ground_truth(x)
+                if self._bucket is not None:
+                    self._bucket.all_reduce_(average=not fold)   # the exchange step of the path (its decoder part started inside backward)
+                self.optimizer.step()
+                if ema_after_step:
+                    self.ema.update()
+                meter.add(batch_loss)
+        finally:                                            # (a loader or capture error must not leave this pipeline's bucket active)
+            train_graph.set_overlap_bucket(prev_overlap)
         avg = meter.flush() / max(1, len(dataloader))
         if verbose:
             logger.info(f"→ Epoch {current_epoch}/{epochs} completed: Avg. training Loss: {avg:.4f}")

@@ -378,6 +378,70 @@ def test_sync_batchnorm_refuses_captured_steps(monkeypatch):
         pipe.train_batches([], epochs=1, verbose=False)
 
 
+def test_overlap_bucket_is_restored_when_the_epoch_raises():
+    """train_batches switches the process-global overlap bucket to its own for the epoch: a loader error must not leave it there
+    (the next grad-enabled forward of any model would start an unmatched asynchronous all-reduce)"""
+    from sbgm_danra_amd import train_graph, training
+    pipe = training.TrainingPipeline_general.__new__(training.TrainingPipeline_general)
+    pipe.cfg = {"training": {"use_hip_graph": False}}
+    pipe.device = "cpu"
+    pipe.model = nn.Linear(2, 2)
+    pipe._bucket, pipe.ema = object(), None
+    pipe.optimizer = torch.optim.SGD(pipe.model.parameters(), lr=0.1)
+    seen = []
+
+    class Loader:
+        def __iter__(self):
+            seen.append(train_graph._OVERLAP_BUCKET[0])
+            raise OSError("loader")
+    before = object()
+    prev = train_graph.set_overlap_bucket(before)
+    try:
+        with pytest.raises(OSError, match="loader"):
+            pipe.train_batches(Loader(), epochs=1, verbose=False)
+        assert seen == [pipe._bucket] and train_graph._OVERLAP_BUCKET[0] is before
+    finally:
+        train_graph.set_overlap_bucket(prev)
+
+
+def test_scratch_pool_capture_rules_on_a_host_tensor():
+    """train_graph._Pool on a CPU tensor (its zeroing falls back to Tensor.zero_ off the device): alignment, exhaustion, and the two
+    rules a captured step depends on: once a capture was seen the whole high-water prefix is re-zeroed, and under capture
+    the usable extent is the high-water mark"""
+    from sbgm_danra_amd.train_graph import _Pool
+    pool = _Pool(torch.zeros(1024))
+    base = pool.buf.data_ptr()
+    a, za = pool.take(10)
+    b, zb = pool.take(100)
+    assert za and zb and a.numel() == 10 and b.numel() == 100
+    assert a.data_ptr() == base and b.data_ptr() == base + 64 * 4 and pool.off == pool.high_water == 192     # 64-float aligned
+    big, zbig = pool.take(1024)                                  # does not fit any more: a fresh zeroed tensor, the pool untouched
+    assert not zbig and big.numel() == 1024 and not big.any() and pool.off == 192
+    assert not base <= big.data_ptr() < base + 4096
+    a.fill_(1.0), b.fill_(2.0)                                   # the step's kernels accumulate into their slices
+    pool.rezero(False)
+    assert pool.buf.data_ptr() == base and not pool.buf.any() and pool.off == 0 and pool.extent == 1024
+    # a shorter step, while something else (the replay of a captured longer step) dirties the rest of the high-water prefix
+    pool.take(10)
+    pool.buf[:192] = 3.0
+    pool.rezero(False)
+    assert pool.high_water == 192 and not pool.buf[:64].any() and bool((pool.buf[64:192] == 3.0).all())    # no capture seen: last step only
+    pool.replayed = True
+    pool.take(10)
+    pool.buf[:192] = 3.0
+    pool.rezero(False)
+    assert not pool.buf.any()                                    # the whole high-water prefix
+    pool.replayed = False
+    pool.take(10)
+    pool.rezero(True)                                            # under capture
+    assert pool.replayed and pool.extent == pool.high_water == 192
+    c, zc = pool.take(128)
+    d, zd = pool.take(100)                                       # past the extent the capture zeroes: never a slice of the pool
+    assert zc and not zd and pool.off == 128 and not base <= d.data_ptr() < base + 4096
+    pool.rezero(False)
+    assert pool.extent == 1024 and pool.replayed
+
+
 # ---- full-domain tiles over ranks (stub sampler) ---------------------------------------------------------------------------
 def _stub_tiles(idx):                                # a tile's result depends on its index only (as with per-tile Langevin norms)
     return torch.stack([torch.full((1, 4, 4), float(i + 1)) * torch.arange(16.).view(1, 4, 4) for i in idx])

@@ -467,3 +467,81 @@ def test_stem_conv_phase_decomposed_data_gradient(B, Cin, Cout, H):
     ph = ph.cpu().view(2, 2, Cin, Cout, 5, 5)
     assert torch.equal(ph[0, 0, :, :, 0, 0], w[:, :, 7, 7].t()) and torch.equal(ph[1, 1, :, :, 4, 4], w[:, :, 0, 0].t())
     assert float(ph[0, :, :, :, 4, :].abs().max()) == 0.0 and float(ph[1, :, :, :, 0, :].abs().max()) == 0.0
+
+
+# ---- the step object (train_graph._Step): one place resets the per-step state ---------------------------------------------
+def _attn_block():
+    """the smallest block that has gradient slots: two slots of two consumers each, S = 16 tokens"""
+    import sbgm_danra_amd as S
+    torch.manual_seed(3)
+    return S.ImageSelfAttention(64, 4).cuda().train(), leaf(rnd(2, 4, 4, 64), True)
+
+
+@pytest.mark.parametrize("hook_on", ["output", "input"])
+def test_a_failed_backward_does_not_disable_the_slot_check(hook_on):
+    """autograd drops the queued end-of-backward callback of a pass that raises; the next step must queue it again, or partial
+    sums parked in a slot are lost silently.  `output`: the pass fails before any slot was touched; `input`: after every slot
+    was (the callback was queued by then: the case that left the check off for good before _Step.begin reset the flag)."""
+    blk, x = _attn_block()
+    T._STEP.begin(x.device)
+    out = T._attention(blk, x)
+
+    def boom(g):
+        raise RuntimeError("boom")                           # host-side: no kernel is involved
+    (out if hook_on == "output" else x).register_hook(boom)
+    with pytest.raises(RuntimeError, match="boom"):
+        out.sum().backward()
+    T._STEP.begin(x.device)
+    tok = leaf(rnd(32, 64, seed=1), True)
+    slot = T._slot(2)                                        # tok feeds the LayerNorm and the residual of the projection
+    n1 = T.LayerNormFn.apply(tok, blk.ln1.weight, blk.ln1.bias, blk.ln1.eps, slot)
+    h = T.linear(n1.detach(), blk.mha.out_proj.weight, blk.mha.out_proj.bias, res=tok, rslot=slot)
+    assert h.requires_grad
+    with pytest.raises(RuntimeError, match=r"gradient slot\(s\) were left incomplete"):
+        n1.sum().backward()                                  # reaches one of the slot's two consumers
+
+
+def test_standalone_calls_do_not_accumulate_state(monkeypatch):
+    """decoder block 1 of the 64x64 model on its own (256 -> 128 channels, 4x4 -> 8x8, attention), 20 calls with backward: the step
+    holds the slots of ONE call, and no weight-pack plan is active inside a stand-alone call"""
+    import sbgm_danra_amd as S
+    torch.manual_seed(5)
+    blk = S.DecoderBlock(256, 128, 256, activation=torch.nn.SiLU, compute_attn=True, n_heads=4, norm="group", gn_groups=8).cuda().train()
+    x, skip, t = leaf(rnd(4, 256, 4, 4), True), rnd(4, 128, 8, 8, seed=1).cuda(), torch.tensor([0.1, 0.4, 0.6, 0.9]).cuda()
+    plans, attention = [], T._attention
+    monkeypatch.setattr(T, "_attention", lambda mod, h: (plans.append(T._STEP.plan), attention(mod, h))[1])
+    counts = []
+    for _ in range(20):
+        blk(x, skip, t).square().mean().backward()
+        counts.append(len(T._STEP.slots))
+    assert counts[0] == 2 and counts[-1] == counts[0], counts
+    assert plans == [None] * 20
+    assert torch.isfinite(x.grad).all()
+
+
+def test_a_step_after_a_standalone_call_is_a_clean_step():
+    """whole step, stand-alone encoder call with its own backward, whole step again: the second whole step computes what the
+    first did (the bound of test_gpu_graph_replay.test_whole_training_step_replays_identically; the loss bit for bit)"""
+    import sbgm_danra_amd as S
+    _, net, _ = build_pair(1)
+    net.train()
+    gen = torch.Generator().manual_seed(1)
+    x, cond = torch.randn(2, 1, 64, 64, generator=gen).cuda(), torch.randn(2, 1, 64, 64, generator=gen).cuda()
+    t, z = (torch.rand(2, generator=gen) * 0.9 + 0.05).cuda(), torch.randn(2, 1, 64, 64, generator=gen).cuda()
+    params = list(net.parameters())
+
+    def step():
+        for p in params:
+            p.grad = None
+        loss = S.loss_fn(net, x, S.marginal_prob_std_fn, cond_img=cond, noise=(t, z))
+        loss.backward()
+        return loss.detach().clone(), [None if p.grad is None else p.grad.clone() for p in params]
+    loss1, g1 = step()
+    sum(f.square().mean() for f in net.encoder(x, t, cond_img=cond)).backward()
+    loss2, g2 = step()
+    assert torch.equal(loss1, loss2), (float(loss1), float(loss2))
+    names = [k for k, _ in net.named_parameters()]
+    assert [g is None for g in g1] == [g is None for g in g2]
+    bad = [(k, float((b - a).abs().max() / a.abs().max())) for k, a, b in zip(names, g1, g2)
+           if a is not None and not float((b - a).abs().max() / a.abs().max()) < 1e-4]
+    assert not bad, bad[:4]
