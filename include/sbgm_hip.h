@@ -649,6 +649,42 @@ int64_t sbgm_radial_spectrum_workspace_bytes(int H, int W);
 int sbgm_radial_spectrum(const float* power, const unsigned char* field_ok, int F, int H, int W, double* psd, int64_t* bin_count,
                          int64_t* n_fields, void* workspace, void* stream);
 
+/* ---- neighbourhood and threshold scores (verify_spatial.hip) -----------------------------------
+ * Validity and masks as above; an event is v >= thr in fp32 at a valid pixel.  `thresholds` (T finite values) and `scales`
+ * (S odd window widths n >= 1, in pixels) are HOST arrays; every other pointer is device memory.  All counts are integers,
+ * so the outputs are exact and bitwise reproducible; the only atomics are 64-bit integer adds.
+ *
+ * sbgm_neighbourhood_scores: gen [N][H][W] against obs [No][H][W], mask [Nm][H][W] or NULL.  With I_g, I_o the event
+ * images of field f at threshold t and C_g, C_o their sums over the n x n window around each of the H*W centres (zero beyond
+ * the domain, never renormalised), num [N][T][S] = sum (C_g - C_o)^2 and den [N][T][S] = sum (C_g^2 + C_o^2): the Fractions
+ * Skill Score's numerator and denominator without their common factor n^-4.  events_gen, events_obs [N][T] = sum I;
+ * valid [N] = valid pixels.  fss_field fp64 [N][T][S] = 1 - num / den; fss fp64 [T][S] = 1 - (sum_f num) / (sum_f den), the
+ * sums in fp64 in field order; both NaN where den is 0.  freq_bias fp64 [T] = sum events_gen / sum events_obs; fss_useful
+ * fp64 [T] = 0.5 + (sum events_obs / sum valid) / 2.  The cost per (field, threshold, width) is O(H*W) whatever the width.
+ * Limits: sides 2..2048, H*W <= 2^20 (so den <= 2^61 and a window count fits 32 bits), N <= 65535.  The fields are
+ * processed in chunks, stream-ordered, so that the workspace never exceeds `workspace_bytes`;
+ * sbgm_neighbourhood_scores_workspace_bytes gives the size to allocate for a cap of max_bytes (at least one field x one
+ * threshold, at most all of them).  sbgm_neighbourhood_scores_strip_columns: columns one workgroup of the window pass owns. */
+#define SBGM_SPATIAL_MAX_THRESHOLDS 16
+#define SBGM_SPATIAL_MAX_SCALES 16
+int sbgm_neighbourhood_scores_strip_columns(void);
+int64_t sbgm_neighbourhood_scores_workspace_bytes(int N, int H, int W, int T, int S, int64_t max_bytes);
+int sbgm_neighbourhood_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
+                              const float* thresholds, int T, const int* scales, int S, int64_t* num, int64_t* den,
+                              int64_t* events_gen, int64_t* events_obs, int64_t* valid, double* fss, double* fss_field,
+                              double* freq_bias, double* fss_useful, void* workspace, int64_t workspace_bytes, void* stream);
+/* sbgm_exceedance_scores: members ens [M][HW] (2 <= M <= 4095), truth obs [HW], mask [HW] or NULL; a pixel with any NaN
+ * member is invalid.  Per threshold t and valid pixel, k = #{members >= thr} and o = [obs >= thr]: table int64 [T][M+1][2]
+ * (overwritten), table[t][k][0] = pixels with that k, table[t][k][1] = those of them with o = 1 (the reliability diagram).
+ * count int64 [1] = valid pixels.  scores fp64 [6][T], from the table alone with p_k = k / M: Brier score, Murphy's
+ * reliability, resolution and uncertainty over the M + 1 probability values (reliability - resolution + uncertainty = Brier),
+ * base rate, and the ROC area (trapezoids over the M + 1 cut-offs; NaN when the event never or always occurs).  No valid
+ * pixel gives NaN.  The table is accumulated in place, so the workspace query returns 0 and `workspace` may be NULL. */
+int64_t sbgm_exceedance_scores_workspace_bytes(int M, int64_t HW, int T);
+int sbgm_exceedance_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
+                           const float* thresholds, int T, int64_t* table, int64_t* count, double* scores, void* workspace,
+                           void* stream);
+
 /* ---- before the network ------------------------------------------------------------------------
  * Batch-level condition assembly: channel concatenation of the sorted *_lr fields (utils.py:441-447), classifier-free-
  * guidance condition dropout (data_modules.py:957-983: LR fields -> 0, class label -> NULL token 0) and the value||mask

@@ -203,6 +203,12 @@ SIGNATURES = {
     "sbgm_ensemble_scores": (_i, [_vp, _vp, _vp, _i, _i, _i64, _u64] + [_vp] * 8),
     "sbgm_radial_spectrum_workspace_bytes": (_i64, [_i, _i]),
     "sbgm_radial_spectrum": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sbgm_neighbourhood_scores_strip_columns": (_i, []),
+    "sbgm_neighbourhood_scores_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i64]),
+    "sbgm_neighbourhood_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _i, C.POINTER(_i), _i] + [_vp] * 10 +
+                                  [_i64, _vp]),
+    "sbgm_exceedance_scores_workspace_bytes": (_i64, [_i, _i64, _i]),
+    "sbgm_exceedance_scores": (_i, [_vp, _vp, _vp, _i, _i, _i64, C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 4          # include/sbgm_hip.h: sbgm_abi_version()

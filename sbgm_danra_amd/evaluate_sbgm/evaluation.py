@@ -1,7 +1,9 @@
 """`Evaluation` — the statistics half of reference sbgm/evaluate_sbgm/evaluation.py:15-444, on the device.  Reads the npz
 files `SampleGenerator` writes, moves them to the GPU once, and computes every statistic with the verification kernels
-(csrc/verify.hip via `..verification`): the reference's pixel, spatial and daily statistics plus ensemble scores (CRPS, rank
-histogram, spread/skill) and radially averaged power spectra.  Only scalars, maps and histograms come back to the host.
+(csrc/verify.hip and csrc/verify_spatial.hip via `..verification`): the reference's pixel, spatial and daily statistics plus
+ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra and, on request, neighbourhood scores
+(Fractions Skill Score) and threshold-exceedance scores (Brier, reliability table, ROC area).  Only scalars, maps and
+histograms come back to the host.
 Plots are out of scope: the plotting keys are accepted and logged as skipped.
 
 Files are found by name: `gen_samples_*`, `eval_samples_*` and `lsm_samples_*` with the suffixes `multi_n_<B>`, `single`,
@@ -12,6 +14,7 @@ from __future__ import annotations
 
 import json
 import logging
+import math
 import os
 import re
 
@@ -96,6 +99,24 @@ def statistics_dir(cfg):
     paths = cfg["paths"]
     base = paths.get("evaluation_dir") or os.path.join(paths["sample_dir"], "evaluation")
     return os.path.join(base, get_model_string(cfg), "statistics")
+
+
+def spatial_scores_config(cfg):
+    """(thresholds, scales) of the optional evaluation.spatial_scores section — thresholds in the units the generated files
+    hold, scales as odd window widths in pixels — or None when the section is absent"""
+    sec = cfg["evaluation"].get("spatial_scores")
+    if sec is None:
+        return None
+    thresholds, scales = sec.get("thresholds"), sec.get("scales")
+    if not isinstance(thresholds, (list, tuple)) or not isinstance(scales, (list, tuple)) or not thresholds or not scales:
+        raise ValueError("evaluation.spatial_scores needs non-empty lists 'thresholds' and 'scales'")
+    if len(thresholds) > 16 or len(scales) > 16:
+        raise ValueError(f"evaluation.spatial_scores: at most 16 thresholds and 16 scales, got {len(thresholds)} and {len(scales)}")
+    if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) for t in thresholds):
+        raise ValueError(f"evaluation.spatial_scores.thresholds must be finite numbers, got {list(thresholds)}")
+    if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 or n % 2 == 0 for n in scales):
+        raise ValueError(f"evaluation.spatial_scores.scales must be odd integers >= 1 (window widths in pixels), got {list(scales)}")
+    return [float(t) for t in thresholds], [int(n) for n in scales]
 
 
 class Evaluation:
@@ -228,6 +249,54 @@ class Evaluation:
         out = {"skipped_gen": int(sg), "skipped_obs": int(so), "n_wavenumbers": int(res["wavenumber"].shape[0])}
         self.metrics["spectral_stats"] = out
         self.fields.update({f"spectral_{k}": v for k, v in res.items()})
+        return dict(res, metrics=out)
+
+    def _spatial_scores(self, thresholds, scales=None):
+        """the given thresholds / scales, each defaulting to the evaluation.spatial_scores section of the config"""
+        if thresholds is not None and scales is not None:
+            return thresholds, scales
+        sec = spatial_scores_config(self.cfg)
+        if sec is None:
+            raise ValueError("no thresholds / scales given and the config has no evaluation.spatial_scores section")
+        return (sec[0] if thresholds is None else thresholds), (sec[1] if scales is None else scales)
+
+    def neighbourhood_statistics(self, thresholds=None, scales=None):
+        """Fractions Skill Score over thresholds x odd window widths (pixels) of the generated fields against their truth:
+        the fss matrix, the frequency bias, the useful-skill level 0.5 + f_o/2 and, per threshold, the smallest width
+        that reaches it; the exact integer numerators, denominators and event counts go to the fields file"""
+        thresholds, scales = self._spatial_scores(thresholds, scales)
+        r = V.neighbourhood_scores(self.gen_imgs, self.eval_imgs, thresholds, scales, mask=self.mask)
+        res = {k: r[k].cpu().numpy() for k in V.NEIGHBOURHOOD_KEYS}
+        thresholds, scales = [float(t) for t in thresholds], [int(n) for n in scales]
+        useful = []
+        for t in range(len(thresholds)):
+            ok = [n for n, f in zip(scales, res["fss"][t]) if f >= res["fss_useful"][t]]          # NaN compares false
+            useful.append(min(ok) if ok else None)
+        out = {"thresholds": thresholds, "scales": scales, "fss": res["fss"].tolist(), "freq_bias": res["freq_bias"].tolist(),
+               "fss_useful": res["fss_useful"].tolist(), "useful_scale": useful, "valid": int(res["valid"].sum()),
+               "definition": "fss = 1 - sum (C_gen - C_obs)^2 / sum (C_gen^2 + C_obs^2); C = events (v >= threshold) in the "
+                             "n x n window, zero beyond the domain"}
+        self.metrics["neighbourhood_stats"] = out
+        self.fields.update({f"neighbourhood_{k}": res[k] for k in ("num", "den", "fss_field", "events_gen", "events_obs")})
+        return dict(res, metrics=out)
+
+    def exceedance_statistics(self, thresholds=None):
+        """Brier score with Murphy's reliability / resolution / uncertainty, base rate and ROC area per threshold of the
+        `repeated` samples as an ensemble forecasting P(value >= threshold); the table behind them (the reliability
+        diagram) goes to the fields file"""
+        if self.generated_sample_type != "repeated":
+            raise ValueError(f"exceedance_statistics needs 'repeated' samples (an ensemble for one condition), not "
+                             f"'{self.generated_sample_type}'")
+        if self.n_samples < 2:
+            raise ValueError(f"exceedance_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        thresholds, _ = self._spatial_scores(thresholds, scales=[1])
+        mask = None if self.mask is None else self.mask[0]
+        r = V.exceedance_scores(self.gen_imgs, self.eval_imgs[0], thresholds, mask=mask)
+        res = {k: r[k].cpu().numpy() for k in ("table",) + V.EXCEEDANCE_KEYS}
+        out = {"thresholds": [float(t) for t in thresholds], "M": self.n_samples, "count": int(r["count"])}
+        out.update({k: res[k].tolist() for k in V.EXCEEDANCE_KEYS})
+        self.metrics["exceedance_stats"] = out
+        self.fields["exceedance_table"] = res["table"]
         return dict(res, metrics=out)
 
     def save(self):

@@ -1,7 +1,9 @@
 """`evaluation_main(cfg)` — reference sbgm/evaluate_sbgm/evaluation_main.py:45-111: seed from evaluation.seed, then for every
 generation type in evaluation.eval_gen_type (default: evaluation.gen_type, then ['multiple']) run the methods of
 evaluation.eval_stat_methods (default ['pixel_stats', 'spatial_stats'], as in the reference) and write each unit's
-`<type>[_rank<r>]_metrics.json` / `_fields.npz`.  Plotting keys are accepted and logged as skipped."""
+`<type>[_rank<r>]_metrics.json` / `_fields.npz`.  Plotting keys are accepted and logged as skipped.  An
+`evaluation.spatial_scores` section (thresholds, scales) adds the neighbourhood scores for every type and the exceedance
+scores for `repeated`; without it neither runs and the output files hold what they always held."""
 from __future__ import annotations
 
 import os
@@ -11,10 +13,11 @@ import torch
 
 from ..training_utils import setup_logger
 from ..utils import get_model_string
-from .evaluation import GEN_TYPES, Evaluation, sample_units
+from .evaluation import GEN_TYPES, Evaluation, sample_units, spatial_scores_config
 
 METHODS = {"pixel_stats": "full_pixel_statistics", "spatial_stats": "spatial_statistics", "daily_stats": "daily_statistics",
            "ensemble_stats": "ensemble_statistics", "spectral_stats": "spectral_statistics"}
+SPATIAL_METHODS = {"neighbourhood_stats": "neighbourhood_statistics", "exceedance_stats": "exceedance_statistics"}
 PLOT_KEYS = ("plot_examples", "save_figs", "show_plots", "show_figs", "mask_plots", "plot_w_cond", "plot_w_lsm")
 
 
@@ -35,6 +38,15 @@ def eval_stat_methods(cfg):
     return methods
 
 
+def unit_statistics(cfg, gen_type):
+    """the statistics evaluate mode runs for one generation type, in order: evaluation.eval_stat_methods, then — only with an
+    evaluation.spatial_scores section — 'neighbourhood_stats' and, for 'repeated', 'exceedance_stats'"""
+    stats = eval_stat_methods(cfg)
+    if spatial_scores_config(cfg) is not None:
+        stats += ["neighbourhood_stats"] + (["exceedance_stats"] if gen_type == "repeated" else [])
+    return stats
+
+
 def n_samples_of(cfg, gen_type):
     ev = cfg["evaluation"]
     return {"multiple": ev.get("batch_size"), "single": 1, "repeated": ev.get("n_repeats")}[gen_type]
@@ -47,7 +59,8 @@ def evaluation_main(cfg):
     torch.manual_seed(seed)
     torch.cuda.manual_seed(seed)
     np.random.seed(seed)
-    types, methods = eval_gen_types(cfg), eval_stat_methods(cfg)       # both validated before any file is read
+    types = eval_gen_types(cfg)
+    methods = {t: unit_statistics(cfg, t) for t in types}             # all validated before any file is read
     model_name_str = get_model_string(cfg)
     log = setup_logger(os.path.join(cfg["paths"]["sample_dir"], "generation", model_name_str, "logs"), name="eval_log")
     skipped = [k for k in PLOT_KEYS if ev.get(k, False)]
@@ -60,8 +73,11 @@ def evaluation_main(cfg):
         for rank, _ in sample_units(sample_dir, gen_type, n):
             runner = Evaluation(cfg, generated_sample_type=gen_type, n_samples=n, rank=rank)
             log.info(f"[INFO] Running evaluation for {runner.label}")
-            for method in methods:
+            for method in methods[gen_type]:
                 log.info(f"[INFO] Running evaluation method: {method}")
+                if method in SPATIAL_METHODS:
+                    getattr(runner, SPATIAL_METHODS[method])()
+                    continue
                 fn = getattr(runner, METHODS[method])
                 if method in ("pixel_stats", "spatial_stats"):
                     fn(save_stats=bool(ev.get("save_stats", False)), n_samples=n if n is not None else runner.n_samples)

@@ -1,5 +1,6 @@
-"""Device-tensor wrappers of the verification kernels (csrc/verify.hip): error statistics, histograms,
-ensemble scores (CRPS, rank histogram, spread/skill) and radially averaged power spectra.  Every function takes tensors on
+"""Device-tensor wrappers of the verification kernels (csrc/verify.hip and csrc/verify_spatial.hip): error
+statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra, neighbourhood
+scores (Fractions Skill Score) and threshold-exceedance scores (Brier, reliability table, ROC area).  Every function takes tensors on
 the ROCm device and returns tensors on the device; arguments and shapes are checked before any launch and nothing is copied
 to the host.  A pixel is valid when gen (every member) and obs are not NaN and the mask admits it (uint8/bool != 0, or float
 > 0.5); every statistic uses the valid pixels only."""
@@ -7,10 +8,19 @@ from __future__ import annotations
 
 import torch
 
+import ctypes as C
+import math
+
 from . import _native as N
 
 GLOBAL_KEYS = ("count", "mean_gen", "mean_obs", "bias", "mae", "rmse", "min_gen", "max_gen", "min_obs", "max_obs")
 ENSEMBLE_KEYS = ("count", "crps_fair", "crps_standard", "skill", "spread", "spread_skill_ratio")
+NEIGHBOURHOOD_KEYS = ("num", "den", "events_gen", "events_obs", "valid", "fss", "fss_field", "freq_bias", "fss_useful")
+EXCEEDANCE_KEYS = ("brier", "brier_reliability", "brier_resolution", "brier_uncertainty", "base_rate", "roc_area")
+MAX_THRESHOLDS = MAX_SCALES = 16                 # include/sbgm_hip.h: SBGM_SPATIAL_MAX_THRESHOLDS / _SCALES
+MAX_FIELD_SIDE, MAX_FIELD_PIXELS = 2048, 1 << 20
+MAX_EXCEEDANCE_MEMBERS = 4095
+DEFAULT_WORKSPACE_BYTES = 256 << 20
 
 
 def _rows(t, name, HW, allowed):
@@ -161,3 +171,110 @@ def rapsd(fields):
     N.check(N.lib().sbgm_radial_spectrum(power.data_ptr(), okb.data_ptr(), F, H, W, psd.data_ptr(), cnt.data_ptr(), nf.data_ptr(),
                                          ws.data_ptr(), N.stream()))
     return torch.arange(nb, device=x.device), psd, F - nf[0]
+
+
+def _thresholds(thresholds, name):
+    """1..16 finite thresholds as a host float array (fp32: the comparison is `v >= thr` in fp32)"""
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= MAX_THRESHOLDS:
+        raise ValueError(f"{name}: {len(thr)} thresholds; need 1..{MAX_THRESHOLDS}")
+    arr = (C.c_float * len(thr))(*thr)
+    if not all(math.isfinite(t) and math.isfinite(a) for t, a in zip(thr, arr)):
+        raise ValueError(f"{name}: thresholds must be finite in fp32, got {thr}")
+    return arr
+
+
+def _scales(scales, name):
+    """1..16 odd window widths >= 1 as a host int array"""
+    sc = list(scales)
+    if not 1 <= len(sc) <= MAX_SCALES:
+        raise ValueError(f"{name}: {len(sc)} window widths; need 1..{MAX_SCALES}")
+    for n in sc:
+        if isinstance(n, bool) or int(n) != n or int(n) < 1 or int(n) % 2 == 0 or int(n) >= 2**31:
+            raise ValueError(f"{name}: window widths must be odd integers >= 1, got {sc}")
+    return (C.c_int * len(sc))(*(int(n) for n in sc))
+
+
+def _shape_rows(t, name, hw, allowed):
+    """shape check of an optional [rows, H, W] (or [H, W]) argument, before anything touches the device"""
+    if t is None:
+        return
+    shape = tuple(t.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[1:] != tuple(hw):
+        raise ValueError(f"{name}: shape {tuple(t.shape)} does not hold fields of {hw[0]}x{hw[1]} pixels")
+    if shape[0] not in allowed:
+        raise ValueError(f"{name}: {shape[0]} fields; expected one of {sorted(set(allowed))}")
+
+
+def neighbourhood_strip_columns():
+    """columns one workgroup of the neighbourhood window pass owns (fields wider than this are walked in several strips)"""
+    return int(N.lib().sbgm_neighbourhood_scores_strip_columns())
+
+
+def neighbourhood_scores(gen, obs, thresholds, scales, mask=None, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+    """Fractions Skill Score (Roberts & Lean 2008) ingredients of gen [N,H,W] against obs [No,H,W] (No in {1, N}), optional
+    mask [Nm,H,W] (Nm in {1, N}), for T thresholds (event: v >= thr in fp32 at a valid pixel) and S odd window widths n.
+    With C_g, C_o the event counts in the n x n window around each of the H*W centres (zero beyond the domain, never
+    renormalised): `num` = sum (C_g - C_o)^2 and `den` = sum (C_g^2 + C_o^2), int64 [N,T,S], exact; `events_gen`, `events_obs`
+    int64 [N,T]; `valid` int64 [N]; `fss_field` fp64 [N,T,S] = 1 - num/den; `fss` fp64 [T,S] = 1 - sum_f num / sum_f den (NaN
+    where den is 0); `freq_bias` fp64 [T] = sum events_gen / sum events_obs; `fss_useful` fp64 [T] = 0.5 + f_o/2 with f_o the
+    observed event frequency.  The fields are processed in chunks whose workspace stays within `max_workspace_bytes` (at
+    least one field x one threshold); the result does not depend on the chunking."""
+    thr, sc = _thresholds(thresholds, "neighbourhood_scores"), _scales(scales, "neighbourhood_scores")
+    if gen.dim() != 3:
+        raise ValueError(f"gen: expected [N, H, W], got {tuple(gen.shape)}")
+    n, H, W = gen.shape
+    if not (2 <= H <= MAX_FIELD_SIDE and 2 <= W <= MAX_FIELD_SIDE) or H * W > MAX_FIELD_PIXELS:
+        raise ValueError(f"neighbourhood_scores: field size {H}x{W}; sides must be 2..{MAX_FIELD_SIDE} and H*W <= 2^20")
+    if not 1 <= n <= 65535:
+        raise ValueError(f"neighbourhood_scores: {n} fields; need 1..65535")
+    _shape_rows(obs, "obs", (H, W), (1, n))
+    _shape_rows(mask, "mask", (H, W), (1, n))
+    g = _fields(gen, "gen")
+    HW = H * W
+    o = _fields(obs, "obs")
+    if o.device != g.device:
+        raise ValueError("gen and obs must be on the same device")
+    m, u8, nm = _mask(mask, HW, (1, n))
+    T, S, dev = len(thr), len(sc), g.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = dict(num=torch.empty(n, T, S, **i64), den=torch.empty(n, T, S, **i64), events_gen=torch.empty(n, T, **i64),
+               events_obs=torch.empty(n, T, **i64), valid=torch.empty(n, **i64), fss=torch.empty(T, S, **f64),
+               fss_field=torch.empty(n, T, S, **f64), freq_bias=torch.empty(T, **f64), fss_useful=torch.empty(T, **f64))
+    nbytes = N.lib().sbgm_neighbourhood_scores_workspace_bytes(n, H, W, T, S, max(int(max_workspace_bytes), 0))
+    ws = _ws(nbytes, dev)
+    N.check(N.lib().sbgm_neighbourhood_scores(g.data_ptr(), o.data_ptr(), N.ptr(m), u8, n, o.shape[0], nm, H, W, thr, T, sc, S,
+                                              *(out[k].data_ptr() for k in NEIGHBOURHOOD_KEYS), ws.data_ptr(), nbytes, N.stream()))
+    return out
+
+
+def exceedance_scores(ens, obs, thresholds, mask=None):
+    """threshold-exceedance probability scores of members ens [M,H,W] (2 <= M <= 4095) against truth obs [H,W], optional mask
+    [H,W].  A pixel is valid when every member and obs are not NaN there and the mask admits it.  Per threshold and valid
+    pixel, k = #{members >= thr} and o = [obs >= thr].  Returns device tensors: `table` int64 [T, M+1, 2] (pixels with that k;
+    those of them with o = 1 — the reliability diagram), `count` int64 scalar, and fp64 [T] `brier`, `brier_reliability`,
+    `brier_resolution`, `brier_uncertainty` (Murphy's decomposition over the M+1 probabilities p_k = k/M: reliability -
+    resolution + uncertainty = brier), `base_rate` and `roc_area` (trapezoids over the M+1 cut-offs; NaN when the event
+    never or always occurs), all computed from the table."""
+    thr = _thresholds(thresholds, "exceedance_scores")
+    if ens.dim() != 3:
+        raise ValueError(f"ens: expected [M, H, W], got {tuple(ens.shape)}")
+    M = ens.shape[0]
+    if not 2 <= M <= MAX_EXCEEDANCE_MEMBERS:
+        raise ValueError(f"exceedance_scores: M={M} members; need 2..{MAX_EXCEEDANCE_MEMBERS}")
+    _shape_rows(obs, "obs", tuple(ens.shape[1:]), (1,))
+    _shape_rows(mask, "mask", tuple(ens.shape[1:]), (1,))
+    e = _fields(ens, "ens")
+    HW = e.shape[1]
+    o = _fields(obs, "obs")
+    m, u8, _ = _mask(mask, HW, (1,))
+    T, dev = len(thr), e.device
+    table = torch.empty(T, M + 1, 2, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    scores = torch.empty(len(EXCEEDANCE_KEYS), T, dtype=torch.float64, device=dev)
+    N.check(N.lib().sbgm_exceedance_scores(e.data_ptr(), o.data_ptr(), N.ptr(m), u8, M, HW, thr, T, table.data_ptr(),
+                                           count.data_ptr(), scores.data_ptr(), None, N.stream()))
+    return dict(table=table, count=count[0], **{k: scores[i] for i, k in enumerate(EXCEEDANCE_KEYS)})
