@@ -159,6 +159,33 @@ int sbgm_sampler_run_held(sbgm_model* m, const sbgm_sampler_args* a, const float
 int sbgm_sampler_run_edm_held(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
                               float s_tmin, float s_tmax, float s_noise, const float* known, const float* known_mask, void* stream);
 
+/* Joint full-domain sampling (Mixture of Diffusers, Jimenez 2023 / MultiDiffusion, Bar-Tal et al. 2023): sbgm_sampler_run and
+ * sbgm_sampler_run_edm as ONE diffusion over a domain of domain_h x a->domain_w pixels whose B samples are ALL its tiles (a->tile_origins,
+ * in-kernel noise, one batch).  Wherever an update kernel (EM / PC predictor, Langevin corrector, EDM Euler, EDM Heun) reads the score of
+ * tile b at domain pixel P it uses
+ *     s*(P) = sum_t w_t(P) s_t(P) / sum_t w_t(P)
+ * over all tiles t of the batch that cover P, in ascending tile index with the reading tile at its own place, w_t = ramp_y * ramp_x the
+ * weight of sbgm_stitch_tiles (ramp length ramp_len = max(1, overlap), no ramp on a domain edge, taken against domain_h and a->domain_w,
+ * the padded width), accumulated in fp32 as acc += w s, wsum += w, acc / wsum.  A pixel only one tile covers uses its score unchanged
+ * (no arithmetic); any number of tiles may cover a pixel.  The initial state is equal across the copies of a domain pixel (domain-keyed
+ * draw 0) and every copy then sees the same x, the same s* computed by the same instruction sequence and the same draw, so all copies of
+ * a domain pixel are bit-equal after every kernel of every step (x_mean included) and sbgm_stitch_tiles of the result equals any copy.
+ *   Langevin corrector: the step size follows the batch-mean rule eps = 2 (snr sqrt(HW) / mean_t ||s_t||)^2 over the RAW tile scores (one
+ *               step size for the domain), not the per-tile norm of a non-joint tiled run.
+ *   EDM Heun:   d = -sigma_hat s*, so the stored slope is the blended one too.
+ *   known, known_mask: both NULL, or both given as in the _held entry points; the hold runs after the blend and sees equal inputs in
+ *               every copy when the fields were cut from domain fields.
+ *   guidance:   acts before the blend (the combined B-row score is what the update reads).
+ * Refused: no tile_origins, injected noise, bn_train, ramp_len < 1, W not a multiple of 4, an origin that is negative, has x0 % 4 != 0 or
+ * has y0 + H > domain_h or x0 + W > domain_w (the table is read back once per call, which waits for `stream`).  No launch is added to the
+ * step and no domain-sized buffer exists; the captured step's key holds the joint flag, domain_h and ramp_len, so a joint and a non-joint
+ * step never share a graph.  Everything else is as in the entry points above. */
+int sbgm_sampler_run_joint(sbgm_model* m, const sbgm_sampler_args* a, int domain_h, int ramp_len, const float* known,
+                           const float* known_mask, void* stream);
+int sbgm_sampler_run_edm_joint(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
+                               float s_tmin, float s_tmax, float s_noise, int domain_h, int ramp_len, const float* known,
+                               const float* known_mask, void* stream);
+
 /* Adaptive deterministic sampler: the probability-flow ODE dx/dt = -1/2 g(t)^2 score(x, t) integrated from t0 to t1 by
  * Dormand-Prince 5(4) with the step controller of scipy.integrate.RK45 (select_initial_step, FSAL, accept when the RMS error
  * norm is < 1, factor min(10, 0.9 err^-0.2), max(0.2, .) on rejection), entirely on the device.  a->kind must be
@@ -716,6 +743,11 @@ int sbgm_extract_tiles(const float* domain, const int* origins, float* tiles, in
                        void* stream);
 int sbgm_stitch_tiles(const float* tiles, const int* origins, float* domain, int T, int C, int Hd, int Wd, int th, int tw,
                       int ramp_len, void* stream);
+/* The score blend of a joint run (sbgm_sampler_run_joint) as an op of its own, out of place: out[t] at tile pixel p = the blend, at p's
+ * domain position, of scores[t'] over every tile t' that covers it (the same device function the fused update kernels call); a pixel
+ * only its own tile covers is copied.  scores, out: device fp32 [T][1][H][W], W % 4 == 0, x origins multiples of 4, out != scores. */
+int sbgm_blend_tile_scores(const float* scores, const int* origins, float* out, int T, int H, int W, int domain_h, int domain_w,
+                           int ramp_len, void* stream);
 
 #ifdef __cplusplus
 }

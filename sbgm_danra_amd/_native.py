@@ -83,6 +83,8 @@ SIGNATURES = {
     "sbgm_sampler_run_edm": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _vp]),
     "sbgm_sampler_run_held": (_i, [_vp, C.POINTER(SamplerArgs), _vp, _vp, _vp]),
     "sbgm_sampler_run_edm_held": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "sbgm_sampler_run_joint": (_i, [_vp, C.POINTER(SamplerArgs), _i, _i, _vp, _vp, _vp]),
+    "sbgm_sampler_run_edm_joint": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
     "sbgm_sampler_run_ode": (_i, [_vp, C.POINTER(SamplerArgs), _d, _d, _d, _d, _i, _i64, _vp, _vp, _vp, _vp]),
     "sbgm_pointwise_chain": (_i, [_vp, _vp, _i64, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     "sbgm_sample_extremes": (_i, [_vp, _i, _i64, _f, _vp, _vp, _vp]),
@@ -94,6 +96,7 @@ SIGNATURES = {
     "sbgm_tconv_weight_to_oihw": (_i, [_vp, _vp, _i, _i, _vp]),
     "sbgm_extract_tiles": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sbgm_stitch_tiles": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sbgm_blend_tile_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sbgm_model_autotune": (_i, [_vp, _i, _i, _i, _vp]),
     "sbgm_model_tune_save": (_i, [_vp, C.c_char_p]),
     "sbgm_model_tune_load": (_i, [_vp, C.c_char_p]),

@@ -248,6 +248,11 @@ int sbgm_stitch_tiles(const float* tiles, const int* origins, float* domain, int
     return sbgm_launch_stitch_tiles(tiles, origins, domain, T, C, Hd, Wd, th, tw, ramp_len, ST);
 }
 
+int sbgm_blend_tile_scores(const float* scores, const int* origins, float* out, int T, int H, int W, int domain_h, int domain_w,
+                           int ramp_len, void* stream) {
+    return sbgm_launch_blend_tile_scores(scores, out, JointMap{origins, T, H, W, domain_h, domain_w, ramp_len}, ST);
+}
+
 int sbgm_depth_to_space2(const float* x, float* y, int B, int H, int W, int C, void* stream) {
     return sbgm_launch_depth_space2(x, y, B, H, W, C, 1, ST);
 }

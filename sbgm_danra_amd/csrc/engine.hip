@@ -212,6 +212,7 @@ struct sbgm_model {
         int B, H, W, kind, guided, bn_train, domain_w, churn, ode_norm;
         const void *y, *cond, *lsm, *topo, *origins, *ws, *table;
         const void *known, *known_mask, *levels;   // constrained runs (null otherwise): a held and an unheld step never share a graph
+        int joint, domain_h, ramp_len;             // joint tiled runs (0 otherwise): a joint and a non-joint step never share a graph
         size_t ws_bytes;
         float cfg, cfg_corr, snr_nn;
         unsigned long long plan_gen;
@@ -361,7 +362,9 @@ struct sbgm_model {
     }
     struct EdmArgs { float sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise; };
     struct HeldArgs { const float *known, *mask; };        // constrained sampling: both device [B][1][H][W], used in place
-    int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr, const HeldArgs* held = nullptr);
+    struct JointArgs { int domain_h, ramp_len; };          // joint tiled sampling: the B tiles are one domain of domain_h x a.domain_w
+    int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr, const HeldArgs* held = nullptr,
+                const JointArgs* joint = nullptr);
     struct OdeArgs { double t0, t1, rtol, atol; int per_sample; long long max_steps; const float* x0; int64_t* stats_i; double* stats_d; };
     int sampler_ode(const sbgm_sampler_args& a, hipStream_t st, const OdeArgs& o);
 };
@@ -1079,9 +1082,27 @@ struct SamplerRun {
     }
 };
 
-int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm, const HeldArgs* held) {
+int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm, const HeldArgs* held,
+                        const JointArgs* joint) {
     const bool heun = edm != nullptr;                      // only sbgm_sampler_run_edm passes EDM arguments
     SBGM_CHECK(!held || (held->known && held->mask), "sampler: a constrained run needs both known and known_mask");
+    if (joint) {
+        SBGM_CHECK(a.tile_origins != nullptr, "sampler: a joint run needs tile_origins (its samples are the tiles of one domain)");
+        SBGM_CHECK(a.noise == nullptr, "sampler: a joint run draws domain-keyed in-kernel noise; it cannot take injected noise");
+        SBGM_CHECK(!a.bn_train, "sampler: a joint run serves eval-mode BatchNorm only (bn_train must be 0)");
+        SBGM_CHECK(joint->ramp_len >= 1, "sampler: joint ramp length %d must be >= 1", joint->ramp_len);
+        SBGM_CHECK(a.B >= 1 && a.W >= 4 && a.W % 4 == 0, "sampler: a joint run needs B >= 1 and W %% 4 == 0 (B=%d, W=%d)", a.B, a.W);
+        // the tile table is read back once per call (a few bytes; this waits for the stream): the blend trusts it for the ramps
+        std::vector<int> org(2 * (size_t)a.B);
+        SBGM_HIP(hipMemcpyAsync(org.data(), a.tile_origins, org.size() * sizeof(int), hipMemcpyDeviceToHost, caller));
+        SBGM_HIP(hipStreamSynchronize(caller));
+        for (int t = 0; t < a.B; ++t) {
+            const int y0 = org[2 * t], x0 = org[2 * t + 1];
+            SBGM_CHECK(y0 >= 0 && x0 >= 0 && x0 % 4 == 0 && y0 + a.H <= joint->domain_h && x0 + a.W <= a.domain_w,
+                       "sampler: joint tile %d at (%d, %d) of %d x %d does not lie quad-aligned inside the %d x %d domain", t, y0, x0, a.H,
+                       a.W, joint->domain_h, a.domain_w);
+        }
+    }
     SBGM_CHECK(heun ? a.kind == SBGM_SAMPLER_EDM_HEUN : (a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC),
                "sampler: unknown kind %d", a.kind);
     SBGM_CHECK(a.num_steps >= 2, "sampler: num_steps=%d must be >= 2 (step size = t0 - t1)", a.num_steps);
@@ -1152,6 +1173,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
 
     if (run.begin()) return 1;
     hold.nm = run.nm;
+    const JointMap jm = joint ? JointMap{a.tile_origins, B, a.H, a.W, joint->domain_h, a.domain_w, joint->ramp_len} : JointMap{};
     // slabs: x (the network input), score, x_mean, and for EDM Heun the derivative d; EDM Heun keeps its state x / x_hat in x_mean
     float *xs = run.slab_at(0), *score = run.slab_at(1), *xmean = run.slab_at(2), *dheun = heun ? run.slab_at(3) : nullptr;
     float* t_dev = run.t_vec();
@@ -1179,18 +1201,18 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
             if (churn && sbgm_launch_edm_churn(xmean, xs, z_ptrs ? next_z() : nullptr, edm_tab, d_state, nullptr, 0, a.seed, n, st, run.nm))
                 return 1;
             if (evaluate(a.cfg_scale)) return 1;
-            if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, edm_tab, d_state, nullptr, t_dev, BE, n, st, hold)) return 1;
+            if (sbgm_launch_edm_euler(xmean, score, dheun, last ? a.out : xs, edm_tab, d_state, nullptr, t_dev, BE, n, st, hold, jm)) return 1;
             if (last) return 0;
             if (evaluate(a.cfg_scale)) return 1;
-            return sbgm_launch_edm_heun(xmean, xs, dheun, score, edm_tab, d_state, nullptr, t_dev, BE, N, n, st, hold);
+            return sbgm_launch_edm_heun(xmean, xs, dheun, score, edm_tab, d_state, nullptr, t_dev, BE, N, n, st, hold, jm);
         }
         if (a.kind == SBGM_SAMPLER_PC) {
             if (evaluate(a.cfg_scale_corrector)) return 1;
-            if (sbgm_launch_langevin(xs, score, z_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, run.nm, hold)) return 1;
+            if (sbgm_launch_langevin(xs, score, z_ptrs ? next_z() : nullptr, snr_nn, sumsq, d_state, 0, a.seed, B, per, st, run.nm, hold, jm)) return 1;
         }
         if (evaluate(a.cfg_scale)) return 1;
         return sbgm_launch_em_update(xs, xmean, score, z_ptrs ? next_z() : nullptr, sde_tab, d_state, nullptr, 0, t_dev, a.seed, B,
-                                     per, N, st, BE, run.nm, hold);
+                                     per, N, st, BE, run.nm, hold, jm);
     };
     // The run: N - tail steps (replays of the captured step, or eager launches), then `tail` eager last steps.  EM / PC: no tail,
     // the result is the x_mean slab, copied to `out`; EDM Heun: the tail is its Euler-only last step, which writes `out` itself.
@@ -1201,6 +1223,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         key.churn = churn; key.domain_w = a.domain_w; key.origins = a.tile_origins; key.table = d_table;
         key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn;
         key.known = hold.known; key.known_mask = hold.mask; key.levels = hold.levels;
+        if (joint) { key.joint = 1; key.domain_h = joint->domain_h; key.ramp_len = joint->ramp_len; }
         rc = run.capture(key, [&] { return step(false, false); });
         for (int i = 0; i < N - tail && rc == 0; ++i)
             if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
@@ -1439,6 +1462,29 @@ int sbgm_sampler_run_edm_held(sbgm_model* m, const sbgm_sampler_args* a, float s
     const sbgm_model::EdmArgs e{sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise};
     const sbgm_model::HeldArgs h{known, known_mask};
     return m->sampler(*a, (hipStream_t)stream, &e, &h);
+}
+
+// The drivers above as ONE diffusion over the domain (joint tiled sampling): the same sbgm_model::sampler, the joint kernels;
+// known / known_mask may both be NULL.
+int sbgm_sampler_run_joint(sbgm_model* m, const sbgm_sampler_args* a, int domain_h, int ramp_len, const float* known,
+                           const float* known_mask, void* stream) {
+    SBGM_CHECK(a, "sampler_run_joint: null args");
+    SBGM_CHECK((known == nullptr) == (known_mask == nullptr), "sampler_run_joint: known and known_mask must be given together");
+    const sbgm_model::HeldArgs h{known, known_mask};
+    const sbgm_model::JointArgs j{domain_h, ramp_len};
+    return m->sampler(*a, (hipStream_t)stream, nullptr, known ? &h : nullptr, &j);
+}
+
+int sbgm_sampler_run_edm_joint(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float s_churn,
+                               float s_tmin, float s_tmax, float s_noise, int domain_h, int ramp_len, const float* known,
+                               const float* known_mask, void* stream) {
+    SBGM_CHECK(a, "sampler_run_edm_joint: null args");
+    SBGM_CHECK((known == nullptr) == (known_mask == nullptr), "sampler_run_edm_joint: known and known_mask must be given together");
+    if (edm_args_check(a, rho, s_churn, s_noise, sigma_min, sigma_max)) return 1;
+    const sbgm_model::EdmArgs e{sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise};
+    const sbgm_model::HeldArgs h{known, known_mask};
+    const sbgm_model::JointArgs j{domain_h, ramp_len};
+    return m->sampler(*a, (hipStream_t)stream, &e, known ? &h : nullptr, &j);
 }
 
 int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, double t1, double rtol, double atol, int per_sample,

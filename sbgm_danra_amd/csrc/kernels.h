@@ -194,6 +194,15 @@ struct NoiseMap {
     int tile_h, tile_w4;  // tile rows, tile width / 4
     int dom_w4;           // ceil(domain width / 4)
 };
+// Joint tiled sampling: the B samples are ALL T tiles of one domain, and every update kernel reads the score through the
+// partition-of-unity blend of the tiles' scores (tile_blend.h).  origins == null (the default) is the kernel without the blend.
+struct JointMap {
+    const int* origins;   // device [T][2] = (y0, x0), x0 % 4 == 0: the run's tile_origins
+    int T;                // tiles in the batch
+    int tile_h, tile_w;   // tile_w % 4 == 0
+    int dom_h, dom_w;     // the domain the ramps are taken against (dom_w: the padded width, a multiple of 4)
+    int R;                // ramp length, max(1, overlap)
+};
 // Constrained sampling: pixels with mask > 0 are held at known + level * z after each state update, in the update
 // kernel's own epilogue.  known == null (the default) is the unconstrained kernel.
 struct HoldLevels {        // noise levels a held pixel is re-noised to in an SDE step: one row per step, parallel to the step table
@@ -220,10 +229,12 @@ int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const flo
                           SamplerState* state, const StepScalars* sc_val, unsigned long long draw_index, float* t_dev,
                           unsigned long long seed, int B, size_t per_sample, int n_steps, hipStream_t st,
                           int t_entries = 0,    // entries of t_dev to refresh (0 -> B; 2B for the batched guidance pass)
-                          NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{});
+                          NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{}, const JointMap& jm = JointMap{});
+// jm set: the step size is the batch-mean rule over the raw tile scores (one step size for the domain), not tile mode's per-tile norm
 int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr_noise_norm, double* sumsq_ws,
                          SamplerState* state, unsigned long long draw_index, unsigned long long seed, int B,
-                         size_t per_sample, hipStream_t st, NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{});
+                         size_t per_sample, hipStream_t st, NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{},
+                         const JointMap& jm = JointMap{});
 // x = hold(x, known + level z, m), x_mean (may be null) = hold(x_mean, known, m); z null: the Philox draw (seed, draw_index)
 int sbgm_launch_hold_known(float* x, float* x_mean, const float* z, float level, unsigned long long seed, unsigned long long draw_index,
                            size_t n, hipStream_t st, const Hold& hold);
@@ -246,12 +257,12 @@ int sbgm_launch_edm_churn(float* x, float* x_copy, const float* z, const EdmStep
 // euler: d = -sigma_hat * score ; x_next = x_hat + (sigma_next - sigma_hat) * d ; t_dev[0 .. t_entries) = t_next
 int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, const EdmStep* table,
                           const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st,
-                          const Hold& hold = Hold{});
+                          const Hold& hold = Hold{}, const JointMap& jm = JointMap{});
 // heun: x = x_hat + (sigma_next - sigma_hat) * 0.5 (d - sigma_next * score), in place over x_hat (x_copy may be null);
 // with a state: t_dev = t_hat of the next step, then the step counter / RNG offset advance
 int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* score, const EdmStep* table, SamplerState* state,
                          const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st,
-                         const Hold& hold = Hold{});
+                         const Hold& hold = Hold{}, const JointMap& jm = JointMap{});
 
 // ---- ode.hip (rk45_sampler: Dormand-Prince 5(4) with scipy's step controller, on the device) -----------------------------------
 enum { SBGM_ODE_RUNNING = 0, SBGM_ODE_FINISHED = 1, SBGM_ODE_TOO_SMALL_STEP = 2, SBGM_ODE_NONFINITE = 3, SBGM_ODE_MAX_STEPS = 4 };
@@ -310,6 +321,8 @@ int sbgm_launch_extract_tiles(const float* dom, const int* origins, float* tiles
                               hipStream_t st);
 int sbgm_launch_stitch_tiles(const float* tiles, const int* origins, float* dom, int T, int C, int Hd, int Wd, int th, int tw,
                              int ramp_len, hipStream_t st);
+// out[T][1][th][tw] = the joint blend of scores[T][1][th][tw] (tile_blend.h), out of place; the host checks nothing about the origins
+int sbgm_launch_blend_tile_scores(const float* scores, float* out, const JointMap& jm, hipStream_t st);
 
 // ---- postproc.hip (after the sampler) ---------------------------------------------------------------------------------
 int sbgm_launch_pointwise_chain(const float* x, float* y, size_t n, int n_ops, const int* ops, const float* consts, hipStream_t st);

@@ -5,11 +5,14 @@
 // Noise: when `z` is null the kernels draw N(0,1) themselves (Philox4x32-10 counter RNG + Box-Muller, keyed by
 // (seed, running offset, element index)), so the sampler loop never round-trips noise through HBM; when `z`
 // is given (parity mode) the host-generated draw is used verbatim.
+// Joint tiled sampling: the JOINT instantiations of the four update kernels read the score through the partition-of-unity
+// blend of all tiles' scores (tile_blend.h), so the T tiles of a domain are one diffusion and copies of a domain pixel stay bit-equal.
 // All per-step scalars come from a device-resident table indexed by a device-side step counter, so one captured
 // hipGraph replays for every step.
 #include "common.h"
 #include "kernels.h"
 #include "philox.h"
+#include "tile_blend.h"
 
 namespace {
 
@@ -43,6 +46,13 @@ __device__ __forceinline__ f32x4 draw0(const Hold& h, unsigned long long seed, s
     return h.z0 ? reinterpret_cast<const f32x4*>(h.z0)[i] : philox_normal4(seed, 0ull, noise_index(h.nm, i));
 }
 
+// the score an update kernel uses at quad i: as stored, or (JOINT) the blend of all tiles' scores at the quad's domain position
+template <bool JOINT>
+__device__ __forceinline__ f32x4 load_score(const float* __restrict__ score, size_t i, const JointMap& jm) {
+    if (JOINT) return joint_score4(score, jm, i);
+    return reinterpret_cast<const f32x4*>(score)[i];
+}
+
 __global__ void fill_kernel(float* t, float v, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) t[i] = v;
@@ -67,21 +77,22 @@ __global__ __launch_bounds__(256) void init_noise_kernel(float* __restrict__ x, 
 }
 
 // x_mean = x + g^2 dt * score ;  x = x_mean + noise_coef * N(0,1);  HELD: x_mean = hold(., known), x = hold(., known + std(t_next) z)
-// with the step's own draw z (the unheld branch discards it on a held pixel, so it is a fresh draw there)
-template <bool HELD>
+// with the step's own draw z (the unheld branch discards it on a held pixel, so it is a fresh draw there);  JOINT (here and in the three
+// kernels below): `score` is read through the tile blend, everything else is unchanged and the hold sees the blended update
+template <bool HELD, bool JOINT>
 __global__ __launch_bounds__(256) void em_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
                                                         const float* __restrict__ score, const float* __restrict__ z,
                                                         const StepScalars* __restrict__ table,
                                                         const SamplerState* __restrict__ state, StepScalars sc_val,
                                                         unsigned long long off_val, unsigned long long seed, size_t n4,
-                                                        NoiseMap nm, Hold hold) {
+                                                        NoiseMap nm, Hold hold, JointMap jm) {
     const StepScalars sc = state ? table[state->step] : sc_val;
     const float s_next = !HELD ? 0.f : (state ? hold.levels[state->step] : hold.lv).next;
     const unsigned long long off = state ? state->rng_offset : off_val;
     if (state) seed = state->seed;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
-        const f32x4 sv = reinterpret_cast<const f32x4*>(score)[i];
+        const f32x4 sv = load_score<JOINT>(score, i, jm);
         const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
         const f32x4 mean = xv + (sc.g2 * sv) * sc.dt;   // association of score_sampling.py:124/:224
         if (HELD) {
@@ -133,13 +144,15 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ sc
 // instead of the batch mean, so a tile's trajectory does not depend on which other tiles share its batch or its GPU
 // (the reference has no tiler, its batch-mean rule :201 applies to batches of independent samples).
 // HELD: x = hold(., known + std(t_i) z); the score norm stays over the whole sample.
-template <bool HELD>
+// JOINT: all tiles of the domain are in the batch, so the reference's batch-mean rule over the RAW tile scores is well defined and gives
+// ONE step size for the domain (copies of a pixel keep the same noise amplitude); the per-tile norm is not used.
+template <bool HELD, bool JOINT>
 __global__ __launch_bounds__(256) void langevin_kernel(float* __restrict__ x, const float* __restrict__ score,
                                                        const float* __restrict__ z, float snr_noise_norm,
                                                        const double* __restrict__ sumsq,
                                                        const SamplerState* __restrict__ state,
                                                        unsigned long long off_val, unsigned long long seed, int B,
-                                                       size_t n4, NoiseMap nm, Hold hold) {
+                                                       size_t n4, NoiseMap nm, Hold hold, JointMap jm) {
     const float s_cur = !HELD ? 0.f : (state ? hold.levels[state->step] : hold.lv).cur;
     float gn = 0.f;
     for (int b = 0; b < B; ++b) gn += (float)sqrt(sumsq[b]);
@@ -147,7 +160,7 @@ __global__ __launch_bounds__(256) void langevin_kernel(float* __restrict__ x, co
     const float r = snr_noise_norm / gn;
     float eps = 2.f * (r * r);
     float nz = sqrtf(2.f * eps);
-    const bool per_tile = nm.origins != nullptr;
+    const bool per_tile = !JOINT && nm.origins != nullptr;
     const size_t per4 = n4 / (size_t)B;
     const unsigned long long off = state ? state->rng_offset : off_val;
     if (state) seed = state->seed;
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(256) void langevin_kernel(float* __restrict__ x, co
             nz = sqrtf(2.f * eps);
         }
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
-        const f32x4 sv = reinterpret_cast<const f32x4*>(score)[i];
+        const f32x4 sv = load_score<JOINT>(score, i, jm);
         const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
         const f32x4 v = xv + eps * sv + nz * n;
         reinterpret_cast<f32x4*>(x)[i] = HELD ? hold4(v, load_known(hold, i) + s_cur * n, load_mask(hold, i)) : v;
@@ -197,12 +210,12 @@ __global__ __launch_bounds__(256) void edm_churn_kernel(float* __restrict__ x, f
 // second evaluation (t_next) is published by the same launch: nothing reads it until the next kernel.
 // HELD (here and in the Heun corrector): a held pixel follows the probability-flow trajectory of a point mass, known + sigma z0 with
 // the run's own draw 0, so the output is hold(., known + sigma_next z0): deterministic, and `known` itself after the last step.
-template <bool HELD>
+template <bool HELD, bool JOINT>
 __global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict__ x_hat, const float* __restrict__ score,
                                                         float* __restrict__ d, float* __restrict__ x_next,
                                                         const EdmStep* __restrict__ table, const SamplerState* __restrict__ state,
                                                         EdmStep sc_val, float* __restrict__ t_dev, int t_entries, size_t n4,
-                                                        Hold hold) {
+                                                        Hold hold, JointMap jm) {
     const EdmStep sc = state ? table[state->step] : sc_val;
     const unsigned long long seed = state ? state->seed : hold.seed;
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
@@ -210,7 +223,7 @@ __global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict_
         for (size_t j = gid; j < (size_t)t_entries; j += stride) t_dev[j] = sc.t_next;
     const float h = sc.sigma_next - sc.sigma_hat;
     for (size_t i = gid; i < n4; i += stride) {
-        const f32x4 dv = (-sc.sigma_hat) * reinterpret_cast<const f32x4*>(score)[i];
+        const f32x4 dv = (-sc.sigma_hat) * load_score<JOINT>(score, i, jm);
         reinterpret_cast<f32x4*>(d)[i] = dv;
         const f32x4 v = reinterpret_cast<const f32x4*>(x_hat)[i] + h * dv;
         reinterpret_cast<f32x4*>(x_next)[i] =
@@ -220,12 +233,12 @@ __global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict_
 
 // Heun corrector: x = x_hat + (sigma_next - sigma_hat) * 0.5 (d + d'), d' = -sigma_next * score(x', sigma_next); in place over
 // x_hat, mirrored into the network-input slab.  Publishes the first evaluation time of the next step (the advance follows).
-template <bool HELD>
+template <bool HELD, bool JOINT>
 __global__ __launch_bounds__(256) void edm_heun_kernel(float* __restrict__ x, float* __restrict__ x_copy,
                                                        const float* __restrict__ d, const float* __restrict__ score,
                                                        const EdmStep* __restrict__ table, const SamplerState* __restrict__ state,
                                                        EdmStep sc_val, float* __restrict__ t_dev, int t_entries, int n_steps,
-                                                       size_t n4, Hold hold) {
+                                                       size_t n4, Hold hold, JointMap jm) {
     const unsigned long long s = state ? state->step : 0ull;
     const unsigned long long seed = state ? state->seed : hold.seed;
     const EdmStep sc = state ? table[s] : sc_val;
@@ -237,7 +250,7 @@ __global__ __launch_bounds__(256) void edm_heun_kernel(float* __restrict__ x, fl
     }
     const float h = sc.sigma_next - sc.sigma_hat;
     for (size_t i = gid; i < n4; i += stride) {
-        const f32x4 d2 = (-sc.sigma_next) * reinterpret_cast<const f32x4*>(score)[i];
+        const f32x4 d2 = (-sc.sigma_next) * load_score<JOINT>(score, i, jm);
         f32x4 v = reinterpret_cast<const f32x4*>(x)[i] + (h * 0.5f) * (reinterpret_cast<const f32x4*>(d)[i] + d2);
         if (HELD) v = hold4(v, load_known(hold, i) + sc.sigma_next * draw0(hold, seed, i), load_mask(hold, i));
         reinterpret_cast<f32x4*>(x)[i] = v;
@@ -264,6 +277,25 @@ __global__ __launch_bounds__(256) void hold_known_kernel(float* __restrict__ x, 
         if (held) hipLaunchKernelGGL((kernel<true>), grid, dim3(256), 0, st, __VA_ARGS__);              \
         else hipLaunchKernelGGL((kernel<false>), grid, dim3(256), 0, st, __VA_ARGS__);                  \
     } while (0)
+// ... and of the four update kernels, which also come with and without the joint tile blend
+#define SBGM_LAUNCH_STEP(kernel, held, joint, grid, st, ...)                                            \
+    do {                                                                                                \
+        if (joint) {                                                                                    \
+            if (held) hipLaunchKernelGGL((kernel<true, true>), grid, dim3(256), 0, st, __VA_ARGS__);    \
+            else hipLaunchKernelGGL((kernel<false, true>), grid, dim3(256), 0, st, __VA_ARGS__);        \
+        } else {                                                                                        \
+            if (held) hipLaunchKernelGGL((kernel<true, false>), grid, dim3(256), 0, st, __VA_ARGS__);   \
+            else hipLaunchKernelGGL((kernel<false, false>), grid, dim3(256), 0, st, __VA_ARGS__);       \
+        }                                                                                               \
+    } while (0)
+// a joint launch blends over the whole batch: its map must describe exactly the launch's [B][H][W]
+inline int check_joint(const JointMap& jm, size_t n, const char* who) {
+    if (!jm.origins) return 0;
+    SBGM_CHECK(jm.T >= 1 && jm.tile_h >= 1 && jm.tile_w >= 4 && jm.tile_w % 4 == 0 && jm.R >= 1 &&
+               (size_t)jm.T * jm.tile_h * jm.tile_w == n, "%s: the joint tile map (%d tiles of %d x %d, ramp %d) does not match %zu elements",
+               who, jm.T, jm.tile_h, jm.tile_w, jm.R, n);
+    return 0;
+}
 inline int check_hold(const Hold& h, const char* who) {
     SBGM_CHECK((h.known == nullptr) == (h.mask == nullptr), "%s: known and known_mask must be given together", who);
     return 0;
@@ -296,17 +328,17 @@ int sbgm_launch_init_noise(float* x, float scale, const float* z, unsigned long 
 int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const float* z, const StepScalars* table,
                           SamplerState* state, const StepScalars* sc_val, unsigned long long draw_index, float* t_dev,
                           unsigned long long seed, int B, size_t per_sample, int n_steps, hipStream_t st, int t_entries,
-                          NoiseMap nm, const Hold& hold) {
+                          NoiseMap nm, const Hold& hold, const JointMap& jm) {
     const size_t n = (size_t)B * per_sample;
     if (t_entries <= 0) t_entries = B;
     SBGM_CHECK(n % 4 == 0, "em_update: element count must be a multiple of 4");
     SBGM_CHECK(t_entries <= 1024, "em_update: %d time entries > 1024", t_entries);
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "em_update: need a device table or explicit scalars");
     SBGM_CHECK(!(hold.known && state && !hold.levels), "em_update: a held run with a device state needs the hold-level table");
-    if (check_hold(hold, "em_update")) return 1;
+    if (check_hold(hold, "em_update") || check_joint(jm, n, "em_update")) return 1;
     const StepScalars v = sc_val ? *sc_val : StepScalars{};
-    SBGM_LAUNCH_HELD(em_update_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x, x_mean, score, z, table, state, v,
-                     draw_index, seed, n / 4, nm, hold);
+    SBGM_LAUNCH_STEP(em_update_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x, x_mean, score, z,
+                     table, state, v, draw_index, seed, n / 4, nm, hold, jm);
     SBGM_LAUNCH_CHECK();
     if (state) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1024), 0, st, state, table, t_dev, t_entries, 1, n_steps);
@@ -317,17 +349,17 @@ int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const flo
 
 int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr_noise_norm, double* sumsq_ws,
                          SamplerState* state, unsigned long long draw_index, unsigned long long seed, int B,
-                         size_t per_sample, hipStream_t st, NoiseMap nm, const Hold& hold) {
+                         size_t per_sample, hipStream_t st, NoiseMap nm, const Hold& hold, const JointMap& jm) {
     SBGM_CHECK(per_sample % 4 == 0, "langevin: per-sample element count must be a multiple of 4");
     SBGM_CHECK(!(hold.known && state && !hold.levels), "langevin: a held run with a device state needs the hold-level table");
-    if (check_hold(hold, "langevin")) return 1;
+    if (check_hold(hold, "langevin") || check_joint(jm, (size_t)B * per_sample, "langevin")) return 1;
     { if (sbgm_zero_async(sumsq_ws, sizeof(double) * B, st)) return 1; }
     const int bx = (int)std::min<size_t>((per_sample / 4 + 255) / 256, B >= 64 ? 4 : 16);
     hipLaunchKernelGGL(sumsq_kernel, dim3(bx, B), dim3(256), 0, st, score, sumsq_ws, per_sample / 4);
     SBGM_LAUNCH_CHECK();
     const size_t n4 = (size_t)B * per_sample / 4;
-    SBGM_LAUNCH_HELD(langevin_kernel, hold.known != nullptr, dim3(stream_blocks(n4)), st, x, score, z, snr_noise_norm, sumsq_ws,
-                     state, draw_index, seed, B, n4, nm, hold);
+    SBGM_LAUNCH_STEP(langevin_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n4)), st, x, score, z,
+                     snr_noise_norm, sumsq_ws, state, draw_index, seed, B, n4, nm, hold, jm);
     SBGM_LAUNCH_CHECK();
     if (state) {
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0);
@@ -350,25 +382,26 @@ int sbgm_launch_edm_churn(float* x, float* x_copy, const float* z, const EdmStep
 
 int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, const EdmStep* table,
                           const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st,
-                          const Hold& hold) {
+                          const Hold& hold, const JointMap& jm) {
     SBGM_CHECK(n % 4 == 0, "edm_euler: element count must be a multiple of 4");
-    if (check_hold(hold, "edm_euler")) return 1;
+    if (check_hold(hold, "edm_euler") || check_joint(jm, n, "edm_euler")) return 1;
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_euler: need a device table or explicit scalars");
     const EdmStep v = sc_val ? *sc_val : EdmStep{};
-    SBGM_LAUNCH_HELD(edm_euler_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x_hat, score, d, x_next, table, state, v,
-                     t_dev, t_dev ? t_entries : 0, n / 4, hold);
+    SBGM_LAUNCH_STEP(edm_euler_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x_hat, score, d,
+                     x_next, table, state, v, t_dev, t_dev ? t_entries : 0, n / 4, hold, jm);
     SBGM_LAUNCH_CHECK();
     return 0;
 }
 
 int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* score, const EdmStep* table, SamplerState* state,
-                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st, const Hold& hold) {
+                         const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st, const Hold& hold,
+                         const JointMap& jm) {
     SBGM_CHECK(n % 4 == 0, "edm_heun: element count must be a multiple of 4");
-    if (check_hold(hold, "edm_heun")) return 1;
+    if (check_hold(hold, "edm_heun") || check_joint(jm, n, "edm_heun")) return 1;
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_heun: need a device table or explicit scalars");
     const EdmStep v = sc_val ? *sc_val : EdmStep{};
-    SBGM_LAUNCH_HELD(edm_heun_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x, x_copy, d, score, table, state, v, t_dev,
-                     t_dev ? t_entries : 0, n_steps, n / 4, hold);
+    SBGM_LAUNCH_STEP(edm_heun_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x, x_copy, d, score,
+                     table, state, v, t_dev, t_dev ? t_entries : 0, n_steps, n / 4, hold, jm);
     SBGM_LAUNCH_CHECK();
     if (state) {                     // step counter and RNG offset: the EM mechanism, without its StepScalars time publish
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 1, n_steps);

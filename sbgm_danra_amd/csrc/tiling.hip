@@ -8,11 +8,14 @@
 //         out = sum_t w_t * tile_t / sum_t w_t,   w_t = wy * wx,
 //         w(i) = min(d_lo, d_hi, R) / R  with d_lo = i + 1, d_hi = L - i, except that an edge lying on the domain boundary
 //         does not ramp (there is no neighbour to blend with).  Gather form: deterministic, no atomics.
-// Both are HBM-bound copies (8 B per element moved).
+// K36 blend_tile_scores_kernel — the same blend in tile space, out of place: out_b(p) = the blend at p's domain position of every
+//         tile's value there (the gather the joint update kernels of sampler.hip apply to the score, on its own for unit tests).
+// All are HBM-bound copies (8 B per element moved).
 #include <algorithm>
 
 #include "common.h"
 #include "kernels.h"
+#include "tile_blend.h"
 
 namespace {
 
@@ -27,12 +30,6 @@ __global__ __launch_bounds__(256) void extract_tiles_kernel(const float* __restr
         const int t = (int)(r / C);
         tiles[i] = dom[((size_t)c * Hd + origins[2 * t] + y) * Wd + origins[2 * t + 1] + x];
     }
-}
-
-__device__ __forceinline__ float ramp(int i, int L, int origin, int dom_len, int R) {
-    const int lo = origin == 0 ? R : i + 1;                    // distance to the tile's low edge (no ramp on the domain edge)
-    const int hi = origin + L == dom_len ? R : L - i;
-    return (float)min(min(lo, hi), R) / (float)R;
 }
 
 __global__ __launch_bounds__(256) void stitch_tiles_kernel(const float* __restrict__ tiles, const int* __restrict__ origins,
@@ -53,6 +50,12 @@ __global__ __launch_bounds__(256) void stitch_tiles_kernel(const float* __restri
         }
         dom[i] = wsum > 0.f ? acc / wsum : 0.f;
     }
+}
+
+__global__ __launch_bounds__(256) void blend_tile_scores_kernel(const float* __restrict__ scores, float* __restrict__ out, JointMap jm,
+                                                                size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x)
+        reinterpret_cast<f32x4*>(out)[i] = joint_score4(scores, jm, i);
 }
 
 }  // namespace
@@ -80,6 +83,18 @@ int sbgm_launch_stitch_tiles(const float* tiles, const int* origins, float* dom,
     const size_t total = (size_t)C * Hd * Wd;
     hipLaunchKernelGGL(stitch_tiles_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, st, tiles, origins,
                        dom, T, C, Hd, Wd, th, tw, ramp_len, total);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sbgm_launch_blend_tile_scores(const float* scores, float* out, const JointMap& jm, hipStream_t st) {
+    if (check_tiling(jm.T, 1, jm.dom_h, jm.dom_w, jm.tile_h, jm.tile_w)) return 1;
+    SBGM_CHECK(scores && out && jm.origins && scores != out, "blend_tile_scores: scores, origins and a separate out are required");
+    SBGM_CHECK(jm.tile_w % 4 == 0, "blend_tile_scores: tile width %d must be a multiple of 4", jm.tile_w);
+    SBGM_CHECK(jm.R >= 1, "blend_tile_scores: ramp length %d must be >= 1", jm.R);
+    const size_t n4 = (size_t)jm.T * jm.tile_h * (jm.tile_w / 4);
+    hipLaunchKernelGGL(blend_tile_scores_kernel, dim3((int)std::min<size_t>((n4 + 255) / 256, 8192)), dim3(256), 0, st, scores, out, jm,
+                       n4);
     SBGM_LAUNCH_CHECK();
     return 0;
 }

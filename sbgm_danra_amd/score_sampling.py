@@ -148,8 +148,26 @@ def sde_hold_levels(kind, num_steps, sigma_sde=25.0, eps=1e-3):
     return {"t": t, "s_cur": s_cur, "s_next": np.append(s_cur[1:], np.float32(0.0))}
 
 
+def _prep_joint(joint_tiles, tile_origins, noise, who):
+    """`joint_tiles` as (domain_height, ramp_len) ints, or None; the argument checks of a joint run that need no device"""
+    if joint_tiles is None:
+        return None
+    try:
+        domain_height, ramp_len = (int(v) for v in joint_tiles)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: joint_tiles must be (domain_height, ramp_len), got {joint_tiles!r}") from None
+    if tile_origins is None:
+        raise ValueError(f"{who}: joint_tiles needs tile_origins (the batch must be all tiles of one domain)")
+    if noise is not None:
+        raise ValueError(f"{who}: joint_tiles draws domain-keyed in-kernel noise; it cannot be combined with injected noise")
+    if domain_height < 1 or ramp_len < 1:
+        raise ValueError(f"{who}: joint_tiles = (domain_height, ramp_len) = ({domain_height}, {ramp_len}) must both be >= 1")
+    return domain_height, ramp_len
+
+
 def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw, y, cond_img, lsm_cond, topo_cond,
-                noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm_args=None, held=(None, None)):
+                noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm_args=None, held=(None, None),
+                joint=None):
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if dev.type != "cuda":
         raise N.NativeError(f"the native samplers run on a ROCm device, got device={device!r}")
@@ -175,6 +193,12 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
         if noise is not None:
             raise ValueError("tile_origins keys the in-kernel noise; it cannot be combined with injected noise")
     known, mask = held
+    if joint is not None:                                  # one diffusion over the domain: the tiles' scores are blended at every step
+        if edm_args is not None:
+            N.check(eng.lib.sbgm_sampler_run_edm_joint(eng.h, C.byref(a), *edm_args, *joint, N.ptr(known), N.ptr(mask), N.stream()))
+        else:
+            N.check(eng.lib.sbgm_sampler_run_joint(eng.h, C.byref(a), *joint, N.ptr(known), N.ptr(mask), N.stream()))
+        return out
     if edm_args is not None:
         if known is not None:
             N.check(eng.lib.sbgm_sampler_run_edm_held(eng.h, C.byref(a), *edm_args, known.data_ptr(), mask.data_ptr(), N.stream()))
@@ -190,9 +214,11 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
     return out
 
 
-def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scale, tile_origins, churn=False):
-    """Setup of the host-driven loops: refuses `tile_origins`, checks that `noise` holds the run's draws, and returns the initial
+def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scale, tile_origins, churn=False, joint=None):
+    """Setup of the host-driven loops: refuses `tile_origins` and `joint_tiles`, checks that `noise` holds the run's draws, and returns the initial
     x = scale * (draw 0) and z(i), the i-th noise draw (None: the kernels draw in-kernel Philox noise)."""
+    if joint is not None:
+        raise N.NativeError("joint tiled sampling (joint_tiles) needs the native sampler loop (a ScoreNet in eval mode)")
     if tile_origins is not None:
         raise N.NativeError("domain-keyed noise (tile_origins) needs the native sampler loop (a ScoreNet in eval mode)")
     if noise is not None:
@@ -210,18 +236,21 @@ def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scal
 
 def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=500, device="cuda",
                            eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
-                           noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None):
+                           noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None,
+                           joint_tiles=None):
     """Euler-Maruyama reverse-SDE sampler (reference score_sampling.py:63-127).  Returns the last `mean_x`.
-    `known` / `known_mask` (not in the reference): hold the masked pixels at `known`, see `pc_sampler`."""
+    `known` / `known_mask` (not in the reference): hold the masked pixels at `known`, see `pc_sampler`; `joint_tiles`: see `pc_sampler`."""
     seed = _fresh_seed() if seed is None else seed
+    joint = _prep_joint(joint_tiles, tile_origins, noise, "Euler_Maruyama_sampler")
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "Euler_Maruyama_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_EM, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
-                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask))
+                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask),
+                           joint=joint)
     lib, st = N.lib(), N.stream
     ones = torch.ones(batch_size, device=device)
     x, z = _host_start(N.SAMPLER_EM, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
-                       tile_origins)
+                       tile_origins, joint=joint)
     time_steps = torch.linspace(1.0, eps, num_steps, device=device)
     step_size = float(time_steps[0] - time_steps[1])
     mean_x = torch.empty_like(x)
@@ -243,7 +272,8 @@ def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batc
 
 def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=800, snr=signal_to_noise_ratio,
                device="cuda", eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
-               noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None):
+               noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None,
+               joint_tiles=None):
     """Predictor-corrector sampler: Langevin corrector with the batch-mean gradient norm, then an Euler-Maruyama
     predictor (reference score_sampling.py:136-230).  Returns the last `x_mean`.
 
@@ -252,16 +282,25 @@ def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, n
     moved).  Pixels with mask 1 are held: after every state update they are overwritten with `known` plus noise of the level the state
     is at (reusing that update's own draw: no extra draw, `noise=` keeps its layout), so the result equals `known` there bit for bit and
     the free pixels are sampled consistently with them.  Mask 0 leaves a pixel exactly as without the arguments (`known` may be NaN
-    there); values in between blend.  Both or neither must be given (ValueError)."""
+    there); values in between blend.  Both or neither must be given (ValueError).
+
+    Joint full-domain sampling (not in the reference; Mixture of Diffusers / MultiDiffusion): `joint_tiles=(domain_height, ramp_len)` with
+    `tile_origins` and `domain_width` declares the batch to be ALL tiles of one domain and runs ONE diffusion over it: wherever an update
+    reads a tile's score it reads the stitch-weighted blend of every tile's score at that domain pixel (ramps of `ramp_len` pixels, as
+    `FullDomainTiler.stitch`), and the corrector's step size is the batch-mean rule over the tiles.  All copies of a domain pixel then
+    stay bit-equal through the run, so stitching the result averages nothing.  Needs the native loop and in-kernel noise; composes with
+    `known` / `known_mask` and guidance.  `FullDomainTiler.sample(..., joint=True)` sets it up."""
     seed = _fresh_seed() if seed is None else seed
+    joint = _prep_joint(joint_tiles, tile_origins, noise, "pc_sampler")
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "pc_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_PC, score_model, batch_size, num_steps, snr, eps, img_size, y, cond_img, lsm_cond,
-                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask))
+                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask),
+                           joint=joint)
     lib, st = N.lib(), N.stream
     ones = torch.ones(batch_size, device=device)
     x, z = _host_start(N.SAMPLER_PC, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
-                       tile_origins)
+                       tile_origins, joint=joint)
     time_steps = np.linspace(1.0, eps, num_steps)
     step_size = float(time_steps[0] - time_steps[1])
     x_mean = torch.empty_like(x)
@@ -395,30 +434,31 @@ def edm_sampler_kwargs(cfg) -> dict:
 def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=32, device="cuda", eps=1e-3,
                      img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, sigma_min=None, sigma_max=None,
                      rho=7.0, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, noise=None, use_graph=True, seed=None,
-                     tile_origins=None, domain_width=0, known=None, known_mask=None):
+                     tile_origins=None, domain_width=0, known=None, known_mask=None, joint_tiles=None):
     """Heun (2nd-order) solver of the probability-flow ODE dx/dsigma = -sigma * score on the Karras sigma ladder, with optional
     stochastic churn (Karras et al. 2022, Alg. 2); works with the VE-SDE score network as trained.  `num_steps` N costs 2N-1
     network evaluations (18-64 is the intended range).  Conditions, guidance (`cfg`: both evaluations of a step use
     guidance_scale), `noise` (draw 0 = initial state, draw 1+i = churn of step i when s_churn > 0), `seed`, `use_graph` and
     `tile_origins` behave as in `pc_sampler`.  `diffusion_coeff` is accepted for signature compatibility and unused.
     `known` / `known_mask` as in `pc_sampler`; here a held pixel follows known + sigma * (draw 0), the exact trajectory of a point mass,
-    so the sampler stays deterministic in its seed.
+    so the sampler stays deterministic in its seed.  `joint_tiles` as in `pc_sampler`: both slopes of a step use the blended score.
     Returns x after the last step, [B,1,H,W] (no noise added at the end).  Sample quality against `pc_sampler` at 1000 steps
     has not been measured."""
     sig = float(score_model.sigma) if isinstance(score_model, ScoreNet) else _sigma_of(marginal_prob_std)
     sch = edm_heun_schedule(num_steps, sig, eps, sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise)
     seed = _fresh_seed() if seed is None else seed
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "edm_heun_sampler")
+    joint = _prep_joint(joint_tiles, tile_origins, noise, "edm_heun_sampler")
     if isinstance(score_model, ScoreNet) and not score_model.training:
         edm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
                     float(s_churn), float(s_tmin), float(s_tmax), float(s_noise))
         return _native_run(N.SAMPLER_EDM_HEUN, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
                            topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, edm_args=edm_args,
-                           held=(known, known_mask))
+                           held=(known, known_mask), joint=joint)
     lib, st = N.lib(), N.stream
     churn = s_churn > 0
     x, z = _host_start(N.SAMPLER_EDM_HEUN, batch_size, num_steps, img_size, device, noise, seed, float(np.float32(sch["sigma"][0])),
-                       tile_origins, churn)
+                       tile_origins, churn, joint=joint)
     n = x.numel()
     xp, d, out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     ones = torch.ones(batch_size, device=device)

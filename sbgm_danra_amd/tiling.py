@@ -15,6 +15,11 @@ The result does NOT depend on the world size or on `tiles_per_batch`: with `tile
 tile uses that tile's own score norm (csrc/sampler.hip; the reference's batch-mean rule, score_sampling.py:201, is for
 batches of independent samples), the noise is keyed by domain position and everything else in the network is per
 sample in eval mode.
+
+Joint sampling (`sample(..., joint=True)`): ONE diffusion over the domain instead of T that share their noise.  All
+tiles run as one batch and every update kernel reads the stitch-weighted blend of the tiles' scores (`joint_tiles` of the samplers),
+so all copies of a domain pixel stay bit-equal through the run and the stitch has nothing left to average: no band of smoother
+texture over the overlaps.  One rank, one batch; `pc_sampler` then uses the batch-mean Langevin step size over the tiles.
 """
 from __future__ import annotations
 
@@ -105,15 +110,30 @@ class FullDomainTiler:
         return dom[:, :, : self.Wd].contiguous() if self.Wd_pad != self.Wd else dom
 
     def sample(self, score_model, sampler, marginal_prob_std, diffusion_coeff, num_steps, cond_img=None, lsm_cond=None,
-               topo_cond=None, y=None, seed=None, tiles_per_batch=None, known=None, known_mask=None, **sampler_kw) -> torch.Tensor:
+               topo_cond=None, y=None, seed=None, tiles_per_batch=None, known=None, known_mask=None, joint=False,
+               **sampler_kw) -> torch.Tensor:
         """Sample the whole domain: cond_img [C,Hd,Wd] / lsm_cond, topo_cond [2,Hd,Wd] / y scalar class -> [1,Hd,Wd].
         Tiles are sharded over the ranks of the process group (if any) and, per rank, run in batches of
         `tiles_per_batch`; every batch shares `seed`, so the domain-keyed noise is identical wherever tiles overlap.
         `known`, `known_mask` [1,Hd,Wd] (constrained sampling, see `pc_sampler`): cut into tiles like the conditions and passed to
         the sampler; after the stitch the hold is applied once more against the domain fields, so the result equals `known` on the
-        mask bit for bit and not just to the rounding of the blend."""
+        mask bit for bit and not just to the rounding of the blend.
+        `joint=True`: one diffusion over the domain (the sampler's `joint_tiles`): all tiles in one batch on one rank, the tiles'
+        scores blended at every step, so the tiles agree bit for bit wherever they overlap and the stitch only assembles them."""
         import inspect
         from .score_sampling import _fresh_seed
+        _, world = parallel.world()
+        if joint:
+            if "joint_tiles" not in inspect.signature(sampler).parameters:
+                raise ValueError(f"FullDomainTiler.sample: {getattr(sampler, '__name__', sampler)} does not take joint_tiles (the per-sample "
+                                 "step controllers of the adaptive samplers would let the copies of a pixel drift)")
+            if tiles_per_batch is not None and tiles_per_batch < len(self):
+                raise ValueError(f"FullDomainTiler.sample: a joint run needs all {len(self)} tiles in one batch, got tiles_per_batch="
+                                 f"{tiles_per_batch}")
+            if world > 1:
+                raise ValueError("FullDomainTiler.sample: a joint run blends the scores of all tiles at every step and cannot be split "
+                                 f"over {world} ranks; let each rank sample whole domains instead")
+            sampler_kw = dict(sampler_kw, joint_tiles=(self.Hd, max(1, self.overlap)))
         if (known is None) != (known_mask is None):
             raise ValueError("FullDomainTiler.sample: known and known_mask must be given together")
         held = {}
@@ -125,7 +145,6 @@ class FullDomainTiler:
                 if tuple(f.shape) != (1, self.Hd, self.Wd):
                     raise ValueError(f"FullDomainTiler.sample: {name} {tuple(f.shape)} must be [1, {self.Hd}, {self.Wd}]")
             held = {"known": known, "known_mask": known_mask}
-        _, world = parallel.world()
         seed = _fresh_seed() if seed is None else seed
         if world > 1:                                  # one seed for the whole domain
             import torch.distributed as dist
