@@ -381,6 +381,25 @@ int sbgm_final_block_fwd(const float* x, const float* in_affine, const float* in
                          const float* w_wino, const float* w_wino2d, const float* bc, const float* b2, const float* t, float sigma,
                          float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, const int* tile, void* stream);
 
+/* The same block with the channels mixed at LOW resolution (conv_final.hip, the route of the EM / PC / EDM Heun samplers): the channel
+ * mix commutes with the per-channel bilinear x2 and the two 3x3 stencils compose into one 5x5 stencil, so
+ *   Z[s] = sum_ci Wz[s][ci] v[ci] (low-res, s = (sy, sx) in 0..4 x 0..4),   out[o] = beta + sum_{s, o+s-2 inside the image} up(Z[s])[o + s - 2].
+ * conv zero-pads conv_up's OUTPUT, so the first and the last output row / column drop the taps whose intermediate pixel lies outside:
+ * 3 classes per axis (first, interior, last), 9 sets (Wz, beta), class index 3*cy + cx:
+ *   Wz[c][sy][sx][ci] = sum over ty in valid(cy), tx in valid(cx), ty+vy = sy, tx+vx = sx of sum_co w2[0][co][ty][tx] w1[co][ci][vy][vx],
+ *   beta[c] = b2 + sum over the valid taps of sum_co w2[0][co][tap] b1[co];   valid: first {1,2}, interior {0,1,2}, last {0,1}.
+ * pack: -> wz_out [9][25][C] and beta_out [9] (fp64 sums rounded once; wz_out may be NULL) and wz_packed
+ * (sbgm_final_lowres_packed_numel(C) floats: per class the MFMA A operand [C/16][32][16], rows 25..31 zero).
+ * fwd: x = the low-resolution NHWC input [B,H/2,W/2,C], optionally act(x*scale + shift + in_skip) on load (any map size); out [B,1,H,W],
+ * divided by sigma(t) when t [B] is given.  ws: sbgm_final_lowres_ws_numel(B, H, W) floats.  C % 16 == 0, C <= 128, H and W even, >= 4. */
+int64_t sbgm_final_lowres_packed_numel(int C);
+int64_t sbgm_final_lowres_ws_numel(int B, int H, int W);
+int sbgm_final_lowres_pack(const float* w1_oihw, const float* b1, const float* w2_oihw, const float* b2, float* wz_out, float* beta_out,
+                           float* wz_packed, int C, void* stream);
+int sbgm_final_lowres_fwd(const float* x_lowres_nhwc, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed,
+                          const float* beta, const float* t, float sigma, float* out, float* ws, int64_t ws_floats, int B, int H, int W,
+                          int C, void* stream);
+
 /* ConvTranspose2d(k=2,s=2) = one 1x1 convolution to 4C channels (weights from sbgm_tconv_weight_to_oihw, bias repeated
  * 4x) followed by depth->space; its backward is space->depth followed by the 1x1 convolution's backward. */
 int sbgm_depth_to_space2(const float* x /* [B,H,W,4C] */, float* y /* [B,2H,2W,C] */, int B, int H, int W, int C, void* stream);

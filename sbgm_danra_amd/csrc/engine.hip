@@ -105,11 +105,17 @@ struct Stem : Derived {
 // Composed final block (conv_final.hip): final_layer.conv(final_layer.conv_up(.)) as one 3x3 convolution to 16 channels, the 9 taps
 // of `conv` first.  cw / cb are no Params of the model (not in the state_dict, the gradient arena or Adam): their images live in one
 // allocation at fixed addresses (Wc OIHW [16][ci][3][3], bc [16], then the three packed images), so a cached step graph stays valid.
-struct FinalBlock : Derived {                                  // up: final_layer.conv_up.weight / .bias, w2: final_layer.conv.weight
+// The low-resolution form of the same block (`lowres`: Wz of the 9 border classes as MFMA A operands, beta [9]) follows them in that
+// allocation and is rebuilt with them; it also reads conv's bias, which therefore feeds this image too.
+struct FinalBlock : Derived {                                  // up: final_layer.conv_up.weight / .bias, conv: final_layer.conv.weight / .bias
     float* wc = nullptr;
     Param cw, cb;                                              // the composed weight and bias
+    bool lowres = false;
+    float *wz = nullptr, *beta = nullptr;
     static bool env_on() { static const bool v = getenv("SBGM_NO_FINAL_COMPOSE") == nullptr; return v; }
-    int build(const ConvW& up, Param* w2, int ci, bool resize_conv) {
+    static bool env_lowres() { static const bool v = getenv("SBGM_NO_FINAL_LOWRES") == nullptr; return v; }
+    int build(const ConvW& up, const ConvW& conv, int ci, bool resize_conv) {
+        Param* const w2 = conv.w;
         // the 16-channel op runs on the LDS-staged Winograd kernels only, so the switches that take those away keep the projection path
         on = env_on() && resize_conv && ci % 16 == 0 && up.w->img[IMG_WINO] != nullptr && !sbgm_conv_switches().no_lds &&
              !sbgm_conv_switches().round1;
@@ -119,25 +125,36 @@ struct FinalBlock : Derived {                                  // up: final_laye
         cw.cout = 16; cw.cin = ci; cw.kh = cw.kw = 3; cw.cs = ci; cw.want_wino = true;
         sbgm_conv_image_floats(3, 3, ci, 16, true, cw.floats);
         cb.name = "final_layer.composed.bias"; cb.numel = cb.floats[0] = 16;
-        const size_t wc_floats = align_up((size_t)cw.numel, 64), total = wc_floats + cb.storage_floats() + cw.storage_floats();
+        lowres = env_lowres() && ci <= FINAL_LOWRES_MAX_C;
+        if (lowres) conv.b->feeds = this;
+        const size_t wz_floats = lowres ? align_up(sbgm_final_lowres_packed_floats(ci), 64) : 0;
+        const size_t wc_floats = align_up((size_t)cw.numel, 64), images = wc_floats + cb.storage_floats() + cw.storage_floats();
+        const size_t total = images + wz_floats + (lowres ? 64 : 0);
         if (alloc(wc, total)) return 1;
         SBGM_HIP(hipMemset(wc, 0, total * 4));
         cw.place(cb.place(wc + wc_floats));
         cw.filled = cb.filled = true;
+        if (lowres) { wz = wc + images; beta = wz + wz_floats; }
         return 0;
     }
-    int prepare(const ConvW& up, const Param& w2, hipStream_t st) {
+    int prepare(const ConvW& up, const ConvW& conv, hipStream_t st) {
         if (!on || !dirty) return 0;
+        const Param& w2 = *conv.w;
         SBGM_CHECK(up.w->oihw && w2.oihw && up.b->filled, "final block: final_layer.conv_up / conv weights were never uploaded");
         if (sbgm_launch_final_compose(up.w->oihw, up.b->dev(), w2.oihw, wc, cb.dev(), cw.cin, st)) return 1;
         if (sbgm_pack_conv_images(wc, cw.img, 16, cw.cin, 3, 3, cw.cin, st)) return 1;
+        if (lowres) {
+            SBGM_CHECK(conv.b->filled, "final block: final_layer.conv.bias was never uploaded");
+            if (sbgm_launch_final_lowres_pack(up.w->oihw, up.b->dev(), w2.oihw, conv.b->dev(), nullptr, beta, wz, cw.cin, st)) return 1;
+        }
         dirty = false;
         return 0;
     }
 };
 
 // Which evaluations take the composed stem (+ the run's condition term, null without condition channels) and the composed final block
-struct Routes { bool stem = false, fin = false; const float* stem_T = nullptr; };
+// (fin_lowres: as the low-resolution mix + gather instead of the composed 3x3 convolution)
+struct Routes { bool stem = false, fin = false, fin_lowres = false; const float* stem_T = nullptr; };
 enum Caller { CALL_PLAIN, CALL_SDE_RUN, CALL_MEASURE };
 
 }  // namespace
@@ -166,7 +183,7 @@ struct sbgm_model {
     // where an EM / PC / EDM Heun run begins: a plain forward or a training-time evaluation must not start packing a 22x22 image.
     int refresh_derived(hipStream_t st) {
         if (bn_dirty && fold_bn(st)) return 1;
-        return fin.prepare(fin_up, *fin_conv.w, st);
+        return fin.prepare(fin_up, fin_conv, st);
     }
     // The one place that decides who evaluates through which form of the network, from the kind of caller:
     //   the EM / PC / EDM Heun driver: composed stem and composed final block, for the duration of a run (~SamplerRun ends them);
@@ -177,7 +194,8 @@ struct sbgm_model {
     //   (bound 9), where the projection path gives 464 / 464; a stem that rounds differently flips such decisions too.
     Routes routes;
     void set_routes(Caller c, const float* stem_T = nullptr) {
-        routes = Routes{c == CALL_SDE_RUN && stem.on, c != CALL_PLAIN && fin.on, c == CALL_SDE_RUN ? stem_T : nullptr};
+        routes = Routes{c == CALL_SDE_RUN && stem.on, c != CALL_PLAIN && fin.on, c != CALL_PLAIN && fin.on && fin.lowres,
+                        c == CALL_SDE_RUN ? stem_T : nullptr};
     }
     size_t stem_t_bytes(int B, int H, int W) const { return stem.on && cin_total > 1 ? align_up((size_t)B * H * W * 4 * 4, 256) : 0; }
     // workspace
@@ -497,7 +515,7 @@ int sbgm_model::build(const sbgm_model_config& c) {
         for (auto& b : layers[li]) { place_bn(b.bn1, b.cout); place_bn(b.bn2, b.cout); if (b.has_ds) place_bn(b.dsbn, b.cout); }
     SBGM_HIP(hipMalloc(&d_state, sizeof(SamplerState)));
     stem.build(conv1.w, conv2.w);
-    return fin.build(fin_up, fin_conv.w, dec[3].cout, !c.decoder_transpose);   // after place(): the route needs conv_up's Winograd image
+    return fin.build(fin_up, fin_conv, dec[3].cout, !c.decoder_transpose);   // after place(): the route needs conv_up's Winograd image
 }
 
 int sbgm_model::ensure_ws(size_t bytes) {
@@ -855,6 +873,18 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             if (conv(ConvGeom{1, 1, 1, 0}, p, *fin_up.w, st)) return 1;
             if (sbgm_launch_depth_space2(up, a, B, ch, cw_, ci, 1, st)) return 1;
             return sbgm_launch_conv3x3_cout1(a, fin_conv.w->dev(), fin_conv.b->dev(), t, cfg.sigma, out, B, H, W, ci, st);
+        }
+        if (routes.fin_lowres && !tuning) {
+            // conv(conv_up(up(.))) with the channels mixed at low resolution: Z = Wz . v on the low-res map (the pending normalisation
+            // applied on load, or the finished map where nothing is pending), then the 5x5 gather through the bilinear x2.  A tuning
+            // evaluation keeps timing the composed 3x3 convolution below: SBGM_NO_FINAL_LOWRES=1 still runs it.
+            float* zb = wsalloc(sbgm_final_lowres_ws_floats(B, ch, cw_));
+            if (!zb) return 1;
+            const bool live = pend.live;
+            pend.live = false;
+            if (sbgm_launch_final_mix(live ? pend.raw : cur, live ? pend.affine : nullptr, live ? pend.skip : nullptr,
+                                      live ? pend.act : SBGM_ACT_NONE, fin.wz, zb, B, ch, cw_, ci, st)) return 1;
+            return sbgm_launch_final_gather(zb, fin.beta, t, cfg.sigma, out, B, ch, cw_, st);
         }
         if (routes.fin) {
             // conv(conv_up(.)) composed: one 3x3 convolution from ci to the 9 taps (16 channels stored), rows [M][16], then the gather
@@ -1647,6 +1677,28 @@ int sbgm_final_block_fwd(const float* x, const float* in_affine, const float* in
                "final_block_fwd: tile {%d,%d,%d,%d,%d,%d} is no 16-channel LDS-staged Winograd kernel", v[0], v[1], v[2], v[3], v[4], v[5]);
     if (sbgm_launch_tile(ConvGeom{3, 3, 1, 1}, p, im, ct, nullptr, st)) return 1;
     return sbgm_launch_tap_gather_rows(ws, b2, t, sigma, out, B, H, W, st);
+}
+
+// ---- the same block mixed at low resolution (conv_final.hip, second half; the engine's fin_lowres route) ----------------------------
+int64_t sbgm_final_lowres_packed_numel(int C) { return C >= 16 && C % 16 == 0 ? (int64_t)sbgm_final_lowres_packed_floats(C) : 0; }
+int64_t sbgm_final_lowres_ws_numel(int B, int H, int W) {
+    return B >= 1 && H >= 2 && W >= 2 ? (int64_t)sbgm_final_lowres_ws_floats(B, H / 2, W / 2) : 0;
+}
+
+int sbgm_final_lowres_pack(const float* w1_oihw, const float* b1, const float* w2_oihw, const float* b2, float* wz_out, float* beta_out,
+                           float* wz_packed, int C, void* stream) {
+    return sbgm_launch_final_lowres_pack(w1_oihw, b1, w2_oihw, b2, wz_out, beta_out, wz_packed, C, (hipStream_t)stream);
+}
+
+int sbgm_final_lowres_fwd(const float* x_lowres_nhwc, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed,
+                          const float* beta, const float* t, float sigma, float* out, float* ws, int64_t ws_floats, int B, int H, int W,
+                          int C, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(x_lowres_nhwc && wz_packed && beta && out && ws, "final_lowres_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 4 && H % 2 == 0 && W >= 4 && W % 2 == 0, "final_lowres_fwd: needs even H, W >= 4 (B=%d H=%d W=%d)", B, H, W);
+    SBGM_CHECK(ws_floats >= sbgm_final_lowres_ws_numel(B, H, W), "final_lowres_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    if (sbgm_launch_final_mix(x_lowres_nhwc, in_affine, in_skip, in_act, wz_packed, ws, B, H / 2, W / 2, C, st)) return 1;
+    return sbgm_launch_final_gather(ws, beta, t, sigma, out, B, H / 2, W / 2, st);
 }
 
 int sbgm_event_create(void** ev) { hipEvent_t e; SBGM_HIP(hipEventCreate(&e)); *ev = e; return 0; }

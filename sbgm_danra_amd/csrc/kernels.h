@@ -72,6 +72,20 @@ int sbgm_launch_final_compose(const float* w1_oihw, const float* b1, const float
 // sbgm_launch_tap_stencil over the pixel-major rows d [B][H][W][16] a 16-channel convolution writes (floats 0..8 of a row = the taps)
 int sbgm_launch_tap_gather_rows(const float* d, const float* bias, const float* t, float sigma, float* out, int B, int H, int W,
                                 hipStream_t st);
+// The same block as a low-resolution 1x1 product to the 25 positions of the composed 5x5 stencil and a gather through the bilinear x2
+// (conv_final.hip, second half).  wz_packed: 9 border classes x [C/16][32][16] A-operand images; beta [9]; wz [9][25][C] may be null.
+constexpr int FINAL_LOWRES_ZROW = 28;           // floats per low-res pixel of Z: 25 used + 3 zeros (seven 16-byte stores)
+constexpr int FINAL_LOWRES_MAX_C = 128;
+size_t sbgm_final_lowres_packed_floats(int C);
+size_t sbgm_final_lowres_ws_floats(int B, int h, int w);      // Z [B*h*w][28] + the border strips of the 8 non-interior classes
+int sbgm_launch_final_lowres_pack(const float* w1_oihw, const float* b1, const float* w2_oihw, const float* b2, float* wz, float* beta,
+                                  float* wz_packed, int C, hipStream_t st);
+// x: low-res NHWC [B][h][w][C] (+ affine [B][C/4][2][4], skip, activation on load) -> zbuf (sbgm_final_lowres_ws_floats)
+int sbgm_launch_final_mix(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed, float* zbuf,
+                          int B, int h, int w, int C, hipStream_t st);
+// zbuf -> out [B][1][2h][2w] (/ sigma(t_b) when t is given)
+int sbgm_launch_final_gather(const float* zbuf, const float* beta, const float* t, float sigma, float* out, int B, int h, int w,
+                             hipStream_t st);
 
 // ---- pointwise.hip ---------------------------------------------------------------------------------
 struct PackSrc {
