@@ -730,6 +730,27 @@ int64_t sbgm_exceedance_scores_workspace_bytes(int M, int64_t HW, int T);
 int sbgm_exceedance_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
                            const float* thresholds, int T, int64_t* table, int64_t* count, double* scores, void* workspace,
                            void* stream);
+/* sbgm_ensemble_products (verify_products.hip): per-pixel products of members ens [M][HW]
+ * (2 <= M <= 4095), mask [HW] or NULL.  A pixel is valid when no member is NaN there and the mask admits it; every map is
+ * NaN at an invalid pixel and count int64 [1] = valid pixels.  `quantiles` (Q levels in [0, 1], fp64) and `thresholds` (T
+ * finite values) are HOST arrays, 0 <= Q, T <= 16; with Q (T) = 0 the levels and `quant` (the values and `exceed`) may be NULL.
+ * With the members of a pixel ordered by value, x_(0) <= ... <= x_(M-1) (-0 and +0 compare equal; a zero order statistic is
+ * +0): vmin = x_(0), vmax = x_(M-1), exact.  quant [Q][HW], numpy's default (Hyndman-Fan type 7): h = q (M - 1),
+ * lo = floor(h), g = h - lo, hi = min(lo + 1, M - 1) in fp64 on the host; with a = x_(lo), b = x_(hi) the value is a when
+ * g == 0 or a == b, else (float)(a + g (b - a)) evaluated in fp64 -- so q = 0 is vmin and q = 1 is vmax bit for bit, and the
+ * value lies in [a, b].  exceed [T][HW] = (float)((double)k / M), k = #{x_i >= thr} in fp32.  mean = (float)(sum x_i / M)
+ * and std = (float)sqrt(sum (x_i - mean64)^2 / (M - 1)), both sums in fp64 in member order, the second against the unrounded
+ * fp64 mean.  The order statistics, quant and exceed do not depend on the order of the members; two calls give bit-equal
+ * outputs (no float atomics).  Cost: 2 + 32 ceil(Q / 8) sweeps over the members, each read coalesced; every statistic
+ * lives in registers, so the workspace query returns 0 and `workspace` may be NULL. */
+#define SBGM_PRODUCTS_MAX_QUANTILES 16
+#define SBGM_PRODUCTS_MAX_THRESHOLDS 16
+int64_t sbgm_ensemble_products_workspace_bytes(int M, int64_t HW, int Q, int T);
+int sbgm_ensemble_products(const float* ens, const void* mask, int mask_is_u8, int M, int64_t HW,
+                           const double* quantiles, int Q, const float* thresholds, int T,      /* HOST arrays */
+                           float* mean, float* std, float* vmin, float* vmax,                    /* [HW] */
+                           float* quant /* [Q][HW] */, float* exceed /* [T][HW] */, int64_t* count /* [1] */,
+                           void* workspace, void* stream);
 
 /* ---- before the network ------------------------------------------------------------------------
  * Batch-level condition assembly: channel concatenation of the sorted *_lr fields (utils.py:441-447), classifier-free-

@@ -216,6 +216,8 @@ SIGNATURES = {
                                   [_i64, _vp]),
     "sbgm_exceedance_scores_workspace_bytes": (_i64, [_i, _i64, _i]),
     "sbgm_exceedance_scores": (_i, [_vp, _vp, _vp, _i, _i, _i64, C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp]),
+    "sbgm_ensemble_products_workspace_bytes": (_i64, [_i, _i64, _i, _i]),
+    "sbgm_ensemble_products": (_i, [_vp, _vp, _i, _i, _i64, C.POINTER(_d), _i, C.POINTER(_f), _i] + [_vp] * 9),
 }
 
 ABI_VERSION = 4          # include/sbgm_hip.h: sbgm_abi_version()

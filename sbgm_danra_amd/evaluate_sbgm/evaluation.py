@@ -2,7 +2,8 @@
 files `SampleGenerator` writes, moves them to the GPU once, and computes every statistic with the verification kernels
 (csrc/verify.hip and csrc/verify_spatial.hip via `..verification`): the reference's pixel, spatial and daily statistics plus
 ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra and, on request, neighbourhood scores
-(Fractions Skill Score) and threshold-exceedance scores (Brier, reliability table, ROC area).  Only scalars, maps and
+(Fractions Skill Score), threshold-exceedance scores (Brier, reliability table, ROC area) and ensemble products (mean, spread,
+envelope, quantile and exceedance-probability maps with the coverage of each quantile map).  Only scalars, maps and
 histograms come back to the host.
 Plots are out of scope: the plotting keys are accepted and logged as skipped.
 
@@ -117,6 +118,25 @@ def spatial_scores_config(cfg):
     if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 or n % 2 == 0 for n in scales):
         raise ValueError(f"evaluation.spatial_scores.scales must be odd integers >= 1 (window widths in pixels), got {list(scales)}")
     return [float(t) for t in thresholds], [int(n) for n in scales]
+
+
+def ensemble_products_config(cfg):
+    """(quantiles, thresholds) of the optional evaluation.ensemble_products section — quantile levels in [0, 1], thresholds in
+    the units the generated files hold; either list may be empty, not both — or None when the section is absent"""
+    sec = cfg["evaluation"].get("ensemble_products")
+    if sec is None:
+        return None
+    quantiles, thresholds = sec.get("quantiles") or [], sec.get("thresholds") or []
+    if not isinstance(quantiles, (list, tuple)) or not isinstance(thresholds, (list, tuple)) or not (quantiles or thresholds):
+        raise ValueError("evaluation.ensemble_products needs lists 'quantiles' and 'thresholds', at least one of them non-empty")
+    if len(quantiles) > 16 or len(thresholds) > 16:
+        raise ValueError(f"evaluation.ensemble_products: at most 16 quantiles and 16 thresholds, got {len(quantiles)} and "
+                         f"{len(thresholds)}")
+    if any(isinstance(q, bool) or not isinstance(q, (int, float)) or not math.isfinite(q) or not 0.0 <= q <= 1.0 for q in quantiles):
+        raise ValueError(f"evaluation.ensemble_products.quantiles must be numbers in [0, 1], got {list(quantiles)}")
+    if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) for t in thresholds):
+        raise ValueError(f"evaluation.ensemble_products.thresholds must be finite numbers, got {list(thresholds)}")
+    return [float(q) for q in quantiles], [float(t) for t in thresholds]
 
 
 class Evaluation:
@@ -297,6 +317,38 @@ class Evaluation:
         out.update({k: res[k].tolist() for k in V.EXCEEDANCE_KEYS})
         self.metrics["exceedance_stats"] = out
         self.fields["exceedance_table"] = res["table"]
+        return dict(res, metrics=out)
+
+    def product_statistics(self, quantiles=None, thresholds=None):
+        """ensemble products of the `repeated` samples — mean, standard deviation, minimum, maximum, quantile maps and
+        exceedance-probability maps, all to the fields file — and, per quantile level, the coverage: the fraction of valid
+        pixels with a non-NaN truth that lies at or below the quantile map, beside its nominal value"""
+        if self.generated_sample_type != "repeated":
+            raise ValueError(f"product_statistics needs 'repeated' samples (an ensemble for one condition), not "
+                             f"'{self.generated_sample_type}'")
+        if self.n_samples < 2:
+            raise ValueError(f"product_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        if quantiles is None or thresholds is None:
+            sec = ensemble_products_config(self.cfg)
+            if sec is None:
+                raise ValueError("no quantiles / thresholds given and the config has no evaluation.ensemble_products section")
+            quantiles, thresholds = (sec[0] if quantiles is None else quantiles), (sec[1] if thresholds is None else thresholds)
+        quantiles, thresholds = [float(q) for q in quantiles], [float(t) for t in thresholds]
+        mask = None if self.mask is None else self.mask[0]
+        r = V.ensemble_products(self.gen_imgs, quantiles, thresholds, mask=mask)
+        M, obs = self.n_samples, self.eval_imgs[0]
+        ok = ~(torch.isnan(r["mean"]) | torch.isnan(obs))
+        n_ok = int(ok.sum())
+        coverage = [float(((obs <= qmap) & ok).sum()) / n_ok if n_ok else float("nan") for qmap in r["quantiles"]]
+        res = {k: r[k].cpu().numpy() for k in ("mean", "std", "min", "max", "quantiles", "exceed_prob")}
+        out = {"quantile_levels": quantiles, "thresholds": thresholds, "M": M, "count": int(r["count"]), "coverage": coverage,
+               "coverage_nominal": [(q * (M - 1) + 1) / (M + 1) for q in quantiles],
+               "definition": "quantiles: numpy's default (Hyndman-Fan type 7) over the members of each pixel; exceed_prob = "
+                             "#{members >= threshold} / M; std with ddof 1; coverage = fraction of valid pixels whose truth is <= "
+                             "the quantile map; coverage_nominal = (q (M - 1) + 1) / (M + 1), exact for an exchangeable "
+                             "continuous ensemble where q (M - 1) is an integer"}
+        self.metrics["product_stats"] = out
+        self.fields.update({f"products_{k}": v for k, v in res.items()})
         return dict(res, metrics=out)
 
     def save(self):

@@ -3,7 +3,8 @@ generation type in evaluation.eval_gen_type (default: evaluation.gen_type, then 
 evaluation.eval_stat_methods (default ['pixel_stats', 'spatial_stats'], as in the reference) and write each unit's
 `<type>[_rank<r>]_metrics.json` / `_fields.npz`.  Plotting keys are accepted and logged as skipped.  An
 `evaluation.spatial_scores` section (thresholds, scales) adds the neighbourhood scores for every type and the exceedance
-scores for `repeated`; without it neither runs and the output files hold what they always held."""
+scores for `repeated`; an `evaluation.ensemble_products` section (quantiles, thresholds) adds the ensemble products for
+`repeated`; without a section its statistics do not run and the output files hold what they always held."""
 from __future__ import annotations
 
 import os
@@ -13,11 +14,13 @@ import torch
 
 from ..training_utils import setup_logger
 from ..utils import get_model_string
-from .evaluation import GEN_TYPES, Evaluation, sample_units, spatial_scores_config
+from .evaluation import GEN_TYPES, Evaluation, ensemble_products_config, sample_units, spatial_scores_config
 
 METHODS = {"pixel_stats": "full_pixel_statistics", "spatial_stats": "spatial_statistics", "daily_stats": "daily_statistics",
            "ensemble_stats": "ensemble_statistics", "spectral_stats": "spectral_statistics"}
 SPATIAL_METHODS = {"neighbourhood_stats": "neighbourhood_statistics", "exceedance_stats": "exceedance_statistics"}
+PRODUCT_METHODS = {"product_stats": "product_statistics"}
+SECTION_METHODS = {**SPATIAL_METHODS, **PRODUCT_METHODS}          # run without arguments: they read their section
 PLOT_KEYS = ("plot_examples", "save_figs", "show_plots", "show_figs", "mask_plots", "plot_w_cond", "plot_w_lsm")
 
 
@@ -40,10 +43,13 @@ def eval_stat_methods(cfg):
 
 def unit_statistics(cfg, gen_type):
     """the statistics evaluate mode runs for one generation type, in order: evaluation.eval_stat_methods, then — only with an
-    evaluation.spatial_scores section — 'neighbourhood_stats' and, for 'repeated', 'exceedance_stats'"""
+    evaluation.spatial_scores section — 'neighbourhood_stats' and, for 'repeated', 'exceedance_stats'; then — only with an
+    evaluation.ensemble_products section, for 'repeated' — 'product_stats'"""
     stats = eval_stat_methods(cfg)
     if spatial_scores_config(cfg) is not None:
         stats += ["neighbourhood_stats"] + (["exceedance_stats"] if gen_type == "repeated" else [])
+    if ensemble_products_config(cfg) is not None and gen_type == "repeated":
+        stats += ["product_stats"]
     return stats
 
 
@@ -75,8 +81,8 @@ def evaluation_main(cfg):
             log.info(f"[INFO] Running evaluation for {runner.label}")
             for method in methods[gen_type]:
                 log.info(f"[INFO] Running evaluation method: {method}")
-                if method in SPATIAL_METHODS:
-                    getattr(runner, SPATIAL_METHODS[method])()
+                if method in SECTION_METHODS:
+                    getattr(runner, SECTION_METHODS[method])()
                     continue
                 fn = getattr(runner, METHODS[method])
                 if method in ("pixel_stats", "spatial_stats"):

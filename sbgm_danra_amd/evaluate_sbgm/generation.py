@@ -1,7 +1,9 @@
 """`SampleGenerator` — reference sbgm/evaluate_sbgm/generation.py:40-314 (its live part): draws a batch, runs
 `pc_sampler` with the reference's kwargs, squeezes / moves to CPU exactly like `_run_sampler` (:56-83) and saves
 `gen_samples_* / eval_samples_* / lsm_samples_* / seasons_*` npz files.  Plotting and the stats-file back-transforms
-are out of scope.
+are out of scope.  With an `evaluation.ensemble_products` section, `generate_repeated` also writes
+`ens_products_*`: the per-pixel mean, spread, envelope, quantile and exceedance-probability maps of its members, computed on
+the device (verification.ensemble_products).
 
 Deliberate deviation: the reference writes `self.model.eval` without calling it, so its generation
 runs BatchNorm in training mode.  Here `eval()` IS called; pass `literal_reference_bn=True` to reproduce the
@@ -15,9 +17,11 @@ import numpy as np
 import torch
 
 from .. import parallel
+from .. import verification as V
 from ..score_sampling import edm_heun_sampler, edm_sampler_kwargs, ode_sampler_kwargs, pc_sampler, rk45_sampler
 from ..score_unet import diffusion_coeff_fn, marginal_prob_std_fn
 from ..utils import extract_samples, get_model_string
+from .evaluation import ensemble_products_config
 
 logger = logging.getLogger(__name__)
 
@@ -60,6 +64,7 @@ class SampleGenerator:
         os.makedirs(self.sample_path, exist_ok=True)
         hw = cfg["highres"]["data_size"]
         self.constraint = constraint_mask(cfg, (hw[0], hw[0]))       # raises here, at start, on a sampler that cannot hold pixels
+        self.products = ensemble_products_config(cfg)                # likewise on a malformed evaluation.ensemble_products section
 
     def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond, known=None):
         """the sampler output as [B,H,W] still on the device (what _run_sampler returns after .cpu()).  pc_sampler, as in the
@@ -113,11 +118,13 @@ class SampleGenerator:
             cond_images = [[v[b] for v in per_var] for b in range(cond_images.shape[0])]
         return x, generated, cond_images
 
-    def _generate(self, x, seasons, cond, lsm, topo, suffix, batch=None):
+    def _generate(self, x, seasons, cond, lsm, topo, suffix, batch=None, products=None):
         gen = self._sample_device(x.shape[0] if batch is None else batch, seasons, cond, lsm, topo, known=x)
         cond_out = cond
         if self.cfg["evaluation"].get("transform_back", False):
             x, gen, cond_out = self._apply_backtransforms(x, gen, cond, seasons)
+        if products is not None:
+            self._save_products(gen, products, suffix)
         gen = gen.cpu()
         self._save_npz({"gen_samples": gen, "eval_samples": x, "lsm_samples": lsm, "seasons": seasons,
                         "constraint_mask": self.constraint}, suffix)
@@ -125,6 +132,16 @@ class SampleGenerator:
             for i, k in enumerate(self.cfg["lowres"]["condition_variables"] or []):
                 self._save_npz({f"cond_samples_{k}": torch.stack([im[i] for im in cond_out])}, suffix)
         return gen
+
+    def _save_products(self, gen, products, suffix):
+        """ens_products_<suffix>.npz: the products of the members gen [M,H,W] (on the device, in the units of the gen_samples
+        file), without a mask"""
+        quantiles, thresholds = products
+        r = V.ensemble_products(gen, quantiles, thresholds)
+        arrays = {k: r[k].cpu().numpy() for k in ("mean", "std", "min", "max", "quantiles", "exceed_prob")}
+        np.savez_compressed(os.path.join(self.sample_path, f"ens_products_{suffix}.npz"), **arrays,
+                            quantile_levels=np.asarray(quantiles, dtype=np.float64),
+                            thresholds=np.asarray(thresholds, dtype=np.float64), members=np.int64(gen.shape[0]))
 
     def _save_npz(self, data, suffix):
         for k, v in data.items():
@@ -153,13 +170,18 @@ class SampleGenerator:
 
     def generate_repeated(self):
         """cfg.evaluation.n_repeats samples from ONE conditioning sample, drawn as one batch (independent noise per
-        row); with several ranks the repeats are independent units and are sharded, no collective."""
+        row); with several ranks the repeats are independent units and are sharded, no collective.  With an
+        evaluation.ensemble_products section every rank also writes the products of its own members (at least 2)."""
+        products = self.products
         x, seasons, cond, lsm, topo = self._batch(first_only=True)
         n = int(self.cfg["evaluation"]["n_repeats"])
         rank, world = parallel.world()
         mine = len(parallel.shard_range(n, rank, world))
+        if products is not None and mine == 1:
+            raise ValueError(f"evaluation.ensemble_products needs at least 2 members per rank; rank {rank} of {world} draws 1 of "
+                             f"n_repeats={n}")
         rep = lambda t: None if t is None else t.repeat(mine, *([1] * (t.dim() - 1)))   # noqa: E731
         if not mine:
             return None
         return self._generate(x, rep(seasons), rep(cond), rep(lsm), rep(topo),
-                              f"repeated_n_{n}" + (f"_rank{rank}" if world > 1 else ""), batch=mine)
+                              f"repeated_n_{n}" + (f"_rank{rank}" if world > 1 else ""), batch=mine, products=products)

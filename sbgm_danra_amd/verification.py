@@ -1,6 +1,7 @@
-"""Device-tensor wrappers of the verification kernels (csrc/verify.hip and csrc/verify_spatial.hip): error
-statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra, neighbourhood
-scores (Fractions Skill Score) and threshold-exceedance scores (Brier, reliability table, ROC area).  Every function takes tensors on
+"""Device-tensor wrappers of the verification kernels (csrc/verify.hip, csrc/verify_spatial.hip and csrc/verify_products.hip,
+DESIGN.md §11): error statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power
+spectra, neighbourhood scores (Fractions Skill Score), threshold-exceedance scores (Brier, reliability table, ROC area) and
+ensemble products (per-pixel mean, spread, envelope, quantile and exceedance-probability maps).  Every function takes tensors on
 the ROCm device and returns tensors on the device; arguments and shapes are checked before any launch and nothing is copied
 to the host.  A pixel is valid when gen (every member) and obs are not NaN and the mask admits it (uint8/bool != 0, or float
 > 0.5); every statistic uses the valid pixels only."""
@@ -20,6 +21,8 @@ EXCEEDANCE_KEYS = ("brier", "brier_reliability", "brier_resolution", "brier_unce
 MAX_THRESHOLDS = MAX_SCALES = 16                 # include/sbgm_hip.h: SBGM_SPATIAL_MAX_THRESHOLDS / _SCALES
 MAX_FIELD_SIDE, MAX_FIELD_PIXELS = 2048, 1 << 20
 MAX_EXCEEDANCE_MEMBERS = 4095
+MAX_PRODUCT_QUANTILES = 16                       # include/sbgm_hip.h: SBGM_PRODUCTS_MAX_QUANTILES; thresholds: MAX_THRESHOLDS
+MAX_PRODUCT_MEMBERS = 4095
 DEFAULT_WORKSPACE_BYTES = 256 << 20
 
 
@@ -278,3 +281,37 @@ def exceedance_scores(ens, obs, thresholds, mask=None):
     N.check(N.lib().sbgm_exceedance_scores(e.data_ptr(), o.data_ptr(), N.ptr(m), u8, M, HW, thr, T, table.data_ptr(),
                                            count.data_ptr(), scores.data_ptr(), None, N.stream()))
     return dict(table=table, count=count[0], **{k: scores[i] for i, k in enumerate(EXCEEDANCE_KEYS)})
+
+
+def ensemble_products(ens, quantiles=(), thresholds=(), mask=None):
+    """per-pixel products of members ens [M,H,W] (2 <= M <= 4095), optional mask [H,W].  A pixel is valid when no member is NaN
+    there and the mask admits it; every map is NaN elsewhere.  Returns device tensors: `mean`, `std` (ddof 1), `min`, `max`
+    [H,W] fp32; `quantiles` [Q,H,W], numpy's default (Hyndman-Fan type 7: h = q (M - 1), lo = floor(h), g = h - lo; x_(lo) when
+    g == 0 or x_(lo) == x_(hi), else (float)(x_(lo) + g (x_(hi) - x_(lo))) in fp64 — exact order statistics, so q = 0 is
+    `min` and q = 1 is `max` bit for bit); `exceed_prob` [T,H,W] = #{members >= thr} / M (comparison in fp32); `count` int64
+    scalar, the valid pixels.  Up to 16 quantile levels in [0, 1] and 16 finite thresholds; either list may be empty."""
+    if ens.dim() != 3:
+        raise ValueError(f"ens: expected [M, H, W], got {tuple(ens.shape)}")
+    M, shape = ens.shape[0], tuple(ens.shape[1:])
+    if not 2 <= M <= MAX_PRODUCT_MEMBERS:
+        raise ValueError(f"ensemble_products: M={M} members; need 2..{MAX_PRODUCT_MEMBERS}")
+    qs, thr = [float(q) for q in quantiles], list(thresholds)
+    if len(qs) > MAX_PRODUCT_QUANTILES:
+        raise ValueError(f"ensemble_products: {len(qs)} quantiles; at most {MAX_PRODUCT_QUANTILES}")
+    if not all(math.isfinite(q) and 0.0 <= q <= 1.0 for q in qs):
+        raise ValueError(f"ensemble_products: quantiles must lie in [0, 1], got {qs}")
+    tarr = _thresholds(thr, "ensemble_products") if thr else None
+    _shape_rows(mask, "mask", shape, (1,))
+    e = _fields(ens, "ens")
+    HW = e.shape[1]
+    m, u8, _ = _mask(mask, HW, (1,))
+    Q, T, dev = len(qs), len(thr), e.device
+    mean, std, vmin, vmax = (torch.empty(HW, device=dev) for _ in range(4))
+    quant, exceed = torch.empty(Q, HW, device=dev), torch.empty(T, HW, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    N.check(N.lib().sbgm_ensemble_products(e.data_ptr(), N.ptr(m), u8, M, HW, (C.c_double * Q)(*qs) if Q else None, Q,
+                                           tarr, T, mean.data_ptr(), std.data_ptr(), vmin.data_ptr(), vmax.data_ptr(),
+                                           quant.data_ptr() if Q else None, exceed.data_ptr() if T else None, count.data_ptr(), None,
+                                           N.stream()))
+    return dict(mean=mean.view(shape), std=std.view(shape), min=vmin.view(shape), max=vmax.view(shape),
+                quantiles=quant.view(Q, *shape), exceed_prob=exceed.view(T, *shape), count=count[0])
