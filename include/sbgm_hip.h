@@ -400,6 +400,20 @@ int sbgm_final_lowres_fwd(const float* x_lowres_nhwc, const float* in_affine, co
                           const float* beta, const float* t, float sigma, float* out, float* ws, int64_t ws_floats, int B, int H, int W,
                           int C, void* stream);
 
+/* A resize DecoderBlock's conv_up(up(x)) on a small map with the channels mixed at LOW resolution (conv_uplow.hip, the route the EM / PC /
+ * EDM Heun samplers take for blocks whose output is narrower than 32 pixels): `up` acts per channel and a tap's weight per pixel, so
+ *   Z_tap[co] = sum_ci W[co][ci][k][l] x[ci] (low-res, tap = 3k + l),   out[co][o] = b[co] + sum_{tap, o+tap-1 inside the 2x map} up(Z_tap)[co][o + tap - 1].
+ * pack: w OIHW [C][C][3][3] -> w_taps, the OIHW [9C][C][1][1] weight of the mix (row tap*C + co), and w_packed, its implicit-GEMM image
+ * (sbgm_up_lowres_weight_numel(C) floats each).
+ * fwd: x = the low-resolution NHWC input [B,H/2,W/2,C] -> out NHWC [B,H,W,C]; groups > 0: followed by GroupNorm(groups) with eps and the
+ * affine gamma / beta (both NULL: none), formed inside the gather where a (sample, group) fits one workgroup.  ws:
+ * sbgm_up_lowres_ws_numel(B, H, W, C, groups) floats, 8-byte aligned.  C % 16 == 0, H and W even. */
+int64_t sbgm_up_lowres_weight_numel(int C);
+int64_t sbgm_up_lowres_ws_numel(int B, int H, int W, int C, int groups);
+int sbgm_up_lowres_pack(const float* w_oihw, float* w_taps, float* w_packed, int C, void* stream);
+int sbgm_up_lowres_fwd(const float* x_lowres_nhwc, const float* w_packed, const float* bias, const float* gamma, const float* beta,
+                       int groups, float eps, float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream);
+
 /* ConvTranspose2d(k=2,s=2) = one 1x1 convolution to 4C channels (weights from sbgm_tconv_weight_to_oihw, bias repeated
  * 4x) followed by depth->space; its backward is space->depth followed by the 1x1 convolution's backward. */
 int sbgm_depth_to_space2(const float* x /* [B,H,W,4C] */, float* y /* [B,2H,2W,C] */, int B, int H, int W, int C, void* stream);

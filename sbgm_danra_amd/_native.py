@@ -124,6 +124,10 @@ SIGNATURES = {
     "sbgm_final_lowres_ws_numel": (_i64, [_i, _i, _i]),
     "sbgm_final_lowres_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sbgm_final_lowres_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sbgm_up_lowres_weight_numel": (_i64, [_i]),
+    "sbgm_up_lowres_ws_numel": (_i64, [_i, _i, _i, _i, _i]),
+    "sbgm_up_lowres_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "sbgm_up_lowres_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sbgm_final_block_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i,
                                   C.POINTER(C.c_int), _vp]),
     "sbgm_conv2d_fwd": (_i, [C.POINTER(ConvArgs), _vp]),

@@ -152,9 +152,47 @@ struct FinalBlock : Derived {                                  // up: final_laye
     }
 };
 
+// A resize decoder block whose conv_up runs on a small map (conv_uplow.hip): the 1x1 weight [9 ci][ci] of the low-resolution tap mix.
+// w1 is no Param of the model; its OIHW form and its implicit-GEMM image live in one allocation made by the first prepare() (so a
+// training upload pays a copy of the source and nothing else) and kept at fixed addresses after it: a cached step graph stays valid.
+// Which blocks take the route is decided in sbgm_model::up_lowres_block, from `on` (the configuration) and up_lowres_shape (the size);
+// only those are ever packed.
+struct UpLowres : Derived {                                    // up: residual_layers.<i>.conv_up.weight
+    float* taps = nullptr;
+    Param w1;                                                  // the mix as an ordinary 1x1 convolution weight
+    static bool env_on() { static const bool v = getenv("SBGM_NO_UP_LOWRES") == nullptr; return v; }
+    void build(const ConvW& up, int ci, bool resize_conv) {
+        on = env_on() && resize_conv && ci % 16 == 0;
+        if (!on) return;
+        up.w->feeds = this; up.w->keep_oihw = true;             // the bias is read from its Param at launch: no part of the image
+        w1.name = "conv_up.taps.weight"; w1.kind = P_CONV; w1.numel = (int64_t)sbgm_up_lowres_weight_floats(ci);
+        w1.cout = 9 * ci; w1.cin = ci; w1.kh = w1.kw = 1; w1.cs = ci;
+        w1.floats[IMG_IGEMM] = sbgm_up_lowres_weight_floats(ci);
+    }
+    int prepare(const ConvW& up, hipStream_t st) {
+        if (!on || !dirty) return 0;
+        SBGM_CHECK(up.w->oihw, "decoder: a conv_up weight was never uploaded");
+        const size_t n = align_up((size_t)w1.numel, 64);
+        if (alloc(taps, 2 * n)) return 1;
+        w1.img[IMG_IGEMM] = taps + n;
+        if (sbgm_launch_up_lowres_pack(up.w->oihw, taps, taps + n, w1.cin, st)) return 1;
+        w1.filled = true;
+        dirty = false;
+        return 0;
+    }
+};
+// The static rule: the block sizes at which mix + gather measured faster than upsample2x + conv_up + the norm1 passes (DESIGN.md 3.1,
+// profiles/r10_block_sums.txt): low-res maps of 2x2 to 8x8 with 128 to 512 channels, 2 Ki to 32 Ki low-res elements per sample, at
+// batch 2, 16 and 32.  Nothing outside that range has been measured, so nothing outside it takes the route.
+inline bool up_lowres_shape(int ci, int h, int w) {
+    const long long n = (long long)ci * h * w;
+    return h >= 2 && w >= 2 && h <= 8 && w <= 8 && ci >= 128 && ci <= 512 && n >= 2048 && n <= 32768;
+}
+
 // Which evaluations take the composed stem (+ the run's condition term, null without condition channels) and the composed final block
-// (fin_lowres: as the low-resolution mix + gather instead of the composed 3x3 convolution)
-struct Routes { bool stem = false, fin = false, fin_lowres = false; const float* stem_T = nullptr; };
+// (fin_lowres: as the low-resolution mix + gather instead of the composed 3x3 convolution) and the low-resolution conv_up of the
+// small-map decoder blocks (up_lowres)
+struct Routes { bool stem = false, fin = false, fin_lowres = false, up_lowres = false; const float* stem_T = nullptr; };
 enum Caller { CALL_PLAIN, CALL_SDE_RUN, CALL_MEASURE };
 
 }  // namespace
@@ -177,13 +215,27 @@ struct sbgm_model {
     DecW dec[4];
     ConvW fin_up, fin_conv;
     bool bn_dirty = true;                    // folded BatchNorm (see Derived)
-    Stem stem; FinalBlock fin;
+    Stem stem; FinalBlock fin; UpLowres uplow[4];
     // What every evaluation reads besides the uploaded parameters: the BatchNorm fold and the final block, refreshed from forward_impl
     // for eager calls and from SamplerRun, prepare_ws and autotune ahead of a capture.  The composed stem is NOT refreshed here but only
     // where an EM / PC / EDM Heun run begins: a plain forward or a training-time evaluation must not start packing a 22x22 image.
-    int refresh_derived(hipStream_t st) {
+    // A decoder block's low-resolution image is built only for a caller that takes that route (`up_route`) at an input size H x W at
+    // which the block is eligible: a plain forward, a training-time evaluation or a network whose blocks never qualify packs nothing.
+    int refresh_derived(hipStream_t st, bool up_route = false, int H = 0, int W = 0) {
         if (bn_dirty && fold_bn(st)) return 1;
+        for (int i = 0; i < 4 && up_route; ++i)
+            if (up_lowres_block(i, (H / 32) << i, (W / 32) << i) && uplow[i].prepare(dec[i].up, st)) return 1;
         return fin.prepare(fin_up, fin_conv, st);
+    }
+    // Whether a 3x3 convolution of the decoder takes its input through the fused load path (forward_impl, "Fused path")
+    bool can_fuse(const ConvW& cw, int c_in, int w_out) const {
+        static const bool fused_ok = getenv("SBGM_NO_FUSED_DECODER") == nullptr && !sbgm_conv_switches().no_lds && !sbgm_conv_switches().no_wino;
+        return fused_ok && !cfg.decoder_transpose && w_out >= 32 && w_out % 16 == 0 && c_in % 16 == 0 && cw.w->img[IMG_WINO] != nullptr;
+    }
+    // The one place that decides which blocks run conv_up at low resolution, from block i's low-res map h x w: the configuration
+    // (UpLowres::on), a block that is on the unfused path today, and the static rule on its size
+    bool up_lowres_block(int i, int h, int w) const {
+        return uplow[i].on && h >= 1 && w >= 1 && !can_fuse(dec[i].up, dec[i].cin, 2 * w) && up_lowres_shape(dec[i].cin, h, w);
     }
     // The one place that decides who evaluates through which form of the network, from the kind of caller:
     //   the EM / PC / EDM Heun driver: composed stem and composed final block, for the duration of a run (~SamplerRun ends them);
@@ -194,7 +246,7 @@ struct sbgm_model {
     //   (bound 9), where the projection path gives 464 / 464; a stem that rounds differently flips such decisions too.
     Routes routes;
     void set_routes(Caller c, const float* stem_T = nullptr) {
-        routes = Routes{c == CALL_SDE_RUN && stem.on, c != CALL_PLAIN && fin.on, c != CALL_PLAIN && fin.on && fin.lowres,
+        routes = Routes{c == CALL_SDE_RUN && stem.on, c != CALL_PLAIN && fin.on, c != CALL_PLAIN && fin.on && fin.lowres, c != CALL_PLAIN,
                         c == CALL_SDE_RUN ? stem_T : nullptr};
     }
     size_t stem_t_bytes(int B, int H, int W) const { return stem.on && cin_total > 1 ? align_up((size_t)B * H * W * 4 * 4, 256) : 0; }
@@ -515,6 +567,7 @@ int sbgm_model::build(const sbgm_model_config& c) {
         for (auto& b : layers[li]) { place_bn(b.bn1, b.cout); place_bn(b.bn2, b.cout); if (b.has_ds) place_bn(b.dsbn, b.cout); }
     SBGM_HIP(hipMalloc(&d_state, sizeof(SamplerState)));
     stem.build(conv1.w, conv2.w);
+    for (int i = 0; i < 4; ++i) uplow[i].build(dec[i].up, dec[i].cin, !c.decoder_transpose);
     return fin.build(fin_up, fin_conv, dec[3].cout, !c.decoder_transpose);   // after place(): the route needs conv_up's Winograd image
 }
 
@@ -650,7 +703,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
         SBGM_CHECK(fwd_need(B, H, W, bn_train) <= ws_bytes, "forward: workspace not prepared for B=%d H=%d W=%d", B, H, W);
         ws_used = 0;
     }
-    if (refresh_derived(st)) return 1;
+    if (refresh_derived(st, routes.up_lowres, H, W)) return 1;
     partial = wsalloc(PARTIAL_FLOATS);
     if (!partial) return 1;
 
@@ -779,10 +832,6 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     // passes everywhere.
     const int G_of = cfg.gn_groups;
     auto groups = [&](int c) { return cfg.decoder_norm == SBGM_NORM_GROUP ? std::max(1, std::min(G_of, c)) : c; };
-    static const bool fused_ok = getenv("SBGM_NO_FUSED_DECODER") == nullptr && !sbgm_conv_switches().no_lds && !sbgm_conv_switches().no_wino;
-    auto can_fuse = [&](const ConvW& cw, int c_in, int w_out) {
-        return fused_ok && !cfg.decoder_transpose && w_out >= 32 && w_out % 16 == 0 && c_in % 16 == 0 && cw.w->img[IMG_WINO] != nullptr;
-    };
     struct Pending { const float* raw; const float* affine; const float* skip; int act; bool live; } pend{nullptr, nullptr, nullptr, SBGM_ACT_NONE, false};
     // statistics of `t` [B][hw][c] for its GroupNorm: from the convolution epilogue (chunks > 0) or a separate partial pass
     auto ensure_stats = [&](const float* t, int hw, int c, int& chunks) -> int {
@@ -815,8 +864,24 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
         float* a = wsalloc((size_t)B * oh * ow * d.cin);
         if (!a) return 1;
         ConvParams p{};
-        int gn1_chunks = 0;
-        if (cfg.decoder_transpose) {                 // ConvTranspose2d: 1x1 conv to 4*cin phase-major channels, then depth -> space
+        int gn1_chunks = 0, normed1 = 0;
+        // A small-map block (up_lowres): conv_up(up(cur)) as the 1x1 tap mix on the low-res map and the gather, which also forms norm1
+        // where a workgroup holds a whole group.  Z is reserved on every route, so the workspace's high-water mark, measured by a plain
+        // evaluation, covers the route as well; a tuning evaluation runs both forms, so the mix and the parent convolution are both tuned.
+        const bool lowres = up_lowres_block(i, ch, cw_);
+        float* zb = lowres ? wsalloc(sbgm_up_lowres_ws_floats(B, ch, cw_, d.cin)) : nullptr;
+        if (lowres && !zb) return 1;
+        const bool take_lowres = lowres && routes.up_lowres;
+        if (take_lowres) {
+            SBGM_CHECK(!pend.live, "decoder: a pending normalisation reached a low-resolution conv_up");
+            p.x = cur; p.out = zb; p.B = B; p.H = ch; p.W = cw_; p.Cs = d.cin; p.Cout = 9 * d.cin;
+            if (conv(ConvGeom{1, 1, 1, 0}, p, uplow[i].w1, st)) return 1;
+            const bool gn = cfg.decoder_norm == SBGM_NORM_GROUP;
+            if (sbgm_launch_up_gather(zb, d.up.b->dev(), a, d.n1g ? d.n1g->dev() : nullptr, d.n1b ? d.n1b->dev() : nullptr, stats,
+                                      gn ? groups(d.cin) : 0, GN_EPS, B, ch, cw_, d.cin, &gn1_chunks, &normed1, st)) return 1;
+        }
+        if (take_lowres && !tuning) {                // `a` (and what the gather did of norm1) stands
+        } else if (cfg.decoder_transpose) {          // ConvTranspose2d: 1x1 conv to 4*cin phase-major channels, then depth -> space
             float* up = wsalloc((size_t)B * oh * ow * d.cin);
             if (!up) return 1;
             p.x = cur; p.out = up; p.bias = d.up.b->dev(); p.B = B; p.H = ch; p.W = cw_; p.Cs = d.cin; p.Cout = 4 * d.cin;
@@ -827,14 +892,16 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             p.gn_stats = stats; p.gn_groups = groups(d.cin);        // GroupNorm statistics in the epilogue when the LDS kernel runs
             if (conv(ConvGeom{3, 3, 1, 1}, p, *d.up.w, st)) return 1;
             gn1_chunks = sbgm_tile_gn_chunks(p, last_tile);
+            normed1 = 0;
         }
         float* c2 = wsalloc((size_t)B * oh * ow * d.cout);
         if (!c2) return 1;
-        if (ensure_stats(a, oh * ow, d.cin, gn1_chunks)) return 1;
+        if (!normed1 && ensure_stats(a, oh * ow, d.cin, gn1_chunks)) return 1;
         p = ConvParams{};
         p.B = B; p.H = oh; p.W = ow; p.Cs = d.cin;
         p.x = a; p.out = c2; p.bias = d.conv.b->dev(); p.Cout = d.cout;
-        if (can_fuse(d.conv, d.cin, ow)) {           // norm1 applied while `conv` stages its patch
+        if (normed1) {                               // the gather stored norm1's output
+        } else if (can_fuse(d.conv, d.cin, ow)) {    // norm1 applied while `conv` stages its patch
             float* aff1 = wsalloc((size_t)B * d.cin * 2);
             if (!aff1) return 1;
             if (sbgm_launch_gn_finalize(stats, gn1_chunks, d.n1g ? d.n1g->dev() : nullptr, d.n1b ? d.n1b->dev() : nullptr, nullptr, aff1, B, oh * ow,
@@ -1066,7 +1133,7 @@ struct SamplerRun {
             SBGM_HIP(hipEventCreateWithFlags(&m->ev_replayed, hipEventDisableTiming));
         }
         top = m->ws + m->ws_bytes - keep();
-        if (m->refresh_derived(st)) return 1;
+        if (m->refresh_derived(st, a.kind != SBGM_SAMPLER_RK45, H, W)) return 1;
         if (guided && conds.add_unconditional(a, m->cfg)) return 1;
         if (a.kind != SBGM_SAMPLER_RK45) {
             // The run's condition term T: the composed filter over the channels that do not change from step to step (lsm, topo, cond_img,
@@ -1562,7 +1629,7 @@ int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, in
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (m->ensure_ws(2 * m->ws_need(B, H, W))) return 1;
-    if (m->refresh_derived(st)) return 1;
+    if (m->refresh_derived(st, true, H, W)) return 1;
     if (m->dummy_forward(B, H, W, true, st)) return 1;
     // the tuned plan's high-water mark, then the slab at its final size: what runs next (a sampler capturing its step) finds both settled
     if (m->dummy_forward(B, H, W, false, st)) return 1;
@@ -1699,6 +1766,41 @@ int sbgm_final_lowres_fwd(const float* x_lowres_nhwc, const float* in_affine, co
     SBGM_CHECK(ws_floats >= sbgm_final_lowres_ws_numel(B, H, W), "final_lowres_fwd: workspace of %lld floats is too small", (long long)ws_floats);
     if (sbgm_launch_final_mix(x_lowres_nhwc, in_affine, in_skip, in_act, wz_packed, ws, B, H / 2, W / 2, C, st)) return 1;
     return sbgm_launch_final_gather(ws, beta, t, sigma, out, B, H / 2, W / 2, st);
+}
+
+// ---- a small-map decoder block's conv_up at low resolution (conv_uplow.hip; the engine's up_lowres route) ----------------------------
+int64_t sbgm_up_lowres_weight_numel(int C) { return C >= 16 && C % 16 == 0 ? (int64_t)sbgm_up_lowres_weight_floats(C) : 0; }
+// Z, then the chunk partials of the GroupNorm fallback ([B][64][G][2] doubles)
+int64_t sbgm_up_lowres_ws_numel(int B, int H, int W, int C, int groups) {
+    if (B < 1 || H < 2 || W < 2 || C < 16) return 0;
+    return (int64_t)sbgm_up_lowres_ws_floats(B, H / 2, W / 2, C) + (int64_t)B * 64 * std::max(groups, 0) * 4;
+}
+
+int sbgm_up_lowres_pack(const float* w_oihw, float* w_taps, float* w_packed, int C, void* stream) {
+    return sbgm_launch_up_lowres_pack(w_oihw, w_taps, w_packed, C, (hipStream_t)stream);
+}
+
+int sbgm_up_lowres_fwd(const float* x_lowres_nhwc, const float* w_packed, const float* bias, const float* gamma, const float* beta,
+                       int groups, float eps, float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(x_lowres_nhwc && w_packed && bias && out && ws, "up_lowres_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 2 && H % 2 == 0 && W >= 2 && W % 2 == 0 && C >= 16 && C % 16 == 0 && groups >= 0,
+               "up_lowres_fwd: needs even H, W >= 2 and C %% 16 == 0 (B=%d H=%d W=%d C=%d)", B, H, W, C);
+    SBGM_CHECK(ws_floats >= sbgm_up_lowres_ws_numel(B, H, W, C, groups), "up_lowres_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    const int h = H / 2, w = W / 2;
+    const ConvGeom lin{1, 1, 1, 0};
+    ConvParams p{};
+    p.x = x_lowres_nhwc; p.out = ws; p.B = B; p.H = h; p.W = w; p.Cs = C; p.Cout = 9 * C;
+    const ConvImages im{{w_packed, nullptr, nullptr, nullptr}};
+    ConvTile ct = sbgm_static_tile(lin, p, im);
+    ct.splits = 1;                                   // no split-K scratch here
+    if (sbgm_launch_tile(lin, p, im, ct, nullptr, st)) return 1;
+    double* stats = reinterpret_cast<double*>(ws + sbgm_up_lowres_ws_floats(B, h, w, C));
+    int chunks = 0, normed = 0;
+    if (sbgm_launch_up_gather(ws, bias, out, gamma, beta, groups > 0 ? stats : nullptr, groups, eps, B, h, w, C, &chunks, &normed, st)) return 1;
+    if (groups == 0 || normed) return 0;
+    if (chunks == 0 && sbgm_launch_gn_partial(out, stats, B, H * W, C, groups, &chunks, st)) return 1;
+    return sbgm_launch_groupnorm_apply(out, out, gamma, beta, nullptr, nullptr, SBGM_ACT_NONE, B, H * W, C, groups, eps, stats, chunks, st);
 }
 
 int sbgm_event_create(void** ev) { hipEvent_t e; SBGM_HIP(hipEventCreate(&e)); *ev = e; return 0; }

@@ -87,6 +87,17 @@ int sbgm_launch_final_mix(const float* x, const float* in_affine, const float* i
 int sbgm_launch_final_gather(const float* zbuf, const float* beta, const float* t, float sigma, float* out, int B, int h, int w,
                              hipStream_t st);
 
+// ---- conv_uplow.hip: a small-map decoder block's conv_up(up(x)) as a low-resolution 1x1 product to the 9 taps and a gather ----------
+size_t sbgm_up_lowres_weight_floats(int C);                  // 9 C^2: the OIHW [9C][C][1][1] weight and its implicit-GEMM image alike
+size_t sbgm_up_lowres_ws_floats(int B, int h, int w, int C);  // Z [B*h*w][9C]
+// w OIHW [C][C][3][3] -> w_taps [9C][C] (row tap * C + co) -> w_packed, the image a 1x1 convolution from C to 9C channels reads
+int sbgm_launch_up_lowres_pack(const float* w_oihw, float* w_taps, float* w_packed, int C, hipStream_t st);
+// Z -> out [B][2h][2w][C] = conv_up(up(x)) + bias.  G > 0 with stats: the GroupNorm of G groups that follows.  *normed_out = 1: out
+// is already normalised (gamma / beta applied, either may be null together); else *chunks_out > 0: raw map + that many chunk partials
+// in stats ([b][chunk][G][2], what sbgm_launch_groupnorm_apply reduces); else the raw map alone.
+int sbgm_launch_up_gather(const float* z, const float* bias, float* out, const float* gamma, const float* beta, double* stats, int G,
+                          float eps, int B, int h, int w, int C, int* chunks_out, int* normed_out, hipStream_t st);
+
 // ---- pointwise.hip ---------------------------------------------------------------------------------
 struct PackSrc {
     const float* ptr[4];   // NCHW sources, concatenated along C in this order
