@@ -5,9 +5,9 @@
 //   Z_tap[co]             = sum_ci W[co][ci][k][l] x[ci]                       on the low-resolution map
 // The 9 tap mixes are ONE 1x1 product with N = 9 C over a quarter of the pixels (2 C^2 9/4 flop per output pixel instead of 2 C^2 9),
 // run by the ordinary implicit-GEMM convolution from the image sbgm_launch_up_lowres_pack builds; Z is [B h w][9 C], row n = tap C + co.
-// The gather below finishes the block: 9 taps x 4 bilinear neighbours per output element from Z rows staged in LDS, the bias, and, where
-// a workgroup holds a whole (sample, GroupNorm group), norm1 itself.  A tap whose intermediate pixel lies outside the high-res map is
-// skipped: that is the zero padding of conv_up's input.
+// The gather below finishes the block from Z rows staged in LDS: the 9 taps through the bilinear x2 as a horizontal and a vertical pass
+// (`up` is a tensor product of its two axes), the bias, and, where a workgroup holds a whole (sample, GroupNorm group), norm1 itself.
+// A tap whose intermediate pixel lies outside the high-res map is skipped: that is the zero padding of conv_up's input.
 #include "common.h"
 #include "kernels.h"
 
@@ -54,62 +54,133 @@ struct UpGatherArgs {
     int rows;                // high-res rows per chunk (even; the whole map when gridDim.y == 1)
     int mode;
     float eps;
+    int tps;                 // taps staged at a time: 9 (all of Z beside R) or 3 (one tap row ky at a time, three stagings)
+    int rpp;                 // rows a sweep of the workgroup covers: blockDim / (2 w CW / 4), at least 1
+    int sl, st, sq;          // blockDim as a step of the staging index: sl pixels + st taps + sq channel quads
 };
 
-// Grid (channel slices, row chunks, B).  A workgroup stages the low-res rows its chunk reads, all 9 taps of its CW channels, as
-// s[pixel][tap][CW]; a thread owns a channel quad of an output pixel (lanes along the channels: 16-byte LDS reads of consecutive
-// addresses), sums the taps in a fixed order and stores the raw value.  With statistics every thread adds its values in fp64, the
-// waves combine by butterfly and the workgroup in wave order: no atomics, the same sum in every run.  UP_NORMED (one chunk): the
-// workgroup holds the whole (sample, group), so each thread reads back what it stored and applies norm1 as groupnorm_apply_kernel does.
-__global__ __launch_bounds__(256) void up_gather_kernel(UpGatherArgs a) {
+constexpr int UP_MAX_THREADS = 1024;
+constexpr int UP_MAX_ITEMS = 8;      // the largest register-resident instantiation (16 spills under the 128 VGPRs of 1024 threads)
+
+// Grid (channel slices, row chunks, B).  The bilinear x2 is separable, so a workgroup works in two passes over the low-res rows its
+// chunk reads.  Z rows are staged as z[pixel][tap][CW] (all 9 taps, or one tap row ky at a time where 9 do not fit beside R);
+//   horizontal  R[ky][j][ox] = sum_kx in_x(kx) (wx Z[ky, kx][j][xa] + (1 - wx) Z[ky, kx][j][xb])       low-res row j, high-res column ox
+//   vertical    out[oy][ox]  = b + sum_ky in_y(ky) (wy R[ky][ya][ox] + (1 - wy) R[ky][yb][ox])
+// R lives in LDS behind Z.  A thread keeps one (column, channel quad) for both sweeps (lanes along the channels: 16-byte LDS accesses
+// of consecutive addresses) and walks the rows r0, r0 + rpp, ..: the column's geometry is computed once, a row's from the loop counter.
+// With statistics every thread adds its values in fp64 in row order, the waves combine by butterfly and the workgroup in wave order: no
+// atomics, the same sum in every run.  UP_NORMED (one chunk: the workgroup holds the whole (sample, group)) with NI > 0: the thread's
+// NI output values stay in registers across the statistics barrier and are stored once, normalised as groupnorm_apply_kernel does.
+// NI == 0 is the general form (any number of columns and rows per thread): raw values are stored as they are formed, and UP_NORMED
+// reads back what the thread itself stored.
+template <int NI>
+__global__ __launch_bounds__(UP_MAX_THREADS) void up_gather_kernel(UpGatherArgs a) {
     extern __shared__ __attribute__((aligned(16))) float s[];
-    __shared__ double red[8];
-    const int tid = threadIdx.x, slice = blockIdx.x, chunk = blockIdx.y, b = blockIdx.z;
+    __shared__ double red[2 * UP_MAX_THREADS / 64];
+    const int tid = threadIdx.x, nt = blockDim.x, slice = blockIdx.x, chunk = blockIdx.y, b = blockIdx.z;
     const int H = 2 * a.h, W = 2 * a.w, C = a.C, qs = a.CW >> 2, c0 = slice * a.CW, cq = C >> 2;
     const int y0 = chunk * a.rows, y1 = min(H, y0 + a.rows);
-    const int ly0 = up_lo(max(y0 - 1, 0)), ly1 = up_hi(min(y1, H - 1), a.h);
-    const int row_q = 9 * qs, n_q = (ly1 - ly0 + 1) * a.w * row_q;
-    const f32x4* const zq = reinterpret_cast<const f32x4*>(a.z) + ((size_t)b * a.h + ly0) * a.w * (size_t)(9 * cq) + (c0 >> 2);
-    f32x4* const s4 = reinterpret_cast<f32x4*>(s);
-    for (int i = tid; i < n_q; i += 256) {
-        const int lp = i / row_q, r = i - lp * row_q, tap = r / qs, q = r - tap * qs;
-        s4[i] = zq[(size_t)lp * (9 * cq) + tap * cq + q];
+    const int ly0 = up_lo(max(y0 - 1, 0)), ly1 = up_hi(min(y1, H - 1), a.h), nl = ly1 - ly0 + 1;
+    const int tps = a.tps, row_q = tps * qs, n_px = nl * a.w;
+    f32x4* const z4 = reinterpret_cast<f32x4*>(s);
+    f32x4* const r4 = z4 + n_px * row_q;                       // R[3][nl][W][qs]
+    const int col = W * qs, r0 = tid / col, cid0 = tid - r0 * col;
+    const bool active = r0 < a.rpp;                            // the threads past the last whole sweep row only stage
+    // staging: item i = (pixel lp, tap, quad q) flattened, i = tid, tid + nt, ..; the step is applied with carries
+    const int lp0 = tid / row_q, rem0 = tid - lp0 * row_q, tap0 = rem0 / qs, q0 = rem0 - tap0 * qs;
+    for (int stage = 0; stage * tps < 9; ++stage) {
+        if (stage) __syncthreads();                            // the horizontal pass of the tap row before is done with Z
+        const f32x4* const zq = reinterpret_cast<const f32x4*>(a.z) + ((size_t)b * a.h + ly0) * a.w * (size_t)(9 * cq) + (c0 >> 2) + stage * tps * cq;
+        int lp = lp0, tap = tap0, q = q0, i = tid;
+        while (lp < n_px) {
+            f32x4 v[4];
+            int at[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {                      // four loads in flight
+                at[u] = lp < n_px ? i : -1;
+                if (lp < n_px) v[u] = zq[(size_t)lp * (9 * cq) + tap * cq + q];
+                i += nt;
+                q += a.sq;
+                if (q >= qs) { q -= qs; ++tap; }
+                tap += a.st;
+                if (tap >= tps) { tap -= tps; ++lp; }
+                lp += a.sl;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (at[u] >= 0) z4[at[u]] = v[u];
+        }
+        __syncthreads();
+        for (int cid = cid0; cid < col && active; cid += nt) {
+            const int ox = cid / qs, q = cid - ox * qs;
+            const UpAxis rx = up_axis(ox, a.w);
+            for (int j = r0; j < nl; j += a.rpp) {
+                const f32x4* const zr = z4 + j * a.w * row_q + q;
+#pragma unroll
+                for (int kl = 0; kl < 3; ++kl) {
+                    if (tps == 3 && kl) break;
+                    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) {
+                        if (!rx.in[kx]) continue;
+                        const f32x4* const t = zr + (kl * 3 + kx) * qs;
+                        const float wx = rx.wa[kx];
+                        acc += wx * t[rx.a[kx] * row_q] + (1.f - wx) * t[rx.b[kx] * row_q];
+                    }
+                    r4[(((stage + kl) * nl + j) * W + ox) * qs + q] = acc;
+                }
+            }
+        }
     }
     __syncthreads();
-    const int items = (y1 - y0) * W * qs;
     f32x4* const ob = reinterpret_cast<f32x4*>(a.out) + (size_t)b * H * W * cq + (c0 >> 2);
     double sm = 0.0, sq = 0.0;
-    for (int i = tid; i < items; i += 256) {
-        const int px = i / qs, q = i - px * qs, py = px / W, ox = px - py * W, oy = y0 + py;
-        const UpAxis ry = up_axis(oy, a.h), rx = up_axis(ox, a.w);
-        f32x4 v = *reinterpret_cast<const f32x4*>(a.bias + c0 + 4 * q);
+    // one output element from the column's R entries (rq = r4 + ox qs + q)
+    auto vertical = [&](const f32x4* rq, int oy, f32x4 v) {
+        const UpAxis ry = up_axis(oy, a.h);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             if (!ry.in[ky]) continue;
-            const int ra = (ry.a[ky] - ly0) * a.w, rb = (ry.b[ky] - ly0) * a.w;
+            const f32x4* const t = rq + ky * nl * col;
             const float wy = ry.wa[ky];
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                if (!rx.in[kx]) continue;
-                const f32x4* const t = s4 + (ky * 3 + kx) * qs + q;
-                const float wx = rx.wa[kx];
-                const f32x4 top = wx * t[(ra + rx.a[kx]) * row_q] + (1.f - wx) * t[(ra + rx.b[kx]) * row_q];
-                const f32x4 bot = wx * t[(rb + rx.a[kx]) * row_q] + (1.f - wx) * t[(rb + rx.b[kx]) * row_q];
-                v += wy * top + (1.f - wy) * bot;
-            }
+            v += wy * t[(ry.a[ky] - ly0) * col] + (1.f - wy) * t[(ry.b[ky] - ly0) * col];
         }
-        ob[((size_t)oy * W + ox) * cq + q] = v;
-        if (a.mode != UP_RAW) {
+        return v;
+    };
+    f32x4 keep[NI > 0 ? NI : 1];
+    if constexpr (NI > 0) {                                    // one column per thread, at most NI rows: the values stay in registers
+        const int ox = cid0 / qs, q = cid0 - ox * qs;
+        const f32x4 bq = *reinterpret_cast<const f32x4*>(a.bias + c0 + 4 * q);
+#pragma unroll
+        for (int k = 0; k < NI; ++k) {
+            const int oy = r0 + k * a.rpp;
+            if (!active || oy >= H) continue;
+            const f32x4 v = vertical(r4 + cid0, oy, bq);
+            keep[k] = v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { sm += (double)v[e]; sq += (double)v[e] * (double)v[e]; }
         }
+    } else {
+        for (int cid = cid0; cid < col && active; cid += nt) {
+            const int ox = cid / qs, q = cid - ox * qs;
+            const f32x4 bq = *reinterpret_cast<const f32x4*>(a.bias + c0 + 4 * q);
+            for (int oy = y0 + r0; oy < y1; oy += a.rpp) {
+                const f32x4 v = vertical(r4 + cid, oy, bq);
+                ob[((size_t)oy * W + ox) * cq + q] = v;
+                if (a.mode != UP_RAW) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { sm += (double)v[e]; sq += (double)v[e] * (double)v[e]; }
+                }
+            }
+        }
+        if (a.mode == UP_RAW) return;
     }
-    if (a.mode == UP_RAW) return;
     sm = wave_sum_d(sm);
     sq = wave_sum_d(sq);
     if ((tid & 63) == 0) { red[2 * (tid >> 6)] = sm; red[2 * (tid >> 6) + 1] = sq; }
     __syncthreads();
-    const double tot = ((red[0] + red[2]) + red[4]) + red[6], tot2 = ((red[1] + red[3]) + red[5]) + red[7];
+    double tot = red[0], tot2 = red[1];
+    for (int wv = 1; wv < (nt >> 6); ++wv) { tot += red[2 * wv]; tot2 += red[2 * wv + 1]; }
     if (a.mode == UP_PARTIALS) {
         if (tid == 0) {
             double* o = a.stats + (((size_t)b * gridDim.y + chunk) * gridDim.x + slice) * 2;
@@ -122,21 +193,54 @@ __global__ __launch_bounds__(256) void up_gather_kernel(UpGatherArgs a) {
     const double mean = tot * inv_n;
     const double var = fmax(tot2 * inv_n - mean * mean, 0.0);
     const float mu = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)a.eps));
-    for (int i = tid; i < items; i += 256) {
-        const int px = i / qs, q = i - px * qs, py = px / W, ox = px - py * W, oy = y0 + py;
-        const int c = c0 + 4 * q;
+    for (int cid = cid0; cid < col && active; cid += nt) {
+        const int ox = cid / qs, q = cid - ox * qs, c = c0 + 4 * q;
         f32x4 g = f32x4{rstd, rstd, rstd, rstd}, bt = f32x4{0.f, 0.f, 0.f, 0.f};
         if (a.gamma != nullptr) {
             g *= *reinterpret_cast<const f32x4*>(a.gamma + c);
             bt = *reinterpret_cast<const f32x4*>(a.beta + c);
         }
-        f32x4* const o = ob + ((size_t)oy * W + ox) * cq + q;
-        *o = (*o - mu) * g + bt;
+        f32x4* const o = ob + (size_t)ox * cq + q;
+        if constexpr (NI > 0) {
+#pragma unroll
+            for (int k = 0; k < NI; ++k) {
+                const int oy = r0 + k * a.rpp;
+                if (oy < H) o[(size_t)oy * W * cq] = (keep[k] - mu) * g + bt;
+            }
+        } else {
+            for (int oy = y0 + r0; oy < y1; oy += a.rpp) {
+                f32x4* const e = o + (size_t)oy * W * cq;
+                *e = (*e - mu) * g + bt;
+            }
+        }
     }
 }
 
-constexpr size_t UP_LDS_MAX = 160 * 1024 - 512;      // staged Z rows of one workgroup (the reduction scratch is static)
+constexpr size_t UP_LDS_MAX = 160 * 1024 - 512;      // staged Z rows and R of one workgroup (the reduction scratch is static)
 constexpr int UP_MAX_CHUNKS = 64;                    // as many chunk partials as groupnorm_apply reduces
+
+// Threads per workgroup: the grid of the network's blocks is one workgroup per CU, so this is the occupancy (DESIGN.md 3.1 has the
+// measurements).  SBGM_UP_GATHER_THREADS = 256 / 512 / 1024 overrides it for such a measurement.
+int up_threads() {
+    static const int v = [] {
+        const char* e = getenv("SBGM_UP_GATHER_THREADS");
+        const int n = e ? atoi(e) : 0;
+        return n == 256 || n == 512 || n == 1024 ? n : 1024;
+    }();
+    return v;
+}
+
+template <int NI>
+int up_gather_launch(const UpGatherArgs& a, dim3 grid, int threads, size_t lds, hipStream_t st) {
+    static bool attr = false;
+    if (lds > 64 * 1024 && !attr) {
+        SBGM_HIP(hipFuncSetAttribute((const void*)up_gather_kernel<NI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)UP_LDS_MAX));
+        attr = true;
+    }
+    hipLaunchKernelGGL(up_gather_kernel<NI>, grid, dim3(threads), lds, st, a);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
 
 }  // namespace
 
@@ -162,12 +266,16 @@ int sbgm_launch_up_gather(const float* z, const float* bias, float* out, const f
     bool aware = G > 0 && stats != nullptr && C % G == 0 && (C / G) % 4 == 0;
     int CW = aware ? C / G : 16;
     const int H = 2 * h;
-    int rows = H, chunks = 1;
-    auto fit = [&]() {      // the chunking at which a workgroup's Z rows fit the LDS; false: not even two output rows do
-        const size_t px_bytes = (size_t)9 * CW * 4;
-        rows = H; chunks = 1;
-        if ((size_t)h * w * px_bytes <= UP_LDS_MAX) return true;
-        const size_t lo_rows = UP_LDS_MAX / ((size_t)w * px_bytes);      // an even chunk of R rows reads R / 2 + 2 low-res rows
+    int rows = H, chunks = 1, tps = 9;
+    // The LDS plan, per low-res pixel of the slice: Z with all 9 taps beside R (36 + 24 bytes per channel); else Z one tap row at a time
+    // beside R (12 + 24); else row chunks of the latter.  false: not even two output rows fit
+    auto fit = [&]() {
+        const size_t ch_bytes = (size_t)CW * 4;
+        rows = H; chunks = 1; tps = 9;
+        if ((size_t)h * w * 15 * ch_bytes <= UP_LDS_MAX) return true;
+        tps = 3;
+        if ((size_t)h * w * 9 * ch_bytes <= UP_LDS_MAX) return true;
+        const size_t lo_rows = UP_LDS_MAX / ((size_t)w * 9 * ch_bytes);      // an even chunk of R rows reads R / 2 + 2 low-res rows
         if (lo_rows < 3) return false;
         rows = (int)std::min<size_t>(2 * (lo_rows - 2), (size_t)H);
         chunks = (H + rows - 1) / rows;
@@ -177,15 +285,22 @@ int sbgm_launch_up_gather(const float* z, const float* bias, float* out, const f
     if (aware && (!ok || chunks > UP_MAX_CHUNKS)) { aware = false; CW = 16; ok = fit(); }
     SBGM_CHECK(ok && chunks <= 65535, "up_gather: a low-res row of %d pixels does not fit the LDS", w);
     const int lo_rows = chunks == 1 ? h : std::min(h, rows / 2 + 2);
-    const size_t lds = (size_t)lo_rows * w * 9 * CW * 4;
-    static bool attr = false;
-    if (lds > 64 * 1024 && !attr) {
-        SBGM_HIP(hipFuncSetAttribute((const void*)up_gather_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)UP_LDS_MAX));
-        attr = true;
-    }
+    const size_t lds = (size_t)lo_rows * w * (tps + 6) * CW * 4;
+    const int threads = up_threads(), qs = CW / 4, col = 2 * w * qs, row_q = tps * qs;
     UpGatherArgs a{z, bias, out, gamma, beta, stats, h, w, C, CW, rows, aware ? (chunks == 1 ? UP_NORMED : UP_PARTIALS) : UP_RAW, eps};
-    hipLaunchKernelGGL(up_gather_kernel, dim3(C / CW, chunks, B), dim3(256), lds, st, a);
-    SBGM_LAUNCH_CHECK();
+    a.tps = tps;
+    a.rpp = std::max(1, threads / col);
+    a.sl = threads / row_q; a.st = threads % row_q / qs; a.sq = threads % qs;
+    // register-resident norm1: one column per thread and at most UP_MAX_ITEMS rows of it
+    const int items = col <= threads ? (H + a.rpp - 1) / a.rpp : UP_MAX_ITEMS + 1;
+    const dim3 grid(C / CW, chunks, B);
+    int rc;
+    if (a.mode != UP_NORMED || items > UP_MAX_ITEMS) rc = up_gather_launch<0>(a, grid, threads, lds, st);
+    else if (items <= 1) rc = up_gather_launch<1>(a, grid, threads, lds, st);
+    else if (items <= 2) rc = up_gather_launch<2>(a, grid, threads, lds, st);
+    else if (items <= 4) rc = up_gather_launch<4>(a, grid, threads, lds, st);
+    else rc = up_gather_launch<8>(a, grid, threads, lds, st);
+    if (rc) return 1;
     *chunks_out = a.mode == UP_PARTIALS ? chunks : 0;
     *normed_out = a.mode == UP_NORMED;
     return 0;

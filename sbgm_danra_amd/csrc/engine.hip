@@ -183,7 +183,8 @@ struct UpLowres : Derived {                                    // up: residual_l
 };
 // The static rule: the block sizes at which mix + gather measured faster than upsample2x + conv_up + the norm1 passes (DESIGN.md 3.1,
 // profiles/r10_block_sums.txt): low-res maps of 2x2 to 8x8 with 128 to 512 channels, 2 Ki to 32 Ki low-res elements per sample, at
-// batch 2, 16 and 32.  Nothing outside that range has been measured, so nothing outside it takes the route.
+// batch 2, 16 and 32.  Nothing outside that range has been measured inside the network, so nothing outside it takes the route (the next
+// blocks up, 16x16 and 32x32 low-res maps, were timed as mix + gather alone with the two-pass gather: profiles/r11_block_sums.txt).
 inline bool up_lowres_shape(int ci, int h, int w) {
     const long long n = (long long)ci * h * w;
     return h >= 2 && w >= 2 && h <= 8 && w <= 8 && ci >= 128 && ci <= 512 && n >= 2048 && n <= 32768;
