@@ -299,6 +299,12 @@ typedef struct sbgm_conv_args {
     const float* w_wino2d;
 } sbgm_conv_args;
 int sbgm_conv2d_fwd(const sbgm_conv_args* a, void* stream);
+/* Two convolutions of ONE input (same x, B, H, W, c_pad), each with its explicit tile as in sbgm_conv2d_fwd: what the encoder does with a
+ * BasicBlock's 3x3 / stride 2 / pad 1 convolution (main) and its 1x1 / stride 2 shortcut (aux).  Where the implicit-GEMM kernels serve the
+ * pair of tiles (a small instantiated set, no grid split-K) both run in one launch, otherwise as two launches, main first; the outputs
+ * are those of the two sbgm_conv2d_fwd calls bit for bit.  *paired (may be NULL): 1 when it was one launch.  SBGM_NO_CONV_PAIR=1 in the
+ * environment: always two launches.  Both calls name the same split-K workspace `ws` (or none). */
+int sbgm_conv2d_pair_fwd(const sbgm_conv_args* main_conv, const sbgm_conv_args* aux_conv, int* paired, void* stream);
 /* Times the kernel / tile / split candidates for exactly this call (same operands; launches are idempotent; synchronises)
  * and writes the fastest as tile[6] = {tile_co, tile_px, splits, waves_per_tile, winograd bit 0, LDS kernel: 0 off / 1 on (bit 1) / 2 double-buffered (bits 1+2)}, the values
  * to put into sbgm_conv_args.  Winograd candidates are timed when a->w_wino is given (they need the transformed weights);
@@ -413,6 +419,15 @@ int64_t sbgm_up_lowres_ws_numel(int B, int H, int W, int C, int groups);
 int sbgm_up_lowres_pack(const float* w_oihw, float* w_taps, float* w_packed, int C, void* stream);
 int sbgm_up_lowres_fwd(const float* x_lowres_nhwc, const float* w_packed, const float* bias, const float* gamma, const float* beta,
                        int groups, float eps, float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream);
+
+/* Time rows of an Euler-Maruyama / predictor-corrector run without labels: the run computes the time-bias vectors of all
+ * its steps once, row s = the vectors at the time of step s one after the other, and the end of a step publishes the row of the next.
+ * Host-side statements of the two rules, usable without a device:
+ * sbgm_time_row_layout: widths channels[n] (n in 1..16, positive multiples of 4) -> offsets[n + 1], the start of each vector in a row
+ * in floats with offsets[n] = the row length; returns the row length, or -1 for widths a row cannot hold.
+ * sbgm_time_row_index: the row a run of num_steps steps evaluates at after `advances` completed steps (the last step republishes its own). */
+int sbgm_time_row_layout(const int* channels, int n, int* offsets);
+int64_t sbgm_time_row_index(int64_t advances, int64_t num_steps);
 
 /* ConvTranspose2d(k=2,s=2) = one 1x1 convolution to 4C channels (weights from sbgm_tconv_weight_to_oihw, bias repeated
  * 4x) followed by depth->space; its backward is space->depth followed by the 1x1 convolution's backward. */

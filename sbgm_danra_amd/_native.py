@@ -128,9 +128,12 @@ SIGNATURES = {
     "sbgm_up_lowres_ws_numel": (_i64, [_i, _i, _i, _i, _i]),
     "sbgm_up_lowres_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
     "sbgm_up_lowres_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sbgm_time_row_layout": (_i, [C.POINTER(C.c_int), _i, C.POINTER(C.c_int)]),
+    "sbgm_time_row_index": (_i64, [_i64, _i64]),
     "sbgm_final_block_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i,
                                   C.POINTER(C.c_int), _vp]),
     "sbgm_conv2d_fwd": (_i, [C.POINTER(ConvArgs), _vp]),
+    "sbgm_conv2d_pair_fwd": (_i, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), C.POINTER(C.c_int), _vp]),
     "sbgm_conv2d_tune": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int), _vp]),
     "sbgm_conv_pack_weights_batched": (_i, [_vp, _i, _i, _vp]),
     "sbgm_conv_pack_weights_batched_blocks": (_i, [_i, _i, _i, _i]),

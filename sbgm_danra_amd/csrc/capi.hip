@@ -60,6 +60,17 @@ int sbgm_conv2d_fwd(const sbgm_conv_args* a, void* stream) {
     return sbgm_launch_tile(g, p, w, t, a->ws, ST);
 }
 
+int sbgm_conv2d_pair_fwd(const sbgm_conv_args* main_conv, const sbgm_conv_args* aux_conv, int* paired, void* stream) {
+    ConvGeom gm, ga;
+    ConvParams pm, pa;
+    ConvImages wm, wa;
+    ConvTile tm, ta;
+    if (sbgm_conv_from_args(main_conv, &gm, &pm, &wm, &tm) || sbgm_conv_from_args(aux_conv, &ga, &pa, &wa, &ta)) return 1;
+    SBGM_CHECK(pm.x == pa.x && pm.B == pa.B && pm.H == pa.H && pm.W == pa.W && pm.Cs == pa.Cs, "conv2d_pair: the two convolutions must read one input");
+    SBGM_CHECK(main_conv->ws == aux_conv->ws, "conv2d_pair: the two convolutions share one split-K workspace");
+    return sbgm_launch_tile_pair(gm, pm, wm, tm, ga, pa, wa, ta, main_conv->ws, ST, paired);
+}
+
 int sbgm_conv_pack_weights_batched_blocks(int Cout, int KH, int KW, int c_pad) { return sbgm_conv_pack_blocks(Cout, KH, KW, c_pad); }
 int sbgm_conv_pack_weights_batched(const sbgm_pack_desc* desc_dev, int n, int total_blocks, void* stream) {
     return sbgm_launch_pack_conv_weights_batched(desc_dev, n, total_blocks, ST);   // descriptors live on the device: the caller

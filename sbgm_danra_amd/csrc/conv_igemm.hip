@@ -37,8 +37,10 @@ struct PixLane {      // per-lane decode of the output pixel this lane gathers f
     int y0, x0;       // oy*S - PAD, ox*S - PAD
 };
 
+// The kernel's body as a function of (problem, workgroup index, workgroup count), so that conv_igemm_kernel (one problem per launch) and
+// conv_igemm_pair_kernel (two problems sharing a grid) run the same code: workgroup `bid` of the `nb` that serve problem p.
 template <int KH, int KW, int S, int PAD, int FCO, int FPX, int CMODE, int WS>
-__global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
+__device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int bid, const int nb) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -46,7 +48,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     const int kq = lane >> 4;      // which 4-channel quad of the 16-deep K step this lane supplies
 
     // ---- workgroup -> tile range, XCD-contiguous (blocks b, b+8, ... share an XCD) ---------------
-    const int nb = gridDim.x, bid = blockIdx.x;
     const int q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
     const int lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     constexpr int TPW = 4 / WS;                     // tiles per workgroup
@@ -266,6 +267,25 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     }
 }
 
+template <int KH, int KW, int S, int PAD, int FCO, int FPX, int CMODE, int WS>
+__global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
+    conv_igemm_body<KH, KW, S, PAD, FCO, FPX, CMODE, WS>(p, blockIdx.x, gridDim.x);
+}
+
+// A BasicBlock's two stride-2 convolutions of one input in one launch: the 3x3 / pad 1 (main) on workgroups [0, nA) and the 1x1
+// shortcut (aux) on workgroups [nA8, nA8 + nB), nA8 = nA rounded up to a multiple of 8 so that an aux workgroup's index and its
+// position in the grid agree modulo 8, which is the workgroup-to-XCD rule the body's tile mapping assumes; workgroups [nA, nA8) leave
+// at once.  Every launch of the body is 256 threads; the dynamic LDS is the larger of the two needs; no grid split-K (gridDim.y = 1).
+template <int FCO, int FPX, int WS, int AFCO, int AFPX, int AWS>
+__global__ __launch_bounds__(256) void conv_igemm_pair_kernel(const ConvParams pm, const ConvParams pa, int nA, int nA8, int nB) {
+    const int bid = blockIdx.x;
+    if (bid < nA8) {
+        if (bid < nA) conv_igemm_body<3, 3, 2, 1, FCO, FPX, 0, WS>(pm, bid, nA);
+    } else {
+        conv_igemm_body<1, 1, 2, 0, AFCO, AFPX, 0, AWS>(pa, bid - nA8, nB);
+    }
+}
+
 // Sum split-K partials [nsplit][M][Cout] and apply the same epilogue.  One float4 per thread.
 __global__ __launch_bounds__(256) void splitk_reduce_epilogue(const ConvParams p, const float* part, int nsplit) {
     const size_t n4 = (size_t)p.M * p.Cout / 4;
@@ -445,9 +465,9 @@ int sbgm_launch_pack_conv_weights_batched(const sbgm_pack_desc* desc_dev, int n,
     return 0;
 }
 
-// Launch one convolution.  `cfg` selects the wave tile and the split-K factor; `partial_ws` must hold
-// splits*M*Cout floats when splits > 1.
-int sbgm_launch_conv(const ConvGeom& g, ConvParams p, const ConvTile& cfg, float* partial_ws, hipStream_t st) {
+// Checks a convolution against what the kernels serve and fills the fields of p the kernels derive from the rest; *grid: its launch
+// (y: the grid split-K factor), *cmode_out: the channel mode of its instantiation.
+static int prepare_conv(const ConvGeom& g, ConvParams& p, const ConvTile& cfg, dim3* grid_out, int* cmode_out) {
     SBGM_CHECK(p.Cout % (16 * cfg.fco) == 0, "conv: Cout=%d not a multiple of the %d-row tile", p.Cout, 16 * cfg.fco);
     SBGM_CHECK(p.Cs == 4 || p.Cs == 8 || p.Cs % 16 == 0, "conv: padded Cin %d unsupported", p.Cs);
     SBGM_CHECK(p.act == SBGM_ACT_NONE || p.act == SBGM_ACT_RELU || p.act == SBGM_ACT_GELU, "conv: act=%d does not fuse into the epilogue", p.act);
@@ -478,13 +498,23 @@ int sbgm_launch_conv(const ConvGeom& g, ConvParams p, const ConvTile& cfg, float
     p.w_bytes = (uint32_t)((size_t)p.nsteps * p.Cout * 64);
     const int ntiles = p.n_px_tiles * p.n_co_tiles;
     const int tpw = 4 / cfg.ws;
-    dim3 grid((ntiles + tpw - 1) / tpw, real_splits);
+    *grid_out = dim3((ntiles + tpw - 1) / tpw, real_splits);
+    *cmode_out = two_of_four ? 2 : (p.Cs >= 16 ? 0 : p.Cs);
+    return 0;
+}
+
+// Launch one convolution.  `cfg` selects the wave tile and the split-K factor; `partial_ws` must hold
+// splits*M*Cout floats when splits > 1.
+int sbgm_launch_conv(const ConvGeom& g, ConvParams p, const ConvTile& cfg, float* partial_ws, hipStream_t st) {
+    dim3 grid;
+    int cmode = 0;
+    if (prepare_conv(g, p, cfg, &grid, &cmode)) return 1;
+    const int real_splits = (int)grid.y;
     float* final_out = p.out;
     if (real_splits > 1) {
         SBGM_CHECK(partial_ws != nullptr, "conv: split-K needs a partial workspace");
         p.out = partial_ws;
     }
-    const int cmode = two_of_four ? 2 : (p.Cs >= 16 ? 0 : p.Cs);
     int rc = 1;
 #define SBGM_GEOM(KH_, KW_, S_, PAD_, CM_)                                                        \
     if (g.kh == KH_ && g.kw == KW_ && g.stride == S_ && g.pad == PAD_ && cmode == CM_)            \
@@ -504,5 +534,60 @@ int sbgm_launch_conv(const ConvGeom& g, ConvParams p, const ConvTile& cfg, float
         hipLaunchKernelGGL(splitk_reduce_epilogue, dim3(blocks), dim3(256), 0, st, p, partial_ws, real_splits);
         SBGM_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+// ---- the pair launch ---------------------------------------------------------------------------------------------------------------
+// The (main tile, aux tile) combinations conv_igemm_pair_kernel is instantiated for.  Tuned: the autotuner's choices for the three
+// BasicBlock pairs at the two benchmark shapes differ from collection to collection (profiles/r11_c2_tiles.txt, r11_c4_tiles.txt,
+// r12_c2_tiles.txt, r12_c4_tiles.txt), but stay within 64x32 / 32x32 main tiles of 2 or 4 waves and 32x16 / 64x16 aux tiles: all 24
+// combinations of those.  Static: what sbgm_static_tile chooses at those shapes and on small maps, where it is not among them.
+#define SBGM_PAIRS_AUX(X, FC, FP, W)                                                                                       \
+    X(FC, FP, W, 2, 1, 1) X(FC, FP, W, 2, 1, 2) X(FC, FP, W, 2, 1, 4) X(FC, FP, W, 4, 1, 1) X(FC, FP, W, 4, 1, 2) X(FC, FP, W, 4, 1, 4)
+#define SBGM_PAIRS(X)                                                                                                      \
+    SBGM_PAIRS_AUX(X, 4, 2, 4) SBGM_PAIRS_AUX(X, 4, 2, 2) SBGM_PAIRS_AUX(X, 2, 2, 4) SBGM_PAIRS_AUX(X, 2, 2, 2) /* tuned */ \
+    X(4, 2, 4, 2, 2, 2) X(2, 2, 4, 2, 2, 4) X(2, 1, 4, 2, 1, 4) X(4, 4, 4, 4, 2, 2) X(4, 2, 4, 4, 2, 4) /* static */         \
+    X(2, 1, 4, 2, 1, 2)                                         /* static, small maps: a 64-channel shortcut has 4 K steps */
+
+static bool pair_tiles_match(const ConvTile& m, const ConvTile& a, int fc, int fp, int w, int afc, int afp, int aw) {
+    return m.fco == fc && m.fpx == fp && m.ws == w && a.fco == afc && a.fpx == afp && a.ws == aw;
+}
+
+bool sbgm_conv_pair_served(const ConvGeom& gm, const ConvParams& pm, const ConvTile& tm, const ConvGeom& ga, const ConvParams& pa,
+                           const ConvTile& ta) {
+    if (!(gm.kh == 3 && gm.kw == 3 && gm.stride == 2 && gm.pad == 1 && ga.kh == 1 && ga.kw == 1 && ga.stride == 2 && ga.pad == 0)) return false;
+    if (pm.x != pa.x || pm.B != pa.B || pm.H != pa.H || pm.W != pa.W || pm.Cs != pa.Cs || pm.Cs < 16 || pm.Cs % 16) return false;
+    if (pm.proj_w || pa.proj_w || pm.in_dil == 2 || pa.in_dil == 2 || pm.out_h || pa.out_h || pm.c_real || pa.c_real) return false;
+    if (tm.family() != FAM_IGEMM || ta.family() != FAM_IGEMM) return false;
+    // one grid row each: a tile's split-K factor is clamped to the K steps, a split of one K step is no split
+    if (std::min(tm.splits, sbgm_conv_nsteps(3, 3, pm.Cs)) > 1 || std::min(ta.splits, sbgm_conv_nsteps(1, 1, pa.Cs)) > 1) return false;
+#define SBGM_PAIR_HAS(FC, FP, W, AFC, AFP, AW) if (pair_tiles_match(tm, ta, FC, FP, W, AFC, AFP, AW)) return true;
+    SBGM_PAIRS(SBGM_PAIR_HAS)
+#undef SBGM_PAIR_HAS
+    return false;
+}
+
+// Both convolutions of a served pair (sbgm_conv_pair_served) in one launch; p.wp of each is set by the caller.
+int sbgm_launch_conv_pair(ConvParams pm, const ConvTile& tm, ConvParams pa, const ConvTile& ta, hipStream_t st) {
+    const ConvGeom gm{3, 3, 2, 1}, ga{1, 1, 2, 0};
+    SBGM_CHECK(sbgm_conv_pair_served(gm, pm, tm, ga, pa, ta), "conv pair: no kernel for this pair of convolutions and tiles");
+    dim3 grid_m, grid_a;
+    int cm = 0, ca = 0;
+    if (prepare_conv(gm, pm, tm, &grid_m, &cm) || prepare_conv(ga, pa, ta, &grid_a, &ca)) return 1;
+    SBGM_CHECK(grid_m.y == 1 && grid_a.y == 1 && cm == 0 && ca == 0, "conv pair: a member needs a launch of its own");
+    const int nA = (int)grid_m.x, nA8 = (nA + 7) & ~7, nB = (int)grid_a.x;
+    int rc = 1;
+#define SBGM_PAIR_LAUNCH(FC, FP, W, AFC, AFP, AW)                                                                             \
+    if (pair_tiles_match(tm, ta, FC, FP, W, AFC, AFP, AW)) {                                                                  \
+        const size_t lm = W > 1 ? (size_t)(4 / W) * (W - 1) * FC * FP * 64 * 16 : 0;                                          \
+        const size_t la = AW > 1 ? (size_t)(4 / AW) * (AW - 1) * AFC * AFP * 64 * 16 : 0;                                     \
+        hipLaunchKernelGGL((conv_igemm_pair_kernel<FC, FP, W, AFC, AFP, AW>), dim3(nA8 + nB), dim3(256), std::max(lm, la), st, \
+                           pm, pa, nA, nA8, nB);                                                                              \
+        rc = 0;                                                                                                               \
+    }
+    SBGM_PAIRS(SBGM_PAIR_LAUNCH)
+#undef SBGM_PAIR_LAUNCH
+    SBGM_CHECK(rc == 0, "conv pair: no kernel for these tiles");
+    SBGM_LAUNCH_CHECK();
     return 0;
 }

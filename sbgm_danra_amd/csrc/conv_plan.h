@@ -105,6 +105,10 @@ int sbgm_pack_conv_images(const float* w_oihw, float* const img[CONV_IMAGES], in
 
 // ---- one launch of a tile: the only place that selects a launcher and sets p.wp; checks the geometry the tile's family accepts ------
 int sbgm_launch_tile(const ConvGeom& g, ConvParams p, const ConvImages& w, const ConvTile& ct, float* partial, hipStream_t st);
+// a BasicBlock's strided 3x3 (main) and 1x1 shortcut (aux) of one input: one launch where served, else the two, main first; same bits.
+// *paired (may be null): 1 when it was one launch
+int sbgm_launch_tile_pair(const ConvGeom& gm, ConvParams pm, const ConvImages& wm, const ConvTile& tm, const ConvGeom& ga, ConvParams pa,
+                          const ConvImages& wa, const ConvTile& ta, float* partial, hipStream_t st, int* paired = nullptr);
 // GroupNorm statistics that launch leaves in p.gn_stats (chunks per sample), 0 = none
 int sbgm_tile_gn_chunks(const ConvParams& p, const ConvTile& ct);
 // partial planes [parts][9][M] a tap-projection launch of this tile writes

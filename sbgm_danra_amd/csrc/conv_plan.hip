@@ -86,6 +86,22 @@ int sbgm_launch_tile(const ConvGeom& g, ConvParams p, const ConvImages& w, const
     }
 }
 
+// Two convolutions of one input (a BasicBlock's strided 3x3 and its 1x1 shortcut): one launch where the implicit-GEMM family serves the
+// pair of tiles (sbgm_conv_pair_served), else the two launches, main first.  Same bits either way.  SBGM_NO_CONV_PAIR=1: always two.
+int sbgm_launch_tile_pair(const ConvGeom& gm, ConvParams pm, const ConvImages& wm, const ConvTile& tm, const ConvGeom& ga, ConvParams pa,
+                          const ConvImages& wa, const ConvTile& ta, float* partial, hipStream_t st, int* paired) {
+    static const bool on = getenv("SBGM_NO_CONV_PAIR") == nullptr;
+    if (paired) *paired = 0;
+    pm.wp = wm.img[IMG_IGEMM];
+    pa.wp = wa.img[IMG_IGEMM];
+    if (on && tm.well_formed() && ta.well_formed() && pm.wp && pa.wp && sbgm_conv_pair_served(gm, pm, tm, ga, pa, ta)) {
+        if (paired) *paired = 1;
+        return sbgm_launch_conv_pair(pm, tm, pa, ta, st);
+    }
+    if (sbgm_launch_tile(gm, pm, wm, tm, partial, st)) return 1;
+    return sbgm_launch_tile(ga, pa, wa, ta, partial, st);
+}
+
 int sbgm_tile_gn_chunks(const ConvParams& p, const ConvTile& ct) {
     const auto chunks = FAMILY[ct.family()].gn_chunks;
     return chunks ? chunks(p, ct) : 0;

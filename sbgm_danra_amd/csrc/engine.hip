@@ -193,8 +193,30 @@ inline bool up_lowres_shape(int ci, int h, int w) {
 // Which evaluations take the composed stem (+ the run's condition term, null without condition channels) and the composed final block
 // (fin_lowres: as the low-resolution mix + gather instead of the composed 3x3 convolution) and the low-resolution conv_up of the
 // small-map decoder blocks (up_lowres)
-struct Routes { bool stem = false, fin = false, fin_lowres = false, up_lowres = false; const float* stem_T = nullptr; };
+// tbrun (EM and PC runs without labels): the run's time biases [9][run_B][ch_i], kept current by the step's advance, so
+// the evaluation launches neither the time embedding nor the time projections
+struct Routes {
+    bool stem = false, fin = false, fin_lowres = false, up_lowres = false;
+    const float* stem_T = nullptr;
+    float* tbrun = nullptr;
+    int run_B = 0;
+};
 enum Caller { CALL_PLAIN, CALL_SDE_RUN, CALL_MEASURE };
+
+// A device allocation the model handle owns and a run uses: grown roomily (a changed address invalidates the cached step graph)
+struct RunBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    int need(size_t bytes, size_t roomy) {
+        if (bytes <= cap) return 0;
+        if (p) SBGM_HIP(hipFree(p));
+        p = nullptr; cap = 0;
+        SBGM_HIP(hipMalloc(&p, std::max(bytes, roomy)));
+        cap = std::max(bytes, roomy);
+        return 0;
+    }
+    float* f() const { return static_cast<float*>(p); }
+};
 
 }  // namespace
 
@@ -245,10 +267,37 @@ struct sbgm_model {
     //   network through the plain forward, and at rtol 1e-4 their accept / reject decisions are within rounding of the native loop's: with
     //   the composed block's rounding one run of tests/test_gpu_rk45_sampler.py took 452 evaluations under SciPy against 464 natively
     //   (bound 9), where the projection path gives 464 / 464; a stem that rounds differently flips such decisions too.
+    //   an EM / PC run without a label vector additionally: its own time biases, see sampler().
     Routes routes;
-    void set_routes(Caller c, const float* stem_T = nullptr) {
-        routes = Routes{c == CALL_SDE_RUN && stem.on, c != CALL_PLAIN && fin.on, c != CALL_PLAIN && fin.on && fin.lowres, c != CALL_PLAIN,
-                        c == CALL_SDE_RUN ? stem_T : nullptr};
+    void set_routes(Caller c, const float* stem_T = nullptr, float* tbrun = nullptr, int run_B = 0) {
+        const bool run = c == CALL_SDE_RUN;
+        routes = Routes{run && stem.on, c != CALL_PLAIN && fin.on, c != CALL_PLAIN && fin.on && fin.lowres, c != CALL_PLAIN,
+                        run ? stem_T : nullptr, run ? tbrun : nullptr, run ? run_B : 0};
+    }
+    // The run-owned buffers of that route and the layout of a time row: the nine time-bias vectors in the order of forward_impl's
+    // tb[0..8] (five encoder maps, four decoder blocks); off4 in 16-byte quads, off4[9] = TB / 4
+    static bool env_time_rows() { static const bool v = getenv("SBGM_NO_TIME_ROWS") == nullptr; return v; }
+    RunBuf d_times, d_rows, d_tbrun;
+    int time_row_layout(int off4[10]) const {
+        int ch[9], off[10];
+        for (int i = 0; i < 9; ++i) ch[i] = i < 5 ? FMAP_CH[i] : dec[i - 5].cout;
+        const int TB = sbgm_time_row_layout(ch, 9, off);
+        for (int i = 0; i < 10 && TB > 0; ++i) off4[i] = off[i] / 4;
+        return TB;
+    }
+    // what computes the time biases of B samples at times t into out[i] (rows `stride` floats apart; 0: packed)
+    int time_biases(const float* t, const int64_t* y, int B, float* emb_ws, float* const out[9], int stride, hipStream_t st) const {
+        TimeEmbedArgs te{};
+        te.t = t; te.y = y; te.label_emb = (y && label_emb) ? label_emb->dev() : nullptr;
+        te.B = B; te.D = D;
+        te.n_emb = 5;
+        te.freqs[0] = enc_freq->dev();
+        for (int i = 0; i < 4; ++i) te.freqs[1 + i] = dec[i].freq->dev();
+        te.emb_ws = emb_ws;
+        te.n_proj = 9;
+        for (int i = 0; i < 5; ++i) te.proj[i] = TimeProj{enc_tpw[i]->dev(), enc_tpb[i]->dev(), out[i], FMAP_CH[i], 0, stride};
+        for (int i = 0; i < 4; ++i) te.proj[5 + i] = TimeProj{dec[i].tpw->dev(), dec[i].tpb->dev(), out[5 + i], dec[i].cout, 1 + i, stride};
+        return sbgm_launch_time_embed(te, st);
     }
     size_t stem_t_bytes(int B, int H, int W) const { return stem.on && cin_total > 1 ? align_up((size_t)B * H * W * 4 * 4, 256) : 0; }
     // workspace
@@ -284,6 +333,7 @@ struct sbgm_model {
         const void *y, *cond, *lsm, *topo, *origins, *ws, *table;
         const void *known, *known_mask, *levels;   // constrained runs (null otherwise): a held and an unheld step never share a graph
         int joint, domain_h, ramp_len;             // joint tiled runs (0 otherwise): a joint and a non-joint step never share a graph
+        const void *rows, *tbrun;                  // EM / PC runs that keep their time rows (null otherwise)
         size_t ws_bytes;
         float cfg, cfg_corr, snr_nn;
         unsigned long long plan_gen;
@@ -330,6 +380,7 @@ struct sbgm_model {
         if (d_state) (void)hipFree(d_state);
         if (d_table) (void)hipFree(d_table);
         if (d_levels) (void)hipFree(d_levels);
+        for (RunBuf* b : {&d_times, &d_rows, &d_tbrun}) if (b->p) (void)hipFree(b->p);
         if (h_stage) (void)hipHostFree(h_stage);
         if (ev_stage) (void)hipEventDestroy(ev_stage);
         if (graph_stream) (void)hipStreamDestroy(graph_stream);
@@ -418,6 +469,8 @@ struct sbgm_model {
         return it != tuned.end() ? it->second : sbgm_static_tile(g, p, im);
     }
     int conv(const ConvGeom& g, ConvParams p, const Param& w, hipStream_t st);
+    int conv_pair(const ConvGeom& gm, const ConvParams& pm, const Param& wm, const ConvGeom& ga, const ConvParams& pa, const Param& wa,
+                  hipStream_t st);
     int attention(const AttnW& a, float* x, int B, int S, hipStream_t st);
     int forward_impl(const float* x, const float* t, const int64_t* y, const float* cond, const float* lsm, const float* topo,
                      float* out, float* const* fmaps_out, int B, int H, int W, int bn_train, hipStream_t st);
@@ -644,6 +697,25 @@ int sbgm_model::conv(const ConvGeom& g, ConvParams p, const Param& w, hipStream_
     return rc;
 }
 
+// A BasicBlock's strided 3x3 convolution (main) and its 1x1 shortcut (aux), both of one input: one launch where the planner serves the
+// pair of tiles, for every caller (the bodies and tiles are the ones the two launches use, so the bits are the same).  A tuning
+// evaluation and the profiled forward keep the two launches: the tile table and the roofline CSV have one row per convolution.
+int sbgm_model::conv_pair(const ConvGeom& gm, const ConvParams& pm, const Param& wm, const ConvGeom& ga, const ConvParams& pa, const Param& wa,
+                          hipStream_t st) {
+    if (tuning || prof) return conv(gm, pm, wm, st) || conv(ga, pa, wa, st);
+    const ConvImages im = wm.images(), ia = wa.images();
+    auto tile = [&](const ConvGeom& g, const ConvParams& p, const ConvImages& i) {       // as conv() settles it
+        const int OH = (p.H + 2 * g.pad - g.kh) / g.stride + 1, OW = (p.W + 2 * g.pad - g.kw) / g.stride + 1;
+        const size_t mc = (size_t)p.B * OH * OW * p.Cout;
+        ConvTile ct = pick_tile(g, p, i);
+        if (ct.splits > 1 && mc * ct.splits > PARTIAL_FLOATS) ct.splits = (int)std::max<size_t>(1, PARTIAL_FLOATS / mc);
+        return ct;
+    };
+    const ConvTile tm = tile(gm, pm, im), ta = tile(ga, pa, ia);
+    last_tile = ta;
+    return sbgm_launch_tile_pair(gm, pm, im, tm, ga, pa, ia, ta, partial, st);
+}
+
 // y = h + FF(LN2(h)),  h = x + MHA(LN1(x))   over tokens [B*S, C]  (score_unet.py:136-148); in place on x
 int sbgm_model::attention(const AttnW& a, float* x, int B, int S, hipStream_t st) {
     const int C = a.C, M = B * S;
@@ -716,27 +788,21 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     if (!x0) return 1;
     if (sbgm_launch_pack_input(src, x0, B, H, W, cs_in, st)) return 1;
 
-    TimeEmbedArgs te{};
-    te.t = t; te.y = y; te.label_emb = (y && label_emb) ? label_emb->dev() : nullptr;
-    te.B = B; te.D = D;
-    te.n_emb = 5;
-    te.freqs[0] = enc_freq->dev();
-    for (int i = 0; i < 4; ++i) te.freqs[1 + i] = dec[i].freq->dev();
-    te.emb_ws = wsalloc((size_t)5 * B * D);
-    if (!te.emb_ws) return 1;
+    // An EM / PC run without labels keeps its time biases itself (routes.tbrun); the workspace is carved the same either
+    // way, so every later buffer keeps its address and the measured high-water mark serves both
+    SBGM_CHECK(!routes.tbrun || routes.run_B == B, "forward: the run's time biases hold %d samples, not %d", routes.run_B, B);
+    float* emb_ws = wsalloc((size_t)5 * B * D);
+    if (!emb_ws) return 1;
     float* tb[9];
-    te.n_proj = 9;
-    for (int i = 0; i < 5; ++i) {
-        tb[i] = wsalloc((size_t)B * FMAP_CH[i]);
+    for (int i = 0; i < 9; ++i) {
+        tb[i] = wsalloc((size_t)B * (i < 5 ? FMAP_CH[i] : dec[i - 5].cout));
         if (!tb[i]) return 1;
-        te.proj[i] = TimeProj{enc_tpw[i]->dev(), enc_tpb[i]->dev(), tb[i], FMAP_CH[i], 0};
     }
-    for (int i = 0; i < 4; ++i) {
-        tb[5 + i] = wsalloc((size_t)B * dec[i].cout);
-        if (!tb[5 + i]) return 1;
-        te.proj[5 + i] = TimeProj{dec[i].tpw->dev(), dec[i].tpb->dev(), tb[5 + i], dec[i].cout, 1 + i};
-    }
-    if (sbgm_launch_time_embed(te, st)) return 1;
+    if (routes.tbrun) {
+        int off4[10];
+        time_row_layout(off4);
+        for (int i = 0; i < 9; ++i) tb[i] = routes.tbrun + (size_t)B * off4[i] * 4;
+    } else if (time_biases(t, y, B, emb_ws, tb, 0, st)) return 1;
 
     // GroupNorm: 64 chunks x B x G x 2 doubles (G = C <= 512 for InstanceNorm); BatchNorm: 24 B x C
     const size_t n_groups = (size_t)B * (cfg.decoder_norm == SBGM_NORM_GROUP ? std::min(cfg.gn_groups, 512) : 512);
@@ -798,13 +864,27 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             const int oh = ch / b.stride, ow = cw_ / b.stride;
             float* y1 = wsalloc((size_t)B * oh * ow * b.cout);
             if (!y1) return 1;
-            if (conv_bn(ConvGeom{3, 3, b.stride, 1}, cur, ch, cw_, cc, b.c1, b.bn1, b.cout, nullptr, true, nullptr, y1)) return 1;
             const float* idn = cur;
-            if (b.has_ds) {
+            if (b.has_ds && !bn_train) {
+                // conv1 + bn1 + ReLU and the shortcut's 1x1 + BatchNorm read the same input and do not depend on each other: one launch
                 float* d = wsalloc((size_t)B * oh * ow * b.cout);
                 if (!d) return 1;
-                if (conv_bn(ConvGeom{1, 1, b.stride, 0}, cur, ch, cw_, cc, b.ds, b.dsbn, b.cout, nullptr, false, nullptr, d)) return 1;
+                ConvParams pm{}, pa{};
+                pm.x = cur; pm.B = B; pm.H = ch; pm.W = cw_; pm.Cs = cc; pm.Cout = b.cout;
+                pm.tbias_after_act = 1;
+                pa = pm;
+                pm.out = y1; pm.scale = b.bn1.scale; pm.bias = b.bn1.bias; pm.act = SBGM_ACT_RELU;
+                pa.out = d; pa.scale = b.dsbn.scale; pa.bias = b.dsbn.bias; pa.act = SBGM_ACT_NONE;
+                if (conv_pair(ConvGeom{3, 3, b.stride, 1}, pm, *b.c1.w, ConvGeom{1, 1, b.stride, 0}, pa, *b.ds.w, st)) return 1;
                 idn = d;
+            } else {
+                if (conv_bn(ConvGeom{3, 3, b.stride, 1}, cur, ch, cw_, cc, b.c1, b.bn1, b.cout, nullptr, true, nullptr, y1)) return 1;
+                if (b.has_ds) {
+                    float* d = wsalloc((size_t)B * oh * ow * b.cout);
+                    if (!d) return 1;
+                    if (conv_bn(ConvGeom{1, 1, b.stride, 0}, cur, ch, cw_, cc, b.ds, b.dsbn, b.cout, nullptr, false, nullptr, d)) return 1;
+                    idn = d;
+                }
             }
             float* y2 = wsalloc((size_t)B * oh * ow * b.cout);
             if (!y2) return 1;
@@ -1115,6 +1195,7 @@ struct SamplerRun {
     size_t saved_ws = 0;             // the model's ws_bytes while the run holds its slabs (0: not held)
     SamplerConds conds{a, st};       // guidance: the unconditional half is built once per run
     NoiseMap nm{};
+    float* tbrun = nullptr;          // set by an EM / PC driver before begin(): the run keeps its time biases
     ~SamplerRun() { if (saved_ws) m->ws_bytes = saved_ws; m->set_routes(CALL_PLAIN); }
     size_t keep() const { return m->sampler_keep(BE, H, W, slabs); }
     float* slab_at(int i) const { return reinterpret_cast<float*>(top + (i < lead ? i * slab : m->slabs_keep(BE, H, W, lead) + (i - lead) * slab)); }
@@ -1148,7 +1229,7 @@ struct SamplerRun {
                 if (sbgm_launch_conv_stem22(srcs[i], chs[i], c0, m->cin_total, m->stem.wc, nullptr, nullptr, term, nullptr, nullptr, 0, stem_T(), BE, H, W, st)) return 1;
                 term = stem_T();
             }
-            m->set_routes(CALL_SDE_RUN, term);
+            m->set_routes(CALL_SDE_RUN, term, tbrun, BE);
         }
         if (a.tile_origins && draws_noise) {
             SBGM_CHECK(W % 4 == 0 && a.domain_w >= W, "%s: tiled noise needs W %% 4 == 0 and domain_w >= W (W=%d, domain_w=%d)", who, W, a.domain_w);
@@ -1213,7 +1294,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
 
     // ---- step table and initial state, written into the pinned staging buffer and uploaded from there --------------------------
     static_assert(sizeof(EdmStep) >= sizeof(StepScalars), "the staging buffer is sized for the larger row");
-    const size_t stage_need = (sizeof(EdmStep) + sizeof(HoldLevels)) * (size_t)N + sizeof(SamplerState);
+    const size_t stage_need = (sizeof(EdmStep) + sizeof(HoldLevels) + sizeof(float)) * (size_t)N + sizeof(SamplerState);
     if (stage_pending) {                                   // the previous call's upload still reads the buffer (normally long done)
         SBGM_HIP(hipEventSynchronize(ev_stage));
         stage_pending = false;
@@ -1221,7 +1302,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     if (h_stage_bytes < stage_need) {
         if (h_stage) SBGM_HIP(hipHostFree(h_stage));
         h_stage = nullptr;
-        h_stage_bytes = std::max(stage_need, (sizeof(EdmStep) + sizeof(HoldLevels)) * (size_t)4096 + sizeof(SamplerState));
+        h_stage_bytes = std::max(stage_need, (sizeof(EdmStep) + sizeof(HoldLevels) + sizeof(float)) * (size_t)4096 + sizeof(SamplerState));
         SBGM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_stage), h_stage_bytes, hipHostMallocDefault));
     }
     if (!ev_stage) SBGM_HIP(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming));
@@ -1263,6 +1344,34 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         for (int i = 0; i < N; ++i) lv[i].next = i + 1 < N ? lv[i + 1].cur : 0.f;
         SBGM_HIP(hipMemcpyAsync(d_levels, lv, sizeof(HoldLevels) * (size_t)N, hipMemcpyHostToDevice, st));
         hold.levels = d_levels;
+    }
+    // Time rows: an EM / PC run without labels evaluates every sample at the table's time of the step, so the nine
+    // time-bias vectors of all N steps are computed here, once per call and outside the captured step, by the forward's own two kernels
+    // with the N table times as their "samples" (a row does not depend on the other rows: bit-equal to what the step would compute);
+    // the step's advance then copies row step + 1 into tbrun.  EDM Heun evaluates at two times per step and keeps its launches.
+    TimeRows trows{};
+    const bool keep_rows = !heun && a.y == nullptr && env_time_rows();
+    if (keep_rows) {
+        int off4[10];
+        const int TB = time_row_layout(off4);
+        SBGM_CHECK(TB > 0, "sampler: time-bias widths must be multiples of 4");
+        constexpr int CHUNK = 512;                         // rows per launch: bounds the embedding scratch, taken from the idle workspace
+        const size_t scratch = (size_t)5 * std::min(N, CHUNK) * D * 4;
+        SBGM_CHECK(scratch <= ws_bytes, "sampler: workspace too small for the time-row scratch");
+        if (d_times.need((size_t)N * 4, (size_t)4096 * 4) || d_rows.need((size_t)N * TB * 4, (size_t)1024 * TB * 4) ||
+            d_tbrun.need((size_t)BE * TB * 4, (size_t)64 * TB * 4)) return 1;
+        float* h_times = reinterpret_cast<float*>(h_stage + tab_bytes + sizeof(SamplerState) + sizeof(HoldLevels) * (size_t)N);
+        for (int i = 0; i < N; ++i) h_times[i] = reinterpret_cast<const StepScalars*>(h_stage)[i].t;
+        SBGM_HIP(hipMemcpyAsync(d_times.p, h_times, (size_t)N * 4, hipMemcpyHostToDevice, st));
+        for (int r0 = 0; r0 < N; r0 += CHUNK) {
+            float* out[9];
+            for (int i = 0; i < 9; ++i) out[i] = d_rows.f() + (size_t)r0 * TB + off4[i] * 4;
+            if (time_biases(d_times.f() + r0, nullptr, std::min(CHUNK, N - r0), reinterpret_cast<float*>(ws), out, TB, st)) return 1;
+        }
+        trows.rows = d_rows.f(); trows.tbrun = d_tbrun.f(); trows.n = 9; trows.BE = BE;
+        for (int i = 0; i <= 9; ++i) trows.off4[i] = off4[i];
+        if (sbgm_launch_time_rows_bcast(trows, 0, st)) return 1;
+        run.tbrun = d_tbrun.f();
     }
     SBGM_HIP(hipEventRecord(ev_stage, st));               // no host wait: the copies read pinned memory this handle owns
     stage_pending = true;
@@ -1310,7 +1419,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         }
         if (evaluate(a.cfg_scale)) return 1;
         return sbgm_launch_em_update(xs, xmean, score, z_ptrs ? next_z() : nullptr, sde_tab, d_state, nullptr, 0, t_dev, a.seed, B,
-                                     per, N, st, BE, run.nm, hold, jm);
+                                     per, N, st, BE, run.nm, hold, jm, trows);
     };
     // The run: N - tail steps (replays of the captured step, or eager launches), then `tail` eager last steps.  EM / PC: no tail,
     // the result is the x_mean slab, copied to `out`; EDM Heun: the tail is its Euler-only last step, which writes `out` itself.
@@ -1322,6 +1431,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn;
         key.known = hold.known; key.known_mask = hold.mask; key.levels = hold.levels;
         if (joint) { key.joint = 1; key.domain_h = joint->domain_h; key.ramp_len = joint->ramp_len; }
+        key.rows = trows.rows; key.tbrun = trows.tbrun;
         rc = run.capture(key, [&] { return step(false, false); });
         for (int i = 0; i < N - tail && rc == 0; ++i)
             if (hipGraphLaunch(step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
@@ -1802,6 +1912,21 @@ int sbgm_up_lowres_fwd(const float* x_lowres_nhwc, const float* w_packed, const 
     if (groups == 0 || normed) return 0;
     if (chunks == 0 && sbgm_launch_gn_partial(out, stats, B, H * W, C, groups, &chunks, st)) return 1;
     return sbgm_launch_groupnorm_apply(out, out, gamma, beta, nullptr, nullptr, SBGM_ACT_NONE, B, H * W, C, groups, eps, stats, chunks, st);
+}
+
+int sbgm_time_row_layout(const int* channels, int n, int* offsets) {
+    if (!channels || !offsets || n < 1 || n > 16) return -1;
+    offsets[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        if (channels[i] < 4 || channels[i] % 4) return -1;
+        offsets[i + 1] = offsets[i] + channels[i];
+    }
+    return offsets[n];
+}
+int64_t sbgm_time_row_index(int64_t advances, int64_t num_steps) {
+    unsigned long long s = 0;
+    for (int64_t k = 0; k < advances; ++k) s = sampler_next_step(s, (unsigned long long)num_steps);
+    return (int64_t)s;
 }
 
 int sbgm_event_create(void** ev) { hipEvent_t e; SBGM_HIP(hipEventCreate(&e)); *ev = e; return 0; }

@@ -22,6 +22,12 @@ int sbgm_launch_adam_ema_batched(const sbgm_adam_desc* desc_dev, float* const* e
 int sbgm_launch_ema_batched(const sbgm_adam_desc* desc_dev, float* const* ema_dev, int n, int total_blocks, float ema_rate, hipStream_t st);
 int sbgm_launch_pack_conv_weights_batched(const sbgm_pack_desc* desc_dev, int n, int total_blocks, hipStream_t st);
 int sbgm_launch_conv(const ConvGeom& g, ConvParams p, const ConvTile& cfg, float* partial_ws, hipStream_t st);
+// A BasicBlock's 3x3 / stride 2 / pad 1 convolution (main) and its 1x1 / stride 2 shortcut (aux), both of one input, in ONE launch of
+// the implicit-GEMM kernels (conv_igemm.hip): served for a small set of tile combinations without grid split-K; the launch computes what
+// the two launches of the same tiles compute, bit for bit
+bool sbgm_conv_pair_served(const ConvGeom& gm, const ConvParams& pm, const ConvTile& tm, const ConvGeom& ga, const ConvParams& pa,
+                           const ConvTile& ta);
+int sbgm_launch_conv_pair(ConvParams pm, const ConvTile& tm, ConvParams pa, const ConvTile& ta, hipStream_t st);
 // When set, the launchers below trust that their atomically accumulated scratch (weight-gradient slab, norm-backward sums)
 // arrives zeroed and skip their own memsets (the training path zeroes one pooled buffer per step instead of ~75 small ones).
 extern int sbgm_scratch_prezeroed;
@@ -124,6 +130,7 @@ struct TimeProj {          // out[b][c] = bias[c] + sum_d W[c][d] * silu(emb_g[b
     float* out;            // [B][ch]
     int ch;
     int emb;               // which embedding (index into freqs[])
+    int out_stride = 0;    // floats between the rows of `out` (0: ch, rows packed); a run's time-row table uses its row length
 };
 struct TimeEmbedArgs {
     const float* t;             // [B]
@@ -213,6 +220,8 @@ struct SamplerState {      // device-resident, lets one captured graph serve eve
                                     // reusable across runs with different seeds (the by-value seed argument serves eager calls)
     unsigned long long n_steps;     // length of the run (0: use the launch argument): the last step does not advance past it
 };
+// the step after step s of a run of ns steps: the last step stays where it is
+__host__ __device__ inline unsigned long long sampler_next_step(unsigned long long s, unsigned long long ns) { return s + 1 < ns ? s + 1 : s; }
 // optional map from tile-local quads to domain-global Philox counters (null origins = plain element order)
 struct NoiseMap {
     const int* origins;   // device [B][2] = (y0, x0) of each tile in the domain, x0 % 4 == 0
@@ -244,6 +253,17 @@ struct Hold {
     unsigned long long seed;   // used without a state (the state's seed otherwise)
     NoiseMap nm;
 };
+// Time rows of an EM / PC run without labels: every sample of such a run has the same time and all N times are known
+// when the run starts, so the n time-bias vectors of every step are computed once per run (rows) and the advance at the end of a step
+// copies the next step's row to where the forward reads its time biases (tbrun), the same row for each of the BE samples.
+// rows == null (the default): the forward computes its own embedding and projections.
+struct TimeRows {
+    const float* rows;     // [N][TB]: row s = the n vectors at time table[s].t, concatenated
+    float* tbrun;          // [n][BE][ch_i], contiguous: vector i of sample b at tbrun + BE * off_i + b * ch_i
+    int n, BE;
+    int off4[17];          // start of vector i within a row, in 16-byte quads; off4[n] = TB / 4
+};
+int sbgm_launch_time_rows_bcast(const TimeRows& tr, int row, hipStream_t st);   // tbrun <- row `row` (the run's first evaluation)
 int sbgm_launch_fill_t(float* t, float value, int B, hipStream_t st);
 // `state` != null: scalars / RNG offset come from device memory (graph-replayable) and the state is advanced after
 // the update; `state` == null: explicit by-value scalars and draw index.
@@ -254,7 +274,8 @@ int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const flo
                           SamplerState* state, const StepScalars* sc_val, unsigned long long draw_index, float* t_dev,
                           unsigned long long seed, int B, size_t per_sample, int n_steps, hipStream_t st,
                           int t_entries = 0,    // entries of t_dev to refresh (0 -> B; 2B for the batched guidance pass)
-                          NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{}, const JointMap& jm = JointMap{});
+                          NoiseMap nm = NoiseMap{}, const Hold& hold = Hold{}, const JointMap& jm = JointMap{},
+                          const TimeRows& tr = TimeRows{});    // tr.rows set: the advance also publishes the next step's time row
 // jm set: the step size is the batch-mean rule over the raw tile scores (one step size for the domain), not tile mode's per-tile norm
 int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr_noise_norm, double* sumsq_ws,
                          SamplerState* state, unsigned long long draw_index, unsigned long long seed, int B,

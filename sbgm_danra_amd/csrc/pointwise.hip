@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void time_proj_kernel(TimeEmbedArgs a, int tot
         float v = 0.f;
 #pragma unroll
         for (int j = 0; j < TP_BG; ++j) v = (lane == j) ? acc[j] : v;
-        pr.out[(size_t)(bg * TP_BG + lane) * pr.ch + c] = v + pr.bias[c];
+        pr.out[(size_t)(bg * TP_BG + lane) * (pr.out_stride ? pr.out_stride : pr.ch) + c] = v + pr.bias[c];
     }
 }
 

@@ -53,6 +53,29 @@ __device__ __forceinline__ f32x4 load_score(const float* __restrict__ score, siz
     return reinterpret_cast<const f32x4*>(score)[i];
 }
 
+// tbrun <- row `row` of the run's time rows, the same row for every sample.  A thread loads ONE quad of the row (its vector is found by
+// comparing against the n starts, unrolled so that they stay in scalar registers) and then only stores: to that quad's place in the
+// samples g, g + G, ... of tbrun [n][BE][ch_i], G = the groups of TB / 4 threads the workgroup holds.  The stores of a wave are
+// consecutive quads of one sample's vector, and none waits for a load (a load - store pair per iteration made this 7 us at C2).
+__device__ __forceinline__ void bcast_time_row(const TimeRows& tr, unsigned long long row, int tid, int nthreads) {
+    const int tb4 = tr.off4[tr.n];
+    const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(tr.rows) + (size_t)row * tb4;
+    f32x4* __restrict__ dst = reinterpret_cast<f32x4*>(tr.tbrun);
+    const int G = nthreads >= tb4 ? nthreads / tb4 : 1;
+    const int g = tid / tb4;
+    if (g >= G) return;
+    for (int q = tid - g * tb4; q < tb4; q += nthreads) {        // one pass when the workgroup has at least TB / 4 threads
+        int lo = 0, ch4 = tr.off4[1];
+#pragma unroll
+        for (int k = 1; k < 16; ++k)
+            if (k < tr.n && q >= tr.off4[k]) { lo = tr.off4[k]; ch4 = tr.off4[k + 1] - tr.off4[k]; }
+        const f32x4 v = src[q];
+        f32x4* d = dst + (size_t)lo * tr.BE + (q - lo);
+        for (int b = g; b < tr.BE; b += G) d[(size_t)b * ch4] = v;
+    }
+}
+__global__ __launch_bounds__(1024) void time_rows_bcast_kernel(TimeRows tr, int row) { bcast_time_row(tr, row, threadIdx.x, blockDim.x); }
+
 __global__ void fill_kernel(float* t, float v, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) t[i] = v;
@@ -107,16 +130,20 @@ __global__ __launch_bounds__(256) void em_update_kernel(float* __restrict__ x, f
 }
 
 // runs after the update kernel of a step: advance the step counter / RNG offset, publish the next time
+// and, for a run that keeps its time rows (tr.rows set), the next step's time biases: only the advance that moves the step publishes
+// them (the corrector's does not), and the last step republishes its own row
 __global__ void advance_kernel(SamplerState* state, const StepScalars* table, float* t_dev, int B, int advance_step,
-                               int n_steps) {
+                               int n_steps, TimeRows tr) {
     const unsigned long long s = state->step;
     const unsigned long long ns = state->n_steps ? state->n_steps : (unsigned long long)n_steps;
+    const unsigned long long nxt = sampler_next_step(s, ns);
     const int i = threadIdx.x;
     if (advance_step && t_dev && i < B) t_dev[i] = table[s].t_next;
+    if (advance_step && tr.rows) bcast_time_row(tr, nxt, i, blockDim.x);
     __syncthreads();
     if (i == 0) {
         state->rng_offset += 1;
-        if (advance_step) state->step = (s + 1 < ns) ? s + 1 : s;
+        if (advance_step) state->step = nxt;
     }
 }
 
@@ -301,9 +328,23 @@ inline int check_hold(const Hold& h, const char* who) {
     return 0;
 }
 
+// a usable time-row descriptor: 1..16 vectors of whole quads in increasing order, at least one sample
+inline int check_time_rows(const TimeRows& tr) {
+    if (!tr.rows || !tr.tbrun || tr.n < 1 || tr.n > 16 || tr.BE < 1 || tr.off4[0] != 0) return 1;
+    for (int i = 0; i < tr.n; ++i) if (tr.off4[i + 1] <= tr.off4[i]) return 1;
+    return 0;
+}
+
 inline int stream_blocks(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 2048); }
 
 }  // namespace
+
+int sbgm_launch_time_rows_bcast(const TimeRows& tr, int row, hipStream_t st) {
+    SBGM_CHECK(check_time_rows(tr) == 0 && row >= 0, "time_rows_bcast: bad time-row layout");
+    hipLaunchKernelGGL(time_rows_bcast_kernel, dim3(1), dim3(1024), 0, st, tr, row);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
 
 int sbgm_launch_fill_t(float* t, float value, int B, hipStream_t st) {
     hipLaunchKernelGGL(fill_kernel, dim3((B + 255) / 256), dim3(256), 0, st, t, value, B);
@@ -319,7 +360,7 @@ int sbgm_launch_init_noise(float* x, float scale, const float* z, unsigned long 
                      n / 4, nm, hold);
     SBGM_LAUNCH_CHECK();
     if (state) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0);
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0, TimeRows{});
         SBGM_LAUNCH_CHECK();
     }
     return 0;
@@ -328,20 +369,21 @@ int sbgm_launch_init_noise(float* x, float scale, const float* z, unsigned long 
 int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const float* z, const StepScalars* table,
                           SamplerState* state, const StepScalars* sc_val, unsigned long long draw_index, float* t_dev,
                           unsigned long long seed, int B, size_t per_sample, int n_steps, hipStream_t st, int t_entries,
-                          NoiseMap nm, const Hold& hold, const JointMap& jm) {
+                          NoiseMap nm, const Hold& hold, const JointMap& jm, const TimeRows& tr) {
     const size_t n = (size_t)B * per_sample;
     if (t_entries <= 0) t_entries = B;
     SBGM_CHECK(n % 4 == 0, "em_update: element count must be a multiple of 4");
     SBGM_CHECK(t_entries <= 1024, "em_update: %d time entries > 1024", t_entries);
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "em_update: need a device table or explicit scalars");
     SBGM_CHECK(!(hold.known && state && !hold.levels), "em_update: a held run with a device state needs the hold-level table");
+    SBGM_CHECK(!tr.rows || (state && check_time_rows(tr) == 0), "em_update: time rows need a device state and a valid layout");
     if (check_hold(hold, "em_update") || check_joint(jm, n, "em_update")) return 1;
     const StepScalars v = sc_val ? *sc_val : StepScalars{};
     SBGM_LAUNCH_STEP(em_update_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x, x_mean, score, z,
                      table, state, v, draw_index, seed, n / 4, nm, hold, jm);
     SBGM_LAUNCH_CHECK();
     if (state) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1024), 0, st, state, table, t_dev, t_entries, 1, n_steps);
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1024), 0, st, state, table, t_dev, t_entries, 1, n_steps, tr);
         SBGM_LAUNCH_CHECK();
     }
     return 0;
@@ -362,7 +404,7 @@ int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr
                      snr_noise_norm, sumsq_ws, state, draw_index, seed, B, n4, nm, hold, jm);
     SBGM_LAUNCH_CHECK();
     if (state) {
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0);
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 0, 0, TimeRows{});
         SBGM_LAUNCH_CHECK();
     }
     return 0;
@@ -404,7 +446,7 @@ int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* s
                      table, state, v, t_dev, t_dev ? t_entries : 0, n_steps, n / 4, hold, jm);
     SBGM_LAUNCH_CHECK();
     if (state) {                     // step counter and RNG offset: the EM mechanism, without its StepScalars time publish
-        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 1, n_steps);
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 1, n_steps, TimeRows{});
         SBGM_LAUNCH_CHECK();
     }
     return 0;
