@@ -26,7 +26,7 @@ int sbgm_abi_version(void);
 
 enum { SBGM_NONE = 0, SBGM_RELU = 1, SBGM_SILU = 2, SBGM_GELU = 3 };   /* activation codes */
 enum { SBGM_NORM_INSTANCE = 0, SBGM_NORM_GROUP = 1 };
-enum { SBGM_SAMPLER_EM = 0, SBGM_SAMPLER_PC = 1, SBGM_SAMPLER_EDM_HEUN = 2, SBGM_SAMPLER_RK45 = 3 };
+enum { SBGM_SAMPLER_EM = 0, SBGM_SAMPLER_PC = 1, SBGM_SAMPLER_EDM_HEUN = 2, SBGM_SAMPLER_RK45 = 3, SBGM_SAMPLER_DPMPP_2M = 4 };
 
 /* ------------------------------------------------------------------------------------------------------------
  * Model handle.  Replaces: training_utils.get_model -> Encoder/Decoder/ScoreNet construction
@@ -206,6 +206,24 @@ int sbgm_sampler_run_edm_joint(sbgm_model* m, const sbgm_sampler_args* a, float 
  * other samplers the call returns only when the run is complete. */
 int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, double t1, double rtol, double atol, int per_sample,
                          int64_t max_steps, const float* x0, int64_t* stats_i, double* stats_d, void* stream);
+
+/* Second-order multistep sampler at ONE evaluation per step: DPM-Solver++(2M) (Lu et al. 2022) on the Karras ladder of sbgm_sampler_run_edm
+ * (same sigma_min / sigma_max / rho rules, sigma_N = 0, no churn), for the same VE-SDE score network; eta > 0 is its SDE variant ("2M SDE",
+ * midpoint form).  a->kind must be SBGM_SAMPLER_DPMPP_2M; a->snr and a->cfg_scale_corrector are ignored; a->bn_train must be 0.
+ *   step i: D_i = x_i + sigma_i^2 score(x_i, t(sigma_i));  x_{i+1} = c_x x_i + c_0 D_i + c_1 D_{i-1} + c_z z_i  with, for sigma_{i+1} > 0,
+ *           h_i = ln(sigma_i / sigma_{i+1}), a_i = -expm1(-(1+eta) h_i), c_x = (sigma_{i+1} / sigma_i) exp(-eta h_i),
+ *           c_0 = a_i, c_1 = 0 (i = 0);  c_0 = a_i (1 + 1/(2r)), c_1 = -a_i / (2r), r = h_{i-1} / h_i (i >= 1),
+ *           c_z = s_noise sigma_{i+1} sqrt(-expm1(-2 eta h_i));  the last step is x_N = D_{N-1}.  The table is built in float64 and stored as
+ *           fp32.  Exactly N = num_steps network evaluations; out = x_N, NCHW [B,1,H,W].
+ *   noise:  init x = sigma_0 z_0; with eta > 0 also z_{1+i} for step i (the last step consumes its draw with c_z = 0): 1 draw, or 1 + N.
+ *   known, known_mask: both NULL, or constrained sampling as in the _held entry points: x_{i+1} = hold(., known + sigma_{i+1} z, m) with
+ *           z the run's draw 0 when eta = 0 (the point-mass trajectory, as EDM Heun) and the step's own draw when eta > 0 (as EM / PC);
+ *           out equals known where the mask is 1.  The history D is not held.
+ *   domain_h, ramp_len: both 0, or joint full-domain sampling as in the _joint entry points (the update reads the blended score).
+ * With use_graph one step (evaluation + update) is captured and replayed N times; a deterministic and a stochastic step never share a graph.
+ * A run without labels (a->y NULL) keeps its time rows like EM / PC.  Blocking behaviour is that of sbgm_sampler_run. */
+int sbgm_sampler_run_dpmpp(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float eta, float s_noise,
+                           const float* known, const float* known_mask, int domain_h, int ramp_len, void* stream);
 
 /* Conv autotuning: time the tile / split-K candidates of every convolution of the (B,H,W) plan once and keep the
  * fastest.  Synchronises the stream.  Optional; without it a static heuristic is used. */
@@ -627,7 +645,10 @@ int sbgm_dsm_loss_bwd(const float* score, const float* z, const float* std, cons
  *   cfg:      out = (1+w)*s_cond - w*s_uncond                                                        :55
  *   edm churn: x += churn_coef*z                     (EDM Heun, sbgm_sampler_run_edm)
  *   edm euler: d = -sigma_hat*score ; x_next = x_hat + (sigma_next - sigma_hat)*d
- *   edm heun:  x = x + (sigma_next - sigma_hat)*0.5*(d - sigma_next*score)   (x holds x_hat on entry)              */
+ *   edm heun:  x = x + (sigma_next - sigma_hat)*0.5*(d - sigma_next*score)   (x holds x_hat on entry)
+ *   dpmpp 2m:  D = x + sigma^2*score ; x = c_x*x + c_0*D + c_1*hist + c_z*z ; hist = D     (sbgm_sampler_run_dpmpp)
+ *              hist is read only when c_1 != 0 (it may hold anything on the first step); a draw is taken only when z is given or
+ *              c_z != 0.  A constrained loop follows it with sbgm_hold_known.                                          */
 int sbgm_em_step(float* x, float* x_mean, const float* score, const float* z, float g2, float dt, float noise_coef,
                  uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
 int sbgm_langevin_step(float* x, const float* score, const float* z, float snr_noise_norm, void* sumsq_ws /* >= 8*B B */,
@@ -638,6 +659,8 @@ int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, ui
 int sbgm_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, float sigma_hat, float sigma_next, int64_t n,
                    void* stream);
 int sbgm_edm_heun(float* x, const float* d, const float* score, float sigma_hat, float sigma_next, int64_t n, void* stream);
+int sbgm_dpmpp_2m_step(float* x, const float* score, float* hist, const float* z, float sigma, float c_x, float c_0, float c_1, float c_z,
+                       uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
 /* The hold of constrained sampling as an op of its own, called after a step op above by loops that run the network themselves:
  * x = hold(x, known + level*z, m) and, when x_mean is not NULL, x_mean = hold(x_mean, known, m).  z NULL -> the Philox draw
  * (seed, draw_index), i.e. the draw the step op just consumed. */

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libsbgm_hip.so")
 
 NONE, RELU, SILU, GELU = 0, 1, 2, 3
 NORM_INSTANCE, NORM_GROUP = 0, 1
-SAMPLER_EM, SAMPLER_PC, SAMPLER_EDM_HEUN, SAMPLER_RK45 = 0, 1, 2, 3
+SAMPLER_EM, SAMPLER_PC, SAMPLER_EDM_HEUN, SAMPLER_RK45, SAMPLER_DPMPP_2M = 0, 1, 2, 3, 4
 ODE_FINISHED, ODE_TOO_SMALL_STEP, ODE_NONFINITE, ODE_MAX_STEPS = 1, 2, 3, 4      # controller status of the RK45 solver
 ODE_PHASE_F0, ODE_PHASE_F1 = 7, 8                                              # sbgm_rk45_stage phases besides stages 1..6
 
@@ -85,6 +85,7 @@ SIGNATURES = {
     "sbgm_sampler_run_edm_held": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
     "sbgm_sampler_run_joint": (_i, [_vp, C.POINTER(SamplerArgs), _i, _i, _vp, _vp, _vp]),
     "sbgm_sampler_run_edm_joint": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp]),
+    "sbgm_sampler_run_dpmpp": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _vp, _vp, _i, _i, _vp]),
     "sbgm_sampler_run_ode": (_i, [_vp, C.POINTER(SamplerArgs), _d, _d, _d, _d, _i, _i64, _vp, _vp, _vp, _vp]),
     "sbgm_pointwise_chain": (_i, [_vp, _vp, _i64, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     "sbgm_sample_extremes": (_i, [_vp, _i, _i64, _f, _vp, _vp, _vp]),
@@ -200,6 +201,7 @@ SIGNATURES = {
     "sbgm_edm_churn": (_i, [_vp, _vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_edm_euler": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i64, _vp]),
     "sbgm_edm_heun": (_i, [_vp, _vp, _vp, _f, _f, _i64, _vp]),
+    "sbgm_dpmpp_2m_step": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _u64, _u64, _i64, _vp]),
     "sbgm_hold_known": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_rk45_state_bytes": (_i64, [_i]),
     "sbgm_rk45_partials_bytes": (_i64, [_i, _i64]),
@@ -227,7 +229,7 @@ SIGNATURES = {
     "sbgm_ensemble_products": (_i, [_vp, _vp, _i, _i, _i64, C.POINTER(_d), _i, C.POINTER(_f), _i] + [_vp] * 9),
 }
 
-ABI_VERSION = 4          # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 5          # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

@@ -405,6 +405,12 @@ int sbgm_edm_heun(float* x, const float* d, const float* score, float sigma_hat,
     const EdmStep sc{0.f, sigma_hat, sigma_next, 0.f, 0.f, 0.f};
     return sbgm_launch_edm_heun(x, nullptr, d, score, nullptr, nullptr, &sc, nullptr, 0, 1, (size_t)n, ST);
 }
+int sbgm_dpmpp_2m_step(float* x, const float* score, float* hist, const float* z, float sigma, float c_x, float c_0, float c_1, float c_z,
+                       uint64_t seed, uint64_t draw_index, int64_t n, void* stream) {
+    const DpmStep sc{sigma, 0.f, 0.f, c_x, c_0, c_1, c_z};
+    return sbgm_launch_dpmpp_2m(x, nullptr, score, hist, z, nullptr, nullptr, &sc, draw_index, seed, z != nullptr || c_z != 0.f, nullptr, 0,
+                                1, (size_t)n, ST);
+}
 
 int64_t sbgm_rk45_state_bytes(int groups) { return (int64_t)sbgm_ode_state_bytes(groups); }
 int64_t sbgm_rk45_partials_bytes(int B, int64_t per) { return (int64_t)sbgm_ode_partials_bytes(B, (size_t)per); }

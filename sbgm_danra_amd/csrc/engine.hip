@@ -305,7 +305,7 @@ struct sbgm_model {
     size_t ws_bytes = 0, ws_used = 0;
     // sampler state
     SamplerState* d_state = nullptr;
-    void* d_table = nullptr;                // step table of the current run: StepScalars rows (EM, PC) or EdmStep rows (EDM Heun)
+    void* d_table = nullptr;                // step table of the current run: StepScalars rows (EM, PC), EdmStep rows (EDM Heun) or DpmStep rows (2M)
     size_t table_bytes = 0;                 // its capacity
     HoldLevels* d_levels = nullptr;         // hold levels of a constrained EM / PC run, one row per step (allocated by the first such run)
     size_t levels_rows = 0;                 // its capacity
@@ -448,7 +448,8 @@ struct sbgm_model {
     std::map<std::array<int, 4>, size_t> ws_peak;
     size_t ws_target = 0;                   // largest measured total need (forward + sampler slabs) of any shape seen so far
     size_t fwd_need(int B, int H, int W, int bn_train = 0) const;
-    // persistent sampler slabs: x, score, x_mean (+ the Heun derivative d for SBGM_SAMPLER_EDM_HEUN), then time vector, norm partials.
+    // persistent sampler slabs: x, score, x_mean (+ the Heun derivative d for SBGM_SAMPLER_EDM_HEUN; SBGM_SAMPLER_DPMPP_2M keeps its
+    // history D in the x_mean slab), then time vector, norm partials.
     // Evaluations and autotuning reserve the three slabs of EM / PC, so that such a sampler finds its workspace settled.
     // SBGM_SAMPLER_RK45: network input, the 2B score of a guided evaluation, seven stage scores, y and y_new in float64 (two slabs
     // each), one slab for the state block and the norm partials.
@@ -487,8 +488,9 @@ struct sbgm_model {
     struct EdmArgs { float sigma_min, sigma_max, rho, s_churn, s_tmin, s_tmax, s_noise; };
     struct HeldArgs { const float *known, *mask; };        // constrained sampling: both device [B][1][H][W], used in place
     struct JointArgs { int domain_h, ramp_len; };          // joint tiled sampling: the B tiles are one domain of domain_h x a.domain_w
+    struct DpmArgs { float sigma_min, sigma_max, rho, eta, s_noise; };     // DPM-Solver++(2M): eta > 0 is the SDE variant
     int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr, const HeldArgs* held = nullptr,
-                const JointArgs* joint = nullptr);
+                const JointArgs* joint = nullptr, const DpmArgs* dpm = nullptr);
     struct OdeArgs { double t0, t1, rtol, atol; int per_sample; long long max_steps; const float* x0; int64_t* stats_i; double* stats_d; };
     int sampler_ode(const sbgm_sampler_args& a, hipStream_t st, const OdeArgs& o);
 };
@@ -1109,32 +1111,67 @@ static StepTable pc_table(void* stage, int N, float sig, float eps) {
     return {sizeof(StepScalars), tab[0].t};
 }
 
-// EDM Heun step table (Karras et al. 2022, Alg. 2) for the VE SDE std(t) = sqrt((sigma^2t - 1) / (2 ln sigma)): the Karras ladder between
-// sigma_min and sigma_max (<= 0: the trained range [std(eps), std(1)]; other values are clipped to it), churn gamma_i, t(sigma) =
-// log1p(2 ln sigma * s^2) / (2 ln sigma) clamped to [eps, 1].  float64 throughout, stored as fp32: score_sampling.edm_heun_schedule.
+// The Karras ladder of the few-step samplers for the VE SDE std(t) = sqrt((sigma^2t - 1) / (2 ln sigma)): sigma_0 .. sigma_{N-1} between
+// sigma_min and sigma_max (<= 0: the trained range [std(eps), std(1)]; other values are clipped to it), sigma_N = 0, and t(sigma) =
+// log1p(2 ln sigma * s^2) / (2 ln sigma) clamped to [eps, 1].  float64 throughout.
+struct KarrasLadder {
+    double ls, lo, hi, eps;
+    std::vector<double> sg;                                // [N + 1]
+    KarrasLadder(int N, double sig, double eps_, float sigma_min, float sigma_max, float rho_) : ls(std::log(sig)), eps(eps_), sg(N + 1) {
+        auto std_of = [&](double t) { return std::sqrt(std::expm1(2.0 * t * ls) / (2.0 * ls)); };
+        lo = std_of(eps); hi = std_of(1.0);
+        const double smin = sigma_min > 0 ? std::min(hi, std::max(lo, (double)sigma_min)) : lo;
+        const double smax = sigma_max > 0 ? std::min(hi, std::max(lo, (double)sigma_max)) : hi;
+        const double rho = rho_, a0 = std::pow(smax, 1.0 / rho), a1 = std::pow(smin, 1.0 / rho);
+        for (int i = 0; i < N; ++i) sg[i] = std::pow(a0 + (double)i / (double)(N - 1) * (a1 - a0), rho);
+        sg[0] = smax; sg[N - 1] = smin; sg[N] = 0.0;       // the ends exactly (the power round trip is off by an ulp)
+    }
+    double t_of(double s) const {                          // clamped in sigma too: sigma >= std(1) is t = 1 exactly
+        return s >= hi ? 1.0 : s <= lo ? eps : std::min(1.0, std::max(eps, std::log1p(2.0 * ls * s * s) / (2.0 * ls)));
+    }
+};
+
+// EDM Heun step table (Karras et al. 2022, Alg. 2): the ladder with the churn gamma_i.  Stored as fp32: score_sampling.edm_heun_schedule.
 static StepTable edm_table(void* stage, int N, double sig, double eps, const sbgm_model::EdmArgs& e) {
     EdmStep* tab = static_cast<EdmStep*>(stage);
-    const double ls = std::log(sig);
-    auto std_of = [&](double t) { return std::sqrt(std::expm1(2.0 * t * ls) / (2.0 * ls)); };
-    const double lo = std_of(eps), hi = std_of(1.0);
-    auto t_of = [&](double s) {                            // clamped in sigma too: sigma >= std(1) is t = 1 exactly
-        return s >= hi ? 1.0 : s <= lo ? eps : std::min(1.0, std::max(eps, std::log1p(2.0 * ls * s * s) / (2.0 * ls)));
-    };
-    const double smin = e.sigma_min > 0 ? std::min(hi, std::max(lo, (double)e.sigma_min)) : lo;
-    const double smax = e.sigma_max > 0 ? std::min(hi, std::max(lo, (double)e.sigma_max)) : hi;
-    const double rho = e.rho, a0 = std::pow(smax, 1.0 / rho), a1 = std::pow(smin, 1.0 / rho);
-    std::vector<double> sg(N + 1);
-    for (int i = 0; i < N; ++i) sg[i] = std::pow(a0 + (double)i / (double)(N - 1) * (a1 - a0), rho);
-    sg[0] = smax; sg[N - 1] = smin; sg[N] = 0.0;           // the ends exactly (the power round trip is off by an ulp)
+    const KarrasLadder k(N, sig, eps, e.sigma_min, e.sigma_max, e.rho);
+    const std::vector<double>& sg = k.sg;
     const double gmax = std::min((double)e.s_churn / (double)N, std::sqrt(2.0) - 1.0);
     for (int i = 0; i < N; ++i) {
         double g = (e.s_tmin <= sg[i] && sg[i] <= e.s_tmax) ? gmax : 0.0;
         g = std::min(g, sg[0] / sg[i] - 1.0);
         const double sh = sg[i] * (1.0 + g);
-        tab[i] = EdmStep{(float)sg[i], (float)sh, (float)sg[i + 1], (float)t_of(sh), (float)t_of(sg[i + 1]),
+        tab[i] = EdmStep{(float)sg[i], (float)sh, (float)sg[i + 1], (float)k.t_of(sh), (float)k.t_of(sg[i + 1]),
                          (float)((double)e.s_noise * std::sqrt(std::max(0.0, sh * sh - sg[i] * sg[i])))};
     }
     return {sizeof(EdmStep), tab[0].t_hat};
+}
+
+// DPM-Solver++(2M) step table (Lu et al. 2022; eta > 0: 2M SDE, midpoint form) on the same ladder, alpha = 1: the coefficients of
+// x_{i+1} = c_x x_i + c_0 D_i + c_1 D_{i-1} + c_z z_i (kernels.h: DpmStep).  Stored as fp32: score_sampling.dpmpp_2m_schedule.
+static StepTable dpm_table(void* stage, int N, double sig, double eps, const sbgm_model::DpmArgs& d) {
+    DpmStep* tab = static_cast<DpmStep*>(stage);
+    const KarrasLadder k(N, sig, eps, d.sigma_min, d.sigma_max, d.rho);
+    const std::vector<double>& sg = k.sg;
+    const double eta = d.eta;
+    double h_prev = 0.0;
+    for (int i = 0; i < N; ++i) {
+        double c_x = 0.0, c_0 = 1.0, c_1 = 0.0, c_z = 0.0;   // the last step: x_N = D_{N-1}
+        if (i + 1 < N) {
+            const double h = std::log(sg[i] / sg[i + 1]), a = -std::expm1(-(1.0 + eta) * h);
+            c_x = sg[i + 1] / sg[i] * std::exp(-eta * h);
+            c_0 = a;
+            if (i >= 1) {
+                const double r = h_prev / h;
+                c_0 = a * (1.0 + 1.0 / (2.0 * r));
+                c_1 = -a / (2.0 * r);
+            }
+            c_z = (double)d.s_noise * sg[i + 1] * std::sqrt(std::max(0.0, -std::expm1(-2.0 * eta * h)));
+            h_prev = h;
+        }
+        tab[i] = DpmStep{(float)sg[i], (float)k.t_of(sg[i]), (float)k.t_of(sg[i + 1]), (float)c_x, (float)c_0, (float)c_1, (float)c_z};
+    }
+    return {sizeof(DpmStep), tab[0].t};
 }
 
 // Condition tensors of a run's network evaluations: the caller's, or with guidance (guided_score_fn :27-43) per-call copies of 2B rows
@@ -1262,8 +1299,10 @@ struct SamplerRun {
 };
 
 int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm, const HeldArgs* held,
-                        const JointArgs* joint) {
+                        const JointArgs* joint, const DpmArgs* dpm) {
     const bool heun = edm != nullptr;                      // only sbgm_sampler_run_edm passes EDM arguments
+    const bool dpm2m = dpm != nullptr;                     // only sbgm_sampler_run_dpmpp passes 2M arguments
+    const bool dpm_sde = dpm2m && dpm->eta > 0.f;          // 2M SDE: every step takes a draw
     SBGM_CHECK(!held || (held->known && held->mask), "sampler: a constrained run needs both known and known_mask");
     if (joint) {
         SBGM_CHECK(a.tile_origins != nullptr, "sampler: a joint run needs tile_origins (its samples are the tiles of one domain)");
@@ -1282,8 +1321,9 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
                        a.W, joint->domain_h, a.domain_w);
         }
     }
-    SBGM_CHECK(heun ? a.kind == SBGM_SAMPLER_EDM_HEUN : (a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC),
-               "sampler: unknown kind %d", a.kind);
+    SBGM_CHECK(!(heun && dpm2m), "sampler: EDM Heun and 2M arguments exclude each other");
+    SBGM_CHECK(heun ? a.kind == SBGM_SAMPLER_EDM_HEUN : dpm2m ? a.kind == SBGM_SAMPLER_DPMPP_2M
+                    : (a.kind == SBGM_SAMPLER_EM || a.kind == SBGM_SAMPLER_PC), "sampler: unknown kind %d", a.kind);
     SBGM_CHECK(a.num_steps >= 2, "sampler: num_steps=%d must be >= 2 (step size = t0 - t1)", a.num_steps);
     SBGM_CHECK(a.out != nullptr, "sampler: out is required");
     SamplerRun run{this, a, caller, "sampler", a.use_graph && !a.noise};
@@ -1293,8 +1333,8 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     hipStream_t& st = run.st;
 
     // ---- step table and initial state, written into the pinned staging buffer and uploaded from there --------------------------
-    static_assert(sizeof(EdmStep) >= sizeof(StepScalars), "the staging buffer is sized for the larger row");
-    const size_t stage_need = (sizeof(EdmStep) + sizeof(HoldLevels) + sizeof(float)) * (size_t)N + sizeof(SamplerState);
+    static_assert(sizeof(DpmStep) >= sizeof(EdmStep) && sizeof(EdmStep) >= sizeof(StepScalars), "the staging buffer is sized for the largest row");
+    const size_t stage_need = (sizeof(DpmStep) + sizeof(HoldLevels) + sizeof(float)) * (size_t)N + sizeof(SamplerState);
     if (stage_pending) {                                   // the previous call's upload still reads the buffer (normally long done)
         SBGM_HIP(hipEventSynchronize(ev_stage));
         stage_pending = false;
@@ -1302,12 +1342,13 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     if (h_stage_bytes < stage_need) {
         if (h_stage) SBGM_HIP(hipHostFree(h_stage));
         h_stage = nullptr;
-        h_stage_bytes = std::max(stage_need, (sizeof(EdmStep) + sizeof(HoldLevels) + sizeof(float)) * (size_t)4096 + sizeof(SamplerState));
+        h_stage_bytes = std::max(stage_need, (sizeof(DpmStep) + sizeof(HoldLevels) + sizeof(float)) * (size_t)4096 + sizeof(SamplerState));
         SBGM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_stage), h_stage_bytes, hipHostMallocDefault));
     }
     if (!ev_stage) SBGM_HIP(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming));
     const float sig = cfg.sigma;
     const StepTable tab = heun ? edm_table(h_stage, N, (double)sig, (double)a.eps, *edm)
+                        : dpm2m ? dpm_table(h_stage, N, (double)sig, (double)a.eps, *dpm)
                         : a.kind == SBGM_SAMPLER_EM ? em_table(h_stage, N, sig, a.eps) : pc_table(h_stage, N, sig, a.eps);
     const size_t tab_bytes = tab.row_bytes * (size_t)N;
     if (table_bytes < tab_bytes) {                         // roomy: a new table address invalidates the cached step graph
@@ -1323,11 +1364,12 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     SBGM_HIP(hipMemcpyAsync(d_state, state0, sizeof(SamplerState), hipMemcpyHostToDevice, st));
     // Constrained EM / PC run: the levels its held pixels are re-noised to, std(t_i) and std(t_{i+1}) (0 after the last step) with std =
     // marginal_prob_std in double at the table's fp32 times, as a table parallel to the step table (EDM Heun: EdmStep has sigma_next).
+    // 2M: the ladder itself, sigma_i and sigma_{i+1} as the table stores them.
     Hold hold{};
     if (held) {
         hold.known = held->known;
         hold.mask = held->mask;
-        hold.z0 = heun ? a.noise : nullptr;
+        hold.z0 = heun || (dpm2m && !dpm_sde) ? a.noise : nullptr;     // the deterministic kinds hold with the run's draw 0
         hold.seed = a.seed;
     }
     if (held && !heun) {
@@ -1340,7 +1382,9 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         HoldLevels* lv = reinterpret_cast<HoldLevels*>(h_stage + tab_bytes + sizeof(SamplerState));
         const StepScalars* rows = reinterpret_cast<const StepScalars*>(h_stage);
         const double lsd = std::log((double)sig);
-        for (int i = 0; i < N; ++i) lv[i].cur = (float)std::max(std::sqrt(std::expm1(2.0 * (double)rows[i].t * lsd) / (2.0 * lsd)), 1e-5);
+        for (int i = 0; i < N; ++i)
+            lv[i].cur = dpm2m ? reinterpret_cast<const DpmStep*>(h_stage)[i].sigma
+                              : (float)std::max(std::sqrt(std::expm1(2.0 * (double)rows[i].t * lsd) / (2.0 * lsd)), 1e-5);
         for (int i = 0; i < N; ++i) lv[i].next = i + 1 < N ? lv[i + 1].cur : 0.f;
         SBGM_HIP(hipMemcpyAsync(d_levels, lv, sizeof(HoldLevels) * (size_t)N, hipMemcpyHostToDevice, st));
         hold.levels = d_levels;
@@ -1348,7 +1392,8 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     // Time rows: an EM / PC run without labels evaluates every sample at the table's time of the step, so the nine
     // time-bias vectors of all N steps are computed here, once per call and outside the captured step, by the forward's own two kernels
     // with the N table times as their "samples" (a row does not depend on the other rows: bit-equal to what the step would compute);
-    // the step's advance then copies row step + 1 into tbrun.  EDM Heun evaluates at two times per step and keeps its launches.
+    // the step's advance then copies row step + 1 into tbrun.  EDM Heun evaluates at two times per step and keeps its launches; a 2M
+    // step evaluates once, at its table's time, and keeps its rows like EM / PC.
     TimeRows trows{};
     const bool keep_rows = !heun && a.y == nullptr && env_time_rows();
     if (keep_rows) {
@@ -1361,7 +1406,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         if (d_times.need((size_t)N * 4, (size_t)4096 * 4) || d_rows.need((size_t)N * TB * 4, (size_t)1024 * TB * 4) ||
             d_tbrun.need((size_t)BE * TB * 4, (size_t)64 * TB * 4)) return 1;
         float* h_times = reinterpret_cast<float*>(h_stage + tab_bytes + sizeof(SamplerState) + sizeof(HoldLevels) * (size_t)N);
-        for (int i = 0; i < N; ++i) h_times[i] = reinterpret_cast<const StepScalars*>(h_stage)[i].t;
+        for (int i = 0; i < N; ++i) h_times[i] = dpm2m ? reinterpret_cast<const DpmStep*>(h_stage)[i].t : reinterpret_cast<const StepScalars*>(h_stage)[i].t;
         SBGM_HIP(hipMemcpyAsync(d_times.p, h_times, (size_t)N * 4, hipMemcpyHostToDevice, st));
         for (int r0 = 0; r0 < N; r0 += CHUNK) {
             float* out[9];
@@ -1377,11 +1422,13 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     stage_pending = true;
     const StepScalars* sde_tab = static_cast<const StepScalars*>(d_table);
     const EdmStep* edm_tab = static_cast<const EdmStep*>(d_table);
+    const DpmStep* dpm_tab = static_cast<const DpmStep*>(d_table);
 
     if (run.begin()) return 1;
     hold.nm = run.nm;
     const JointMap jm = joint ? JointMap{a.tile_origins, B, a.H, a.W, joint->domain_h, a.domain_w, joint->ramp_len} : JointMap{};
-    // slabs: x (the network input), score, x_mean, and for EDM Heun the derivative d; EDM Heun keeps its state x / x_hat in x_mean
+    // slabs: x (the network input), score, x_mean, and for EDM Heun the derivative d; EDM Heun keeps its state x / x_hat in x_mean;
+    // 2M keeps its state in the network input and its history D_{i-1} in x_mean
     float *xs = run.slab_at(0), *score = run.slab_at(1), *xmean = run.slab_at(2), *dheun = heun ? run.slab_at(3) : nullptr;
     float* t_dev = run.t_vec();
     double* sumsq = run.partials();                          // the Langevin corrector's norm partials
@@ -1392,7 +1439,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     const float* z = a.noise;
     size_t draw = 0;
     auto next_z = [&]() -> const float* { const float* p = z ? z + draw * n : nullptr; ++draw; return p; };
-    const float x0_scale = heun ? reinterpret_cast<const EdmStep*>(h_stage)->sigma : std1;
+    const float x0_scale = heun ? reinterpret_cast<const EdmStep*>(h_stage)->sigma : dpm2m ? reinterpret_cast<const DpmStep*>(h_stage)->sigma : std1;
     if (sbgm_launch_init_noise(heun ? xmean : xs, x0_scale, next_z(), a.seed, d_state, 0, n, st, run.nm, hold)) return 1;
     if (heun) SBGM_HIP(hipMemcpyAsync(xs, xmean, n * 4, hipMemcpyDeviceToDevice, st));
     if (sbgm_launch_fill_t(t_dev, tab.t_first, BE, st)) return 1;
@@ -1403,7 +1450,13 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     // One step of the run's kind; z_ptrs: read the caller's noise draws (eager runs).
     //   EM:  eval -> predictor + advance          PC: eval -> Langevin corrector -> eval -> predictor + advance
     //   EDM: (churn) -> eval -> euler -> eval -> heun + advance; `last` (sigma_N = 0) is Euler only, into `out`
+    //   2M:  eval -> update + advance, all N steps alike (the last row of the table makes x_N = D_{N-1})
     auto step = [&](bool z_ptrs, bool last) -> int {
+        if (dpm2m) {
+            if (evaluate(a.cfg_scale)) return 1;
+            return sbgm_launch_dpmpp_2m(xs, nullptr, score, xmean, z_ptrs && dpm_sde ? next_z() : nullptr, dpm_tab, d_state, nullptr, 0, a.seed,
+                                        dpm_sde, t_dev, BE, N, n, st, run.nm, hold, jm, trows);
+        }
         if (heun) {
             if (churn && sbgm_launch_edm_churn(xmean, xs, z_ptrs ? next_z() : nullptr, edm_tab, d_state, nullptr, 0, a.seed, n, st, run.nm))
                 return 1;
@@ -1422,13 +1475,14 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
                                      per, N, st, BE, run.nm, hold, jm, trows);
     };
     // The run: N - tail steps (replays of the captured step, or eager launches), then `tail` eager last steps.  EM / PC: no tail,
-    // the result is the x_mean slab, copied to `out`; EDM Heun: the tail is its Euler-only last step, which writes `out` itself.
+    // the result is the x_mean slab, copied to `out`; EDM Heun: the tail is its Euler-only last step, which writes `out` itself; 2M: no
+    // tail, the result is its state, the network-input slab.
     const int tail = heun ? 1 : 0;
     int rc = 0;
     if (run.graphed) {
         StepGraphKey key{};
-        key.churn = churn; key.domain_w = a.domain_w; key.origins = a.tile_origins; key.table = d_table;
-        key.cfg_corr = heun ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun ? 0.f : snr_nn;
+        key.churn = churn || dpm_sde; key.domain_w = a.domain_w; key.origins = a.tile_origins; key.table = d_table;
+        key.cfg_corr = heun || dpm2m ? 0.f : a.cfg_scale_corrector; key.snr_nn = heun || dpm2m ? 0.f : snr_nn;
         key.known = hold.known; key.known_mask = hold.mask; key.levels = hold.levels;
         if (joint) { key.joint = 1; key.domain_h = joint->domain_h; key.ramp_len = joint->ramp_len; }
         key.rows = trows.rows; key.tbrun = trows.tbrun;
@@ -1440,7 +1494,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     }
     if (tail && rc == 0) rc = step(z != nullptr, true);
     if ((rc = run.replay_done(rc))) return rc;
-    if (!tail) SBGM_HIP(hipMemcpyAsync(a.out, xmean, n * 4, hipMemcpyDeviceToDevice, st));
+    if (!tail) SBGM_HIP(hipMemcpyAsync(a.out, dpm2m ? xs : xmean, n * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
@@ -1555,7 +1609,7 @@ const char* sbgm_get_error();
 extern "C" {
 
 const char* sbgm_last_error(void) { return sbgm_get_error(); }
-int sbgm_abi_version(void) { return 4; }
+int sbgm_abi_version(void) { return 5; }
 int sbgm_model_config_size(void) { return (int)sizeof(sbgm_model_config); }
 
 int sbgm_model_create(const sbgm_model_config* cfg, sbgm_model** out) {
@@ -1693,6 +1747,22 @@ int sbgm_sampler_run_edm_joint(sbgm_model* m, const sbgm_sampler_args* a, float 
     const sbgm_model::HeldArgs h{known, known_mask};
     const sbgm_model::JointArgs j{domain_h, ramp_len};
     return m->sampler(*a, (hipStream_t)stream, &e, known ? &h : nullptr, &j);
+}
+
+// DPM-Solver++(2M) / 2M SDE with its optional parts as arguments: the same sbgm_model::sampler, the dpmpp_2m kernels.
+int sbgm_sampler_run_dpmpp(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float eta, float s_noise,
+                           const float* known, const float* known_mask, int domain_h, int ramp_len, void* stream) {
+    SBGM_CHECK(a, "sampler_run_dpmpp: null args");
+    SBGM_CHECK(a->kind == SBGM_SAMPLER_DPMPP_2M, "sampler_run_dpmpp: kind %d is not SBGM_SAMPLER_DPMPP_2M", a->kind);
+    SBGM_CHECK(!a->bn_train, "sampler_run_dpmpp: serves eval-mode BatchNorm only (bn_train must be 0)");
+    SBGM_CHECK(rho > 0.f && eta >= 0.f && s_noise >= 0.f, "sampler_run_dpmpp: need rho > 0, eta >= 0, s_noise >= 0");
+    SBGM_CHECK(!(sigma_min > 0.f && sigma_max > 0.f && sigma_min >= sigma_max), "sampler_run_dpmpp: sigma_min %g >= sigma_max %g",
+               sigma_min, sigma_max);
+    SBGM_CHECK((known == nullptr) == (known_mask == nullptr), "sampler_run_dpmpp: known and known_mask must be given together");
+    const sbgm_model::DpmArgs d{sigma_min, sigma_max, rho, eta, s_noise};
+    const sbgm_model::HeldArgs h{known, known_mask};
+    const sbgm_model::JointArgs j{domain_h, ramp_len};
+    return m->sampler(*a, (hipStream_t)stream, nullptr, known ? &h : nullptr, domain_h || ramp_len ? &j : nullptr, &d);
 }
 
 int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, double t1, double rtol, double atol, int per_sample,

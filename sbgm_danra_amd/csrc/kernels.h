@@ -310,6 +310,26 @@ int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* s
                          const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st,
                          const Hold& hold = Hold{}, const JointMap& jm = JointMap{});
 
+// DPM-Solver++(2M) sampler (Lu et al. 2022; eta > 0: its SDE variant in midpoint form) on the same Karras ladder: one row per step i,
+// built in float64 on the host and stored as fp32 (score_sampling.dpmpp_2m_schedule is the same table).  With D_i = x_i + sigma_i^2 s_i
+// the step is x_{i+1} = c_x x_i + c_0 D_i + c_1 D_{i-1} + c_z z_i; row 0 has c_1 = 0 and the last row is (0, 1, 0, 0): x_N = D_{N-1}.
+struct DpmStep {
+    float sigma;           // sigma_i
+    float t;               // t(sigma_i), the time of the step's evaluation
+    float t_next;          // t(sigma_{i+1}), the time of the next step's evaluation (unused after the last step)
+    float c_x, c_0, c_1;   // coefficients of x_i, D_i and the history D_{i-1}
+    float c_z;             // coefficient of the step's draw (0 in a deterministic run and on the last step)
+};
+// one 2M step: x (in place; x_copy, may be null, receives it too) and hist <- D_i (read only when c_1 != 0); t_dev[0 .. t_entries) =
+// t_next; with a state the step counter / RNG offset advance (tr.rows set: the advance also publishes the next step's time row).
+// stochastic: the step takes its draw (z, or null: Philox at the run's RNG offset / draw_index); a deterministic step draws nothing.
+// Held: x = hold(x, known + level z, m), level = hold.levels[step].next (hold.lv.next without a state), z = the step's draw in a
+// stochastic run, else the run's draw 0 (hold.z0 or recomputed).  The history is not held.
+int sbgm_launch_dpmpp_2m(float* x, float* x_copy, const float* score, float* hist, const float* z, const DpmStep* table,
+                         SamplerState* state, const DpmStep* sc_val, unsigned long long draw_index, unsigned long long seed,
+                         int stochastic, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st, NoiseMap nm = NoiseMap{},
+                         const Hold& hold = Hold{}, const JointMap& jm = JointMap{}, const TimeRows& tr = TimeRows{});
+
 // ---- ode.hip (rk45_sampler: Dormand-Prince 5(4) with scipy's step controller, on the device) -----------------------------------
 enum { SBGM_ODE_RUNNING = 0, SBGM_ODE_FINISHED = 1, SBGM_ODE_TOO_SMALL_STEP = 2, SBGM_ODE_NONFINITE = 3, SBGM_ODE_MAX_STEPS = 4 };
 enum { SBGM_ODE_PHASE_F0 = 7, SBGM_ODE_PHASE_F1 = 8 };     // stage phases besides the Runge-Kutta stages 1..6

@@ -1,11 +1,12 @@
 // K25 / K26 / K27: per-step state updates of the reverse-SDE samplers, fused with the Gaussian draw.
 // reference sbgm/score_sampling.py:124-125 (Euler-Maruyama), :200-204 (Langevin corrector), :224-227 (predictor),
-// :55 (classifier-free-guidance combine).  Beyond the reference: the EDM Heun updates of edm_heun_sampler (churn / euler / heun).
+// :55 (classifier-free-guidance combine).  Beyond the reference: the EDM Heun updates of edm_heun_sampler (churn / euler / heun) and the
+// DPM-Solver++(2M) update of dpmpp_2m_sampler.
 //
 // Noise: when `z` is null the kernels draw N(0,1) themselves (Philox4x32-10 counter RNG + Box-Muller, keyed by
 // (seed, running offset, element index)), so the sampler loop never round-trips noise through HBM; when `z`
 // is given (parity mode) the host-generated draw is used verbatim.
-// Joint tiled sampling: the JOINT instantiations of the four update kernels read the score through the partition-of-unity
+// Joint tiled sampling: the JOINT instantiations of the five update kernels read the score through the partition-of-unity
 // blend of all tiles' scores (tile_blend.h), so the T tiles of a domain are one diffusion and copies of a domain pixel stay bit-equal.
 // All per-step scalars come from a device-resident table indexed by a device-side step counter, so one captured
 // hipGraph replays for every step.
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(256) void init_noise_kernel(float* __restrict__ x, 
 }
 
 // x_mean = x + g^2 dt * score ;  x = x_mean + noise_coef * N(0,1);  HELD: x_mean = hold(., known), x = hold(., known + std(t_next) z)
-// with the step's own draw z (the unheld branch discards it on a held pixel, so it is a fresh draw there);  JOINT (here and in the three
+// with the step's own draw z (the unheld branch discards it on a held pixel, so it is a fresh draw there);  JOINT (here and in the four
 // kernels below): `score` is read through the tile blend, everything else is unchanged and the hold sees the blended update
 template <bool HELD, bool JOINT>
 __global__ __launch_bounds__(256) void em_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
@@ -285,6 +286,48 @@ __global__ __launch_bounds__(256) void edm_heun_kernel(float* __restrict__ x, fl
     }
 }
 
+// DPM-Solver++(2M) step (kernels.h: DpmStep): D = x + sigma^2 score; x = c_x x + c_0 D + c_1 hist + c_z z; hist = D.  One evaluation per
+// step: the second-order term is the previous step's D, read and rewritten at the same index by the same thread.  The history is NOT read
+// when c_1 == 0 (step 0 finds whatever the workspace held there, and 0 * NaN would poison the run); the draw is taken only in a
+// stochastic run.  Publishes the time of the next step's evaluation (the advance follows).
+// HELD: x = hold(., known + sigma_{i+1} z) with the step's own draw in a stochastic run (the EM / PC convention), else with the run's
+// draw 0 (the point-mass trajectory, as in EDM Heun); sigma_N = 0, so the result is `known` itself.  The history is not held.
+template <bool HELD, bool JOINT>
+__global__ __launch_bounds__(256) void dpmpp_2m_kernel(float* __restrict__ x, float* __restrict__ x_copy, const float* __restrict__ score,
+                                                       float* __restrict__ hist, const float* __restrict__ z,
+                                                       const DpmStep* __restrict__ table, const SamplerState* __restrict__ state,
+                                                       DpmStep sc_val, unsigned long long off_val, unsigned long long seed,
+                                                       int stochastic, float* __restrict__ t_dev, int t_entries, size_t n4,
+                                                       NoiseMap nm, Hold hold, JointMap jm) {
+    const DpmStep sc = state ? table[state->step] : sc_val;
+    const float s_next = !HELD ? 0.f : (state ? hold.levels[state->step] : hold.lv).next;
+    const unsigned long long off = state ? state->rng_offset : off_val;
+    if (state) seed = state->seed;
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    if (t_dev)
+        for (size_t j = gid; j < (size_t)t_entries; j += stride) t_dev[j] = sc.t_next;
+    const float sig2 = sc.sigma * sc.sigma;
+    const bool second = sc.c_1 != 0.f;
+    for (size_t i = gid; i < n4; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 dv = xv + sig2 * load_score<JOINT>(score, i, jm);
+        f32x4 v = sc.c_x * xv + sc.c_0 * dv;
+        if (second) v = v + sc.c_1 * reinterpret_cast<const f32x4*>(hist)[i];
+        f32x4 n = {0.f, 0.f, 0.f, 0.f};
+        if (stochastic) {
+            n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
+            v = v + sc.c_z * n;
+        }
+        if (HELD) {
+            if (!stochastic) n = draw0(hold, seed, i);
+            v = hold4(v, load_known(hold, i) + s_next * n, load_mask(hold, i));
+        }
+        reinterpret_cast<f32x4*>(x)[i] = v;
+        if (x_copy) reinterpret_cast<f32x4*>(x_copy)[i] = v;
+        reinterpret_cast<f32x4*>(hist)[i] = dv;
+    }
+}
+
 // The hold as an op of its own, for loops that run the network themselves: x = hold(x, known + level z, m) and, when given,
 // x_mean = hold(x_mean, known, m); z null -> the Philox draw (seed, draw_index) the preceding step op consumed.
 __global__ __launch_bounds__(256) void hold_known_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ z,
@@ -304,7 +347,7 @@ __global__ __launch_bounds__(256) void hold_known_kernel(float* __restrict__ x, 
         if (held) hipLaunchKernelGGL((kernel<true>), grid, dim3(256), 0, st, __VA_ARGS__);              \
         else hipLaunchKernelGGL((kernel<false>), grid, dim3(256), 0, st, __VA_ARGS__);                  \
     } while (0)
-// ... and of the four update kernels, which also come with and without the joint tile blend
+// ... and of the five update kernels, which also come with and without the joint tile blend
 #define SBGM_LAUNCH_STEP(kernel, held, joint, grid, st, ...)                                            \
     do {                                                                                                \
         if (joint) {                                                                                    \
@@ -447,6 +490,29 @@ int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* s
     SBGM_LAUNCH_CHECK();
     if (state) {                     // step counter and RNG offset: the EM mechanism, without its StepScalars time publish
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr, 0, 1, n_steps, TimeRows{});
+        SBGM_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int sbgm_launch_dpmpp_2m(float* x, float* x_copy, const float* score, float* hist, const float* z, const DpmStep* table,
+                         SamplerState* state, const DpmStep* sc_val, unsigned long long draw_index, unsigned long long seed,
+                         int stochastic, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st, NoiseMap nm,
+                         const Hold& hold, const JointMap& jm, const TimeRows& tr) {
+    SBGM_CHECK(n % 4 == 0, "dpmpp_2m: element count must be a multiple of 4");
+    SBGM_CHECK(x && score && hist, "dpmpp_2m: x, score and the history slab are required");
+    SBGM_CHECK(state ? table != nullptr : sc_val != nullptr, "dpmpp_2m: need a device table with a state, or explicit scalars");
+    SBGM_CHECK(!(z && !stochastic), "dpmpp_2m: a deterministic step takes no draw");
+    SBGM_CHECK(!(hold.known && state && !hold.levels), "dpmpp_2m: a held run with a device state needs the hold-level table");
+    SBGM_CHECK(!tr.rows || (state && check_time_rows(tr) == 0), "dpmpp_2m: time rows need a device state and a valid layout");
+    if (check_hold(hold, "dpmpp_2m") || check_joint(jm, n, "dpmpp_2m")) return 1;
+    const DpmStep v = sc_val ? *sc_val : DpmStep{};
+    SBGM_LAUNCH_STEP(dpmpp_2m_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x, x_copy, score,
+                     hist, z, table, state, v, draw_index, seed, stochastic, t_dev, t_dev ? t_entries : 0, n / 4, nm, hold, jm);
+    SBGM_LAUNCH_CHECK();
+    if (state) {                     // step counter and RNG offset; a run that keeps its time rows publishes the next step's row here
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(tr.rows ? 1024 : 64), 0, st, state, (const StepScalars*)nullptr, (float*)nullptr,
+                           0, 1, n_steps, tr);
         SBGM_LAUNCH_CHECK();
     }
     return 0;

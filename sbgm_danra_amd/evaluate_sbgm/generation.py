@@ -18,7 +18,8 @@ import torch
 
 from .. import parallel
 from .. import verification as V
-from ..score_sampling import edm_heun_sampler, edm_sampler_kwargs, ode_sampler_kwargs, pc_sampler, rk45_sampler
+from ..score_sampling import (dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs, ode_sampler_kwargs, pc_sampler,
+                              rk45_sampler)
 from ..score_unet import diffusion_coeff_fn, marginal_prob_std_fn
 from ..utils import extract_samples, get_model_string
 from .evaluation import ensemble_products_config
@@ -34,7 +35,7 @@ def constraint_mask(cfg, hw):
     if not sec.get("enabled", False):
         return None
     if cfg["sampler"].get("sampler_type") == "rk45_sampler":
-        raise ValueError("constraint.enabled: rk45_sampler does not take known pixels (use pc_sampler or edm_heun_sampler)")
+        raise ValueError("constraint.enabled: rk45_sampler does not take known pixels (use pc_sampler, edm_heun_sampler or dpmpp_2m_sampler)")
     H, W = int(hw[0]), int(hw[1])
     if sec.get("mask_file"):
         mask = np.load(sec["mask_file"]).astype(np.float32)
@@ -69,7 +70,8 @@ class SampleGenerator:
     def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond, known=None):
         """the sampler output as [B,H,W] still on the device (what _run_sampler returns after .cpu()).  pc_sampler, as in the
         reference, unless cfg.sampler.sampler_type is "edm_heun_sampler": then n_timesteps is its Heun step count N (2N-1
-        network evaluations; 18-64 is the intended range) and the optional `edm:` section sets the sigma ladder; or "rk45_sampler":
+        network evaluations; 18-64 is the intended range) and the optional `edm:` section sets the sigma ladder; "dpmpp_2m_sampler":
+        n_timesteps is its step count N (N evaluations) and the optional `dpm:` section sets the ladder, eta and s_noise; or "rk45_sampler":
         the adaptive ODE solver, which ignores n_timesteps and reads its tolerances from the optional `ode:` section.
         With a `constraint:` section, `known` (the batch's true field, model space) is held on the section's mask."""
         held = {}
@@ -81,6 +83,11 @@ class SampleGenerator:
                                    batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,
                                    img_size=self.cfg["highres"]["data_size"][0], y=y, cond_img=cond_img, lsm_cond=lsm_cond,
                                    topo_cond=topo_cond, **edm_sampler_kwargs(self.cfg), **held)
+        elif self.cfg["sampler"].get("sampler_type") == "dpmpp_2m_sampler":
+            gen = dpmpp_2m_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
+                                   batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,
+                                   img_size=self.cfg["highres"]["data_size"][0], y=y, cond_img=cond_img, lsm_cond=lsm_cond,
+                                   topo_cond=topo_cond, **dpm_sampler_kwargs(self.cfg), **held)
         elif self.cfg["sampler"].get("sampler_type") == "rk45_sampler":
             gen = rk45_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                                batch_size=batch_size, device=self.device, img_size=self.cfg["highres"]["data_size"][0], y=y,

@@ -19,6 +19,8 @@ the level the state is at, in the epilogue of the update kernels; `sde_hold_leve
 
 Beyond the reference: `edm_heun_sampler`, a deterministic few-step Heun solver of the probability-flow ODE on the Karras
 sigma ladder (Karras et al. 2022, Alg. 2) for the same VE-trained network; `edm_heun_schedule` is its one host definition.
+`dpmpp_2m_sampler`, DPM-Solver++(2M) (Lu et al. 2022) on the same ladder: second order at ONE evaluation per step (the previous step's
+denoised estimate is the second-order term), with `eta > 0` its SDE variant; `dpmpp_2m_schedule` is its one host definition.
 `rk45_sampler`, the adaptive probability-flow ODE solver on the device (Dormand-Prince 5(4) with scipy's RK45 step controller):
 conditioned, guided, tileable, in both directions of the flow, with one controller per batch or per sample; `rk45_host_solve` is
 its definition in numpy.
@@ -96,9 +98,11 @@ def _guidance(cfg):
 
 def _counts(kind, num_steps, churn=False):
     """(network evaluations per step, noise draws of a run) of a sampler kind: draw 0 is the initial state; then one draw per
-    evaluation of an SDE step (PC: corrector and predictor), or one per EDM Heun step with churn"""
+    evaluation of an SDE step (PC: corrector and predictor), or one per EDM Heun step with churn / per 2M step with eta > 0 (`churn`)"""
     if kind == N.SAMPLER_EDM_HEUN:
         return 2, 1 + (int(num_steps) if churn else 0)
+    if kind == N.SAMPLER_DPMPP_2M:
+        return 1, 1 + (int(num_steps) if churn else 0)
     if kind == N.SAMPLER_RK45:                                # six evaluations per attempt; the only draw is the start
         return 6, 1
     per_step = 2 if kind == N.SAMPLER_PC else 1
@@ -167,7 +171,7 @@ def _prep_joint(joint_tiles, tile_origins, noise, who):
 
 def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw, y, cond_img, lsm_cond, topo_cond,
                 noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm_args=None, held=(None, None),
-                joint=None):
+                joint=None, dpm_args=None):
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if dev.type != "cuda":
         raise N.NativeError(f"the native samplers run on a ROCm device, got device={device!r}")
@@ -179,7 +183,8 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
     nz = None
     if noise is not None:
         nz = noise if torch.is_tensor(noise) else torch.stack(list(noise))
-        need = _counts(kind, num_steps, edm_args is not None and edm_args[3] > 0)[1]          # edm_args[3]: s_churn
+        stochastic = edm_args[3] > 0 if edm_args is not None else dpm_args is not None and dpm_args[3] > 0   # s_churn / eta
+        need = _counts(kind, num_steps, stochastic)[1]
         if nz.shape[0] < need:
             raise ValueError(f"noise holds {nz.shape[0]} draws, the sampler consumes {need}")
         nz = N.f32c(nz.to(dev))
@@ -193,6 +198,9 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
         if noise is not None:
             raise ValueError("tile_origins keys the in-kernel noise; it cannot be combined with injected noise")
     known, mask = held
+    if dpm_args is not None:                               # one entry point: the constraint and the joint blend are optional arguments
+        N.check(eng.lib.sbgm_sampler_run_dpmpp(eng.h, C.byref(a), *dpm_args, N.ptr(known), N.ptr(mask), *(joint or (0, 0)), N.stream()))
+        return out
     if joint is not None:                                  # one diffusion over the domain: the tiles' scores are blended at every step
         if edm_args is not None:
             N.check(eng.lib.sbgm_sampler_run_edm_joint(eng.h, C.byref(a), *edm_args, *joint, N.ptr(known), N.ptr(mask), N.stream()))
@@ -386,40 +394,48 @@ def edm_heun_schedule(num_steps, sigma_sde=25.0, eps=1e-3, sigma_min=None, sigma
     sigma_min/max     the ladder's ends after clipping
 
     sigma_min / sigma_max default to the trained range [std(eps), std(1)]; other values are clipped to it, with one warning."""
-    N_ = int(num_steps)
-    if N_ < 2:
-        raise ValueError(f"edm_heun_sampler: num_steps={num_steps} must be >= 2")
-    if not rho > 0:
-        raise ValueError(f"edm_heun_sampler: rho={rho} must be > 0")
-    if not s_noise >= 0:
-        raise ValueError(f"edm_heun_sampler: s_noise={s_noise} must be >= 0")
     if not s_churn >= 0:
         raise ValueError(f"edm_heun_sampler: s_churn={s_churn} must be >= 0")
+    N_, sigma, t_of, smin, smax = _karras_ladder("edm_heun_sampler", num_steps, sigma_sde, eps, sigma_min, sigma_max, rho, s_noise)
+    s = sigma[:N_]
+    gamma = np.where((s_tmin <= s) & (s <= s_tmax), min(s_churn / N_, math.sqrt(2.0) - 1.0), 0.0)
+    gamma = np.minimum(gamma, sigma[0] / s - 1.0)
+    sigma_hat = s * (1.0 + gamma)
+    return {"sigma": sigma, "gamma": gamma, "sigma_hat": sigma_hat, "t_hat": t_of(sigma_hat), "t_next": t_of(sigma[1:]),
+            "churn_coef": s_noise * np.sqrt(np.maximum(0.0, sigma_hat ** 2 - s ** 2)), "nfe": 2 * N_ - 1,
+            "draws": _counts(N.SAMPLER_EDM_HEUN, N_, s_churn > 0)[1], "sigma_min": smin, "sigma_max": smax}
+
+
+def _karras_ladder(who, num_steps, sigma_sde, eps, sigma_min, sigma_max, rho, s_noise):
+    """what the few-step schedules share: the checked arguments, the Karras ladder sigma [N+1] (sigma_N = 0) clipped to the trained range
+    with one warning, and t(sigma).  Returns (N, sigma, t_of, sigma_min, sigma_max)."""
+    N_ = int(num_steps)
+    if N_ < 2:
+        raise ValueError(f"{who}: num_steps={num_steps} must be >= 2")
+    if not rho > 0:
+        raise ValueError(f"{who}: rho={rho} must be > 0")
+    if not s_noise >= 0:
+        raise ValueError(f"{who}: s_noise={s_noise} must be >= 0")
     ls = math.log(sigma_sde)
     lo, hi = float(_ve_std(eps, sigma_sde)), float(_ve_std(1.0, sigma_sde))
     smin = lo if sigma_min is None else float(sigma_min)
     smax = hi if sigma_max is None else float(sigma_max)
     clipped_min, clipped_max = min(hi, max(lo, smin)), min(hi, max(lo, smax))
     if (clipped_min, clipped_max) != (smin, smax):
-        logger.warning(f"edm_heun_sampler: sigma range [{smin:g}, {smax:g}] clipped to the trained range [{lo:.6g}, {hi:.6g}] "
+        logger.warning(f"{who}: sigma range [{smin:g}, {smax:g}] clipped to the trained range [{lo:.6g}, {hi:.6g}] "
                        f"(std(eps), std(1) of the VE SDE with sigma={sigma_sde:g})")
     smin, smax = clipped_min, clipped_max
     if not smin < smax:
-        raise ValueError(f"edm_heun_sampler: sigma_min={smin:g} must be below sigma_max={smax:g}")
+        raise ValueError(f"{who}: sigma_min={smin:g} must be below sigma_max={smax:g}")
     a0, a1 = smax ** (1.0 / rho), smin ** (1.0 / rho)
     sigma = np.zeros(N_ + 1)
     sigma[:N_] = (a0 + np.arange(N_, dtype=np.float64) / (N_ - 1) * (a1 - a0)) ** rho
     sigma[0], sigma[N_ - 1] = smax, smin                   # the ends exactly (the power round trip is off by an ulp)
-    s = sigma[:N_]
-    gamma = np.where((s_tmin <= s) & (s <= s_tmax), min(s_churn / N_, math.sqrt(2.0) - 1.0), 0.0)
-    gamma = np.minimum(gamma, sigma[0] / s - 1.0)
-    sigma_hat = s * (1.0 + gamma)
+
     def t_of(v):                                           # clamped in sigma too: sigma >= std(1) is t = 1 exactly
         t = np.clip(np.log1p(2.0 * ls * np.square(v)) / (2.0 * ls), eps, 1.0)
         return np.where(v >= hi, 1.0, np.where(v <= lo, eps, t))
-    return {"sigma": sigma, "gamma": gamma, "sigma_hat": sigma_hat, "t_hat": t_of(sigma_hat), "t_next": t_of(sigma[1:]),
-            "churn_coef": s_noise * np.sqrt(np.maximum(0.0, sigma_hat ** 2 - s ** 2)), "nfe": 2 * N_ - 1,
-            "draws": _counts(N.SAMPLER_EDM_HEUN, N_, s_churn > 0)[1], "sigma_min": smin, "sigma_max": smax}
+    return N_, sigma, t_of, smin, smax
 
 
 def edm_sampler_kwargs(cfg) -> dict:
@@ -483,6 +499,92 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
             N.check(lib.sbgm_edm_heun(x.data_ptr(), d.data_ptr(), s2.data_ptr(), sh, sn, n, st()))
             hold(x, sn)
     return out
+
+
+def dpmpp_2m_schedule(num_steps, sigma_sde=25.0, eps=1e-3, sigma_min=None, sigma_max=None, rho=7.0, eta=0.0, s_noise=1.0):
+    """Step table of `dpmpp_2m_sampler` (DPM-Solver++(2M), Lu et al. 2022, on the VE SDE: alpha = 1, sigma = marginal_prob_std; eta > 0 is
+    its SDE variant in midpoint form), in float64.  The engine builds the same table (stored as fp32) for its native loop.  With
+    D_i = x_i + sigma_i^2 score(x_i, t_i) step i is x_{i+1} = c_x x_i + c_0 D_i + c_1 D_{i-1} + c_z z_i.  Returns a dict of numpy arrays
+    and counts:
+
+    sigma [N+1]       the Karras ladder of `edm_heun_schedule` (same defaults, same clipping with one warning), sigma_N = 0
+    t [N]             t(sigma_i), the evaluation times, clamped to [eps, 1]
+    c_x, c_0, c_1     with h_i = ln(sigma_i / sigma_{i+1}), a_i = -expm1(-(1 + eta) h_i): c_x = (sigma_{i+1} / sigma_i) exp(-eta h_i);
+                      c_0 = a_i, c_1 = 0 at i = 0; c_0 = a_i (1 + 1/(2r)), c_1 = -a_i / (2r), r = h_{i-1} / h_i at i >= 1
+    c_z               s_noise sigma_{i+1} sqrt(-expm1(-2 eta h_i))
+                      the last row is (c_x, c_0, c_1, c_z) = (0, 1, 0, 0): x_N = D_{N-1}
+    nfe, draws        N network evaluations; 1 noise draw (+N when eta > 0: draw 1+i belongs to step i)
+    sigma_min/max     the ladder's ends after clipping"""
+    if not eta >= 0:
+        raise ValueError(f"dpmpp_2m_sampler: eta={eta} must be >= 0")
+    N_, sigma, t_of, smin, smax = _karras_ladder("dpmpp_2m_sampler", num_steps, sigma_sde, eps, sigma_min, sigma_max, rho, s_noise)
+    c_x, c_0, c_1, c_z = np.zeros(N_), np.ones(N_), np.zeros(N_), np.zeros(N_)
+    h = np.log(sigma[:N_ - 1] / sigma[1:N_])
+    a = -np.expm1(-(1.0 + eta) * h)
+    c_x[:-1] = sigma[1:N_] / sigma[:N_ - 1] * np.exp(-eta * h)
+    c_0[:-1] = a
+    r = h[:-1] / h[1:]                                     # r_i = h_{i-1} / h_i of the steps 1 .. N-2
+    c_0[1:-1] = a[1:] * (1.0 + 1.0 / (2.0 * r))
+    c_1[1:-1] = -a[1:] / (2.0 * r)
+    c_z[:-1] = s_noise * sigma[1:N_] * np.sqrt(np.maximum(0.0, -np.expm1(-2.0 * eta * h)))
+    return {"sigma": sigma, "t": t_of(sigma[:N_]), "c_x": c_x, "c_0": c_0, "c_1": c_1, "c_z": c_z, "nfe": N_,
+            "draws": _counts(N.SAMPLER_DPMPP_2M, N_, eta > 0)[1], "sigma_min": smin, "sigma_max": smax}
+
+
+def dpm_sampler_kwargs(cfg) -> dict:
+    """keyword arguments of `dpmpp_2m_sampler` from the optional `dpm:` section of a config (sigma_min, sigma_max, rho, eta, s_noise); a
+    missing section or key keeps the sampler's default.  `sampler.sampler_type: dpmpp_2m_sampler` selects the sampler."""
+    sec = (cfg or {}).get("dpm") or {}
+    return {k: float(sec[k]) for k in ("sigma_min", "sigma_max", "rho", "eta", "s_noise") if sec.get(k) is not None}
+
+
+def dpmpp_2m_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=32, device="cuda", eps=1e-3,
+                     img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, sigma_min=None, sigma_max=None,
+                     rho=7.0, eta=0.0, s_noise=1.0, noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0,
+                     known=None, known_mask=None, joint_tiles=None):
+    """DPM-Solver++(2M) (Lu et al. 2022) on the Karras sigma ladder of `edm_heun_sampler`: a second-order multistep solver that reuses the
+    previous step's denoised estimate, so `num_steps` N costs exactly N network evaluations (EDM Heun: 2N-1).  `eta = 0` is the
+    deterministic solver of the probability-flow ODE; `eta > 0` is the SDE variant ("2M SDE", midpoint form), which adds noise of weight
+    `s_noise` in every step.  `dpmpp_2m_schedule` is the table.  Conditions, guidance (`cfg`: the evaluation uses guidance_scale), `seed`,
+    `use_graph`, `tile_origins` and `joint_tiles` behave as in `pc_sampler`; `noise`: draw 0 = initial state, and with eta > 0 draw 1+i =
+    step i.  `diffusion_coeff` is accepted for signature compatibility and unused.
+    `known` / `known_mask` as in `pc_sampler`: after every step the held pixels are known + sigma_{i+1} z, with z the run's draw 0 when
+    eta = 0 (the trajectory of a point mass, as in `edm_heun_sampler`: deterministic in the seed) and the step's own draw when eta > 0.
+    An eval-mode ScoreNet runs the native loop (`sbgm_sampler_run_dpmpp`); any other callable runs a Python loop over the same update
+    kernel.  Returns x after the last step, [B,1,H,W].  On the analytic Gaussian problem it has the error of EDM Heun at the same N;
+    sample quality on a trained checkpoint has not been measured."""
+    sig = float(score_model.sigma) if isinstance(score_model, ScoreNet) else _sigma_of(marginal_prob_std)
+    sch = dpmpp_2m_schedule(num_steps, sig, eps, sigma_min, sigma_max, rho, eta, s_noise)
+    seed = _fresh_seed() if seed is None else seed
+    known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "dpmpp_2m_sampler")
+    joint = _prep_joint(joint_tiles, tile_origins, noise, "dpmpp_2m_sampler")
+    if isinstance(score_model, ScoreNet) and not score_model.training:
+        dpm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
+                    float(eta), float(s_noise))
+        return _native_run(N.SAMPLER_DPMPP_2M, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
+                           topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask),
+                           joint=joint, dpm_args=dpm_args)
+    lib, st = N.lib(), N.stream
+    sde = eta > 0
+    f32 = lambda v: float(np.float32(v))  # noqa: E731
+    x, z = _host_start(N.SAMPLER_DPMPP_2M, batch_size, num_steps, img_size, device, noise, seed, f32(sch["sigma"][0]), tile_origins, sde,
+                       joint=joint)
+    n = x.numel()
+    hist = torch.empty_like(x)
+    ones = torch.ones(batch_size, device=device)
+    if known is not None:
+        x = _held_start(x, known, known_mask)
+    with torch.no_grad():
+        for i in range(int(num_steps)):
+            draw = 1 + i if sde else 0                     # the draw a held pixel is re-noised with
+            score = N.f32c(_score(score_model, cfg, x, ones * f32(sch["t"][i]), y, cond_img, lsm_cond, topo_cond))
+            N.check(lib.sbgm_dpmpp_2m_step(x.data_ptr(), score.data_ptr(), hist.data_ptr(), N.ptr(z(draw)) if sde else None,
+                                           f32(sch["sigma"][i]), f32(sch["c_x"][i]), f32(sch["c_0"][i]), f32(sch["c_1"][i]),
+                                           f32(sch["c_z"][i]), seed, draw, n, st()))
+            if known is not None:
+                N.check(lib.sbgm_hold_known(x.data_ptr(), None, known.data_ptr(), known_mask.data_ptr(), N.ptr(z(draw)),
+                                            f32(sch["sigma"][i + 1]), seed, draw, n, st()))
+    return x
 
 
 # ---- rk45_sampler: Dormand-Prince 5(4) with the step controller of scipy.integrate.RK45 -------------------------------------------

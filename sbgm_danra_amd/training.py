@@ -21,14 +21,15 @@ import torch.nn as nn
 
 from . import parallel
 from .ema import EMA_COUNT_KEY, EMA_KEY, ModelEMA, pick_network_params
-from .score_sampling import (Euler_Maruyama_sampler, edm_heun_sampler, edm_sampler_kwargs, ode_sampler, ode_sampler_kwargs, pc_sampler,
-                             rk45_sampler)
+from .score_sampling import (Euler_Maruyama_sampler, dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs,
+                             ode_sampler, ode_sampler_kwargs, pc_sampler, rk45_sampler)
 from .utils import (draw_condition_dropout, extract_samples, extract_samples_device, get_model_string,
                     report_precip_extremes)
 
 logger = logging.getLogger(__name__)
 _SAMPLERS = {"pc_sampler": pc_sampler, "Euler_Maruyama_sampler": Euler_Maruyama_sampler, "ode_sampler": ode_sampler,
-             "edm_heun_sampler": edm_heun_sampler, "rk45_sampler": rk45_sampler}
+             "edm_heun_sampler": edm_heun_sampler, "rk45_sampler": rk45_sampler,
+             "dpmpp_2m_sampler": dpmpp_2m_sampler}
 
 
 class TrainingPipeline_general:
@@ -353,6 +354,8 @@ class TrainingPipeline_general:
             kw.update(y=seasons, cond_img=cond, lsm_cond=lsm, topo_cond=topo)
         if sampler is edm_heun_sampler:                      # n_timesteps is the Heun step count N (2N-1 evaluations)
             kw.update(edm_sampler_kwargs(cfg))
+        if sampler is dpmpp_2m_sampler:                      # n_timesteps is the step count N, which is also the number of evaluations
+            kw.update(dpm_sampler_kwargs(cfg))
         if sampler is rk45_sampler:                          # adaptive: the optional `ode:` tolerances decide the steps, not n_timesteps
             kw.pop("num_steps")
             kw.update(ode_sampler_kwargs(cfg))
