@@ -424,6 +424,19 @@ int sbgm_final_lowres_fwd(const float* x_lowres_nhwc, const float* in_affine, co
                           const float* beta, const float* t, float sigma, float* out, float* ws, int64_t ws_floats, int B, int H, int W,
                           int C, void* stream);
 
+/* The same block where the step samplers form the decoder's last skip inside the mix instead of reading the stem's map (C = 64):
+ *   v = act(raw * scale + shift + skip),   skip = conv1(x || cond) + tb0 = sc + tb0 + conv1_x(x)
+ * with conv1 the encoder's 8x8 / stride-2 / pad-3 convolution, conv1_x its share over input channel 0 and sc its share over the other
+ * channels (constant during a run).  pack: w1 OIHW [64][Cin][8][8] -> w1x, sbgm_skip_mix_packed_numel() floats, the MFMA A operand
+ * [16 k steps][64 co][4]: k step s, quarter kq = tap 4 s + kq = 8 v + u of channel 0.
+ * fwd: raw = the low-resolution NHWC map [B,H/2,W/2,64] with in_affine / in_act as above; x_planar [B,1,H,W]; sc_nhwc [B,H/2,W/2,64] or
+ * NULL (no condition channels); tb0 [B,64]; out, t, sigma and ws as in sbgm_final_lowres_fwd. */
+int64_t sbgm_skip_mix_packed_numel(void);
+int sbgm_skip_mix_pack(const float* w1_oihw, float* w1x, int Cin, void* stream);
+int sbgm_final_lowres_skip_fwd(const float* raw_lowres_nhwc, const float* in_affine, int in_act, const float* wz_packed, const float* beta,
+                               const float* x_planar, const float* sc_nhwc, const float* tb0, const float* w1x, const float* t, float sigma,
+                               float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream);
+
 /* A resize DecoderBlock's conv_up(up(x)) on a small map with the channels mixed at LOW resolution (conv_uplow.hip, the route the EM / PC /
  * EDM Heun samplers take for blocks whose output is narrower than 32 pixels): `up` acts per channel and a tap's weight per pixel, so
  *   Z_tap[co] = sum_ci W[co][ci][k][l] x[ci] (low-res, tap = 3k + l),   out[co][o] = b[co] + sum_{tap, o+tap-1 inside the 2x map} up(Z_tap)[co][o + tap - 1].

@@ -125,6 +125,9 @@ SIGNATURES = {
     "sbgm_final_lowres_ws_numel": (_i64, [_i, _i, _i]),
     "sbgm_final_lowres_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sbgm_final_lowres_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sbgm_skip_mix_packed_numel": (_i64, []),
+    "sbgm_skip_mix_pack": (_i, [_vp, _vp, _i, _vp]),
+    "sbgm_final_lowres_skip_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sbgm_up_lowres_weight_numel": (_i64, [_i]),
     "sbgm_up_lowres_ws_numel": (_i64, [_i, _i, _i, _i, _i]),
     "sbgm_up_lowres_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
@@ -229,7 +232,7 @@ SIGNATURES = {
     "sbgm_ensemble_products": (_i, [_vp, _vp, _i, _i, _i64, C.POINTER(_d), _i, C.POINTER(_f), _i] + [_vp] * 9),
 }
 
-ABI_VERSION = 5          # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 6         # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

@@ -192,11 +192,51 @@ __device__ __forceinline__ void mix_product(const f32x4 (&a)[NKS][2], const f32x
         if (kq < 3) row[4 + kq] = acc[1];
     }
 }
-template <int NKS>
+// SKIPX (NKS = 4, the sampler route): the skip is not loaded but formed in place as the encoder's conv1 (8x8, stride 2, pad 3) at the
+// pixel.  conv1 is linear: its share over the condition channels is the run's constant `skip` (Sc, null without such channels), its
+// time bias the row tb0 [B][64], and its share over x, K = 64 taps, is 16 products per 16-channel fragment whose accumulator IS
+// sk[ks]: the C/D layout of v_mfma_f32_16x16x4_f32 (column = lane & 15 = the pixel, rows 4 (lane >> 4) + reg = the channel quad) is
+// the layout mix_operand reads.  k step s and lane quarter kq give tap 4 s + kq = 8 v + u.  The B values, x[b][2 ly + v - 3][2 lx + u - 3]
+// of the planar input, are 4-byte global loads under a row and a column mask (a linear bounds check alone would wrap columns into the
+// neighbouring row).  The A values are read per fragment from the workgroup's LDS copy of w1x [k step][64 co][4] (wl = the lane's own
+// float of a 64-float row: conflict-free 4-byte reads at constant offsets).  Measured at batch 32 x 128^2 (the mix without the skip
+// 27.4 us): every wave fetching its 64 A values from global memory 66 us (16 KB per wave, as many bytes again through the L2 as the
+// kernel streams from HBM); the LDS copy with the values held in registers across the wave's fragments 51 us (188 VGPRs, 2 waves per
+// SIMD); read per fragment 44 us (124 VGPRs, 3 waves per SIMD as without the skip).  Fewer, longer-lived workgroups striding over
+// the fragments measured slower (70 us and more): the strip fragments then form a tail.
+__device__ __forceinline__ void skip_from_x(f32x4 (&sk)[4], const float* __restrict__ wl, const float* __restrict__ xin,
+                                            const float* __restrict__ tb0, const f32x4* __restrict__ sc4, bool ok, int pix, int b, int ly,
+                                            int lx, int H, int W, int kq) {
+    int off = 0;                                       // an offset the compiler cannot see through: the A values are read here, per
+    asm volatile("" : "+v"(off));                      // fragment, instead of living in 64 registers across the wave's fragments
+    wl += off;
+    const float* const xb = xin + (size_t)b * H * W;
+    const int ix0 = 2 * lx + kq - 3, ix1 = ix0 + 4;
+    const bool cm0 = ok && (unsigned)ix0 < (unsigned)W, cm1 = ok && (unsigned)ix1 < (unsigned)W;
+    float tap[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int iy = 2 * ly + (s >> 1) - 3;
+        const bool in = (unsigned)iy < (unsigned)H && ((s & 1) ? cm1 : cm0);
+        tap[s] = in ? xb[iy * W + ((s & 1) ? ix1 : ix0)] : 0.f;
+    }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        sk[ks] = reinterpret_cast<const f32x4*>(tb0)[b * 16 + ks * 4 + kq];
+        if (sc4 != nullptr) sk[ks] += sc4[(size_t)pix * 16 + ks * 4 + kq];
+    }
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) sk[ks] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[(s * 64 + ks * 16) * 4], tap[s], sk[ks], 0, 0, 0);
+}
+template <int NKS, bool SKIPX>
 __global__ __launch_bounds__(256) void final_mix_kernel(const float* __restrict__ x, const float* __restrict__ aff,
                                                         const float* __restrict__ skip, int act, const float* __restrict__ wzp,
                                                         float* __restrict__ z, float* __restrict__ edge, int h, int w, int M,
-                                                        int n_main, int n_edge_frags) {
+                                                        int n_main, int n_edge_frags, const float* __restrict__ xin,
+                                                        const float* __restrict__ tb0, const float* __restrict__ w1x) {
+    static_assert(!SKIPX || NKS == 4, "conv1 has 64 output channels");
     constexpr int QPP = NKS * 4;                       // quads per pixel
     constexpr int CLS_QUADS = NKS * 32 * 4;            // quads per class image
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -206,6 +246,13 @@ __global__ __launch_bounds__(256) void final_mix_kernel(const float* __restrict_
     const f32x4* const s4 = reinterpret_cast<const f32x4*>(skip);
     const int hw = h * w;
     f32x4 a[NKS][2];
+    __shared__ float w1s[SKIPX ? SKIP_MIX_PACKED_FLOATS : 1];
+    const float* const wl = w1s + (SKIPX ? r16 * 4 + kq : 0);
+    if constexpr (SKIPX) {                             // before any wave leaves: every thread takes part in the copy and the barrier
+        for (int i = threadIdx.x; i < SKIP_MIX_PACKED_FLOATS / 4; i += 256)
+            reinterpret_cast<f32x4*>(w1s)[i] = reinterpret_cast<const f32x4*>(w1x)[i];
+        __syncthreads();
+    }
     if ((int)blockIdx.x >= n_main) {                   // ---- one strip fragment of a border class ----
         const int ef = ((int)blockIdx.x - n_main) * 4 + wave;
         if (ef >= n_edge_frags) return;
@@ -231,9 +278,10 @@ __global__ __launch_bounds__(256) void final_mix_kernel(const float* __restrict_
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             v[ks] = x4[(size_t)pix * QPP + ks * 4 + kq];
-            sk[ks] = skip != nullptr ? s4[(size_t)pix * QPP + ks * 4 + kq] : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (!SKIPX) sk[ks] = skip != nullptr ? s4[(size_t)pix * QPP + ks * 4 + kq] : f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        mix_operand<NKS>(v, sk, ok, b, kq, aff, skip != nullptr, act);
+        if constexpr (SKIPX) skip_from_x(sk, wl, xin, tb0, skip != nullptr ? s4 : nullptr, ok, pix, b, ly, lx, 2 * h, 2 * w, kq);
+        mix_operand<NKS>(v, sk, ok, b, kq, aff, SKIPX || skip != nullptr, act);
         const size_t ep = (size_t)b * lr_edge_pixels(h, w) + (ok ? lr_edge_index(c, ly, lx, h, w) : 0);
         mix_product<NKS>(a, v, reinterpret_cast<f32x4*>(edge) + ep * 7, ok, kq);
         return;
@@ -253,15 +301,20 @@ __global__ __launch_bounds__(256) void final_mix_kernel(const float* __restrict_
             v[f][ks] = sk[f][ks] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (pix < M) {
                 v[f][ks] = x4[(size_t)pix * QPP + ks * 4 + kq];
-                if (skip != nullptr) sk[f][ks] = s4[(size_t)pix * QPP + ks * 4 + kq];
+                if (!SKIPX && skip != nullptr) sk[f][ks] = s4[(size_t)pix * QPP + ks * 4 + kq];
             }
+        }
+        if constexpr (SKIPX) {
+            const bool ok = pix < M;
+            const int p = ok ? pix : 0, b = p / hw, r = p - b * hw, ly = r / w;
+            skip_from_x(sk[f], wl, xin, tb0, skip != nullptr ? s4 : nullptr, ok, p, b, ly, r - ly * w, 2 * h, 2 * w, kq);
         }
     }
 #pragma unroll
     for (int f = 0; f < MIX_FPW; ++f) {
         const int pix = (frag0 + f) * 16 + r16;
         const bool ok = pix < M;
-        mix_operand<NKS>(v[f], sk[f], ok, ok ? pix / hw : 0, kq, aff, skip != nullptr, act);
+        mix_operand<NKS>(v[f], sk[f], ok, ok ? pix / hw : 0, kq, aff, SKIPX || skip != nullptr, act);
         mix_product<NKS>(a, v[f], reinterpret_cast<f32x4*>(z) + (size_t)(ok ? pix : 0) * 7, ok, kq);
     }
 }
@@ -367,6 +420,14 @@ __global__ __launch_bounds__(256) void final_gather_kernel(const float* __restri
     }
 }
 
+// conv1's x-channel weights w1[co][0][v][u] (OIHW [64][cin][8][8]) as the A operand of skip_from_x: img[k step s][co][kq] = tap 4 s + kq
+__global__ void skip_mix_pack_kernel(const float* __restrict__ w1, float* __restrict__ img, int cin) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= SKIP_MIX_PACKED_FLOATS) return;
+    const int kq = i & 3, co = (i >> 2) & 63, s = i >> 8;
+    img[i] = w1[(size_t)co * cin * 64 + 4 * s + kq];
+}
+
 }  // namespace
 
 int sbgm_launch_final_compose(const float* w1_oihw, const float* b1, const float* w2_oihw, float* wc_oihw, float* bc, int C,
@@ -414,8 +475,31 @@ static int final_lowres_shape_ok(const char* who, int B, int h, int w) {
     return 0;
 }
 
+int sbgm_launch_skip_mix_pack(const float* w1_oihw, float* w1x, int cin, hipStream_t st) {
+    SBGM_CHECK(w1_oihw && w1x && cin >= 1, "skip_mix_pack: bad arguments");
+    hipLaunchKernelGGL(skip_mix_pack_kernel, dim3(SKIP_MIX_PACKED_FLOATS / 256), dim3(256), 0, st, w1_oihw, w1x, cin);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
+
+static int final_mix_launch(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed, float* zbuf,
+                            int B, int h, int w, int C, const float* xin, const float* tb0, const float* w1x, hipStream_t st);
+
 int sbgm_launch_final_mix(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed, float* zbuf,
                           int B, int h, int w, int C, hipStream_t st) {
+    return final_mix_launch(x, in_affine, in_skip, in_act, wz_packed, zbuf, B, h, w, C, nullptr, nullptr, nullptr, st);
+}
+
+int sbgm_launch_final_mix_skipx(const float* x, const float* in_affine, int in_act, const float* wz_packed, const float* xin,
+                                const float* sc, const float* tb0, const float* w1x, float* zbuf, int B, int h, int w, int C,
+                                hipStream_t st) {
+    SBGM_CHECK(xin && tb0 && w1x, "final_mix: the skip needs the planar input, the time row and conv1's x weights");
+    SBGM_CHECK(C == 64, "final_mix: conv1's skip has 64 channels, the block %d", C);
+    return final_mix_launch(x, in_affine, sc, in_act, wz_packed, zbuf, B, h, w, C, xin, tb0, w1x, st);
+}
+
+static int final_mix_launch(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed, float* zbuf,
+                            int B, int h, int w, int C, const float* xin, const float* tb0, const float* w1x, hipStream_t st) {
     SBGM_CHECK(x && wz_packed && zbuf, "final_mix: null tensor");
     SBGM_CHECK(C >= 16 && C % 16 == 0 && C <= FINAL_LOWRES_MAX_C, "final_mix: C=%d must be a multiple of 16, at most %d", C, FINAL_LOWRES_MAX_C);
     if (final_lowres_shape_ok("final_mix", B, h, w)) return 1;
@@ -426,10 +510,13 @@ int sbgm_launch_final_mix(const float* x, const float* in_affine, const float* i
     const dim3 grid(n_main + (n_edge_frags + 3) / 4);
 #define SBGM_MIX(NKS)                                                                                                              \
     case NKS:                                                                                                                      \
-        hipLaunchKernelGGL(final_mix_kernel<NKS>, grid, dim3(256), 0, st, x, in_affine, in_skip, in_act, wz_packed, zbuf, edge, h, w, M, \
-                           n_main, n_edge_frags);                                                                                  \
+        hipLaunchKernelGGL((final_mix_kernel<NKS, false>), grid, dim3(256), 0, st, x, in_affine, in_skip, in_act, wz_packed, zbuf, edge, h, \
+                           w, M, n_main, n_edge_frags, xin, tb0, w1x);                                                             \
         break;
-    switch (C / 16) {
+    if (xin != nullptr) {
+        hipLaunchKernelGGL((final_mix_kernel<4, true>), grid, dim3(256), 0, st, x, in_affine, in_skip, in_act, wz_packed, zbuf, edge, h, w, M,
+                           n_main, n_edge_frags, xin, tb0, w1x);
+    } else switch (C / 16) {
         SBGM_MIX(1) SBGM_MIX(2) SBGM_MIX(3) SBGM_MIX(4) SBGM_MIX(5) SBGM_MIX(6) SBGM_MIX(7) SBGM_MIX(8)
     }
 #undef SBGM_MIX

@@ -85,9 +85,13 @@ struct Derived {
 
 // Composed stem of the samplers (conv_stem22.hip): conv2(conv1(.) + tb0) as one 22x22 / stride-4 kernel, built before an EM / PC / EDM
 // Heun run, never by a training upload or a plain forward.
+// With it, and rebuilt with it (conv1.weight feeds both): w1x, conv1's x-channel weights as the final mix reads them where the run forms
+// the decoder's last skip there instead of launching conv1 (conv_final.hip, skip_from_x; sbgm_model::skip_mix_route).
 struct Stem : Derived {
     float *wc = nullptr, *sb = nullptr;                    // composed weights and time-bias sums of the 25 border classes
+    float* w1x = nullptr;
     static bool env_on() { static const bool v = getenv("SBGM_NO_STEM_COMPOSE") == nullptr; return v; }
+    static bool env_skip_mix() { static const bool v = getenv("SBGM_NO_SKIP_MIX") == nullptr; return v; }
     void build(Param* w1, Param* w2) {                     // encoder.conv1 / conv2 weights
         on = env_on();
         w1->feeds = w2->feeds = this; w1->keep_oihw = w2->keep_oihw = true;
@@ -96,7 +100,9 @@ struct Stem : Derived {
         if (!on || !dirty) return 0;
         SBGM_CHECK(w1.oihw && w2.oihw, "sampler: encoder.conv1 / conv2 weights were never uploaded");
         if (alloc(wc, sbgm_stem22_packed_floats(cin_total)) || alloc(sb, sbgm_stem22_bias_floats())) return 1;
+        if (alloc(w1x, SKIP_MIX_PACKED_FLOATS)) return 1;
         if (sbgm_launch_pack_stem22(w1.oihw, w2.oihw, wc, sb, cin_total, st)) return 1;
+        if (sbgm_launch_skip_mix_pack(w1.oihw, w1x, cin_total, st)) return 1;
         dirty = false;
         return 0;
     }
@@ -195,11 +201,15 @@ inline bool up_lowres_shape(int ci, int h, int w) {
 // small-map decoder blocks (up_lowres)
 // tbrun (EM and PC runs without labels): the run's time biases [9][run_B][ch_i], kept current by the step's advance, so
 // the evaluation launches neither the time embedding nor the time projections
+// skip_mix (the step samplers only): the evaluation launches neither pack_input nor conv1; the final mix forms the decoder's last skip
+// from x, the time row and the run's condition share skip_Sc of conv1 (null without condition channels)
 struct Routes {
     bool stem = false, fin = false, fin_lowres = false, up_lowres = false;
     const float* stem_T = nullptr;
     float* tbrun = nullptr;
     int run_B = 0;
+    bool skip_mix = false;
+    const float* skip_Sc = nullptr;
 };
 enum Caller { CALL_PLAIN, CALL_SDE_RUN, CALL_MEASURE };
 
@@ -269,10 +279,22 @@ struct sbgm_model {
     //   (bound 9), where the projection path gives 464 / 464; a stem that rounds differently flips such decisions too.
     //   an EM / PC run without a label vector additionally: its own time biases, see sampler().
     Routes routes;
-    void set_routes(Caller c, const float* stem_T = nullptr, float* tbrun = nullptr, int run_B = 0) {
+    void set_routes(Caller c, const float* stem_T = nullptr, float* tbrun = nullptr, int run_B = 0, bool skip_mix = false,
+                    const float* skip_Sc = nullptr) {
         const bool run = c == CALL_SDE_RUN;
         routes = Routes{run && stem.on, c != CALL_PLAIN && fin.on, c != CALL_PLAIN && fin.on && fin.lowres, c != CALL_PLAIN,
-                        run ? stem_T : nullptr, run ? tbrun : nullptr, run ? run_B : 0};
+                        run ? stem_T : nullptr, run ? tbrun : nullptr, run ? run_B : 0, run && skip_mix, run && skip_mix ? skip_Sc : nullptr};
+    }
+    // Whether a step sampler's evaluations at width W form the decoder's last skip inside the final mix (Routes::skip_mix): the composed
+    // stem (so nothing else reads conv1's output in the encoder), the low-resolution final block, and a last decoder block that leaves
+    // its normalisation pending with fm[0] as the skip (no attention, fused conv_up of the final layer).  SBGM_NO_SKIP_MIX=1: never.
+    bool skip_mix_route(int W) const {
+        return Stem::env_skip_mix() && stem.on && fin.on && fin.lowres && dec[3].cout == 64 && !dec[3].has_attn &&
+               can_fuse(fin_up, dec[3].cout, W);
+    }
+    // the run's condition share of conv1, NHWC [B][H/2][W/2][64], after the composed stem's term at the top of the workspace
+    size_t skip_sc_bytes(int B, int H, int W) const {
+        return skip_mix_route(W) && cin_total > 1 ? align_up((size_t)B * (H / 2) * (W / 2) * 64 * 4, 256) : 0;
     }
     // The run-owned buffers of that route and the layout of a time row: the nine time-bias vectors in the order of forward_impl's
     // tb[0..8] (five encoder maps, four decoder blocks); off4 in 16-byte quads, off4[9] = TB / 4
@@ -428,7 +450,7 @@ struct sbgm_model {
     int build(const sbgm_model_config& c);
     int ensure_ws(size_t bytes);
     int dummy_forward(int B, int H, int W, bool tune, hipStream_t st);
-    int prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, int slabs);
+    int prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, int slabs, size_t run_extra = 0);
     float* wsalloc(size_t floats) {     // bump allocator over the activation workspace; nullptr (+ error text) when full
         const size_t bytes = align_up(floats * 4, 256);
         if (ws_used + bytes > ws_bytes) {
@@ -481,7 +503,8 @@ struct sbgm_model {
         if (!rc && !tuning) {                                // the evaluation's high-water mark sizes every later call of this shape
             size_t& pk = ws_peak[std::array<int, 4>{B, H, W, bn_train != 0}];
             pk = std::max(pk, ws_used);
-            ws_target = std::max(ws_target, pk + ((size_t)8 << 20) + sampler_keep(B, H, W, 3));
+            // (with a step sampler's condition share of conv1: a plain call between two runs must not trim what the next run asks back)
+            ws_target = std::max(ws_target, pk + ((size_t)8 << 20) + sampler_keep(B, H, W, 3) + skip_sc_bytes(B, H, W));
         }
         return rc;
     }
@@ -788,7 +811,11 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     push(x, 1); push(lsm, cfg.n_lsm_channels); push(topo, cfg.n_topo_channels); push(cond, cfg.n_cond_channels);
     float* x0 = wsalloc((size_t)B * H * W * cs_in);
     if (!x0) return 1;
-    if (sbgm_launch_pack_input(src, x0, B, H, W, cs_in, st)) return 1;
+    // A step sampler's evaluation whose final mix forms the decoder's last skip itself (Routes::skip_mix) launches neither this packing
+    // nor conv1 below: the composed stem reads x, and nothing else reads fm[0].  x0 and fm[0] are carved all the same, so every later
+    // buffer keeps its address and the measured high-water mark covers the route.
+    const bool skip_mix = routes.skip_mix && routes.stem && routes.fin_lowres && !tuning && !prof && fmaps_out == nullptr;
+    if (!skip_mix && sbgm_launch_pack_input(src, x0, B, H, W, cs_in, st)) return 1;
 
     // An EM / PC run without labels keeps its time biases itself (routes.tbrun); the workspace is carved the same either
     // way, so every later buffer keeps its address and the measured high-water mark serves both
@@ -836,7 +863,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     fh[0] = H / 2; fw[0] = W / 2;
     fm[0] = wsalloc((size_t)B * fh[0] * fw[0] * 64);
     if (!fm[0]) return 1;
-    {
+    if (!skip_mix) {
         ConvParams p{};
         p.x = x0; p.out = fm[0]; p.tbias = tb[0]; p.B = B; p.H = H; p.W = W; p.Cs = cs_in; p.Cout = 64;
         p.c_real = cin_total == 2 ? 2 : 0;
@@ -847,7 +874,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
     if (!cur) return 1;
     if (routes.stem) {
         // sampler runs: conv2(fm[0]) + bn1 + ReLU straight from x, the run's condition term and tb[0] (conv_stem22.hip); conv1 above
-        // still writes fm[0], the decoder's last skip
+        // still writes fm[0], the decoder's last skip, unless the final mix forms it (skip_mix)
         float* o = cur;
         if (bn_train) {
             o = wsalloc((size_t)B * ch * cw_ * 64);
@@ -1032,6 +1059,13 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
             if (!zb) return 1;
             const bool live = pend.live;
             pend.live = false;
+            if (skip_mix) {
+                // the pending skip is fm[0], which nothing wrote: conv1(x || cond) + tb[0] inside the mix, from x, the run's Sc and tb[0]
+                SBGM_CHECK(live && pend.skip == fm[0] && ci == 64, "forward: the final mix cannot form a skip that is not the stem's map");
+                if (sbgm_launch_final_mix_skipx(pend.raw, pend.affine, pend.act, fin.wz, x, routes.skip_Sc, tb[0], stem.w1x, zb, B, ch, cw_, ci,
+                                                st)) return 1;
+                return sbgm_launch_final_gather(zb, fin.beta, t, cfg.sigma, out, B, ch, cw_, st);
+            }
             if (sbgm_launch_final_mix(live ? pend.raw : cur, live ? pend.affine : nullptr, live ? pend.skip : nullptr,
                                       live ? pend.act : SBGM_ACT_NONE, fin.wz, zb, B, ch, cw_, ci, st)) return 1;
             return sbgm_launch_final_gather(zb, fin.beta, t, cfg.sigma, out, B, ch, cw_, st);
@@ -1217,7 +1251,7 @@ struct SamplerConds {
 // capture, builds the conditions, the routes and the tiled noise map and takes the buffers out of the forward's reach.  The destructor
 // gives the workspace back and ends the routes on every exit path.  Layout from `top` (BE = B, or 2B with guidance): `lead` slabs of
 // BE*per floats (slab 0: the network input, rows B.. mirror rows 0..B-1), the time vector [BE], double partials [BE], the kind's
-// further slabs, the composed stem's condition term.
+// further slabs, the composed stem's condition term, conv1's condition share for the skip the final mix forms (skip_Sc).
 struct SamplerRun {
     sbgm_model* m;
     const sbgm_sampler_args& a;
@@ -1234,15 +1268,17 @@ struct SamplerRun {
     NoiseMap nm{};
     float* tbrun = nullptr;          // set by an EM / PC driver before begin(): the run keeps its time biases
     ~SamplerRun() { if (saved_ws) m->ws_bytes = saved_ws; m->set_routes(CALL_PLAIN); }
-    size_t keep() const { return m->sampler_keep(BE, H, W, slabs); }
+    size_t sc_bytes() const { return a.kind != SBGM_SAMPLER_RK45 ? m->skip_sc_bytes(BE, H, W) : 0; }
+    size_t keep() const { return m->sampler_keep(BE, H, W, slabs) + sc_bytes(); }
     float* slab_at(int i) const { return reinterpret_cast<float*>(top + (i < lead ? i * slab : m->slabs_keep(BE, H, W, lead) + (i - lead) * slab)); }
     float* t_vec() const { return reinterpret_cast<float*>(top + lead * slab); }
     double* partials() const { return reinterpret_cast<double*>(top + lead * slab + align_up((size_t)BE * 4, 256)); }
     float* stem_T() const { return reinterpret_cast<float*>(top + m->slabs_keep(BE, H, W, slabs)); }
+    float* skip_Sc() const { return reinterpret_cast<float*>(top + m->sampler_keep(BE, H, W, slabs)); }
     int open() {
         SBGM_CHECK(B >= 1 && H >= 32 && W >= 32, "%s: needs B >= 1 and H, W >= 32, got B=%d H=%d W=%d", who, B, H, W);
         SBGM_CHECK(!(guided && a.bn_train), "%s: guidance with train-mode BatchNorm would couple the two halves of the batch", who);
-        return m->prepare_ws(BE, H, W, a.bn_train, st, slabs);
+        return m->prepare_ws(BE, H, W, a.bn_train, st, slabs, sc_bytes());
     }
     int begin(bool draws_noise = true) {
         // Graph CAPTURE is illegal on the legacy default stream, so the step is captured on a private stream (capture records, it runs
@@ -1266,7 +1302,28 @@ struct SamplerRun {
                 if (sbgm_launch_conv_stem22(srcs[i], chs[i], c0, m->cin_total, m->stem.wc, nullptr, nullptr, term, nullptr, nullptr, 0, stem_T(), BE, H, W, st)) return 1;
                 term = stem_T();
             }
-            m->set_routes(CALL_SDE_RUN, term, tbrun, BE);
+            // The same for the decoder's last skip where the final mix forms it (skip_mix_route): conv1 is linear, so its share over those
+            // channels, Sc, is one pack_input with the x slot left zero and one conv1 launch without time bias into the run's buffer,
+            // staged through the forward's part of the workspace, which nothing uses between evaluations.
+            const bool skip_mix = m->skip_mix_route(W);
+            const float* sc = nullptr;
+            if (skip_mix && m->cin_total > 1) {
+                PackSrc src{};
+                src.c0 = 1;
+                for (int i = 0; i < 3; ++i)
+                    if (chs[i]) { src.ptr[src.n] = srcs[i]; src.ch[src.n] = chs[i]; ++src.n; }
+                m->ws_used = 0;
+                m->partial = m->wsalloc(sbgm_model::PARTIAL_FLOATS);
+                float* x0 = m->partial ? m->wsalloc((size_t)BE * H * W * m->cs_in) : nullptr;
+                if (!x0) return 1;
+                if (sbgm_launch_pack_input(src, x0, BE, H, W, m->cs_in, st)) return 1;
+                ConvParams p{};
+                p.x = x0; p.out = skip_Sc(); p.B = BE; p.H = H; p.W = W; p.Cs = m->cs_in; p.Cout = 64;
+                p.c_real = m->cin_total == 2 ? 2 : 0;
+                if (m->conv(ConvGeom{8, 8, 2, 3}, p, *m->conv1.w, st)) return 1;
+                sc = skip_Sc();
+            }
+            m->set_routes(CALL_SDE_RUN, term, tbrun, BE, skip_mix, sc);
         }
         if (a.tile_origins && draws_noise) {
             SBGM_CHECK(W % 4 == 0 && a.domain_w >= W, "%s: tiled noise needs W %% 4 == 0 and domain_w >= W (W=%d, domain_w=%d)", who, W, a.domain_w);
@@ -1609,7 +1666,7 @@ const char* sbgm_get_error();
 extern "C" {
 
 const char* sbgm_last_error(void) { return sbgm_get_error(); }
-int sbgm_abi_version(void) { return 5; }
+int sbgm_abi_version(void) { return 6; }
 int sbgm_model_config_size(void) { return (int)sizeof(sbgm_model_config); }
 
 int sbgm_model_create(const sbgm_model_config* cfg, sbgm_model** out) {
@@ -1798,13 +1855,13 @@ int sbgm_model::dummy_forward(int B, int H, int W, bool tune, hipStream_t st) {
 // BEFORE the caller's work, so the slab has its final size (and address) from the first real call on: a sampler's captured step graph
 // is then captured once, not again after a later call has trimmed the slab.  Train-mode BatchNorm shapes are not pre-measured (an
 // evaluation would move the running statistics): they run on the generous bound first and are trimmed by a later call.
-int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, int slabs) {
+int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, int slabs, size_t run_extra) {
     if (!bn_train && ws_peak.find(std::array<int, 4>{B, H, W, 0}) == ws_peak.end() && sbgm_model_check_complete(this) == 0) {
-        if (ensure_ws(ws_need(B, H, W, 0, slabs) + ((size_t)B * H * W * 16 + 1024) * 4 + 4096)) return 1;
+        if (ensure_ws(ws_need(B, H, W, 0, slabs) + run_extra + ((size_t)B * H * W * 16 + 1024) * 4 + 4096)) return 1;
         if (refresh_derived(st)) return 1;
         if (dummy_forward(B, H, W, false, st)) return 1;
     }
-    return ensure_ws(ws_need(B, H, W, bn_train, slabs));
+    return ensure_ws(ws_need(B, H, W, bn_train, slabs) + run_extra);     // run_extra: what a step sampler keeps beyond sampler_keep
 }
 
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {
@@ -1946,6 +2003,25 @@ int sbgm_final_lowres_fwd(const float* x_lowres_nhwc, const float* in_affine, co
     SBGM_CHECK(B >= 1 && H >= 4 && H % 2 == 0 && W >= 4 && W % 2 == 0, "final_lowres_fwd: needs even H, W >= 4 (B=%d H=%d W=%d)", B, H, W);
     SBGM_CHECK(ws_floats >= sbgm_final_lowres_ws_numel(B, H, W), "final_lowres_fwd: workspace of %lld floats is too small", (long long)ws_floats);
     if (sbgm_launch_final_mix(x_lowres_nhwc, in_affine, in_skip, in_act, wz_packed, ws, B, H / 2, W / 2, C, st)) return 1;
+    return sbgm_launch_final_gather(ws, beta, t, sigma, out, B, H / 2, W / 2, st);
+}
+
+// ---- the same with the decoder's last skip formed inside the mix (the step samplers' skip_mix route) --------------------------------
+int64_t sbgm_skip_mix_packed_numel(void) { return SKIP_MIX_PACKED_FLOATS; }
+
+int sbgm_skip_mix_pack(const float* w1_oihw, float* w1x, int Cin, void* stream) {
+    return sbgm_launch_skip_mix_pack(w1_oihw, w1x, Cin, (hipStream_t)stream);
+}
+
+int sbgm_final_lowres_skip_fwd(const float* raw_lowres_nhwc, const float* in_affine, int in_act, const float* wz_packed, const float* beta,
+                               const float* x_planar, const float* sc_nhwc, const float* tb0, const float* w1x, const float* t, float sigma,
+                               float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(raw_lowres_nhwc && wz_packed && beta && out && ws, "final_lowres_skip_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 4 && H % 2 == 0 && W >= 4 && W % 2 == 0, "final_lowres_skip_fwd: needs even H, W >= 4 (B=%d H=%d W=%d)", B, H, W);
+    SBGM_CHECK(ws_floats >= sbgm_final_lowres_ws_numel(B, H, W), "final_lowres_skip_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    if (sbgm_launch_final_mix_skipx(raw_lowres_nhwc, in_affine, in_act, wz_packed, x_planar, sc_nhwc, tb0, w1x, ws, B, H / 2, W / 2, C, st))
+        return 1;
     return sbgm_launch_final_gather(ws, beta, t, sigma, out, B, H / 2, W / 2, st);
 }
 

@@ -89,6 +89,14 @@ int sbgm_launch_final_lowres_pack(const float* w1_oihw, const float* b1, const f
 // x: low-res NHWC [B][h][w][C] (+ affine [B][C/4][2][4], skip, activation on load) -> zbuf (sbgm_final_lowres_ws_floats)
 int sbgm_launch_final_mix(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed, float* zbuf,
                           int B, int h, int w, int C, hipStream_t st);
+// The mix with the skip formed in place (C = 64, the sampler route): skip = conv1(x || cond) + tb0 of the encoder's 8x8 / stride-2 stem as
+// sc + tb0 + conv1_x(xin): xin planar [B][2h][2w], sc NHWC [B][h][w][64] = conv1 over the condition channels (null: none), tb0 [B][64],
+// w1x = conv1's x-channel weights packed by sbgm_launch_skip_mix_pack ([16 k steps][64 co][4], tap 4 s + kq = 8 v + u)
+constexpr int SKIP_MIX_PACKED_FLOATS = 64 * 64;
+int sbgm_launch_skip_mix_pack(const float* w1_oihw, float* w1x, int cin, hipStream_t st);
+int sbgm_launch_final_mix_skipx(const float* x, const float* in_affine, int in_act, const float* wz_packed, const float* xin,
+                                const float* sc, const float* tb0, const float* w1x, float* zbuf, int B, int h, int w, int C,
+                                hipStream_t st);
 // zbuf -> out [B][1][2h][2w] (/ sigma(t_b) when t is given)
 int sbgm_launch_final_gather(const float* zbuf, const float* beta, const float* t, float sigma, float* out, int B, int h, int w,
                              hipStream_t st);
@@ -109,6 +117,7 @@ struct PackSrc {
     const float* ptr[4];   // NCHW sources, concatenated along C in this order
     int ch[4];
     int n;
+    int c0;                // channel of dst the first source lands on (the channels below it are written as zeros)
 };
 int sbgm_launch_pack_input(const PackSrc& src, float* dst_nhwc, int B, int H, int W, int Cs, hipStream_t st);
 int sbgm_launch_nhwc_to_nchw(const float* src, float* dst, int B, int H, int W, int C, hipStream_t st);

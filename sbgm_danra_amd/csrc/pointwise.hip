@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void pack_input_kernel(PackSrc src, float* __r
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            int c = q * 4 + e;
+            int c = q * 4 + e - src.c0;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 if (s < src.n) {
@@ -381,7 +381,7 @@ int sbgm_launch_pack_input(const PackSrc& src, float* dst, int B, int H, int W, 
     int ctot = 0;
     for (int i = 0; i < src.n; ++i) ctot += src.ch[i];
     SBGM_CHECK(src.n >= 1 && src.n <= 4, "pack_input: %d sources (1..4 supported)", src.n);
-    SBGM_CHECK(Cs % 4 == 0 && ctot <= Cs, "pack_input: %d channels do not fit padded width %d", ctot, Cs);
+    SBGM_CHECK(Cs % 4 == 0 && src.c0 >= 0 && src.c0 + ctot <= Cs, "pack_input: %d channels from %d do not fit padded width %d", ctot, src.c0, Cs);
     hipLaunchKernelGGL(pack_input_kernel, dim3(stream_blocks((size_t)B * H * W * (Cs / 4))), dim3(256), 0, st, src, dst, B,
                        H * W, Cs);
     SBGM_LAUNCH_CHECK();
