@@ -840,6 +840,41 @@ typedef struct sbgm_assemble_args {
 } sbgm_assemble_args;
 int sbgm_assemble_conditions(const sbgm_assemble_args* a, void* stream);
 
+/* ---- device-resident cutout batches (cutout.hip) ------------------------------------------------
+ * The per-sample host work of the reference's dataset (data_modules.py:727-997) for fields that live on the device as stacks
+ * [N][Hd][Wd] (one plane per day) and static planes [Hd][Wd].  Every op is stream-ordered without a host synchronisation.
+ *
+ * sbgm_cutout_draw: find_rand_points (data_modules.py:184-223) for B samples.  rect: HOST int [4] = [r0, r1, c0, c1], rows first,
+ * end-exclusive, inside the Hd x Wd domain; crop h x w no larger than it (both checked on the host).  origins: device int32 [B][2] =
+ * (y0, x0).  Sample b takes the uniforms of Philox block (seed, offset = draw, idx = b): y0 = r0 + min(max_off_y, (int)floorf(u_0 *
+ * (float)(max_off_y + 1))), x0 likewise from u_1 with c0, max_off = extent - crop; every step in fp32.
+ *
+ * sbgm_cutout_gather: dst[f][b][0][y][x] = program_f(src[f][item][y0_b + y][x0_b + x]) for every field f in ONE launch, item = items[b]
+ * for a stack (n_items[f] = N > 0) and 0 for a static plane (n_items[f] = 0).  At most 1 + SBGM_ASSEMBLE_MAX_LR stacks and 2 planes.
+ * srcs, dsts (each dst [B][1][h][w]) and n_items are HOST arrays of n_fields entries.  programs: DEVICE int32
+ * [n_fields][SBGM_CUTOUT_PROGRAM_WORDS], per field the steps and per-step fp32 rounding of sbgm_pointwise_chain (fill a host copy
+ * with sbgm_cutout_program_init, which validates it, and upload it once); a field with is_mask set is binarised after its program
+ * to v > 0.5 ? 1 : 0 (data_modules.py:874, :909).  items: device int32 [B]; origins: device int32 [B][2].  Any h, w >= 1; dst rows are
+ * written as 16-byte vectors when w % 4 == 0 and every dst is 16-byte aligned.  A sample whose item or origin lies outside its stack
+ * is filled with NaN.
+ *
+ * sbgm_sdf_from_mask: generate_sdf + normalize_sdf (data_modules.py:93-118) of mask [B][h][w] (land = mask > 0), per sample:
+ * D2 = the EXACT squared Euclidean distance in pixels to the nearest land pixel (0 on land; integer arithmetic, no search window),
+ * raw = 10 land - sqrt(D2), sdf = (raw - min raw) / (max raw - min raw), sqrt and normalisation in fp64 per pixel, rounded once to fp32.
+ * Two deliberate differences from the reference, on crops without a coastline: a sample with no sea gives sdf = 1 everywhere (reference:
+ * 0 / 0 = NaN); a sample with no land gives sdf = 0 everywhere (reference: scipy's transform of an input without background, which is
+ * not a distance to anything).  sdf: fp32 [B][h][w]; d2: int32 [B][h][w] or NULL (-1 throughout a sample with no land).  Sides <= 4096.
+ * ws: sbgm_sdf_workspace_bytes(B, h, w) bytes (-1: bad shape), cleared by the op itself.  Three launches; the only atomics are integer
+ * max / or, so two calls give bit-equal outputs. */
+#define SBGM_CUTOUT_MAX_FIELDS (1 + SBGM_ASSEMBLE_MAX_LR + 2)
+#define SBGM_CUTOUT_PROGRAM_WORDS (2 + 2 * SBGM_CHAIN_MAX_OPS)   /* n_ops, is_mask, ops[12] (int32), consts[12] (fp32) */
+int sbgm_cutout_draw(uint64_t seed, uint64_t draw, int B, const int* rect, int h, int w, int Hd, int Wd, int* origins, void* stream);
+int sbgm_cutout_program_init(int32_t* words_host, int n_ops, const int* ops, const float* consts, int is_mask);
+int sbgm_cutout_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const int32_t* programs,
+                       const int* items, const int* origins, int B, int Hd, int Wd, int h, int w, void* stream);
+int64_t sbgm_sdf_workspace_bytes(int B, int h, int w);
+int sbgm_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, int B, int h, int w, void* stream);
+
 /* ---- full-domain tiling (no reference counterpart, specification in DESIGN.md) -----------------
  * origins: device int32 [T][2] = (y0, x0) of every tile; the host validates that each tile lies inside the domain.
  * extract: tiles[T][C][th][tw] <- domain[C][Hd][Wd].   stitch: domain <- normalised blend of the covering tiles with

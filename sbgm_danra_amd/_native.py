@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libsbgm_hip.so")
 
 NONE, RELU, SILU, GELU = 0, 1, 2, 3
 NORM_INSTANCE, NORM_GROUP = 0, 1
+CUTOUT_MAX_FIELDS, CUTOUT_PROGRAM_WORDS = 19, 26                            # include/sbgm_hip.h
 SAMPLER_EM, SAMPLER_PC, SAMPLER_EDM_HEUN, SAMPLER_RK45, SAMPLER_DPMPP_2M = 0, 1, 2, 3, 4
 ODE_FINISHED, ODE_TOO_SMALL_STEP, ODE_NONFINITE, ODE_MAX_STEPS = 1, 2, 3, 4      # controller status of the RK45 solver
 ODE_PHASE_F0, ODE_PHASE_F1 = 7, 8                                              # sbgm_rk45_stage phases besides stages 1..6
@@ -90,6 +91,11 @@ SIGNATURES = {
     "sbgm_pointwise_chain": (_i, [_vp, _vp, _i64, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     "sbgm_sample_extremes": (_i, [_vp, _i, _i64, _f, _vp, _vp, _vp]),
     "sbgm_assemble_conditions": (_i, [C.POINTER(AssembleArgs), _vp]),
+    "sbgm_cutout_draw": (_i, [_u64, _u64, _i, C.POINTER(C.c_int), _i, _i, _i, _i, _vp, _vp]),
+    "sbgm_cutout_program_init": (_i, [C.POINTER(C.c_int32), _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _i]),
+    "sbgm_cutout_gather": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sbgm_sdf_workspace_bytes": (_i64, [_i, _i, _i]),
+    "sbgm_sdf_from_mask": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sbgm_depth_to_space2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "sbgm_space_to_depth2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "sbgm_depth_to_space": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -232,7 +238,7 @@ SIGNATURES = {
     "sbgm_ensemble_products": (_i, [_vp, _vp, _i, _i, _i64, C.POINTER(_d), _i, C.POINTER(_f), _i] + [_vp] * 9),
 }
 
-ABI_VERSION = 6         # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 7         # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

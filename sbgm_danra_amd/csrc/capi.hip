@@ -1,4 +1,6 @@
 // Per-op C-ABI entry points declared in include/sbgm_hip.h (the model / sampler entry points live in engine.hip).
+#include <string.h>
+
 #include "../../include/sbgm_hip.h"
 #include "common.h"
 #include "kernels.h"
@@ -241,6 +243,34 @@ int sbgm_pointwise_chain(const float* x, float* y, int64_t n, int n_ops, const i
 int sbgm_sample_extremes(const float* x, int B, int64_t per_sample, float q, float* out_max, float* out_q, void* stream) {
     SBGM_CHECK(x && out_max && out_q && per_sample > 0, "sample_extremes: bad arguments");
     return sbgm_launch_sample_extremes(x, B, (size_t)per_sample, q, out_max, out_q, ST);
+}
+
+// ---- device-resident cutout batches (cutout.hip) ----------------------------------------------------------------------
+int sbgm_cutout_draw(uint64_t seed, uint64_t draw, int B, const int* rect, int h, int w, int Hd, int Wd, int* origins, void* stream) {
+    return sbgm_launch_cutout_draw((unsigned long long)seed, (unsigned long long)draw, B, rect, h, w, Hd, Wd, origins, ST);
+}
+int sbgm_cutout_program_init(int32_t* words_host, int n_ops, const int* ops, const float* consts, int is_mask) {
+    SBGM_CHECK(words_host && (n_ops == 0 || (ops && consts)), "cutout_program_init: null argument");
+    SBGM_CHECK(n_ops >= 0 && n_ops <= SBGM_CHAIN_MAX_OPS, "cutout_program_init: %d ops (max %d)", n_ops, SBGM_CHAIN_MAX_OPS);
+    CutoutProgram p{};
+    p.n_ops = n_ops;
+    p.is_mask = is_mask ? 1 : 0;
+    for (int i = 0; i < n_ops; ++i) {
+        SBGM_CHECK(ops[i] >= SBGM_OP_ADD && ops[i] <= SBGM_OP_LOG, "cutout_program_init: unknown op code %d", ops[i]);
+        p.ops[i] = ops[i];
+        p.consts[i] = consts[i];
+    }
+    memcpy(words_host, &p, sizeof(p));
+    return 0;
+}
+int sbgm_cutout_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const int32_t* programs,
+                       const int* items, const int* origins, int B, int Hd, int Wd, int h, int w, void* stream) {
+    return sbgm_launch_cutout_gather(srcs, dsts, n_items, n_fields, reinterpret_cast<const CutoutProgram*>(programs), items, origins, B, Hd,
+                                     Wd, h, w, ST);
+}
+int64_t sbgm_sdf_workspace_bytes(int B, int h, int w) { return (int64_t)sbgm_sdf_ws_bytes(B, h, w); }
+int sbgm_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, int B, int h, int w, void* stream) {
+    return sbgm_launch_sdf_from_mask(mask, sdf, d2, ws, B, h, w, ST);
 }
 
 int sbgm_assemble_conditions(const sbgm_assemble_args* a, void* stream) {

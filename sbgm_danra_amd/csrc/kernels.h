@@ -399,6 +399,19 @@ int sbgm_launch_stitch_tiles(const float* tiles, const int* origins, float* dom,
 // out[T][1][th][tw] = the joint blend of scores[T][1][th][tw] (tile_blend.h), out of place; the host checks nothing about the origins
 int sbgm_launch_blend_tile_scores(const float* scores, float* out, const JointMap& jm, hipStream_t st);
 
+// ---- cutout.hip (device-resident cutout batches) ----------------------------------------------------------------------
+int sbgm_launch_cutout_draw(unsigned long long seed, unsigned long long draw, int B, const int* rect, int h, int w, int Hd, int Wd,
+                            int* origins, hipStream_t st);
+struct CutoutProgram {                        // one row of the device program table: SBGM_CUTOUT_PROGRAM_WORDS 32-bit words
+    int n_ops, is_mask;
+    int ops[12];
+    float consts[12];
+};
+int sbgm_launch_cutout_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const CutoutProgram* programs,
+                              const int* items, const int* origins, int B, int Hd, int Wd, int h, int w, hipStream_t st);
+long long sbgm_sdf_ws_bytes(int B, int h, int w);
+int sbgm_launch_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, int B, int h, int w, hipStream_t st);
+
 // ---- postproc.hip (after the sampler) ---------------------------------------------------------------------------------
 int sbgm_launch_pointwise_chain(const float* x, float* y, size_t n, int n_ops, const int* ops, const float* consts, hipStream_t st);
 int sbgm_launch_sample_extremes(const float* x, int B, size_t per, float q, float* out_max, float* out_q, hipStream_t st);

@@ -14,35 +14,11 @@
 #include <cmath>
 
 #include "../../include/sbgm_hip.h"
+#include "chain.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace {
-
-struct ChainProgram {
-    int n_ops;
-    int op[SBGM_CHAIN_MAX_OPS];
-    float c[SBGM_CHAIN_MAX_OPS];
-};
-
-__device__ __forceinline__ float chain_apply(float v, const ChainProgram& p) {
-#pragma unroll
-    for (int i = 0; i < SBGM_CHAIN_MAX_OPS; ++i) {
-        if (i >= p.n_ops) break;
-        const float c = p.c[i];
-        switch (p.op[i]) {
-            case SBGM_OP_ADD: v = __fadd_rn(v, c); break;
-            case SBGM_OP_MUL: v = __fmul_rn(v, c); break;
-            case SBGM_OP_DIV: v = __fdiv_rn(v, c); break;
-            case SBGM_OP_CLAMP_MIN: v = v < c ? c : v; break;     // comparisons keep NaN, like torch.clamp
-            case SBGM_OP_CLAMP_MAX: v = v > c ? c : v; break;
-            case SBGM_OP_EXP: v = expf(v); break;
-            case SBGM_OP_LOG: v = logf(v); break;
-            default: break;
-        }
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(256) void pointwise_chain_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n,
                                                               ChainProgram p) {

@@ -21,7 +21,7 @@ from .. import verification as V
 from ..score_sampling import (dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs, ode_sampler_kwargs, pc_sampler,
                               rk45_sampler)
 from ..score_unet import diffusion_coeff_fn, marginal_prob_std_fn
-from ..utils import extract_samples, get_model_string
+from ..utils import extract_any, get_model_string
 from .evaluation import ensemble_products_config
 
 logger = logging.getLogger(__name__)
@@ -156,7 +156,7 @@ class SampleGenerator:
                 np.savez_compressed(os.path.join(self.sample_path, f"{k}_{suffix}.npz"), v.cpu().numpy() if torch.is_tensor(v) else v)
 
     def _batch(self, first_only=False):
-        x, seasons, cond, _lsm_hr, lsm, _sdf, topo, _hp, _lp = extract_samples(next(iter(self.dataloader)), self.device)
+        x, seasons, cond, _lsm_hr, lsm, _sdf, topo, _hp, _lp = extract_any(next(iter(self.dataloader)), self.device)
         if first_only:
             x, seasons, cond, lsm, topo = [None if t is None else t[:1] for t in (x, seasons, cond, lsm, topo)]
         return x, seasons, cond, lsm, topo

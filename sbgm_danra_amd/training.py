@@ -23,7 +23,7 @@ from . import parallel
 from .ema import EMA_COUNT_KEY, EMA_KEY, ModelEMA, pick_network_params
 from .score_sampling import (Euler_Maruyama_sampler, dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs,
                              ode_sampler, ode_sampler_kwargs, pc_sampler, rk45_sampler)
-from .utils import (draw_condition_dropout, extract_samples, extract_samples_device, get_model_string,
+from .utils import (draw_condition_dropout, extract_any, extract_samples, extract_samples_device, get_model_string,
                     report_precip_extremes)
 
 logger = logging.getLogger(__name__)
@@ -346,7 +346,7 @@ class TrainingPipeline_general:
         if sampler is None:
             raise ValueError(f"Sampler type {cfg['sampler']['sampler_type']} not recognized.")
         samples = next(iter(gen_dataloader))
-        x, seasons, cond, _lsm_hr, lsm, _sdf, topo, _hp, _lp = extract_samples(samples, self.device)
+        x, seasons, cond, _lsm_hr, lsm, _sdf, topo, _hp, _lp = extract_any(samples, self.device)
         kw = dict(score_model=model, marginal_prob_std=self.marginal_prob_std_fn, diffusion_coeff=self.diffusion_coeff_fn,
                   batch_size=x.shape[0], num_steps=cfg["sampler"]["n_timesteps"], device=self.device,
                   img_size=cfg["highres"]["data_size"][0])

@@ -2,8 +2,9 @@
 (reference sbgm/training_utils.py: infer_in_channels :585-595, get_model :597-669, get_optimizer :672-696,
 get_scheduler, get_dataloader, get_gen_dataloader, setup_logger :793-823).
 
-Data: the reference reads zarr archives (out of scope); here `get_dataloader` serves synthetic
-batches of the same dict layout unless a caller passes its own loaders to the pipeline."""
+Data: the reference reads zarr archives (out of scope).  With `data_handling.resident_fields` in the config
+`get_dataloader` / `get_gen_dataloader` serve real fields from device memory (resident_data.py); without it they serve synthetic
+batches of the same dict layout.  A caller may also pass its own loaders to the pipeline."""
 from __future__ import annotations
 
 import logging
@@ -77,9 +78,13 @@ def get_scheduler(cfg, optimizer):
 
 
 def get_dataloader(cfg, shard=None):
-    """-> (train, val, gen) loaders of synthetic batches (see module docstring).  `shard=(rank, world)` splits the training
+    """-> (train, val, gen) loaders: resident cutout loaders with `data_handling.resident_fields`, else synthetic batches (see module
+    docstring).  `shard=(rank, world)` splits the training
     items over the data-parallel ranks (the reference's train loader drops the ragged last batch, data_modules / training_utils
     `drop_last=True`; kept here so every rank runs the same number of steps); validation and generation stay whole on every rank."""
+    if (cfg.get("data_handling", {}) or {}).get("resident_fields"):
+        from .resident_data import resident_loaders
+        return resident_loaders(cfg, shard=shard)
     bs = cfg["training"]["batch_size"]
     n_gen = max(1, int(cfg["data_handling"].get("n_gen_samples", 1) or 1))
     world = shard[1] if shard else 1
@@ -89,6 +94,9 @@ def get_dataloader(cfg, shard=None):
 
 def get_gen_dataloader(cfg, shard=None):
     """`shard=(rank, world)`: every rank draws its OWN evaluation batch (independent units, no collective: SURVEY.md 8e)"""
+    if (cfg.get("data_handling", {}) or {}).get("resident_fields"):
+        from .resident_data import resident_gen_loader
+        return resident_gen_loader(cfg, shard=shard)
     bs = int(cfg["evaluation"]["batch_size"])
     world = shard[1] if shard is not None else 1
     return synthetic_loader(cfg, bs, n_items=bs * world, seed=4, shard=shard if world > 1 else None)

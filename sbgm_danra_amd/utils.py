@@ -88,6 +88,13 @@ def extract_samples_device(samples: dict, device, dropped: torch.Tensor | None =
     return hr, y_out, lr_out, img("lsm_hr"), lsm_out, img("sdf"), topo_out, pts[0], pts[1]
 
 
+def extract_any(samples: dict, device):
+    """`extract_samples` for batches that already carry value||mask geo fields, `extract_samples_device` for raw ones (1-channel geo
+    fields, as the resident loader yields them): what an evaluation or generation batch needs, with no condition dropout."""
+    raw_geo = any(samples.get(k) is not None and samples[k].shape[1] == 1 for k in ("lsm", "topo"))
+    return extract_samples_device(samples, device) if raw_geo else extract_samples(samples, device)
+
+
 def get_model_string(cfg) -> str:
     """Checkpoint / output naming scheme of the reference (utils.py:88-128)."""
     hr = tuple(cfg["highres"]["data_size"]) if cfg["highres"].get("data_size") is not None else (128, 128)
