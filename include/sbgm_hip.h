@@ -521,6 +521,26 @@ int sbgm_attn_qkv_fwd(const float* x, const float* ln_gamma, const float* ln_bet
 int sbgm_attn_tail_fwd(const float* att, const float* x, const float* w_out_packed, const float* b_out, const float* ln_gamma,
                        const float* ln_beta, const float* w_ff1_packed, const float* b_ff1, const float* w_ff2_packed,
                        const float* b_ff2, float* out, int M, int C, float eps, void* stream);
+/* Which kernel instantiation ("variant") the attention launchers run for a shape.  Host-only: no device, no stream, no launch; the
+ * launchers call the same functions, and the SBGM_NO_LDS_ATTENTION / SBGM_NO_MHA_BWD_MFMA / SBGM_MHA_BWD_G / SBGM_MHA_BWD_WIDE_S
+ * environment switches act on both alike (each is read once per process).  A variant id indexes the complete list of instantiations
+ * of its family, 0 .. _variant_count() - 1; _variant_name(id) is the kernel's name (NULL outside the list).  The return value is the
+ * id, or -1 where the launcher refuses the shape (info is then unspecified).
+ *   sbgm_mha_core_fwd_variant : info = { family SBGM_MHA_FWD_*, d16 = ceil(head dim / 16), KSPLIT (register) or NQ (LDS), qsplit }
+ *   sbgm_mha_core_bwd_variant : info = { family SBGM_MHA_BWD_*, head dim, G (query blocks per workgroup; 1 outside mfma), workgroups }
+ *                               (head dims that are no multiple of 4 are not refused: they take the scalar kernel)
+ *   sbgm_attn_tokens_variant  : info = { C / 64, tokens per tile }; one id stands for that instantiation of BOTH token kernels */
+enum { SBGM_MHA_FWD_REGISTER = 0, SBGM_MHA_FWD_LDS = 1 };
+enum { SBGM_MHA_BWD_MFMA = 0, SBGM_MHA_BWD_LDS16 = 1, SBGM_MHA_BWD_LDS32 = 2, SBGM_MHA_BWD_SCALAR = 3 };
+int sbgm_mha_core_fwd_variant(int B, int S, int C, int heads, int info[4]);
+int sbgm_mha_core_fwd_variant_count(void);
+const char* sbgm_mha_core_fwd_variant_name(int id);
+int sbgm_mha_core_bwd_variant(int B, int S, int C, int heads, int info[4]);
+int sbgm_mha_core_bwd_variant_count(void);
+const char* sbgm_mha_core_bwd_variant_name(int id);
+int sbgm_attn_tokens_variant(int M, int C, int info[2]);
+int sbgm_attn_tokens_variant_count(void);
+const char* sbgm_attn_tokens_variant_name(int id);
 /* SinusoidalEmbedding (+ label embedding) -> SiLU -> Linear, for one projection.  score_unet.py:41-45, :377-381 */
 int sbgm_time_proj_fwd(const float* t, const int64_t* y, const float* label_emb, const float* freqs, const float* weight,
                        const float* bias, float* out, float* emb_ws /* [B,D] silu(emb) */, float* emb_raw /* [B,D] or NULL */,

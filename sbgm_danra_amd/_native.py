@@ -20,6 +20,8 @@ CUTOUT_MAX_FIELDS, CUTOUT_PROGRAM_WORDS = 19, 26                            # in
 SAMPLER_EM, SAMPLER_PC, SAMPLER_EDM_HEUN, SAMPLER_RK45, SAMPLER_DPMPP_2M = 0, 1, 2, 3, 4
 ODE_FINISHED, ODE_TOO_SMALL_STEP, ODE_NONFINITE, ODE_MAX_STEPS = 1, 2, 3, 4      # controller status of the RK45 solver
 ODE_PHASE_F0, ODE_PHASE_F1 = 7, 8                                              # sbgm_rk45_stage phases besides stages 1..6
+MHA_FWD_REGISTER, MHA_FWD_LDS = 0, 1                                           # families of sbgm_mha_core_fwd_variant
+MHA_BWD_MFMA, MHA_BWD_LDS16, MHA_BWD_LDS32, MHA_BWD_SCALAR = 0, 1, 2, 3        # families of sbgm_mha_core_bwd_variant
 
 _vp, _i, _f, _i64, _u64, _d = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64, C.c_double
 
@@ -174,6 +176,15 @@ SIGNATURES = {
     "sbgm_mha_core_dropout_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _u64, _u64, _vp]),
     "sbgm_mha_dropout_mask": (_i, [_vp, _i, _i, _i, _f, _u64, _u64, _vp]),
     "sbgm_attn_tail_fwd": (_i, [_vp] * 11 + [_i, _i, _f, _vp]),
+    "sbgm_mha_core_fwd_variant": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "sbgm_mha_core_fwd_variant_count": (_i, []),
+    "sbgm_mha_core_fwd_variant_name": (C.c_char_p, [_i]),
+    "sbgm_mha_core_bwd_variant": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "sbgm_mha_core_bwd_variant_count": (_i, []),
+    "sbgm_mha_core_bwd_variant_name": (C.c_char_p, [_i]),
+    "sbgm_attn_tokens_variant": (_i, [_i, _i, C.POINTER(C.c_int)]),
+    "sbgm_attn_tokens_variant_count": (_i, []),
+    "sbgm_attn_tokens_variant_name": (C.c_char_p, [_i]),
     "sbgm_time_proj_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sbgm_cout1_pack_weight": (_i, [_vp, _vp, _i, _vp]),
     "sbgm_conv3x3_cout1_fwd": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp]),
@@ -238,7 +249,7 @@ SIGNATURES = {
     "sbgm_ensemble_products": (_i, [_vp, _vp, _i, _i, _i64, C.POINTER(_d), _i, C.POINTER(_f), _i] + [_vp] * 9),
 }
 
-ABI_VERSION = 7         # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 8         # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

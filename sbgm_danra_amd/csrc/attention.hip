@@ -265,16 +265,55 @@ __global__ __launch_bounds__(256) void mha_core_lds_kernel(const float* __restri
     }
 }
 
+// Every instantiation of the two kernels, as X(D16, KSPLIT) / X(D16, NQ).  The variant ids (register kernels first, in this
+// order), their names, the lookup of sbgm_mha_fwd_plan and the launcher's switch are all generated from these two lists, so an
+// instantiation cannot exist without an id.
+#define SBGM_MHA_REG_VARIANTS(X)                                                                                                       \
+    X(1, 1) X(1, 4) X(2, 1) X(2, 4) X(3, 1) X(3, 4) X(4, 1) X(4, 4) X(6, 1) X(6, 4) X(8, 1) X(8, 4) X(12, 1) X(12, 4) X(16, 1) X(16, 4) \
+    X(32, 1)
+#define SBGM_MHA_LDS_VARIANTS(X) X(1, 1) X(1, 2) X(1, 4) X(2, 1) X(2, 2) X(2, 4) X(3, 1) X(3, 2) X(3, 4) X(4, 1) X(4, 2) X(4, 4)
+
+enum {
+#define X(DD, KK) MHA_REG_##DD##_##KK,
+    SBGM_MHA_REG_VARIANTS(X)
+#undef X
+#define X(DD, NN) MHA_LDS_##DD##_##NN,
+    SBGM_MHA_LDS_VARIANTS(X)
+#undef X
+    MHA_FWD_VARIANTS
+};
+struct MhaFwdVariant { int family, d16, kn; const char* name; };
+constexpr MhaFwdVariant mha_fwd_variants[MHA_FWD_VARIANTS] = {
+#define X(DD, KK) {MHA_FWD_REGISTER, DD, KK, "mha_core_kernel<" #DD "," #KK ">"},
+    SBGM_MHA_REG_VARIANTS(X)
+#undef X
+#define X(DD, NN) {MHA_FWD_LDS, DD, NN, "mha_core_lds_kernel<" #DD "," #NN ">"},
+    SBGM_MHA_LDS_VARIANTS(X)
+#undef X
+};
+int mha_fwd_variant_id(int family, int d16, int kn) {
+    for (int i = 0; i < MHA_FWD_VARIANTS; ++i)
+        if (mha_fwd_variants[i].family == family && mha_fwd_variants[i].d16 == d16 && mha_fwd_variants[i].kn == kn) return i;
+    return -1;
+}
+
 }  // namespace
 
-int sbgm_launch_mha_core(const float* qkv, float* out, int B, int S, int C, int heads, hipStream_t st) {
-    SBGM_CHECK(heads > 0 && C % heads == 0, "mha: C=%d not divisible by heads=%d", C, heads);
+int sbgm_mha_fwd_variant_count() { return MHA_FWD_VARIANTS; }
+const char* sbgm_mha_fwd_variant_name(int id) { return id >= 0 && id < MHA_FWD_VARIANTS ? mha_fwd_variants[id].name : nullptr; }
+
+// The one place that picks a forward variant and its launch geometry from the shape; no device call.
+int sbgm_mha_fwd_plan(int B, int S, int C, int heads, MhaFwdPlan* p) {
+    *p = MhaFwdPlan{};
+    p->id = -1;
+    if (!(B > 0 && S > 0 && heads > 0 && C > 0 && C % heads == 0)) return -1;
     const int d = C / heads;
-    SBGM_CHECK(d % 4 == 0 && d <= 512, "mha: head dim %d must be a multiple of 4 (<= 512)", d);
+    if (!(d % 4 == 0 && d <= 512)) return -1;
     const int d16 = (d + 15) / 16;
+    p->d16 = d16;
     // scores are kept in base-2 units (q pre-scaled by log2(e)/sqrt(d)): softmax = 2^(s - max) / sum, evaluated with the hardware
     // exp2 (1 ulp) — the full-range expf expansion cost as many VALU cycles per key block as its MFMAs
-    const float scale = 1.4426950408889634f / sqrtf((float)d);
+    p->scale = 1.4426950408889634f / sqrtf((float)d);
     static const bool lds_ok = getenv("SBGM_NO_LDS_ATTENTION") == nullptr;
     if (lds_ok && S >= 128 && d16 <= 4) {
         // query blocks of one (sample, head) are dealt to `qsplit` workgroups: one workgroup per CU if possible (every split stages
@@ -286,36 +325,44 @@ int sbgm_launch_mha_core(const float* qkv, float* out, int B, int S, int C, int 
         int qsplit = std::max((wg_target + bh - 1) / bh, (qblocks + 4 * MHA_NQ_MAX - 1) / (4 * MHA_NQ_MAX));
         qsplit = std::max(1, std::min(qsplit, qblocks));
         const int per_wave = (qblocks + 4 * qsplit - 1) / (4 * qsplit);          // query blocks per wave
-        const int nq = per_wave <= 1 ? 1 : per_wave <= 2 ? 2 : 4;
-        const size_t lds = (size_t)MHA_KCH * (d16 | 1) * 64 + (size_t)MHA_KCH * (16 * d16 + 4) * 4;
-        const dim3 grid(bh * qsplit), block(256);
-        int rc = 1;
-#define SBGM_MHAL(DD, NN)                                                                                                              \
-    if (d16 == DD && nq == NN) {                                                                                                       \
-        hipLaunchKernelGGL((mha_core_lds_kernel<DD, NN>), grid, block, lds, st, qkv, out, B, S, C, heads, scale, qsplit);            \
-        rc = 0;                                                                                                                        \
+        p->family = MHA_FWD_LDS;
+        p->kn = per_wave <= 1 ? 1 : per_wave <= 2 ? 2 : 4;
+        p->qsplit = qsplit;
+        p->lds = (size_t)MHA_KCH * (d16 | 1) * 64 + (size_t)MHA_KCH * (16 * d16 + 4) * 4;
+        p->grid = bh * qsplit;
+    } else {
+        const int waves = B * heads * ((S + 15) / 16);
+        const bool ksplit = S >= 64 && d <= 256;         // >= 4 key blocks: spread them over the 4 waves of a workgroup
+        p->family = MHA_FWD_REGISTER;
+        p->kn = ksplit ? 4 : 1;
+        p->qsplit = 1;
+        p->lds = ksplit ? (size_t)4 * 64 * 2 * 4 + (size_t)4 * d16 * 64 * 16 : 0;
+        p->grid = ksplit ? waves : (waves + 3) / 4;
     }
-        SBGM_MHAL(1, 1) SBGM_MHAL(1, 2) SBGM_MHAL(1, 4) SBGM_MHAL(2, 1) SBGM_MHAL(2, 2) SBGM_MHAL(2, 4)
-        SBGM_MHAL(3, 1) SBGM_MHAL(3, 2) SBGM_MHAL(3, 4) SBGM_MHAL(4, 1) SBGM_MHAL(4, 2) SBGM_MHAL(4, 4)
-#undef SBGM_MHAL
-        SBGM_CHECK(rc == 0, "mha: no LDS kernel for head dim %d", d);
-        SBGM_LAUNCH_CHECK();
-        return 0;
-    }
-    const int waves = B * heads * ((S + 15) / 16);
-    const bool ksplit = S >= 64 && d <= 256;             // >= 4 key blocks: spread them over the 4 waves of a workgroup
-    const dim3 grid(ksplit ? waves : (waves + 3) / 4), block(256);
-    const size_t lds = ksplit ? (size_t)4 * 64 * 2 * 4 + (size_t)4 * d16 * 64 * 16 : 0;
-    switch (d16) {
-#define SBGM_MHA(N)                                                                                                      \
-    case N:                                                                                                              \
-        if (ksplit) hipLaunchKernelGGL((mha_core_kernel<N, 4>), grid, block, lds, st, qkv, out, B, S, C, heads, scale);    \
-        else hipLaunchKernelGGL((mha_core_kernel<N, 1>), grid, block, 0, st, qkv, out, B, S, C, heads, scale);             \
+    p->id = mha_fwd_variant_id(p->family, d16, p->kn);
+    return p->id;
+}
+
+int sbgm_launch_mha_core(const float* qkv, float* out, int B, int S, int C, int heads, hipStream_t st) {
+    SBGM_CHECK(heads > 0 && C % heads == 0, "mha: C=%d not divisible by heads=%d", C, heads);
+    const int d = C / heads;
+    SBGM_CHECK(d % 4 == 0 && d <= 512, "mha: head dim %d must be a multiple of 4 (<= 512)", d);
+    MhaFwdPlan p;
+    SBGM_CHECK(sbgm_mha_fwd_plan(B, S, C, heads, &p) >= 0, "mha: head dim %d not instantiated (B=%d S=%d)", d, B, S);
+    const dim3 grid(p.grid), block(256);
+    switch (p.id) {
+#define X(DD, KK)                                                                                                                      \
+    case MHA_REG_##DD##_##KK:                                                                                                          \
+        hipLaunchKernelGGL((mha_core_kernel<DD, KK>), grid, block, p.lds, st, qkv, out, B, S, C, heads, p.scale);                     \
         break;
-        SBGM_MHA(1) SBGM_MHA(2) SBGM_MHA(3) SBGM_MHA(4) SBGM_MHA(6) SBGM_MHA(8) SBGM_MHA(12) SBGM_MHA(16)
-#undef SBGM_MHA
-        case 32: hipLaunchKernelGGL((mha_core_kernel<32, 1>), dim3((waves + 3) / 4), block, 0, st, qkv, out, B, S, C, heads, scale); break;
-        default: SBGM_CHECK(false, "mha: head dim %d not instantiated", d);
+        SBGM_MHA_REG_VARIANTS(X)
+#undef X
+#define X(DD, NN)                                                                                                                      \
+    case MHA_LDS_##DD##_##NN:                                                                                                          \
+        hipLaunchKernelGGL((mha_core_lds_kernel<DD, NN>), grid, block, p.lds, st, qkv, out, B, S, C, heads, p.scale, p.qsplit);       \
+        break;
+        SBGM_MHA_LDS_VARIANTS(X)
+#undef X
     }
     SBGM_LAUNCH_CHECK();
     return 0;

@@ -288,9 +288,41 @@ inline size_t tile_lds_bytes(int C, int tok) { return (size_t)2 * tok * C * size
 // 32-token tiles when that still gives every CU a workgroup, 16-token tiles below
 inline int tile_tokens(int M) { return M >= 256 * 64 ? 32 : 16; }
 
+// Every instantiation of attn_in_kernel / attn_out_kernel, as X(FCO = C / 64, FPX = tile tokens / 16).  The variant ids, their
+// names and the launchers' switch are generated from this list, so an instantiation cannot exist without an id.
+#define SBGM_ATTN_VARIANTS(X) X(1, 1) X(1, 2) X(2, 1) X(2, 2) X(4, 1) X(4, 2) X(8, 1) X(8, 2)
+enum {
+#define X(F, P_) ATTN_TOK_##F##_##P_,
+    SBGM_ATTN_VARIANTS(X)
+#undef X
+    ATTN_TOK_VARIANTS
+};
+struct AttnTokensVariant { int fco, fpx; const char* name; };
+constexpr AttnTokensVariant attn_tokens_variants[ATTN_TOK_VARIANTS] = {
+#define X(F, P_) {F, P_, "attn_in_kernel<" #F "," #P_ ">, attn_out_kernel<" #F "," #P_ ">"},
+    SBGM_ATTN_VARIANTS(X)
+#undef X
+};
+
 }  // namespace
 
 int sbgm_attn_tokens_supported(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
+int sbgm_attn_tok_variant_count() { return ATTN_TOK_VARIANTS; }
+const char* sbgm_attn_tok_variant_name(int id) { return id >= 0 && id < ATTN_TOK_VARIANTS ? attn_tokens_variants[id].name : nullptr; }
+
+// The one place that picks the token-tile variant and its launch geometry from the shape; no device call.
+int sbgm_attn_tokens_plan(int M, int C, AttnTokensPlan* p) {
+    *p = AttnTokensPlan{};
+    p->id = -1;
+    if (!sbgm_attn_tokens_supported(C) || M < 1) return -1;
+    p->fco = C / 64;
+    p->tok = tile_tokens(M);
+    p->grid = (M + p->tok - 1) / p->tok;
+    p->lds = tile_lds_bytes(C, p->tok);
+    for (int i = 0; i < ATTN_TOK_VARIANTS; ++i)
+        if (attn_tokens_variants[i].fco == p->fco && 16 * attn_tokens_variants[i].fpx == p->tok) p->id = i;
+    return p->id;
+}
 
 #define SBGM_ATTN_LAUNCH(KERNEL, F, P_)                                                                                       \
     {                                                                                                                         \
@@ -298,17 +330,12 @@ int sbgm_attn_tokens_supported(int C) { return C == 64 || C == 128 || C == 256 |
         if (!attr) { SBGM_HIP(hipFuncSetAttribute((const void*)KERNEL<F, P_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; } \
         hipLaunchKernelGGL((KERNEL<F, P_>), grid, dim3(256), lds, st, a);                                                     \
     }
-#define SBGM_ATTN_SWITCH(KERNEL)                                                                                              \
-    switch ((C / 64) * 4 + tok / 16) {                                                                                        \
-        case 1 * 4 + 1: SBGM_ATTN_LAUNCH(KERNEL, 1, 1) break;                                                                 \
-        case 1 * 4 + 2: SBGM_ATTN_LAUNCH(KERNEL, 1, 2) break;                                                                 \
-        case 2 * 4 + 1: SBGM_ATTN_LAUNCH(KERNEL, 2, 1) break;                                                                 \
-        case 2 * 4 + 2: SBGM_ATTN_LAUNCH(KERNEL, 2, 2) break;                                                                 \
-        case 4 * 4 + 1: SBGM_ATTN_LAUNCH(KERNEL, 4, 1) break;                                                                 \
-        case 4 * 4 + 2: SBGM_ATTN_LAUNCH(KERNEL, 4, 2) break;                                                                 \
-        case 8 * 4 + 1: SBGM_ATTN_LAUNCH(KERNEL, 8, 1) break;                                                                 \
-        case 8 * 4 + 2: SBGM_ATTN_LAUNCH(KERNEL, 8, 2) break;                                                                 \
-    }
+#define SBGM_ATTN_CASE(F, P_) case ATTN_TOK_##F##_##P_: SBGM_ATTN_LAUNCH(SBGM_ATTN_KERNEL, F, P_) break;
+// expects SBGM_ATTN_KERNEL to name the kernel template
+#define SBGM_ATTN_SWITCH(PLAN)                                                                                                \
+    const dim3 grid((PLAN).grid);                                                                                             \
+    const size_t lds = (PLAN).lds;                                                                                            \
+    switch ((PLAN).id) { SBGM_ATTN_VARIANTS(SBGM_ATTN_CASE) }
 
 int sbgm_launch_attn_in(const float* x, const float* ln_g, const float* ln_b, const float* w_packed, const float* bias, float* qkv,
                         int M, int C, float eps, hipStream_t st) {
@@ -316,10 +343,11 @@ int sbgm_launch_attn_in(const float* x, const float* ln_g, const float* ln_b, co
     SBGM_CHECK(sbgm_attn_tokens_supported(C), "attn_in: C=%d (supported: 64, 128, 256, 512)", C);
     SBGM_CHECK(M >= 1, "attn_in: M=%d", M);
     AttnInArgs a{x, ln_g, ln_b, w_packed, bias, qkv, M, eps, (unsigned)((size_t)3 * C * C * sizeof(float))};
-    const int tok = tile_tokens(M);
-    const dim3 grid((M + tok - 1) / tok);
-    const size_t lds = tile_lds_bytes(C, tok);
-    SBGM_ATTN_SWITCH(attn_in_kernel)
+    AttnTokensPlan plan;
+    SBGM_CHECK(sbgm_attn_tokens_plan(M, C, &plan) >= 0, "attn_in: no kernel for M=%d C=%d", M, C);
+#define SBGM_ATTN_KERNEL attn_in_kernel
+    SBGM_ATTN_SWITCH(plan)
+#undef SBGM_ATTN_KERNEL
     SBGM_LAUNCH_CHECK();
     return 0;
 }
@@ -332,10 +360,11 @@ int sbgm_launch_attn_out(const float* att, const float* x, const float* wo, cons
     SBGM_CHECK(M >= 1, "attn_out: M=%d", M);
     SBGM_CHECK(out != att, "attn_out: out must not alias att");
     AttnOutArgs a{att, x, wo, bo, ln_g, ln_b, w1, b1, w2, b2, out, M, eps, (unsigned)((size_t)C * C * sizeof(float))};
-    const int tok = tile_tokens(M);
-    const dim3 grid((M + tok - 1) / tok);
-    const size_t lds = tile_lds_bytes(C, tok);
-    SBGM_ATTN_SWITCH(attn_out_kernel)
+    AttnTokensPlan plan;
+    SBGM_CHECK(sbgm_attn_tokens_plan(M, C, &plan) >= 0, "attn_out: no kernel for M=%d C=%d", M, C);
+#define SBGM_ATTN_KERNEL attn_out_kernel
+    SBGM_ATTN_SWITCH(plan)
+#undef SBGM_ATTN_KERNEL
     SBGM_LAUNCH_CHECK();
     return 0;
 }

@@ -1997,55 +1997,107 @@ int sbgm_launch_layernorm_bwd(const float* x, const float* dy, const float* gamm
     return 0;
 }
 
-int sbgm_launch_mha_core_bwd(const float* qkv, const float* dout, float* dqkv, int B, int S, int C, int heads, hipStream_t st) {
-    SBGM_CHECK(heads > 0 && C % heads == 0, "mha_bwd: C=%d heads=%d", C, heads);
-    SBGM_CHECK((size_t)2 * 16 * S * 4 <= 150 * 1024, "mha_bwd: S=%d too long for the LDS-resident score rows", S);
-    if (!sbgm_scratch_prezeroed) { if (sbgm_zero_async(dqkv, (size_t)B * S * 3 * C * 4, st)) return 1; }
+// Every attention-backward kernel, as X(enumerator, kernel, family, template parameter, launch form).  The variant ids, their
+// names and the launcher's switch are generated from this list, so an instantiation cannot exist without an id.
+#define SBGM_MHA_BWD_VARIANTS(X)                                                                                                  \
+    X(MHAB_MFMA32, mha_core_bwd_mfma_kernel<32>, MHA_BWD_MFMA, 32, MFMA)                                                          \
+    X(MHAB_MFMA64, mha_core_bwd_mfma_kernel<64>, MHA_BWD_MFMA, 64, MFMA)                                                          \
+    X(MHAB_MFMA128, mha_core_bwd_mfma_kernel<128>, MHA_BWD_MFMA, 128, MFMA)                                                       \
+    X(MHAB_LDS16, mha_core_bwd_lds_kernel<16>, MHA_BWD_LDS16, 16, LDS)                                                            \
+    X(MHAB_LDS32, mha_core_bwd_lds_kernel<32>, MHA_BWD_LDS32, 32, LDS)                                                            \
+    X(MHAB_SCALAR, mha_core_bwd_kernel, MHA_BWD_SCALAR, 0, SCALAR)
+namespace {
+enum {
+#define X(E, K, F, T, L) E,
+    SBGM_MHA_BWD_VARIANTS(X)
+#undef X
+    MHAB_VARIANTS
+};
+struct MhaBwdVariant { int family, tparam; const char* name; };
+constexpr MhaBwdVariant mha_bwd_variants[MHAB_VARIANTS] = {
+#define X(E, K, F, T, L) {F, T, #K},
+    SBGM_MHA_BWD_VARIANTS(X)
+#undef X
+};
+int mha_bwd_variant_id(int family, int tparam) {
+    for (int i = 0; i < MHAB_VARIANTS; ++i)
+        if (mha_bwd_variants[i].family == family && (family != MHA_BWD_MFMA || mha_bwd_variants[i].tparam == tparam)) return i;
+    return -1;
+}
+constexpr size_t MHA_BWD_LDS_MAX = 150 * 1024;
+}  // namespace
+
+int sbgm_mha_bwd_variant_count() { return MHAB_VARIANTS; }
+const char* sbgm_mha_bwd_variant_name(int id) { return id >= 0 && id < MHAB_VARIANTS ? mha_bwd_variants[id].name : nullptr; }
+
+// The one place that picks a backward variant and its launch geometry from the shape; no device call.
+int sbgm_mha_bwd_plan(int B, int S, int C, int heads, MhaBwdPlan* p) {
+    *p = MhaBwdPlan{};
+    p->id = -1;
+    if (!(B > 0 && S > 0 && heads > 0 && C > 0 && C % heads == 0)) return -1;
+    if (!((size_t)2 * 16 * S * 4 <= MHA_BWD_LDS_MAX)) return -1;      // the score rows of 16 queries stay in LDS in every variant
     const int blocks = B * heads * ((S + 15) / 16);
     const int d = C / heads;
-    {   // matrix-pipe form: head dim 32 / 64 / 128, K and V of a (sample, head) LDS-resident, <= 128 / d key blocks per wave
-        const int S16 = (S + 15) & ~15;
-        const size_t lds_mfma = ((size_t)(2 * S16 + 32) * (d + 4) + (size_t)32 * (S16 + 4)) * 4;
-        static const bool mfma_ok = getenv("SBGM_NO_MHA_BWD_MFMA") == nullptr;
-        if (mfma_ok && (d == 32 || d == 64 || d == 128) && lds_mfma <= 150 * 1024 && S16 / 16 <= 4 * (128 / d)) {
-            const float scale = 1.0f / sqrtf((float)d);
-            // G query blocks per workgroup share one staging of K / V and one round of dK / dV atomics: as many as still leave every CU a
-            // workgroup (the 256-token block of a batch-8 step: 512 -> 256 workgroups of 2 query blocks)
-            static const int gmax = getenv("SBGM_MHA_BWD_G") ? atoi(getenv("SBGM_MHA_BWD_G")) : 0;
-            const int qblocks = (S + 15) / 16;
-            int G = gmax > 0 ? gmax : std::max(1, blocks / 256);
-            G = std::max(1, std::min(G, qblocks));
-            const int grid = B * heads * ((qblocks + G - 1) / G);
-#define SBGM_MB(DD)                                                                                                              \
+    p->d = d;
+    p->G = 1;
+    p->grid = blocks;
+    // matrix-pipe form: head dim 32 / 64 / 128, K and V of a (sample, head) LDS-resident, <= 128 / d key blocks per wave
+    const int S16 = (S + 15) & ~15;
+    const size_t lds_mfma = ((size_t)(2 * S16 + 32) * (d + 4) + (size_t)32 * (S16 + 4)) * 4;
+    static const bool mfma_ok = getenv("SBGM_NO_MHA_BWD_MFMA") == nullptr;
+    const size_t lds_staged = ((size_t)(2 * S + 32) * (d + 1) + (size_t)32 * S) * 4;
+    if (mfma_ok && (d == 32 || d == 64 || d == 128) && lds_mfma <= MHA_BWD_LDS_MAX && S16 / 16 <= 4 * (128 / d)) {
+        // G query blocks per workgroup share one staging of K / V and one round of dK / dV atomics: as many as still leave every CU a
+        // workgroup (the 256-token block of a batch-8 step: 512 -> 256 workgroups of 2 query blocks)
+        static const int gmax = getenv("SBGM_MHA_BWD_G") ? atoi(getenv("SBGM_MHA_BWD_G")) : 0;
+        const int qblocks = (S + 15) / 16;
+        int G = gmax > 0 ? gmax : std::max(1, blocks / 256);
+        G = std::max(1, std::min(G, qblocks));
+        p->family = MHA_BWD_MFMA;
+        p->G = G;
+        p->grid = B * heads * ((qblocks + G - 1) / G);
+        p->lds = lds_mfma;
+        p->id = mha_bwd_variant_id(MHA_BWD_MFMA, d);
+    } else if (d % 4 == 0 && lds_staged <= MHA_BWD_LDS_MAX) {
+        static const int wide_from = getenv("SBGM_MHA_BWD_WIDE_S") ? atoi(getenv("SBGM_MHA_BWD_WIDE_S")) : 16;
+        p->family = S >= wide_from ? MHA_BWD_LDS32 : MHA_BWD_LDS16;
+        p->lds = lds_staged;
+        p->id = mha_bwd_variant_id(p->family, 0);
+    } else {
+        p->family = MHA_BWD_SCALAR;
+        p->lds = (size_t)2 * 16 * S * 4;
+        p->id = mha_bwd_variant_id(MHA_BWD_SCALAR, 0);
+    }
+    return p->id;
+}
+
+int sbgm_launch_mha_core_bwd(const float* qkv, const float* dout, float* dqkv, int B, int S, int C, int heads, hipStream_t st) {
+    SBGM_CHECK(heads > 0 && C % heads == 0, "mha_bwd: C=%d heads=%d", C, heads);
+    SBGM_CHECK((size_t)2 * 16 * S * 4 <= MHA_BWD_LDS_MAX, "mha_bwd: S=%d too long for the LDS-resident score rows", S);
+    MhaBwdPlan p;
+    SBGM_CHECK(sbgm_mha_bwd_plan(B, S, C, heads, &p) >= 0, "mha_bwd: no kernel for B=%d S=%d C=%d heads=%d", B, S, C, heads);
+    if (!sbgm_scratch_prezeroed) { if (sbgm_zero_async(dqkv, (size_t)B * S * 3 * C * 4, st)) return 1; }
+    const float scale = 1.0f / sqrtf((float)p.d);
+#define SBGM_MHAB_LAUNCH_MFMA(K)                                                                                                  \
     {                                                                                                                              \
         static bool attr = false;                                                                                                  \
-        if (!attr) { SBGM_HIP(hipFuncSetAttribute((const void*)mha_core_bwd_mfma_kernel<DD>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr = true; } \
-        hipLaunchKernelGGL(mha_core_bwd_mfma_kernel<DD>, dim3(grid), dim3(256), lds_mfma, st, qkv, dout, dqkv, B, S, C, heads, scale, G);  \
+        if (!attr) { SBGM_HIP(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MHA_BWD_LDS_MAX)); attr = true; } \
+        hipLaunchKernelGGL(K, dim3(p.grid), dim3(256), p.lds, st, qkv, dout, dqkv, B, S, C, heads, scale, p.G);                    \
     }
-            if (d == 32) SBGM_MB(32) else if (d == 64) SBGM_MB(64) else SBGM_MB(128)
-#undef SBGM_MB
-            SBGM_LAUNCH_CHECK();
-            return 0;
-        }
+#define SBGM_MHAB_LAUNCH_LDS(K)                                                                                                   \
+    {                                                                                                                              \
+        if (p.lds > 64 * 1024) SBGM_HIP(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds)); \
+        hipLaunchKernelGGL(K, dim3(p.grid), dim3(p.family == MHA_BWD_LDS32 ? 512 : 256), p.lds, st, qkv, dout, dqkv, B, S, C, heads, scale); \
     }
-    const size_t lds_staged = ((size_t)(2 * S + 32) * (d + 1) + (size_t)32 * S) * 4;
-    if (d % 4 == 0 && lds_staged <= 150 * 1024) {
-        if (lds_staged > 64 * 1024)
-            SBGM_HIP(hipFuncSetAttribute((const void*)mha_core_bwd_lds_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_staged));
-        if (lds_staged > 64 * 1024)
-            SBGM_HIP(hipFuncSetAttribute((const void*)mha_core_bwd_lds_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_staged));
-        static const int wide_from = getenv("SBGM_MHA_BWD_WIDE_S") ? atoi(getenv("SBGM_MHA_BWD_WIDE_S")) : 16;
-        if (S >= wide_from)
-            hipLaunchKernelGGL(mha_core_bwd_lds_kernel<32>, dim3(blocks), dim3(512), lds_staged, st, qkv, dout, dqkv, B, S, C, heads,
-                               1.0f / sqrtf((float)d));
-        else
-            hipLaunchKernelGGL(mha_core_bwd_lds_kernel<16>, dim3(blocks), dim3(256), lds_staged, st, qkv, dout, dqkv, B, S, C, heads,
-                               1.0f / sqrtf((float)d));
-        SBGM_LAUNCH_CHECK();
-        return 0;
+#define SBGM_MHAB_LAUNCH_SCALAR(K) hipLaunchKernelGGL(K, dim3(p.grid), dim3(256), p.lds, st, qkv, dout, dqkv, B, S, C, heads, scale);
+    switch (p.id) {
+#define X(E, K, F, T, L) case E: SBGM_MHAB_LAUNCH_##L(K) break;
+        SBGM_MHA_BWD_VARIANTS(X)
+#undef X
     }
-    hipLaunchKernelGGL(mha_core_bwd_kernel, dim3(blocks), dim3(256), (size_t)2 * 16 * S * 4, st, qkv, dout, dqkv, B, S, C, heads,
-                       1.0f / sqrtf((float)(C / heads)));
+#undef SBGM_MHAB_LAUNCH_MFMA
+#undef SBGM_MHAB_LAUNCH_LDS
+#undef SBGM_MHAB_LAUNCH_SCALAR
     SBGM_LAUNCH_CHECK();
     return 0;
 }

@@ -203,6 +203,33 @@ int sbgm_attn_tail_fwd(const float* att, const float* x, const float* w_out_pack
                        const float* b_ff2, float* out, int M, int C, float eps, void* stream) {
     return sbgm_launch_attn_out(att, x, w_out_packed, b_out, ln_gamma, ln_beta, w_ff1_packed, b_ff1, w_ff2_packed, b_ff2, out, M, C, eps, ST);
 }
+static_assert(SBGM_MHA_FWD_REGISTER == MHA_FWD_REGISTER && SBGM_MHA_FWD_LDS == MHA_FWD_LDS, "family codes of the header");
+static_assert(SBGM_MHA_BWD_MFMA == MHA_BWD_MFMA && SBGM_MHA_BWD_LDS16 == MHA_BWD_LDS16 && SBGM_MHA_BWD_LDS32 == MHA_BWD_LDS32 &&
+              SBGM_MHA_BWD_SCALAR == MHA_BWD_SCALAR, "family codes of the header");
+int sbgm_mha_core_fwd_variant(int B, int S, int C, int heads, int info[4]) {
+    MhaFwdPlan p;
+    const int id = sbgm_mha_fwd_plan(B, S, C, heads, &p);
+    if (info) { info[0] = p.family; info[1] = p.d16; info[2] = p.kn; info[3] = p.qsplit; }
+    return id;
+}
+int sbgm_mha_core_fwd_variant_count(void) { return sbgm_mha_fwd_variant_count(); }
+const char* sbgm_mha_core_fwd_variant_name(int id) { return sbgm_mha_fwd_variant_name(id); }
+int sbgm_mha_core_bwd_variant(int B, int S, int C, int heads, int info[4]) {
+    MhaBwdPlan p;
+    const int id = sbgm_mha_bwd_plan(B, S, C, heads, &p);
+    if (info) { info[0] = p.family; info[1] = p.d; info[2] = p.G; info[3] = p.grid; }
+    return id;
+}
+int sbgm_mha_core_bwd_variant_count(void) { return sbgm_mha_bwd_variant_count(); }
+const char* sbgm_mha_core_bwd_variant_name(int id) { return sbgm_mha_bwd_variant_name(id); }
+int sbgm_attn_tokens_variant(int M, int C, int info[2]) {
+    AttnTokensPlan p;
+    const int id = sbgm_attn_tokens_plan(M, C, &p);
+    if (info) { info[0] = p.fco; info[1] = p.tok; }
+    return id;
+}
+int sbgm_attn_tokens_variant_count(void) { return sbgm_attn_tok_variant_count(); }
+const char* sbgm_attn_tokens_variant_name(int id) { return sbgm_attn_tok_variant_name(id); }
 int sbgm_time_proj_fwd(const float* t, const int64_t* y, const float* label_emb, const float* freqs, const float* weight,
                        const float* bias, float* out, float* emb_ws, float* emb_raw, int B, int D, int ch, void* stream) {
     TimeEmbedArgs a{};

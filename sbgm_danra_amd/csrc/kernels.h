@@ -200,8 +200,28 @@ int sbgm_launch_batchnorm_bwd_apply(const float* x, const float* dy, const float
 
 // ---- attention.hip -------------------------------------------------------------------------------------
 int sbgm_launch_mha_core(const float* qkv, float* out, int B, int S, int C, int heads, hipStream_t st);
+// Which kernel instantiation a shape takes, decided on the host without a device call.  The launchers run exactly what these
+// return; the C ABI exposes them (sbgm_*_variant, include/sbgm_hip.h) so that tests can prove they reach every instantiation.
+// family codes = the SBGM_MHA_FWD_* / SBGM_MHA_BWD_* enums of the public header.
+constexpr int MHA_FWD_REGISTER = 0, MHA_FWD_LDS = 1;
+struct MhaFwdPlan {
+    int id;            // index into the variant table, -1 = refused
+    int family, d16;
+    int kn;            // KSPLIT of the register kernel, NQ of the LDS kernel
+    int qsplit;        // workgroups per (sample, head) of the LDS kernel (1 for the register kernel)
+    float scale;
+    int grid;
+    size_t lds;
+};
+int sbgm_mha_fwd_plan(int B, int S, int C, int heads, MhaFwdPlan* p);      // returns p->id
+int sbgm_mha_fwd_variant_count();
+const char* sbgm_mha_fwd_variant_name(int id);
 // attn_tokens.hip: the per-token halves of an attention block, one launch each (C in {64, 128, 256, 512})
 int sbgm_attn_tokens_supported(int C);
+struct AttnTokensPlan { int id, fco, tok, grid; size_t lds; };               // id: (C/64, tile tokens) of attn_in_kernel and attn_out_kernel
+int sbgm_attn_tokens_plan(int M, int C, AttnTokensPlan* p);                 // returns p->id, -1 = refused
+int sbgm_attn_tok_variant_count();
+const char* sbgm_attn_tok_variant_name(int id);
 // ---- attention_dropout.hip: the attention core with train-mode dropout on the softmax probabilities (Philox mask keyed by seed / offset)
 // forward: out_or_dqkv = out [B,S,C], dout unused;  backward != 0: out_or_dqkv = dqkv [B,S,3C] (zeroed unless sbgm_scratch_prezeroed)
 int sbgm_launch_mha_core_dropout(const float* qkv, const float* dout, float* out_or_dqkv, int B, int S, int C, int heads, float p,
@@ -443,6 +463,18 @@ int sbgm_launch_batchnorm_bwd(const float* x, const float* dy, const float* y, c
 int sbgm_launch_layernorm_bwd(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta, int M, int C,
                               float eps, hipStream_t st, const float* dx_add = nullptr);   // dx_add [M, C] or null: summed into dx
 int sbgm_launch_mha_core_bwd(const float* qkv, const float* dout, float* dqkv, int B, int S, int C, int heads, hipStream_t st);
+constexpr int MHA_BWD_MFMA = 0, MHA_BWD_LDS16 = 1, MHA_BWD_LDS32 = 2, MHA_BWD_SCALAR = 3;
+struct MhaBwdPlan {
+    int id;            // index into the variant table, -1 = refused
+    int family;
+    int d;             // head dim
+    int G;             // query blocks per workgroup of the matrix-pipe kernel (1 elsewhere)
+    int grid;
+    size_t lds;
+};
+int sbgm_mha_bwd_plan(int B, int S, int C, int heads, MhaBwdPlan* p);      // returns p->id
+int sbgm_mha_bwd_variant_count();
+const char* sbgm_mha_bwd_variant_name(int id);
 int sbgm_launch_upsample2x_bwd(const float* dy, float* dx, int B, int H, int W, int C, hipStream_t st);
 int sbgm_launch_cout1_bwd(const float* dout, const float* a, const float* w_tap_c, const float* t, float sigma, float* da,
                           float* dw_tap_c, float* dbias, int B, int H, int W, int C, hipStream_t st);
