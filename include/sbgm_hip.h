@@ -837,6 +837,43 @@ int sbgm_ensemble_products(const float* ens, const void* mask, int mask_is_u8, i
                            float* quant /* [Q][HW] */, float* exceed /* [T][HW] */, int64_t* count /* [1] */,
                            void* workspace, void* stream);
 
+/* ---- object-based verification (verify_objects.hip) ----------------------------------------------
+ * Validity and masks as above.  For a side F in {gen, obs} an object pixel is a valid pixel with F >= thr in fp32; objects are
+ * the 4- or 8-connected components (`connectivity`) of the object pixels.  Limits: sides 2..2048, H*W <= 2^20, N <= 65535.
+ *
+ * sbgm_object_labels: fields [N][H][W], mask [Nm][H][W] or NULL -> labels int32 [N][H][W]: 1 + the smallest linear index
+ * row * W + col of the pixel's object, 0 for background.  The labels array is the only working memory.
+ *
+ * sbgm_object_scores: gen [N][H][W] against obs [No][H][W]; index 0 of every [2] axis is gen, 1 is obs.  `thresholds` is a
+ * HOST array of n_fixed finite values (0..16), used on both sides; with has_relative, one more threshold index follows them:
+ * thr = (float)(rel_factor * q) with q the type-7 quantile (level rel_quantile; exact order statistics, fp64 interpolation,
+ * rounded to fp32 as sbgm_ensemble_products defines it) of that side's valid values >= rel_wet of that field, NaN (no
+ * objects) when there is none.  T = n_fixed + has_relative >= 1.  Per object n: area a_n, mass R_n = sum F, peak Rmax_n,
+ * centre x_n = sum F (row, col) / R_n.  Outputs: threshold fp32 [2][N][T]; n_objects, area int64 [2][N][T]; mass = sum_n R_n,
+ * V = sum_n R_n (R_n / Rmax_n) / mass, r = sum_n R_n |x - x_n| / mass fp64 [2][N][T]; domain_mean fp64 [2][N] = mean of F
+ * over the valid pixels; com fp64 [2][N][2] = x, the F-weighted centre of the valid pixels; valid int64 [N]; with
+ * d = sqrt((H-1)^2 + (W-1)^2): S = (V_g - V_o) / (0.5 (V_g + V_o)), L2 = 2 |r_g - r_o| / d, L = L1 + L2 fp64 [N][T];
+ * A = (D_g - D_o) / (0.5 (D_g + D_o)), L1 = |x_g - x_o| / d fp64 [N]; a score is NaN where a denominator is 0, S and L2 where
+ * either side has no object, A and L1 where there is no valid pixel or a side sums to 0.  area_hist int64 [2][T][21]: objects
+ * with floor(log2 a_n) = b, over all fields.  status int32 [1]: 0, or SBGM_OBJECTS_STATUS_* bits when a union-find walk hit
+ * its step cap (a bug; the results are then not to be used).  Each pixel enters the sums as a 31-bit fixed-point integer
+ * scaled to its field's largest magnitude: exact for values that are multiples of 2^-8 below 256, within (vmax / thr) 2^-30
+ * relative otherwise; integer atomics only, fp64 sums in a fixed order, so two calls are bit-equal.  The (field, threshold)
+ * pairs are processed in chunks, stream-ordered, within `workspace_bytes`; sbgm_object_scores_workspace_bytes gives the size
+ * to allocate for a cap of max_bytes (at least one pair, at most all).  The result does not depend on the chunking. */
+#define SBGM_OBJECTS_MAX_THRESHOLDS 16
+#define SBGM_OBJECTS_AREA_BINS 21
+#define SBGM_OBJECTS_STATUS_MERGE_CAP 1
+#define SBGM_OBJECTS_STATUS_FIND_CAP 2
+int sbgm_object_labels(const float* fields, const void* mask, int mask_is_u8, int N, int Nm, int H, int W, float threshold,
+                       int connectivity, int* labels, int* status, void* stream);
+int64_t sbgm_object_scores_workspace_bytes(int N, int H, int W, int T, int64_t max_bytes);
+int sbgm_object_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
+                       const float* thresholds, int n_fixed, int has_relative, double rel_factor, double rel_quantile, float rel_wet,
+                       int connectivity, float* threshold, int64_t* n_objects, int64_t* area, double* mass, double* V, double* r,
+                       double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A, double* L1, double* L,
+                       int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- before the network ------------------------------------------------------------------------
  * Batch-level condition assembly: channel concatenation of the sorted *_lr fields (utils.py:441-447), classifier-free-
  * guidance condition dropout (data_modules.py:957-983: LR fields -> 0, class label -> NULL token 0) and the value||mask

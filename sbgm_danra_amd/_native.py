@@ -247,9 +247,12 @@ SIGNATURES = {
     "sbgm_exceedance_scores": (_i, [_vp, _vp, _vp, _i, _i, _i64, C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp]),
     "sbgm_ensemble_products_workspace_bytes": (_i64, [_i, _i64, _i, _i]),
     "sbgm_ensemble_products": (_i, [_vp, _vp, _i, _i, _i64, C.POINTER(_d), _i, C.POINTER(_f), _i] + [_vp] * 9),
+    "sbgm_object_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "sbgm_object_scores_workspace_bytes": (_i64, [_i, _i, _i, _i, _i64]),
+    "sbgm_object_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _i, _i, _d, _d, _f, _i] + [_vp] * 17 + [_i64, _vp]),
 }
 
-ABI_VERSION = 8         # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 9         # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

@@ -360,6 +360,24 @@ int sbgm_exceedance_scores(const float* ens, const float* obs, const void* mask,
     return sbgm_launch_exceedance_scores(ens, obs, mask, mask_is_u8, M, HW, thresholds, T, table, count, scores, ST);
 }
 
+// ---- object-based verification (verify_objects.hip) --------------------------------------------------------------------
+int sbgm_object_labels(const float* fields, const void* mask, int mask_is_u8, int N, int Nm, int H, int W, float threshold,
+                       int connectivity, int* labels, int* status, void* stream) {
+    return sbgm_launch_object_labels(fields, mask, mask_is_u8, N, Nm, H, W, threshold, connectivity, labels, status, ST);
+}
+int64_t sbgm_object_scores_workspace_bytes(int N, int H, int W, int T, int64_t max_bytes) {
+    return sbgm_object_chunk_bytes(N, H, W, T, max_bytes);
+}
+int sbgm_object_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
+                       const float* thresholds, int n_fixed, int has_relative, double rel_factor, double rel_quantile, float rel_wet,
+                       int connectivity, float* threshold, int64_t* n_objects, int64_t* area, double* mass, double* V, double* r,
+                       double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A, double* L1, double* L,
+                       int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    return sbgm_launch_object_scores(gen, obs, mask, mask_is_u8, N, No, Nm, H, W, thresholds, n_fixed, has_relative, rel_factor,
+                                     rel_quantile, rel_wet, connectivity, threshold, n_objects, area, mass, V, r, domain_mean, com, valid,
+                                     S, L2, A, L1, L, area_hist, status, workspace, workspace_bytes, ST);
+}
+
 // ---- training path: backward entry points ---------------------------------------------------------------------------
 int sbgm_conv_pack_weight_dgrad(const float* w_oihw, float* packed, int Cout, int Cin, int KH, int KW, void* stream) {
     // operator of the data gradient: Cout' = Cin, Cin' = Cout (padded to 16), taps flipped

@@ -446,6 +446,17 @@ int sbgm_launch_neighbourhood_scores(const float* gen, const float* obs, const v
 int sbgm_launch_exceedance_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
                                   const float* thresholds, int T, int64_t* table, int64_t* count, double* scores, hipStream_t st);
 
+// ---- verify_objects.hip (connected objects and SAL ingredients; thresholds is a host array) ------------------------------
+int sbgm_launch_object_labels(const float* fields, const void* mask, int mask_is_u8, int N, int Nm, int H, int W, float threshold,
+                              int connectivity, int* labels, int* status, hipStream_t st);
+int64_t sbgm_object_chunk_bytes(int N, int H, int W, int T, int64_t max_bytes);
+int sbgm_launch_object_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
+                              const float* thresholds, int n_fixed, int has_relative, double rel_factor, double rel_quantile,
+                              float rel_wet, int connectivity, float* threshold, int64_t* n_objects, int64_t* area, double* mass,
+                              double* V, double* r, double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A,
+                              double* L1, double* L, int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes,
+                              hipStream_t st);
+
 // ---- backward.hip (training path) ------------------------------------------------------------------------------------
 int sbgm_launch_conv_wgrad(const float* dy, const float* x, float* dw_oihw, float* dwp_ws, int B, int H, int W, int Cs, int Cin,
                            int Cout, int KH, int KW, int S, int PAD, hipStream_t st,

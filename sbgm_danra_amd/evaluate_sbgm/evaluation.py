@@ -2,9 +2,9 @@
 files `SampleGenerator` writes, moves them to the GPU once, and computes every statistic with the verification kernels
 (csrc/verify.hip and csrc/verify_spatial.hip via `..verification`): the reference's pixel, spatial and daily statistics plus
 ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra and, on request, neighbourhood scores
-(Fractions Skill Score), threshold-exceedance scores (Brier, reliability table, ROC area) and ensemble products (mean, spread,
-envelope, quantile and exceedance-probability maps with the coverage of each quantile map).  Only scalars, maps and
-histograms come back to the host.
+(Fractions Skill Score), threshold-exceedance scores (Brier, reliability table, ROC area), ensemble products (mean, spread,
+envelope, quantile and exceedance-probability maps with the coverage of each quantile map) and object-based scores (connected
+objects and SAL: structure, amplitude, location).  Only scalars, maps, per-field arrays and histograms come back to the host.
 Plots are out of scope: the plotting keys are accepted and logged as skipped.
 
 Files are found by name: `gen_samples_*`, `eval_samples_*` and `lsm_samples_*` with the suffixes `multi_n_<B>`, `single`,
@@ -137,6 +137,45 @@ def ensemble_products_config(cfg):
     if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) for t in thresholds):
         raise ValueError(f"evaluation.ensemble_products.thresholds must be finite numbers, got {list(thresholds)}")
     return [float(q) for q in quantiles], [float(t) for t in thresholds]
+
+
+def object_scores_config(cfg):
+    """(thresholds, relative, connectivity) of the optional evaluation.object_scores section — `thresholds`: up to 16 finite
+    numbers in the units the generated files hold (may be empty or absent when `relative` is given); `relative`: None or
+    {factor, quantile, wet}, Wernli's R* = factor * R^quantile over the values >= wet; `connectivity`: 4 or 8 (default 8) — or
+    None when the section is absent"""
+    sec = cfg["evaluation"].get("object_scores")
+    if sec is None:
+        return None
+    thresholds, relative, connectivity = sec.get("thresholds") or [], sec.get("relative"), sec.get("connectivity", 8)
+    if not isinstance(thresholds, (list, tuple)) or not (thresholds or relative is not None):
+        raise ValueError("evaluation.object_scores needs a list 'thresholds', a 'relative' section, or both")
+    if len(thresholds) > 16:
+        raise ValueError(f"evaluation.object_scores: at most 16 thresholds, got {len(thresholds)}")
+    if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) for t in thresholds):
+        raise ValueError(f"evaluation.object_scores.thresholds must be finite numbers, got {list(thresholds)}")
+    if relative is not None:
+        if not hasattr(relative, "keys") or set(relative.keys()) != {"factor", "quantile", "wet"}:
+            raise ValueError("evaluation.object_scores.relative needs exactly the keys 'factor', 'quantile' and 'wet'")
+        vals = {k: relative[k] for k in ("factor", "quantile", "wet")}
+        if any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in vals.values()):
+            raise ValueError(f"evaluation.object_scores.relative: factor, quantile and wet must be finite numbers, got {vals}")
+        if not 0.0 <= vals["quantile"] <= 1.0:
+            raise ValueError(f"evaluation.object_scores.relative.quantile must lie in [0, 1], got {vals['quantile']}")
+        relative = {k: float(v) for k, v in vals.items()}
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"evaluation.object_scores.connectivity must be 4 or 8, got {connectivity!r}")
+    return [float(t) for t in thresholds], relative, int(connectivity)
+
+
+def _nan_quartiles(a):
+    """(median, 25th, 75th percentile, NaN count) of a 1-D array, NaNs ignored; NaN quartiles when nothing is left"""
+    a = np.asarray(a, np.float64)
+    good = a[~np.isnan(a)]
+    if good.size == 0:
+        return float("nan"), float("nan"), float("nan"), int(a.size)
+    q25, q50, q75 = np.percentile(good, [25, 50, 75])
+    return float(q50), float(q25), float(q75), int(a.size - good.size)
 
 
 class Evaluation:
@@ -349,6 +388,48 @@ class Evaluation:
                              "continuous ensemble where q (M - 1) is an integer"}
         self.metrics["product_stats"] = out
         self.fields.update({f"products_{k}": v for k, v in res.items()})
+        return dict(res, metrics=out)
+
+    def object_statistics(self, thresholds=None, relative=None, connectivity=None):
+        """SAL (structure, amplitude, location; Wernli et al. 2008) of the generated fields against their truth, from the
+        connected objects of both at each threshold.  The metrics entry `objects` holds, per threshold, the median and the
+        quartiles over the fields of S, A and L (NaNs ignored, and counted), the object counts of both sides and the
+        area histogram; the per-field arrays go to the fields file.  Arguments default to the evaluation.object_scores
+        section.  Meant for non-negative fields such as precipitation."""
+        if thresholds is None and relative is None:
+            sec = object_scores_config(self.cfg)
+            if sec is None:
+                raise ValueError("no thresholds / relative given and the config has no evaluation.object_scores section")
+            thresholds, relative = sec[0], sec[1]
+            connectivity = sec[2] if connectivity is None else connectivity
+        thresholds = [float(t) for t in (thresholds or [])]
+        connectivity = 8 if connectivity is None else connectivity
+        r = V.object_scores(self.gen_imgs, self.eval_imgs, thresholds, relative=relative, mask=self.mask, connectivity=connectivity)
+        status = int(r["status"])
+        if status != 0:
+            raise RuntimeError(f"object_scores: the labelling kernels reported status {status} (a union-find walk hit its step cap); "
+                               f"the object statistics of {self.label} are not usable")
+        res = {k: r[k].cpu().numpy() for k in V.OBJECT_KEYS if k != "status"}
+        names = [f"{t:g}" for t in thresholds] + (["relative"] if relative is not None else [])
+        per_thr = []
+        a50, a25, a75, a_nan = _nan_quartiles(res["A"])
+        for t, name in enumerate(names):
+            row = {"threshold": name, "A": {"median": a50, "p25": a25, "p75": a75, "nan": a_nan}}
+            for key in ("S", "L"):
+                q50, q25, q75, n_nan = _nan_quartiles(res[key][:, t])
+                row[key] = {"median": q50, "p25": q25, "p75": q75, "nan": n_nan}
+            row["n_objects_gen"], row["n_objects_obs"] = (int(v) for v in res["n_objects"][:, :, t].sum(axis=1))
+            row["area_hist_gen"], row["area_hist_obs"] = (res["area_hist"][side, t].tolist() for side in (0, 1))
+            per_thr.append(row)
+        out = {"thresholds": thresholds, "relative": relative, "connectivity": int(connectivity), "n_fields": self.n_samples,
+               "valid": int(res["valid"].sum()), "per_threshold": per_thr,
+               "definition": "objects: connected components of the valid pixels with value >= threshold; S = (V_gen - V_obs) / "
+                             "(0.5 (V_gen + V_obs)), V = sum_n R_n (R_n / Rmax_n) / sum_n R_n; A = (D_gen - D_obs) / (0.5 (D_gen + "
+                             "D_obs)), D the domain mean; L = L1 + L2, L1 = |x_gen - x_obs| / d, L2 = 2 |r_gen - r_obs| / d, r the "
+                             "mass-weighted mean distance of the objects' centres from the field's centre x, d the domain diagonal; "
+                             "area_hist: objects with floor(log2 area) = bin"}
+        self.metrics["objects"] = out
+        self.fields.update({f"objects_{k}": v for k, v in res.items()})
         return dict(res, metrics=out)
 
     def save(self):

@@ -4,7 +4,8 @@ evaluation.eval_stat_methods (default ['pixel_stats', 'spatial_stats'], as in th
 `<type>[_rank<r>]_metrics.json` / `_fields.npz`.  Plotting keys are accepted and logged as skipped.  An
 `evaluation.spatial_scores` section (thresholds, scales) adds the neighbourhood scores for every type and the exceedance
 scores for `repeated`; an `evaluation.ensemble_products` section (quantiles, thresholds) adds the ensemble products for
-`repeated`; without a section its statistics do not run and the output files hold what they always held."""
+`repeated`; an `evaluation.object_scores` section (thresholds, relative, connectivity) adds the object-based scores (SAL) for
+every type; without a section its statistics do not run and the output files hold what they always held."""
 from __future__ import annotations
 
 import os
@@ -14,13 +15,14 @@ import torch
 
 from ..training_utils import setup_logger
 from ..utils import get_model_string
-from .evaluation import GEN_TYPES, Evaluation, ensemble_products_config, sample_units, spatial_scores_config
+from .evaluation import GEN_TYPES, Evaluation, ensemble_products_config, object_scores_config, sample_units, spatial_scores_config
 
 METHODS = {"pixel_stats": "full_pixel_statistics", "spatial_stats": "spatial_statistics", "daily_stats": "daily_statistics",
            "ensemble_stats": "ensemble_statistics", "spectral_stats": "spectral_statistics"}
 SPATIAL_METHODS = {"neighbourhood_stats": "neighbourhood_statistics", "exceedance_stats": "exceedance_statistics"}
 PRODUCT_METHODS = {"product_stats": "product_statistics"}
-SECTION_METHODS = {**SPATIAL_METHODS, **PRODUCT_METHODS}          # run without arguments: they read their section
+OBJECT_METHODS = {"object_stats": "object_statistics"}
+SECTION_METHODS = {**SPATIAL_METHODS, **PRODUCT_METHODS, **OBJECT_METHODS}      # run without arguments: they read their section
 PLOT_KEYS = ("plot_examples", "save_figs", "show_plots", "show_figs", "mask_plots", "plot_w_cond", "plot_w_lsm")
 
 
@@ -44,12 +46,15 @@ def eval_stat_methods(cfg):
 def unit_statistics(cfg, gen_type):
     """the statistics evaluate mode runs for one generation type, in order: evaluation.eval_stat_methods, then — only with an
     evaluation.spatial_scores section — 'neighbourhood_stats' and, for 'repeated', 'exceedance_stats'; then — only with an
-    evaluation.ensemble_products section, for 'repeated' — 'product_stats'"""
+    evaluation.ensemble_products section, for 'repeated' — 'product_stats'; then — only with an evaluation.object_scores
+    section — 'object_stats'"""
     stats = eval_stat_methods(cfg)
     if spatial_scores_config(cfg) is not None:
         stats += ["neighbourhood_stats"] + (["exceedance_stats"] if gen_type == "repeated" else [])
     if ensemble_products_config(cfg) is not None and gen_type == "repeated":
         stats += ["product_stats"]
+    if object_scores_config(cfg) is not None:
+        stats += ["object_stats"]
     return stats
 
 

@@ -1,7 +1,8 @@
-"""Device-tensor wrappers of the verification kernels (csrc/verify.hip, csrc/verify_spatial.hip and csrc/verify_products.hip,
-DESIGN.md §11): error statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power
-spectra, neighbourhood scores (Fractions Skill Score), threshold-exceedance scores (Brier, reliability table, ROC area) and
-ensemble products (per-pixel mean, spread, envelope, quantile and exceedance-probability maps).  Every function takes tensors on
+"""Device-tensor wrappers of the verification kernels (csrc/verify.hip, csrc/verify_spatial.hip, csrc/verify_products.hip and
+csrc/verify_objects.hip): error statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill),
+radially averaged power spectra, neighbourhood scores (Fractions Skill Score), threshold-exceedance scores (Brier, reliability
+table, ROC area), ensemble products (per-pixel mean, spread, envelope, quantile and exceedance-probability maps) and
+object-based scores (connected objects and SAL: structure, amplitude, location).  Every function takes tensors on
 the ROCm device and returns tensors on the device; arguments and shapes are checked before any launch and nothing is copied
 to the host.  A pixel is valid when gen (every member) and obs are not NaN and the mask admits it (uint8/bool != 0, or float
 > 0.5); every statistic uses the valid pixels only."""
@@ -24,6 +25,9 @@ MAX_EXCEEDANCE_MEMBERS = 4095
 MAX_PRODUCT_QUANTILES = 16                       # include/sbgm_hip.h: SBGM_PRODUCTS_MAX_QUANTILES; thresholds: MAX_THRESHOLDS
 MAX_PRODUCT_MEMBERS = 4095
 DEFAULT_WORKSPACE_BYTES = 256 << 20
+OBJECT_KEYS = ("threshold", "n_objects", "area", "mass", "V", "r", "domain_mean", "com", "valid", "S", "L2", "A", "L1", "L",
+               "area_hist", "status")               # the argument order of sbgm_object_scores
+OBJECT_AREA_BINS = 21                            # include/sbgm_hip.h: SBGM_OBJECTS_AREA_BINS; fixed thresholds: MAX_THRESHOLDS
 
 
 def _rows(t, name, HW, allowed):
@@ -315,3 +319,106 @@ def ensemble_products(ens, quantiles=(), thresholds=(), mask=None):
                                            N.stream()))
     return dict(mean=mean.view(shape), std=std.view(shape), min=vmin.view(shape), max=vmax.view(shape),
                 quantiles=quant.view(Q, *shape), exceed_prob=exceed.view(T, *shape), count=count[0])
+
+
+def _connectivity(connectivity, name):
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"{name}: connectivity must be 4 or 8, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _object_shape(x, name, what):
+    if x.dim() != 3:
+        raise ValueError(f"{what}: expected [N, H, W], got {tuple(x.shape)}")
+    n, H, W = x.shape
+    if not (2 <= H <= MAX_FIELD_SIDE and 2 <= W <= MAX_FIELD_SIDE) or H * W > MAX_FIELD_PIXELS:
+        raise ValueError(f"{name}: field size {H}x{W}; sides must be 2..{MAX_FIELD_SIDE} and H*W <= 2^20")
+    if not 1 <= n <= 65535:
+        raise ValueError(f"{name}: {n} fields; need 1..65535")
+    return n, H, W
+
+
+def _relative(relative, name):
+    """(factor, quantile, wet) of a relative threshold R* = factor * R^quantile over the values >= wet"""
+    if not isinstance(relative, dict) or set(relative) != {"factor", "quantile", "wet"}:
+        raise ValueError(f"{name}: relative must be a dict with the keys factor, quantile and wet, got {relative!r}")
+    vals = [relative[k] for k in ("factor", "quantile", "wet")]
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in vals):
+        raise ValueError(f"{name}: relative.factor, .quantile and .wet must be finite numbers, got {relative!r}")
+    factor, quantile, wet = (float(v) for v in vals)
+    if not 0.0 <= quantile <= 1.0 or not math.isfinite(C.c_float(wet).value):
+        raise ValueError(f"{name}: relative.quantile must lie in [0, 1] and relative.wet be finite in fp32, got {relative!r}")
+    return factor, quantile, wet
+
+
+def object_labels(fields, threshold, mask=None, connectivity=8, return_status=False):
+    """connected objects of fields [N,H,W] (sides 2..2048, H*W <= 2^20), optional mask [Nm,H,W] (Nm in {1, N}): an object pixel
+    is a valid pixel (not NaN, admitted by the mask) with `v >= threshold` in fp32, objects are its 4- or 8-connected
+    (`connectivity`) components.  Returns int32 [N,H,W] canonical labels: 1 + the smallest linear index row * W + col among the
+    pixels of the object, 0 for background.  At most 65535 fields per call.  With return_status also the int32 device scalar
+    that is non-zero only if a union-find walk of the kernel hit its step cap (a defect, never an input's fault; the labels are
+    then not to be used).  Nothing is copied to the host here, so by default that status is NOT checked: a caller who needs
+    to know must pass return_status=True and look at it."""
+    conn = _connectivity(connectivity, "object_labels")
+    thr = _thresholds([threshold], "object_labels")[0]
+    n, H, W = _object_shape(fields, "object_labels", "fields")
+    _shape_rows(mask, "mask", (H, W), (1, n))
+    x = _fields(fields, "fields")
+    m, u8, nm = _mask(mask, H * W, (1, n))
+    labels = torch.empty(n, H, W, dtype=torch.int32, device=x.device)
+    status = torch.empty(1, dtype=torch.int32, device=x.device)
+    N.check(N.lib().sbgm_object_labels(x.data_ptr(), N.ptr(m), u8, n, nm, H, W, thr, conn, labels.data_ptr(), status.data_ptr(),
+                                       N.stream()))
+    return (labels, status[0]) if return_status else labels
+
+
+def object_scores(gen, obs, thresholds=(), relative=None, mask=None, connectivity=8, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+    """SAL (structure, amplitude, location; Wernli et al. 2008) of gen [N,H,W] against obs [No,H,W] (No in {1, N}), optional mask
+    [Nm,H,W] (Nm in {1, N}), N <= 65535; meant for non-negative fields such as precipitation (not checked).  For a side F in {gen, obs} and a
+    threshold, objects are the 4- or 8-connected components of the valid pixels with `F >= thr` in fp32.  `thresholds`: up to 16
+    finite values, the same on both sides; `relative` = {factor, quantile, wet} adds, as the last threshold index, Wernli's
+    R* = factor * R^quantile per side and field: thr = (float)(factor * q), q the type-7 quantile (as ensemble_products defines it)
+    of that side's valid values >= wet, NaN (no objects) where there is none.  With T thresholds in all, per object n the area
+    a_n, mass R_n = sum F, peak Rmax_n and centre x_n = sum F (row, col) / R_n; per field D = mean of F and x = F-weighted centre
+    over the valid pixels; d = sqrt((H-1)^2 + (W-1)^2).  Returns device tensors, index 0 of a leading [2] being gen and 1 obs:
+    `threshold` fp32 [2,N,T]; `n_objects`, `area` int64 [2,N,T]; `mass` = sum_n R_n, `V` = sum_n R_n (R_n / Rmax_n) / mass,
+    `r` = sum_n R_n |x - x_n| / mass fp64 [2,N,T]; `domain_mean` fp64 [2,N]; `com` fp64 [2,N,2]; `valid` int64 [N];
+    `S` = (V_g - V_o) / (0.5 (V_g + V_o)), `L2` = 2 |r_g - r_o| / d, `L` = L1 + L2 fp64 [N,T]; `A` = (D_g - D_o) / (0.5 (D_g + D_o)),
+    `L1` = |x_g - x_o| / d fp64 [N] (NaN where a denominator is 0; S, L2 where a side has no object; A, L1 where there is no valid
+    pixel or a side sums to 0); `area_hist` int64 [2,T,21], objects with floor(log2 a_n) = b over all fields; `status` int32
+    scalar, 0 unless a union-find walk hit its step cap.  The (field, threshold) pairs are processed in chunks whose workspace
+    stays within `max_workspace_bytes` (at least one pair); the result does not depend on the chunking, and two calls give
+    bit-equal results."""
+    conn = _connectivity(connectivity, "object_scores")
+    fixed = list(thresholds)
+    if len(fixed) > MAX_THRESHOLDS:
+        raise ValueError(f"object_scores: {len(fixed)} thresholds; at most {MAX_THRESHOLDS}")
+    thr = _thresholds(fixed, "object_scores") if fixed else None
+    rel = None if relative is None else _relative(relative, "object_scores")
+    T = len(fixed) + (rel is not None)
+    if T < 1:
+        raise ValueError("object_scores: no threshold given (thresholds is empty and relative is None)")
+    n, H, W = _object_shape(gen, "object_scores", "gen")
+    _shape_rows(obs, "obs", (H, W), (1, n))
+    _shape_rows(mask, "mask", (H, W), (1, n))
+    g = _fields(gen, "gen")
+    o = _fields(obs, "obs")
+    if o.device != g.device:
+        raise ValueError("gen and obs must be on the same device")
+    m, u8, nm = _mask(mask, H * W, (1, n))
+    dev = g.device
+    i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
+    out = dict(threshold=torch.empty(2, n, T, device=dev), n_objects=torch.empty(2, n, T, **i64), area=torch.empty(2, n, T, **i64),
+               mass=torch.empty(2, n, T, **f64), V=torch.empty(2, n, T, **f64), r=torch.empty(2, n, T, **f64),
+               domain_mean=torch.empty(2, n, **f64), com=torch.empty(2, n, 2, **f64), valid=torch.empty(n, **i64),
+               S=torch.empty(n, T, **f64), L2=torch.empty(n, T, **f64), A=torch.empty(n, **f64), L1=torch.empty(n, **f64),
+               L=torch.empty(n, T, **f64), area_hist=torch.empty(2, T, OBJECT_AREA_BINS, **i64),
+               status=torch.empty(1, dtype=torch.int32, device=dev))
+    nbytes = N.lib().sbgm_object_scores_workspace_bytes(n, H, W, T, max(int(max_workspace_bytes), 0))
+    ws = _ws(nbytes, dev)
+    factor, quantile, wet = rel if rel is not None else (0.0, 0.0, 0.0)
+    N.check(N.lib().sbgm_object_scores(g.data_ptr(), o.data_ptr(), N.ptr(m), u8, n, o.shape[0], nm, H, W, thr, len(fixed),
+                                       int(rel is not None), factor, quantile, wet, conn, *(out[k].data_ptr() for k in OBJECT_KEYS),
+                                       ws.data_ptr(), nbytes, N.stream()))
+    out["status"] = out["status"][0]
+    return out
