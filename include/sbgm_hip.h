@@ -874,6 +874,42 @@ int sbgm_object_scores(const float* gen, const float* obs, const void* mask, int
                        double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A, double* L1, double* L,
                        int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- multivariate ensemble scores (verify_multivariate.hip) -----------------------------------------
+ * Members ens [M][HW] (2 <= M <= 4095, HW <= 2^20) against the truth obs [HW], mask [HW] or NULL.  A pixel is valid when every
+ * member and the truth are not NaN there and the mask admits it; an invalid pixel contributes nothing.  Both calls keep the
+ * valid flags, the partial sums and nothing else in `workspace` (size from the _workspace_bytes query, which returns 0 for
+ * arguments the call would reject), use no floating-point atomics and sum in an order that depends on the arguments alone:
+ * two calls give bit-equal outputs.
+ *
+ * sbgm_energy_scores: dist2 fp64 [M+1][M+1], the squared Euclidean distances over the valid pixels between all members and
+ * the truth (row / column M): every fp32 value converted to fp64 once, then d = a - b, sum = fma(d, d, sum) — the difference
+ * form, so a duplicated member gives an exact 0.  Symmetric bit for bit with a zero diagonal.  scores fp64 [6]: count (valid
+ * pixels); es_fair = (1/M) sum_m |x_m - y| - 1/(2 M (M-1)) sum_{m != k} |x_m - x_k|; es_standard, the same with 1/(2 M^2);
+ * mean_dist_obs = (1/M) sum_m |x_m - y|; mean_dist_pair = 1/(M (M-1)) sum_{m != k} |x_m - x_k|; min_dist_pair = min_{m != k}
+ * |x_m - x_k|.  Every norm is |a - b| = sqrt(dist2 / count), an RMS distance.  count = 0 gives dist2 = 0 and NaN scores.
+ *
+ * sbgm_variogram_scores (Scheuerer & Hamill 2015): the pixel pairs (i, j = i + (dy, dx)) with (dy, dx) in the half-plane
+ * (dy > 0, or dy == 0 and dx > 0) and dy^2 + dx^2 <= radius^2, radius 1..8, in the order sbgm_variogram_offsets lists them
+ * (dy ascending, then dx ascending; at most 98), both pixels valid and inside the field.  For such a pair g_ens = (1/M) sum_m
+ * |x_i^m - x_j^m|^p and g_obs = |y_i - y_j|^p — the difference and its power (p = order: 0.5, 1 or 2, nothing else) in fp32,
+ * the sum over the members and everything after it in fp64 — and term = (g_obs - g_ens)^2.  With w = 1, or 1 / sqrt(dy^2 +
+ * dx^2) (rounded to fp32) when inverse_distance != 0: vs_map fp32 [H][W] = sum of w term over the pairs a pixel owns (its
+ * half-plane neighbours), NaN at an invalid pixel; gamma_ens, gamma_obs fp64 [n_off] = mean of g_ens, g_obs over the pairs of
+ * an offset (NaN without pairs); pairs int64 [n_off]; scores fp64 [4]: vs = sum w term / sum w, n_pairs, sum_w (both sums
+ * over the counted pairs), vs_unweighted = sum term / n_pairs. */
+#define SBGM_VARIOGRAM_MAX_OFFSETS 98
+int64_t sbgm_energy_scores_workspace_bytes(int M, int64_t HW);
+int sbgm_energy_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
+                       double* dist2 /* [M+1][M+1] */, double* scores /* [6] */, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+/* HOST arrays: *n_offsets and dydx [n_offsets][2] (room for SBGM_VARIOGRAM_MAX_OFFSETS pairs) */
+int sbgm_variogram_offsets(int radius, int* n_offsets, int* dydx);
+int64_t sbgm_variogram_scores_workspace_bytes(int M, int H, int W, int radius);
+int sbgm_variogram_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int H, int W, int radius,
+                          double order, int inverse_distance, float* vs_map /* [H][W] */, double* gamma_ens, double* gamma_obs,
+                          int64_t* pairs /* [n_off] each */, double* scores /* [4] */, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
 /* ---- before the network ------------------------------------------------------------------------
  * Batch-level condition assembly: channel concatenation of the sorted *_lr fields (utils.py:441-447), classifier-free-
  * guidance condition dropout (data_modules.py:957-983: LR fields -> 0, class label -> NULL token 0) and the value||mask

@@ -250,9 +250,14 @@ SIGNATURES = {
     "sbgm_object_labels": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "sbgm_object_scores_workspace_bytes": (_i64, [_i, _i, _i, _i, _i64]),
     "sbgm_object_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _i, _i, _d, _d, _f, _i] + [_vp] * 17 + [_i64, _vp]),
+    "sbgm_energy_scores_workspace_bytes": (_i64, [_i, _i64]),
+    "sbgm_energy_scores": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sbgm_variogram_offsets": (_i, [_i, C.POINTER(_i), C.POINTER(_i)]),
+    "sbgm_variogram_scores_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "sbgm_variogram_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i] + [_vp] * 6 + [_i64, _vp]),
 }
 
-ABI_VERSION = 9         # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 10        # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

@@ -3,8 +3,8 @@ files `SampleGenerator` writes, moves them to the GPU once, and computes every s
 (csrc/verify.hip and csrc/verify_spatial.hip via `..verification`): the reference's pixel, spatial and daily statistics plus
 ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra and, on request, neighbourhood scores
 (Fractions Skill Score), threshold-exceedance scores (Brier, reliability table, ROC area), ensemble products (mean, spread,
-envelope, quantile and exceedance-probability maps with the coverage of each quantile map) and object-based scores (connected
-objects and SAL: structure, amplitude, location).  Only scalars, maps, per-field arrays and histograms come back to the host.
+envelope, quantile and exceedance-probability maps with the coverage of each quantile map), object-based scores (connected
+objects and SAL: structure, amplitude, location) and multivariate ensemble scores (energy score, variogram score).  Only scalars, maps, per-field arrays and histograms come back to the host.
 Plots are out of scope: the plotting keys are accepted and logged as skipped.
 
 Files are found by name: `gen_samples_*`, `eval_samples_*` and `lsm_samples_*` with the suffixes `multi_n_<B>`, `single`,
@@ -166,6 +166,35 @@ def object_scores_config(cfg):
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
         raise ValueError(f"evaluation.object_scores.connectivity must be 4 or 8, got {connectivity!r}")
     return [float(t) for t in thresholds], relative, int(connectivity)
+
+
+def multivariate_scores_config(cfg):
+    """(energy, variogram) of the optional evaluation.multivariate_scores section — `energy`: bool (default false);
+    `variogram`: None or {radius: 1..8 (default 4), order: 0.5, 1 or 2 (default 0.5), weights: 'inverse_distance' (default) or
+    'unit'}; at least one of the two must be asked for — or None when the section is absent"""
+    sec = cfg["evaluation"].get("multivariate_scores")
+    if sec is None:
+        return None
+    if not hasattr(sec, "keys") or not set(sec.keys()) <= {"energy", "variogram"}:
+        raise ValueError("evaluation.multivariate_scores takes the keys 'energy' and 'variogram' only")
+    energy, variogram = sec.get("energy", False), sec.get("variogram")
+    if not isinstance(energy, bool):
+        raise ValueError(f"evaluation.multivariate_scores.energy must be true or false, got {energy!r}")
+    if variogram is not None:
+        if not hasattr(variogram, "keys") or not set(variogram.keys()) <= {"radius", "order", "weights"}:
+            raise ValueError("evaluation.multivariate_scores.variogram takes the keys 'radius', 'order' and 'weights' only")
+        radius, order, weights = variogram.get("radius", 4), variogram.get("order", 0.5), variogram.get("weights", "inverse_distance")
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= V.MAX_VARIOGRAM_RADIUS:
+            raise ValueError(f"evaluation.multivariate_scores.variogram.radius must be an integer in 1..{V.MAX_VARIOGRAM_RADIUS}, "
+                             f"got {radius!r}")
+        if isinstance(order, bool) or not isinstance(order, (int, float)) or float(order) not in V.VARIOGRAM_ORDERS:
+            raise ValueError(f"evaluation.multivariate_scores.variogram.order must be one of {V.VARIOGRAM_ORDERS}, got {order!r}")
+        if weights not in V.VARIOGRAM_WEIGHTS:
+            raise ValueError(f"evaluation.multivariate_scores.variogram.weights must be one of {V.VARIOGRAM_WEIGHTS}, got {weights!r}")
+        variogram = {"radius": int(radius), "order": float(order), "weights": str(weights)}
+    if not energy and variogram is None:
+        raise ValueError("evaluation.multivariate_scores asks for nothing: set 'energy: true', give a 'variogram' section, or both")
+    return energy, variogram
 
 
 def _nan_quartiles(a):
@@ -432,8 +461,49 @@ class Evaluation:
         self.fields.update({f"objects_{k}": v for k, v in res.items()})
         return dict(res, metrics=out)
 
+    def multivariate_statistics(self, energy=None, variogram=None):
+        """energy score and variogram score of the `repeated` samples as an ensemble against their one truth: the scalar
+        scores go to the metrics entry `multivariate`; the distance matrix `energy_dist2` and the variogram's `vs_map`,
+        `gamma_ens`, `gamma_obs`, `offsets` and `pairs` go to a file of their own, <label>_multivariate.npz, which save() writes
+        beside the fields file.  Arguments default to the evaluation.multivariate_scores section."""
+        if self.generated_sample_type != "repeated":
+            raise ValueError(f"multivariate_statistics needs 'repeated' samples (an ensemble for one condition), not "
+                             f"'{self.generated_sample_type}'")
+        if self.n_samples < 2:
+            raise ValueError(f"multivariate_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        if energy is None and variogram is None:
+            sec = multivariate_scores_config(self.cfg)
+            if sec is None:
+                raise ValueError("no energy / variogram given and the config has no evaluation.multivariate_scores section")
+            energy, variogram = sec
+        mask = None if self.mask is None else self.mask[0]
+        out, res = {"M": self.n_samples}, {}
+        if energy:
+            r = V.energy_scores(self.gen_imgs, self.eval_imgs[0], mask=mask)
+            s = r["scores"].cpu().numpy()
+            out["energy"] = dict(zip(V.ENERGY_KEYS, (float(v) for v in s)))
+            out["energy"]["count"] = int(s[0])
+            out["energy"]["definition"] = ("es_fair = (1/M) sum_m |x_m - y| - 1/(2 M (M-1)) sum_{m != k} |x_m - x_k|; es_standard "
+                                           "with 1/(2 M^2); |a - b| = sqrt(sum over the valid pixels of (a - b)^2 / count)")
+            res["energy_dist2"] = r["dist2"].cpu().numpy()
+        if variogram is not None:
+            r = V.variogram_scores(self.gen_imgs, self.eval_imgs[0], mask=mask, **variogram)
+            s = r["scores"].cpu().numpy()
+            out["variogram"] = dict(variogram, **dict(zip(V.VARIOGRAM_KEYS, (float(v) for v in s))))
+            out["variogram"]["n_pairs"] = int(s[1])
+            out["variogram"]["definition"] = ("vs = sum w (g_obs - g_ens)^2 / sum w over the pixel pairs with offset in the half "
+                                              "disc of the radius; g_ens = (1/M) sum_m |x_i^m - x_j^m|^order, g_obs = |y_i - "
+                                              "y_j|^order; w = 1 / distance or 1")
+            res.update({f"variogram_{k}": r[k].cpu().numpy() for k in ("vs_map", "gamma_ens", "gamma_obs", "offsets", "pairs")})
+        self.metrics["multivariate"] = out
+        self.multivariate_fields = res
+        return dict(res, metrics=out)
+
     def save(self):
-        """<label>_metrics.json and <label>_fields.npz under the statistics directory; returns their paths"""
+        """<label>_metrics.json and <label>_fields.npz under the statistics directory; returns their paths.  After
+        multivariate_statistics also <label>_multivariate.npz."""
+        if getattr(self, "multivariate_fields", None):
+            np.savez(os.path.join(self.evaluation_stats_path, f"{self.label}_multivariate.npz"), **self.multivariate_fields)
         mpath = os.path.join(self.evaluation_stats_path, f"{self.label}_metrics.json")
         fpath = os.path.join(self.evaluation_stats_path, f"{self.label}_fields.npz")
         with open(mpath, "w") as f:

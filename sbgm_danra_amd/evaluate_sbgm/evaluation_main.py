@@ -5,7 +5,9 @@ evaluation.eval_stat_methods (default ['pixel_stats', 'spatial_stats'], as in th
 `evaluation.spatial_scores` section (thresholds, scales) adds the neighbourhood scores for every type and the exceedance
 scores for `repeated`; an `evaluation.ensemble_products` section (quantiles, thresholds) adds the ensemble products for
 `repeated`; an `evaluation.object_scores` section (thresholds, relative, connectivity) adds the object-based scores (SAL) for
-every type; without a section its statistics do not run and the output files hold what they always held."""
+every type; an `evaluation.multivariate_scores` section (energy, variogram) adds the energy and variogram scores for
+`repeated` (their arrays go to `<type>[_rank<r>]_multivariate.npz`; for another type the section is logged as skipped); without
+a section its statistics do not run and the output files hold what they always held."""
 from __future__ import annotations
 
 import os
@@ -15,14 +17,17 @@ import torch
 
 from ..training_utils import setup_logger
 from ..utils import get_model_string
-from .evaluation import GEN_TYPES, Evaluation, ensemble_products_config, object_scores_config, sample_units, spatial_scores_config
+from .evaluation import (GEN_TYPES, Evaluation, ensemble_products_config, multivariate_scores_config, object_scores_config, sample_units,
+                         spatial_scores_config)
 
 METHODS = {"pixel_stats": "full_pixel_statistics", "spatial_stats": "spatial_statistics", "daily_stats": "daily_statistics",
            "ensemble_stats": "ensemble_statistics", "spectral_stats": "spectral_statistics"}
 SPATIAL_METHODS = {"neighbourhood_stats": "neighbourhood_statistics", "exceedance_stats": "exceedance_statistics"}
 PRODUCT_METHODS = {"product_stats": "product_statistics"}
 OBJECT_METHODS = {"object_stats": "object_statistics"}
-SECTION_METHODS = {**SPATIAL_METHODS, **PRODUCT_METHODS, **OBJECT_METHODS}      # run without arguments: they read their section
+MULTIVARIATE_METHODS = {"multivariate_stats": "multivariate_statistics"}
+# run without arguments: they read their section
+SECTION_METHODS = {**SPATIAL_METHODS, **PRODUCT_METHODS, **OBJECT_METHODS, **MULTIVARIATE_METHODS}
 PLOT_KEYS = ("plot_examples", "save_figs", "show_plots", "show_figs", "mask_plots", "plot_w_cond", "plot_w_lsm")
 
 
@@ -47,7 +52,8 @@ def unit_statistics(cfg, gen_type):
     """the statistics evaluate mode runs for one generation type, in order: evaluation.eval_stat_methods, then — only with an
     evaluation.spatial_scores section — 'neighbourhood_stats' and, for 'repeated', 'exceedance_stats'; then — only with an
     evaluation.ensemble_products section, for 'repeated' — 'product_stats'; then — only with an evaluation.object_scores
-    section — 'object_stats'"""
+    section — 'object_stats'; then — only with an evaluation.multivariate_scores section, for 'repeated' —
+    'multivariate_stats'"""
     stats = eval_stat_methods(cfg)
     if spatial_scores_config(cfg) is not None:
         stats += ["neighbourhood_stats"] + (["exceedance_stats"] if gen_type == "repeated" else [])
@@ -55,6 +61,8 @@ def unit_statistics(cfg, gen_type):
         stats += ["product_stats"]
     if object_scores_config(cfg) is not None:
         stats += ["object_stats"]
+    if multivariate_scores_config(cfg) is not None and gen_type == "repeated":
+        stats += ["multivariate_stats"]
     return stats
 
 
@@ -78,6 +86,10 @@ def evaluation_main(cfg):
     if skipped:
         log.info(f"[INFO] Plotting is not part of this evaluation; skipped: {skipped}")
     sample_dir = os.path.join(cfg["paths"]["sample_dir"], "generation", model_name_str, "generated_samples")
+    if multivariate_scores_config(cfg) is not None:
+        for t in types:
+            if t != "repeated":
+                log.info(f"[INFO] evaluation.multivariate_scores needs 'repeated' samples (an ensemble); skipped for '{t}'")
     out = {}
     for gen_type in types:
         n = n_samples_of(cfg, gen_type)

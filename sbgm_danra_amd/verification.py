@@ -1,8 +1,9 @@
-"""Device-tensor wrappers of the verification kernels (csrc/verify.hip, csrc/verify_spatial.hip, csrc/verify_products.hip and
-csrc/verify_objects.hip): error statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill),
+"""Device-tensor wrappers of the verification kernels (csrc/verify.hip, csrc/verify_spatial.hip, csrc/verify_products.hip,
+csrc/verify_objects.hip and csrc/verify_multivariate.hip): error statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill),
 radially averaged power spectra, neighbourhood scores (Fractions Skill Score), threshold-exceedance scores (Brier, reliability
 table, ROC area), ensemble products (per-pixel mean, spread, envelope, quantile and exceedance-probability maps) and
-object-based scores (connected objects and SAL: structure, amplitude, location).  Every function takes tensors on
+object-based scores (connected objects and SAL: structure, amplitude, location) and multivariate ensemble scores (energy score,
+variogram score).  Every function takes tensors on
 the ROCm device and returns tensors on the device; arguments and shapes are checked before any launch and nothing is copied
 to the host.  A pixel is valid when gen (every member) and obs are not NaN and the mask admits it (uint8/bool != 0, or float
 > 0.5); every statistic uses the valid pixels only."""
@@ -28,6 +29,12 @@ DEFAULT_WORKSPACE_BYTES = 256 << 20
 OBJECT_KEYS = ("threshold", "n_objects", "area", "mass", "V", "r", "domain_mean", "com", "valid", "S", "L2", "A", "L1", "L",
                "area_hist", "status")               # the argument order of sbgm_object_scores
 OBJECT_AREA_BINS = 21                            # include/sbgm_hip.h: SBGM_OBJECTS_AREA_BINS; fixed thresholds: MAX_THRESHOLDS
+ENERGY_KEYS = ("count", "es_fair", "es_standard", "mean_dist_obs", "mean_dist_pair", "min_dist_pair")
+VARIOGRAM_KEYS = ("vs", "n_pairs", "sum_w", "vs_unweighted")
+MAX_MULTIVARIATE_MEMBERS = 4095
+MAX_VARIOGRAM_RADIUS, MAX_VARIOGRAM_OFFSETS = 8, 98    # include/sbgm_hip.h: SBGM_VARIOGRAM_MAX_OFFSETS
+VARIOGRAM_ORDERS = (0.5, 1.0, 2.0)
+VARIOGRAM_WEIGHTS = ("inverse_distance", "unit")
 
 
 def _rows(t, name, HW, allowed):
@@ -422,3 +429,85 @@ def object_scores(gen, obs, thresholds=(), relative=None, mask=None, connectivit
                                        ws.data_ptr(), nbytes, N.stream()))
     out["status"] = out["status"][0]
     return out
+
+
+def variogram_offsets(radius):
+    """the pixel-pair offsets (dy, dx) of variogram_scores for a radius 1..8, in the kernel's order: the half-plane (dy > 0, or
+    dy == 0 and dx > 0) of the disc dy^2 + dx^2 <= radius^2, dy ascending, then dx ascending"""
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= MAX_VARIOGRAM_RADIUS:
+        raise ValueError(f"variogram: radius must be an integer in 1..{MAX_VARIOGRAM_RADIUS}, got {radius!r}")
+    return [(dy, dx) for dy in range(radius + 1) for dx in range(-radius, radius + 1)
+            if (dy > 0 or dx > 0) and dy * dy + dx * dx <= radius * radius]
+
+
+def _multivariate_args(name, ens, obs, mask):
+    """shape, dtype and limit checks shared by energy_scores and variogram_scores -> (ens [M, HW], obs [1, HW], mask, is_u8)"""
+    if ens.dim() != 3:
+        raise ValueError(f"ens: expected [M, H, W], got {tuple(ens.shape)}")
+    M, H, W = ens.shape
+    if not 2 <= M <= MAX_MULTIVARIATE_MEMBERS:
+        raise ValueError(f"{name}: M={M} members; need 2..{MAX_MULTIVARIATE_MEMBERS}")
+    if H < 1 or W < 1 or H * W > MAX_FIELD_PIXELS:
+        raise ValueError(f"{name}: field size {H}x{W}; need H*W in 1..2^20")
+    _shape_rows(obs, "obs", (H, W), (1,))
+    _shape_rows(mask, "mask", (H, W), (1,))
+    if not ens.is_floating_point() or not obs.is_floating_point():
+        raise TypeError(f"{name}: ens and obs must be floating tensors, got {ens.dtype} and {obs.dtype}")
+    e = _fields(ens, "ens")
+    o = _fields(obs, "obs")
+    if o.device != e.device:
+        raise ValueError("ens and obs must be on the same device")
+    m, u8, _ = _mask(mask, H * W, (1,))
+    return e, o, m, u8
+
+
+def energy_scores(ens, obs, mask=None):
+    """energy score (Gneiting et al. 2008) of members ens [M,H,W] (2 <= M <= 4095, H*W <= 2^20) against truth obs [H,W],
+    optional mask [H,W].  A pixel is valid when every member and obs are not NaN there and the mask admits it.  Returns device
+    tensors: `dist2` fp64 [M+1, M+1], the squared Euclidean distances over the valid pixels between all members and the truth
+    (row / column M), accumulated in fp64 from differences (symmetric bit for bit, zero diagonal, an exact 0 between
+    duplicated members); `scores` fp64 [6] in ENERGY_KEYS order: count, es_fair = (1/M) sum_m |x_m - y| - 1/(2 M (M-1))
+    sum_{m != k} |x_m - x_k|, es_standard (the same with 1/(2 M^2)), mean_dist_obs, mean_dist_pair and min_dist_pair, every
+    norm |a - b| = sqrt(dist2 / count), an RMS distance.  No valid pixel gives count 0 and NaN scores.  Two calls give
+    bit-equal results."""
+    e, o, m, u8 = _multivariate_args("energy_scores", ens, obs, mask)
+    M, HW = e.shape
+    dev = e.device
+    dist2 = torch.empty(M + 1, M + 1, dtype=torch.float64, device=dev)
+    scores = torch.empty(len(ENERGY_KEYS), dtype=torch.float64, device=dev)
+    nbytes = N.lib().sbgm_energy_scores_workspace_bytes(M, HW)
+    ws = _ws(nbytes, dev)
+    N.check(N.lib().sbgm_energy_scores(e.data_ptr(), o.data_ptr(), N.ptr(m), u8, M, HW, dist2.data_ptr(), scores.data_ptr(),
+                                       ws.data_ptr(), nbytes, N.stream()))
+    return dict(dist2=dist2, scores=scores)
+
+
+def variogram_scores(ens, obs, radius=4, order=0.5, weights="inverse_distance", mask=None):
+    """variogram score of order p = `order` (Scheuerer & Hamill 2015) of members ens [M,H,W] (2 <= M <= 4095, H*W <= 2^20)
+    against truth obs [H,W], optional mask [H,W], over the pixel pairs (i, j = i + (dy, dx)) of variogram_offsets(radius) with
+    both pixels valid and inside the field.  Per pair g_ens = (1/M) sum_m |x_i^m - x_j^m|^p, g_obs = |y_i - y_j|^p (difference
+    and power in fp32, sums in fp64) and term = (g_obs - g_ens)^2; w = 1 / sqrt(dy^2 + dx^2) for weights "inverse_distance", 1
+    for "unit".  order is 0.5, 1 or 2; radius 1..8.  Returns device tensors: `vs_map` fp32 [H,W], each pixel's sum of w term
+    over its own pairs (NaN at an invalid pixel); `offsets` int32 [n_off, 2]; `gamma_ens`, `gamma_obs` fp64 [n_off], the
+    domain-mean variograms per offset (NaN without pairs); `pairs` int64 [n_off]; `scores` fp64 [4] in VARIOGRAM_KEYS order:
+    vs = sum w term / sum w, n_pairs, sum_w, vs_unweighted = sum term / n_pairs.  Two calls give bit-equal results."""
+    offsets = variogram_offsets(radius)
+    if isinstance(order, bool) or not isinstance(order, (int, float)) or float(order) not in VARIOGRAM_ORDERS:
+        raise ValueError(f"variogram_scores: order must be one of {VARIOGRAM_ORDERS}, got {order!r}")
+    if weights not in VARIOGRAM_WEIGHTS:
+        raise ValueError(f"variogram_scores: weights must be one of {VARIOGRAM_WEIGHTS}, got {weights!r}")
+    e, o, m, u8 = _multivariate_args("variogram_scores", ens, obs, mask)
+    M, (H, W) = e.shape[0], ens.shape[1:]
+    dev, n_off = e.device, len(offsets)
+    f64 = dict(dtype=torch.float64, device=dev)
+    vs_map = torch.empty(H, W, device=dev)
+    gamma_ens, gamma_obs = torch.empty(n_off, **f64), torch.empty(n_off, **f64)
+    pairs = torch.empty(n_off, dtype=torch.int64, device=dev)
+    scores = torch.empty(len(VARIOGRAM_KEYS), **f64)
+    nbytes = N.lib().sbgm_variogram_scores_workspace_bytes(M, H, W, radius)
+    ws = _ws(nbytes, dev)
+    N.check(N.lib().sbgm_variogram_scores(e.data_ptr(), o.data_ptr(), N.ptr(m), u8, M, H, W, radius, float(order),
+                                          int(weights == "inverse_distance"), vs_map.data_ptr(), gamma_ens.data_ptr(),
+                                          gamma_obs.data_ptr(), pairs.data_ptr(), scores.data_ptr(), ws.data_ptr(), nbytes, N.stream()))
+    return dict(vs_map=vs_map, offsets=torch.tensor(offsets, dtype=torch.int32, device=dev), gamma_ens=gamma_ens,
+                gamma_obs=gamma_obs, pairs=pairs, scores=scores)
