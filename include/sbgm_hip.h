@@ -451,6 +451,23 @@ int sbgm_up_lowres_pack(const float* w_oihw, float* w_taps, float* w_packed, int
 int sbgm_up_lowres_fwd(const float* x_lowres_nhwc, const float* w_packed, const float* bias, const float* gamma, const float* beta,
                        int groups, float eps, float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream);
 
+/* nn.LayerNorm(C, eps) followed by nn.Linear(C, Cout) without a normalisation pass (conv_igemm.hip; the route the EM / PC / EDM Heun
+ * samplers take for the attention blocks that run separate GEMMs, score_unet.py:136-148): LN(x) = r diag(gamma) (I - 11^T/C) x + beta with
+ * r = 1/sqrt(var(x) + eps), so
+ *   linear(LN(x))[co] = r * sum_k W''[co][k] x[k] + h[co],   W'' = W diag(gamma) (I - 11^T/C),   h = b + W beta.
+ * pack: w [Cout][C], b [Cout] or NULL, gamma / beta [C] -> w2_oihw [Cout][C] (W'') and h [Cout], summed in fp64 and rounded once, and
+ * w2_packed, the implicit-GEMM image of W'' (sbgm_conv_packed_numel(Cout, 1, 1, C) floats).  C % 16 == 0.
+ * fwd: x [M][C] raw rows -> out [M][Cout] = act(r * W'' x + h + res), res [M][Cout] or NULL, act as in sbgm_conv_args.  The product loads
+ * every element of a row as its B operand and sums it and its square in fp64 on the way, so r is the two-pass fp64 value to fp32 rounding
+ * for rows with |mean|/sigma up to 64 at least.  tile: NULL or six zeros = the static choice, else one of sbgm_ln_linear_tiles'
+ * candidates {tile_co, tile_px, 1, waves_per_tile, 0, 0}, tile_co in {1, 2, 4}; Cout % (16 tile_co) == 0, no grid split-K.
+ * sbgm_ln_linear_tiles writes up to `cap` candidates (6 ints each), the ones the autotuner times for this op, and returns their number. */
+int sbgm_ln_fold_pack(const float* w, const float* b, const float* gamma, const float* beta, int C, int Cout, float* w2_oihw, float* w2_packed,
+                      float* h, void* stream);
+int sbgm_ln_linear_tiles(int M, int C, int Cout, int* tiles, int cap);
+int sbgm_ln_linear_fwd(const float* x, const float* w2_packed, const float* h, const float* res, int act, float eps, float* out, int M, int C,
+                       int Cout, const int* tile, void* stream);
+
 /* Time rows of an Euler-Maruyama / predictor-corrector run without labels: the run computes the time-bias vectors of all
  * its steps once, row s = the vectors at the time of step s one after the other, and the end of a step publishes the row of the next.
  * Host-side statements of the two rules, usable without a device:

@@ -140,6 +140,9 @@ SIGNATURES = {
     "sbgm_up_lowres_ws_numel": (_i64, [_i, _i, _i, _i, _i]),
     "sbgm_up_lowres_pack": (_i, [_vp, _vp, _vp, _i, _vp]),
     "sbgm_up_lowres_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sbgm_ln_fold_pack": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "sbgm_ln_linear_tiles": (_i, [_i, _i, _i, C.POINTER(C.c_int), _i]),
+    "sbgm_ln_linear_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _i, _i, _i, C.POINTER(C.c_int), _vp]),
     "sbgm_time_row_layout": (_i, [C.POINTER(C.c_int), _i, C.POINTER(C.c_int)]),
     "sbgm_time_row_index": (_i64, [_i64, _i64]),
     "sbgm_final_block_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _i, _i, _i, _i,
@@ -257,7 +260,7 @@ SIGNATURES = {
     "sbgm_variogram_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i] + [_vp] * 6 + [_i64, _vp]),
 }
 
-ABI_VERSION = 10        # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 11       # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

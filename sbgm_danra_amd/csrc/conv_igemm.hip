@@ -19,6 +19,15 @@
 // accumulators through LDS before the epilogue (in-workgroup split-K: more waves per SIMD to hide the operand
 // latency, no extra launch, no global traffic), and, for the tiniest layers, split-K over gridDim.y followed by
 // splitk_reduce_epilogue.
+//
+// LayerNorm on load (ConvParams::in_mode 3, conv_igemm_kernel<1,1,1,0,1,FCO,FPX,0,WS>; 1x1 only): the linear that follows a LayerNorm runs on the RAW rows.
+// LN(x) = r * diag(gamma) (I - 11^T/C) x + beta with r = 1/sqrt(var(x) + eps), so the fixed map is folded into the weights once per
+// upload (ln_fold_kernel: W'' = W diag(gamma) (I - 11^T/C), h = b + W beta) and only r is left per token.  The B operand already brings
+// every element of the row through the lanes, so a lane adds the quads it loads into an fp64 sum and sum of squares per pixel fragment;
+// the four kq lane groups (and the WS waves of the tile, beside the accumulator hand-off) combine them, and the epilogue scales the
+// accumulator by r before the usual bias / residual / activation.  fp64 because var = E[x^2] - mean^2 cancels |mean/sigma|^2 of its
+// leading digits: at |mean|/sigma = 64 that is 12 of fp64's 53 bits (x^2 of an fp32 x is exact in fp64), where fp32 sums would have none
+// left; r then equals the two-pass fp64 value to fp32 rounding.
 #include "../../include/sbgm_hip.h"
 #include "common.h"
 #include "kernels.h"
@@ -39,7 +48,9 @@ struct PixLane {      // per-lane decode of the output pixel this lane gathers f
 
 // The kernel's body as a function of (problem, workgroup index, workgroup count), so that conv_igemm_kernel (one problem per launch) and
 // conv_igemm_pair_kernel (two problems sharing a grid) run the same code: workgroup `bid` of the `nb` that serve problem p.
-template <int KH, int KW, int S, int PAD, int FCO, int FPX, int CMODE, int WS>
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+template <int KH, int KW, int S, int PAD, int FCO, int FPX, int CMODE, int WS, int LNF = 0>
 __device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int bid, const int nb) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int lane = threadIdx.x & 63;
@@ -158,6 +169,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int b
     for (int i = 0; i < FCO; ++i)
 #pragma unroll
         for (int j = 0; j < FPX; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    double ln_s[FPX], ln_q[FPX];    // LNF: this lane's share of pixel fragment j's sum and sum of squares over the row
+#pragma unroll
+    for (int j = 0; j < FPX; ++j) ln_s[j] = ln_q[j] = 0.0;
 
     auto compute = [&](const Frags<FCO, FPX>& fr) {
 #pragma unroll
@@ -167,6 +181,16 @@ __device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int b
 #pragma unroll
                 for (int j = 0; j < FPX; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fr.a[i][k], fr.b[j][k], acc[i][j], 0, 0, 0);
+        if (LNF) {                  // here, not in load_next: the step loaded past s_end is never counted
+#pragma unroll
+            for (int j = 0; j < FPX; ++j)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double x = (double)fr.b[j][k];
+                    ln_s[j] += x;
+                    ln_q[j] = fma(x, x, ln_q[j]);
+                }
+        }
     };
 
     // Software pipeline, two register sets.  The pair loop body is branch-free so the loads of step s+1
@@ -187,16 +211,30 @@ __device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int b
         if (s < s_end) compute(f0);
     }
 
+    if (LNF) {                      // the row's four channel quads of a K step sit on the four kq lane groups
+#pragma unroll
+        for (int j = 0; j < FPX; ++j) {
+            ln_s[j] += __shfl_xor(ln_s[j], 16, 64);
+            ln_q[j] += __shfl_xor(ln_q[j], 16, 64);
+            ln_s[j] += __shfl_xor(ln_s[j], 32, 64);
+            ln_q[j] += __shfl_xor(ln_q[j], 32, 64);
+        }
+    }
+
     // ---- in-workgroup split-K: waves 1..WS-1 of a tile hand their accumulators to wave 0 through LDS --------------
     if (WS > 1) {
-        f32x4* red = reinterpret_cast<f32x4*>(smem_raw);      // [tslot][kpart-1][frag][lane]
-        constexpr int NF = FCO * FPX;
+        f32x4* red = reinterpret_cast<f32x4*>(smem_raw);      // [tslot][kpart-1][frag][lane]; LNF: FPX more 16-byte slots, (sum, sum of squares)
+        constexpr int NF = FCO * FPX + (LNF ? FPX : 0);
         if (kpart > 0) {
             f32x4* dst = red + ((tslot * (WS - 1) + (kpart - 1)) * NF) * 64 + lane;
 #pragma unroll
             for (int i = 0; i < FCO; ++i)
 #pragma unroll
                 for (int j = 0; j < FPX; ++j) dst[(i * FPX + j) * 64] = acc[i][j];
+            if (LNF) {
+#pragma unroll
+                for (int j = 0; j < FPX; ++j) *reinterpret_cast<f64x2*>(dst + (FCO * FPX + j) * 64) = f64x2{ln_s[j], ln_q[j]};
+            }
         }
         __syncthreads();
         if (kpart > 0 || !tile_ok) return;
@@ -207,6 +245,14 @@ __device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int b
             for (int i = 0; i < FCO; ++i)
 #pragma unroll
                 for (int j = 0; j < FPX; ++j) acc[i][j] += src[(i * FPX + j) * 64];
+            if (LNF) {
+#pragma unroll
+                for (int j = 0; j < FPX; ++j) {
+                    const f64x2 sq = *reinterpret_cast<const f64x2*>(src + (FCO * FPX + j) * 64);
+                    ln_s[j] += sq[0];
+                    ln_q[j] += sq[1];
+                }
+            }
         }
     }
 
@@ -255,12 +301,19 @@ __device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int b
 #pragma unroll
     for (int j = 0; j < FPX; ++j) {
         const int m = m0 + 16 * j + r16;
+        float ln_r = 1.f;           // LNF: 1/sqrt(var + eps) of this lane's pixel (a pixel past M read zeros: 1/sqrt(eps), never stored)
+        if (LNF) {
+            const double mean = ln_s[j] / (double)p.Cs;
+            const double var = fmax(ln_q[j] / (double)p.Cs - mean * mean, 0.0);
+            ln_r = (float)(1.0 / sqrt(var + (double)p.ln_eps));
+        }
         if (m >= p.M) continue;
         const int b = m / ohw;
 #pragma unroll
         for (int i = 0; i < FCO; ++i) {
             const int co = co0 + 16 * i + 4 * kq;
             f32x4 v = acc[i][j];
+            if (LNF) v *= ln_r;
             if (!partial) v = conv_epilogue(v, p, co, (size_t)m, b);
             *reinterpret_cast<f32x4*>(outp + (size_t)m * p.Cout + co) = v;
         }
@@ -270,6 +323,13 @@ __device__ __forceinline__ void conv_igemm_body(const ConvParams& p, const int b
 template <int KH, int KW, int S, int PAD, int FCO, int FPX, int CMODE, int WS>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     conv_igemm_body<KH, KW, S, PAD, FCO, FPX, CMODE, WS>(p, blockIdx.x, gridDim.x);
+}
+
+// The nine-argument form names the input mode after the geometry: LNF = 1 is a linear (1x1) on the rows a LayerNorm would have normalised
+// (in_mode 3, see the header comment): p.wp = W'', p.bias = h, one grid row.  Instantiated for <1, 1, 1, 0, 1, FCO, FPX, 0, WS> only.
+template <int KH, int KW, int S, int PAD, int LNF, int FCO, int FPX, int CMODE, int WS>
+__global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
+    conv_igemm_body<KH, KW, S, PAD, FCO, FPX, CMODE, WS, LNF>(p, blockIdx.x, gridDim.x);
 }
 
 // A BasicBlock's two stride-2 convolutions of one input in one launch: the 3x3 / pad 1 (main) on workgroups [0, nA) and the 1x1
@@ -426,9 +486,49 @@ int launch_geom(const ConvParams& p, const ConvTile& t, dim3 grid, hipStream_t s
     }
 #define SBGM_TILES(W) SBGM_TILE(4, 4, W) SBGM_TILE(4, 2, W) SBGM_TILE(4, 1, W) SBGM_TILE(2, 4, W) SBGM_TILE(2, 2, W) SBGM_TILE(2, 1, W)
     SBGM_TILES(1) SBGM_TILES(2) SBGM_TILES(4)
+#undef SBGM_TILE
+    return 1;
+}
+
+int launch_ln(const ConvParams& p, const ConvTile& t, dim3 grid, hipStream_t st) {
+#define SBGM_TILE(FC, FP, W)                                                                                  \
+    if (t.fco == FC && t.fpx == FP && t.ws == W) {                                                            \
+        const size_t lds = W > 1 ? (size_t)(4 / W) * (W - 1) * (FC * FP + FP) * 64 * 16 : 0;                   \
+        hipLaunchKernelGGL((conv_igemm_kernel<1, 1, 1, 0, 1, FC, FP, 0, W>), grid, dim3(256), lds, st, p);      \
+        return 0;                                                                                             \
+    }
+    SBGM_TILES(1) SBGM_TILES(2) SBGM_TILES(4)
+#define SBGM_TILES16(W) SBGM_TILE(1, 4, W) SBGM_TILE(1, 2, W) SBGM_TILE(1, 1, W)    /* 16-channel tiles: a Cout that is no multiple of 32 */
+    SBGM_TILES16(1) SBGM_TILES16(2) SBGM_TILES16(4)
+#undef SBGM_TILES16
 #undef SBGM_TILES
 #undef SBGM_TILE
     return 1;
+}
+
+// W''[co][k] = W[co][k] gamma[k] - (1/C) sum_j W[co][j] gamma[j],  h[co] = b[co] + sum_k W[co][k] beta[k]: one workgroup per output row,
+// fp64 sums in a fixed order (lane-strided, butterfly, waves in order), each result rounded to fp32 once.
+__global__ __launch_bounds__(256) void ln_fold_kernel(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float* __restrict__ w2, float* __restrict__ h, int C) {
+    __shared__ double red[2][4];
+    const int co = blockIdx.x, tid = threadIdx.x;
+    const float* wr = w + (size_t)co * C;
+    double sg = 0.0, sb = 0.0;
+    for (int k = tid; k < C; k += 256) {
+        sg = fma((double)wr[k], (double)gamma[k], sg);
+        sb = fma((double)wr[k], (double)beta[k], sb);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        sg += __shfl_xor(sg, o, 64);
+        sb += __shfl_xor(sb, o, 64);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = sg; red[1][tid >> 6] = sb; }
+    __syncthreads();
+    const double tg = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3], tb = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    const double mean = tg / (double)C;
+    for (int k = tid; k < C; k += 256) w2[(size_t)co * C + k] = (float)((double)wr[k] * (double)gamma[k] - mean);
+    if (tid == 0) h[co] = (float)((b ? (double)b[co] : 0.0) + tb);
 }
 
 }  // namespace
@@ -448,6 +548,15 @@ int sbgm_launch_pack_conv_weight(const float* w_oihw, float* wp, int Cout, int C
     const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(blocks), dim3(256), 0, st, w_oihw, wp, Cout, Cin, KH, KW, cs, nsteps,
                        transposed);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sbgm_launch_ln_fold(const float* w, const float* b, const float* gamma, const float* beta, float* w2_oihw, float* h, int C, int Cout,
+                        hipStream_t st) {
+    SBGM_CHECK(w && gamma && beta && w2_oihw && h, "ln_fold: null tensor");
+    SBGM_CHECK(C >= 16 && C % 16 == 0 && Cout >= 1, "ln_fold: needs C %% 16 == 0 (C=%d Cout=%d)", C, Cout);
+    hipLaunchKernelGGL(ln_fold_kernel, dim3(Cout), dim3(256), 0, st, w, b, gamma, beta, w2_oihw, h, C);
     SBGM_LAUNCH_CHECK();
     return 0;
 }
@@ -514,6 +623,16 @@ int sbgm_launch_conv(const ConvGeom& g, ConvParams p, const ConvTile& cfg, float
     if (real_splits > 1) {
         SBGM_CHECK(partial_ws != nullptr, "conv: split-K needs a partial workspace");
         p.out = partial_ws;
+    }
+    if (p.in_mode == 3) {
+        SBGM_CHECK(g.kh == 1 && g.kw == 1 && g.stride == 1 && g.pad == 0 && cmode == 0 && p.c_real == 0 && p.in_dil == 1 && p.out_h == 0,
+                   "conv: LayerNorm on load (in_mode 3) is a 1x1 / stride 1 product over C %% 16 == 0 real channels (k=%dx%d s=%d Cs=%d)", g.kh,
+                   g.kw, g.stride, p.Cs);
+        SBGM_CHECK(cfg.splits <= 1 && p.proj_w == nullptr && p.scale == nullptr && p.ln_eps > 0.f,
+                   "conv: LayerNorm on load takes no grid split-K, no tap projection and no scale, and needs eps > 0");
+        SBGM_CHECK(launch_ln(p, cfg, grid, st) == 0, "conv: no LayerNorm-on-load kernel for tile=%dx%d ws=%d", cfg.fco, cfg.fpx, cfg.ws);
+        SBGM_LAUNCH_CHECK();
+        return 0;
     }
     int rc = 1;
 #define SBGM_GEOM(KH_, KW_, S_, PAD_, CM_)                                                        \

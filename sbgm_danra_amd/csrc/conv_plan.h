@@ -83,7 +83,8 @@ struct ConvParams {
                           // 8 taps x 2 channels (weights packed with cs = 2) instead of 4 taps x 4 slots, halving the MFMA work
     int in_dil;           // 1, or 2: read the input through a zero-inserted grid (data-gradient of a stride-2 conv)
     int out_h, out_w;     // explicit output size (required with in_dil == 2), else 0
-    // conv_lds only — what happens to the input while the halo patch is staged (conv_lds.hip, "Input modes"):
+    // conv_lds only (modes 1, 2) — what happens to the input while the halo patch is staged (conv_lds.hip, "Input modes");
+    // conv_igemm only (mode 3) — LayerNorm on load: implicit GEMM 1x1 only, see ln_eps below:
     int in_mode;          // 0 plain; 1 affine on load (x*scale + shift per (sample, channel), zero padding kept); 2 bilinear x2 on
                           // load: x is the LOW-resolution map [B][H/2][W/2][Cs] (H, W stay the convolution's own size), optionally
                           // transformed act(x*scale + shift + skip) before the interpolation
@@ -93,6 +94,11 @@ struct ConvParams {
     // filled by sbgm_launch_conv:
     int OH, OW, M, cb_per_tap, nsteps, steps_per_split, n_px_tiles, n_co_tiles;
     uint32_t x_bytes, w_bytes;
+    // conv_igemm only — in_mode 3, LayerNorm on load: implicit GEMM 1x1 / stride 1 only.  The rows of x are raw, wp is the folded weight
+    // W'' and bias the folded h (sbgm_launch_ln_fold); the kernel finds each row's 1/sqrt(var + ln_eps) from the B operand it loads and
+    // scales the accumulator by it.  Cs is the real channel count, a multiple of 16; no grid split-K, no scale, no tap projection.
+    // (An input like in_mode, set by the caller; it sits last, in what was the struct's tail padding, so no other field moved.)
+    float ln_eps;
 };
 
 // ---- weight images ---------------------------------------------------------------------------------------------------------------
@@ -136,6 +142,8 @@ inline ConvOpKey sbgm_conv_op_key(const ConvGeom& g, const ConvParams& p) {
 }
 typedef std::map<ConvOpKey, ConvTile> ConvTileTable;
 // text file, one line per convolution: "kh kw stride pad B H W Cin_pad Cout proj in_mode | fco fpx splits ws wino lds"
+// (a linear with a folded LayerNorm, in_mode 3, has a row of its own beside the plain linear of the same shape: 1x1 / stride 1,
+// implicit-GEMM tiles with fco in {1, 2, 4} and splits = 1; any other geometry or family under in_mode 3 is refused on load)
 int sbgm_tile_table_save(const ConvTileTable& table, const char* path);
 int sbgm_tile_table_load(ConvTileTable* table, const char* path);      // adds to / overrides *table; untouched when a line is malformed
 

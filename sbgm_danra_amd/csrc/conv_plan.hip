@@ -73,6 +73,8 @@ int sbgm_launch_tile(const ConvGeom& g, ConvParams p, const ConvImages& w, const
     const FamilyInfo& fi = FAMILY[f];
     SBGM_CHECK(geom_admits(fi.geom, g.kh, g.kw, g.stride, g.pad) && (fi.geom == GEOM_ANY || p.in_dil <= 1),
                "conv: the %s kernel is %s only (no input dilation)", fi.name, GEOM_TEXT[fi.geom]);
+    SBGM_CHECK(p.in_mode >= 0 && p.in_mode <= 3 && (p.in_mode != 3 || f == FAM_IGEMM),
+               "conv: input mode %d is not served by the %s kernel", p.in_mode, fi.name);
     p.wp = w.img[fi.image];
     SBGM_CHECK(p.wp != nullptr, "conv: the %s kernel reads a weight image this weight does not have", fi.name);
     switch (f) {
@@ -182,6 +184,15 @@ ConvTile sbgm_cout16_tile(const ConvParams& p, const ConvImages& w) {
     return ConvTile::lds_wino(1, 1);
 }
 ConvTile sbgm_static_tile(const ConvGeom& g, const ConvParams& p, const ConvImages& w) {
+    if (p.in_mode == 3) {                    // LayerNorm on load: the tile of the plain 1x1 of the same shape, without grid split-K
+        const int ns = p.Cs / 16;
+        if (p.Cout % 32) return ConvTile::igemm(1, 2, 1, ns >= 8 ? 4 : ns >= 4 ? 2 : 1);       // only its 16-channel tiles serve such a Cout
+        ConvParams q = p;
+        q.in_mode = 0;
+        ConvTile t = sbgm_static_tile(g, q, w);
+        t.splits = 1;
+        return t;
+    }
     const int OH = (p.H + 2 * g.pad - g.kh) / g.stride + 1, OW = (p.W + 2 * g.pad - g.kw) / g.stride + 1;
     const bool round1 = sbgm_conv_switches().round1;                         // the round-1 table (A/B of this function)
     const bool lds_ok = !sbgm_conv_switches().no_lds && !round1;
@@ -266,16 +277,17 @@ std::vector<ConvTile> sbgm_conv_candidates(const ConvGeom& g, const ConvParams& 
     const int nsteps = sbgm_conv_nsteps(g.kh, g.kw, p.c_real == 2 ? 2 : p.Cs);
     const bool has_wino = w.img[IMG_WINO] != nullptr, has_w2d = w.img[IMG_W2D] != nullptr, lds_ok = !sbgm_conv_switches().no_lds;
     std::vector<ConvTile> cands;
-    const int tiles[6][2] = {{4, 4}, {4, 2}, {4, 1}, {2, 4}, {2, 2}, {2, 1}};
+    const int tiles[9][2] = {{4, 4}, {4, 2}, {4, 1}, {2, 4}, {2, 2}, {2, 1}, {1, 4}, {1, 2}, {1, 1}};
     for (auto& t : tiles) {
-        if (p.in_mode != 0) break;                    // the fused input modes exist in the LDS-staged Winograd kernel only
+        if (t[0] == 1 && p.in_mode != 3) break;       // 16-channel wave tiles: the LayerNorm-on-load kernel only
+        if (p.in_mode != 0 && p.in_mode != 3) break;  // the fused input modes 1 and 2 exist in the LDS-staged Winograd kernel only
         if (p.Cout % (16 * t[0])) continue;
         if (p.proj_w && 16 * t[0] != p.Cout) continue;
         const long ntile = (long)(((size_t)p.B * OH * OW + 16 * t[1] - 1) / (16 * t[1])) * (p.Cout / (16 * t[0]));
         for (int ws : {1, 2, 4}) {
             if (ws > 1 && (nsteps / ws < 2 || ntile * ws > 32768)) continue;
             for (int sp : {1, 2, 4, 8, 16}) {
-                if (sp > 1 && (p.proj_w || !partial || nsteps / (sp * ws) < 2 || ntile * ws >= 4096)) continue;   // already enough waves
+                if (sp > 1 && (p.proj_w || p.in_mode == 3 || !partial || nsteps / (sp * ws) < 2 || ntile * ws >= 4096)) continue;   // already enough waves
                 cands.push_back(ConvTile::igemm(t[0], t[1], sp, ws));
             }
         }
@@ -406,7 +418,11 @@ int sbgm_tile_table_save(const ConvTileTable& table, const char* path) {
 // key of the geometry that family accepts.
 static bool tile_line_ok(const ConvOpKey& k, const ConvTile& t) {
     auto pow2_upto = [](int v, int hi) { return v >= 1 && v <= hi && (v & (v - 1)) == 0; };
-    if (k.in_mode < 0 || k.in_mode > 2 || !pow2_upto(t.fco, 4) || !pow2_upto(t.fpx, 4) || t.splits < 1 || t.splits > 64 ||
+    // LayerNorm on load: a 1x1 / stride 1 product over whole 16-channel steps on the implicit-GEMM family, one grid row
+    if (k.in_mode == 3 && !(k.kh == 1 && k.kw == 1 && k.s == 1 && k.p == 0 && k.Cs >= 16 && k.Cs % 16 == 0 && k.proj == 0 && t.well_formed() &&
+                            t.family() == FAM_IGEMM && t.splits == 1 && t.ws <= 4))
+        return false;
+    if (k.in_mode < 0 || k.in_mode > 3 || !pow2_upto(t.fco, 4) || !pow2_upto(t.fpx, 4) || t.splits < 1 || t.splits > 64 ||
         !pow2_upto(t.ws, 8) || !t.well_formed() || k.Cout % (16 * t.fco) != 0)
         return false;
     const FamilyInfo& fi = FAMILY[t.family()];
@@ -450,6 +466,10 @@ std::string sbgm_tile_kernel_name(const ConvGeom& g, const ConvTile& t, int Cs, 
         case FAM_LDS_WINO: snprintf(b, sizeof b, "conv3x3_lds_kernel<%d; %d; true; %s; %d>", t.fco, t.fpx, two, in_mode); break;
         case FAM_WINO: snprintf(b, sizeof b, "conv3x3_wino_kernel<%d; %d; %d>", t.fco, t.fpx, t.ws); break;
         default:
+            if (in_mode == 3) {      // the nine-argument form: the input mode follows the geometry
+                snprintf(b, sizeof b, "conv_igemm_kernel<1; 1; 1; 0; 1; %d; %d; 0; %d>", t.fco, t.fpx, t.ws);
+                break;
+            }
             snprintf(b, sizeof b, "conv_igemm_kernel<%d; %d; %d; %d; %d; %d; %d; %d>", g.kh, g.kw, g.stride, g.pad, t.fco, t.fpx,
                      c_real == 2 ? 2 : (Cs >= 16 ? 0 : Cs), t.ws);
     }

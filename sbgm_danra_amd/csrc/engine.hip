@@ -55,12 +55,16 @@ struct Param {
 
 struct ConvW { Param* w = nullptr; Param* b = nullptr; };          // weight (+ optional bias)
 struct BNW { Param *g, *b, *rm, *rv; float *scale, *bias; };       // + folded eval scale/bias
-struct AttnW { Param *ln1g, *ln1b, *ln2g, *ln2b, *inw, *inb, *outw, *outb, *f1w, *f1b, *f2w, *f2b; int C; };
+struct LnFold;
+struct AttnW {
+    Param *ln1g, *ln1b, *ln2g, *ln2b, *inw, *inb, *outw, *outb, *f1w, *f1b, *f2w, *f2b; int C;
+    LnFold *fold1 = nullptr, *fold2 = nullptr;      // ln1 -> in_proj and ln2 -> ff[0] as folded operands (owned by sbgm_model::ln_folds)
+};
 struct BlockW { ConvW c1, c2, ds; BNW bn1, bn2, dsbn; bool has_ds; int cin, cout, stride; };
 struct DecW { ConvW up, conv; Param *n1g, *n1b, *n2g, *n2b, *freq, *tpw, *tpb; AttnW attn; bool has_attn; int cin, cout; };
 
 // ---- weights derived from uploaded weights ---------------------------------------------------------------------
-// Three images are computed from uploaded tensors, lazily and outside any captured step (who rebuilds which: refresh_derived).  The
+// Several images are computed from uploaded tensors, lazily and outside any captured step (who rebuilds which: refresh_derived).  The
 // folded BatchNorm (sbgm_model::bn_dirty) is raised by EVERY upload of any tensor.  The composed stem and the composed final block each
 // decide once whether they are active (`on`), are raised by an upload of one of their sources (Param::feeds, all the upload path knows
 // of them) and own every allocation behind them.
@@ -187,6 +191,42 @@ struct UpLowres : Derived {                                    // up: residual_l
         return 0;
     }
 };
+// A LayerNorm followed by a linear of an attention block on the separate-GEMM path (conv_igemm.hip, in_mode 3): the linear's weight with the
+// LayerNorm's fixed map folded in, W'' = W diag(gamma) (I - 11^T/C) as an ordinary 1x1 weight, and h = b + W beta.  Neither is a Param of the
+// model; W'' in OIHW, its implicit-GEMM image and h live in one allocation made by the first prepare() and kept at fixed addresses after it:
+// a cached step graph stays valid.  Raised by an upload of any of the four sources; rebuilt only by refresh_derived for a caller on the
+// route (Routes::ln_fold) and a block that runs the separate GEMMs at that size, so a training step never builds it.  SBGM_NO_LN_FOLD=1:
+// never.
+struct LnFold : Derived {
+    Param *g = nullptr, *b = nullptr, *w = nullptr, *bias = nullptr;
+    float* buf = nullptr;
+    Param w2;                                                  // W'' as a 1x1 convolution weight
+    float* h = nullptr;
+    static bool env_on() { static const bool v = getenv("SBGM_NO_LN_FOLD") == nullptr; return v; }
+    void build(Param* gamma, Param* beta, Param* weight, Param* wbias) {
+        g = gamma; b = beta; w = weight; bias = wbias;
+        on = env_on() && w->cin % 16 == 0 && w->cs == w->cin;
+        if (!on) return;
+        g->feeds = b->feeds = w->feeds = bias->feeds = this; w->keep_oihw = true;
+        w2.name = w->name + ".ln_folded"; w2.kind = P_CONV; w2.numel = w->numel;
+        w2.cout = w->cout; w2.cin = w2.cs = w->cin; w2.kh = w2.kw = 1;
+        w2.floats[IMG_IGEMM] = (size_t)w->numel;
+    }
+    int prepare(hipStream_t st) {
+        if (!on || !dirty) return 0;
+        SBGM_CHECK(w->oihw && g->filled && b->filled && bias->filled, "attention: '%s' or its LayerNorm was never uploaded", w->name.c_str());
+        const size_t n = align_up((size_t)w2.numel, 64);
+        if (alloc(buf, 2 * n + align_up((size_t)w2.cout, 64))) return 1;
+        w2.img[IMG_IGEMM] = buf + n;
+        h = buf + 2 * n;
+        if (sbgm_launch_ln_fold(w->oihw, bias->dev(), g->dev(), b->dev(), buf, h, w2.cin, w2.cout, st)) return 1;
+        if (sbgm_pack_conv_images(buf, w2.img, w2.cout, w2.cin, 1, 1, w2.cs, st)) return 1;
+        w2.filled = true;
+        dirty = false;
+        return 0;
+    }
+};
+
 // The static rule: the block sizes at which mix + gather measured faster than upsample2x + conv_up + the norm1 passes (DESIGN.md 3.1,
 // profiles/r10_block_sums.txt): low-res maps of 2x2 to 8x8 with 128 to 512 channels, 2 Ki to 32 Ki low-res elements per sample, at
 // batch 2, 16 and 32.  Nothing outside that range has been measured inside the network, so nothing outside it takes the route (the next
@@ -198,7 +238,7 @@ inline bool up_lowres_shape(int ci, int h, int w) {
 
 // Which evaluations take the composed stem (+ the run's condition term, null without condition channels) and the composed final block
 // (fin_lowres: as the low-resolution mix + gather instead of the composed 3x3 convolution) and the low-resolution conv_up of the
-// small-map decoder blocks (up_lowres)
+// small-map decoder blocks (up_lowres) and the folded LayerNorms of the attention blocks on the separate-GEMM path (ln_fold)
 // tbrun (EM and PC runs without labels): the run's time biases [9][run_B][ch_i], kept current by the step's advance, so
 // the evaluation launches neither the time embedding nor the time projections
 // skip_mix (the step samplers only): the evaluation launches neither pack_input nor conv1; the final mix forms the decoder's last skip
@@ -210,6 +250,7 @@ struct Routes {
     int run_B = 0;
     bool skip_mix = false;
     const float* skip_Sc = nullptr;
+    bool ln_fold = false;
 };
 enum Caller { CALL_PLAIN, CALL_SDE_RUN, CALL_MEASURE };
 
@@ -249,17 +290,37 @@ struct sbgm_model {
     ConvW fin_up, fin_conv;
     bool bn_dirty = true;                    // folded BatchNorm (see Derived)
     Stem stem; FinalBlock fin; UpLowres uplow[4];
+    std::vector<std::unique_ptr<LnFold>> ln_folds;       // two per attention block (AttnW::fold1 / fold2)
     // What every evaluation reads besides the uploaded parameters: the BatchNorm fold and the final block, refreshed from forward_impl
     // for eager calls and from SamplerRun, prepare_ws and autotune ahead of a capture.  The composed stem is NOT refreshed here but only
     // where an EM / PC / EDM Heun run begins: a plain forward or a training-time evaluation must not start packing a 22x22 image.
     // A decoder block's low-resolution image is built only for a caller that takes that route (`up_route`) at an input size H x W at
     // which the block is eligible: a plain forward, a training-time evaluation or a network whose blocks never qualify packs nothing.
-    int refresh_derived(hipStream_t st, bool up_route = false, int H = 0, int W = 0) {
+    // The same rule for the folded LayerNorms (`ln_route`): only the attention blocks that run the separate GEMMs at batch B.
+    int refresh_derived(hipStream_t st, bool up_route = false, int H = 0, int W = 0, bool ln_route = false, int B = 0) {
         if (bn_dirty && fold_bn(st)) return 1;
         for (int i = 0; i < 4 && up_route; ++i)
             if (up_lowres_block(i, (H / 32) << i, (W / 32) << i) && uplow[i].prepare(dec[i].up, st)) return 1;
+        auto folds = [&](const AttnW& a, int h, int w) {
+            return ln_fold_block(a, B * h * w) && (a.fold1->prepare(st) || a.fold2->prepare(st));
+        };
+        for (int i = 0; i < 5 && ln_route; ++i)                     // encoder map 0 is H / 2 high, map i >= 1 H / 2^(i+1)
+            if (enc_has_attn[i] && folds(enc_attn[i], H >> (i ? i + 1 : 1), W >> (i ? i + 1 : 1))) return 1;
+        for (int i = 0; i < 4 && ln_route; ++i)
+            if (dec[i].has_attn && folds(dec[i].attn, (H / 32) << (i + 1), (W / 32) << (i + 1))) return 1;
         return fin.prepare(fin_up, fin_conv, st);
     }
+    // The one place that decides which form of an attention block M tokens take: the token-tile kernels when there are enough 16-token
+    // tiles to give every CU one (3 launches: LN1 + in_proj | core | out_proj + residual + LN2 + FF + residual).  Deep levels (few
+    // tokens, 256-512 channels) are bound by streaming 1-6 MB of weights: there the separate GEMMs, which split the OUTPUT CHANNELS over
+    // the chip, stay faster (measured: 512 tokens x 512 channels 90 us per fused kernel on 32 workgroups vs ~8 us per GEMM).
+    static bool attn_token_tiles(int C, int M) {
+        static const bool no_fused = getenv("SBGM_NO_FUSED_ATTENTION") != nullptr;
+        static const int fused_min_m = getenv("SBGM_ATTN_FUSED_MIN_M") ? atoi(getenv("SBGM_ATTN_FUSED_MIN_M")) : 256 * 16;
+        return !no_fused && sbgm_attn_tokens_supported(C) && M >= fused_min_m;
+    }
+    // ... and whether a block on the separate GEMMs has its two LayerNorms folded into the linears after them
+    static bool ln_fold_block(const AttnW& a, int M) { return M >= 1 && a.fold1->on && a.fold2->on && !attn_token_tiles(a.C, M); }
     // Whether a 3x3 convolution of the decoder takes its input through the fused load path (forward_impl, "Fused path")
     bool can_fuse(const ConvW& cw, int c_in, int w_out) const {
         static const bool fused_ok = getenv("SBGM_NO_FUSED_DECODER") == nullptr && !sbgm_conv_switches().no_lds && !sbgm_conv_switches().no_wino;
@@ -273,6 +334,7 @@ struct sbgm_model {
     // The one place that decides who evaluates through which form of the network, from the kind of caller:
     //   the EM / PC / EDM Heun driver: composed stem and composed final block, for the duration of a run (~SamplerRun ends them);
     //   profile_forward and a tuning evaluation: the final block only (the roofline and the tile table describe the two-convolution stem);
+    //   the same callers as the final block: the attention blocks' LayerNorms folded into the linears after them (ln_fold);
     //   the plain forward and the RK45 driver: neither.  rk45_sampler's Python loop and SciPy's solver behind ode_sampler evaluate the
     //   network through the plain forward, and at rtol 1e-4 their accept / reject decisions are within rounding of the native loop's: with
     //   the composed block's rounding one run of tests/test_gpu_rk45_sampler.py took 452 evaluations under SciPy against 464 natively
@@ -283,7 +345,8 @@ struct sbgm_model {
                     const float* skip_Sc = nullptr) {
         const bool run = c == CALL_SDE_RUN;
         routes = Routes{run && stem.on, c != CALL_PLAIN && fin.on, c != CALL_PLAIN && fin.on && fin.lowres, c != CALL_PLAIN,
-                        run ? stem_T : nullptr, run ? tbrun : nullptr, run ? run_B : 0, run && skip_mix, run && skip_mix ? skip_Sc : nullptr};
+                        run ? stem_T : nullptr, run ? tbrun : nullptr, run ? run_B : 0, run && skip_mix, run && skip_mix ? skip_Sc : nullptr,
+                        c != CALL_PLAIN && LnFold::env_on()};
     }
     // Whether a step sampler's evaluations at width W form the decoder's last skip inside the final mix (Routes::skip_mix): the composed
     // stem (so nothing else reads conv1's output in the encoder), the low-resolution final block, and a last decoder block that leaves
@@ -444,6 +507,12 @@ struct sbgm_model {
         a.ln2g = vec(pre + ".ln2.weight", C); a.ln2b = vec(pre + ".ln2.bias", C);
         a.f1w = convw(pre + ".ff.0.weight", C, C, 1, 1); a.f1b = vec(pre + ".ff.0.bias", C);
         a.f2w = convw(pre + ".ff.2.weight", C, C, 1, 1); a.f2b = vec(pre + ".ff.2.bias", C);
+        for (LnFold** f : {&a.fold1, &a.fold2}) {
+            ln_folds.emplace_back(new LnFold());
+            *f = ln_folds.back().get();
+        }
+        a.fold1->build(a.ln1g, a.ln1b, a.inw, a.inb);
+        a.fold2->build(a.ln2g, a.ln2b, a.f1w, a.f1b);
         return a;
     }
 
@@ -744,13 +813,7 @@ int sbgm_model::conv_pair(const ConvGeom& gm, const ConvParams& pm, const Param&
 // y = h + FF(LN2(h)),  h = x + MHA(LN1(x))   over tokens [B*S, C]  (score_unet.py:136-148); in place on x
 int sbgm_model::attention(const AttnW& a, float* x, int B, int S, hipStream_t st) {
     const int C = a.C, M = B * S;
-    static const bool no_fused = getenv("SBGM_NO_FUSED_ATTENTION") != nullptr;
-    // Token-tile kernels when there are enough 16-token tiles to give every CU one (3 launches: LN1 + in_proj | core | out_proj +
-    // residual + LN2 + FF + residual).  Deep levels (few tokens, 256-512 channels) are bound by streaming 1-6 MB of weights: there
-    // the separate GEMMs, which split the OUTPUT CHANNELS over the chip, stay faster (measured: 512 tokens x 512 channels 90 us
-    // per fused kernel on 32 workgroups vs ~8 us per GEMM).
-    static const int fused_min_m = getenv("SBGM_ATTN_FUSED_MIN_M") ? atoi(getenv("SBGM_ATTN_FUSED_MIN_M")) : 256 * 16;
-    if (!no_fused && sbgm_attn_tokens_supported(C) && M >= fused_min_m) {
+    if (attn_token_tiles(C, M)) {
         float* qkv = wsalloc((size_t)M * 3 * C);
         if (!qkv) return 1;
         float* att = wsalloc((size_t)M * C);
@@ -771,17 +834,35 @@ int sbgm_model::attention(const AttnW& a, float* x, int B, int S, hipStream_t st
     float* f1 = wsalloc((size_t)M * C);
     if (!f1) return 1;
     const ConvGeom lin{1, 1, 1, 0};
-    if (sbgm_launch_layernorm(x, n1, a.ln1g->dev(), a.ln1b->dev(), M, C, LN_EPS, st)) return 1;
+    // With the route's fold (Routes::ln_fold) neither LayerNorm is launched: in_proj reads x and ff[0] reads h through the folded operands
+    // (in_mode 3).  n1 is carved all the same, so every later buffer keeps its address and the measured high-water mark serves both forms.
+    // A tuning evaluation runs both forms, so both keys of the tile table are tuned whichever a later caller takes.
+    const bool fold = routes.ln_fold && ln_fold_block(a, M);
+    SBGM_CHECK(!fold || (!a.fold1->dirty && !a.fold2->dirty), "attention: the folded LayerNorm operands of %d tokens x %d channels are stale", M, C);
     ConvParams p{};
     p.B = 1; p.H = 1; p.W = M; p.Cs = C;
-    p.x = n1; p.out = qkv; p.bias = a.inb->dev(); p.Cout = 3 * C;
-    if (conv(lin, p, *a.inw, st)) return 1;
+    p.out = qkv; p.Cout = 3 * C;
+    auto folded = [&](const float* rows, const LnFold& f) {
+        ConvParams q = p;
+        q.x = rows; q.bias = f.h; q.in_mode = 3; q.ln_eps = LN_EPS;
+        return conv(lin, q, f.w2, st);
+    };
+    if (!fold || tuning) {
+        if (sbgm_launch_layernorm(x, n1, a.ln1g->dev(), a.ln1b->dev(), M, C, LN_EPS, st)) return 1;
+        p.x = n1; p.bias = a.inb->dev();
+        if (conv(lin, p, *a.inw, st)) return 1;
+    }
+    if (fold && folded(x, *a.fold1)) return 1;
     if (sbgm_launch_mha_core(qkv, att, B, S, C, cfg.n_heads, st)) return 1;
     p.x = att; p.out = h; p.bias = a.outb->dev(); p.Cout = C; p.res = x;
     if (conv(lin, p, *a.outw, st)) return 1;
-    if (sbgm_launch_layernorm(h, n1, a.ln2g->dev(), a.ln2b->dev(), M, C, LN_EPS, st)) return 1;
-    p.x = n1; p.out = f1; p.bias = a.f1b->dev(); p.res = nullptr; p.act = SBGM_ACT_GELU;   // :131-132
-    if (conv(lin, p, *a.f1w, st)) return 1;
+    p.out = f1; p.res = nullptr; p.act = SBGM_ACT_GELU;   // :131-132
+    if (!fold || tuning) {
+        if (sbgm_launch_layernorm(h, n1, a.ln2g->dev(), a.ln2b->dev(), M, C, LN_EPS, st)) return 1;
+        p.x = n1; p.bias = a.f1b->dev();
+        if (conv(lin, p, *a.f1w, st)) return 1;
+    }
+    if (fold && folded(h, *a.fold2)) return 1;
     p.x = f1; p.out = x; p.bias = a.f2b->dev(); p.res = h; p.act = SBGM_ACT_NONE;
     return conv(lin, p, *a.f2w, st);
 }
@@ -801,7 +882,7 @@ int sbgm_model::forward_impl(const float* x, const float* t, const int64_t* y, c
         SBGM_CHECK(fwd_need(B, H, W, bn_train) <= ws_bytes, "forward: workspace not prepared for B=%d H=%d W=%d", B, H, W);
         ws_used = 0;
     }
-    if (refresh_derived(st, routes.up_lowres, H, W)) return 1;
+    if (refresh_derived(st, routes.up_lowres, H, W, routes.ln_fold, B)) return 1;
     partial = wsalloc(PARTIAL_FLOATS);
     if (!partial) return 1;
 
@@ -1288,7 +1369,7 @@ struct SamplerRun {
             SBGM_HIP(hipEventCreateWithFlags(&m->ev_replayed, hipEventDisableTiming));
         }
         top = m->ws + m->ws_bytes - keep();
-        if (m->refresh_derived(st, a.kind != SBGM_SAMPLER_RK45, H, W)) return 1;
+        if (m->refresh_derived(st, a.kind != SBGM_SAMPLER_RK45, H, W, a.kind != SBGM_SAMPLER_RK45, BE)) return 1;
         if (guided && conds.add_unconditional(a, m->cfg)) return 1;
         if (a.kind != SBGM_SAMPLER_RK45) {
             // The run's condition term T: the composed filter over the channels that do not change from step to step (lsm, topo, cond_img,
@@ -1666,7 +1747,7 @@ const char* sbgm_get_error();
 extern "C" {
 
 const char* sbgm_last_error(void) { return sbgm_get_error(); }
-int sbgm_abi_version(void) { return 10; }
+int sbgm_abi_version(void) { return 11; }
 int sbgm_model_config_size(void) { return (int)sizeof(sbgm_model_config); }
 
 int sbgm_model_create(const sbgm_model_config* cfg, sbgm_model** out) {
@@ -1867,7 +1948,7 @@ int sbgm_model::prepare_ws(int B, int H, int W, int bn_train, hipStream_t st, in
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (m->ensure_ws(2 * m->ws_need(B, H, W))) return 1;
-    if (m->refresh_derived(st, true, H, W)) return 1;
+    if (m->refresh_derived(st, true, H, W, true, B)) return 1;
     if (m->dummy_forward(B, H, W, true, st)) return 1;
     // the tuned plan's high-water mark, then the slab at its final size: what runs next (a sampler capturing its step) finds both settled
     if (m->dummy_forward(B, H, W, false, st)) return 1;
@@ -2058,6 +2139,48 @@ int sbgm_up_lowres_fwd(const float* x_lowres_nhwc, const float* w_packed, const 
     if (groups == 0 || normed) return 0;
     if (chunks == 0 && sbgm_launch_gn_partial(out, stats, B, H * W, C, groups, &chunks, st)) return 1;
     return sbgm_launch_groupnorm_apply(out, out, gamma, beta, nullptr, nullptr, SBGM_ACT_NONE, B, H * W, C, groups, eps, stats, chunks, st);
+}
+
+// ---- a LayerNorm folded into the linear after it (conv_igemm.hip, in_mode 3; the engine's ln_fold route, without a network) ----------
+extern "C++" {
+static ConvParams ln_linear_conv(int M, int C, int Cout, float eps) {
+    ConvParams p{};
+    p.B = 1; p.H = 1; p.W = M; p.Cs = C; p.Cout = Cout;
+    p.in_mode = 3; p.ln_eps = eps;
+    return p;
+}
+}  // extern "C++"
+
+int sbgm_ln_fold_pack(const float* w, const float* b, const float* gamma, const float* beta, int C, int Cout, float* w2_oihw, float* w2_packed,
+                      float* h, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(w2_packed, "ln_fold_pack: null tensor");
+    if (sbgm_launch_ln_fold(w, b, gamma, beta, w2_oihw, h, C, Cout, st)) return 1;
+    return sbgm_launch_pack_conv_weight(w2_oihw, w2_packed, Cout, C, 1, 1, C, st);
+}
+
+int sbgm_ln_linear_tiles(int M, int C, int Cout, int* tiles, int cap) {
+    if (M < 1 || C < 16 || C % 16 || Cout < 16 || Cout % 16 || !tiles) return 0;
+    static const float present = 0.f;
+    const ConvImages im{{&present, nullptr, nullptr, nullptr}};
+    const std::vector<ConvTile> c = sbgm_conv_candidates(ConvGeom{1, 1, 1, 0}, ln_linear_conv(M, C, Cout, LN_EPS), im, false);
+    for (int i = 0; i < (int)c.size() && i < cap; ++i) c[i].to_ints(tiles + 6 * i);
+    return (int)c.size();
+}
+
+int sbgm_ln_linear_fwd(const float* x, const float* w2_packed, const float* h, const float* res, int act, float eps, float* out, int M, int C,
+                       int Cout, const int* tile, void* stream) {
+    SBGM_CHECK(x && w2_packed && h && out, "ln_linear_fwd: null tensor");
+    SBGM_CHECK(M >= 1 && C >= 16 && C % 16 == 0 && Cout >= 16 && Cout % 16 == 0 && eps > 0.f,
+               "ln_linear_fwd: needs C %% 16 == 0, Cout %% 16 == 0 and eps > 0 (M=%d C=%d Cout=%d)", M, C, Cout);
+    SBGM_CHECK(act == SBGM_NONE || act == SBGM_RELU || act == SBGM_GELU, "ln_linear_fwd: act must be none, relu or gelu");
+    const ConvGeom lin{1, 1, 1, 0};
+    ConvParams p = ln_linear_conv(M, C, Cout, eps);
+    p.x = x; p.out = out; p.bias = h; p.res = res; p.act = act;
+    const ConvImages im{{w2_packed, nullptr, nullptr, nullptr}};
+    const bool given = tile && (tile[0] | tile[1] | tile[2] | tile[3] | tile[4] | tile[5]) != 0;      // all zeros: the static tile
+    const ConvTile ct = given ? ConvTile::from_ints(tile) : sbgm_static_tile(lin, p, im);
+    return sbgm_launch_tile(lin, p, im, ct, nullptr, (hipStream_t)stream);
 }
 
 int sbgm_time_row_layout(const int* channels, int n, int* offsets) {

@@ -22,6 +22,10 @@ int sbgm_launch_adam_ema_batched(const sbgm_adam_desc* desc_dev, float* const* e
 int sbgm_launch_ema_batched(const sbgm_adam_desc* desc_dev, float* const* ema_dev, int n, int total_blocks, float ema_rate, hipStream_t st);
 int sbgm_launch_pack_conv_weights_batched(const sbgm_pack_desc* desc_dev, int n, int total_blocks, hipStream_t st);
 int sbgm_launch_conv(const ConvGeom& g, ConvParams p, const ConvTile& cfg, float* partial_ws, hipStream_t st);
+// LayerNorm (gamma, beta) followed by a linear (w [Cout][C], b or null) as operands of the in_mode 3 launch: w2_oihw [Cout][C] =
+// W diag(gamma) (I - 11^T/C) and h [Cout] = b + W beta, fp64 sums rounded once; pack w2_oihw as an ordinary 1x1 weight
+int sbgm_launch_ln_fold(const float* w, const float* b, const float* gamma, const float* beta, float* w2_oihw, float* h, int C, int Cout,
+                        hipStream_t st);
 // A BasicBlock's 3x3 / stride 2 / pad 1 convolution (main) and its 1x1 / stride 2 shortcut (aux), both of one input, in ONE launch of
 // the implicit-GEMM kernels (conv_igemm.hip): served for a small set of tile combinations without grid split-K; the launch computes what
 // the two launches of the same tiles compute, bit for bit
