@@ -337,47 +337,6 @@ int sbgm_tconv_weight_to_oihw(const float* w, float* oihw, int Cin, int Cout, vo
     return sbgm_launch_tconv_weight(w, oihw, Cin, Cout, ST);
 }
 
-// ---- neighbourhood and threshold scores (verify_spatial.hip) -----------------------------------------------------------
-int sbgm_neighbourhood_scores_strip_columns(void) { return sbgm_neighbourhood_strip_columns(); }
-int64_t sbgm_neighbourhood_scores_workspace_bytes(int N, int H, int W, int T, int S, int64_t max_bytes) {
-    return sbgm_neighbourhood_chunk_bytes(N, H, W, T, S, max_bytes);
-}
-int sbgm_neighbourhood_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
-                              const float* thresholds, int T, const int* scales, int S, int64_t* num, int64_t* den,
-                              int64_t* events_gen, int64_t* events_obs, int64_t* valid, double* fss, double* fss_field,
-                              double* freq_bias, double* fss_useful, void* workspace, int64_t workspace_bytes, void* stream) {
-    return sbgm_launch_neighbourhood_scores(gen, obs, mask, mask_is_u8, N, No, Nm, H, W, thresholds, T, scales, S, num, den, events_gen,
-                                            events_obs, valid, fss, fss_field, freq_bias, fss_useful, workspace, workspace_bytes, ST);
-}
-int64_t sbgm_exceedance_scores_workspace_bytes(int M, int64_t HW, int T) {
-    (void)M; (void)HW; (void)T;
-    return 0;                          // the table is accumulated in place; the query exists so callers size every score alike
-}
-int sbgm_exceedance_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
-                           const float* thresholds, int T, int64_t* table, int64_t* count, double* scores, void* workspace,
-                           void* stream) {
-    (void)workspace;
-    return sbgm_launch_exceedance_scores(ens, obs, mask, mask_is_u8, M, HW, thresholds, T, table, count, scores, ST);
-}
-
-// ---- object-based verification (verify_objects.hip) --------------------------------------------------------------------
-int sbgm_object_labels(const float* fields, const void* mask, int mask_is_u8, int N, int Nm, int H, int W, float threshold,
-                       int connectivity, int* labels, int* status, void* stream) {
-    return sbgm_launch_object_labels(fields, mask, mask_is_u8, N, Nm, H, W, threshold, connectivity, labels, status, ST);
-}
-int64_t sbgm_object_scores_workspace_bytes(int N, int H, int W, int T, int64_t max_bytes) {
-    return sbgm_object_chunk_bytes(N, H, W, T, max_bytes);
-}
-int sbgm_object_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
-                       const float* thresholds, int n_fixed, int has_relative, double rel_factor, double rel_quantile, float rel_wet,
-                       int connectivity, float* threshold, int64_t* n_objects, int64_t* area, double* mass, double* V, double* r,
-                       double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A, double* L1, double* L,
-                       int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes, void* stream) {
-    return sbgm_launch_object_scores(gen, obs, mask, mask_is_u8, N, No, Nm, H, W, thresholds, n_fixed, has_relative, rel_factor,
-                                     rel_quantile, rel_wet, connectivity, threshold, n_objects, area, mass, V, r, domain_mean, com, valid,
-                                     S, L2, A, L1, L, area_hist, status, workspace, workspace_bytes, ST);
-}
-
 // ---- training path: backward entry points ---------------------------------------------------------------------------
 int sbgm_conv_pack_weight_dgrad(const float* w_oihw, float* packed, int Cout, int Cin, int KH, int KW, void* stream) {
     // operator of the data gradient: Cout' = Cin, Cin' = Cout (padded to 16), taps flipped

@@ -440,27 +440,6 @@ int sbgm_launch_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, 
 int sbgm_launch_pointwise_chain(const float* x, float* y, size_t n, int n_ops, const int* ops, const float* consts, hipStream_t st);
 int sbgm_launch_sample_extremes(const float* x, int B, size_t per, float q, float* out_max, float* out_q, hipStream_t st);
 
-// ---- verify_spatial.hip (neighbourhood and threshold scores; thresholds / scales are host arrays) ----------------------
-int sbgm_neighbourhood_strip_columns();
-int64_t sbgm_neighbourhood_chunk_bytes(int N, int H, int W, int T, int S, int64_t max_bytes);
-int sbgm_launch_neighbourhood_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H,
-                                     int W, const float* thresholds, int T, const int* scales, int S, int64_t* num, int64_t* den,
-                                     int64_t* events_gen, int64_t* events_obs, int64_t* valid, double* fss, double* fss_field,
-                                     double* freq_bias, double* fss_useful, void* workspace, int64_t workspace_bytes, hipStream_t st);
-int sbgm_launch_exceedance_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
-                                  const float* thresholds, int T, int64_t* table, int64_t* count, double* scores, hipStream_t st);
-
-// ---- verify_objects.hip (connected objects and SAL ingredients; thresholds is a host array) ------------------------------
-int sbgm_launch_object_labels(const float* fields, const void* mask, int mask_is_u8, int N, int Nm, int H, int W, float threshold,
-                              int connectivity, int* labels, int* status, hipStream_t st);
-int64_t sbgm_object_chunk_bytes(int N, int H, int W, int T, int64_t max_bytes);
-int sbgm_launch_object_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
-                              const float* thresholds, int n_fixed, int has_relative, double rel_factor, double rel_quantile,
-                              float rel_wet, int connectivity, float* threshold, int64_t* n_objects, int64_t* area, double* mass,
-                              double* V, double* r, double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A,
-                              double* L1, double* L, int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes,
-                              hipStream_t st);
-
 // ---- backward.hip (training path) ------------------------------------------------------------------------------------
 int sbgm_launch_conv_wgrad(const float* dy, const float* x, float* dw_oihw, float* dwp_ws, int B, int H, int W, int Cs, int Cin,
                            int Cout, int KH, int KW, int S, int PAD, hipStream_t st,

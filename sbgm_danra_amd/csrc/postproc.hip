@@ -17,6 +17,7 @@
 #include "chain.h"
 #include "common.h"
 #include "kernels.h"
+#include "verify_common.h"
 
 namespace {
 
@@ -34,17 +35,9 @@ __global__ __launch_bounds__(256) void pointwise_chain_kernel(const float* __res
     if (t < n) y[t] = chain_apply(x[t], p);
 }
 
-// ascending order-preserving key of an fp32 value (NaN sorts above +inf, as torch.sort places it last)
-__device__ __forceinline__ unsigned int order_key(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned int k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 // One workgroup per sample.  Selects the k0-th smallest key (0-based) with 4 passes of an 8-bit MSB-first radix histogram,
 // then one pass finds the next order statistic (k0+1) = either the same value (duplicates) or the smallest larger key.
+// The keys are verify_common.h's float_key: ascending, a NaN above +inf, as torch.sort places it last.
 __global__ __launch_bounds__(1024) void sample_extremes_kernel(const float* __restrict__ x, size_t per, unsigned int k0,
                                                                int need_next, float weight, float* __restrict__ out_max,
                                                                float* __restrict__ out_q) {
@@ -62,7 +55,7 @@ __global__ __launch_bounds__(1024) void sample_extremes_kernel(const float* __re
         unsigned int local_max = 0, local_nan = 0;
         for (size_t i = tid; i < per; i += 1024) {
             const float f = xs[i];
-            const unsigned int k = order_key(f);
+            const unsigned int k = float_key(f);
             if (pass == 0) { local_max = k > local_max ? k : local_max; local_nan |= (f != f); }
             if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 0xFF], 1u);
         }
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(1024) void sample_extremes_kernel(const float* __re
     if (need_next) {
         unsigned int cnt = 0, mn = 0xFFFFFFFFu;
         for (size_t i = tid; i < per; i += 1024) {
-            const unsigned int k = order_key(xs[i]);
+            const unsigned int k = float_key(xs[i]);
             cnt += (k <= key0);
             if (k > key0 && k < mn) mn = k;
         }
@@ -93,16 +86,16 @@ __global__ __launch_bounds__(1024) void sample_extremes_kernel(const float* __re
         __syncthreads();
     }
     if (tid == 0) {
-        const float v0 = key_value(key0);
+        const float v0 = key_float(key0);
         float q = v0;
         if (need_next) {
-            const float v1 = (sh_cnt_le >= k0 + 2) ? v0 : key_value(sh_min_gt);
+            const float v1 = (sh_cnt_le >= k0 + 2) ? v0 : key_float(sh_min_gt);
             const float diff = v1 - v0;                 // ATen lerp (native/Lerp.h): two-sided form
             q = weight < 0.5f ? v0 + weight * diff : v1 - diff * (1.f - weight);
         }
-        const float nanv = __uint_as_float(0x7FC00000u);
+        const float nanv = nan_f();
         out_q[blockIdx.x] = sh_nan ? nanv : q;          // torch.quantile / torch.max propagate NaN
-        out_max[blockIdx.x] = sh_nan ? nanv : key_value(sh_max);
+        out_max[blockIdx.x] = sh_nan ? nanv : key_float(sh_max);
     }
 }
 

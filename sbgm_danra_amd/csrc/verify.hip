@@ -6,16 +6,16 @@
 //                         members; rank histogram, mean fair / standard CRPS, skill, spread and spread/skill ratio.
 //   K44 radial_spectrum — radially averaged power spectral density of |F|^2 fields (the FFT itself is torch.fft's).
 // A pixel is valid when gen (every member, for K43) and obs are not NaN and the mask (uint8 != 0, or fp32 > 0.5) admits it.
-// Reproducibility: float sums are fp64 per-wave partials that a finalize kernel adds in a fixed order; histograms are
-// LDS-private integer bins flushed with one global integer atomic per non-empty bin per workgroup.  No float atomics.
+// Reproducibility: float sums are fp64 per-wave partials that a finalize kernel adds in a fixed order (verify_common.h,
+// block_sum_butterfly_waves); histograms are LDS-private integer bins flushed with one global integer atomic per non-empty
+// bin per workgroup.  No float atomics.  The helpers shared with the other verify files are in verify_common.h.
 // FP contraction is off in this file so that every statistic is the exact op sequence its numpy restatement performs.
 #include <algorithm>
 #include <cmath>
 
-#include "../../include/sbgm_hip.h"
-#include "common.h"
 #include "kernels.h"
 #include "philox.h"
+#include "verify_common.h"
 
 #pragma clang fp contract(off)
 
@@ -31,14 +31,6 @@ constexpr int kEnsChunk = 16;                // members held in registers per pa
 constexpr int kMaxBins = 8192;               // LDS histogram: 32 KB of uint32
 constexpr int kMaxSpectrumL = 2048;          // LDS: 4 wave rows of L/2+1 doubles
 
-__device__ __forceinline__ float nanf_() { return __uint_as_float(0x7FC00000u); }
-__device__ __forceinline__ bool is_nan(float v) { return v != v; }
-
-__device__ __forceinline__ bool mask_at(const void* mask, int mask_u8, size_t i) {
-    if (!mask) return true;
-    return mask_u8 ? static_cast<const unsigned char*>(mask)[i] != 0 : static_cast<const float*>(mask)[i] > 0.5f;
-}
-
 // 4 consecutive pixels [p0, p0+4) of one row of a [.][HW] array; out-of-range pixels read NaN.  VEC: HW % 4 == 0 and the
 // base is 16-byte aligned, so one f32x4 load; otherwise scalar loads with the tail guarded.
 template <bool VEC>
@@ -46,7 +38,7 @@ __device__ __forceinline__ f32x4 load_px4(const float* row, size_t p0, size_t HW
     if (VEC) return *reinterpret_cast<const f32x4*>(row + p0);
     f32x4 v;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (p0 + e < HW) ? row[p0 + e] : nanf_();
+    for (int e = 0; e < 4; ++e) v[e] = (p0 + e < HW) ? row[p0 + e] : nan_f();
     return v;
 }
 template <bool VEC>
@@ -69,23 +61,6 @@ __device__ __forceinline__ void mask_px4(bool (&m)[4], const void* mask, int mas
     }
 }
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// fixed-order block sum of one double: wave butterflies, then the waves in index order (deterministic for a fixed blockDim)
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int w = 0; w < kWaves; ++w) s += sh[w];
-    return s;
-}
-
 // ---- K41 error statistics ------------------------------------------------------------------------------------------------
 // grid ceil(HW / 1024): one thread owns 4 consecutive pixels and walks the N samples; wave slot = blockIdx.x * 4 + wave.
 template <bool VEC>
@@ -102,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void error_stats_kernel(const float* __re
     double sad[4] = {0, 0, 0, 0}, ssd[4] = {0, 0, 0, 0}, sg[4] = {0, 0, 0, 0}, so[4] = {0, 0, 0, 0};
     float gmin = INFINITY, gmax = -INFINITY, omin = INFINITY, omax = -INFINITY;
     for (int n = 0; n < N; ++n) {
-        f32x4 g = {nanf_(), nanf_(), nanf_(), nanf_()}, o = g;
+        f32x4 g = {nan_f(), nan_f(), nan_f(), nan_f()}, o = g;
         bool m[4] = {false, false, false, false};
         if (p0 < HW) {
             g = load_px4<VEC>(gen + (size_t)n * HW, p0, HW);
@@ -141,9 +116,9 @@ __global__ __launch_bounds__(kThreads) void error_stats_kernel(const float* __re
             const int k = cnt[e];
             const double kd = (double)k;
             pix_cnt[p] = k;
-            pix_mae[p] = k ? (float)(sad[e] / kd) : nanf_();
-            pix_rmse[p] = k ? (float)sqrt(ssd[e] / kd) : nanf_();
-            pix_bias[p] = k ? (float)(sg[e] / kd - so[e] / kd) : nanf_();
+            pix_mae[p] = k ? (float)(sad[e] / kd) : nan_f();
+            pix_rmse[p] = k ? (float)sqrt(ssd[e] / kd) : nan_f();
+            pix_bias[p] = k ? (float)(sg[e] / kd - so[e] / kd) : nan_f();
         }
         c += (double)cnt[e]; a += sad[e]; s += ssd[e]; gs += sg[e]; os += so[e];
     }
@@ -163,13 +138,13 @@ __global__ __launch_bounds__(kThreads) void error_stats_finish_kernel(const doub
                                                                       const double* __restrict__ glob_part, int N, int slots,
                                                                       double* __restrict__ sample_out, double* __restrict__ global_out) {
     __shared__ double sh[kWaves];
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double nan = nan_d();
     if ((int)blockIdx.x < N) {
         const int n = blockIdx.x;
         double v[3] = {0, 0, 0};
         for (int s = threadIdx.x; s < slots; s += kThreads)
             for (int f = 0; f < 3; ++f) v[f] += smp_part[((size_t)s * N + n) * 3 + f];
-        for (int f = 0; f < 3; ++f) v[f] = block_sum_d(v[f], sh);
+        for (int f = 0; f < 3; ++f) v[f] = block_sum_butterfly_waves<kThreads>(v[f], sh);
         if (threadIdx.x == 0) {
             sample_out[n * 3 + 0] = v[0];
             sample_out[n * 3 + 1] = v[0] > 0 ? v[1] / v[0] : nan;
@@ -185,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void error_stats_finish_kernel(const doub
         mn[0] = fminf(mn[0], (float)q[5]); mx[0] = fmaxf(mx[0], (float)q[6]);
         mn[1] = fminf(mn[1], (float)q[7]); mx[1] = fmaxf(mx[1], (float)q[8]);
     }
-    for (int f = 0; f < 5; ++f) v[f] = block_sum_d(v[f], sh);
+    for (int f = 0; f < 5; ++f) v[f] = block_sum_butterfly_waves<kThreads>(v[f], sh);
     __shared__ float shm[4][kWaves];
     const float r[4] = {wave_min(mn[0]), wave_max(mx[0]), wave_min(mn[1]), wave_max(mx[1])};
     if ((threadIdx.x & 63) == 0)
@@ -268,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void ensemble_kernel(const float* __restr
     const size_t slot = (size_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
     const size_t p = (size_t)blockIdx.x * kThreads + threadIdx.x;
     const bool inb = p < HW;
-    const float y = inb ? obs[p] : nanf_();
+    const float y = inb ? obs[p] : nan_f();
     bool valid = inb && !is_nan(y) && mask_at(mask, mask_u8, p);
     const double yd = (double)y;
     double sx = 0.0, sad = 0.0, spair = 0.0, spair2 = 0.0;
@@ -319,9 +294,9 @@ __global__ __launch_bounds__(kThreads) void ensemble_kernel(const float* __restr
         atomicAdd(&rbin[r], 1u);
         c = 1.0; cf = crps_fair; cs = crps_std; se = (mean - yd) * (mean - yd); vv = var;
     } else if (inb) {
-        mean_out[p] = nanf_();
-        var_out[p] = nanf_();
-        crps_out[p] = nanf_();
+        mean_out[p] = nan_f();
+        var_out[p] = nan_f();
+        crps_out[p] = nan_f();
         rank_out[p] = -1;
     }
     c = wave_sum_d(c); cf = wave_sum_d(cf); cs = wave_sum_d(cs); se = wave_sum_d(se); vv = wave_sum_d(vv);
@@ -342,9 +317,9 @@ __global__ __launch_bounds__(kThreads) void ensemble_finish_kernel(const double*
     double v[kEnsFields] = {0, 0, 0, 0, 0};
     for (int s = threadIdx.x; s < slots; s += kThreads)
         for (int f = 0; f < kEnsFields; ++f) v[f] += part[(size_t)s * kEnsFields + f];
-    for (int f = 0; f < kEnsFields; ++f) v[f] = block_sum_d(v[f], sh);
+    for (int f = 0; f < kEnsFields; ++f) v[f] = block_sum_butterfly_waves<kThreads>(v[f], sh);
     if (threadIdx.x == 0) {
-        const double nan = __longlong_as_double(0x7FF8000000000000ll);
+        const double nan = nan_d();
         const bool any = v[0] > 0;
         const double skill = sqrt(v[3] / v[0]), spread = sqrt(v[4] / v[0]);
         scores[0] = v[0];
@@ -421,7 +396,7 @@ __global__ __launch_bounds__(kThreads) void spectrum_finish_kernel(const double*
         double s = 0.0;
         for (int k = 0; k < nblk; ++k) s += part[(size_t)k * nb + b];
         const double denom = (double)bin_count[b] * (double)nv;
-        psd[b] = denom > 0 ? s / denom : __longlong_as_double(0x7FF8000000000000ll);
+        psd[b] = denom > 0 ? s / denom : nan_d();
     }
     if (threadIdx.x == 0) n_fields[0] = nv;
 }

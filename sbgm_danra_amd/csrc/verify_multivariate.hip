@@ -23,26 +23,14 @@
 // sqrtf, p = 1: identity, p = 2: square — three compiled paths, no powf), converted once and added in fp64 in member order.
 // A pixel owns the pairs to its half-plane neighbours, so the map needs no atomics; per offset the block sums (butterfly, then
 // waves in order) go to the workspace and variogram_collect adds the tiles in tile order.
-#include <algorithm>
-#include <cmath>
-
-#include "../../include/sbgm_hip.h"
-#include "common.h"
+// The helpers shared with the other verify files (validity, limits, block_sum_tree / block_min_tree) are in verify_common.h.
+#include "verify_common.h"
 
 #define ST ((hipStream_t)stream)
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxMembers = 4095;
-constexpr int64_t kMaxPixels = 1 << 20;
-
-__device__ __forceinline__ bool is_nan(float v) { return v != v; }
-__device__ __forceinline__ bool mask_at(const void* mask, int mask_u8, size_t i) {
-    if (!mask) return true;
-    return mask_u8 ? static_cast<const unsigned char*>(mask)[i] != 0 : static_cast<const float*>(mask)[i] > 0.5f;
-}
-__device__ __forceinline__ double nan_d() { return __longlong_as_double(0x7FF8000000000000LL); }
 
 // valid[p] and the number of valid pixels (a 64-bit integer atomic: exact in any order)
 __global__ __launch_bounds__(kThreads) void valid_kernel(const float* __restrict__ ens, const float* __restrict__ obs,
@@ -195,30 +183,6 @@ __global__ __launch_bounds__(kThreads) void energy_collect_kernel(const double* 
     D2[(size_t)j * N + i] = v;
 }
 
-// fixed-order block sum / minimum of one value per thread (tree over LDS)
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double block_min_d(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] = fmin(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // member i: sum and minimum over the other members k of the RMS distance sqrt(D2[i][k] / count), and the distance to the truth
 __global__ __launch_bounds__(kThreads) void energy_rows_kernel(const double* __restrict__ D2, const unsigned long long* __restrict__ count,
                                                                int M, double* __restrict__ rows) {
@@ -232,8 +196,8 @@ __global__ __launch_bounds__(kThreads) void energy_rows_kernel(const double* __r
         sum += d;
         mn = fmin(mn, d);
     }
-    sum = block_sum_d(sum, sh);
-    mn = block_min_d(mn, sh);
+    sum = block_sum_tree<kThreads>(sum, sh);
+    mn = block_min_tree<kThreads>(mn, sh);
     if (threadIdx.x == 0) {
         rows[i] = sum;
         rows[N + i] = mn;
@@ -251,9 +215,9 @@ __global__ __launch_bounds__(kThreads) void energy_scores_kernel(const double* _
         mn = fmin(mn, rows[N + i]);
         obs += rows[2 * N + i];
     }
-    pair = block_sum_d(pair, sh);
-    obs = block_sum_d(obs, sh);
-    mn = block_min_d(mn, sh);
+    pair = block_sum_tree<kThreads>(pair, sh);
+    obs = block_sum_tree<kThreads>(obs, sh);
+    mn = block_min_tree<kThreads>(mn, sh);
     if (threadIdx.x == 0) {
         const double m = (double)M, n = (double)*count;
         const double mean_obs = obs / m;
@@ -435,7 +399,7 @@ __global__ __launch_bounds__(kThreads) void variogram_map_kernel(const double* _
     if (p >= HW) return;
     double v = 0.0;
     for (int g = 0; g < n_groups; ++g) v += map_part[(size_t)g * HW + p];
-    vs_map[p] = valid[p] ? (float)v : __uint_as_float(0x7FC00000u);
+    vs_map[p] = valid[p] ? (float)v : nan_f();
 }
 
 // per offset the tiles in tile order; then the offsets in table order

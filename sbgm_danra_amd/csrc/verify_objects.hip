@@ -36,21 +36,17 @@
 // 64-bit integer atomics after a wave has summed the pixels it holds of one object.  No floating-point atomics.  The fp64
 // sums over objects are made per segment of 4096 slots by one workgroup: thread t adds the segment's slots t, t + 256, ...
 // in ascending order, then a fixed tree over the 256 threads; one thread per problem then adds the segments in ascending
-// order.  The scores are computed by single threads.  FP contraction is off in this file.
-#include <algorithm>
-#include <cmath>
-
-#include "../../include/sbgm_hip.h"
-#include "common.h"
-#include "kernels.h"
+// order.  The scores are computed by single threads.  FP contraction is off in this file.  The helpers shared with the other
+// verify files (validity, the key, ThrList, limits, block reductions, the chunk planner) are in verify_common.h; kMaxThr
+// there bounds the fixed thresholds, the relative one is an extra index.
+#include "verify_common.h"
 
 #pragma clang fp contract(off)
 
+#define ST ((hipStream_t)stream)
+
 namespace {
 
-constexpr int kMaxThr = SBGM_OBJECTS_MAX_THRESHOLDS;      // fixed thresholds; the relative one is an extra index
-constexpr int kMaxSide = 2048;
-constexpr int64_t kMaxPixels = 1ll << 20;
 constexpr int kRowThreads = 256;                          // runs: one workgroup per row,
 constexpr int kRowPer = kMaxSide / kRowThreads;           // each thread owns 8 consecutive columns
 constexpr int kPix = 256;                                 // merge / flatten: one pixel per thread
@@ -66,8 +62,6 @@ constexpr int64_t kMaxChunkProblems = 65534;              // gridDim.y
 constexpr int64_t kProblemBytes = 36;                     // per pixel of one problem: 3 x int64, area, peak key, lab
 constexpr int64_t kSegmentBytes = (kPartSums + kPartCounts) * 8;      // per segment of one problem: the two partials
 
-struct ThrList { float v[kMaxThr]; };
-
 // where the problems of a launch come from.  labels_mode: problem q is field q of `gen` at thr_host.  Otherwise problem q is
 // side q & 1 of pair q >> 1, pair = (field f0 + pair / nt, threshold t0 + pair % nt), at threshold[side][f][t] on the device.
 struct Src {
@@ -77,12 +71,6 @@ struct Src {
 };
 struct Prob { int side, f, t; const float* v; float thr; };
 
-__device__ __forceinline__ bool is_nan(float v) { return v != v; }
-__device__ __forceinline__ double nan_d() { return __longlong_as_double(0x7FF8000000000000ll); }
-__device__ __forceinline__ bool mask_at(const void* mask, int mask_u8, size_t i) {
-    if (!mask) return true;
-    return mask_u8 ? static_cast<const unsigned char*>(mask)[i] != 0 : static_cast<const float*>(mask)[i] > 0.5f;
-}
 __device__ __forceinline__ Prob problem(const Src& s, int q) {
     Prob p;
     const size_t HW = (size_t)s.H * s.W;
@@ -101,13 +89,6 @@ __device__ __forceinline__ bool valid_at(const Src& s, int f, size_t i) {
     return !is_nan(s.gen[(size_t)f * HW + i]) && !is_nan(s.obs[(size_t)f * s.obs_step * HW + i]) &&
            mask_at(s.mask, s.mask_u8, (size_t)f * s.mask_step * HW + i);
 }
-// monotone map of the non-NaN floats onto uint32 (-0 just below +0), and back; no float maps to 0
-__device__ __forceinline__ unsigned int key_of(float v) {
-    const unsigned int b = __float_as_uint(v);
-    return (b >> 31) ? ~b : b | 0x80000000u;
-}
-__device__ __forceinline__ float float_of(unsigned int k) { return __uint_as_float((k >> 31) ? k & 0x7FFFFFFFu : ~k); }
-
 __device__ __forceinline__ unsigned int lab_load(const unsigned int* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -227,33 +208,6 @@ __global__ __launch_bounds__(kPix) void object_spread_kernel(unsigned int* __res
     lab[p] = lab[mine - 1u];
 }
 
-// ---- block reductions of the prepare kernel ------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned int wave_max_u32(unsigned int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned int)__shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned int wave_min_u32(unsigned int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned int)__shfl_xor(v, o, 64));
-    return v;
-}
-// every thread gets the sum over the workgroup (integers: the order does not matter); `slot` holds one entry per wave
-__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* slot) {
-    v = wave_sum_u64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-    __syncthreads();
-    unsigned long long t = 0;
-    for (int w = 0; w < kPrepThreads / SBGM_WAVE; ++w) t += slot[w];
-    return t;
-}
-
 // ---- K52 prepare: grid (N, 2), one workgroup per (field, side) ---------------------------------------------------------------
 // Sweeps its field a few times: (1) valid count, max |v| and the count of values >= wet; (2) the fixed-point sums of v,
 // v * row and v * col -> domain_mean, com; then, for the relative threshold, (3..6) a radix select of the order statistic
@@ -283,8 +237,8 @@ __global__ __launch_bounds__(kPrepThreads) void object_prepare_kernel(Src s, int
         cntw += x >= wet;
         mx = max(mx, __float_as_uint(x) & 0x7FFFFFFFu);       // |x| as bits: integer order is magnitude order
     }
-    const unsigned long long nvalid = block_sum_u64(cnt, slot);
-    const unsigned long long nwet = block_sum_u64(cntw, slot);
+    const unsigned long long nvalid = block_sum_u64<kPrepThreads>(cnt, slot);
+    const unsigned long long nwet = block_sum_u64<kPrepThreads>(cntw, slot);
     mx = wave_max_u32(mx);
     if ((tid & 63) == 0) wmax[tid >> 6] = mx;
     __syncthreads();
@@ -303,9 +257,9 @@ __global__ __launch_bounds__(kPrepThreads) void object_prepare_kernel(Src s, int
         const long long fx = fabsf(x) < __builtin_inff() ? __double2ll_rn((double)x * up) : 0;
         s0 += fx; s1 += fx * (p / W); s2 += fx * (p % W);
     }
-    const long long t0 = (long long)block_sum_u64((unsigned long long)s0, slot);
-    const long long t1 = (long long)block_sum_u64((unsigned long long)s1, slot);
-    const long long t2 = (long long)block_sum_u64((unsigned long long)s2, slot);
+    const long long t0 = (long long)block_sum_u64<kPrepThreads>((unsigned long long)s0, slot);
+    const long long t1 = (long long)block_sum_u64<kPrepThreads>((unsigned long long)s1, slot);
+    const long long t2 = (long long)block_sum_u64<kPrepThreads>((unsigned long long)s2, slot);
     if (tid == 0) {
         fexp[sf] = e;
         if (side == 0) valid[f] = (long long)nvalid;
@@ -317,7 +271,7 @@ __global__ __launch_bounds__(kPrepThreads) void object_prepare_kernel(Src s, int
     if (!has_rel) return;
     float* out = threshold + sf * s.T + Tfixed;
     if (nwet == 0) {                                          // uniform over the workgroup
-        if (tid == 0) *out = __uint_as_float(0x7FC00000u);
+        if (tid == 0) *out = nan_f();
         return;
     }
     const double h = quantile * (double)(nwet - 1);
@@ -332,7 +286,7 @@ __global__ __launch_bounds__(kPrepThreads) void object_prepare_kernel(Src s, int
             if (!valid_at(s, f, p)) continue;
             const float x = v[p];
             if (!(x >= wet)) continue;
-            const unsigned int k = key_of(x);
+            const unsigned int k = float_key(x);
             if ((k & himask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
         }
         __syncthreads();
@@ -358,7 +312,7 @@ __global__ __launch_bounds__(kPrepThreads) void object_prepare_kernel(Src s, int
             if (!valid_at(s, f, p)) continue;
             const float x = v[p];
             if (!(x >= wet)) continue;
-            const unsigned int k = key_of(x);
+            const unsigned int k = float_key(x);
             if (k > klo) mn = min(mn, k);
         }
         mn = wave_min_u32(mn);
@@ -366,7 +320,7 @@ __global__ __launch_bounds__(kPrepThreads) void object_prepare_kernel(Src s, int
         __syncthreads();
     }
     if (tid == 0) {
-        const float xlo = float_of(klo), xhi = need_hi ? float_of(sel_min) : xlo;
+        const float xlo = key_float(klo), xhi = need_hi ? key_float(sel_min) : xlo;
         const float qv = (g == 0.0 || xlo == xhi) ? xlo : (float)((double)xlo + g * ((double)xhi - (double)xlo));
         *out = (float)(factor * (double)qv);
     }
@@ -418,7 +372,7 @@ __global__ __launch_bounds__(256) void object_accumulate_kernel(Src s, const uns
                 root = lab[l1 - 1u] - 1u;                     // run start -> root (a root points at itself)
                 const float x = pr.v[p];
                 fx = fabsf(x) < __builtin_inff() ? __double2ll_rn((double)x * up) : 0;
-                k = key_of(x);
+                k = float_key(x);
             }
         }
         const bool has = root != kNone;
@@ -438,18 +392,8 @@ __global__ __launch_bounds__(256) void object_accumulate_kernel(Src s, const uns
 
 // ---- K52 sums: grid (segments of 4096 slots, problems) -----------------------------------------------------------------------
 // Slot i with area > 0 is the object with label i + 1: R = mass, x_n = (mass * row, mass * col) / mass, Rmax from the peak key.
-// Thread t adds the segment's slots t, t + 256, ... in ascending order; tree_sum then adds the 256 partial sums in a fixed
-// order.  part_sums fp64 [problems][segments][3]; part_counts int64 [problems][segments][2] = (objects, area).
-__device__ __forceinline__ double tree_sum(double v, double* buf) {
-    __syncthreads();
-    buf[threadIdx.x] = v;
-    __syncthreads();
-    for (int st = kFinThreads / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) buf[threadIdx.x] += buf[threadIdx.x + st];
-        __syncthreads();
-    }
-    return buf[0];
-}
+// Thread t adds the segment's slots t, t + 256, ... in ascending order; block_sum_tree then adds the 256 partial sums in a
+// fixed order.  part_sums fp64 [problems][segments][3]; part_counts int64 [problems][segments][2] = (objects, area).
 __global__ __launch_bounds__(kFinThreads) void object_sums_kernel(Src s, const int* __restrict__ fexp, const long long* __restrict__ acc_all,
                                                                   const unsigned int* __restrict__ area_all,
                                                                   const unsigned int* __restrict__ peak_all, const double* __restrict__ com,
@@ -478,11 +422,12 @@ __global__ __launch_bounds__(kFinThreads) void object_sums_kernel(Src s, const i
         const double dr = cr - (double)acc[(size_t)HW + i] / mi, dc = cc - (double)acc[2 * (size_t)HW + i] / mi;
         sR += R;
         sRd += R * sqrt(dr * dr + dc * dc);
-        sRV += R * (R / (double)float_of(pk[i]));
+        sRV += R * (R / (double)key_float(pk[i]));
         ++nobj; atot += a;
         atomicAdd(&bins[31 - __clz(a)], 1u);
     }
-    const double tR = tree_sum(sR, buf), tRd = tree_sum(sRd, buf), tRV = tree_sum(sRV, buf);
+    const double tR = block_sum_tree<kFinThreads>(sR, buf), tRd = block_sum_tree<kFinThreads>(sRd, buf),
+                 tRV = block_sum_tree<kFinThreads>(sRV, buf);
     nobj = wave_sum_u64(nobj); atot = wave_sum_u64(atot);
     if ((threadIdx.x & 63) == 0) { atomicAdd(&cnt[0], nobj); atomicAdd(&cnt[1], atot); }
     __syncthreads();
@@ -549,19 +494,14 @@ __global__ __launch_bounds__(256) void object_scores_kernel(int N, int T, int H,
     if (t == 0) { A[f] = a; L1[f] = l1; }
 }
 
-inline bool shape_ok(int N, int H, int W) {
-    return N >= 1 && N <= 65535 && H >= 2 && W >= 2 && H <= kMaxSide && W <= kMaxSide && (int64_t)H * W <= kMaxPixels;
-}
 inline int64_t head_bytes(int N) { return ((int64_t)2 * N * (int64_t)sizeof(int) + 255) / 256 * 256; }
 inline int segments(int HW) { return (HW + kSegSlots - 1) / kSegSlots; }
 inline int64_t pair_bytes(int H, int W) {
     return 2 * (kProblemBytes * (int64_t)H * W + (int64_t)segments(H * W) * kSegmentBytes);
 }
-// (field, threshold) pairs per chunk: whole fields while they fit into max_bytes, else thresholds of one field; at least one
-inline int64_t chunk_pairs(int N, int H, int W, int T, int64_t max_bytes) {
-    const int64_t room = std::max<int64_t>(0, max_bytes - head_bytes(N));
-    const int64_t fit = std::min(kMaxChunkProblems / 2, std::max<int64_t>(1, room / pair_bytes(H, W)));
-    return fit >= T ? std::min<int64_t>(fit / T, N) * T : fit;
+// a pair is two problems (gen and obs); the head (fexp) comes off the room first
+inline ChunkPlan chunk_plan(int N, int H, int W, int T, int64_t max_bytes) {
+    return plan_chunks(N, T, std::max<int64_t>(0, max_bytes - head_bytes(N)), pair_bytes(H, W), kMaxChunkProblems / 2);
 }
 inline int pix_blocks(int HW) { return (HW + kPix - 1) / kPix; }
 
@@ -578,10 +518,13 @@ int label_launches(const Src& src, unsigned int* lab, int nprob, int conn8, int*
 
 }  // namespace
 
-int sbgm_launch_object_labels(const float* fields, const void* mask, int mask_is_u8, int N, int Nm, int H, int W, float threshold,
-                              int connectivity, int* labels, int* status, hipStream_t st) {
+extern "C" {
+
+int sbgm_object_labels(const float* fields, const void* mask, int mask_is_u8, int N, int Nm, int H, int W, float threshold,
+                       int connectivity, int* labels, int* status, void* stream) {
+    hipStream_t st = ST;
     SBGM_CHECK(fields && labels && status, "object_labels: null argument");
-    SBGM_CHECK(shape_ok(N, H, W), "object_labels: N=%d H=%d W=%d (N 1..65535, sides 2..%d, H*W <= 2^20)", N, H, W, kMaxSide);
+    SBGM_CHECK(field_shape_ok(N, H, W), "object_labels: N=%d H=%d W=%d (N 1..65535, sides 2..%d, H*W <= 2^20)", N, H, W, kMaxSide);
     SBGM_CHECK(!mask || Nm == 1 || Nm == N, "object_labels: mask has %d fields; need 1 or N=%d", Nm, N);
     SBGM_CHECK(connectivity == 4 || connectivity == 8, "object_labels: connectivity %d; need 4 or 8", connectivity);
     SBGM_CHECK(std::isfinite(threshold), "object_labels: the threshold is not finite");
@@ -594,20 +537,20 @@ int sbgm_launch_object_labels(const float* fields, const void* mask, int mask_is
     return 0;
 }
 
-int64_t sbgm_object_chunk_bytes(int N, int H, int W, int T, int64_t max_bytes) {
-    if (!shape_ok(N, H, W) || T < 1 || T > kMaxThr + 1) return 0;
-    return head_bytes(N) + chunk_pairs(N, H, W, T, max_bytes) * pair_bytes(H, W);
+int64_t sbgm_object_scores_workspace_bytes(int N, int H, int W, int T, int64_t max_bytes) {
+    if (!field_shape_ok(N, H, W) || T < 1 || T > kMaxThr + 1) return 0;
+    return head_bytes(N) + chunk_plan(N, H, W, T, max_bytes).pairs * pair_bytes(H, W);
 }
 
-int sbgm_launch_object_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
-                              const float* thresholds, int n_fixed, int has_relative, double rel_factor, double rel_quantile,
-                              float rel_wet, int connectivity, float* threshold, int64_t* n_objects, int64_t* area, double* mass,
-                              double* V, double* r, double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A,
-                              double* L1, double* L, int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes,
-                              hipStream_t st) {
+int sbgm_object_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
+                       const float* thresholds, int n_fixed, int has_relative, double rel_factor, double rel_quantile, float rel_wet,
+                       int connectivity, float* threshold, int64_t* n_objects, int64_t* area, double* mass, double* V, double* r,
+                       double* domain_mean, double* com, int64_t* valid, double* S, double* L2, double* A, double* L1, double* L,
+                       int64_t* area_hist, int* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    hipStream_t st = ST;
     SBGM_CHECK(gen && obs && threshold && n_objects && area && mass && V && r && domain_mean && com && valid && S && L2 && A && L1 && L &&
                area_hist && status && workspace, "object_scores: null argument");
-    SBGM_CHECK(shape_ok(N, H, W), "object_scores: N=%d H=%d W=%d (N 1..65535, sides 2..%d, H*W <= 2^20)", N, H, W, kMaxSide);
+    SBGM_CHECK(field_shape_ok(N, H, W), "object_scores: N=%d H=%d W=%d (N 1..65535, sides 2..%d, H*W <= 2^20)", N, H, W, kMaxSide);
     SBGM_CHECK(No == 1 || No == N, "object_scores: obs has %d fields; need 1 or N=%d", No, N);
     SBGM_CHECK(!mask || Nm == 1 || Nm == N, "object_scores: mask has %d fields; need 1 or N=%d", Nm, N);
     SBGM_CHECK(connectivity == 4 || connectivity == 8, "object_scores: connectivity %d; need 4 or 8", connectivity);
@@ -615,18 +558,14 @@ int sbgm_launch_object_scores(const float* gen, const float* obs, const void* ma
                kMaxThr);
     const int T = n_fixed + (has_relative ? 1 : 0);
     SBGM_CHECK(T >= 1, "object_scores: no threshold given");
-    ThrList thr{};
-    for (int t = 0; t < n_fixed; ++t) {
-        SBGM_CHECK(std::isfinite(thresholds[t]), "object_scores: threshold %d is not finite", t);
-        thr.v[t] = thresholds[t];
-    }
+    ThrList thr;
+    if (int rc = fill_thresholds("object_scores", thresholds, n_fixed, thr)) return rc;
     if (has_relative)
         SBGM_CHECK(std::isfinite(rel_factor) && rel_quantile >= 0.0 && rel_quantile <= 1.0 && std::isfinite(rel_wet),
                    "object_scores: relative threshold needs a finite factor, a quantile in [0, 1] and a finite wet value");
     const int64_t pb = pair_bytes(H, W), hb = head_bytes(N);
     SBGM_CHECK(workspace_bytes >= hb + pb, "object_scores: workspace of %lld bytes; one field x one threshold needs %lld",
                (long long)workspace_bytes, (long long)(hb + pb));
-    const int64_t pairs = chunk_pairs(N, H, W, T, workspace_bytes);
     const int HW = H * W, nseg = segments(HW);
     int* fexp = static_cast<int*>(workspace);
     char* chunk = static_cast<char*>(workspace) + hb;
@@ -636,36 +575,36 @@ int sbgm_launch_object_scores(const float* gen, const float* obs, const void* ma
     hipLaunchKernelGGL(object_prepare_kernel, dim3(N, 2), dim3(kPrepThreads), 0, st, src, n_fixed, thr, has_relative, rel_factor,
                        rel_quantile, rel_wet, threshold, reinterpret_cast<long long*>(valid), domain_mean, com, fexp);
     SBGM_LAUNCH_CHECK();
-    const int cf = pairs >= T ? (int)(pairs / T) : 1, ct = pairs >= T ? T : (int)pairs;      // fields x thresholds of a full chunk
-    for (int f0 = 0; f0 < N; f0 += cf) {
-        const int nf = std::min(cf, N - f0);
-        for (int t0 = 0; t0 < T; t0 += ct) {
-            const int nt = std::min(ct, T - t0), np = 2 * nf * nt;
-            // the chunk: part_sums fp64 [np][nseg][3], part_counts int64 [np][nseg][2], acc int64 [np][3][HW], area [np][HW],
-            // peak [np][HW] (the last three zeroed together; np is even, so they start on a 16-byte boundary), then lab [np][HW]
-            double* part_sums = reinterpret_cast<double*>(chunk);
-            long long* part_counts = reinterpret_cast<long long*>(part_sums + (size_t)np * nseg * kPartSums);
-            long long* acc = part_counts + (size_t)np * nseg * kPartCounts;
-            unsigned int* ar = reinterpret_cast<unsigned int*>(acc + (size_t)np * 3 * HW);
-            unsigned int* pk = ar + (size_t)np * HW;
-            unsigned int* lab = pk + (size_t)np * HW;
-            src.f0 = f0; src.t0 = t0; src.nt = nt;
-            if (int rc = sbgm_zero_async(acc, (size_t)np * 32 * HW, st)) return rc;
-            if (int rc = label_launches(src, lab, np, connectivity == 8, status, st)) return rc;
-            hipLaunchKernelGGL(object_accumulate_kernel, dim3((HW + kAccBlock - 1) / kAccBlock, np), dim3(256), 0, st, src, lab, fexp, acc,
-                               ar, pk);
-            SBGM_LAUNCH_CHECK();
-            hipLaunchKernelGGL(object_sums_kernel, dim3(nseg, np), dim3(kFinThreads), 0, st, src, fexp, acc, ar, pk, com, part_sums,
-                               part_counts, reinterpret_cast<unsigned long long*>(area_hist));
-            SBGM_LAUNCH_CHECK();
-            hipLaunchKernelGGL(object_collect_kernel, dim3((np + 63) / 64), dim3(64), 0, st, src, part_sums, part_counts, nseg, np,
-                               reinterpret_cast<long long*>(n_objects), reinterpret_cast<long long*>(area), mass, V, r);
-            SBGM_LAUNCH_CHECK();
-        }
-    }
+    const int rc = for_each_chunk(chunk_plan(N, H, W, T, workspace_bytes), N, T, [&](int f0, int nf, int t0, int nt) -> int {
+        const int np = 2 * nf * nt;
+        // the chunk: part_sums fp64 [np][nseg][3], part_counts int64 [np][nseg][2], acc int64 [np][3][HW], area [np][HW],
+        // peak [np][HW] (the last three zeroed together; np is even, so they start on a 16-byte boundary), then lab [np][HW]
+        double* part_sums = reinterpret_cast<double*>(chunk);
+        long long* part_counts = reinterpret_cast<long long*>(part_sums + (size_t)np * nseg * kPartSums);
+        long long* acc = part_counts + (size_t)np * nseg * kPartCounts;
+        unsigned int* ar = reinterpret_cast<unsigned int*>(acc + (size_t)np * 3 * HW);
+        unsigned int* pk = ar + (size_t)np * HW;
+        unsigned int* lab = pk + (size_t)np * HW;
+        src.f0 = f0; src.t0 = t0; src.nt = nt;
+        if (int rc = sbgm_zero_async(acc, (size_t)np * 32 * HW, st)) return rc;
+        if (int rc = label_launches(src, lab, np, connectivity == 8, status, st)) return rc;
+        hipLaunchKernelGGL(object_accumulate_kernel, dim3((HW + kAccBlock - 1) / kAccBlock, np), dim3(256), 0, st, src, lab, fexp, acc, ar,
+                           pk);
+        SBGM_LAUNCH_CHECK();
+        hipLaunchKernelGGL(object_sums_kernel, dim3(nseg, np), dim3(kFinThreads), 0, st, src, fexp, acc, ar, pk, com, part_sums,
+                           part_counts, reinterpret_cast<unsigned long long*>(area_hist));
+        SBGM_LAUNCH_CHECK();
+        hipLaunchKernelGGL(object_collect_kernel, dim3((np + 63) / 64), dim3(64), 0, st, src, part_sums, part_counts, nseg, np,
+                           reinterpret_cast<long long*>(n_objects), reinterpret_cast<long long*>(area), mass, V, r);
+        SBGM_LAUNCH_CHECK();
+        return 0;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(object_scores_kernel, dim3((N * T + 255) / 256), dim3(256), 0, st, N, T, H, W,
                        reinterpret_cast<const long long*>(valid), domain_mean, com, reinterpret_cast<const long long*>(n_objects), V, r, S,
                        L2, A, L1, L);
     SBGM_LAUNCH_CHECK();
     return 0;
 }
+
+}  // extern "C"

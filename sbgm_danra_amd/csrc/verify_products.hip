@@ -15,11 +15,8 @@
 // maps are bit-equal to min / max.  Order statistics and counts do not depend on the member order.
 // Reproducibility: no float atomics (the only atomic is the 64-bit integer add of the valid-pixel count).
 // FP contraction is off in this file, as in verify.hip: the fp64 expressions are the op sequences of the numpy restatement.
-#include <algorithm>
-#include <cmath>
-
-#include "../../include/sbgm_hip.h"
-#include "common.h"
+// The helpers shared with the other verify files (validity, ThrList, limits, the key) are in verify_common.h.
+#include "verify_common.h"
 
 #pragma clang fp contract(off)
 
@@ -29,35 +26,18 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;
-constexpr int kMaxThr = SBGM_PRODUCTS_MAX_THRESHOLDS;
 constexpr int kMaxQuant = SBGM_PRODUCTS_MAX_QUANTILES;
-constexpr int kMaxMembers = 4095;
 constexpr int kQuantPerLaunch = 8;           // 16 ranks: 16 prefixes, candidates and counters in registers (77 VGPRs)
 
-struct ThrList { float v[kMaxThr]; };
 // one launch's quantiles: x_(lo), x_(hi) and the weight g of x_(hi)
 template <int NQ>
 struct QuantGroup { int lo[NQ], hi[NQ]; double g[NQ]; };
 
-__device__ __forceinline__ float nanf_() { return __uint_as_float(0x7FC00000u); }
-__device__ __forceinline__ bool is_nan(float v) { return v != v; }
-__device__ __forceinline__ bool mask_at(const void* mask, int mask_u8, size_t i) {
-    if (!mask) return true;
-    return mask_u8 ? static_cast<const unsigned char*>(mask)[i] != 0 : static_cast<const float*>(mask)[i] > 0.5f;
-}
-// order-preserving image of a non-NaN fp32 value, and its inverse
-__device__ __forceinline__ unsigned int key_of(float v) {
-    unsigned int u = __float_as_uint(v);
-    u = u == 0x80000000u ? 0u : u;
-    return u ^ ((unsigned int)((int)u >> 31) | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned int k) {
-    return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+// the key of a member: -0 is folded onto +0 before float_key, which alone would place it just below +0.  So the two zeros are
+// one order statistic here, and a zero minimum, maximum or quantile is +0 in every map whichever zero the members held.
+__device__ __forceinline__ unsigned int member_key(float v) {
+    const unsigned int b = __float_as_uint(v);
+    return float_key(__uint_as_float(b == 0x80000000u ? 0u : b));
 }
 
 __global__ __launch_bounds__(kThreads) void products_moments_kernel(const float* __restrict__ ens, const void* __restrict__ mask,
@@ -83,7 +63,7 @@ __global__ __launch_bounds__(kThreads) void products_moments_kernel(const float*
                 const float v = col[(size_t)m * HW];
                 valid = valid && !is_nan(v);
                 sum += (double)v;
-                const unsigned int key = key_of(v);
+                const unsigned int key = member_key(v);
                 kmin = min(kmin, key);
                 kmax = max(kmax, key);
 #pragma unroll
@@ -99,13 +79,13 @@ __global__ __launch_bounds__(kThreads) void products_moments_kernel(const float*
             }
         }
         nvalid += valid;
-        mean[p] = valid ? (float)mu : nanf_();
-        sdev[p] = valid ? (float)sqrt(ss / (double)(M - 1)) : nanf_();
-        vmin[p] = valid ? value_of(kmin) : nanf_();
-        vmax[p] = valid ? value_of(kmax) : nanf_();
+        mean[p] = valid ? (float)mu : nan_f();
+        sdev[p] = valid ? (float)sqrt(ss / (double)(M - 1)) : nan_f();
+        vmin[p] = valid ? key_float(kmin) : nan_f();
+        vmax[p] = valid ? key_float(kmax) : nan_f();
 #pragma unroll
         for (int t = 0; t < kMaxThr; ++t)
-            if (t < T) exceed[(size_t)t * HW + p] = valid ? (float)((double)k[t] / (double)M) : nanf_();
+            if (t < T) exceed[(size_t)t * HW + p] = valid ? (float)((double)k[t] / (double)M) : nan_f();
     }
     nvalid = wave_sum_u64(nvalid);
     if ((threadIdx.x & 63) == 0 && nvalid) atomicAdd(count, nvalid);
@@ -120,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void products_quantile_kernel(const float
     for (size_t p = (size_t)blockIdx.x * kThreads + threadIdx.x; p < HW; p += (size_t)gridDim.x * kThreads) {
         if (is_nan(vmin[p])) {
 #pragma unroll
-            for (int j = 0; j < NQ; ++j) quant[(size_t)j * HW + p] = nanf_();
+            for (int j = 0; j < NQ; ++j) quant[(size_t)j * HW + p] = nan_f();
             continue;
         }
         const float* col = ens + p;
@@ -133,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void products_quantile_kernel(const float
             for (int s = 0; s < S; ++s) { cand[s] = prefix[s] | (1u << bit); below[s] = 0u; }
 #pragma unroll 4
             for (int m = 0; m < M; ++m) {
-                const unsigned int key = key_of(col[(size_t)m * HW]);
+                const unsigned int key = member_key(col[(size_t)m * HW]);
 #pragma unroll
                 for (int s = 0; s < S; ++s) below[s] += key < cand[s];
             }
@@ -145,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void products_quantile_kernel(const float
         }
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
-            const float a = value_of(prefix[2 * j]), b = value_of(prefix[2 * j + 1]);
+            const float a = key_float(prefix[2 * j]), b = key_float(prefix[2 * j + 1]);
             const double g = qg.g[j];
             quant[(size_t)j * HW + p] = (g == 0.0 || a == b) ? a : (float)((double)a + g * ((double)b - (double)a));
         }
@@ -182,11 +162,8 @@ int sbgm_ensemble_products(const float* ens, const void* mask, int mask_is_u8, i
                "levels and maps)", Q, kMaxQuant);
     SBGM_CHECK(T >= 0 && T <= kMaxThr && (T == 0 || (thresholds && exceed)), "ensemble_products: %d thresholds (0..%d, with their "
                "values and maps)", T, kMaxThr);
-    ThrList thr{};
-    for (int t = 0; t < T; ++t) {
-        SBGM_CHECK(std::isfinite(thresholds[t]), "ensemble_products: threshold %d is not finite", t);
-        thr.v[t] = thresholds[t];
-    }
+    ThrList thr;
+    if (int rc = fill_thresholds("ensemble_products", thresholds, T, thr)) return rc;
     int lo[kMaxQuant], hi[kMaxQuant];
     double g[kMaxQuant];
     for (int q = 0; q < Q; ++q) {

@@ -8,22 +8,17 @@
 // an event is `v >= thr` in fp32 at a valid pixel.
 // Reproducibility: counts are integers (LDS-private bins and per-wave partials; the only global atomics are 64-bit integer
 // adds), and the fp64 scores are computed by single threads of the finalize kernels in a fixed order.  No float atomics.
-// FP contraction is off in this file, as in verify.hip.
-#include <algorithm>
-#include <cmath>
-
-#include "../../include/sbgm_hip.h"
-#include "common.h"
-#include "kernels.h"
+// FP contraction is off in this file, as in verify.hip.  The helpers shared with the other verify files (validity, ThrList,
+// limits, the chunk planner) are in verify_common.h.
+#include "verify_common.h"
 
 #pragma clang fp contract(off)
 
+#define ST ((hipStream_t)stream)
+
 namespace {
 
-constexpr int kMaxThr = SBGM_SPATIAL_MAX_THRESHOLDS;
 constexpr int kMaxScales = SBGM_SPATIAL_MAX_SCALES;
-constexpr int kMaxSide = 2048;
-constexpr int64_t kMaxPixels = 1ll << 20;
 constexpr int kRowThreads = 256;                          // K45 pass 1: one workgroup per row,
 constexpr int kRowPer = kMaxSide / kRowThreads;           // each thread owns 8 consecutive columns
 constexpr int kStrip = 256;                               // K45 pass 2: columns per workgroup, one per lane
@@ -32,22 +27,8 @@ constexpr int64_t kMaxChunkPairs = 65535;                 // gridDim.z of pass 2
 constexpr int kExcThreads = 512;
 constexpr int kExcMaxBlocks = 256;
 constexpr int kExcLdsBytes = 32768;                       // LDS tables of one workgroup: (M + 1) * 8 bytes per threshold
-constexpr int kMaxMembers = 4095;
 
-struct ThrList { float v[kMaxThr]; };
 struct ScaleList { int r[kMaxScales]; };                  // window radii, clamped to max(H, W)
-
-__device__ __forceinline__ bool is_nan(float v) { return v != v; }
-__device__ __forceinline__ double nan_d() { return __longlong_as_double(0x7FF8000000000000ll); }
-__device__ __forceinline__ bool mask_at(const void* mask, int mask_u8, size_t i) {
-    if (!mask) return true;
-    return mask_u8 ? static_cast<const unsigned char*>(mask)[i] != 0 : static_cast<const float*>(mask)[i] > 0.5f;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- K45 pass 1: row-wise inclusive prefix sums of the two indicator images ------------------------------------------------
 // grid (H, nf): the workgroup reads row `blockIdx.x` of field f0 + blockIdx.y once and, for each of the nt thresholds from t0,
@@ -304,41 +285,38 @@ inline int strips(int W) { return (W + kStrip - 1) / kStrip; }
 inline int64_t pair_bytes(int H, int W, int S) {
     return (int64_t)H * W * (int64_t)sizeof(unsigned int) + (int64_t)S * strips(W) * kStripWaves * 2 * (int64_t)sizeof(unsigned long long);
 }
-// (field, threshold) pairs per chunk: whole fields while they fit into max_bytes, else thresholds of one field; at least one
-inline int64_t chunk_pairs(int N, int H, int W, int T, int S, int64_t max_bytes) {
-    const int64_t fit = std::min(kMaxChunkPairs, std::max<int64_t>(1, max_bytes / pair_bytes(H, W, S)));
-    return fit >= T ? std::min<int64_t>(fit / T, N) * T : fit;
+inline ChunkPlan chunk_plan(int N, int H, int W, int T, int S, int64_t max_bytes) {
+    return plan_chunks(N, T, max_bytes, pair_bytes(H, W, S), kMaxChunkPairs);
 }
 inline bool shape_ok(int N, int H, int W, int T, int S) {
-    return N >= 1 && N <= 65535 && H >= 2 && W >= 2 && H <= kMaxSide && W <= kMaxSide && (int64_t)H * W <= kMaxPixels && T >= 1 &&
-           T <= kMaxThr && S >= 1 && S <= kMaxScales;
+    return field_shape_ok(N, H, W) && T >= 1 && T <= kMaxThr && S >= 1 && S <= kMaxScales;
 }
 
 }  // namespace
 
-int sbgm_neighbourhood_strip_columns() { return kStrip; }
+extern "C" {
 
-int64_t sbgm_neighbourhood_chunk_bytes(int N, int H, int W, int T, int S, int64_t max_bytes) {
+int sbgm_neighbourhood_scores_strip_columns(void) { return kStrip; }
+
+int64_t sbgm_neighbourhood_scores_workspace_bytes(int N, int H, int W, int T, int S, int64_t max_bytes) {
     if (!shape_ok(N, H, W, T, S)) return 0;
-    return chunk_pairs(N, H, W, T, S, max_bytes) * pair_bytes(H, W, S);
+    return chunk_plan(N, H, W, T, S, max_bytes).pairs * pair_bytes(H, W, S);
 }
 
-int sbgm_launch_neighbourhood_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H,
-                                     int W, const float* thresholds, int T, const int* scales, int S, int64_t* num, int64_t* den,
-                                     int64_t* events_gen, int64_t* events_obs, int64_t* valid, double* fss, double* fss_field,
-                                     double* freq_bias, double* fss_useful, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+int sbgm_neighbourhood_scores(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int No, int Nm, int H, int W,
+                              const float* thresholds, int T, const int* scales, int S, int64_t* num, int64_t* den,
+                              int64_t* events_gen, int64_t* events_obs, int64_t* valid, double* fss, double* fss_field,
+                              double* freq_bias, double* fss_useful, void* workspace, int64_t workspace_bytes, void* stream) {
+    hipStream_t st = ST;
     SBGM_CHECK(gen && obs && thresholds && scales && num && den && events_gen && events_obs && valid && fss && fss_field && freq_bias &&
                fss_useful && workspace, "neighbourhood_scores: null argument");
     SBGM_CHECK(shape_ok(N, H, W, T, S), "neighbourhood_scores: N=%d H=%d W=%d T=%d S=%d (N 1..65535, sides 2..%d, H*W <= 2^20, "
                "1..%d thresholds, 1..%d widths)", N, H, W, T, S, kMaxSide, kMaxThr, kMaxScales);
     SBGM_CHECK(No == 1 || No == N, "neighbourhood_scores: obs has %d fields; need 1 or N=%d", No, N);
     SBGM_CHECK(!mask || Nm == 1 || Nm == N, "neighbourhood_scores: mask has %d fields; need 1 or N=%d", Nm, N);
-    ThrList thr{};
+    ThrList thr;
     ScaleList sc{};
-    for (int t = 0; t < T; ++t) {
-        SBGM_CHECK(std::isfinite(thresholds[t]), "neighbourhood_scores: threshold %d is not finite", t);
-        thr.v[t] = thresholds[t];
-    }
+    if (int rc = fill_thresholds("neighbourhood_scores", thresholds, T, thr)) return rc;
     for (int s = 0; s < S; ++s) {
         SBGM_CHECK(scales[s] >= 1 && scales[s] % 2 == 1, "neighbourhood_scores: width %d must be odd and >= 1", scales[s]);
         sc.r[s] = std::min((scales[s] - 1) / 2, std::max(H, W));       // a window past both sides covers the field either way
@@ -346,30 +324,27 @@ int sbgm_launch_neighbourhood_scores(const float* gen, const float* obs, const v
     const int64_t pb = pair_bytes(H, W, S);
     SBGM_CHECK(workspace_bytes >= pb, "neighbourhood_scores: workspace of %lld bytes; one field x one threshold needs %lld",
                (long long)workspace_bytes, (long long)pb);
-    const int64_t pairs = chunk_pairs(N, H, W, T, S, workspace_bytes);
     const int nslot = strips(W) * kStripWaves;
     if (int rc = sbgm_zero_async(events_gen, (size_t)N * T * sizeof(int64_t), st)) return rc;
     if (int rc = sbgm_zero_async(events_obs, (size_t)N * T * sizeof(int64_t), st)) return rc;
     if (int rc = sbgm_zero_async(valid, (size_t)N * sizeof(int64_t), st)) return rc;
-    const int cf = pairs >= T ? (int)(pairs / T) : 1, ct = pairs >= T ? T : (int)pairs;      // fields x thresholds of a full chunk
-    for (int f0 = 0; f0 < N; f0 += cf) {
-        const int nf = std::min(cf, N - f0);
-        for (int t0 = 0; t0 < T; t0 += ct) {
-            const int nt = std::min(ct, T - t0), np = nf * nt;
-            unsigned long long* part = static_cast<unsigned long long*>(workspace);          // 8-byte aligned: partials first
-            unsigned int* prefix = reinterpret_cast<unsigned int*>(part + (size_t)np * S * nslot * 2);
-            hipLaunchKernelGGL(neighbourhood_prefix_kernel, dim3(H, nf), dim3(kRowThreads), 0, st, gen, obs, mask, mask_is_u8,
-                               No == 1 ? 0 : 1, Nm == 1 ? 0 : 1, H, W, f0, T, t0, nt, thr, prefix,
-                               reinterpret_cast<unsigned long long*>(events_gen), reinterpret_cast<unsigned long long*>(events_obs),
-                               reinterpret_cast<unsigned long long*>(valid));
-            SBGM_LAUNCH_CHECK();
-            hipLaunchKernelGGL(neighbourhood_walk_kernel, dim3(strips(W), S, np), dim3(kStrip), 0, st, prefix, H, W, sc, part);
-            SBGM_LAUNCH_CHECK();
-            hipLaunchKernelGGL(neighbourhood_collect_kernel, dim3((np * S + 255) / 256), dim3(256), 0, st, part, nslot, f0, T, t0, nt, S,
-                               np, reinterpret_cast<long long*>(num), reinterpret_cast<long long*>(den), fss_field);
-            SBGM_LAUNCH_CHECK();
-        }
-    }
+    const int rc = for_each_chunk(chunk_plan(N, H, W, T, S, workspace_bytes), N, T, [&](int f0, int nf, int t0, int nt) -> int {
+        const int np = nf * nt;
+        unsigned long long* part = static_cast<unsigned long long*>(workspace);              // 8-byte aligned: partials first
+        unsigned int* prefix = reinterpret_cast<unsigned int*>(part + (size_t)np * S * nslot * 2);
+        hipLaunchKernelGGL(neighbourhood_prefix_kernel, dim3(H, nf), dim3(kRowThreads), 0, st, gen, obs, mask, mask_is_u8,
+                           No == 1 ? 0 : 1, Nm == 1 ? 0 : 1, H, W, f0, T, t0, nt, thr, prefix,
+                           reinterpret_cast<unsigned long long*>(events_gen), reinterpret_cast<unsigned long long*>(events_obs),
+                           reinterpret_cast<unsigned long long*>(valid));
+        SBGM_LAUNCH_CHECK();
+        hipLaunchKernelGGL(neighbourhood_walk_kernel, dim3(strips(W), S, np), dim3(kStrip), 0, st, prefix, H, W, sc, part);
+        SBGM_LAUNCH_CHECK();
+        hipLaunchKernelGGL(neighbourhood_collect_kernel, dim3((np * S + 255) / 256), dim3(256), 0, st, part, nslot, f0, T, t0, nt, S, np,
+                           reinterpret_cast<long long*>(num), reinterpret_cast<long long*>(den), fss_field);
+        SBGM_LAUNCH_CHECK();
+        return 0;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(neighbourhood_finish_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const long long*>(num),
                        reinterpret_cast<const long long*>(den), reinterpret_cast<const long long*>(events_gen),
                        reinterpret_cast<const long long*>(events_obs), reinterpret_cast<const long long*>(valid), N, T, S, fss,
@@ -378,17 +353,22 @@ int sbgm_launch_neighbourhood_scores(const float* gen, const float* obs, const v
     return 0;
 }
 
-int sbgm_launch_exceedance_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
-                                  const float* thresholds, int T, int64_t* table, int64_t* count, double* scores, hipStream_t st) {
+int64_t sbgm_exceedance_scores_workspace_bytes(int M, int64_t HW, int T) {
+    (void)M; (void)HW; (void)T;
+    return 0;                          // the table is accumulated in place; the query exists so callers size every score alike
+}
+
+int sbgm_exceedance_scores(const float* ens, const float* obs, const void* mask, int mask_is_u8, int M, int64_t HW,
+                           const float* thresholds, int T, int64_t* table, int64_t* count, double* scores, void* workspace,
+                           void* stream) {
+    (void)workspace;
+    hipStream_t st = ST;
     SBGM_CHECK(ens && obs && thresholds && table && count && scores, "exceedance_scores: null argument");
     SBGM_CHECK(M >= 2 && M <= kMaxMembers, "exceedance_scores: M=%d members (2..%d)", M, kMaxMembers);
     SBGM_CHECK(HW >= 1 && HW < (1ll << 31), "exceedance_scores: HW=%lld", (long long)HW);
     SBGM_CHECK(T >= 1 && T <= kMaxThr, "exceedance_scores: %d thresholds (1..%d)", T, kMaxThr);
-    ThrList thr{};
-    for (int t = 0; t < T; ++t) {
-        SBGM_CHECK(std::isfinite(thresholds[t]), "exceedance_scores: threshold %d is not finite", t);
-        thr.v[t] = thresholds[t];
-    }
+    ThrList thr;
+    if (int rc = fill_thresholds("exceedance_scores", thresholds, T, thr)) return rc;
     if (int rc = sbgm_zero_async(table, (size_t)T * (M + 1) * 2 * sizeof(int64_t), st)) return rc;
     const int tg = std::max(1, std::min(T, kExcLdsBytes / ((M + 1) * 8)));        // thresholds per workgroup: the LDS budget
     const int bx = (int)std::min<int64_t>((HW + kExcThreads - 1) / kExcThreads, kExcMaxBlocks);
@@ -400,3 +380,5 @@ int sbgm_launch_exceedance_scores(const float* ens, const float* obs, const void
     SBGM_LAUNCH_CHECK();
     return 0;
 }
+
+}  // extern "C"

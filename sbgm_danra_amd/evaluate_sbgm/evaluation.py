@@ -102,6 +102,16 @@ def statistics_dir(cfg):
     return os.path.join(base, get_model_string(cfg), "statistics")
 
 
+def _number_list(key, values, lo=None, hi=None):
+    """the config list `key` as floats: at most 16 finite numbers (no bools), within [lo, hi] when bounds are given"""
+    if len(values) > V.MAX_THRESHOLDS:
+        raise ValueError(f"{key}: at most {V.MAX_THRESHOLDS} entries, got {len(values)}")
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not (lo is None or lo <= v <= hi)
+           for v in values):
+        raise ValueError(f"{key} must be {'finite numbers' if lo is None else f'numbers in [{lo}, {hi}]'}, got {list(values)}")
+    return [float(v) for v in values]
+
+
 def spatial_scores_config(cfg):
     """(thresholds, scales) of the optional evaluation.spatial_scores section — thresholds in the units the generated files
     hold, scales as odd window widths in pixels — or None when the section is absent"""
@@ -111,13 +121,12 @@ def spatial_scores_config(cfg):
     thresholds, scales = sec.get("thresholds"), sec.get("scales")
     if not isinstance(thresholds, (list, tuple)) or not isinstance(scales, (list, tuple)) or not thresholds or not scales:
         raise ValueError("evaluation.spatial_scores needs non-empty lists 'thresholds' and 'scales'")
-    if len(thresholds) > 16 or len(scales) > 16:
-        raise ValueError(f"evaluation.spatial_scores: at most 16 thresholds and 16 scales, got {len(thresholds)} and {len(scales)}")
-    if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) for t in thresholds):
-        raise ValueError(f"evaluation.spatial_scores.thresholds must be finite numbers, got {list(thresholds)}")
+    if len(scales) > V.MAX_SCALES:
+        raise ValueError(f"evaluation.spatial_scores.scales: at most {V.MAX_SCALES} entries, got {len(scales)}")
+    thresholds = _number_list("evaluation.spatial_scores.thresholds", thresholds)
     if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 or n % 2 == 0 for n in scales):
         raise ValueError(f"evaluation.spatial_scores.scales must be odd integers >= 1 (window widths in pixels), got {list(scales)}")
-    return [float(t) for t in thresholds], [int(n) for n in scales]
+    return thresholds, [int(n) for n in scales]
 
 
 def ensemble_products_config(cfg):
@@ -129,14 +138,8 @@ def ensemble_products_config(cfg):
     quantiles, thresholds = sec.get("quantiles") or [], sec.get("thresholds") or []
     if not isinstance(quantiles, (list, tuple)) or not isinstance(thresholds, (list, tuple)) or not (quantiles or thresholds):
         raise ValueError("evaluation.ensemble_products needs lists 'quantiles' and 'thresholds', at least one of them non-empty")
-    if len(quantiles) > 16 or len(thresholds) > 16:
-        raise ValueError(f"evaluation.ensemble_products: at most 16 quantiles and 16 thresholds, got {len(quantiles)} and "
-                         f"{len(thresholds)}")
-    if any(isinstance(q, bool) or not isinstance(q, (int, float)) or not math.isfinite(q) or not 0.0 <= q <= 1.0 for q in quantiles):
-        raise ValueError(f"evaluation.ensemble_products.quantiles must be numbers in [0, 1], got {list(quantiles)}")
-    if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) for t in thresholds):
-        raise ValueError(f"evaluation.ensemble_products.thresholds must be finite numbers, got {list(thresholds)}")
-    return [float(q) for q in quantiles], [float(t) for t in thresholds]
+    return (_number_list("evaluation.ensemble_products.quantiles", quantiles, 0, 1),
+            _number_list("evaluation.ensemble_products.thresholds", thresholds))
 
 
 def object_scores_config(cfg):
@@ -150,22 +153,18 @@ def object_scores_config(cfg):
     thresholds, relative, connectivity = sec.get("thresholds") or [], sec.get("relative"), sec.get("connectivity", 8)
     if not isinstance(thresholds, (list, tuple)) or not (thresholds or relative is not None):
         raise ValueError("evaluation.object_scores needs a list 'thresholds', a 'relative' section, or both")
-    if len(thresholds) > 16:
-        raise ValueError(f"evaluation.object_scores: at most 16 thresholds, got {len(thresholds)}")
-    if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) for t in thresholds):
-        raise ValueError(f"evaluation.object_scores.thresholds must be finite numbers, got {list(thresholds)}")
+    thresholds = _number_list("evaluation.object_scores.thresholds", thresholds)
     if relative is not None:
         if not hasattr(relative, "keys") or set(relative.keys()) != {"factor", "quantile", "wet"}:
             raise ValueError("evaluation.object_scores.relative needs exactly the keys 'factor', 'quantile' and 'wet'")
-        vals = {k: relative[k] for k in ("factor", "quantile", "wet")}
-        if any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in vals.values()):
-            raise ValueError(f"evaluation.object_scores.relative: factor, quantile and wet must be finite numbers, got {vals}")
-        if not 0.0 <= vals["quantile"] <= 1.0:
-            raise ValueError(f"evaluation.object_scores.relative.quantile must lie in [0, 1], got {vals['quantile']}")
-        relative = {k: float(v) for k, v in vals.items()}
+        keys = ("factor", "quantile", "wet")
+        values = _number_list("evaluation.object_scores.relative: factor, quantile and wet", [relative[k] for k in keys])
+        relative = dict(zip(keys, values))
+        if not 0.0 <= relative["quantile"] <= 1.0:
+            raise ValueError(f"evaluation.object_scores.relative.quantile must lie in [0, 1], got {relative['quantile']}")
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
         raise ValueError(f"evaluation.object_scores.connectivity must be 4 or 8, got {connectivity!r}")
-    return [float(t) for t in thresholds], relative, int(connectivity)
+    return thresholds, relative, int(connectivity)
 
 
 def multivariate_scores_config(cfg):
@@ -245,6 +244,13 @@ class Evaluation:
         self.fields = {}
         self._err = None
 
+    def _need_ensemble(self, what):
+        """the `repeated` samples are an ensemble for one condition: `what` needs them, and at least 2 members"""
+        if self.generated_sample_type != "repeated":
+            raise ValueError(f"{what} needs 'repeated' samples (an ensemble for one condition), not '{self.generated_sample_type}'")
+        if self.n_samples < 2:
+            raise ValueError(f"{what} needs at least 2 members; {self.label} has {self.n_samples}")
+
     def _error_stats(self):
         if self._err is None:
             self._err = V.error_stats(self.gen_imgs, self.eval_imgs, self.mask)
@@ -312,11 +318,7 @@ class Evaluation:
     def ensemble_statistics(self, seed=None):
         """CRPS (fair map, fair and standard means), rank histogram, skill, spread and spread/skill ratio of the `repeated`
         samples as an ensemble of M members against their one truth"""
-        if self.generated_sample_type != "repeated":
-            raise ValueError(f"ensemble_statistics needs 'repeated' samples (an ensemble for one condition), not "
-                             f"'{self.generated_sample_type}'")
-        if self.n_samples < 2:
-            raise ValueError(f"ensemble_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        self._need_ensemble("ensemble_statistics")
         seed = int(self.cfg["evaluation"].get("seed", 0)) if seed is None else int(seed)
         mask = None if self.mask is None else self.mask[0]
         r = V.ensemble_scores(self.gen_imgs, self.eval_imgs[0], mask=mask, seed=seed)
@@ -372,11 +374,7 @@ class Evaluation:
         """Brier score with Murphy's reliability / resolution / uncertainty, base rate and ROC area per threshold of the
         `repeated` samples as an ensemble forecasting P(value >= threshold); the table behind them (the reliability
         diagram) goes to the fields file"""
-        if self.generated_sample_type != "repeated":
-            raise ValueError(f"exceedance_statistics needs 'repeated' samples (an ensemble for one condition), not "
-                             f"'{self.generated_sample_type}'")
-        if self.n_samples < 2:
-            raise ValueError(f"exceedance_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        self._need_ensemble("exceedance_statistics")
         thresholds, _ = self._spatial_scores(thresholds, scales=[1])
         mask = None if self.mask is None else self.mask[0]
         r = V.exceedance_scores(self.gen_imgs, self.eval_imgs[0], thresholds, mask=mask)
@@ -391,11 +389,7 @@ class Evaluation:
         """ensemble products of the `repeated` samples — mean, standard deviation, minimum, maximum, quantile maps and
         exceedance-probability maps, all to the fields file — and, per quantile level, the coverage: the fraction of valid
         pixels with a non-NaN truth that lies at or below the quantile map, beside its nominal value"""
-        if self.generated_sample_type != "repeated":
-            raise ValueError(f"product_statistics needs 'repeated' samples (an ensemble for one condition), not "
-                             f"'{self.generated_sample_type}'")
-        if self.n_samples < 2:
-            raise ValueError(f"product_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        self._need_ensemble("product_statistics")
         if quantiles is None or thresholds is None:
             sec = ensemble_products_config(self.cfg)
             if sec is None:
@@ -466,11 +460,7 @@ class Evaluation:
         scores go to the metrics entry `multivariate`; the distance matrix `energy_dist2` and the variogram's `vs_map`,
         `gamma_ens`, `gamma_obs`, `offsets` and `pairs` go to a file of their own, <label>_multivariate.npz, which save() writes
         beside the fields file.  Arguments default to the evaluation.multivariate_scores section."""
-        if self.generated_sample_type != "repeated":
-            raise ValueError(f"multivariate_statistics needs 'repeated' samples (an ensemble for one condition), not "
-                             f"'{self.generated_sample_type}'")
-        if self.n_samples < 2:
-            raise ValueError(f"multivariate_statistics needs at least 2 members; {self.label} has {self.n_samples}")
+        self._need_ensemble("multivariate_statistics")
         if energy is None and variogram is None:
             sec = multivariate_scores_config(self.cfg)
             if sec is None:

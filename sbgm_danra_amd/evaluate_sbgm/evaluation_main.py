@@ -20,14 +20,32 @@ from ..utils import get_model_string
 from .evaluation import (GEN_TYPES, Evaluation, ensemble_products_config, multivariate_scores_config, object_scores_config, sample_units,
                          spatial_scores_config)
 
-METHODS = {"pixel_stats": "full_pixel_statistics", "spatial_stats": "spatial_statistics", "daily_stats": "daily_statistics",
-           "ensemble_stats": "ensemble_statistics", "spectral_stats": "spectral_statistics"}
-SPATIAL_METHODS = {"neighbourhood_stats": "neighbourhood_statistics", "exceedance_stats": "exceedance_statistics"}
-PRODUCT_METHODS = {"product_stats": "product_statistics"}
-OBJECT_METHODS = {"object_stats": "object_statistics"}
-MULTIVARIATE_METHODS = {"multivariate_stats": "multivariate_statistics"}
-# run without arguments: they read their section
-SECTION_METHODS = {**SPATIAL_METHODS, **PRODUCT_METHODS, **OBJECT_METHODS, **MULTIVARIATE_METHODS}
+# statistic -> (method of Evaluation, config function of the section that switches it on or None, for 'repeated' only).
+# Without a config function the statistic is one evaluation.eval_stat_methods may list; with one it runs, without arguments
+# (it reads its section), after those and in this order whenever the section is there.
+STATISTICS = {
+    "pixel_stats": ("full_pixel_statistics", None, False),
+    "spatial_stats": ("spatial_statistics", None, False),
+    "daily_stats": ("daily_statistics", None, False),
+    "ensemble_stats": ("ensemble_statistics", None, False),
+    "spectral_stats": ("spectral_statistics", None, False),
+    "neighbourhood_stats": ("neighbourhood_statistics", spatial_scores_config, False),
+    "exceedance_stats": ("exceedance_statistics", spatial_scores_config, True),
+    "product_stats": ("product_statistics", ensemble_products_config, True),
+    "object_stats": ("object_statistics", object_scores_config, False),
+    "multivariate_stats": ("multivariate_statistics", multivariate_scores_config, True),
+}
+
+
+def _methods_of(config):
+    """{statistic: method} of the table's rows with this config function"""
+    return {name: method for name, (method, c, _) in STATISTICS.items() if c is config}
+
+
+# views of the table: the names evaluation.eval_stat_methods may list, and the statistics of each section
+METHODS = _methods_of(None)
+SPATIAL_METHODS, PRODUCT_METHODS = _methods_of(spatial_scores_config), _methods_of(ensemble_products_config)
+OBJECT_METHODS, MULTIVARIATE_METHODS = _methods_of(object_scores_config), _methods_of(multivariate_scores_config)
 PLOT_KEYS = ("plot_examples", "save_figs", "show_plots", "show_figs", "mask_plots", "plot_w_cond", "plot_w_lsm")
 
 
@@ -55,14 +73,9 @@ def unit_statistics(cfg, gen_type):
     section — 'object_stats'; then — only with an evaluation.multivariate_scores section, for 'repeated' —
     'multivariate_stats'"""
     stats = eval_stat_methods(cfg)
-    if spatial_scores_config(cfg) is not None:
-        stats += ["neighbourhood_stats"] + (["exceedance_stats"] if gen_type == "repeated" else [])
-    if ensemble_products_config(cfg) is not None and gen_type == "repeated":
-        stats += ["product_stats"]
-    if object_scores_config(cfg) is not None:
-        stats += ["object_stats"]
-    if multivariate_scores_config(cfg) is not None and gen_type == "repeated":
-        stats += ["multivariate_stats"]
+    for name, (_, config, ensemble_only) in STATISTICS.items():
+        if config is not None and config(cfg) is not None and (gen_type == "repeated" or not ensemble_only):
+            stats.append(name)
     return stats
 
 
@@ -86,10 +99,13 @@ def evaluation_main(cfg):
     if skipped:
         log.info(f"[INFO] Plotting is not part of this evaluation; skipped: {skipped}")
     sample_dir = os.path.join(cfg["paths"]["sample_dir"], "generation", model_name_str, "generated_samples")
-    if multivariate_scores_config(cfg) is not None:
-        for t in types:
-            if t != "repeated":
-                log.info(f"[INFO] evaluation.multivariate_scores needs 'repeated' samples (an ensemble); skipped for '{t}'")
+    # a section all of whose statistics are for 'repeated' only does nothing for another type: say so
+    for config in dict.fromkeys(c for _, c, _ in STATISTICS.values() if c is not None):
+        if all(only for _, c, only in STATISTICS.values() if c is config) and config(cfg) is not None:
+            for t in types:
+                if t != "repeated":
+                    log.info(f"[INFO] evaluation.{config.__name__[:-len('_config')]} needs 'repeated' samples (an ensemble); "
+                             f"skipped for '{t}'")
     out = {}
     for gen_type in types:
         n = n_samples_of(cfg, gen_type)
@@ -98,10 +114,7 @@ def evaluation_main(cfg):
             log.info(f"[INFO] Running evaluation for {runner.label}")
             for method in methods[gen_type]:
                 log.info(f"[INFO] Running evaluation method: {method}")
-                if method in SECTION_METHODS:
-                    getattr(runner, SECTION_METHODS[method])()
-                    continue
-                fn = getattr(runner, METHODS[method])
+                fn = getattr(runner, STATISTICS[method][0])
                 if method in ("pixel_stats", "spatial_stats"):
                     fn(save_stats=bool(ev.get("save_stats", False)), n_samples=n if n is not None else runner.n_samples)
                 else:

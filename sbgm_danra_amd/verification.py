@@ -1,6 +1,6 @@
 """Device-tensor wrappers of the verification kernels (csrc/verify.hip, csrc/verify_spatial.hip, csrc/verify_products.hip,
-csrc/verify_objects.hip and csrc/verify_multivariate.hip): error statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill),
-radially averaged power spectra, neighbourhood scores (Fractions Skill Score), threshold-exceedance scores (Brier, reliability
+csrc/verify_objects.hip and csrc/verify_multivariate.hip, their shared helpers in csrc/verify_common.h): error
+statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra, neighbourhood scores (Fractions Skill Score), threshold-exceedance scores (Brier, reliability
 table, ROC area), ensemble products (per-pixel mean, spread, envelope, quantile and exceedance-probability maps) and
 object-based scores (connected objects and SAL: structure, amplitude, location) and multivariate ensemble scores (energy score,
 variogram score).  Every function takes tensors on
@@ -21,17 +21,15 @@ ENSEMBLE_KEYS = ("count", "crps_fair", "crps_standard", "skill", "spread", "spre
 NEIGHBOURHOOD_KEYS = ("num", "den", "events_gen", "events_obs", "valid", "fss", "fss_field", "freq_bias", "fss_useful")
 EXCEEDANCE_KEYS = ("brier", "brier_reliability", "brier_resolution", "brier_uncertainty", "base_rate", "roc_area")
 MAX_THRESHOLDS = MAX_SCALES = 16                 # include/sbgm_hip.h: SBGM_SPATIAL_MAX_THRESHOLDS / _SCALES
-MAX_FIELD_SIDE, MAX_FIELD_PIXELS = 2048, 1 << 20
-MAX_EXCEEDANCE_MEMBERS = 4095
+MAX_FIELDS, MAX_FIELD_SIDE, MAX_FIELD_PIXELS = 65535, 2048, 1 << 20        # csrc/verify_common.h
+MAX_EXCEEDANCE_MEMBERS = MAX_PRODUCT_MEMBERS = MAX_MULTIVARIATE_MEMBERS = 4095
 MAX_PRODUCT_QUANTILES = 16                       # include/sbgm_hip.h: SBGM_PRODUCTS_MAX_QUANTILES; thresholds: MAX_THRESHOLDS
-MAX_PRODUCT_MEMBERS = 4095
 DEFAULT_WORKSPACE_BYTES = 256 << 20
 OBJECT_KEYS = ("threshold", "n_objects", "area", "mass", "V", "r", "domain_mean", "com", "valid", "S", "L2", "A", "L1", "L",
                "area_hist", "status")               # the argument order of sbgm_object_scores
 OBJECT_AREA_BINS = 21                            # include/sbgm_hip.h: SBGM_OBJECTS_AREA_BINS; fixed thresholds: MAX_THRESHOLDS
 ENERGY_KEYS = ("count", "es_fair", "es_standard", "mean_dist_obs", "mean_dist_pair", "min_dist_pair")
 VARIOGRAM_KEYS = ("vs", "n_pairs", "sum_w", "vs_unweighted")
-MAX_MULTIVARIATE_MEMBERS = 4095
 MAX_VARIOGRAM_RADIUS, MAX_VARIOGRAM_OFFSETS = 8, 98    # include/sbgm_hip.h: SBGM_VARIOGRAM_MAX_OFFSETS
 VARIOGRAM_ORDERS = (0.5, 1.0, 2.0)
 VARIOGRAM_WEIGHTS = ("inverse_distance", "unit")
@@ -222,6 +220,62 @@ def _shape_rows(t, name, hw, allowed):
         raise ValueError(f"{name}: {shape[0]} fields; expected one of {sorted(set(allowed))}")
 
 
+def _field_shape(x, name, what):
+    """(N, H, W) of the fields `what` = x [N,H,W] of the function `name`, within the limits of the chunked scores"""
+    if x.dim() != 3:
+        raise ValueError(f"{what}: expected [N, H, W], got {tuple(x.shape)}")
+    n, H, W = x.shape
+    if not (2 <= H <= MAX_FIELD_SIDE and 2 <= W <= MAX_FIELD_SIDE) or H * W > MAX_FIELD_PIXELS:
+        raise ValueError(f"{name}: field size {H}x{W}; sides must be 2..{MAX_FIELD_SIDE} and H*W <= 2^20")
+    if not 1 <= n <= MAX_FIELDS:
+        raise ValueError(f"{name}: {n} fields; need 1..{MAX_FIELDS}")
+    return n, H, W
+
+
+def _paired(name, gen, obs, mask, what="gen"):
+    """paired fields: gen [N,H,W] within the field limits, obs [No,H,W] (None: no second side) and mask [Nm,H,W] with No, Nm in
+    {1, N}, all shapes checked before anything touches the device -> (gen [N, HW], obs [No, HW] or None, mask, is_u8, Nm)"""
+    n, H, W = _field_shape(gen, name, what)
+    _shape_rows(obs, "obs", (H, W), (1, n))
+    _shape_rows(mask, "mask", (H, W), (1, n))
+    g = _fields(gen, what)
+    o = None
+    if obs is not None:
+        o = _fields(obs, "obs")
+        if o.device != g.device:
+            raise ValueError("gen and obs must be on the same device")
+    return (g, o) + _mask(mask, H * W, (1, n))
+
+
+def _members(name, ens, max_members):
+    """(M, H, W) of an ensemble ens [M,H,W] with 2 <= M <= max_members"""
+    if ens.dim() != 3:
+        raise ValueError(f"ens: expected [M, H, W], got {tuple(ens.shape)}")
+    M, H, W = ens.shape
+    if not 2 <= M <= max_members:
+        raise ValueError(f"{name}: M={M} members; need 2..{max_members}")
+    return M, H, W
+
+
+def _ensemble(name, ens, obs, mask, max_members, max_pixels=None, strict=False):
+    """ensemble: ens [M,H,W] with 2 <= M <= max_members (and 1 <= H*W <= max_pixels, if given), obs [H,W] (None: no truth) and
+    mask [H,W], all shapes checked before anything touches the device -> (ens [M, HW], obs [1, HW] or None, mask, is_u8).
+    strict: ens and a given obs must also be floating before they are converted, and on one device."""
+    M, H, W = _members(name, ens, max_members)
+    if max_pixels is not None and (H < 1 or W < 1 or H * W > max_pixels):
+        raise ValueError(f"{name}: field size {H}x{W}; need H*W in 1..2^20")
+    _shape_rows(obs, "obs", (H, W), (1,))
+    _shape_rows(mask, "mask", (H, W), (1,))
+    if strict and obs is not None and not (ens.is_floating_point() and obs.is_floating_point()):
+        raise TypeError(f"{name}: ens and obs must be floating tensors, got {ens.dtype} and {obs.dtype}")
+    e = _fields(ens, "ens")
+    o = None if obs is None else _fields(obs, "obs")
+    if strict and o is not None and o.device != e.device:
+        raise ValueError("ens and obs must be on the same device")
+    m, u8, _ = _mask(mask, H * W, (1,))
+    return e, o, m, u8
+
+
 def neighbourhood_strip_columns():
     """columns one workgroup of the neighbourhood window pass owns (fields wider than this are walked in several strips)"""
     return int(N.lib().sbgm_neighbourhood_scores_strip_columns())
@@ -237,22 +291,8 @@ def neighbourhood_scores(gen, obs, thresholds, scales, mask=None, max_workspace_
     observed event frequency.  The fields are processed in chunks whose workspace stays within `max_workspace_bytes` (at
     least one field x one threshold); the result does not depend on the chunking."""
     thr, sc = _thresholds(thresholds, "neighbourhood_scores"), _scales(scales, "neighbourhood_scores")
-    if gen.dim() != 3:
-        raise ValueError(f"gen: expected [N, H, W], got {tuple(gen.shape)}")
-    n, H, W = gen.shape
-    if not (2 <= H <= MAX_FIELD_SIDE and 2 <= W <= MAX_FIELD_SIDE) or H * W > MAX_FIELD_PIXELS:
-        raise ValueError(f"neighbourhood_scores: field size {H}x{W}; sides must be 2..{MAX_FIELD_SIDE} and H*W <= 2^20")
-    if not 1 <= n <= 65535:
-        raise ValueError(f"neighbourhood_scores: {n} fields; need 1..65535")
-    _shape_rows(obs, "obs", (H, W), (1, n))
-    _shape_rows(mask, "mask", (H, W), (1, n))
-    g = _fields(gen, "gen")
-    HW = H * W
-    o = _fields(obs, "obs")
-    if o.device != g.device:
-        raise ValueError("gen and obs must be on the same device")
-    m, u8, nm = _mask(mask, HW, (1, n))
-    T, S, dev = len(thr), len(sc), g.device
+    g, o, m, u8, nm = _paired("neighbourhood_scores", gen, obs, mask)
+    (n, H, W), T, S, dev = gen.shape, len(thr), len(sc), g.device
     i64 = dict(dtype=torch.int64, device=dev)
     f64 = dict(dtype=torch.float64, device=dev)
     out = dict(num=torch.empty(n, T, S, **i64), den=torch.empty(n, T, S, **i64), events_gen=torch.empty(n, T, **i64),
@@ -274,18 +314,8 @@ def exceedance_scores(ens, obs, thresholds, mask=None):
     resolution + uncertainty = brier), `base_rate` and `roc_area` (trapezoids over the M+1 cut-offs; NaN when the event
     never or always occurs), all computed from the table."""
     thr = _thresholds(thresholds, "exceedance_scores")
-    if ens.dim() != 3:
-        raise ValueError(f"ens: expected [M, H, W], got {tuple(ens.shape)}")
-    M = ens.shape[0]
-    if not 2 <= M <= MAX_EXCEEDANCE_MEMBERS:
-        raise ValueError(f"exceedance_scores: M={M} members; need 2..{MAX_EXCEEDANCE_MEMBERS}")
-    _shape_rows(obs, "obs", tuple(ens.shape[1:]), (1,))
-    _shape_rows(mask, "mask", tuple(ens.shape[1:]), (1,))
-    e = _fields(ens, "ens")
-    HW = e.shape[1]
-    o = _fields(obs, "obs")
-    m, u8, _ = _mask(mask, HW, (1,))
-    T, dev = len(thr), e.device
+    e, o, m, u8 = _ensemble("exceedance_scores", ens, obs, mask, MAX_EXCEEDANCE_MEMBERS)
+    (M, HW), T, dev = e.shape, len(thr), e.device
     table = torch.empty(T, M + 1, 2, dtype=torch.int64, device=dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
     scores = torch.empty(len(EXCEEDANCE_KEYS), T, dtype=torch.float64, device=dev)
@@ -301,22 +331,15 @@ def ensemble_products(ens, quantiles=(), thresholds=(), mask=None):
     g == 0 or x_(lo) == x_(hi), else (float)(x_(lo) + g (x_(hi) - x_(lo))) in fp64 — exact order statistics, so q = 0 is
     `min` and q = 1 is `max` bit for bit); `exceed_prob` [T,H,W] = #{members >= thr} / M (comparison in fp32); `count` int64
     scalar, the valid pixels.  Up to 16 quantile levels in [0, 1] and 16 finite thresholds; either list may be empty."""
-    if ens.dim() != 3:
-        raise ValueError(f"ens: expected [M, H, W], got {tuple(ens.shape)}")
-    M, shape = ens.shape[0], tuple(ens.shape[1:])
-    if not 2 <= M <= MAX_PRODUCT_MEMBERS:
-        raise ValueError(f"ensemble_products: M={M} members; need 2..{MAX_PRODUCT_MEMBERS}")
+    _members("ensemble_products", ens, MAX_PRODUCT_MEMBERS)               # the member count first, then the levels
     qs, thr = [float(q) for q in quantiles], list(thresholds)
     if len(qs) > MAX_PRODUCT_QUANTILES:
         raise ValueError(f"ensemble_products: {len(qs)} quantiles; at most {MAX_PRODUCT_QUANTILES}")
     if not all(math.isfinite(q) and 0.0 <= q <= 1.0 for q in qs):
         raise ValueError(f"ensemble_products: quantiles must lie in [0, 1], got {qs}")
     tarr = _thresholds(thr, "ensemble_products") if thr else None
-    _shape_rows(mask, "mask", shape, (1,))
-    e = _fields(ens, "ens")
-    HW = e.shape[1]
-    m, u8, _ = _mask(mask, HW, (1,))
-    Q, T, dev = len(qs), len(thr), e.device
+    e, _, m, u8 = _ensemble("ensemble_products", ens, None, mask, MAX_PRODUCT_MEMBERS)
+    (M, HW), shape, Q, T, dev = e.shape, tuple(ens.shape[1:]), len(qs), len(thr), e.device
     mean, std, vmin, vmax = (torch.empty(HW, device=dev) for _ in range(4))
     quant, exceed = torch.empty(Q, HW, device=dev), torch.empty(T, HW, device=dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
@@ -332,17 +355,6 @@ def _connectivity(connectivity, name):
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
         raise ValueError(f"{name}: connectivity must be 4 or 8, got {connectivity!r}")
     return int(connectivity)
-
-
-def _object_shape(x, name, what):
-    if x.dim() != 3:
-        raise ValueError(f"{what}: expected [N, H, W], got {tuple(x.shape)}")
-    n, H, W = x.shape
-    if not (2 <= H <= MAX_FIELD_SIDE and 2 <= W <= MAX_FIELD_SIDE) or H * W > MAX_FIELD_PIXELS:
-        raise ValueError(f"{name}: field size {H}x{W}; sides must be 2..{MAX_FIELD_SIDE} and H*W <= 2^20")
-    if not 1 <= n <= 65535:
-        raise ValueError(f"{name}: {n} fields; need 1..65535")
-    return n, H, W
 
 
 def _relative(relative, name):
@@ -368,10 +380,8 @@ def object_labels(fields, threshold, mask=None, connectivity=8, return_status=Fa
     to know must pass return_status=True and look at it."""
     conn = _connectivity(connectivity, "object_labels")
     thr = _thresholds([threshold], "object_labels")[0]
-    n, H, W = _object_shape(fields, "object_labels", "fields")
-    _shape_rows(mask, "mask", (H, W), (1, n))
-    x = _fields(fields, "fields")
-    m, u8, nm = _mask(mask, H * W, (1, n))
+    x, _, m, u8, nm = _paired("object_labels", fields, None, mask, what="fields")
+    n, H, W = fields.shape
     labels = torch.empty(n, H, W, dtype=torch.int32, device=x.device)
     status = torch.empty(1, dtype=torch.int32, device=x.device)
     N.check(N.lib().sbgm_object_labels(x.data_ptr(), N.ptr(m), u8, n, nm, H, W, thr, conn, labels.data_ptr(), status.data_ptr(),
@@ -405,15 +415,8 @@ def object_scores(gen, obs, thresholds=(), relative=None, mask=None, connectivit
     T = len(fixed) + (rel is not None)
     if T < 1:
         raise ValueError("object_scores: no threshold given (thresholds is empty and relative is None)")
-    n, H, W = _object_shape(gen, "object_scores", "gen")
-    _shape_rows(obs, "obs", (H, W), (1, n))
-    _shape_rows(mask, "mask", (H, W), (1, n))
-    g = _fields(gen, "gen")
-    o = _fields(obs, "obs")
-    if o.device != g.device:
-        raise ValueError("gen and obs must be on the same device")
-    m, u8, nm = _mask(mask, H * W, (1, n))
-    dev = g.device
+    g, o, m, u8, nm = _paired("object_scores", gen, obs, mask)
+    (n, H, W), dev = gen.shape, g.device
     i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
     out = dict(threshold=torch.empty(2, n, T, device=dev), n_objects=torch.empty(2, n, T, **i64), area=torch.empty(2, n, T, **i64),
                mass=torch.empty(2, n, T, **f64), V=torch.empty(2, n, T, **f64), r=torch.empty(2, n, T, **f64),
@@ -440,27 +443,6 @@ def variogram_offsets(radius):
             if (dy > 0 or dx > 0) and dy * dy + dx * dx <= radius * radius]
 
 
-def _multivariate_args(name, ens, obs, mask):
-    """shape, dtype and limit checks shared by energy_scores and variogram_scores -> (ens [M, HW], obs [1, HW], mask, is_u8)"""
-    if ens.dim() != 3:
-        raise ValueError(f"ens: expected [M, H, W], got {tuple(ens.shape)}")
-    M, H, W = ens.shape
-    if not 2 <= M <= MAX_MULTIVARIATE_MEMBERS:
-        raise ValueError(f"{name}: M={M} members; need 2..{MAX_MULTIVARIATE_MEMBERS}")
-    if H < 1 or W < 1 or H * W > MAX_FIELD_PIXELS:
-        raise ValueError(f"{name}: field size {H}x{W}; need H*W in 1..2^20")
-    _shape_rows(obs, "obs", (H, W), (1,))
-    _shape_rows(mask, "mask", (H, W), (1,))
-    if not ens.is_floating_point() or not obs.is_floating_point():
-        raise TypeError(f"{name}: ens and obs must be floating tensors, got {ens.dtype} and {obs.dtype}")
-    e = _fields(ens, "ens")
-    o = _fields(obs, "obs")
-    if o.device != e.device:
-        raise ValueError("ens and obs must be on the same device")
-    m, u8, _ = _mask(mask, H * W, (1,))
-    return e, o, m, u8
-
-
 def energy_scores(ens, obs, mask=None):
     """energy score (Gneiting et al. 2008) of members ens [M,H,W] (2 <= M <= 4095, H*W <= 2^20) against truth obs [H,W],
     optional mask [H,W].  A pixel is valid when every member and obs are not NaN there and the mask admits it.  Returns device
@@ -470,7 +452,7 @@ def energy_scores(ens, obs, mask=None):
     sum_{m != k} |x_m - x_k|, es_standard (the same with 1/(2 M^2)), mean_dist_obs, mean_dist_pair and min_dist_pair, every
     norm |a - b| = sqrt(dist2 / count), an RMS distance.  No valid pixel gives count 0 and NaN scores.  Two calls give
     bit-equal results."""
-    e, o, m, u8 = _multivariate_args("energy_scores", ens, obs, mask)
+    e, o, m, u8 = _ensemble("energy_scores", ens, obs, mask, MAX_MULTIVARIATE_MEMBERS, MAX_FIELD_PIXELS, strict=True)
     M, HW = e.shape
     dev = e.device
     dist2 = torch.empty(M + 1, M + 1, dtype=torch.float64, device=dev)
@@ -496,7 +478,7 @@ def variogram_scores(ens, obs, radius=4, order=0.5, weights="inverse_distance", 
         raise ValueError(f"variogram_scores: order must be one of {VARIOGRAM_ORDERS}, got {order!r}")
     if weights not in VARIOGRAM_WEIGHTS:
         raise ValueError(f"variogram_scores: weights must be one of {VARIOGRAM_WEIGHTS}, got {weights!r}")
-    e, o, m, u8 = _multivariate_args("variogram_scores", ens, obs, mask)
+    e, o, m, u8 = _ensemble("variogram_scores", ens, obs, mask, MAX_MULTIVARIATE_MEMBERS, MAX_FIELD_PIXELS, strict=True)
     M, (H, W) = e.shape[0], ens.shape[1:]
     dev, n_off = e.device, len(offsets)
     f64 = dict(dtype=torch.float64, device=dev)
