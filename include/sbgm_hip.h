@@ -328,6 +328,13 @@ int sbgm_conv2d_pair_fwd(const sbgm_conv_args* main_conv, const sbgm_conv_args* 
  * to put into sbgm_conv_args.  Winograd candidates are timed when a->w_wino is given (they need the transformed weights);
  * split-K candidates are considered when a->ws is given.  Used by the training path, whose convolutions run op by op. */
 int sbgm_conv2d_tune(const sbgm_conv_args* a, int* tile, void* stream);
+/* The candidates sbgm_conv2d_tune would time for exactly this call, without timing anything: host only, no device, no stream, no
+ * launch, and no pointer of `a` is dereferenced (x, w_packed, out must be non-NULL; w_wino / w_wino2d / ws count as present or
+ * absent).  Same checks as sbgm_conv2d_tune (winograd == 0, Cout %% 32 == 0).  Writes up to `cap` candidates, 6 ints each in the
+ * tile[6] form above (tile[4] == 2: F(2x2,3x3), tile[5] == 3: its persistent form), in the order the tuner times them, and returns
+ * their number, which may exceed `cap`; 0 for a call sbgm_conv2d_tune refuses.  Split-K candidates appear only with a->ws, and only
+ * those whose partial sums (B*OH*OW*Cout*splits floats) fit ws_floats.  Every entry is a tile sbgm_conv2d_fwd runs for this call. */
+int sbgm_conv2d_tiles(const sbgm_conv_args* a, int* tiles, int cap);
 /* Pack many convolution weights in one launch.  desc: DEVICE array of n descriptors; block_begin = exclusive prefix of
  * sbgm_conv_pack_weights_batched_blocks(Cout, KH, KW, cs) over the descriptors (the workgroups each weight needs),
  * total_blocks = its total; nsteps = sbgm_conv_packed_numel / (Cout*16).

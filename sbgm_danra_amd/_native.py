@@ -150,6 +150,7 @@ SIGNATURES = {
     "sbgm_conv2d_fwd": (_i, [C.POINTER(ConvArgs), _vp]),
     "sbgm_conv2d_pair_fwd": (_i, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), C.POINTER(C.c_int), _vp]),
     "sbgm_conv2d_tune": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int), _vp]),
+    "sbgm_conv2d_tiles": (_i, [C.POINTER(ConvArgs), C.POINTER(C.c_int), _i]),
     "sbgm_conv_pack_weights_batched": (_i, [_vp, _i, _i, _vp]),
     "sbgm_conv_pack_weights_batched_blocks": (_i, [_i, _i, _i, _i]),
     "sbgm_adam_step_blocks": (_i, [C.c_int64]),
@@ -260,7 +261,7 @@ SIGNATURES = {
     "sbgm_variogram_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i] + [_vp] * 6 + [_i64, _vp]),
 }
 
-ABI_VERSION = 11       # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 12      # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

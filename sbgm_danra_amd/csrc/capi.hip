@@ -151,18 +151,35 @@ int sbgm_wgrad_flush(void* stream) { return sbgm_launch_wgrad_flush(ST); }
 int sbgm_wgrad_flush_pending(void) { return sbgm_wgrad_pending(); }
 int sbgm_wgrad_discard(void) { const int n = sbgm_wgrad_pending(); sbgm_wgrad_discard_queue(); return n; }
 
+// the checks sbgm_conv2d_tune and sbgm_conv2d_tiles share, and the call in the planner's terms; *own: the call's own tile
+static int tune_call_from_args(const char* who, const sbgm_conv_args* a, ConvGeom* g, ConvParams* p, ConvImages* w, ConvTile* own) {
+    SBGM_CHECK(a->winograd == 0, "%s: winograd must be 0 (the search decides the kernel; w_wino / w_wino2d say which images exist)", who);
+    SBGM_CHECK(a->Cout % 32 == 0, "%s: Cout=%d must be a multiple of 32", who, a->Cout);
+    return sbgm_conv_from_args(a, g, p, w, own);
+}
+
 int sbgm_conv2d_tune(const sbgm_conv_args* a, int* tile, void* stream) {
     SBGM_CHECK(a && tile, "conv2d_tune: null argument");
-    SBGM_CHECK(a->winograd == 0, "conv2d_tune: winograd must be 0 (the search decides the kernel; w_wino / w_wino2d say which images exist)");
-    SBGM_CHECK(a->Cout % 32 == 0, "conv2d_tune: Cout=%d must be a multiple of 32", a->Cout);
     ConvGeom g;
     ConvParams p;
     ConvImages w;
     ConvTile best;                      // the call's own tile (the default one when its tile fields are zero) is the fallback
-    if (sbgm_conv_from_args(a, &g, &p, &w, &best)) return 1;
+    if (tune_call_from_args("conv2d_tune", a, &g, &p, &w, &best)) return 1;
     if (sbgm_tune_conv(g, p, w, a->ws, a->ws ? (size_t)a->ws_floats : 0, ST, &best)) return 1;
     best.to_ints(tile);
     return 0;
+}
+
+int sbgm_conv2d_tiles(const sbgm_conv_args* a, int* tiles, int cap) {
+    if (!a || (!tiles && cap > 0) || cap < 0) return 0;
+    ConvGeom g;
+    ConvParams p;
+    ConvImages w;
+    ConvTile own;
+    if (tune_call_from_args("conv2d_tiles", a, &g, &p, &w, &own)) return 0;
+    const std::vector<ConvTile> c = sbgm_conv_tune_list(g, p, w, a->ws != nullptr, a->ws ? (size_t)a->ws_floats : 0);
+    for (int i = 0; i < (int)c.size() && i < cap; ++i) c[i].to_ints(tiles + 6 * i);
+    return (int)c.size();
 }
 
 int sbgm_upsample2x_fwd(const float* x, float* y, int B, int H, int W, int C, void* stream) {

@@ -128,6 +128,8 @@ const ConvSwitches& sbgm_conv_switches();                          // read from 
 ConvTile sbgm_static_tile(const ConvGeom& g, const ConvParams& p, const ConvImages& w);   // for a convolution the autotuner has not timed
 ConvTile sbgm_cout16_tile(const ConvParams& p, const ConvImages& w);                      // ... of 16 output channels (composed final block)
 std::vector<ConvTile> sbgm_conv_candidates(const ConvGeom& g, const ConvParams& p, const ConvImages& w, bool partial);
+// the candidates the tuner times for one call: sbgm_conv_candidates minus the split-K tiles a workspace of partial_floats floats cannot hold
+std::vector<ConvTile> sbgm_conv_tune_list(const ConvGeom& g, const ConvParams& p, const ConvImages& w, bool partial, size_t partial_floats);
 // times the candidates of ONE convolution on its real operands, fastest in *best (in: the fallback); synchronises
 int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, const ConvImages& w, float* partial, size_t partial_floats, hipStream_t st,
                    ConvTile* best);

@@ -345,15 +345,24 @@ std::vector<ConvTile> sbgm_conv_candidates(const ConvGeom& g, const ConvParams& 
     return cands;
 }
 
+// What the timing loop below runs for one call, in its order: the candidates, minus the split-K ones whose partial sums
+// (B*OH*OW*Cout floats per split) the workspace of partial_floats floats cannot hold.  sbgm_conv2d_tiles hands out the same list.
+std::vector<ConvTile> sbgm_conv_tune_list(const ConvGeom& g, const ConvParams& p, const ConvImages& w, bool partial, size_t partial_floats) {
+    const int OH = p.out_h > 0 ? p.out_h : (p.H + 2 * g.pad - g.kh) / g.stride + 1;
+    const int OW = p.out_w > 0 ? p.out_w : (p.W + 2 * g.pad - g.kw) / g.stride + 1;
+    const size_t mc = (size_t)p.B * OH * OW * p.Cout;
+    std::vector<ConvTile> list;
+    for (auto& ct : sbgm_conv_candidates(g, p, w, partial))
+        if (ct.splits <= 1 || mc * ct.splits <= partial_floats) list.push_back(ct);
+    return list;
+}
+
 // Times the tile candidates (template x tile x waves-per-tile x split-K) of ONE convolution on its real operands and returns
 // the fastest in *best (in: the fallback).  A launch never reads what it writes, so repeating it is harmless.  Synchronises.
 int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, const ConvImages& w, float* partial, size_t partial_floats, hipStream_t st,
                    ConvTile* best) {
-    const int OH = p.out_h > 0 ? p.out_h : (p.H + 2 * g.pad - g.kh) / g.stride + 1;
-    const int OW = p.out_w > 0 ? p.out_w : (p.W + 2 * g.pad - g.kw) / g.stride + 1;
-    const size_t mc = (size_t)p.B * OH * OW * p.Cout;
     auto launch = [&](const ConvTile& ct) -> int { return sbgm_launch_tile(g, p, w, ct, partial, st); };
-    const std::vector<ConvTile> cands = sbgm_conv_candidates(g, p, w, partial != nullptr);
+    const std::vector<ConvTile> cands = sbgm_conv_tune_list(g, p, w, partial != nullptr, partial_floats);
     hipEvent_t e0, e1;
     SBGM_HIP(hipEventCreate(&e0));
     SBGM_HIP(hipEventCreate(&e1));
@@ -362,7 +371,6 @@ int sbgm_tune_conv(const ConvGeom& g, const ConvParams& p, const ConvImages& w, 
     int rc = 0;
     for (int round = 0; round < 3 && !rc; ++round)          // three interleaved rounds, keep each candidate's best (DVFS / noise)
         for (auto& ct : cands) {
-            if (ct.splits > 1 && mc * ct.splits > partial_floats) continue;
             constexpr int REPS = 6;
             float ms = 0.f;
             if (cold && partial) {

@@ -43,9 +43,17 @@ def leaf(t, dev=False):
                                                  (5, 128, 8, 64, 3, 1, 1), (8, 64, 8, 64, 3, 1, 1), (1, 64, 8, 64, 3, 1, 1),      # ... 8 x 8 maps: 4 images per tile
                                                  (9, 64, 16, 64, 3, 1, 1),                                                       # several tiles per workgroup
                                                  (3, 128, 16, 64, 1, 1, 0), (1, 64, 6, 128, 1, 1, 0), (2, 192, 10, 64, 1, 2, 0),  # LDS-staged 1x1 (pixel split / ragged tile / stride 2)
-                                                 (8, 64, 32, 64, 1, 1, 0)])
+                                                 (8, 64, 32, 64, 1, 1, 0),
+                                                 (2, 32, 6, 64, 3, 1, 1), (1, 96, 6, 64, 3, 1, 1),        # neither halo nor per-tap: conv_wgrad_kernel<2>
+                                                 (2, 64, "16x32", 64, 3, 1, 1), (2, 64, "32x16", 64, 3, 1, 1)])   # non-square halo tiles
 def test_conv_backward(B, Cin, H, Cout, k, s, p):
-    x, w, b = rnd(B, Cin, H, H), rnd(Cout, Cin, k, k, seed=1, scale=1 / math.sqrt(Cin * k * k)), rnd(Cout, seed=2)
+    conv_backward_case(B, Cin, H, Cout, k, s, p)
+
+
+def conv_backward_case(B, Cin, H, Cout, k, s, p):
+    """H: the side of a square map, or a string 'HxW'"""
+    H, W = (H, H) if isinstance(H, int) else map(int, H.split("x"))
+    x, w, b = rnd(B, Cin, H, W), rnd(Cout, Cin, k, k, seed=1, scale=1 / math.sqrt(Cin * k * k)), rnd(Cout, seed=2)
     res_shape = F.conv2d(x, w, b, s, p).shape
     res, tb, go = rnd(*res_shape, seed=3), rnd(B, Cout, seed=4), rnd(*res_shape, seed=5)
     xr, wr, br, rr, tr = leaf(x), leaf(w), leaf(b), leaf(res), leaf(tb)
@@ -56,6 +64,14 @@ def test_conv_backward(B, Cin, H, Cout, k, s, p):
     assert maxrel(nchw(xd.grad.cpu()), xr.grad) < GT
     assert maxrel(wd.grad.cpu(), wr.grad) < GT and maxrel(bd.grad.cpu(), br.grad) < GT
     assert maxrel(nchw(rd.grad.cpu()), rr.grad) < GT and maxrel(td.grad.cpu(), tr.grad) < GT
+
+
+@pytest.mark.parametrize("B,Cin,H,Cout,k,s,p", [(2, 64, 8, 64, 3, 1, 1), (1, 128, 4, 64, 3, 2, 1)])
+def test_conv_backward_general_weight_gradient_kernel(B, Cin, H, Cout, k, s, p, monkeypatch):
+    """SBGM_NO_LDS_WGRAD (read by the launcher on every call) takes the halo and per-tap kernels away: conv_wgrad_kernel<4>, the
+    fallback for every layer those refuse and for tensors of 2 GiB and more"""
+    monkeypatch.setenv("SBGM_NO_LDS_WGRAD", "1")
+    conv_backward_case(B, Cin, H, Cout, k, s, p)
 
 
 @pytest.mark.parametrize("cin", [2, 7, 13])

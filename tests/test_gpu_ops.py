@@ -543,11 +543,14 @@ def test_batched_weight_pack_equals_single_packs(transposed):
         assert torch.equal(single, batched)
 
 
-@pytest.mark.parametrize("transposed", [0, 1])
-def test_batched_weight_pack_winograd_layout(transposed):
-    """sbgm_pack_desc.transposed bit 1: the Winograd image of the forward operator == sbgm_conv_wino_pack_weight; of the
-    data-gradient operator == sbgm_conv_wino_pack_weight of the explicitly transposed + 180-degree-flipped weight; and a
-    convolution through it (the training path's use) matches F.conv2d / its input gradient"""
+@pytest.mark.parametrize("transposed,image", [(0, 2), (1, 2), (0, 4), (1, 4)], ids=["0", "1", "0-f2x2", "1-f2x2"])
+def test_batched_weight_pack_winograd_layout(transposed, image):
+    """sbgm_pack_desc.transposed bit 1 (image 2): the Winograd F(2,3) image of the forward operator == sbgm_conv_wino_pack_weight; of
+    the data-gradient operator == sbgm_conv_wino_pack_weight of the explicitly transposed + 180-degree-flipped weight.  Bit 2 (image
+    4): the same, bit for bit, for the F(2x2,3x3) image against sbgm_conv_wino2d_pack_weight.  (A convolution through these images
+    against the float64 input gradient: test_gpu_conv_dgrad.py.)"""
+    numel_of, pack_one = ((lib().sbgm_conv_wino_packed_numel, lib().sbgm_conv_wino_pack_weight) if image == 2 else
+                          (lib().sbgm_conv_wino2d_packed_numel, lib().sbgm_conv_wino2d_pack_weight))
     shapes = [(64, 64), (128, 64), (64, 48), (32, 128)]                                          # (Cout, Cin), 3x3
     ws = [rnd(co, ci, 3, 3, seed=i, scale=0.1).to(DEV) for i, (co, ci) in enumerate(shapes)]
     descs, outs, blk, keep = [], [], 0, []
@@ -559,10 +562,10 @@ def test_batched_weight_pack_winograd_layout(transposed):
             pco, pci, cs = ci, co, co
         else:
             weff, pco, pci, cs = w, co, ci, (ci + 15) // 16 * 16
-        numel = lib().sbgm_conv_wino_packed_numel(pco, cs)
+        numel = numel_of(pco, cs)
         single, batched = torch.empty(numel, device=DEV), torch.full((numel,), 7.0, device=DEV)
-        N.check(lib().sbgm_conv_wino_pack_weight(weff.data_ptr(), single.data_ptr(), pco, pci, cs, N.stream()))
-        descs.append(N.PackDesc(w.data_ptr(), batched.data_ptr(), pco, pci, 3, 3, cs, 0, transposed | 2, blk))
+        N.check(pack_one(weff.data_ptr(), single.data_ptr(), pco, pci, cs, N.stream()))
+        descs.append(N.PackDesc(w.data_ptr(), batched.data_ptr(), pco, pci, 3, 3, cs, 0, transposed | image, blk))
         blk += lib().sbgm_conv_pack_weights_batched_blocks(pco, 3, 3, cs)
         outs.append((single, batched))
         keep.append(weff)
