@@ -602,6 +602,25 @@ int sbgm_conv2d_wgrad(const float* dy, const float* x, float* dw_oihw, float* ws
 /* the same, plus the bias gradient db[Cout] = sum_p dy[p,:] produced by the waves that stream dy anyway */
 int sbgm_conv2d_wgrad_bias(const float* dy, const float* x, float* dw_oihw, float* dbias, float* ws, int B, int H, int W, int c_pad,
                            int Cin, int Cout, int KH, int KW, int stride, int pad, void* stream);
+/* What an immediate sbgm_conv2d_wgrad[_bias] call of this geometry launches; host arithmetic only (no device, no pointers), the
+ * helper the launcher itself acts on.  out = {family, gx, gy, tiles_per_wg, n_tiles, direct, M = B*OH*OW, 0}:
+ *   family: SBGM_WGRAD_GENERAL1/2/4 the wave-level kernel with 16 / 32 / 64 input channels per tile (any geometry),
+ *           SBGM_WGRAD_HALO16 / _HALO8 the 3x3 stride-1 halo kernel on 16x16 tiles / on 8x8 maps (four images per tile),
+ *           SBGM_WGRAD_TAP64 / _TAP128 the per-tap split-K GEMM on 64x64 blocks over 128-pixel tiles / 128x128 blocks over 64-pixel
+ *           tiles, SBGM_WGRAD_STEM its form for 8x8 kernels on c_pad = 8;
+ *   gx x gy workgroups, each walking tiles_per_wg of the n_tiles pixel tiles (general kernel: gy pixel splits of tiles_per_wg
+ *   pixels, n_tiles = M);  direct = 1: gy == 1 and the kernel stores OIHW itself, ws is not touched and no layout pass runs.
+ * Non-zero (text in sbgm_last_error) for a geometry sbgm_conv2d_wgrad refuses.  Reads SBGM_NO_LDS_WGRAD per call, SBGM_NO_TAP128 and
+ * SBGM_WG_TARGET once per process, as the launcher does. */
+enum { SBGM_WGRAD_GENERAL1 = 0, SBGM_WGRAD_GENERAL2 = 1, SBGM_WGRAD_GENERAL4 = 2, SBGM_WGRAD_HALO16 = 3, SBGM_WGRAD_HALO8 = 4,
+       SBGM_WGRAD_TAP64 = 5, SBGM_WGRAD_TAP128 = 6, SBGM_WGRAD_STEM = 7 };
+int sbgm_conv2d_wgrad_plan(int B, int H, int W, int c_pad, int Cin, int Cout, int KH, int KW, int stride, int pad, int out[8]);
+/* What sbgm_wgrad_flush would launch for the work queued at this moment (sbgm_wgrad_defer bit 1); changes nothing.  Returns the number
+ * of queued GEMMs n.  out (may be NULL; else 2 + 7 * cap ints): out[0] = layout passes the flush will run (those already queued and
+ * those its GEMMs add), out[1] = layout launches, then min(n, cap) rows {family, launch, gx, gy, tiles_per_wg, n_tiles, direct} in
+ * launch order (16x16 halo layers, 8x8 halo layers, per-tap layers); launch = index of the batched launch of its family the GEMM
+ * rides in.  The split of a queued GEMM depends on everything queued with it, so the rows hold until the next call that queues. */
+int sbgm_wgrad_flush_plan(int* out, int cap);
 /* `optimizer.step()` of torch.optim.Adam (decoupled = 0: weight decay as an L2 term on the gradient) or AdamW (decoupled = 1)
  * over every parameter tensor in one launch (reference training.py:407, training_utils.py:50-59).  desc: DEVICE array of n
  * descriptors, block_begin = exclusive prefix of sbgm_adam_step_blocks(numel), total_blocks = its total.  step: DEVICE

@@ -197,6 +197,8 @@ SIGNATURES = {
     "sbgm_conv8x8s2_dgrad_phase_weight": (_i, [_vp, _vp, _i, _i, _vp]),
     "sbgm_conv2d_wgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "sbgm_conv2d_wgrad_bias": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sbgm_conv2d_wgrad_plan": (_i, [_i] * 10 + [C.POINTER(C.c_int)]),
+    "sbgm_wgrad_flush_plan": (_i, [C.POINTER(C.c_int), _i]),
     "sbgm_colsum": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "sbgm_samplesum": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sbgm_groupnorm_bwd": (_i, [_vp] * 14 + [_i, _i, _i, _i, _vp]),
@@ -261,7 +263,7 @@ SIGNATURES = {
     "sbgm_variogram_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i] + [_vp] * 6 + [_i64, _vp]),
 }
 
-ABI_VERSION = 12      # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 13     # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

@@ -1682,32 +1682,82 @@ static int tap_set_attr() {
     return 0;
 }
 
+// ---- the flush's plan: which launch a queued GEMM rides in and how its pixels are split.  tap_flush, halo_flush and the layout stage below
+// act on these rows; sbgm_wgrad_flush_rows (the C ABI's sbgm_wgrad_flush_plan) reports the same rows without launching
+
+// a layer's pixel split at the flush: its share of the batch's work times the batch's workgroup target, in whole tiles
+static void batch_split(WgradFlushRow& r, int target, double share) {
+    int gy = (int)std::lround(target * share / r.gx);
+    gy = std::max(1, std::min(gy, r.n_tiles));
+    r.tiles_per_wg = (r.n_tiles + gy - 1) / gy;
+    r.gy = (r.n_tiles + r.tiles_per_wg - 1) / r.tiles_per_wg;
+}
+static double tap_cost(const TapQueued& q) { return (double)q.d.gx * q.n_tiles * (q.d.big ? 2.0 : 1.0); }   // MFMAs per tile-step: 128 vs 64 per wave
+static double tap_work() {
+    double work = 0.0;
+    for (auto& q : g_tap_queue) work += tap_cost(q);
+    return work;
+}
+static WgradFlushRow tap_row(size_t i, double work) {
+    static const int target = getenv("SBGM_TAP_BATCH_WGS") ? atoi(getenv("SBGM_TAP_BATCH_WGS")) : 1024;
+    const TapQueued& q = g_tap_queue[i];
+    WgradFlushRow r{q.d.g.stem ? SBGM_WG_STEM : q.d.big ? SBGM_WG_TAP128 : SBGM_WG_TAP64, (int)(i / TAP_MAX), q.d.gx, 1, 1, q.n_tiles, 0, 0};
+    batch_split(r, target, tap_cost(q) / work);
+    // no pixel split: plain OIHW stores, no slab, no layout pass (not for the stem's slab layout)
+    r.direct = r.gy == 1 && !q.d.g.stem ? 1 : 0;
+    r.unpack = q.d.g.stem || (!r.direct && !q.aliased) ? 1 : 0;
+    return r;
+}
+static double halo_work(int which) {
+    double work = 0.0;
+    for (auto& q : g_halo_queue[which]) work += (double)q.d.gx * q.n_tiles;
+    return work;
+}
+static WgradFlushRow halo_row(int which, size_t i, double work) {
+    static const int target = getenv("SBGM_HALO_BATCH_WGS") ? atoi(getenv("SBGM_HALO_BATCH_WGS")) : 768;
+    const HaloQueued& q = g_halo_queue[which][i];
+    WgradFlushRow r{which == 0 ? SBGM_WG_HALO16 : SBGM_WG_HALO8, (int)(i / HALO_MAX), q.d.gx, 1, 1, q.n_tiles, 0, 0};
+    batch_split(r, target, (double)q.d.gx * q.n_tiles / work);
+    r.direct = r.gy == 1 ? 1 : 0;                            // no pixel split: plain OIHW stores, no slab, no layout pass
+    r.unpack = !r.direct;
+    return r;
+}
+static int unpack_launch_of(size_t i) { return (int)(i / UNPACK_MAX); }
+
+std::vector<WgradFlushRow> sbgm_wgrad_flush_rows(int* layout_passes, int* unpack_launches) {
+    std::vector<WgradFlushRow> rows;
+    size_t passes = g_unpack_queue.size();
+    for (int which = 0; which < 2; ++which) {
+        const double work = halo_work(which);
+        for (size_t i = 0; i < g_halo_queue[which].size(); ++i) rows.push_back(halo_row(which, i, work));
+    }
+    const double work = tap_work();
+    for (size_t i = 0; i < g_tap_queue.size(); ++i) rows.push_back(tap_row(i, work));
+    for (auto& r : rows) passes += r.unpack;
+    if (layout_passes) *layout_passes = (int)passes;
+    if (unpack_launches) *unpack_launches = passes ? unpack_launch_of(passes - 1) + 1 : 0;
+    return rows;
+}
+
 // the queued per-tap GEMMs: split each layer's pixels so that all layers together make ~4 workgroups per CU, launch, queue the layout passes
 static int tap_flush(hipStream_t st) {
     if (g_tap_queue.empty()) return 0;
     if (tap_set_attr()) return 1;
-    static const int target = getenv("SBGM_TAP_BATCH_WGS") ? atoi(getenv("SBGM_TAP_BATCH_WGS")) : 1024;
-    double work = 0.0;
-    auto cost = [](const TapQueued& q) { return (double)q.d.gx * q.n_tiles * (q.d.big ? 2.0 : 1.0); };   // MFMAs per tile-step: 128 vs 64 per wave
-    for (auto& q : g_tap_queue) work += cost(q);
+    const double work = tap_work();
     const size_t lds = (size_t)2 * W1_PX * W1_PS * 4;
     size_t i = 0;
     while (i < g_tap_queue.size()) {
         TapTable t{};
         int nb = 0;
-        for (; i < g_tap_queue.size() && t.n < TAP_MAX; ++i) {
+        for (const int launch = tap_row(i, work).launch; i < g_tap_queue.size(); ++i) {
+            const WgradFlushRow r = tap_row(i, work);
+            if (r.launch != launch) break;
             TapQueued& q = g_tap_queue[i];
             TapDesc d = q.d;
-            const double share = cost(q) / work;
-            int gy = (int)std::lround(target * share / d.gx);
-            gy = std::max(1, std::min(gy, q.n_tiles));
-            d.tiles_per_wg = (q.n_tiles + gy - 1) / gy;
-            d.gy = (q.n_tiles + d.tiles_per_wg - 1) / d.tiles_per_wg;
-            // no pixel split: plain OIHW stores, no slab, no layout pass (not for the stem's slab layout)
-            const bool direct = d.gy == 1 && !d.g.stem;
-            d.dw_direct = direct ? q.dw_oihw : nullptr;
-            if (q.d.g.stem) g_unpack_queue.push_back(UnpackDesc{d.dwp, q.dw_oihw, d.Cout, d.Cin, d.Cs, q.unpack_taps});
-            else if (!direct && !q.aliased) g_unpack_queue.push_back(UnpackDesc{d.dwp, q.dw_oihw, d.Cout, d.Cin, d.Cs, q.unpack_taps});
+            d.tiles_per_wg = r.tiles_per_wg;
+            d.gy = r.gy;
+            d.dw_direct = r.direct ? q.dw_oihw : nullptr;
+            if (r.unpack) g_unpack_queue.push_back(UnpackDesc{d.dwp, q.dw_oihw, d.Cout, d.Cin, d.Cs, q.unpack_taps});
             t.d[t.n] = d;
             t.start[t.n] = nb;
             nb += d.gx * d.gy;
@@ -1745,24 +1795,21 @@ static int halo_flush(int which, hipStream_t st) {
     std::vector<HaloQueued>& qv = g_halo_queue[which];
     if (qv.empty()) return 0;
     if (halo_set_attr()) return 1;
-    static const int target = getenv("SBGM_HALO_BATCH_WGS") ? atoi(getenv("SBGM_HALO_BATCH_WGS")) : 768;
-    double work = 0.0;
-    for (auto& q : qv) work += (double)q.d.gx * q.n_tiles;
+    const double work = halo_work(which);
     const size_t lds = (size_t)(WG_DY_FLOATS + (which == 0 ? WgTile<16>::X_FLOATS : WgTile<8>::X_FLOATS)) * 4;
     size_t i = 0;
     while (i < qv.size()) {
         HaloTable t{};
         int nb = 0;
-        for (; i < qv.size() && t.n < HALO_MAX; ++i) {
+        for (const int launch = halo_row(which, i, work).launch; i < qv.size(); ++i) {
+            const WgradFlushRow r = halo_row(which, i, work);
+            if (r.launch != launch) break;
             HaloQueued& q = qv[i];
             HaloDesc d = q.d;
-            int gy = (int)std::lround(target * ((double)d.gx * q.n_tiles / work) / d.gx);
-            gy = std::max(1, std::min(gy, q.n_tiles));
-            d.tiles_per_wg = (q.n_tiles + gy - 1) / gy;
-            d.gy = (q.n_tiles + d.tiles_per_wg - 1) / d.tiles_per_wg;
-            const bool direct = d.gy == 1;                   // no pixel split: plain OIHW stores, no slab, no layout pass
-            d.dw_direct = direct ? q.dw_oihw : nullptr;
-            if (!direct) g_unpack_queue.push_back(UnpackDesc{d.dwp, q.dw_oihw, d.Cout, d.Cin, d.Cs, 9});
+            d.tiles_per_wg = r.tiles_per_wg;
+            d.gy = r.gy;
+            d.dw_direct = r.direct ? q.dw_oihw : nullptr;
+            if (r.unpack) g_unpack_queue.push_back(UnpackDesc{d.dwp, q.dw_oihw, d.Cout, d.Cin, d.Cs, 9});
             t.d[t.n] = d;
             t.start[t.n] = nb;
             nb += d.gx * d.gy;
@@ -1790,7 +1837,7 @@ int sbgm_launch_wgrad_flush(hipStream_t st) {
         UnpackTable t{};
         int nb = 0;
         t.n = 0;
-        for (; i < n && t.n < UNPACK_MAX; ++i) {
+        for (const int launch = unpack_launch_of(i); i < n && unpack_launch_of(i) == launch; ++i) {
             const UnpackDesc& d = g_unpack_queue[i];
             const size_t total = (size_t)d.Cout * d.Cin * (d.taps < 0 ? -d.taps * 8 : d.taps);
             t.d[t.n] = d;
@@ -1810,82 +1857,106 @@ int sbgm_launch_wgrad_flush(hipStream_t st) {
     return 0;
 }
 
-int sbgm_launch_conv_wgrad(const float* dy, const float* x, float* dw_oihw, float* dwp_ws, int B, int H, int W, int Cs, int Cin,
-                           int Cout, int KH, int KW, int S, int PAD, hipStream_t st, float* dbias) {
+// Which kernel body and which pixel split a weight gradient of this geometry gets when launched at once: the launcher below acts on it, and
+// sbgm_conv2d_wgrad_plan (capi.hip) reports it.  Under GEMM deferral the family and n_tiles hold; the split is decided at the flush (above).
+int sbgm_wgrad_plan(WgradPlan* p, int B, int H, int W, int Cs, int Cin, int Cout, int KH, int KW, int S, int PAD) {
     SBGM_CHECK(Cout % 64 == 0, "wgrad: Cout=%d must be a multiple of 64", Cout);
     SBGM_CHECK((Cs == 4 || Cs == 8 || Cs % 16 == 0) && Cin <= Cs, "wgrad: padded Cin %d unsupported (Cin=%d)", Cs, Cin);
     const int OH = (H + 2 * PAD - KH) / S + 1, OW = (W + 2 * PAD - KW) / S + 1, M = B * OH * OW;
+    p->M = M, p->OH = OH, p->OW = OW;
+    p->dy_bytes = (size_t)M * Cout * 4, p->x_bytes = (size_t)B * H * W * Cs * 4;
+    const bool small = p->dy_bytes < (1ull << 31) && p->x_bytes < (1ull << 31), lds_ok = getenv("SBGM_NO_LDS_WGRAD") == nullptr;
+    const bool lds16 = W % 16 == 0 && H % 16 == 0, lds8 = W == 8 && H == 8;
+    const bool stem = Cs == 8 && KW == 8;
+    // the LDS-staged bodies: a workgroup owns a block of (co, ci) and walks tiles_per_wg pixel tiles; one 8-wave workgroup per CU
+    auto tiled = [&](int family, int blocks_x, int n_tiles, bool may_direct) {
+        const int wgs_y = std::max(1, std::min(n_tiles, (256 + blocks_x - 1) / blocks_x));
+        p->family = family, p->gx = blocks_x, p->n_tiles = n_tiles;
+        p->tiles_per_wg = (n_tiles + wgs_y - 1) / wgs_y;
+        p->gy = (n_tiles + p->tiles_per_wg - 1) / p->tiles_per_wg;
+        p->direct = p->gy == 1 && may_direct ? 1 : 0;         // no pixel split: no atomics, no slab, no unpack pass
+    };
+    if (KH == 3 && KW == 3 && S == 1 && PAD == 1 && Cs % 32 == 0 && (lds16 || lds8) && small && lds_ok) {
+        tiled(lds16 ? SBGM_WG_HALO16 : SBGM_WG_HALO8, (Cout / 32) * (Cs / 32), lds16 ? B * (H / 16) * (W / 16) : (B + 3) / 4, true);
+        return 0;
+    }
+    if ((Cs % 64 == 0 || stem) && small && lds_ok) {
+        // one split-K GEMM per tap (1x1 / linear layers, and whatever the halo kernel above does not take)
+        const int taps = stem ? KH : KH * KW;
+        static const bool big_ok = getenv("SBGM_NO_TAP128") == nullptr;
+        const bool big = big_ok && !stem && Cs % 128 == 0 && Cout % 128 == 0;
+        tiled(stem ? SBGM_WG_STEM : big ? SBGM_WG_TAP128 : SBGM_WG_TAP64,
+              big ? taps * (Cout / 128) * (Cs / 128) : taps * (Cout / 64) * (stem ? 1 : Cs / 64),
+              big ? (M + W2_PX - 1) / W2_PX : (M + W1_PX - 1) / W1_PX, !stem);
+        return 0;
+    }
     const int fci = Cs % 64 == 0 ? 4 : (Cs % 32 == 0 ? 2 : 1);
     const int tiles = KH * KW * (Cout / 64) * ((Cs + 16 * fci - 1) / (16 * fci));
     static const int wtarget = getenv("SBGM_WG_TARGET") ? atoi(getenv("SBGM_WG_TARGET")) : 4096;
     int splits = std::max(1, std::min((M + 63) / 64, (wtarget + tiles - 1) / tiles));   // measured: 1024 target waves is 14 % slower per step
-    int pps = ((M + splits - 1) / splits + 3) / 4 * 4;
+    const int pps = ((M + splits - 1) / splits + 3) / 4 * 4;
     splits = (M + pps - 1) / pps;
+    p->family = fci == 4 ? SBGM_WG_GENERAL4 : fci == 2 ? SBGM_WG_GENERAL2 : SBGM_WG_GENERAL1;
+    p->gx = (tiles + 3) / 4, p->gy = splits, p->tiles_per_wg = pps, p->n_tiles = M, p->direct = 0;
+    return 0;
+}
+
+int sbgm_launch_conv_wgrad(const float* dy, const float* x, float* dw_oihw, float* dwp_ws, int B, int H, int W, int Cs, int Cin,
+                           int Cout, int KH, int KW, int S, int PAD, hipStream_t st, float* dbias) {
+    WgradPlan pl;
+    if (sbgm_wgrad_plan(&pl, B, H, W, Cs, Cin, Cout, KH, KW, S, PAD)) return 1;
+    const bool halo = pl.family == SBGM_WG_HALO16 || pl.family == SBGM_WG_HALO8, stem = pl.family == SBGM_WG_STEM;
+    const bool tap = stem || pl.family == SBGM_WG_TAP64 || pl.family == SBGM_WG_TAP128;
+    // ws == dw_oihw: for a 1x1 kernel without channel padding the per-tap kernel's slab IS the OIHW gradient, so the caller may hand in the
+    // (zeroed) gradient tensor as workspace and no unpack pass is needed
+    const bool aliased = dwp_ws == dw_oihw;
+    if (tap) SBGM_CHECK(!aliased || (KH * KW == 1 && Cs == Cin), "wgrad: ws may alias dw only for 1x1 kernels with c_pad == Cin");
+    const int OH = pl.OH, OW = pl.OW, M = pl.M;
     const size_t n = (size_t)KH * KW * Cout * Cs;
     if (!sbgm_scratch_prezeroed && dbias) { if (sbgm_zero_async(dbias, (size_t)Cout * 4, st)) return 1; }
-    const size_t dy_b = (size_t)M * Cout * 4, x_b = (size_t)B * H * W * Cs * 4;
-    const bool lds16 = W % 16 == 0 && H % 16 == 0, lds8 = W == 8 && H == 8;
-    if (KH == 3 && KW == 3 && S == 1 && PAD == 1 && Cs % 32 == 0 && (lds16 || lds8) && dy_b < (1ull << 31) && x_b < (1ull << 31) &&
-        getenv("SBGM_NO_LDS_WGRAD") == nullptr) {
-        const int blocks_x = (Cout / 32) * (Cs / 32);
-        const int n_tiles = lds16 ? B * (H / 16) * (W / 16) : (B + 3) / 4;
-        const int wgs_y = std::max(1, std::min(n_tiles, (256 + blocks_x - 1) / blocks_x));      // one 8-wave workgroup per CU
-        const int tpw = (n_tiles + wgs_y - 1) / wgs_y;
-        const dim3 grid_lds(blocks_x, (n_tiles + tpw - 1) / tpw);
+    const dim3 grid(pl.gx, pl.gy);
+    float* direct = pl.direct ? dw_oihw : nullptr;
+    if (halo) {
+        const bool lds16 = pl.family == SBGM_WG_HALO16;
         if (halo_set_attr()) return 1;
-        HaloDesc d{dy, x, dwp_ws, dbias, nullptr, B, H, W, Cs, Cout, tpw, Cin, blocks_x, (int)grid_lds.y, (uint32_t)dy_b, (uint32_t)x_b};
+        HaloDesc d{dy, x, dwp_ws, dbias, nullptr, B, H, W, Cs, Cout, pl.tiles_per_wg, Cin, pl.gx, pl.gy, (uint32_t)pl.dy_bytes, (uint32_t)pl.x_bytes};
         if (sbgm_wgrad_deferred & 2) {                      // queued for the sweep's batched launch (the split is decided at the flush)
             if (!sbgm_scratch_prezeroed) { if (sbgm_zero_async(dwp_ws, n * 4, st)) return 1; }
-            g_halo_queue[lds16 ? 0 : 1].push_back(HaloQueued{d, n_tiles, dw_oihw});
+            g_halo_queue[lds16 ? 0 : 1].push_back(HaloQueued{d, pl.n_tiles, dw_oihw});
             return 0;
         }
-        float* direct = grid_lds.y == 1 ? dw_oihw : nullptr;          // no pixel split: no atomics, no slab, no unpack pass
         if (!direct && !sbgm_scratch_prezeroed) { if (sbgm_zero_async(dwp_ws, n * 4, st)) return 1; }
         d.dw_direct = direct;
-        if (lds16) hipLaunchKernelGGL(conv3x3_wgrad_lds_kernel<16>, grid_lds, dim3(WG_THREADS), (size_t)(WG_DY_FLOATS + WgTile<16>::X_FLOATS) * 4, st, d);
-        else hipLaunchKernelGGL(conv3x3_wgrad_lds_kernel<8>, grid_lds, dim3(WG_THREADS), (size_t)(WG_DY_FLOATS + WgTile<8>::X_FLOATS) * 4, st, d);
+        if (lds16) hipLaunchKernelGGL(conv3x3_wgrad_lds_kernel<16>, grid, dim3(WG_THREADS), (size_t)(WG_DY_FLOATS + WgTile<16>::X_FLOATS) * 4, st, d);
+        else hipLaunchKernelGGL(conv3x3_wgrad_lds_kernel<8>, grid, dim3(WG_THREADS), (size_t)(WG_DY_FLOATS + WgTile<8>::X_FLOATS) * 4, st, d);
         SBGM_LAUNCH_CHECK();
         if (!direct) return unpack_or_queue(dwp_ws, dw_oihw, Cout, Cin, Cs, KH * KW, st);
         return 0;
     }
-    const bool stem = Cs == 8 && KW == 8;
-    if ((Cs % 64 == 0 || stem) && dy_b < (1ull << 31) && x_b < (1ull << 31) && getenv("SBGM_NO_LDS_WGRAD") == nullptr) {
-        // one split-K GEMM per tap (1x1 / linear layers, and whatever the halo kernel above does not take)
-        const int taps = stem ? KH : KH * KW;
-        static const bool big_ok = getenv("SBGM_NO_TAP128") == nullptr;
-        const int big = big_ok && !stem && Cs % 128 == 0 && Cout % 128 == 0 ? 1 : 0;
-        const int blocks_x = big ? taps * (Cout / 128) * (Cs / 128) : taps * (Cout / 64) * (stem ? 1 : Cs / 64);
-        const int n_tiles = big ? (M + W2_PX - 1) / W2_PX : (M + W1_PX - 1) / W1_PX;
-        const int wgs_y = std::max(1, std::min(n_tiles, (256 + blocks_x - 1) / blocks_x));      // one 8-wave workgroup per CU
-        const int tpw = (n_tiles + wgs_y - 1) / wgs_y;
-        const dim3 grid_lds(blocks_x, (n_tiles + tpw - 1) / tpw);
+    if (tap) {
         const size_t lds = (size_t)2 * W1_PX * W1_PS * 4;
         if (tap_set_attr()) return 1;
-        // ws == dw_oihw: for a 1x1 kernel without channel padding the slab IS the OIHW gradient, so the caller may hand in the
-        // (zeroed) gradient tensor as workspace and no unpack pass is needed
-        const bool aliased = dwp_ws == dw_oihw;
-        SBGM_CHECK(!aliased || (KH * KW == 1 && Cs == Cin), "wgrad: ws may alias dw only for 1x1 kernels with c_pad == Cin");
         const TapGeom tg{M, OH, OW, H, W, S, PAD, KW, KH * KW, stem ? 1 : 0};
-        TapDesc d{dy, x, dwp_ws, dbias, nullptr, tg, Cs, Cout, tpw, Cin, blocks_x, (int)grid_lds.y, (uint32_t)dy_b, (uint32_t)x_b, big};
+        TapDesc d{dy, x, dwp_ws, dbias, nullptr, tg, Cs, Cout, pl.tiles_per_wg, Cin, pl.gx, pl.gy, (uint32_t)pl.dy_bytes, (uint32_t)pl.x_bytes,
+                  pl.family == SBGM_WG_TAP128 ? 1 : 0};
         if (sbgm_wgrad_deferred & 2) {
             // queued: the slab may still be needed (the split is decided at the flush), so it is zeroed now unless it arrives zeroed
             if (!sbgm_scratch_prezeroed) { if (sbgm_zero_async(dwp_ws, n * 4, st)) return 1; }
-            g_tap_queue.push_back(TapQueued{d, n_tiles, dw_oihw, stem ? -KH : KH * KW, aliased});
+            g_tap_queue.push_back(TapQueued{d, pl.n_tiles, dw_oihw, stem ? -KH : KH * KW, aliased});
             return 0;
         }
-        float* direct = grid_lds.y == 1 && !stem ? dw_oihw : nullptr;
         if (!direct && !sbgm_scratch_prezeroed) { if (sbgm_zero_async(dwp_ws, n * 4, st)) return 1; }
         d.dw_direct = direct;
-        hipLaunchKernelGGL(conv_tap_wgrad_lds_kernel, grid_lds, dim3(WG_THREADS), lds, st, d);
+        hipLaunchKernelGGL(conv_tap_wgrad_lds_kernel, grid, dim3(WG_THREADS), lds, st, d);
         SBGM_LAUNCH_CHECK();
         if (stem) return unpack_or_queue(dwp_ws, dw_oihw, Cout, Cin, Cs, -KH, st);
         if (!direct && !aliased) return unpack_or_queue(dwp_ws, dw_oihw, Cout, Cin, Cs, KH * KW, st);
         return 0;
     }
     if (!sbgm_scratch_prezeroed) { if (sbgm_zero_async(dwp_ws, n * 4, st)) return 1; }
-    dim3 grid((tiles + 3) / 4, splits);
+    const int pps = pl.tiles_per_wg;
 #define SBGM_WG(F) hipLaunchKernelGGL(conv_wgrad_kernel<F>, grid, dim3(256), 0, st, dy, x, dwp_ws, B, H, W, Cs, OH, OW, Cout, KH, KW, S, PAD, pps, dbias)
-    if (fci == 4) SBGM_WG(4); else if (fci == 2) SBGM_WG(2); else SBGM_WG(1);
+    if (pl.family == SBGM_WG_GENERAL4) SBGM_WG(4); else if (pl.family == SBGM_WG_GENERAL2) SBGM_WG(2); else SBGM_WG(1);
 #undef SBGM_WG
     SBGM_LAUNCH_CHECK();
     return unpack_or_queue(dwp_ws, dw_oihw, Cout, Cin, Cs, KH * KW, st);

@@ -368,6 +368,30 @@ int sbgm_conv2d_wgrad_bias(const float* dy, const float* x, float* dw_oihw, floa
     SBGM_CHECK(dbias != nullptr, "conv2d_wgrad_bias: dbias is required");
     return sbgm_launch_conv_wgrad(dy, x, dw_oihw, ws, B, H, W, c_pad, Cin, Cout, KH, KW, stride, pad, ST, dbias);
 }
+static_assert(SBGM_WG_GENERAL1 == SBGM_WGRAD_GENERAL1 && SBGM_WG_GENERAL4 == SBGM_WGRAD_GENERAL4 && SBGM_WG_HALO16 == SBGM_WGRAD_HALO16 &&
+                  SBGM_WG_HALO8 == SBGM_WGRAD_HALO8 && SBGM_WG_TAP64 == SBGM_WGRAD_TAP64 && SBGM_WG_TAP128 == SBGM_WGRAD_TAP128 &&
+                  SBGM_WG_STEM == SBGM_WGRAD_STEM, "kernels.h and include/sbgm_hip.h number the weight-gradient families alike");
+int sbgm_conv2d_wgrad_plan(int B, int H, int W, int c_pad, int Cin, int Cout, int KH, int KW, int stride, int pad, int out[8]) {
+    SBGM_CHECK(out != nullptr, "conv2d_wgrad_plan: out is required");
+    WgradPlan p;
+    if (sbgm_wgrad_plan(&p, B, H, W, c_pad, Cin, Cout, KH, KW, stride, pad)) return 1;
+    const int v[8] = {p.family, p.gx, p.gy, p.tiles_per_wg, p.n_tiles, p.direct, p.M, 0};
+    std::copy(v, v + 8, out);
+    return 0;
+}
+int sbgm_wgrad_flush_plan(int* out, int cap) {
+    int passes = 0, launches = 0;
+    const std::vector<WgradFlushRow> rows = sbgm_wgrad_flush_rows(&passes, &launches);
+    if (out) {
+        out[0] = passes, out[1] = launches;
+        for (int i = 0; i < (int)rows.size() && i < cap; ++i) {
+            const WgradFlushRow& r = rows[i];
+            const int v[7] = {r.family, r.launch, r.gx, r.gy, r.tiles_per_wg, r.n_tiles, r.direct};
+            std::copy(v, v + 7, out + 2 + 7 * i);
+        }
+    }
+    return (int)rows.size();
+}
 int sbgm_colsum(const float* x, const float* y, float* out, int M, int C, void* stream) { return sbgm_launch_colsum(x, y, out, M, C, ST); }
 int sbgm_samplesum(const float* x, float* out, int B, int HW, int C, void* stream) { return sbgm_launch_samplesum(x, out, B, HW, C, ST); }
 int sbgm_groupnorm_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* skip, const float* tbias,

@@ -39,6 +39,26 @@ extern int sbgm_wgrad_deferred;                 // backward.hip: queue the slab 
 int sbgm_wgrad_pending();
 void sbgm_wgrad_discard_queue();
 int sbgm_launch_wgrad_flush(hipStream_t st);
+// What sbgm_launch_conv_wgrad launches for a geometry, and what sbgm_launch_wgrad_flush will launch for a queued GEMM: the launcher and
+// the flush act on these, and the C ABI's plan queries report them.  Host arithmetic only.
+enum { SBGM_WG_GENERAL1 = 0, SBGM_WG_GENERAL2, SBGM_WG_GENERAL4, SBGM_WG_HALO16, SBGM_WG_HALO8, SBGM_WG_TAP64, SBGM_WG_TAP128, SBGM_WG_STEM };
+struct WgradPlan {
+    int family;            // SBGM_WG_*
+    int gx, gy;            // grid; general kernel: gy = pixel splits
+    int tiles_per_wg;      // pixel tiles a workgroup walks; general kernel: pixels per split
+    int n_tiles;           // pixel tiles of the call; general kernel: output pixels M
+    int direct;            // 1: one workgroup owns a block and stores OIHW, no slab, no layout pass
+    int M, OH, OW;
+    size_t dy_bytes, x_bytes;
+};
+int sbgm_wgrad_plan(WgradPlan* p, int B, int H, int W, int Cs, int Cin, int Cout, int KH, int KW, int S, int PAD);
+struct WgradFlushRow {
+    int family, launch;    // launch: index of the batched launch (table) of its family the GEMM rides in
+    int gx, gy, tiles_per_wg, n_tiles, direct;
+    int unpack;            // 1: the flush queues a layout pass behind it
+};
+// rows of the queued GEMMs in launch order; *layout_passes / *unpack_launches: what the flush's layout stage will run
+std::vector<WgradFlushRow> sbgm_wgrad_flush_rows(int* layout_passes, int* unpack_launches);
 
 // ---- conv_wino.hip: 3x3 stride-1 pad-1 convolution, 1-D Winograd F(2,3) along rows ------------------------------------
 size_t sbgm_wino_packed_floats(int Cout, int cs);

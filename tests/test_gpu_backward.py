@@ -41,7 +41,8 @@ def leaf(t, dev=False):
                                                  (1, 64, 16, 64, 8, 2, 3), (2, 128, 4, 64, 3, 1, 1), (1, 256, 2, 512, 3, 2, 1),
                                                  (2, 64, 16, 64, 3, 1, 1), (1, 128, 32, 64, 3, 1, 1), (3, 64, 16, 128, 3, 1, 1),    # LDS-staged wgrad
                                                  (5, 128, 8, 64, 3, 1, 1), (8, 64, 8, 64, 3, 1, 1), (1, 64, 8, 64, 3, 1, 1),      # ... 8 x 8 maps: 4 images per tile
-                                                 (9, 64, 16, 64, 3, 1, 1),                                                       # several tiles per workgroup
+                                                 (9, 64, 16, 64, 3, 1, 1),                                                       # 9 tiles, 9 workgroup rows: one tile each
+                                                 (5, 256, 16, 256, 3, 1, 1),                                                     # two tiles per workgroup, ragged last (sbgm_conv2d_wgrad_plan)
                                                  (3, 128, 16, 64, 1, 1, 0), (1, 64, 6, 128, 1, 1, 0), (2, 192, 10, 64, 1, 2, 0),  # LDS-staged 1x1 (pixel split / ragged tile / stride 2)
                                                  (8, 64, 32, 64, 1, 1, 0),
                                                  (2, 32, 6, 64, 3, 1, 1), (1, 96, 6, 64, 3, 1, 1),        # neither halo nor per-tap: conv_wgrad_kernel<2>
