@@ -35,7 +35,7 @@ int sbgm_launch_conv_pair(ConvParams pm, const ConvTile& tm, ConvParams pa, cons
 // When set, the launchers below trust that their atomically accumulated scratch (weight-gradient slab, norm-backward sums)
 // arrives zeroed and skip their own memsets (the training path zeroes one pooled buffer per step instead of ~75 small ones).
 extern int sbgm_scratch_prezeroed;
-extern int sbgm_wgrad_deferred;                 // backward.hip: queue the slab -> OIHW passes for sbgm_launch_wgrad_flush
+extern int sbgm_wgrad_deferred;                 // conv_wgrad.hip: bit 0 queues the slab -> OIHW passes, bit 1 the GEMMs, for sbgm_launch_wgrad_flush
 int sbgm_wgrad_pending();
 void sbgm_wgrad_discard_queue();
 int sbgm_launch_wgrad_flush(hipStream_t st);
@@ -460,10 +460,12 @@ int sbgm_launch_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, 
 int sbgm_launch_pointwise_chain(const float* x, float* y, size_t n, int n_ops, const int* ops, const float* consts, hipStream_t st);
 int sbgm_launch_sample_extremes(const float* x, int B, size_t per, float q, float* out_max, float* out_q, hipStream_t st);
 
-// ---- backward.hip (training path) ------------------------------------------------------------------------------------
+// ---- conv_wgrad.hip (training path: weight gradients; the plan and flush declarations above are its too) ---------------
 int sbgm_launch_conv_wgrad(const float* dy, const float* x, float* dw_oihw, float* dwp_ws, int B, int H, int W, int Cs, int Cin,
                            int Cout, int KH, int KW, int S, int PAD, hipStream_t st,
                            float* dbias = nullptr);   // optional bias gradient [Cout] (zeroed by the launcher unless pre-zeroed)
+
+// ---- backward.hip (training path) ------------------------------------------------------------------------------------
 // OIHW operator [4*Cin][Cout][5][5] of the phase-decomposed data gradient of an 8x8/s2/p3 convolution (see backward.hip)
 int sbgm_launch_dgrad_phase_weight(const float* w_oihw, float* out, int Cout, int Cin, hipStream_t st);
 int sbgm_launch_colsum(const float* x, const float* y, float* out, int M, int C, hipStream_t st);

@@ -1,7 +1,8 @@
 """sbgm_conv2d_wgrad_plan / sbgm_wgrad_flush_plan without a device: the case table of conv_wgrad_ref.py reaches every kernel body, store
 path and tile edge of the weight-gradient launcher that test_gpu_conv_wgrad.py then runs against float64.  The queries report the
-helpers the launcher and the flush themselves act on (csrc/backward.hip: sbgm_wgrad_plan, sbgm_wgrad_flush_rows)."""
+helpers the launcher and the flush themselves act on (csrc/conv_wgrad.hip: sbgm_wgrad_plan, sbgm_wgrad_flush_rows)."""
 import ctypes as C
+import json
 import pathlib
 import re
 
@@ -13,11 +14,19 @@ from sbgm_danra_amd import _native as N
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 
-def plan(geom):
-    """dict of the immediate plan, or None where the launcher refuses the call"""
+def raw_plan(geom):
+    """the eight integers of sbgm_conv2d_wgrad_plan, or None where the launcher refuses the call"""
     B, Cin, H, W, Cout, k, s, p, cs = R.full(geom)
     out = (C.c_int * 8)(*([-7] * 8))
     if N.lib().sbgm_conv2d_wgrad_plan(B, H, W, cs, Cin, Cout, k, k, s, p, out):
+        return None
+    return list(out)
+
+
+def plan(geom):
+    """dict of the immediate plan, or None where the launcher refuses the call"""
+    out = raw_plan(geom)
+    if out is None:
         return None
     fam, gx, gy, tpw, n_tiles, direct, M, zero = out
     assert M == R.pixels(geom) and zero == 0 and direct in (0, 1) and gx >= 1 and gy >= 1 and tpw >= 1
@@ -117,6 +126,26 @@ def test_refused_calls():
     assert plan(R.ALIAS_REFUSED)["family"] == R.TAP64
     assert lib.sbgm_conv2d_wgrad(4096, 4096, 8192, 8192, B, H, W, cs, Cin, Cout, k, k, s, p, None) != 0
     assert b"alias" in lib.sbgm_last_error()
+
+
+def test_every_plan_equals_the_one_recorded_before_the_launcher_moved(monkeypatch):
+    """tests/golden/wgrad_plans_parent.json (tools/record_wgrad_plans.py) holds the eight integers the planner gave, at the commit named in
+    the file, for every geometry of the case tables and of tools/bench_wgrad.py; a refused geometry is recorded as null.  Exact equality."""
+    golden = json.loads((ROOT / "tests" / "golden" / "wgrad_plans_parent.json").read_text())
+    assert re.fullmatch(r"[0-9a-f]{40}", golden["parent"])
+    recorded = set()
+    for row in golden["plans"]:
+        if row["no_lds"]:
+            monkeypatch.setenv("SBGM_NO_LDS_WGRAD", "1")
+        else:
+            monkeypatch.delenv("SBGM_NO_LDS_WGRAD", raising=False)
+        assert raw_plan(tuple(row["geom"])) == row["plan"], row
+        recorded.add((row["source"], tuple(row["geom"]), row["no_lds"], row["plan"] is None))
+    monkeypatch.delenv("SBGM_NO_LDS_WGRAD", raising=False)
+    want = {("CASES", R.full(g), False, False) for g, _, _ in R.CASES} | {("ONE_HOT_CASES", R.full(g), False, False) for g, _ in R.ONE_HOT_CASES}
+    want |= {("REFUSED", R.full(g), False, True) for g in R.REFUSED} | {("GENERAL4_CASES", R.full(g), e, False) for g in R.GENERAL4_CASES for e in (False, True)}
+    assert want <= recorded, want - recorded
+    assert sum(1 for r in recorded if r[0].startswith("bench_wgrad.")) == 21
 
 
 def test_flush_plan_of_an_empty_queue_and_its_cap():

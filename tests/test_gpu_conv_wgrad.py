@@ -14,6 +14,8 @@ geometry, family, mode, the tap (kh, kw) and the worst (co, ci).
 The defer mask, the prezeroed switch and the queue are process-wide: every test restores them and discards the queue in a `finally`."""
 import contextlib
 import ctypes as C
+import json
+import pathlib
 
 import pytest
 import torch
@@ -28,6 +30,7 @@ DEV = "cuda"
 NAN = float("nan")
 MODES = ["immediate", "prezeroed", "unpack-deferred", "gemm-deferred"]
 QUEUED = (R.HALO16, R.HALO8, R.TAP64, R.TAP128, R.STEM)           # the families sbgm_wgrad_defer bit 1 queues
+GOLDEN = json.loads((pathlib.Path(__file__).parent / "golden" / "wgrad_plans_parent.json").read_text())
 
 
 def lib():
@@ -62,6 +65,15 @@ def flush_plan(cap=256):
     assert all(v == -7 for v in buf[2 + 7 * min(n, cap):]), "sbgm_wgrad_flush_plan wrote past its cap"
     keys = ("family", "launch", "gx", "gy", "tpw", "n_tiles", "direct")
     return [dict(zip(keys, buf[2 + 7 * i:9 + 7 * i])) for i in range(min(n, cap))], buf[0], buf[1]
+
+
+def flush_record(rows, passes, launches):
+    return dict(rows=[[r[k] for k in ("family", "launch", "gx", "gy", "tpw", "n_tiles", "direct")] for r in rows], passes=passes, launches=launches)
+
+
+def check_against_parent(name, rows, passes, launches):
+    """exactly the flush plan this queue got at the commit named in tests/golden/wgrad_plans_parent.json (tools/record_wgrad_plans.py)"""
+    assert flush_record(rows, passes, launches) == GOLDEN["flush"][name], name
 
 
 def ragged_multi(row):
@@ -182,6 +194,7 @@ def flush_queue(name, entries, defer, expect, bias_every=2):
             call.launch()
             calls.append(call)
         rows, passes, launches = flush_plan()
+        check_against_parent(name, rows, passes, launches)
         expect(rows, passes, launches)
         N.check(lib().sbgm_wgrad_flush(N.stream()))
         assert lib().sbgm_wgrad_flush_pending() == 0

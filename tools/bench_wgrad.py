@@ -18,11 +18,15 @@ def run(B, H, C, cout, k=3, stride=1, reps=20):
     us = e0.elapsed_time(e1) / reps * 1e3
     fl = 2 * B * OH * OH * C * cout * k * k
     print(f"B{B} H{H} C{C}->{cout} k{k}s{stride}: {us:.1f} us  {fl/us/1e6:.1f} TF", flush=True)
-cfgs = [(8, 64, 64, 64), (8, 32, 128, 128), (8, 16, 256, 256), (8, 64, 128, 64), (8, 32, 256, 128), (8, 16, 512, 256), (8, 128, 64, 64), (8, 64, 128, 128), (32, 64, 64, 64), (32, 16, 256, 256)]
-if len(sys.argv) > 1 and sys.argv[1] == "general":
-    cfgs = [(8, 8, 512, 512), (8, 8, 1024, 512), (8, 16, 256, 512, 3, 2), (8, 32, 128, 256, 3, 2), (8, 64, 64, 128, 3, 2), (8, 16, 256, 512, 1, 2),
-            (8, 16, 256, 768, 1, 1), (8, 16, 256, 256, 1, 1), (8, 8, 512, 1536, 1, 1), (8, 32, 256, 128, 1, 1), (8, 64, 128, 64, 1, 1)]
-elif len(sys.argv) > 1:
-    cfgs = cfgs[:int(sys.argv[1])]
-for a in cfgs:
-    run(*a)
+# (B, H, C, cout[, k, stride]); tools/record_wgrad_plans.py records the plan of every row of both lists
+CFGS = [(8, 64, 64, 64), (8, 32, 128, 128), (8, 16, 256, 256), (8, 64, 128, 64), (8, 32, 256, 128), (8, 16, 512, 256), (8, 128, 64, 64), (8, 64, 128, 128), (32, 64, 64, 64), (32, 16, 256, 256)]
+GENERAL_CFGS = [(8, 8, 512, 512), (8, 8, 1024, 512), (8, 16, 256, 512, 3, 2), (8, 32, 128, 256, 3, 2), (8, 64, 64, 128, 3, 2), (8, 16, 256, 512, 1, 2),
+                (8, 16, 256, 768, 1, 1), (8, 16, 256, 256, 1, 1), (8, 8, 512, 1536, 1, 1), (8, 32, 256, 128, 1, 1), (8, 64, 128, 64, 1, 1)]
+if __name__ == "__main__":
+    cfgs = CFGS
+    if len(sys.argv) > 1 and sys.argv[1] == "general":
+        cfgs = GENERAL_CFGS
+    elif len(sys.argv) > 1:
+        cfgs = cfgs[:int(sys.argv[1])]
+    for a in cfgs:
+        run(*a)
