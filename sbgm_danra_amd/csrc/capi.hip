@@ -1,5 +1,8 @@
-// Per-op C-ABI entry points declared in include/sbgm_hip.h (the model / sampler entry points live in engine.hip).
+// Per-op C-ABI entry points declared in include/sbgm_hip.h (the model entry points live in model.hip and forward.hip, the sampler
+// entry points in sampler_run.hip).
 #include <string.h>
+#include <algorithm>
+#include <vector>
 
 #include "../../include/sbgm_hip.h"
 #include "common.h"
@@ -7,7 +10,31 @@
 
 #define ST ((hipStream_t)stream)
 
+// ---- helpers of the stand-alone operators at the end of this file ------------------------------------------------------------
+constexpr float LN_EPS = 1e-5f;      // the attention blocks' LayerNorm (engine.h); sbgm_ln_linear_tiles lists candidates for it
+// the block's convolution: bilinear x2 on load where the decoder fuses it (width >= 32), else a plain one on an upsampled copy
+static bool final_block_fused(int W) { return W >= 32; }
+static ConvParams final_block_conv(int B, int H, int W, int C) {
+    ConvParams p{};
+    p.B = B; p.H = H; p.W = W; p.Cs = C; p.Cout = 16;
+    p.in_mode = final_block_fused(W) ? 2 : 0;
+    return p;
+}
+// a LayerNorm folded into the linear after it, as the convolution it runs as
+static ConvParams ln_linear_conv(int M, int C, int Cout, float eps) {
+    ConvParams p{};
+    p.B = 1; p.H = 1; p.W = M; p.Cs = C; p.Cout = Cout;
+    p.in_mode = 3; p.ln_eps = eps;
+    return p;
+}
+
+const char* sbgm_get_error();
+
 extern "C" {
+
+const char* sbgm_last_error(void) { return sbgm_get_error(); }
+int sbgm_abi_version(void) { return 13; }
+int sbgm_model_config_size(void) { return (int)sizeof(sbgm_model_config); }
 
 int sbgm_pack_input(const float* const* srcs, const int* src_channels, int n_src, float* dst_nhwc, int B, int H, int W,
                     int c_pad, void* stream) {
@@ -510,5 +537,182 @@ int sbgm_rk45_commit(const void* state, double* y, const double* y_new, float* K
 int sbgm_rk45_read(const void* state, int groups, int64_t* stats_i, double* stats_d, void* stream) {
     return sbgm_ode_read_state(state, groups, stats_i, stats_d, ST);
 }
+
+// ---- the composed final block on its own (conv_final.hip; the engine's route in forward.hip, without a network) -------------------
+int sbgm_final_compose_pack(const float* w1_oihw, const float* b1, const float* w2_oihw, float* wc_oihw, float* bc, int C, void* stream) {
+    return sbgm_launch_final_compose(w1_oihw, b1, w2_oihw, wc_oihw, bc, C, (hipStream_t)stream);
+}
+
+int sbgm_final_block_tiles(int B, int H, int W, int C, int* tiles, int cap) {
+    static const float present = 0.f;                 // the candidate list only asks which weight images exist
+    const ConvImages im{{&present, &present, &present, nullptr}};
+    const std::vector<ConvTile> c = sbgm_conv_candidates(ConvGeom{3, 3, 1, 1}, final_block_conv(B, H, W, C), im, false);
+    for (int i = 0; i < (int)c.size() && i < cap; ++i) c[i].to_ints(tiles + 6 * i);
+    return (int)c.size();
+}
+
+int sbgm_final_block_fwd(const float* x, const float* in_affine, const float* in_skip, int in_act, const float* w_packed,
+                         const float* w_wino, const float* w_wino2d, const float* bc, const float* b2, const float* t, float sigma,
+                         float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, const int* tile, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(x && w_packed && w_wino && bc && b2 && out && ws, "final_block_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 2 && H % 2 == 0 && W >= 16 && W % 16 == 0 && C >= 16 && C % 16 == 0,
+               "final_block_fwd: needs an even H, W %% 16 == 0 and C %% 16 == 0 (B=%d H=%d W=%d C=%d)", B, H, W, C);
+    const size_t M = (size_t)B * H * W;
+    const bool fused = final_block_fused(W);
+    SBGM_CHECK(fused || (!in_affine && !in_skip && in_act == SBGM_ACT_NONE), "final_block_fwd: affine / skip / activation on load need the fused route (W >= 32)");
+    SBGM_CHECK((size_t)ws_floats >= M * (fused ? 16 : 16 + (size_t)C), "final_block_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    ConvParams p = final_block_conv(B, H, W, C);
+    const ConvImages im{{w_packed, w_wino, w_wino2d, nullptr}};
+    p.bias = bc; p.out = ws;
+    if (fused) {
+        p.x = x; p.in_affine = in_affine; p.in_skip = in_skip; p.in_act = in_act;
+    } else {
+        float* up = ws + M * 16;
+        if (sbgm_launch_upsample2x(x, up, B, H / 2, W / 2, C, st)) return 1;
+        p.x = up;
+    }
+    const ConvTile ct = tile ? ConvTile::from_ints(tile) : sbgm_cout16_tile(p, im);
+    const ConvFamily fam = ct.well_formed() ? ct.family() : FAM_IGEMM;
+    int v[6];
+    ct.to_ints(v);
+    SBGM_CHECK(ct.fco == 1 && ct.splits == 1 && (fam == FAM_LDS_WINO || ((fam == FAM_W2D || fam == FAM_W2DP) && w_wino2d)),
+               "final_block_fwd: tile {%d,%d,%d,%d,%d,%d} is no 16-channel LDS-staged Winograd kernel", v[0], v[1], v[2], v[3], v[4], v[5]);
+    if (sbgm_launch_tile(ConvGeom{3, 3, 1, 1}, p, im, ct, nullptr, st)) return 1;
+    return sbgm_launch_tap_gather_rows(ws, b2, t, sigma, out, B, H, W, st);
+}
+
+// ---- the same block mixed at low resolution (conv_final.hip, second half; the engine's fin_lowres route) ----------------------------
+int64_t sbgm_final_lowres_packed_numel(int C) { return C >= 16 && C % 16 == 0 ? (int64_t)sbgm_final_lowres_packed_floats(C) : 0; }
+int64_t sbgm_final_lowres_ws_numel(int B, int H, int W) {
+    return B >= 1 && H >= 2 && W >= 2 ? (int64_t)sbgm_final_lowres_ws_floats(B, H / 2, W / 2) : 0;
+}
+
+int sbgm_final_lowres_pack(const float* w1_oihw, const float* b1, const float* w2_oihw, const float* b2, float* wz_out, float* beta_out,
+                           float* wz_packed, int C, void* stream) {
+    return sbgm_launch_final_lowres_pack(w1_oihw, b1, w2_oihw, b2, wz_out, beta_out, wz_packed, C, (hipStream_t)stream);
+}
+
+int sbgm_final_lowres_fwd(const float* x_lowres_nhwc, const float* in_affine, const float* in_skip, int in_act, const float* wz_packed,
+                          const float* beta, const float* t, float sigma, float* out, float* ws, int64_t ws_floats, int B, int H, int W,
+                          int C, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(x_lowres_nhwc && wz_packed && beta && out && ws, "final_lowres_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 4 && H % 2 == 0 && W >= 4 && W % 2 == 0, "final_lowres_fwd: needs even H, W >= 4 (B=%d H=%d W=%d)", B, H, W);
+    SBGM_CHECK(ws_floats >= sbgm_final_lowres_ws_numel(B, H, W), "final_lowres_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    if (sbgm_launch_final_mix(x_lowres_nhwc, in_affine, in_skip, in_act, wz_packed, ws, B, H / 2, W / 2, C, st)) return 1;
+    return sbgm_launch_final_gather(ws, beta, t, sigma, out, B, H / 2, W / 2, st);
+}
+
+// ---- the same with the decoder's last skip formed inside the mix (the step samplers' skip_mix route) --------------------------------
+int64_t sbgm_skip_mix_packed_numel(void) { return SKIP_MIX_PACKED_FLOATS; }
+
+int sbgm_skip_mix_pack(const float* w1_oihw, float* w1x, int Cin, void* stream) {
+    return sbgm_launch_skip_mix_pack(w1_oihw, w1x, Cin, (hipStream_t)stream);
+}
+
+int sbgm_final_lowres_skip_fwd(const float* raw_lowres_nhwc, const float* in_affine, int in_act, const float* wz_packed, const float* beta,
+                               const float* x_planar, const float* sc_nhwc, const float* tb0, const float* w1x, const float* t, float sigma,
+                               float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(raw_lowres_nhwc && wz_packed && beta && out && ws, "final_lowres_skip_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 4 && H % 2 == 0 && W >= 4 && W % 2 == 0, "final_lowres_skip_fwd: needs even H, W >= 4 (B=%d H=%d W=%d)", B, H, W);
+    SBGM_CHECK(ws_floats >= sbgm_final_lowres_ws_numel(B, H, W), "final_lowres_skip_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    if (sbgm_launch_final_mix_skipx(raw_lowres_nhwc, in_affine, in_act, wz_packed, x_planar, sc_nhwc, tb0, w1x, ws, B, H / 2, W / 2, C, st))
+        return 1;
+    return sbgm_launch_final_gather(ws, beta, t, sigma, out, B, H / 2, W / 2, st);
+}
+
+// ---- a small-map decoder block's conv_up at low resolution (conv_uplow.hip; the engine's up_lowres route) ----------------------------
+int64_t sbgm_up_lowres_weight_numel(int C) { return C >= 16 && C % 16 == 0 ? (int64_t)sbgm_up_lowres_weight_floats(C) : 0; }
+// Z, then the chunk partials of the GroupNorm fallback ([B][64][G][2] doubles)
+int64_t sbgm_up_lowres_ws_numel(int B, int H, int W, int C, int groups) {
+    if (B < 1 || H < 2 || W < 2 || C < 16) return 0;
+    return (int64_t)sbgm_up_lowres_ws_floats(B, H / 2, W / 2, C) + (int64_t)B * 64 * std::max(groups, 0) * 4;
+}
+
+int sbgm_up_lowres_pack(const float* w_oihw, float* w_taps, float* w_packed, int C, void* stream) {
+    return sbgm_launch_up_lowres_pack(w_oihw, w_taps, w_packed, C, (hipStream_t)stream);
+}
+
+int sbgm_up_lowres_fwd(const float* x_lowres_nhwc, const float* w_packed, const float* bias, const float* gamma, const float* beta,
+                       int groups, float eps, float* out, float* ws, int64_t ws_floats, int B, int H, int W, int C, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(x_lowres_nhwc && w_packed && bias && out && ws, "up_lowres_fwd: null tensor");
+    SBGM_CHECK(B >= 1 && H >= 2 && H % 2 == 0 && W >= 2 && W % 2 == 0 && C >= 16 && C % 16 == 0 && groups >= 0,
+               "up_lowres_fwd: needs even H, W >= 2 and C %% 16 == 0 (B=%d H=%d W=%d C=%d)", B, H, W, C);
+    SBGM_CHECK(ws_floats >= sbgm_up_lowres_ws_numel(B, H, W, C, groups), "up_lowres_fwd: workspace of %lld floats is too small", (long long)ws_floats);
+    const int h = H / 2, w = W / 2;
+    const ConvGeom lin{1, 1, 1, 0};
+    ConvParams p{};
+    p.x = x_lowres_nhwc; p.out = ws; p.B = B; p.H = h; p.W = w; p.Cs = C; p.Cout = 9 * C;
+    const ConvImages im{{w_packed, nullptr, nullptr, nullptr}};
+    ConvTile ct = sbgm_static_tile(lin, p, im);
+    ct.splits = 1;                                   // no split-K scratch here
+    if (sbgm_launch_tile(lin, p, im, ct, nullptr, st)) return 1;
+    double* stats = reinterpret_cast<double*>(ws + sbgm_up_lowres_ws_floats(B, h, w, C));
+    int chunks = 0, normed = 0;
+    if (sbgm_launch_up_gather(ws, bias, out, gamma, beta, groups > 0 ? stats : nullptr, groups, eps, B, h, w, C, &chunks, &normed, st)) return 1;
+    if (groups == 0 || normed) return 0;
+    if (chunks == 0 && sbgm_launch_gn_partial(out, stats, B, H * W, C, groups, &chunks, st)) return 1;
+    return sbgm_launch_groupnorm_apply(out, out, gamma, beta, nullptr, nullptr, SBGM_ACT_NONE, B, H * W, C, groups, eps, stats, chunks, st);
+}
+
+// ---- a LayerNorm folded into the linear after it (conv_igemm.hip, in_mode 3; the engine's ln_fold route, without a network) ----------
+int sbgm_ln_fold_pack(const float* w, const float* b, const float* gamma, const float* beta, int C, int Cout, float* w2_oihw, float* w2_packed,
+                      float* h, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SBGM_CHECK(w2_packed, "ln_fold_pack: null tensor");
+    if (sbgm_launch_ln_fold(w, b, gamma, beta, w2_oihw, h, C, Cout, st)) return 1;
+    return sbgm_launch_pack_conv_weight(w2_oihw, w2_packed, Cout, C, 1, 1, C, st);
+}
+
+int sbgm_ln_linear_tiles(int M, int C, int Cout, int* tiles, int cap) {
+    if (M < 1 || C < 16 || C % 16 || Cout < 16 || Cout % 16 || !tiles) return 0;
+    static const float present = 0.f;
+    const ConvImages im{{&present, nullptr, nullptr, nullptr}};
+    const std::vector<ConvTile> c = sbgm_conv_candidates(ConvGeom{1, 1, 1, 0}, ln_linear_conv(M, C, Cout, LN_EPS), im, false);
+    for (int i = 0; i < (int)c.size() && i < cap; ++i) c[i].to_ints(tiles + 6 * i);
+    return (int)c.size();
+}
+
+int sbgm_ln_linear_fwd(const float* x, const float* w2_packed, const float* h, const float* res, int act, float eps, float* out, int M, int C,
+                       int Cout, const int* tile, void* stream) {
+    SBGM_CHECK(x && w2_packed && h && out, "ln_linear_fwd: null tensor");
+    SBGM_CHECK(M >= 1 && C >= 16 && C % 16 == 0 && Cout >= 16 && Cout % 16 == 0 && eps > 0.f,
+               "ln_linear_fwd: needs C %% 16 == 0, Cout %% 16 == 0 and eps > 0 (M=%d C=%d Cout=%d)", M, C, Cout);
+    SBGM_CHECK(act == SBGM_NONE || act == SBGM_RELU || act == SBGM_GELU, "ln_linear_fwd: act must be none, relu or gelu");
+    const ConvGeom lin{1, 1, 1, 0};
+    ConvParams p = ln_linear_conv(M, C, Cout, eps);
+    p.x = x; p.out = out; p.bias = h; p.res = res; p.act = act;
+    const ConvImages im{{w2_packed, nullptr, nullptr, nullptr}};
+    const bool given = tile && (tile[0] | tile[1] | tile[2] | tile[3] | tile[4] | tile[5]) != 0;      // all zeros: the static tile
+    const ConvTile ct = given ? ConvTile::from_ints(tile) : sbgm_static_tile(lin, p, im);
+    return sbgm_launch_tile(lin, p, im, ct, nullptr, (hipStream_t)stream);
+}
+
+int sbgm_time_row_layout(const int* channels, int n, int* offsets) {
+    if (!channels || !offsets || n < 1 || n > 16) return -1;
+    offsets[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        if (channels[i] < 4 || channels[i] % 4) return -1;
+        offsets[i + 1] = offsets[i] + channels[i];
+    }
+    return offsets[n];
+}
+int64_t sbgm_time_row_index(int64_t advances, int64_t num_steps) {
+    unsigned long long s = 0;
+    for (int64_t k = 0; k < advances; ++k) s = sampler_next_step(s, (unsigned long long)num_steps);
+    return (int64_t)s;
+}
+
+int sbgm_event_create(void** ev) { hipEvent_t e; SBGM_HIP(hipEventCreate(&e)); *ev = e; return 0; }
+int sbgm_event_record(void* ev, void* stream) { SBGM_HIP(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream)); return 0; }
+int sbgm_event_elapsed_ms(void* start, void* stop, float* ms) {
+    SBGM_HIP(hipEventSynchronize((hipEvent_t)stop));
+    SBGM_HIP(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
+    return 0;
+}
+int sbgm_event_destroy(void* ev) { SBGM_HIP(hipEventDestroy((hipEvent_t)ev)); return 0; }
 
 }  // extern "C"

@@ -24,7 +24,7 @@ import sbgm_danra_amd as S  # noqa: E402
 from sbgm_danra_amd import _native as N  # noqa: E402
 from sbgm_danra_amd import score_sampling as SS  # noqa: E402
 from sbgm_danra_amd.tiling import FullDomainTiler  # noqa: E402
-from util_dpmpp_runs import run_specs  # noqa: E402
+from util_step_runs import run_specs  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIG = 25.0

@@ -2,7 +2,7 @@
 of `conv` plus a 9-point gather.  The weight composition against an fp64 einsum, the block alone against the fp64 CPU chain on every
 kernel family the autotuner offers for it (random, one-hot and zero inputs), the whole network against the projection path
 (SBGM_NO_FINAL_COMPOSE=1), graph replay, and weight changes reaching the composed images.  The step samplers (EM, PC, EDM Heun) and
-the profiled forward take the composed route; the plain forward and RK45 keep the projection path (engine.hip, set_routes)."""
+the profiled forward take the composed route; the plain forward and RK45 keep the projection path (engine.h, set_routes)."""
 import ctypes
 import os
 import subprocess

@@ -2,7 +2,7 @@
 the 25 positions of the composed 5x5 stencil on the LOW-resolution map and a gather through the bilinear x2, with nine border-class
 weight sets.  The pack against the fp64 sums, the block alone against the fp64 CPU chain (random, one-hot and zero inputs, plain and
 with the normalisation applied on load), and the whole network against the composed 3x3 route (SBGM_NO_FINAL_LOWRES=1).  The step
-samplers and the profiled forward take this route; the plain forward and RK45 keep the projection path (engine.hip, set_routes)."""
+samplers and the profiled forward take this route; the plain forward and RK45 keep the projection path (engine.h, set_routes)."""
 import os
 import subprocess
 import sys
