@@ -225,6 +225,25 @@ int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, d
 int sbgm_sampler_run_dpmpp(sbgm_model* m, const sbgm_sampler_args* a, float sigma_min, float sigma_max, float rho, float eta, float s_noise,
                            const float* known, const float* known_mask, int domain_h, int ramp_len, void* stream);
 
+/* Row-keyed, temporally correlated in-kernel noise for every sampler entry point above.  A noise plan gives sample b of
+ * the runs to come a noise row r_b = rows[b] (device int32 [B], used in place: new contents at the same address are read by a cached step
+ * graph's replays, as the conditions are) and makes each of its draws a moving average over `lags` = K white rows `stride` = s apart.
+ * With P4 = H W / 4 quads per sample, the draw with stream offset `off` at quad q of sample b is
+ *     xi_k = the four Philox normals of (seed, off, counter (r_b - k s) P4 + q),  k = 0 .. K-1     (64-bit unsigned counter arithmetic)
+ *     z    = w_0 xi_0 ;  z = z + w_k xi_k  for k = 1 .. K-1 in ascending k,  every product and every sum rounded to fp32 on its own,
+ * where xi_k is what sbgm_randn_scaled with (seed, off) writes at flat elements [(r_b - k s) H W, (r_b - k s + 1) H W).  So the noise of
+ * a sample depends on its row, not on its place in the batch or on its batch-mates; rows 0 .. B-1 with K = 1, w = {1} draw bit for bit
+ * what a run without a plan draws; with sum_k w_k^2 = 1 every draw of a sample is N(0,1), independent across pixels and steps, and
+ * samples whose rows are j s apart are correlated with acf[j] = sum_k w_k w_{k+j}.
+ *   weights: host fp32 [lags], copied into the handle (1 <= lags <= 32, stride >= 1).  The caller keeps every r_b >= (K-1) s; the counter
+ *            is never an address, so a smaller row yields other counters, not an out-of-bounds access.
+ *   The plan is held by the handle and used by sbgm_sampler_run, its _edm, _held, _joint and _dpmpp variants and the start draw of
+ *   sbgm_sampler_run_ode until it is cleared with rows = NULL (stride, weights and lags <= 1 are then ignored; NULL rows with lags > 1
+ *   are an error).  It serves the start, EM, PC, EDM Heun's churn and held pixels (the same mixed draw 0), and 2M SDE, each with and
+ *   without known / known_mask and guidance; the captured step's key holds the rows pointer, stride, lags and the weights.
+ * A run refuses a plan together with a->noise, a->tile_origins (tiled and joint runs) or a start state x0. */
+int sbgm_sampler_set_noise_rows(sbgm_model* m, const int32_t* rows, int stride, const float* weights, int lags);
+
 /* Conv autotuning: time the tile / split-K candidates of every convolution of the (B,H,W) plan once and keep the
  * fastest.  Synchronises the stream.  Optional; without it a static heuristic is used. */
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream);
@@ -731,6 +750,10 @@ int sbgm_langevin_step(float* x, const float* score, const float* z, float snr_n
                        uint64_t seed, uint64_t draw_index, int B, int64_t per_sample, void* stream);
 int sbgm_cfg_combine(float* out, const float* s_cond, const float* s_uncond, float scale, int64_t n, void* stream);
 int sbgm_randn_scaled(float* x, float scale, uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
+/* sbgm_randn_scaled under a noise plan (see sbgm_sampler_set_noise_rows): x [B][per_sample] = scale * z, sample b drawn as noise row
+ * rows[b] and mixed over `lags` rows `stride` apart with `weights` (host fp32 [lags]).  per_sample % 4 == 0, 1 <= lags <= 32. */
+int sbgm_randn_rows(float* x, float scale, uint64_t seed, uint64_t draw_index, const int32_t* rows, int B, int64_t per_sample, int stride,
+                    const float* weights, int lags, void* stream);
 int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
 int sbgm_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, float sigma_hat, float sigma_next, int64_t n,
                    void* stream);

@@ -33,7 +33,7 @@ const char* sbgm_get_error();
 extern "C" {
 
 const char* sbgm_last_error(void) { return sbgm_get_error(); }
-int sbgm_abi_version(void) { return 14; }
+int sbgm_abi_version(void) { return 15; }
 int sbgm_model_config_size(void) { return (int)sizeof(sbgm_model_config); }
 
 int sbgm_pack_input(const float* const* srcs, const int* src_channels, int n_src, float* dst_nhwc, int B, int H, int W,
@@ -493,6 +493,16 @@ int sbgm_cfg_combine(float* out, const float* s_cond, const float* s_uncond, flo
 }
 int sbgm_randn_scaled(float* x, float scale, uint64_t seed, uint64_t draw_index, int64_t n, void* stream) {
     return sbgm_launch_init_noise(x, scale, nullptr, seed, nullptr, draw_index, (size_t)n, ST);
+}
+int sbgm_randn_rows(float* x, float scale, uint64_t seed, uint64_t draw_index, const int32_t* rows, int B, int64_t per_sample, int stride,
+                    const float* weights, int lags, void* stream) {
+    SBGM_CHECK(x && rows && weights, "randn_rows: x, rows and weights are required");
+    SBGM_CHECK(B >= 1 && per_sample >= 4 && per_sample % 4 == 0, "randn_rows: need B >= 1 and per_sample a positive multiple of 4 (B=%d, "
+               "per_sample=%lld)", B, (long long)per_sample);
+    SBGM_CHECK(lags >= 1 && lags <= SBGM_NOISE_MAX_LAGS && stride >= 1, "randn_rows: need 1 <= lags <= %d and stride >= 1 (lags=%d, stride=%d)",
+               SBGM_NOISE_MAX_LAGS, lags, stride);
+    return sbgm_launch_init_noise(x, scale, nullptr, seed, nullptr, draw_index, (size_t)B * (size_t)per_sample, ST,
+                                  sbgm_noise_rows_map(rows, stride, lags, weights, (size_t)per_sample));
 }
 int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, uint64_t draw_index, int64_t n, void* stream) {
     const EdmStep sc{0.f, 0.f, 0.f, 0.f, 0.f, churn_coef};

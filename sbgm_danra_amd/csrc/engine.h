@@ -191,6 +191,9 @@ struct StepGraphKey {
     const void *known, *known_mask, *levels;   // constrained runs (null otherwise): a held and an unheld step never share a graph
     int joint, domain_h, ramp_len;             // joint tiled runs (0 otherwise): a joint and a non-joint step never share a graph
     const void *rows, *tbrun;                  // EM / PC runs that keep their time rows (null otherwise)
+    const void* noise_rows;                    // runs with a noise plan (null otherwise): the launches hold the plan by value, so a run
+    int noise_stride, noise_lags;              // with a plan and one without never share a graph, nor do two plans that differ in more
+    float noise_w[SBGM_NOISE_MAX_LAGS];        // than the contents of the rows table
     size_t ws_bytes;
     float cfg, cfg_corr, snr_nn;
     unsigned long long plan_gen;
@@ -322,6 +325,9 @@ struct sbgm_model {
     char* ws = nullptr;
     size_t ws_bytes = 0, ws_used = 0;
     SamplerStore store;
+    // The noise plan of the sampler runs to come (sbgm_sampler_set_noise_rows; kernels.h: NoiseMap): held until cleared, read by every
+    // sampler entry point.  rows == null: none.
+    struct NoiseRows { const int* rows = nullptr; int stride = 1, lags = 1; float w[SBGM_NOISE_MAX_LAGS] = {}; } noise_rows;
     ConvTileTable tuned;
     ConvTile last_tile{};                   // tile of the most recent conv() (tells the caller whether GroupNorm statistics were fused)
     bool tuning = false;
@@ -397,6 +403,6 @@ struct sbgm_model {
     // sampler_run.hip
     struct EdmArgs; struct HeldArgs; struct JointArgs; struct DpmArgs; struct OdeArgs;
     int sampler(const sbgm_sampler_args& a, hipStream_t st, const EdmArgs* edm = nullptr, const HeldArgs* held = nullptr,
-                const JointArgs* joint = nullptr, const DpmArgs* dpm = nullptr);
-    int sampler_ode(const sbgm_sampler_args& a, hipStream_t st, const OdeArgs& o);
+                const JointArgs* joint = nullptr, const DpmArgs* dpm = nullptr, const NoiseRows* plan = nullptr);
+    int sampler_ode(const sbgm_sampler_args& a, hipStream_t st, const OdeArgs& o, const NoiseRows* plan = nullptr);
 };

@@ -276,11 +276,26 @@ struct SamplerState {      // device-resident, lets one captured graph serve eve
 // the step after step s of a run of ns steps: the last step stays where it is
 __host__ __device__ inline unsigned long long sampler_next_step(unsigned long long s, unsigned long long ns) { return s + 1 < ns ? s + 1 : s; }
 // optional map from tile-local quads to domain-global Philox counters (null origins = plain element order)
+// ... and the optional noise plan ("row-keyed noise"): sample b draws as noise row r_b = rows[b] instead of as its
+// position in the batch, and its draw is the moving average z = sum_k w[k] xi(r_b - k stride) over `lags` white rows, every product and
+// sum rounded to fp32 on its own.  rows == null (the default) is the plain counter.  A plan and origins exclude each other.
+constexpr int SBGM_NOISE_MAX_LAGS = 32;
 struct NoiseMap {
     const int* origins;   // device [B][2] = (y0, x0) of each tile in the domain, x0 % 4 == 0
     int tile_h, tile_w4;  // tile rows, tile width / 4
     int dom_w4;           // ceil(domain width / 4)
+    const int* rows;      // device [B]: the noise row of each sample, every one >= (lags - 1) * stride
+    int stride, lags;     // rows between two lags (>= 1), number of lags (1 .. SBGM_NOISE_MAX_LAGS)
+    unsigned long long per4;            // quads per sample, H W / 4
+    float w[SBGM_NOISE_MAX_LAGS];       // the weights, by value
 };
+// nm with the plan (rows, stride, lags, weights) over samples of per_sample elements
+inline NoiseMap sbgm_noise_rows_map(const int* rows, int stride, int lags, const float* w, size_t per_sample) {
+    NoiseMap nm{};
+    nm.rows = rows; nm.stride = stride; nm.lags = lags; nm.per4 = per_sample / 4;
+    for (int k = 0; k < lags && k < SBGM_NOISE_MAX_LAGS; ++k) nm.w[k] = w[k];
+    return nm;
+}
 // Joint tiled sampling: the B samples are ALL T tiles of one domain, and every update kernel reads the score through the
 // partition-of-unity blend of the tiles' scores (tile_blend.h).  origins == null (the default) is the kernel without the blend.
 struct JointMap {

@@ -5,7 +5,8 @@
 //
 // Noise: when `z` is null the kernels draw N(0,1) themselves (Philox4x32-10 counter RNG + Box-Muller, keyed by
 // (seed, running offset, element index)), so the sampler loop never round-trips noise through HBM; when `z`
-// is given (parity mode) the host-generated draw is used verbatim.
+// is given (parity mode) the host-generated draw is used verbatim.  With a noise plan (kernels.h: NoiseMap) the counter
+// is keyed by the sample's noise row instead of its place in the batch and the draw is a moving average over the preceding rows.
 // Joint tiled sampling: the JOINT instantiations of the five update kernels read the score through the partition-of-unity
 // blend of all tiles' scores (tile_blend.h), so the T tiles of a domain are one diffusion and copies of a domain pixel stay bit-equal.
 // All per-step scalars come from a device-resident table indexed by a device-side step counter, so one captured
@@ -28,6 +29,39 @@ __device__ __forceinline__ unsigned long long noise_index(const NoiseMap& m, siz
     return ((unsigned long long)(m.origins[2 * b] + y)) * m.dom_w4 + (unsigned long long)(m.origins[2 * b + 1] >> 2) + x4;
 }
 
+// z + w x (lag 0: w x, the product itself and not 0 + product, which would lose the sign of a zero) with the product and the sum rounded
+// separately: contraction is switched off for this body (HIP's __fmul_rn / __fadd_rn are plain operators and would be fused)
+__device__ __forceinline__ float mix_lag(float z, float w, float x, bool first) {
+#pragma clang fp contract(off)
+    const float p = w * x;
+    return first ? p : z + p;
+}
+// The draw of a noise plan at quad i (kernels.h: NoiseMap): with r the row of the quad's sample and q its place within the sample,
+// z = w[0] xi_0, then z = z + w[k] xi_k in ascending k, xi_k = the white draw at counter (r - k stride) per4 + q in 64-bit unsigned
+// arithmetic.  Each product and sum is an fp32 operation of its own (no contraction), so a float32 loop over the white draws gives the
+// same bits.  The trip count is uniform over the launch and the loop stays a loop: one Philox state is live at a time.
+__device__ __forceinline__ f32x4 philox_rows_normal4(unsigned long long seed, unsigned long long off, const NoiseMap& m, size_t i) {
+    const unsigned long long b = i / m.per4, q = i - b * m.per4;
+    unsigned long long c = (unsigned long long)m.rows[b] * m.per4 + q;
+    const unsigned long long back = (unsigned long long)m.stride * m.per4;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int k = 0; k < m.lags; ++k, c -= back) {
+        const f32x4 xk = philox_normal4(seed, off, c);
+        const float wk = m.w[k];
+        for (int l = 0; l < 4; ++l) acc[l] = mix_lag(acc[l], wk, xk[l], k == 0);
+    }
+    return acc;
+}
+
+// The N(0,1) quad an update kernel uses at quad i: the injected draw, the plan's mixed draw, or the plain / domain-keyed Philox draw
+__device__ __forceinline__ f32x4 noise4(const float* __restrict__ z, unsigned long long seed, unsigned long long off, const NoiseMap& m,
+                                        size_t i) {
+    if (z) return reinterpret_cast<const f32x4*>(z)[i];
+    if (m.rows) return philox_rows_normal4(seed, off, m, i);
+    return philox_normal4(seed, off, noise_index(m, i));
+}
+
 // Constrained sampling: hold(v, target, m) is a select with a soft edge.  m <= 0 keeps v and m >= 1 takes target, both
 // bit-exactly (the other operand is never combined arithmetically, so `known` may hold anything where the mask is 0); in between
 // (1-m) v + m target.  The mask is clamped to [0,1] here; a NaN mask counts as 0.
@@ -42,10 +76,8 @@ __device__ __forceinline__ f32x4 hold4(f32x4 v, f32x4 target, f32x4 m) {
 }
 __device__ __forceinline__ f32x4 load_mask(const Hold& h, size_t i) { return clamp_mask(reinterpret_cast<const f32x4*>(h.mask)[i]); }
 __device__ __forceinline__ f32x4 load_known(const Hold& h, size_t i) { return reinterpret_cast<const f32x4*>(h.known)[i]; }
-// draw 0 of the run (the initial state's noise) at quad i: the injected one, or recomputed from (seed, offset 0, counter)
-__device__ __forceinline__ f32x4 draw0(const Hold& h, unsigned long long seed, size_t i) {
-    return h.z0 ? reinterpret_cast<const f32x4*>(h.z0)[i] : philox_normal4(seed, 0ull, noise_index(h.nm, i));
-}
+// draw 0 of the run (the initial state's noise) at quad i: the injected one, or recomputed from (seed, offset 0, counter or plan)
+__device__ __forceinline__ f32x4 draw0(const Hold& h, unsigned long long seed, size_t i) { return noise4(h.z0, seed, 0ull, h.nm, i); }
 
 // the score an update kernel uses at quad i: as stored, or (JOINT) the blend of all tiles' scores at the quad's domain position
 template <bool JOINT>
@@ -90,7 +122,7 @@ __global__ __launch_bounds__(256) void init_noise_kernel(float* __restrict__ x, 
     const unsigned long long off = state ? state->rng_offset : off_val;
     if (state) seed = state->seed;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
+        const f32x4 n = noise4(z, seed, off, nm, i);
         f32x4 v = n * scale;
         if (HELD) {
             const f32x4 m = load_mask(hold, i), kn = load_known(hold, i);
@@ -117,7 +149,7 @@ __global__ __launch_bounds__(256) void em_update_kernel(float* __restrict__ x, f
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
         const f32x4 sv = load_score<JOINT>(score, i, jm);
-        const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
+        const f32x4 n = noise4(z, seed, off, nm, i);
         const f32x4 mean = xv + (sc.g2 * sv) * sc.dt;   // association of score_sampling.py:124/:224
         if (HELD) {
             const f32x4 m = load_mask(hold, i), kn = load_known(hold, i);
@@ -201,7 +233,7 @@ __global__ __launch_bounds__(256) void langevin_kernel(float* __restrict__ x, co
         }
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
         const f32x4 sv = load_score<JOINT>(score, i, jm);
-        const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
+        const f32x4 n = noise4(z, seed, off, nm, i);
         const f32x4 v = xv + eps * sv + nz * n;
         reinterpret_cast<f32x4*>(x)[i] = HELD ? hold4(v, load_known(hold, i) + s_cur * n, load_mask(hold, i)) : v;
     }
@@ -227,7 +259,7 @@ __global__ __launch_bounds__(256) void edm_churn_kernel(float* __restrict__ x, f
     const unsigned long long off = state ? state->rng_offset : off_val;
     if (state) seed = state->seed;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const f32x4 n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
+        const f32x4 n = noise4(z, seed, off, nm, i);
         const f32x4 v = reinterpret_cast<const f32x4*>(x)[i] + c * n;
         reinterpret_cast<f32x4*>(x)[i] = v;
         if (x_copy) reinterpret_cast<f32x4*>(x_copy)[i] = v;
@@ -315,7 +347,7 @@ __global__ __launch_bounds__(256) void dpmpp_2m_kernel(float* __restrict__ x, fl
         if (second) v = v + sc.c_1 * reinterpret_cast<const f32x4*>(hist)[i];
         f32x4 n = {0.f, 0.f, 0.f, 0.f};
         if (stochastic) {
-            n = z ? reinterpret_cast<const f32x4*>(z)[i] : philox_normal4(seed, off, noise_index(nm, i));
+            n = noise4(z, seed, off, nm, i);
             v = v + sc.c_z * n;
         }
         if (HELD) {
@@ -366,6 +398,16 @@ inline int check_joint(const JointMap& jm, size_t n, const char* who) {
                who, jm.T, jm.tile_h, jm.tile_w, jm.R, n);
     return 0;
 }
+// a noise plan must describe exactly the launch's n elements (the kernel reads rows[quad / per4]) and is not composed with a tile map;
+// checked on the map a kernel reads: `nm` for its own draw, `hold.nm` where it recomputes the run's draw 0 (edm_euler, edm_heun, dpmpp_2m)
+inline int check_noise(const NoiseMap& nm, size_t n, const char* who) {
+    if (!nm.rows) return 0;
+    SBGM_CHECK(nm.origins == nullptr, "%s: noise rows and tile origins exclude each other", who);
+    SBGM_CHECK(nm.lags >= 1 && nm.lags <= SBGM_NOISE_MAX_LAGS && nm.stride >= 1, "%s: noise rows need 1 <= lags <= %d and stride >= 1 "
+               "(lags=%d, stride=%d)", who, SBGM_NOISE_MAX_LAGS, nm.lags, nm.stride);
+    SBGM_CHECK(nm.per4 >= 1 && (n / 4) % nm.per4 == 0, "%s: noise rows over samples of %llu quads do not divide %zu elements", who, nm.per4, n);
+    return 0;
+}
 inline int check_hold(const Hold& h, const char* who) {
     SBGM_CHECK((h.known == nullptr) == (h.mask == nullptr), "%s: known and known_mask must be given together", who);
     return 0;
@@ -398,7 +440,7 @@ int sbgm_launch_fill_t(float* t, float value, int B, hipStream_t st) {
 int sbgm_launch_init_noise(float* x, float scale, const float* z, unsigned long long seed, SamplerState* state,
                            unsigned long long draw_index, size_t n, hipStream_t st, NoiseMap nm, const Hold& hold) {
     SBGM_CHECK(n % 4 == 0, "init_noise: element count must be a multiple of 4");
-    if (check_hold(hold, "init_noise")) return 1;
+    if (check_hold(hold, "init_noise") || check_noise(nm, n, "init_noise")) return 1;
     SBGM_LAUNCH_HELD(init_noise_kernel, hold.known != nullptr, dim3(stream_blocks(n / 4)), st, x, scale, z, seed, state, draw_index,
                      n / 4, nm, hold);
     SBGM_LAUNCH_CHECK();
@@ -420,7 +462,7 @@ int sbgm_launch_em_update(float* x, float* x_mean, const float* score, const flo
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "em_update: need a device table or explicit scalars");
     SBGM_CHECK(!(hold.known && state && !hold.levels), "em_update: a held run with a device state needs the hold-level table");
     SBGM_CHECK(!tr.rows || (state && check_time_rows(tr) == 0), "em_update: time rows need a device state and a valid layout");
-    if (check_hold(hold, "em_update") || check_joint(jm, n, "em_update")) return 1;
+    if (check_hold(hold, "em_update") || check_noise(nm, n, "em_update") || check_joint(jm, n, "em_update")) return 1;
     const StepScalars v = sc_val ? *sc_val : StepScalars{};
     SBGM_LAUNCH_STEP(em_update_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x, x_mean, score, z,
                      table, state, v, draw_index, seed, n / 4, nm, hold, jm);
@@ -437,7 +479,8 @@ int sbgm_launch_langevin(float* x, const float* score, const float* z, float snr
                          size_t per_sample, hipStream_t st, NoiseMap nm, const Hold& hold, const JointMap& jm) {
     SBGM_CHECK(per_sample % 4 == 0, "langevin: per-sample element count must be a multiple of 4");
     SBGM_CHECK(!(hold.known && state && !hold.levels), "langevin: a held run with a device state needs the hold-level table");
-    if (check_hold(hold, "langevin") || check_joint(jm, (size_t)B * per_sample, "langevin")) return 1;
+    if (check_hold(hold, "langevin") || check_noise(nm, (size_t)B * per_sample, "langevin") ||
+        check_joint(jm, (size_t)B * per_sample, "langevin")) return 1;
     { if (sbgm_zero_async(sumsq_ws, sizeof(double) * B, st)) return 1; }
     const int bx = (int)std::min<size_t>((per_sample / 4 + 255) / 256, B >= 64 ? 4 : 16);
     hipLaunchKernelGGL(sumsq_kernel, dim3(bx, B), dim3(256), 0, st, score, sumsq_ws, per_sample / 4);
@@ -458,6 +501,7 @@ int sbgm_launch_edm_churn(float* x, float* x_copy, const float* z, const EdmStep
                           NoiseMap nm) {
     SBGM_CHECK(n % 4 == 0, "edm_churn: element count must be a multiple of 4");
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_churn: need a device table or explicit scalars");
+    if (check_noise(nm, n, "edm_churn")) return 1;
     const EdmStep v = sc_val ? *sc_val : EdmStep{};
     hipLaunchKernelGGL(edm_churn_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, st, x, x_copy, z, table, state, v, draw_index,
                        seed, n / 4, nm);
@@ -469,7 +513,7 @@ int sbgm_launch_edm_euler(const float* x_hat, const float* score, float* d, floa
                           const SamplerState* state, const EdmStep* sc_val, float* t_dev, int t_entries, size_t n, hipStream_t st,
                           const Hold& hold, const JointMap& jm) {
     SBGM_CHECK(n % 4 == 0, "edm_euler: element count must be a multiple of 4");
-    if (check_hold(hold, "edm_euler") || check_joint(jm, n, "edm_euler")) return 1;
+    if (check_hold(hold, "edm_euler") || check_noise(hold.nm, n, "edm_euler") || check_joint(jm, n, "edm_euler")) return 1;
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_euler: need a device table or explicit scalars");
     const EdmStep v = sc_val ? *sc_val : EdmStep{};
     SBGM_LAUNCH_STEP(edm_euler_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x_hat, score, d,
@@ -482,7 +526,7 @@ int sbgm_launch_edm_heun(float* x, float* x_copy, const float* d, const float* s
                          const EdmStep* sc_val, float* t_dev, int t_entries, int n_steps, size_t n, hipStream_t st, const Hold& hold,
                          const JointMap& jm) {
     SBGM_CHECK(n % 4 == 0, "edm_heun: element count must be a multiple of 4");
-    if (check_hold(hold, "edm_heun") || check_joint(jm, n, "edm_heun")) return 1;
+    if (check_hold(hold, "edm_heun") || check_noise(hold.nm, n, "edm_heun") || check_joint(jm, n, "edm_heun")) return 1;
     SBGM_CHECK(state != nullptr || sc_val != nullptr, "edm_heun: need a device table or explicit scalars");
     const EdmStep v = sc_val ? *sc_val : EdmStep{};
     SBGM_LAUNCH_STEP(edm_heun_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x, x_copy, d, score,
@@ -505,7 +549,8 @@ int sbgm_launch_dpmpp_2m(float* x, float* x_copy, const float* score, float* his
     SBGM_CHECK(!(z && !stochastic), "dpmpp_2m: a deterministic step takes no draw");
     SBGM_CHECK(!(hold.known && state && !hold.levels), "dpmpp_2m: a held run with a device state needs the hold-level table");
     SBGM_CHECK(!tr.rows || (state && check_time_rows(tr) == 0), "dpmpp_2m: time rows need a device state and a valid layout");
-    if (check_hold(hold, "dpmpp_2m") || check_joint(jm, n, "dpmpp_2m")) return 1;
+    if (check_hold(hold, "dpmpp_2m") || check_noise(nm, n, "dpmpp_2m") || check_noise(hold.nm, n, "dpmpp_2m") ||
+        check_joint(jm, n, "dpmpp_2m")) return 1;
     const DpmStep v = sc_val ? *sc_val : DpmStep{};
     SBGM_LAUNCH_STEP(dpmpp_2m_kernel, hold.known != nullptr, jm.origins != nullptr, dim3(stream_blocks(n / 4)), st, x, x_copy, score,
                      hist, z, table, state, v, draw_index, seed, stochastic, t_dev, t_dev ? t_entries : 0, n / 4, nm, hold, jm);

@@ -350,6 +350,7 @@ struct SamplerRun {
     size_t saved_ws = 0;             // the model's ws_bytes while the run holds its slabs (0: not held)
     SamplerConds conds{a, st};       // guidance: the unconditional half is built once per run
     NoiseMap nm{};
+    const sbgm_model::NoiseRows* plan = nullptr;   // set by the driver before begin(): the run's noise plan (checked by check_plan)
     float* tbrun = nullptr;          // set by an EM / PC driver before begin(): the run keeps its time biases
     ~SamplerRun() { if (saved_ws) m->ws_bytes = saved_ws; m->set_routes(CALL_PLAIN); }
     size_t sc_bytes() const { return a.kind != SBGM_SAMPLER_RK45 ? m->skip_sc_bytes(BE, H, W) : 0; }
@@ -413,6 +414,10 @@ struct SamplerRun {
             SBGM_CHECK(W % 4 == 0 && a.domain_w >= W, "%s: tiled noise needs W %% 4 == 0 and domain_w >= W (W=%d, domain_w=%d)", who, W, a.domain_w);
             nm = NoiseMap{a.tile_origins, H, W / 4, (a.domain_w + 3) / 4};
         }
+        if (plan && draws_noise) {
+            SBGM_CHECK(per % 4 == 0, "%s: noise rows need H * W %% 4 == 0 (H=%d, W=%d)", who, H, W);
+            nm = sbgm_noise_rows_map(plan->rows, plan->stride, plan->lags, plan->w, per);
+        }
         saved_ws = m->ws_bytes;
         m->ws_bytes -= keep();       // forward() must not touch the run's slabs
         return 0;
@@ -439,8 +444,21 @@ struct SamplerRun {
     }
 };
 
+// A noise plan keys and mixes the in-kernel draws of independent samples: it is refused, not composed, where the run's noise is decided
+// otherwise (injected draws, domain-keyed tiles, a joint run)
+static int check_plan(const sbgm_model::NoiseRows* p, const sbgm_sampler_args& a, bool joint, const char* who) {
+    if (!p) return 0;
+    SBGM_CHECK(p->lags >= 1 && p->lags <= SBGM_NOISE_MAX_LAGS, "%s: noise rows need 1 <= lags <= %d, got %d", who, SBGM_NOISE_MAX_LAGS, p->lags);
+    SBGM_CHECK(p->stride >= 1, "%s: noise row stride %d must be >= 1", who, p->stride);
+    SBGM_CHECK(p->rows != nullptr, "%s: a noise plan needs its rows table", who);
+    SBGM_CHECK(a.noise == nullptr, "%s: noise rows key the in-kernel noise; they cannot be combined with injected noise", who);
+    SBGM_CHECK(a.tile_origins == nullptr && !joint, "%s: noise rows and tile_origins (tiled or joint runs) exclude each other", who);
+    return 0;
+}
+
 int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm, const HeldArgs* held,
-                        const JointArgs* joint, const DpmArgs* dpm) {
+                        const JointArgs* joint, const DpmArgs* dpm, const NoiseRows* plan) {
+    if (check_plan(plan, a, joint != nullptr, "sampler")) return 1;
     SBGM_CHECK(!held || (held->known && held->mask), "sampler: a constrained run needs both known and known_mask");
     if (joint) {
         SBGM_CHECK(a.tile_origins != nullptr, "sampler: a joint run needs tile_origins (its samples are the tiles of one domain)");
@@ -469,6 +487,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
     SBGM_CHECK(a.num_steps >= 2, "sampler: num_steps=%d must be >= 2 (step size = t0 - t1)", a.num_steps);
     SBGM_CHECK(a.out != nullptr, "sampler: out is required");
     SamplerRun run{this, a, caller, "sampler", a.use_graph && !a.noise};
+    run.plan = plan;
     if (run.open()) return 1;
     const int B = a.B, N = a.num_steps, BE = run.BE;
     const size_t per = run.per, n = run.n;
@@ -554,6 +573,10 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         key.known = hold.known; key.known_mask = hold.mask; key.levels = hold.levels;
         if (joint) { key.joint = 1; key.domain_h = joint->domain_h; key.ramp_len = joint->ramp_len; }
         key.rows = trows.rows; key.tbrun = trows.tbrun;
+        if (plan) {                  // the rows' contents are read by every replay, like the conditions'; everything else is baked in
+            key.noise_rows = plan->rows; key.noise_stride = plan->stride; key.noise_lags = plan->lags;
+            std::copy(plan->w, plan->w + plan->lags, key.noise_w);
+        }
         rc = run.capture(key, [&] { return step(false, false); });
         for (int i = 0; i < N - tail && rc == 0; ++i)
             if (hipGraphLaunch(store.step_exec, st) != hipSuccess) { sbgm_set_error("hipGraphLaunch failed at step %d", i); rc = 2; }
@@ -573,7 +596,9 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
 // live in the device state block.  The host replays it on the caller's stream and stays at most one attempt ahead of the done word it
 // waits for, so the device does not idle on the poll; an attempt that runs after done finds every controller frozen and changes
 // nothing.  It sets no route (set_routes).
-int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, const OdeArgs& o) {
+int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, const OdeArgs& o, const NoiseRows* plan) {
+    if (check_plan(plan, a, false, "sampler_ode")) return 1;
+    SBGM_CHECK(!(plan && o.x0), "sampler_ode: noise rows key the start draw; they cannot be combined with a start state x0");
     SBGM_CHECK(a.kind == SBGM_SAMPLER_RK45, "sampler_ode: kind %d is not SBGM_SAMPLER_RK45", a.kind);
     SBGM_CHECK(a.out != nullptr && o.stats_i != nullptr, "sampler_ode: out and stats_i are required");
     SBGM_CHECK(!a.bn_train, "sampler_ode: serves eval-mode BatchNorm only (bn_train must be 0)");
@@ -582,6 +607,7 @@ int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, cons
                "different times in [0, 1]", o.t0, o.t1);
     SBGM_CHECK(!(a.tile_origins && !o.per_sample), "sampler_ode: tiles need one controller per sample (a shared step would couple them)");
     SamplerRun run{this, a, caller, "sampler_ode", a.use_graph != 0};
+    run.plan = plan;
     if (run.open()) return 1;
     const int B = a.B, G = o.per_sample ? B : 1;
     const size_t per = run.per, n = run.n;
@@ -699,10 +725,29 @@ static int run_steps(sbgm_model* m, const sbgm_sampler_args* a, const char* who,
     if (edm && edm_args_check(a, *edm)) return 1;
     const sbgm_model::HeldArgs h{known, known_mask};
     const sbgm_model::JointArgs j{domain_h, ramp_len};
-    return m->sampler(*a, (hipStream_t)stream, edm, known ? &h : nullptr, joint ? &j : nullptr, dpm);
+    return m->sampler(*a, (hipStream_t)stream, edm, known ? &h : nullptr, joint ? &j : nullptr, dpm, m->noise_rows.rows ? &m->noise_rows : nullptr);
 }
 
 extern "C" {
+
+// The noise plan of the handle's sampler runs: copied into the handle (the rows table itself stays the caller's), used by every entry
+// point below until cleared.
+int sbgm_sampler_set_noise_rows(sbgm_model* m, const int32_t* rows, int stride, const float* weights, int lags) {
+    SBGM_CHECK(m, "sampler_set_noise_rows: null model");
+    if (rows == nullptr) {
+        SBGM_CHECK(lags <= 1, "sampler_set_noise_rows: %d lags need a rows table (NULL rows clear the plan)", lags);
+        m->noise_rows = sbgm_model::NoiseRows{};
+        return 0;
+    }
+    SBGM_CHECK(lags >= 1 && lags <= SBGM_NOISE_MAX_LAGS, "sampler_set_noise_rows: lags=%d must be in 1..%d", lags, SBGM_NOISE_MAX_LAGS);
+    SBGM_CHECK(stride >= 1, "sampler_set_noise_rows: stride=%d must be >= 1", stride);
+    SBGM_CHECK(weights != nullptr, "sampler_set_noise_rows: weights are required");
+    sbgm_model::NoiseRows p;
+    p.rows = rows; p.stride = stride; p.lags = lags;
+    std::copy(weights, weights + lags, p.w);
+    m->noise_rows = p;
+    return 0;
+}
 
 int sbgm_sampler_run(sbgm_model* m, const sbgm_sampler_args* a, void* stream) {
     return run_steps(m, a, "sampler_run", nullptr, nullptr, false, nullptr, nullptr, false, 0, 0, stream);
@@ -750,7 +795,7 @@ int sbgm_sampler_run_ode(sbgm_model* m, const sbgm_sampler_args* a, double t0, d
                          int64_t max_steps, const float* x0, int64_t* stats_i, double* stats_d, void* stream) {
     SBGM_CHECK(a, "sampler_run_ode: null args");
     const sbgm_model::OdeArgs o{t0, t1, rtol, atol, per_sample != 0, (long long)max_steps, x0, stats_i, stats_d};
-    return m->sampler_ode(*a, (hipStream_t)stream, o);
+    return m->sampler_ode(*a, (hipStream_t)stream, o, m->noise_rows.rows ? &m->noise_rows : nullptr);
 }
 
 }  // extern "C"

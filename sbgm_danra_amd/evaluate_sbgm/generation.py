@@ -19,8 +19,8 @@ import torch
 
 from .. import parallel
 from .. import verification as V
-from ..score_sampling import (dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs, ode_sampler_kwargs, pc_sampler,
-                              rk45_sampler)
+from ..score_sampling import (NOISE_MAX_LAGS, dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs, fresh_seed,
+                              noise_weights_f32, ode_sampler_kwargs, pc_sampler, rk45_sampler, temporal_noise_acf, temporal_noise_weights)
 from ..score_unet import diffusion_coeff_fn, marginal_prob_std_fn
 from ..utils import extract_any, get_model_string
 from .evaluation import ensemble_products_config
@@ -51,16 +51,43 @@ def constraint_mask(cfg, hw):
 
 def series_config(cfg):
     """(members, max_days) of the optional evaluation.series section: `members` >= 1 samples per day (default 1), `max_days` >= 1
-    or null (default: the whole generation split)"""
+    or null (default: the whole generation split).  The section's other two keys, `seed` and `temporal_noise`, are read by
+    `series_noise_config`."""
     sec = cfg["evaluation"].get("series") or {}
-    if not hasattr(sec, "keys") or not set(sec.keys()) <= {"members", "max_days"}:
-        raise ValueError(f"evaluation.series takes the keys 'members' and 'max_days' only, got {sec!r}")
+    if not hasattr(sec, "keys") or not set(sec.keys()) <= {"members", "max_days", "seed", "temporal_noise"}:
+        raise ValueError(f"evaluation.series takes the keys 'members', 'max_days', 'seed' and 'temporal_noise' only, got {sec!r}")
     members, max_days = sec.get("members", 1), sec.get("max_days")
     if isinstance(members, bool) or not isinstance(members, int) or members < 1:
         raise ValueError(f"evaluation.series.members must be an integer >= 1, got {members!r}")
     if max_days is not None and (isinstance(max_days, bool) or not isinstance(max_days, int) or max_days < 1):
         raise ValueError(f"evaluation.series.max_days must be null or an integer >= 1, got {max_days!r}")
     return members, max_days
+
+
+def series_noise_config(cfg):
+    """(seed, weights) of the optional keys `seed` and `temporal_noise` of evaluation.series, (None, None) when neither is there.
+    `seed`: an integer in [0, 2^63), the one Philox seed of the whole series (None here: `generate_series` draws one).
+    `temporal_noise`: {rho, lags} (weights proportional to rho^k, `score_sampling.temporal_noise_weights`) or {weights: [...]} (1..32
+    numbers whose squares sum to 1 within 1e-5); without it the weights are [1.0], white noise keyed by day."""
+    sec = cfg["evaluation"].get("series") or {}
+    if not hasattr(sec, "keys") or ("seed" not in sec.keys() and "temporal_noise" not in sec.keys()):
+        return None, None
+    seed = sec.get("seed")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 63):
+        raise ValueError(f"evaluation.series.seed must be null or an integer in [0, 2^63), got {seed!r}")
+    tn = sec.get("temporal_noise")
+    if tn is None:
+        return seed, np.ones(1, dtype=np.float32)
+    if not hasattr(tn, "keys") or set(tn.keys()) not in ({"rho", "lags"}, {"weights"}):
+        raise ValueError(f"evaluation.series.temporal_noise takes either the keys 'rho' and 'lags' or the key 'weights', got {tn!r}")
+    if "weights" in tn.keys():
+        return seed, noise_weights_f32(tn["weights"], "evaluation.series.temporal_noise.weights")
+    rho, lags = tn["rho"], tn["lags"]
+    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not -1.0 < rho < 1.0:
+        raise ValueError(f"evaluation.series.temporal_noise.rho must be a number in (-1, 1), got {rho!r}")
+    if isinstance(lags, bool) or not isinstance(lags, int) or not 1 <= lags <= NOISE_MAX_LAGS:
+        raise ValueError(f"evaluation.series.temporal_noise.lags must be an integer in 1..{NOISE_MAX_LAGS}, got {lags!r}")
+    return seed, temporal_noise_weights(rho, lags)
 
 
 def maybe_inverse_transform(k, arr, back_transforms):
@@ -82,17 +109,18 @@ class SampleGenerator:
         self.constraint = constraint_mask(cfg, (hw[0], hw[0]))       # raises here, at start, on a sampler that cannot hold pixels
         self.products = ensemble_products_config(cfg)                # likewise on a malformed evaluation.ensemble_products section
 
-    def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond, known=None):
+    def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond, known=None, noise_plan=None):
         """the sampler output as [B,H,W] still on the device (what _run_sampler returns after .cpu()).  pc_sampler, as in the
         reference, unless cfg.sampler.sampler_type is "edm_heun_sampler": then n_timesteps is its Heun step count N (2N-1
         network evaluations; 18-64 is the intended range) and the optional `edm:` section sets the sigma ladder; "dpmpp_2m_sampler":
         n_timesteps is its step count N (N evaluations) and the optional `dpm:` section sets the ladder, eta and s_noise; or "rk45_sampler":
         the adaptive ODE solver, which ignores n_timesteps and reads its tolerances from the optional `ode:` section.
-        With a `constraint:` section, `known` (the batch's true field, model space) is held on the section's mask."""
-        held = {}
+        With a `constraint:` section, `known` (the batch's true field, model space) is held on the section's mask.
+        `noise_plan`: the seed and noise-row arguments of a series (`generate_series`), passed to the sampler as they are."""
+        held = dict(noise_plan or {})                      # the plan and the constraint compose: both go to the sampler
         if self.constraint is not None and known is not None:
-            held = {"known": known.reshape(-1, 1, *known.shape[-2:]).expand(batch_size, -1, -1, -1),
-                    "known_mask": torch.from_numpy(self.constraint)}
+            held.update(known=known.reshape(-1, 1, *known.shape[-2:]).expand(batch_size, -1, -1, -1),
+                        known_mask=torch.from_numpy(self.constraint))
         if self.cfg["sampler"].get("sampler_type") == "edm_heun_sampler":
             gen = edm_heun_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                                    batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,
@@ -106,7 +134,7 @@ class SampleGenerator:
         elif self.cfg["sampler"].get("sampler_type") == "rk45_sampler":
             gen = rk45_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                                batch_size=batch_size, device=self.device, img_size=self.cfg["highres"]["data_size"][0], y=y,
-                               cond_img=cond_img, lsm_cond=lsm_cond, topo_cond=topo_cond, **ode_sampler_kwargs(self.cfg))
+                               cond_img=cond_img, lsm_cond=lsm_cond, topo_cond=topo_cond, **ode_sampler_kwargs(self.cfg), **(noise_plan or {}))
         else:
             gen = pc_sampler(score_model=self.model, marginal_prob_std=marginal_prob_std_fn, diffusion_coeff=diffusion_coeff_fn,
                              batch_size=batch_size, num_steps=self.cfg["sampler"]["n_timesteps"], device=self.device,
@@ -197,8 +225,20 @@ class SampleGenerator:
         the sampler type, guidance and the `constraint:` section act as for `multiple`.  Writes gen_samples_series_n_<D>
         [D, M, H, W], eval_samples_series_n_<D> [D, H, W], lsm_samples_ / seasons_ as for `multiple`, and series_index_series_n_<D>
         with `members` and, when the batches carry them, `hr_points`.  The days keep the loader's order; several ranks would
-        interleave it, so they are refused."""
+        interleave it, so they are refused.
+
+        With `evaluation.series.seed` or `.temporal_noise` (`series_noise_config`) the noise is keyed by day instead of by batch: every
+        batch runs under the ONE series seed with `noise_rows = (d + K - 1) M + m` for member m of the absolute day d (counted over
+        the loader), `noise_row_stride = M` and the K weights, so the draws of member m on day d are the moving average of the white
+        draws of days d .. d-K+1 (lag-j autocorrelation `temporal_noise_acf(weights)[j]`, members mutually independent), each still
+        N(0,1).  A day's noise then does not depend on the loader's batch size or on `max_days`, and a series can be reproduced or
+        extended; `seed`, `weights` and `acf` go into the index file.  Rows are keyed by position in the crop: the coupling means
+        something for a fixed crop (`sample_w_cutouts: false`) on consecutive days.  `pc_sampler`'s Langevin step still uses the
+        batch-mean score norm, so its result, unlike its noise, depends on a day's batch-mates.  Without the two keys nothing changes."""
         members, max_days = series_config(self.cfg)
+        seed, weights = series_noise_config(self.cfg)
+        if weights is not None and seed is None:
+            seed = fresh_seed()                            # one seed for the whole series, written to the index file
         if parallel.world()[1] > 1:
             raise ValueError("gen_type 'series' runs on one rank: sharded days would interleave in the rank files and break the "
                              "day order")
@@ -212,7 +252,12 @@ class SampleGenerator:
                 keep = max_days - days
                 x, seasons, cond, lsm, topo, hp = [None if t is None else t[:keep] for t in (x, seasons, cond, lsm, topo, hp)]
             B = x.shape[0]
-            gen = self._sample_device(B * members, rep(seasons), rep(cond), rep(lsm), rep(topo), known=rep(x))
+            plan = None
+            if weights is not None:
+                first = (days + len(weights) - 1) * members
+                plan = {"seed": seed, "noise_rows": np.arange(first, first + B * members, dtype=np.int64), "noise_row_stride": members,
+                        "noise_weights": weights}
+            gen = self._sample_device(B * members, rep(seasons), rep(cond), rep(lsm), rep(topo), known=rep(x), noise_plan=plan)
             if self.cfg["evaluation"].get("transform_back", False):
                 x, gen, _ = self._apply_backtransforms(x, gen, None, seasons)
             gens.append(gen.reshape(B, members, *gen.shape[-2:]).cpu())
@@ -229,6 +274,8 @@ class SampleGenerator:
         self._save_npz({"gen_samples": gen, "eval_samples": cat(truths), "lsm_samples": cat(lsms), "seasons": cat(seas),
                         "constraint_mask": self.constraint}, suffix)
         index = {"members": np.int64(members)}
+        if weights is not None:
+            index.update(seed=np.int64(seed), weights=np.asarray(weights, dtype=np.float32), acf=temporal_noise_acf(weights))
         if len(points) == len(gens):
             index["hr_points"] = cat(points).numpy()
         np.savez_compressed(os.path.join(self.sample_path, f"series_index_{suffix}.npz"), **index)

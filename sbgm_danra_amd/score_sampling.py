@@ -24,6 +24,9 @@ denoised estimate is the second-order term), with `eta > 0` its SDE variant; `dp
 `rk45_sampler`, the adaptive probability-flow ODE solver on the device (Dormand-Prince 5(4) with scipy's RK45 step controller):
 conditioned, guided, tileable, in both directions of the flow, with one controller per batch or per sample; `rk45_host_solve` is
 its definition in numpy.
+
+Row-keyed, temporally correlated noise: the five samplers above take keyword-only `noise_rows` / `noise_weights` /
+`noise_row_stride` (see `pc_sampler`); `temporal_noise_weights`, `temporal_noise_acf` and `temporal_noise` are its host helpers.
 """
 from __future__ import annotations
 
@@ -46,6 +49,9 @@ error_tolerance = 1e-5            # reference score_sampling.py:238
 def _fresh_seed() -> int:
     """64-bit seed drawn from torch's default CPU generator, so torch.manual_seed() makes runs repeatable"""
     return int(torch.empty((), dtype=torch.int64).random_().item()) & 0x7FFFFFFFFFFFFFFF
+
+
+fresh_seed = _fresh_seed          # for callers outside this module that fix one seed for several sampler calls (generate_series)
 
 
 def _cfg_enabled(cfg) -> bool:
@@ -169,9 +175,128 @@ def _prep_joint(joint_tiles, tile_origins, noise, who):
     return domain_height, ramp_len
 
 
+NOISE_MAX_LAGS = 32               # include/sbgm_hip.h: sbgm_sampler_set_noise_rows
+
+
+def temporal_noise_weights(rho, lags):
+    """float32 [lags] weights w_k proportional to rho^k with sum w_k^2 = 1 (normalised in float64): the moving average that makes the
+    noise of consecutive rows correlated like a truncated AR(1) of coefficient `rho`.  -1 < rho < 1, 1 <= lags <= 32; rho = 0 or
+    lags = 1 gives [1.0], white noise."""
+    rho, lags = float(rho), int(lags)
+    if not -1.0 < rho < 1.0:
+        raise ValueError(f"temporal_noise_weights: rho={rho!r} must lie in (-1, 1)")
+    if not 1 <= lags <= NOISE_MAX_LAGS:
+        raise ValueError(f"temporal_noise_weights: lags={lags!r} must lie in 1..{NOISE_MAX_LAGS}")
+    w = rho ** np.arange(lags, dtype=np.float64)
+    return (w / np.sqrt((w * w).sum())).astype(np.float32)
+
+
+def temporal_noise_acf(weights):
+    """float64 [K]: acf[j] = sum_k w_k w_{k+j}, the lag-j autocorrelation of every draw under the weights (acf[0] = sum w^2)"""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    return np.array([float(np.dot(w[:w.size - j], w[j:])) for j in range(w.size)], dtype=np.float64)
+
+
+def noise_weights_f32(weights, who="noise_weights"):
+    """`weights` as the float32 [K] array a noise plan carries, checked: 1 <= K <= 32 and |sum w^2 - 1| <= 1e-5 in float64 on the float32
+    values.  `who` names the argument or config key in the ValueError.  The one definition for the samplers and the series config."""
+    try:
+        w64 = np.asarray([float(v) for v in np.asarray(weights).reshape(-1)], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who} must be a list of numbers, got {weights!r}") from None
+    if not 1 <= w64.size <= NOISE_MAX_LAGS:
+        raise ValueError(f"{who} holds {w64.size} lags, must be 1..{NOISE_MAX_LAGS}")
+    w = w64.astype(np.float32)
+    ss = float((w.astype(np.float64) ** 2).sum())
+    if not abs(ss - 1.0) <= 1e-5:
+        raise ValueError(f"{who} must have sum of squares 1 (every draw stays N(0,1)), got {ss!r}")
+    return w
+
+
+def _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, who, noise=None, tile_origins=None, joint_tiles=None):
+    """The noise plan of a run as (rows int64 numpy [B], stride, weights float32 numpy [K]), or None; every check needs the host only."""
+    if noise_rows is None:
+        if noise_weights is not None and [float(v) for v in np.asarray(noise_weights).reshape(-1)] != [1.0]:
+            raise ValueError(f"{who}: noise_weights needs noise_rows (the rows the weights mix)")
+        if int(noise_row_stride) != 1:
+            raise ValueError(f"{who}: noise_row_stride needs noise_rows")
+        return None
+    for other, name in ((noise, "noise"), (tile_origins, "tile_origins"), (joint_tiles, "joint_tiles")):
+        if other is not None:
+            raise ValueError(f"{who}: noise_rows keys and mixes the in-kernel noise; it cannot be combined with {name}")
+    w = noise_weights_f32([1.0] if noise_weights is None else noise_weights, f"{who}: noise_weights")
+    stride = int(noise_row_stride)
+    if stride < 1:
+        raise ValueError(f"{who}: noise_row_stride={noise_row_stride!r} must be >= 1")
+    rows = noise_rows.detach().cpu().numpy() if torch.is_tensor(noise_rows) else np.asarray(noise_rows)
+    if rows.ndim != 1 or rows.shape[0] != int(batch_size) or rows.dtype.kind not in "iu":
+        raise ValueError(f"{who}: noise_rows must be {int(batch_size)} integers (one row per sample), got shape {tuple(rows.shape)} "
+                         f"of {rows.dtype}")
+    rows = rows.astype(np.int64)
+    if (rows < 0).any():
+        raise ValueError(f"{who}: noise_rows must be >= 0, got {int(rows.min())}")
+    if (rows < (w.size - 1) * stride).any():
+        raise ValueError(f"{who}: noise_rows must be >= (lags - 1) * noise_row_stride = {(w.size - 1) * stride} (row {int(rows.min())} "
+                         f"would reach below row 0)")
+    if (rows > 0x7FFFFFFF).any():
+        raise ValueError(f"{who}: noise_rows must fit int32, got {int(rows.max())}")
+    return rows, stride, w
+
+
+def _weights_arg(w):
+    return (C.c_float * len(w))(*[float(v) for v in w])
+
+
+def temporal_noise(seed, draw, rows, per_sample, weights=(1.0,), stride=1, device="cuda", scale=1.0):
+    """scale * the mixed draw `draw` of the stream `seed` for the noise rows `rows`: fp32 [len(rows), per_sample] on the device, what a
+    sampler with `noise_rows=rows, noise_weights=weights, noise_row_stride=stride` uses as its draw `draw` (`sbgm_randn_rows`)."""
+    n_rows = int(rows.shape[0]) if hasattr(rows, "shape") else len(rows)
+    plan = _prep_noise_rows(rows, weights, stride, n_rows, "temporal_noise")
+    per_sample = int(per_sample)
+    if per_sample < 4 or per_sample % 4:
+        raise ValueError(f"temporal_noise: per_sample={per_sample} must be a positive multiple of 4")
+    dev = torch.device(device) if not isinstance(device, torch.device) else device
+    if dev.type != "cuda":
+        raise N.NativeError(f"temporal_noise runs on a ROCm device, got device={device!r}")
+    r, stride, w = plan
+    with torch.cuda.device(dev):
+        r_dev = torch.from_numpy(r.astype(np.int32)).to(dev)
+        x = torch.empty(n_rows, per_sample, device=dev)
+        N.check(N.lib().sbgm_randn_rows(x.data_ptr(), float(scale), int(seed), int(draw), r_dev.data_ptr(), n_rows, per_sample, stride,
+                                        _weights_arg(w), len(w), N.stream()))
+    return x
+
+
+class _noise_plan:
+    """The handle's noise plan around ONE native sampler call: set from `plan` (None: nothing to do) and cleared again whatever happens.
+    The rows live in a device buffer the engine keeps per batch size, so the captured step's key sees one address from call to call."""
+    def __init__(self, eng, plan, dev):
+        self.eng, self.plan, self.dev = eng, plan, dev
+
+    def __enter__(self):
+        if self.plan is None:
+            return self
+        rows, stride, w = self.plan
+        bufs = getattr(self.eng, "_noise_rows", None)
+        if bufs is None:
+            bufs = self.eng._noise_rows = {}
+        index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()     # "cuda" is the current device
+        buf = bufs.get((index, rows.size))
+        if buf is None:
+            buf = bufs[(index, rows.size)] = torch.empty(rows.size, dtype=torch.int32, device=torch.device("cuda", index))
+        buf.copy_(torch.from_numpy(rows.astype(np.int32)))
+        N.check(self.eng.lib.sbgm_sampler_set_noise_rows(self.eng.h, buf.data_ptr(), stride, _weights_arg(w), len(w)))
+        return self
+
+    def __exit__(self, *exc):
+        if self.plan is not None:
+            N.check(self.eng.lib.sbgm_sampler_set_noise_rows(self.eng.h, None, 1, None, 0))
+        return False
+
+
 def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw, y, cond_img, lsm_cond, topo_cond,
                 noise, use_graph, seed, device, cfg=None, tile_origins=None, domain_width=0, edm_args=None, held=(None, None),
-                joint=None, dpm_args=None):
+                joint=None, dpm_args=None, plan=None):
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if dev.type != "cuda":
         raise N.NativeError(f"the native samplers run on a ROCm device, got device={device!r}")
@@ -198,37 +323,40 @@ def _native_run(kind, score_model: ScoreNet, batch_size, num_steps, snr, eps, hw
         if noise is not None:
             raise ValueError("tile_origins keys the in-kernel noise; it cannot be combined with injected noise")
     known, mask = held
-    if dpm_args is not None:                               # one entry point: the constraint and the joint blend are optional arguments
-        N.check(eng.lib.sbgm_sampler_run_dpmpp(eng.h, C.byref(a), *dpm_args, N.ptr(known), N.ptr(mask), *(joint or (0, 0)), N.stream()))
-        return out
-    if joint is not None:                                  # one diffusion over the domain: the tiles' scores are blended at every step
+    with _noise_plan(eng, plan, dev):                      # set and cleared around the one native call
+        if dpm_args is not None:                           # one entry point: the constraint and the joint blend are optional arguments
+            N.check(eng.lib.sbgm_sampler_run_dpmpp(eng.h, C.byref(a), *dpm_args, N.ptr(known), N.ptr(mask), *(joint or (0, 0)), N.stream()))
+            return out
+        if joint is not None:                              # one diffusion over the domain: the tiles' scores are blended at every step
+            if edm_args is not None:
+                N.check(eng.lib.sbgm_sampler_run_edm_joint(eng.h, C.byref(a), *edm_args, *joint, N.ptr(known), N.ptr(mask), N.stream()))
+            else:
+                N.check(eng.lib.sbgm_sampler_run_joint(eng.h, C.byref(a), *joint, N.ptr(known), N.ptr(mask), N.stream()))
+            return out
         if edm_args is not None:
-            N.check(eng.lib.sbgm_sampler_run_edm_joint(eng.h, C.byref(a), *edm_args, *joint, N.ptr(known), N.ptr(mask), N.stream()))
-        else:
-            N.check(eng.lib.sbgm_sampler_run_joint(eng.h, C.byref(a), *joint, N.ptr(known), N.ptr(mask), N.stream()))
-        return out
-    if edm_args is not None:
+            if known is not None:
+                N.check(eng.lib.sbgm_sampler_run_edm_held(eng.h, C.byref(a), *edm_args, known.data_ptr(), mask.data_ptr(), N.stream()))
+            else:
+                N.check(eng.lib.sbgm_sampler_run_edm(eng.h, C.byref(a), *edm_args, N.stream()))
+            return out
         if known is not None:
-            N.check(eng.lib.sbgm_sampler_run_edm_held(eng.h, C.byref(a), *edm_args, known.data_ptr(), mask.data_ptr(), N.stream()))
+            N.check(eng.lib.sbgm_sampler_run_held(eng.h, C.byref(a), known.data_ptr(), mask.data_ptr(), N.stream()))
         else:
-            N.check(eng.lib.sbgm_sampler_run_edm(eng.h, C.byref(a), *edm_args, N.stream()))
-        return out
-    if known is not None:
-        N.check(eng.lib.sbgm_sampler_run_held(eng.h, C.byref(a), known.data_ptr(), mask.data_ptr(), N.stream()))
-    else:
-        N.check(eng.lib.sbgm_sampler_run(eng.h, C.byref(a), N.stream()))
+            N.check(eng.lib.sbgm_sampler_run(eng.h, C.byref(a), N.stream()))
     if score_model.training:
         eng.download_bn_stats(score_model, n_forwards=int(num_steps) * _counts(kind, num_steps)[0])
     return out
 
 
-def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scale, tile_origins, churn=False, joint=None):
+def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scale, tile_origins, churn=False, joint=None, plan=None):
     """Setup of the host-driven loops: refuses `tile_origins` and `joint_tiles`, checks that `noise` holds the run's draws, and returns the initial
     x = scale * (draw 0) and z(i), the i-th noise draw (None: the kernels draw in-kernel Philox noise)."""
     if joint is not None:
         raise N.NativeError("joint tiled sampling (joint_tiles) needs the native sampler loop (a ScoreNet in eval mode)")
     if tile_origins is not None:
         raise N.NativeError("domain-keyed noise (tile_origins) needs the native sampler loop (a ScoreNet in eval mode)")
+    if plan is not None:
+        raise N.NativeError("row-keyed noise (noise_rows) needs the native sampler loop (a ScoreNet in eval mode)")
     if noise is not None:
         noise = noise if torch.is_tensor(noise) else list(noise)
         need = _counts(kind, num_steps, churn)[1]
@@ -245,20 +373,22 @@ def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scal
 def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=500, device="cuda",
                            eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
                            noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None,
-                           joint_tiles=None):
+                           joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1):
     """Euler-Maruyama reverse-SDE sampler (reference score_sampling.py:63-127).  Returns the last `mean_x`.
-    `known` / `known_mask` (not in the reference): hold the masked pixels at `known`, see `pc_sampler`; `joint_tiles`: see `pc_sampler`."""
+    `known` / `known_mask` (not in the reference): hold the masked pixels at `known`, see `pc_sampler`; `joint_tiles`: see `pc_sampler`;
+    `noise_rows` / `noise_weights` / `noise_row_stride` (row-keyed, temporally correlated noise): see `pc_sampler`."""
     seed = _fresh_seed() if seed is None else seed
     joint = _prep_joint(joint_tiles, tile_origins, noise, "Euler_Maruyama_sampler")
+    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "Euler_Maruyama_sampler", noise, tile_origins, joint_tiles)
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "Euler_Maruyama_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_EM, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
                            topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask),
-                           joint=joint)
+                           joint=joint, plan=plan)
     lib, st = N.lib(), N.stream
     ones = torch.ones(batch_size, device=device)
     x, z = _host_start(N.SAMPLER_EM, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
-                       tile_origins, joint=joint)
+                       tile_origins, joint=joint, plan=plan)
     time_steps = torch.linspace(1.0, eps, num_steps, device=device)
     step_size = float(time_steps[0] - time_steps[1])
     mean_x = torch.empty_like(x)
@@ -281,7 +411,7 @@ def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batc
 def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=800, snr=signal_to_noise_ratio,
                device="cuda", eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
                noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None,
-               joint_tiles=None):
+               joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1):
     """Predictor-corrector sampler: Langevin corrector with the batch-mean gradient norm, then an Euler-Maruyama
     predictor (reference score_sampling.py:136-230).  Returns the last `x_mean`.
 
@@ -297,18 +427,29 @@ def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, n
     reads a tile's score it reads the stitch-weighted blend of every tile's score at that domain pixel (ramps of `ramp_len` pixels, as
     `FullDomainTiler.stitch`), and the corrector's step size is the batch-mean rule over the tiles.  All copies of a domain pixel then
     stay bit-equal through the run, so stitching the result averages nothing.  Needs the native loop and in-kernel noise; composes with
-    `known` / `known_mask` and guidance.  `FullDomainTiler.sample(..., joint=True)` sets it up."""
+    `known` / `known_mask` and guidance.  `FullDomainTiler.sample(..., joint=True)` sets it up.
+
+    Row-keyed, temporally correlated noise (not in the reference): `noise_rows` (sequence or int tensor [batch_size])
+    gives sample b the noise row r_b, and every in-kernel draw of the run becomes z = sum_k w_k xi(r_b - k * noise_row_stride) over the K
+    `noise_weights` (default [1.0]; their squares must sum to 1 within 1e-5, K <= 32, every r_b >= (K-1) * noise_row_stride), xi(r) the
+    white draw of row r, i.e. what a run without the arguments draws for its sample r.  Every draw a sample sees is still N(0,1),
+    independent across pixels and steps, so each sample is a sample of this sampler as it is; samples whose rows are j strides apart are
+    correlated with `temporal_noise_acf(noise_weights)[j]`, and a sample's noise depends on (seed, row) only, not on its place in the
+    batch (this sampler's Langevin step size still uses the batch-mean score norm).  Rows 0..B-1 with the default weights reproduce the
+    run without the arguments bit for bit.  Needs the native loop; refused (ValueError) with `noise`, `tile_origins` or `joint_tiles`;
+    composes with `known` / `known_mask` and guidance.  `temporal_noise_weights(rho, lags)` makes AR(1)-like weights."""
     seed = _fresh_seed() if seed is None else seed
     joint = _prep_joint(joint_tiles, tile_origins, noise, "pc_sampler")
+    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "pc_sampler", noise, tile_origins, joint_tiles)
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "pc_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_PC, score_model, batch_size, num_steps, snr, eps, img_size, y, cond_img, lsm_cond,
                            topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask),
-                           joint=joint)
+                           joint=joint, plan=plan)
     lib, st = N.lib(), N.stream
     ones = torch.ones(batch_size, device=device)
     x, z = _host_start(N.SAMPLER_PC, batch_size, num_steps, img_size, device, noise, seed, float(marginal_prob_std(ones)[0]),
-                       tile_origins, joint=joint)
+                       tile_origins, joint=joint, plan=plan)
     time_steps = np.linspace(1.0, eps, num_steps)
     step_size = float(time_steps[0] - time_steps[1])
     x_mean = torch.empty_like(x)
@@ -450,7 +591,8 @@ def edm_sampler_kwargs(cfg) -> dict:
 def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=32, device="cuda", eps=1e-3,
                      img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, sigma_min=None, sigma_max=None,
                      rho=7.0, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, noise=None, use_graph=True, seed=None,
-                     tile_origins=None, domain_width=0, known=None, known_mask=None, joint_tiles=None):
+                     tile_origins=None, domain_width=0, known=None, known_mask=None, joint_tiles=None, noise_rows=None,
+                     noise_weights=None, noise_row_stride=1):
     """Heun (2nd-order) solver of the probability-flow ODE dx/dsigma = -sigma * score on the Karras sigma ladder, with optional
     stochastic churn (Karras et al. 2022, Alg. 2); works with the VE-SDE score network as trained.  `num_steps` N costs 2N-1
     network evaluations (18-64 is the intended range).  Conditions, guidance (`cfg`: both evaluations of a step use
@@ -458,6 +600,7 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     `tile_origins` behave as in `pc_sampler`.  `diffusion_coeff` is accepted for signature compatibility and unused.
     `known` / `known_mask` as in `pc_sampler`; here a held pixel follows known + sigma * (draw 0), the exact trajectory of a point mass,
     so the sampler stays deterministic in its seed.  `joint_tiles` as in `pc_sampler`: both slopes of a step use the blended score.
+    `noise_rows` / `noise_weights` / `noise_row_stride` as in `pc_sampler`: the start, the churn and the held pixels' draw 0 are mixed.
     Returns x after the last step, [B,1,H,W] (no noise added at the end).  Sample quality against `pc_sampler` at 1000 steps
     has not been measured."""
     sig = float(score_model.sigma) if isinstance(score_model, ScoreNet) else _sigma_of(marginal_prob_std)
@@ -465,16 +608,17 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     seed = _fresh_seed() if seed is None else seed
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "edm_heun_sampler")
     joint = _prep_joint(joint_tiles, tile_origins, noise, "edm_heun_sampler")
+    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "edm_heun_sampler", noise, tile_origins, joint_tiles)
     if isinstance(score_model, ScoreNet) and not score_model.training:
         edm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
                     float(s_churn), float(s_tmin), float(s_tmax), float(s_noise))
         return _native_run(N.SAMPLER_EDM_HEUN, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
                            topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, edm_args=edm_args,
-                           held=(known, known_mask), joint=joint)
+                           held=(known, known_mask), joint=joint, plan=plan)
     lib, st = N.lib(), N.stream
     churn = s_churn > 0
     x, z = _host_start(N.SAMPLER_EDM_HEUN, batch_size, num_steps, img_size, device, noise, seed, float(np.float32(sch["sigma"][0])),
-                       tile_origins, churn, joint=joint)
+                       tile_origins, churn, joint=joint, plan=plan)
     n = x.numel()
     xp, d, out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     ones = torch.ones(batch_size, device=device)
@@ -541,7 +685,7 @@ def dpm_sampler_kwargs(cfg) -> dict:
 def dpmpp_2m_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=32, device="cuda", eps=1e-3,
                      img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, sigma_min=None, sigma_max=None,
                      rho=7.0, eta=0.0, s_noise=1.0, noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0,
-                     known=None, known_mask=None, joint_tiles=None):
+                     known=None, known_mask=None, joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1):
     """DPM-Solver++(2M) (Lu et al. 2022) on the Karras sigma ladder of `edm_heun_sampler`: a second-order multistep solver that reuses the
     previous step's denoised estimate, so `num_steps` N costs exactly N network evaluations (EDM Heun: 2N-1).  `eta = 0` is the
     deterministic solver of the probability-flow ODE; `eta > 0` is the SDE variant ("2M SDE", midpoint form), which adds noise of weight
@@ -550,6 +694,7 @@ def dpmpp_2m_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     step i.  `diffusion_coeff` is accepted for signature compatibility and unused.
     `known` / `known_mask` as in `pc_sampler`: after every step the held pixels are known + sigma_{i+1} z, with z the run's draw 0 when
     eta = 0 (the trajectory of a point mass, as in `edm_heun_sampler`: deterministic in the seed) and the step's own draw when eta > 0.
+    `noise_rows` / `noise_weights` / `noise_row_stride` as in `pc_sampler` (the start, and with eta > 0 every step's draw).
     An eval-mode ScoreNet runs the native loop (`sbgm_sampler_run_dpmpp`); any other callable runs a Python loop over the same update
     kernel.  Returns x after the last step, [B,1,H,W].  On the analytic Gaussian problem it has the error of EDM Heun at the same N;
     sample quality on a trained checkpoint has not been measured."""
@@ -558,17 +703,18 @@ def dpmpp_2m_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     seed = _fresh_seed() if seed is None else seed
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "dpmpp_2m_sampler")
     joint = _prep_joint(joint_tiles, tile_origins, noise, "dpmpp_2m_sampler")
+    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "dpmpp_2m_sampler", noise, tile_origins, joint_tiles)
     if isinstance(score_model, ScoreNet) and not score_model.training:
         dpm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
                     float(eta), float(s_noise))
         return _native_run(N.SAMPLER_DPMPP_2M, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
                            topo_cond, noise, use_graph, seed, device, cfg, tile_origins, domain_width, held=(known, known_mask),
-                           joint=joint, dpm_args=dpm_args)
+                           joint=joint, dpm_args=dpm_args, plan=plan)
     lib, st = N.lib(), N.stream
     sde = eta > 0
     f32 = lambda v: float(np.float32(v))  # noqa: E731
     x, z = _host_start(N.SAMPLER_DPMPP_2M, batch_size, num_steps, img_size, device, noise, seed, f32(sch["sigma"][0]), tile_origins, sde,
-                       joint=joint)
+                       joint=joint, plan=plan)
     n = x.numel()
     hist = torch.empty_like(x)
     ones = torch.ones(batch_size, device=device)
@@ -774,7 +920,7 @@ def _ode_stats(raw_i, raw_d, G, per_sample, max_steps, surplus):
 def rk45_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, device="cuda", eps=1e-3, img_size=64, y=None,
                  cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, rtol=1e-5, atol=1e-5, error_norm="batch", t_span=None,
                  z=None, noise=None, seed=None, use_graph=True, max_steps=10000, tile_origins=None, domain_width=0,
-                 return_stats=False):
+                 return_stats=False, noise_rows=None, noise_weights=None, noise_row_stride=1):
     """Adaptive solver of the probability-flow ODE dx/dt = -1/2 g(t)^2 score(x, t) on the device: Dormand-Prince 5(4) with FSAL and
     the step controller of scipy.integrate.RK45 (`rk45_host_solve` is the definition), with the right-hand side in the precision of
     `ode_sampler` (network input and time in fp32, g(t)^2 squared in fp32, state and stage sums in float64).  `rtol` / `atol` take
@@ -788,6 +934,8 @@ def rk45_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64,
                 so a sample's trajectory does not depend on its batch-mates; required with `tile_origins`.
     max_steps   attempts (accepted + rejected) a controller may use; OdeSolverError when they run out, on a non-finite error norm, or
                 when the step size underflows.
+    `noise_rows` / `noise_weights` / `noise_row_stride` as in `pc_sampler`: they key and mix the start draw (the solver draws nothing
+    else), so they are refused with `z`.
     `seed`, `use_graph`, `tile_origins`, `domain_width` as in `edm_heun_sampler`; `diffusion_coeff` is accepted for signature
     compatibility and unused (g(t) = sigma^t of the model).  An eval-mode ScoreNet runs the native loop (`sbgm_sampler_run_ode`:
     one captured attempt replayed until the device reports done); any other callable, or a train-mode model, runs a Python loop over
@@ -810,6 +958,9 @@ def rk45_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64,
             raise ValueError(f"rk45_sampler: z must be [B, 1, H, H], got {tuple(z.shape)}")
         batch_size, img_size = int(z.shape[0]), int(z.shape[-1])
     B, hw = int(batch_size), int(img_size)
+    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, B, "rk45_sampler", noise, tile_origins)
+    if plan is not None and z is not None:
+        raise ValueError("rk45_sampler: noise_rows keys the start draw; it cannot be combined with z")
     G = B if per_sample else 1
     sig = float(score_model.sigma) if isinstance(score_model, ScoreNet) else _sigma_of(marginal_prob_std)
     seed = _fresh_seed() if seed is None else seed
@@ -838,8 +989,9 @@ def rk45_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64,
         a = N.SamplerArgs(N.SAMPLER_RK45, B, hw, hw, 0, float(eps), 0.0, int(seed), int(bool(use_graph)), 0, N.ptr(y), N.ptr(cond_img),
                           N.ptr(lsm_cond), N.ptr(topo_cond), N.ptr(nz), out.data_ptr(), *_guidance(cfg), N.ptr(tile_origins),
                           int(domain_width or 0))
-        N.check(eng.lib.sbgm_sampler_run_ode(eng.h, C.byref(a), t0, t1, float(rtol), float(atol), int(per_sample), int(max_steps),
-                                             N.ptr(x0), raw_i.ctypes.data, raw_d.ctypes.data, N.stream()))
+        with _noise_plan(eng, plan, dev):
+            N.check(eng.lib.sbgm_sampler_run_ode(eng.h, C.byref(a), t0, t1, float(rtol), float(atol), int(per_sample), int(max_steps),
+                                                 N.ptr(x0), raw_i.ctypes.data, raw_d.ctypes.data, N.stream()))
         stats = _ode_stats(raw_i, raw_d, G, per_sample, max_steps, raw_i[4 * G])
         return (out, stats) if return_stats else out
 
@@ -851,7 +1003,7 @@ def rk45_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64,
         x = N.f32c(z.to(dev)).clone()
     else:
         std0 = float(marginal_prob_std(torch.full((B,), t0, device=dev))[0])
-        x, _ = _host_start(N.SAMPLER_RK45, B, 0, hw, dev, noise, seed, std0, tile_origins)
+        x, _ = _host_start(N.SAMPLER_RK45, B, 0, hw, dev, noise, seed, std0, tile_origins, plan=plan)
     N.require_device(x)
     per, n = hw * hw, B * hw * hw
     state = torch.empty(int(lib.sbgm_rk45_state_bytes(G)), dtype=torch.uint8, device=dev)
