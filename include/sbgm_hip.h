@@ -1009,6 +1009,43 @@ int sbgm_climate_indices(const float* gen, const float* obs, const void* mask, i
                          int* days, float* stats, int* spells, int* transitions, float* quant, float* wet_quant, float* heavy,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- pooled ensemble verification of a series (verify_series.hip) --------------------------------------
+ * sbgm_series_scores: D days (1 <= D <= 4095) of M members (2 <= M <= 4095) E[d][m][p] against one truth Y[d][p] per day, pooled
+ * over days x pixels.  Member (d, m) is read at ens + d * day_stride + m * member_stride (strides in elements, each >= H*W; the H*W
+ * pixels of a field are dense), so [D][M][H][W] and [M][D][H][W] both work without a copy.  obs [D][H][W]; mask NULL, [H][W]
+ * (Nm = 1) or [D][H][W] (Nm = D); the field limits above.  groups: NULL (G = 0) or a DEVICE int32 [D] of ids in 0..G-1,
+ * G <= 16 (an id outside is the caller's error; the kernels clamp it, so nothing is written out of bounds).  thresholds: a HOST
+ * array of 0 <= T <= 16 finite values.  A cell (d, p) is valid when Y and every member are not NaN there and the mask admits it;
+ * n_p = the valid days of pixel p.  Per valid cell, in fp64 and in sbgm_ensemble_scores' op order: mean, var (ddof 1),
+ * crps_fair, crps_std, se = (mean - y)^2 and the randomised rank r in {lt..le}, its draw keyed by (seed, d, p), so day 0 draws
+ * what sbgm_ensemble_scores draws.  Row 0 of every [G+1] axis is all days, row 1 + g is group g.
+ *   count int32 [HW]: n_p.
+ *   maps fp32 [4][HW], NaN where n_p = 0: crps = sum_d crps_fair / n_p; spread = sqrt(sum var / n_p); skill = sqrt(sum se / n_p);
+ *     ssr = sqrt((M+1)/M) spread / skill.  Each sum is fp64 in day order in one thread, rounded to fp32 once.
+ *   daily fp64 [D][6]: sbgm_ensemble_scores' scores over the valid pixels of each day.
+ *   scores fp64 [G+1][6]: the same over the valid cells of the row's days.
+ *   rank_hist int64 [G+1][M+1]; table int64 [G+1][T][M+1][2], sbgm_exceedance_scores' table over the row's cells; both exact.
+ *   exceedance fp64 [G+1][6][T]: sbgm_exceedance_scores' scores of each row's table.
+ * With climatology != 0 the reference forecast for day d at pixel p is the leave-one-out ensemble of the truth on the other valid
+ * days of the same row at p (row 0: all days; a group row: the group's days).  With S the sum over the ordered pairs of those n
+ * days of |y_i - y_j|, the reference's fair CRPS summed over the days is C = S / (2 (n - 1)); it needs n >= 3.
+ *   clim_maps fp32 [2][HW]: clim_crps = C_p / n_p; crpss = (float)(1 - F_p / C_p), F_p = sum_d crps_fair.  NaN where n_p < 3;
+ *     crpss also where C_p = 0.
+ *   skill_scores fp64 [G+1][4]: (cells, mean forecast fair CRPS, mean reference CRPS, 1 - sum F / sum C) over the cells of the
+ *     pixels with n >= 3 in that row; the means NaN without cells, the last also when sum C = 0.
+ * With T = 0 thresholds, table and exceedance may be NULL; with climatology = 0, clim_maps and skill_scores.  The workspace
+ * (size from the query, which returns 0 for arguments the call would reject) holds the per-pixel sums, the validity bits, the
+ * per-group per-pixel sums and the per-wave partials of one chunk of days: the days are worked through in chunks that keep it
+ * within max_bytes (at least 32 days a chunk), and no output depends on the chunking.  No float atomics: two calls give
+ * bit-equal outputs.  Cost: M / 16 + 2 sweeps over the members; the climatology is O(n_p^2 / 2) per pixel. */
+#define SBGM_SERIES_MAX_GROUPS 16
+int64_t sbgm_series_scores_workspace_bytes(int D, int M, int H, int W, int T, int G, int climatology, int64_t max_bytes);
+int sbgm_series_scores(const float* ens, int64_t day_stride, int64_t member_stride, const float* obs, const void* mask,
+                       int mask_is_u8, int Nm, const int* groups /* DEVICE */, int G, int D, int M, int H, int W,
+                       const float* thresholds /* HOST */, int T, uint64_t seed, int climatology, int* count, float* maps,
+                       double* daily, double* scores, int64_t* rank_hist, int64_t* table, double* exceedance, float* clim_maps,
+                       double* skill_scores, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- before the network ------------------------------------------------------------------------
  * Batch-level condition assembly: channel concatenation of the sorted *_lr fields (utils.py:441-447), classifier-free-
  * guidance condition dropout (data_modules.py:957-983: LR fields -> 0, class label -> NULL token 0) and the value||mask

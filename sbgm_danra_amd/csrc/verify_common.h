@@ -1,10 +1,10 @@
 // Helpers shared by the verification kernels (verify.hip, verify_spatial.hip, verify_products.hip, verify_objects.hip,
-// verify_multivariate.hip) and, for the order-preserving key, postproc.hip: the validity predicates, the NaN
+// verify_multivariate.hip, verify_series.hip) and, for the order-preserving key, postproc.hip: the validity predicates, the NaN
 // constants, the float <-> uint32 key, the threshold list and its host-side fill, the field / member limits, the block
 // reductions and the host-side planner of (field, threshold) chunks.  Each is defined here once.
 // Some of the including files compile with FP contraction off and some with it on.  The device helpers below contain only
 // adds, comparisons and min / max, so nothing in them can contract and they mean the same in both; keep it that way: no
-// multiply-add belongs in this header.
+// multiply-add belongs in this header.  The one exception, exceedance_finish_row, turns contraction off inside its own body.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -118,6 +118,46 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
     unsigned long long t = 0;
     for (int w = 0; w < THREADS / SBGM_WAVE; ++w) t += slot[w];
     return t;
+}
+
+// ---- the scores of one exceedance table -------------------------------------------------------------------------------------
+// K46's finish, shared by exceedance_scores (one table per threshold) and series_scores (one per row and threshold).  `tab` is
+// threshold t's table [M + 1][2].  With n_k, o_k the two columns, N = sum n_k, O = sum o_k, p_k = k / M, obar = O / N and
+// obar_k = o_k / n_k:
+//   brier = sum_k (n_k p_k^2 - 2 o_k p_k + o_k) / N        reliability = sum_k n_k (p_k - obar_k)^2 / N
+//   resolution = sum_k n_k (obar_k - obar)^2 / N            uncertainty = obar (1 - obar)
+//   roc_area: forecast "yes" when k >= c; the points (false-alarm rate, hit rate) for c = M + 1 (0, 0) down to c = 0 (1, 1)
+//   joined by trapezoids; NaN when the event never or always occurs.
+// scores [6][T]: entry t of (brier, reliability, resolution, uncertainty, base_rate, roc_area); *cells = N.  N == 0 gives NaN.
+__device__ __forceinline__ void exceedance_finish_row(const long long* __restrict__ tab, int M, int T, int t, long long* cells,
+                                                      double* __restrict__ scores) {
+#pragma clang fp contract(off)
+    long long Nn = 0, Oo = 0;
+    for (int k = 0; k <= M; ++k) { Nn += tab[2 * k]; Oo += tab[2 * k + 1]; }
+    *cells = Nn;
+    const double N = (double)Nn, O = (double)Oo, Md = (double)M;
+    double bs = 0.0, rel = 0.0, res = 0.0, area = 0.0;
+    const double obar = O / N;
+    long long hits = 0, fas = 0;
+    for (int k = M; k >= 0; --k) {
+        const double nk = (double)tab[2 * k], ok = (double)tab[2 * k + 1], pk = (double)k / Md;
+        bs += nk * pk * pk - 2.0 * ok * pk + ok;
+        if (tab[2 * k] > 0) {
+            const double obk = ok / nk;
+            rel += nk * (pk - obk) * (pk - obk);
+            res += nk * (obk - obar) * (obk - obar);
+        }
+        const long long h1 = hits + tab[2 * k + 1], f1 = fas + tab[2 * k] - tab[2 * k + 1];
+        area += ((double)(f1 - fas) / (N - O)) * (((double)h1 + (double)hits) / O) / 2.0;
+        hits = h1; fas = f1;
+    }
+    const bool any = Nn > 0;
+    scores[0 * T + t] = any ? bs / N : nan_d();
+    scores[1 * T + t] = any ? rel / N : nan_d();
+    scores[2 * T + t] = any ? res / N : nan_d();
+    scores[3 * T + t] = any ? obar * (1.0 - obar) : nan_d();
+    scores[4 * T + t] = any ? obar : nan_d();
+    scores[5 * T + t] = (any && Oo > 0 && Oo < Nn) ? area : nan_d();
 }
 
 // ---- chunks of (field, threshold) pairs -------------------------------------------------------------------------------------

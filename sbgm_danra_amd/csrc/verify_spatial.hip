@@ -240,44 +240,16 @@ __global__ __launch_bounds__(kExcThreads) void exceedance_kernel(const float* __
         if (bins[b]) atomicAdd(&out[b], (unsigned long long)bins[b]);
 }
 
-// one block; thread t < T walks its threshold's table in bin order.  With n_k, o_k the two columns, N = sum n_k, O = sum o_k,
-// p_k = k / M, obar = O / N and obar_k = o_k / n_k:
-//   brier = sum_k (n_k p_k^2 - 2 o_k p_k + o_k) / N        reliability = sum_k n_k (p_k - obar_k)^2 / N
-//   resolution = sum_k n_k (obar_k - obar)^2 / N            uncertainty = obar (1 - obar)
-//   roc_area: forecast "yes" when k >= c; the points (false-alarm rate, hit rate) for c = M + 1 (0, 0) down to c = 0 (1, 1)
-//   joined by trapezoids; NaN when the event never or always occurs.
-// scores [6][T] = (brier, reliability, resolution, uncertainty, base_rate, roc_area); count[0] = N.  N == 0 gives NaN.
+// one block; thread t < T walks its threshold's table in bin order: exceedance_finish_row (verify_common.h), which
+// verify_series.hip runs on each of its rows.  scores [6][T] = (brier, reliability, resolution, uncertainty, base_rate,
+// roc_area); count[0] = N.  N == 0 gives NaN.
 __global__ __launch_bounds__(64) void exceedance_finish_kernel(const long long* __restrict__ table, int M, int T,
                                                                long long* __restrict__ count, double* __restrict__ scores) {
     const int t = threadIdx.x;
     if (t >= T) return;
-    const long long* tab = table + (size_t)t * (M + 1) * 2;
-    long long Nn = 0, Oo = 0;
-    for (int k = 0; k <= M; ++k) { Nn += tab[2 * k]; Oo += tab[2 * k + 1]; }
-    if (t == 0) count[0] = Nn;
-    const double N = (double)Nn, O = (double)Oo, Md = (double)M;
-    double bs = 0.0, rel = 0.0, res = 0.0, area = 0.0;
-    const double obar = O / N;
-    long long hits = 0, fas = 0;
-    for (int k = M; k >= 0; --k) {
-        const double nk = (double)tab[2 * k], ok = (double)tab[2 * k + 1], pk = (double)k / Md;
-        bs += nk * pk * pk - 2.0 * ok * pk + ok;
-        if (tab[2 * k] > 0) {
-            const double obk = ok / nk;
-            rel += nk * (pk - obk) * (pk - obk);
-            res += nk * (obk - obar) * (obk - obar);
-        }
-        const long long h1 = hits + tab[2 * k + 1], f1 = fas + tab[2 * k] - tab[2 * k + 1];
-        area += ((double)(f1 - fas) / (N - O)) * (((double)h1 + (double)hits) / O) / 2.0;
-        hits = h1; fas = f1;
-    }
-    const bool any = Nn > 0;
-    scores[0 * T + t] = any ? bs / N : nan_d();
-    scores[1 * T + t] = any ? rel / N : nan_d();
-    scores[2 * T + t] = any ? res / N : nan_d();
-    scores[3 * T + t] = any ? obar * (1.0 - obar) : nan_d();
-    scores[4 * T + t] = any ? obar : nan_d();
-    scores[5 * T + t] = (any && Oo > 0 && Oo < Nn) ? area : nan_d();
+    long long cells;
+    exceedance_finish_row(table + (size_t)t * (M + 1) * 2, M, T, t, &cells, scores);
+    if (t == 0) count[0] = cells;
 }
 
 inline int strips(int W) { return (W + kStrip - 1) / kStrip; }

@@ -4,12 +4,13 @@ files `SampleGenerator` writes, moves them to the GPU once, and computes every s
 ensemble scores (CRPS, rank histogram, spread/skill), radially averaged power spectra and, on request, neighbourhood scores
 (Fractions Skill Score), threshold-exceedance scores (Brier, reliability table, ROC area), ensemble products (mean, spread,
 envelope, quantile and exceedance-probability maps with the coverage of each quantile map), object-based scores (connected
-objects and SAL: structure, amplitude, location) and multivariate ensemble scores (energy score, variogram score).  Only scalars, maps, per-field arrays and histograms come back to the host.
+objects and SAL: structure, amplitude, location), multivariate ensemble scores (energy score, variogram score), climate indices
+along the day axis and the pooled ensemble verification of a series over days x pixels.  Only scalars, maps, per-field arrays and histograms come back to the host.
 Plots are out of scope: the plotting keys are accepted and logged as skipped.
 
 Files are found by name: `gen_samples_*`, `eval_samples_*` and `lsm_samples_*` with the suffixes `multi_n_<B>`, `single`,
 `repeated_n_<n>` (this package), `repeated_<n>` (the reference) or `series_n_<D>` (gen_samples [D, M, H, W]: D days of M
-members each; the per-field statistics run on member 0, the climate indices on all members), each optionally followed by
+members each; the per-field statistics run on member 0, the climate indices and the series scores on all members), each optionally followed by
 `_rank<r>`.  Rank files of `multiple` / `single` are concatenated along the sample axis; each rank's `repeated` file is its own
 unit (every rank conditions on a different sample), selected with `rank=`."""
 from __future__ import annotations
@@ -232,6 +233,53 @@ def climate_indices_config(cfg):
             raise ValueError(f"evaluation.climate_indices.{key}: at most {V.MAX_TEMPORAL_QUANTILES} entries, got {len(values)}")
         levels.append(_number_list(f"evaluation.climate_indices.{key}", values, 0, 1))
     return float(wet), levels[0], levels[1]
+
+
+def series_scores_config(cfg):
+    """(thresholds, climatology, groups, seed) of the optional evaluation.series_scores section — `thresholds`: up to 16 finite
+    numbers in the units the generated files hold (default none); `climatology`: bool (default true), the leave-one-out
+    climatological reference and the CRPS skill score; `groups`: None, a list of one integer group id in 0..15 per day, or the
+    path of a .npy file holding one; `seed`: None (evaluation.seed) or an integer, the seed of the rank ties — or None when the
+    section is absent"""
+    sec = cfg["evaluation"].get("series_scores")
+    if sec is None:
+        return None
+    keys = ("thresholds", "climatology", "groups", "seed")
+    if not hasattr(sec, "keys") or not set(sec.keys()) <= set(keys):
+        unknown = sorted(set(sec.keys()) - set(keys)) if hasattr(sec, "keys") else sec
+        raise ValueError(f"evaluation.series_scores takes the keys 'thresholds', 'climatology', 'groups' and 'seed' only, got {unknown!r}")
+    thresholds = sec.get("thresholds")
+    thresholds = [] if thresholds is None else thresholds
+    if not isinstance(thresholds, (list, tuple)):
+        raise ValueError(f"evaluation.series_scores.thresholds must be a list of numbers, got {thresholds!r}")
+    thresholds = _number_list("evaluation.series_scores.thresholds", thresholds)
+    climatology = sec.get("climatology", True)
+    if not isinstance(climatology, bool):
+        raise ValueError(f"evaluation.series_scores.climatology must be true or false, got {climatology!r}")
+    groups = sec.get("groups")
+    if isinstance(groups, str):
+        if not groups.endswith(".npy"):
+            raise ValueError(f"evaluation.series_scores.groups: a path must name a .npy file, got {groups!r}")
+    elif groups is not None:
+        if not isinstance(groups, (list, tuple)) or not groups or any(isinstance(g, bool) or not isinstance(g, int) or
+                                                                      not 0 <= g < V.MAX_SERIES_GROUPS for g in groups):
+            raise ValueError(f"evaluation.series_scores.groups must be null, a .npy path or a list of integers in "
+                             f"0..{V.MAX_SERIES_GROUPS - 1}, one per day, got {groups!r}")
+        groups = [int(g) for g in groups]
+    seed = sec.get("seed")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+        raise ValueError(f"evaluation.series_scores.seed must be null or an integer, got {seed!r}")
+    return thresholds, climatology, groups, seed
+
+
+SERIES_DEFINITION = (
+    "pooled over days x pixels of the series; a cell (day, pixel) is valid when the truth and every member are not NaN and the mask "
+    "admits it.  crps_fair, crps_standard, skill, spread, spread_skill_ratio: as ensemble_stats, over the cells.  rank histogram: rank "
+    "of the truth among the M members, ties broken at random.  rank_reliability_index = sum_k |h_k / N - 1 / (M + 1)|; outside_fraction "
+    "= (h_0 + h_M) / N.  brier scores from the table (members >= threshold, truth >= threshold) over the cells; brier_skill = 1 - brier "
+    "/ brier_uncertainty.  crpss = 1 - sum F / sum C over the cells of the pixels with at least 3 valid days, F the forecast's fair CRPS, "
+    "C that of the leave-one-out ensemble of the truth on the other valid days of the same pixel (and group).  pooled = all days; "
+    "groups = the days with that group id")
 
 
 def _pattern_summary(gen, obs):
@@ -613,9 +661,75 @@ class Evaluation:
         self.climate_fields = res
         return dict(res, metrics=out)
 
+    def series_ensemble_statistics(self, thresholds=None, climatology=None, groups=None, seed=None):
+        """pooled ensemble verification of a 'series' (D days of M >= 2 members, one truth per day) over days x pixels: CRPS,
+        spread and skill maps, daily and pooled scores, rank histogram, reliability table with the Brier scores, and the CRPS
+        skill score against the leave-one-out climatology, pooled and per group of days.  The arrays go to a file of their own,
+        <label>_series_scores.npz, which save() writes; the metrics entry is `series_ensemble`.  Arguments default to the
+        evaluation.series_scores section; `groups` is one id in 0..15 per day (a list, an array or a .npy path)."""
+        if self.generated_sample_type != "series":
+            raise ValueError(f"series_ensemble_statistics needs 'series' samples (days x members), not '{self.generated_sample_type}'")
+        if thresholds is None and climatology is None and groups is None and seed is None:
+            sec = series_scores_config(self.cfg)
+            if sec is None:
+                raise ValueError("no arguments given and the config has no evaluation.series_scores section")
+            thresholds, climatology, groups, seed = sec
+        M, D = int(self.members.shape[0]), int(self.members.shape[1])
+        if M < 2:
+            raise ValueError(f"series_ensemble_statistics needs at least 2 members; {self.label} has {M}: generate with "
+                             f"evaluation.series.members >= 2")
+        if self.eval_imgs.shape[0] != D:
+            raise ValueError(f"series_ensemble_statistics needs as many truths as days; {self.label} has {self.eval_imgs.shape[0]} for {D}")
+        thresholds = [float(t) for t in (thresholds or [])]
+        climatology = True if climatology is None else bool(climatology)
+        seed = int(self.cfg["evaluation"].get("seed", 0)) if seed is None else int(seed)
+        if isinstance(groups, str):
+            groups = np.load(groups)
+        if groups is not None:
+            groups = np.asarray(groups)
+            if groups.ndim != 1 or groups.dtype.kind not in "iu":
+                raise ValueError(f"evaluation.series_scores.groups must hold one integer id per day, got shape {groups.shape} of {groups.dtype}")
+            if len(groups) != D:
+                raise ValueError(f"evaluation.series_scores.groups holds {len(groups)} ids; {self.label} has {D} days")
+            groups = [int(g) for g in groups]
+        r = V.series_ensemble_scores(self.members.permute(1, 0, 2, 3), self.eval_imgs, thresholds, groups=groups, mask=self.mask,
+                                     seed=seed, climatology=climatology)
+        res = {k: r[k].cpu().numpy() for k in V.SERIES_KEYS}
+        res["thresholds"] = np.asarray(thresholds, np.float64)
+        res["groups"] = np.asarray([] if groups is None else groups, np.int64)
+
+        def row(i):
+            s, h = res["scores"][i], res["rank_hist"][i].astype(np.float64)
+            n = h.sum()
+            out = dict(zip(V.ENSEMBLE_KEYS, (float(v) for v in s)))
+            out["count"] = int(s[0])
+            out["rank_reliability_index"] = float(np.abs(h / n - 1.0 / (M + 1)).sum()) if n > 0 else float("nan")
+            out["outside_fraction"] = float((h[0] + h[M]) / n) if n > 0 else float("nan")
+            out.update({k: res["exceedance"][i, j].tolist() for j, k in enumerate(V.EXCEEDANCE_KEYS)})
+            bs, unc = res["exceedance"][i, 0], res["exceedance"][i, 3]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out["brier_skill"] = np.where(unc > 0, 1.0 - bs / unc, np.nan).tolist()
+            if climatology:                  # over the cells of the pixels with >= 3 valid days in the row, a subset of `count`
+                out["climatology"] = dict(zip(V.SERIES_SKILL_KEYS, (float(v) for v in res["skill_scores"][i])))
+                out["climatology"]["cells"] = int(res["skill_scores"][i, 0])
+                out["crpss"] = out["climatology"]["crpss"]
+            return out
+
+        G = res["scores"].shape[0] - 1
+        out = {"M": M, "D": D, "thresholds": thresholds, "climatology": climatology, "rank_seed": seed, "n_groups": G,
+               "pixels": int((res["count"] > 0).sum()), "pooled": row(0), "groups": [row(1 + g) for g in range(G)],
+               "crps_definitions": CRPS_DEFINITIONS, "definition": SERIES_DEFINITION}
+        out["crpss"] = out["pooled"].get("crpss", float("nan"))
+        self.metrics["series_ensemble"] = out
+        self.series_fields = res
+        return dict(res, metrics=out)
+
     def save(self):
         """<label>_metrics.json and <label>_fields.npz under the statistics directory; returns their paths.  After
-        multivariate_statistics also <label>_multivariate.npz, after climate_statistics also <label>_climate.npz."""
+        multivariate_statistics also <label>_multivariate.npz, after climate_statistics also <label>_climate.npz, after
+        series_ensemble_statistics also <label>_series_scores.npz."""
+        if getattr(self, "series_fields", None):
+            np.savez(os.path.join(self.evaluation_stats_path, f"{self.label}_series_scores.npz"), **self.series_fields)
         if getattr(self, "climate_fields", None):
             np.savez(os.path.join(self.evaluation_stats_path, f"{self.label}_climate.npz"), **self.climate_fields)
         if getattr(self, "multivariate_fields", None):

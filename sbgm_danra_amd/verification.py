@@ -4,7 +4,8 @@ statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill), ra
 table, ROC area), ensemble products (per-pixel mean, spread, envelope, quantile and exceedance-probability maps) and
 object-based scores (connected objects and SAL: structure, amplitude, location) and multivariate ensemble scores (energy score,
 variogram score) and per-pixel climate indices along the day axis (wet-day frequency and intensity, spells, transitions,
-lag-1 autocorrelation, quantiles, heavy-rain fraction).  Every function takes tensors on
+lag-1 autocorrelation, quantiles, heavy-rain fraction) and pooled ensemble scores of a series over days x pixels (csrc/verify_series.hip:
+CRPS and spread/skill maps, rank histogram, reliability table, climatological CRPS skill score, per group of days).  Every function takes tensors on
 the ROCm device and returns tensors on the device; arguments and shapes are checked before any launch and nothing is copied
 to the host.  A pixel is valid when gen (every member) and obs are not NaN and the mask admits it (uint8/bool != 0, or float
 > 0.5); every statistic uses the valid pixels only."""
@@ -38,6 +39,12 @@ MAX_TEMPORAL_DAYS, MAX_TEMPORAL_QUANTILES = 4095, 8    # include/sbgm_hip.h: SBG
 CLIMATE_STATS = ("mean", "wet_freq", "sdii", "max", "p_ww", "p_dw", "lag1")      # the order of SBGM_TEMPORAL_STAT_*
 CLIMATE_FLOAT_KEYS = CLIMATE_STATS + ("quantiles", "wet_quantiles", "heavy_fraction")
 CLIMATE_INT_KEYS = ("cwd", "cdd", "transitions")
+MAX_SERIES_GROUPS, MAX_SERIES_MEMBERS = 16, 4095        # include/sbgm_hip.h: SBGM_SERIES_MAX_GROUPS; days: MAX_TEMPORAL_DAYS
+SERIES_MAP_KEYS = ("crps", "spread", "skill", "ssr")
+SERIES_CLIM_MAP_KEYS = ("clim_crps", "crpss")
+SERIES_SKILL_KEYS = ("cells", "crps_fair", "crps_reference", "crpss")
+SERIES_KEYS = (("count",) + SERIES_MAP_KEYS + ("daily", "scores", "rank_hist", "table", "exceedance") + SERIES_CLIM_MAP_KEYS +
+               ("skill_scores",))
 
 
 def _rows(t, name, HW, allowed):
@@ -562,4 +569,102 @@ def climate_indices(gen, obs, wet=1.0, quantiles=(), wet_quantiles=(), mask=None
         out.update({f"{side}_cwd": spells[s, 0].view(H, W), f"{side}_cdd": spells[s, 1].view(H, W),
                     f"{side}_transitions": trans[s].view(4, H, W), f"{side}_quantiles": quant[s].view(Q, H, W),
                     f"{side}_wet_quantiles": wquant[s].view(QW, H, W), f"{side}_heavy_fraction": heavy[s].view(QW, H, W)})
+    return out
+
+
+def _series_groups(groups, D):
+    """(host int list or None, G) of the optional group ids, one per day, each in 0..15; G = the largest id + 1"""
+    if groups is None:
+        return None, 0
+    if isinstance(groups, torch.Tensor):
+        if groups.dim() != 1 or groups.is_floating_point() or groups.dtype == torch.bool:
+            raise ValueError(f"groups: expected a 1-D integer tensor, got {tuple(groups.shape)} of {groups.dtype}")
+        groups = groups.tolist()
+    groups = list(groups)
+    if any(isinstance(g, bool) or int(g) != g for g in groups):
+        raise ValueError(f"series_ensemble_scores: groups must be integers, got {groups}")
+    groups = [int(g) for g in groups]
+    if len(groups) != D:
+        raise ValueError(f"series_ensemble_scores: {len(groups)} group ids for D={D} days")
+    if min(groups) < 0 or max(groups) >= MAX_SERIES_GROUPS:
+        raise ValueError(f"series_ensemble_scores: group ids must lie in 0..{MAX_SERIES_GROUPS - 1} (G <= {MAX_SERIES_GROUPS}), got "
+                         f"{min(groups)}..{max(groups)}")
+    return groups, max(groups) + 1
+
+
+def series_ensemble_scores(ens, obs, thresholds=(), groups=None, mask=None, seed=0, climatology=True,
+                           max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+    """pooled ensemble verification of a series: members ens with logical dims [D,M,H,W] (1 <= D <= 4095 days, 2 <= M <= 4095)
+    against one truth per day obs [D,H,W], optional mask [H,W] or [D,H,W], pooled over days x pixels.  Any fp32 view of ens whose
+    last two dims are dense (such as a permuted [M,D,H,W] tensor) is passed by its strides; anything else is copied.  A cell
+    (d, p) is valid when the truth and every member are not NaN there and the mask admits it.  `groups`: a group id in 0..15 per
+    day (a sequence or an integer tensor; G = the largest id + 1), e.g. the season; row 0 of every [G+1] axis below is all days,
+    row 1 + g is group g.  Up to 16 finite `thresholds`, or none.  Returns a dict of device tensors: `count` int32 [H,W], the valid
+    days n_p; fp32 [H,W] maps, NaN where n_p = 0: `crps` (mean fair CRPS over the days), `spread` = sqrt(mean var), `skill` =
+    sqrt(mean (mean - y)^2), `ssr` = sqrt((M+1)/M) spread / skill; `daily` fp64 [D,6] and `scores` fp64 [G+1,6] in ENSEMBLE_KEYS
+    order (each day's valid pixels; the row's valid cells); `rank_hist` int64 [G+1,M+1] of the randomised ranks (ties broken by
+    a Philox draw keyed by (seed, day, pixel): day 0 draws what ensemble_scores draws); `table` int64 [G+1,T,M+1,2] and
+    `exceedance` fp64 [G+1,6,T] in EXCEEDANCE_KEYS order, exceedance_scores' table and scores per row.  With `climatology` the
+    reference forecast for a day is the leave-one-out ensemble of the truth on the other valid days of the same row at that
+    pixel, scored with the same fair CRPS (it needs n >= 3 days): `clim_crps` fp32 [H,W], its mean over the days; `crpss` fp32
+    [H,W] = 1 - F_p / C_p of the per-pixel sums (NaN where n_p < 3 or C_p = 0); `skill_scores` fp64 [G+1,4] in
+    SERIES_SKILL_KEYS order over the cells of the pixels with n >= 3 in that row; without it the three hold NaN.  The days are
+    worked through in chunks whose workspace stays within `max_workspace_bytes` (at least 32 days); the result does not depend
+    on the chunking, and two calls give bit-equal results."""
+    name = "series_ensemble_scores"
+    if ens.dim() != 4:
+        raise ValueError(f"ens: expected [D, M, H, W], got {tuple(ens.shape)}")
+    if obs.dim() != 3:
+        raise ValueError(f"obs: expected [D, H, W], got {tuple(obs.shape)}")
+    if not (ens.is_floating_point() and obs.is_floating_point()):
+        raise TypeError(f"{name}: ens and obs must be floating tensors, got {ens.dtype} and {obs.dtype}")
+    D, M, H, W = ens.shape
+    if not (2 <= H <= MAX_FIELD_SIDE and 2 <= W <= MAX_FIELD_SIDE) or H * W > MAX_FIELD_PIXELS:
+        raise ValueError(f"{name}: field size {H}x{W}; sides must be 2..{MAX_FIELD_SIDE} and H*W <= 2^20")
+    if not 1 <= D <= MAX_TEMPORAL_DAYS:
+        raise ValueError(f"{name}: D={D} days; need 1..{MAX_TEMPORAL_DAYS}")
+    if not 2 <= M <= MAX_SERIES_MEMBERS:
+        raise ValueError(f"{name}: M={M} members; need 2..{MAX_SERIES_MEMBERS}")
+    if tuple(obs.shape) != (D, H, W):
+        raise ValueError(f"obs: shape {tuple(obs.shape)} does not match ens days and fields {(D, H, W)}")
+    _shape_rows(mask, "mask", (H, W), (1, D))
+    if mask is not None and not (mask.dtype in (torch.uint8, torch.bool) or mask.is_floating_point()):
+        raise TypeError(f"mask: expected uint8, bool or float, got {mask.dtype}")
+    thr = list(thresholds)
+    if len(thr) > MAX_THRESHOLDS:
+        raise ValueError(f"{name}: {len(thr)} thresholds; at most {MAX_THRESHOLDS}")
+    tarr = _thresholds(thr, name) if thr else None
+    gids, G = _series_groups(groups, D)
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError(f"{name}: seed must be an integer, got {seed!r}")
+    N.require_device(ens, obs)
+    if obs.device != ens.device:
+        raise ValueError("ens and obs must be on the same device")
+    e = ens if ens.dtype == torch.float32 else ens.float()
+    HW = H * W
+    if e.stride(3) != 1 or e.stride(2) != W or e.stride(0) < HW or e.stride(1) < HW:
+        e = e.contiguous()
+    o = _fields(obs, "obs")
+    m, u8, nm = _mask(mask, HW, (1, D))
+    T, dev, clim = len(thr), e.device, bool(climatology)
+    g = None if gids is None else torch.tensor(gids, dtype=torch.int32, device=dev)
+    f64, i64 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int64, device=dev)
+    count = torch.empty(HW, dtype=torch.int32, device=dev)
+    maps = torch.empty(len(SERIES_MAP_KEYS), HW, device=dev)
+    daily, scores = torch.empty(D, len(ENSEMBLE_KEYS), **f64), torch.empty(G + 1, len(ENSEMBLE_KEYS), **f64)
+    rank_hist, table = torch.empty(G + 1, M + 1, **i64), torch.empty(G + 1, T, M + 1, 2, **i64)
+    exceedance = torch.empty(G + 1, len(EXCEEDANCE_KEYS), T, **f64)
+    clim_maps = torch.full((len(SERIES_CLIM_MAP_KEYS), HW), float("nan"), device=dev)
+    skill = torch.full((G + 1, len(SERIES_SKILL_KEYS)), float("nan"), **f64)
+    nbytes = N.lib().sbgm_series_scores_workspace_bytes(D, M, H, W, T, G, int(clim), max(int(max_workspace_bytes), 0))
+    ws = _ws(nbytes, dev)
+    N.check(N.lib().sbgm_series_scores(e.data_ptr(), e.stride(0), e.stride(1), o.data_ptr(), N.ptr(m), u8, nm, N.ptr(g), G, D, M, H, W,
+                                       tarr, T, seed & (2**64 - 1), int(clim), count.data_ptr(), maps.data_ptr(), daily.data_ptr(),
+                                       scores.data_ptr(), rank_hist.data_ptr(), table.data_ptr() if T else None,
+                                       exceedance.data_ptr() if T else None, clim_maps.data_ptr(), skill.data_ptr(), ws.data_ptr(),
+                                       nbytes, N.stream()))
+    out = dict(count=count.view(H, W), daily=daily, scores=scores, rank_hist=rank_hist, table=table, exceedance=exceedance,
+               skill_scores=skill)
+    out.update({k: maps[i].view(H, W) for i, k in enumerate(SERIES_MAP_KEYS)})
+    out.update({k: clim_maps[i].view(H, W) for i, k in enumerate(SERIES_CLIM_MAP_KEYS)})
     return out
