@@ -244,6 +244,23 @@ int sbgm_sampler_run_dpmpp(sbgm_model* m, const sbgm_sampler_args* a, float sigm
  * A run refuses a plan together with a->noise, a->tile_origins (tiled and joint runs) or a start state x0. */
 int sbgm_sampler_set_noise_rows(sbgm_model* m, const int32_t* rows, int stride, const float* weights, int lags);
 
+/* The same for tiled and joint runs (a->tile_origins): the domain noise plan.  All tiles of a batch are one field on one
+ * day, so ONE row R = *row_dev (device int32, used in place: a new value at the same address is read by a cached step graph's replays)
+ * serves the whole batch.  With dom_w4 = ceil(a->domain_w / 4) and Q = domain_h dom_w4 quads per domain, the draw with stream offset `off`
+ * at domain row Y, quad column X4 is
+ *     xi_k = the four Philox normals of (seed, off, counter (R - k s) Q + Y dom_w4 + X4),  k = 0 .. K-1     (64-bit unsigned arithmetic)
+ *     z    = w_0 xi_0 ;  z = z + w_k xi_k  in ascending k,  every product and every sum rounded to fp32 on its own,
+ * so R = 0 with K = 1, w = {1} is the tiled draw without a plan bit for bit, a single tile that covers the domain draws what
+ * sbgm_sampler_set_noise_rows with rows = {R} draws, and the copies of a domain pixel in overlapping tiles still receive one draw.
+ *   Held by the handle until cleared with row_dev = NULL; the two plans exclude each other (setting one while the other is held is an
+ *   error; clearing either clears the handle's plan).  1 <= lags <= 32, stride >= 1, domain_h >= 1; weights: host fp32 [lags], copied.
+ *   Used by sbgm_sampler_run, its _edm, _held, _joint and _dpmpp variants (a joint run's domain_h must equal the plan's).  A run reads the
+ *   tile table and the row back once (this waits for `stream`) and refuses a tile that does not lie quad-aligned inside domain_h x
+ *   a->domain_w (its counters would reach into another row's) or R < (K-1) s.  The captured step's key holds the row's address, domain_h,
+ *   stride, lags and the weights, not the row's value: two days of one geometry replay one step.
+ * Refused: no a->tile_origins, a->noise, sbgm_sampler_run_ode.  sbgm_randn_domain_rows is the draw as an op. */
+int sbgm_sampler_set_noise_domain_row(sbgm_model* m, const int32_t* row_dev, int domain_h, int stride, const float* weights, int lags);
+
 /* Conv autotuning: time the tile / split-K candidates of every convolution of the (B,H,W) plan once and keep the
  * fastest.  Synchronises the stream.  Optional; without it a static heuristic is used. */
 int sbgm_model_autotune(sbgm_model* m, int B, int H, int W, void* stream);
@@ -754,6 +771,12 @@ int sbgm_randn_scaled(float* x, float scale, uint64_t seed, uint64_t draw_index,
  * rows[b] and mixed over `lags` rows `stride` apart with `weights` (host fp32 [lags]).  per_sample % 4 == 0, 1 <= lags <= 32. */
 int sbgm_randn_rows(float* x, float scale, uint64_t seed, uint64_t draw_index, const int32_t* rows, int B, int64_t per_sample, int stride,
                     const float* weights, int lags, void* stream);
+/* The tiled draw under a domain noise plan (see sbgm_sampler_set_noise_domain_row): tiles [T][th][tw] = scale * z, tile t cut at
+ * origins[t] = (y0, x0) (device int32 [T][2], x0 % 4 == 0) out of the mixed draw of the domain row *row_dev (ONE device int32) over a
+ * domain of domain_h x domain_w (the padded width) pixels.  tw % 4 == 0, 1 <= lags <= 32; the origins and the row are read back and
+ * checked (every tile inside the domain, row >= (lags - 1) stride), which waits for `stream`. */
+int sbgm_randn_domain_rows(float* tiles, float scale, uint64_t seed, uint64_t draw_index, const int32_t* row_dev, const int32_t* origins,
+                           int T, int th, int tw, int domain_h, int domain_w, int stride, const float* weights, int lags, void* stream);
 int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, uint64_t draw_index, int64_t n, void* stream);
 int sbgm_edm_euler(const float* x_hat, const float* score, float* d, float* x_next, float sigma_hat, float sigma_next, int64_t n,
                    void* stream);

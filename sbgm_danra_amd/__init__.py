@@ -7,6 +7,6 @@ from .score_unet import (Decoder, DecoderBlock, Encoder, ImageSelfAttention, Sco
                          diffusion_coeff, diffusion_coeff_fn, loss_fn, marginal_prob_std, marginal_prob_std_fn)
 from .score_sampling import (Euler_Maruyama_sampler, dpmpp_2m_sampler, edm_heun_sampler, edm_sigma_schedule,  # noqa: F401
                              guided_score_fn, ode_sampler, pc_sampler, rk45_host_solve, rk45_sampler, temporal_noise,
-                             temporal_noise_acf, temporal_noise_weights)
+                             temporal_noise_acf, temporal_noise_domain, temporal_noise_weights)
 
 __version__ = "0.1.0"

@@ -91,6 +91,7 @@ SIGNATURES = {
     "sbgm_sampler_run_dpmpp": (_i, [_vp, C.POINTER(SamplerArgs), _f, _f, _f, _f, _f, _vp, _vp, _i, _i, _vp]),
     "sbgm_sampler_run_ode": (_i, [_vp, C.POINTER(SamplerArgs), _d, _d, _d, _d, _i, _i64, _vp, _vp, _vp, _vp]),
     "sbgm_sampler_set_noise_rows": (_i, [_vp, _vp, _i, C.POINTER(_f), _i]),
+    "sbgm_sampler_set_noise_domain_row": (_i, [_vp, _vp, _i, _i, C.POINTER(_f), _i]),
     "sbgm_pointwise_chain": (_i, [_vp, _vp, _i64, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     "sbgm_sample_extremes": (_i, [_vp, _i, _i64, _f, _vp, _vp, _vp]),
     "sbgm_assemble_conditions": (_i, [C.POINTER(AssembleArgs), _vp]),
@@ -226,6 +227,7 @@ SIGNATURES = {
     "sbgm_cfg_combine": (_i, [_vp, _vp, _vp, _f, _i64, _vp]),
     "sbgm_randn_scaled": (_i, [_vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_randn_rows": (_i, [_vp, _f, _u64, _u64, _vp, _i, _i64, _i, C.POINTER(_f), _i, _vp]),
+    "sbgm_randn_domain_rows": (_i, [_vp, _f, _u64, _u64, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _i, _vp]),
     "sbgm_edm_churn": (_i, [_vp, _vp, _f, _u64, _u64, _i64, _vp]),
     "sbgm_edm_euler": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i64, _vp]),
     "sbgm_edm_heun": (_i, [_vp, _vp, _vp, _f, _f, _i64, _vp]),
@@ -271,7 +273,7 @@ SIGNATURES = {
                            [_i64, _vp]),
 }
 
-ABI_VERSION = 16    # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 17    # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

@@ -33,7 +33,7 @@ const char* sbgm_get_error();
 extern "C" {
 
 const char* sbgm_last_error(void) { return sbgm_get_error(); }
-int sbgm_abi_version(void) { return 16; }
+int sbgm_abi_version(void) { return 17; }
 int sbgm_model_config_size(void) { return (int)sizeof(sbgm_model_config); }
 
 int sbgm_pack_input(const float* const* srcs, const int* src_channels, int n_src, float* dst_nhwc, int B, int H, int W,
@@ -503,6 +503,31 @@ int sbgm_randn_rows(float* x, float scale, uint64_t seed, uint64_t draw_index, c
                SBGM_NOISE_MAX_LAGS, lags, stride);
     return sbgm_launch_init_noise(x, scale, nullptr, seed, nullptr, draw_index, (size_t)B * (size_t)per_sample, ST,
                                   sbgm_noise_rows_map(rows, stride, lags, weights, (size_t)per_sample));
+}
+int sbgm_randn_domain_rows(float* tiles, float scale, uint64_t seed, uint64_t draw_index, const int32_t* row_dev, const int32_t* origins,
+                           int T, int th, int tw, int domain_h, int domain_w, int stride, const float* weights, int lags, void* stream) {
+    SBGM_CHECK(tiles && row_dev && origins && weights, "randn_domain_rows: tiles, row_dev, origins and weights are required");
+    SBGM_CHECK(T >= 1 && th >= 1 && tw >= 4 && tw % 4 == 0, "randn_domain_rows: need T >= 1, th >= 1 and tw a positive multiple of 4 (T=%d, "
+               "th=%d, tw=%d)", T, th, tw);
+    SBGM_CHECK(domain_h >= th && domain_w >= tw, "randn_domain_rows: the %d x %d domain is smaller than a %d x %d tile", domain_h, domain_w,
+               th, tw);
+    SBGM_CHECK(lags >= 1 && lags <= SBGM_NOISE_MAX_LAGS && stride >= 1, "randn_domain_rows: need 1 <= lags <= %d and stride >= 1 (lags=%d, "
+               "stride=%d)", SBGM_NOISE_MAX_LAGS, lags, stride);
+    // the tile table and the row are read back (this waits for the stream): a tile outside the domain would reach into another row's counters
+    std::vector<int> org(2 * (size_t)T);
+    int r = 0;
+    SBGM_HIP(hipMemcpyAsync(org.data(), origins, org.size() * sizeof(int), hipMemcpyDeviceToHost, ST));
+    SBGM_HIP(hipMemcpyAsync(&r, row_dev, sizeof(int), hipMemcpyDeviceToHost, ST));
+    SBGM_HIP(hipStreamSynchronize(ST));
+    for (int t = 0; t < T; ++t)
+        SBGM_CHECK(org[2 * t] >= 0 && org[2 * t + 1] >= 0 && org[2 * t + 1] % 4 == 0 && org[2 * t] + th <= domain_h &&
+                   org[2 * t + 1] + tw <= domain_w, "randn_domain_rows: tile %d at (%d, %d) of %d x %d does not lie quad-aligned inside the "
+                   "%d x %d domain", t, org[2 * t], org[2 * t + 1], th, tw, domain_h, domain_w);
+    SBGM_CHECK((long long)r >= (long long)(lags - 1) * stride, "randn_domain_rows: the row %d must be >= (lags - 1) * stride = %lld", r,
+               (long long)(lags - 1) * stride);
+    const NoiseMap tiled{origins, th, tw / 4, (domain_w + 3) / 4};
+    return sbgm_launch_init_noise(tiles, scale, nullptr, seed, nullptr, draw_index, (size_t)T * th * tw, ST,
+                                  sbgm_noise_domain_map(tiled, row_dev, domain_h, stride, lags, weights));
 }
 int sbgm_edm_churn(float* x, const float* z, float churn_coef, uint64_t seed, uint64_t draw_index, int64_t n, void* stream) {
     const EdmStep sc{0.f, 0.f, 0.f, 0.f, 0.f, churn_coef};

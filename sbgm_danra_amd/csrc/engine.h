@@ -193,7 +193,8 @@ struct StepGraphKey {
     const void *rows, *tbrun;                  // EM / PC runs that keep their time rows (null otherwise)
     const void* noise_rows;                    // runs with a noise plan (null otherwise): the launches hold the plan by value, so a run
     int noise_stride, noise_lags;              // with a plan and one without never share a graph, nor do two plans that differ in more
-    float noise_w[SBGM_NOISE_MAX_LAGS];        // than the contents of the rows table
+    int noise_domain_h;                        // than the contents of the rows table; > 0: the domain plan (the ONE row's value is read
+    float noise_w[SBGM_NOISE_MAX_LAGS];        // by every replay, so two days of one geometry replay the same step)
     size_t ws_bytes;
     float cfg, cfg_corr, snr_nn;
     unsigned long long plan_gen;
@@ -326,8 +327,9 @@ struct sbgm_model {
     size_t ws_bytes = 0, ws_used = 0;
     SamplerStore store;
     // The noise plan of the sampler runs to come (sbgm_sampler_set_noise_rows; kernels.h: NoiseMap): held until cleared, read by every
-    // sampler entry point.  rows == null: none.
-    struct NoiseRows { const int* rows = nullptr; int stride = 1, lags = 1; float w[SBGM_NOISE_MAX_LAGS] = {}; } noise_rows;
+    // sampler entry point.  rows == null: none.  domain_h > 0: the domain plan of tiled runs (sbgm_sampler_set_noise_domain_row): rows
+    // points to ONE row that serves all tiles of a domain of domain_h rows.  The handle holds one of the two plans or none.
+    struct NoiseRows { const int* rows = nullptr; int stride = 1, lags = 1, domain_h = 0; float w[SBGM_NOISE_MAX_LAGS] = {}; } noise_rows;
     ConvTileTable tuned;
     ConvTile last_tile{};                   // tile of the most recent conv() (tells the caller whether GroupNorm statistics were fused)
     bool tuning = false;

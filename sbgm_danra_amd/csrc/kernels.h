@@ -278,15 +278,18 @@ __host__ __device__ inline unsigned long long sampler_next_step(unsigned long lo
 // optional map from tile-local quads to domain-global Philox counters (null origins = plain element order)
 // ... and the optional noise plan ("row-keyed noise"): sample b draws as noise row r_b = rows[b] instead of as its
 // position in the batch, and its draw is the moving average z = sum_k w[k] xi(r_b - k stride) over `lags` white rows, every product and
-// sum rounded to fp32 on its own.  rows == null (the default) is the plain counter.  A plan and origins exclude each other.
+// sum rounded to fp32 on its own.  rows == null (the default) is the plain counter.
+// A plan WITH origins is the domain noise plan ("domain rows"): all tiles of the batch are one field on one day, so
+// `rows` points to ONE row R that serves every tile, per4 holds Q = domain_height * dom_w4, and the white draw of lag k at domain row Y,
+// quad column X4 has the counter (R - k stride) Q + Y dom_w4 + X4.  R = 0 with one lag of weight 1 is the tiled draw without a plan.
 constexpr int SBGM_NOISE_MAX_LAGS = 32;
 struct NoiseMap {
     const int* origins;   // device [B][2] = (y0, x0) of each tile in the domain, x0 % 4 == 0
     int tile_h, tile_w4;  // tile rows, tile width / 4
     int dom_w4;           // ceil(domain width / 4)
-    const int* rows;      // device [B]: the noise row of each sample, every one >= (lags - 1) * stride
+    const int* rows;      // device [B]: the noise row of each sample, every one >= (lags - 1) * stride; with origins: ONE row for all tiles
     int stride, lags;     // rows between two lags (>= 1), number of lags (1 .. SBGM_NOISE_MAX_LAGS)
-    unsigned long long per4;            // quads per sample, H W / 4
+    unsigned long long per4;            // quads per sample, H W / 4; with origins: quads per domain, domain_height * dom_w4
     float w[SBGM_NOISE_MAX_LAGS];       // the weights, by value
 };
 // nm with the plan (rows, stride, lags, weights) over samples of per_sample elements
@@ -295,6 +298,13 @@ inline NoiseMap sbgm_noise_rows_map(const int* rows, int stride, int lags, const
     nm.rows = rows; nm.stride = stride; nm.lags = lags; nm.per4 = per_sample / 4;
     for (int k = 0; k < lags && k < SBGM_NOISE_MAX_LAGS; ++k) nm.w[k] = w[k];
     return nm;
+}
+// the tile map `tiled` with the domain plan (one device row, stride, lags, weights) over a domain of domain_h rows
+inline NoiseMap sbgm_noise_domain_map(NoiseMap tiled, const int* row, int domain_h, int stride, int lags, const float* w) {
+    tiled.rows = row; tiled.stride = stride; tiled.lags = lags;
+    tiled.per4 = (unsigned long long)domain_h * (unsigned long long)tiled.dom_w4;
+    for (int k = 0; k < lags && k < SBGM_NOISE_MAX_LAGS; ++k) tiled.w[k] = w[k];
+    return tiled;
 }
 // Joint tiled sampling: the B samples are ALL T tiles of one domain, and every update kernel reads the score through the
 // partition-of-unity blend of the tiles' scores (tile_blend.h).  origins == null (the default) is the kernel without the blend.

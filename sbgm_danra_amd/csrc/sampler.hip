@@ -40,9 +40,18 @@ __device__ __forceinline__ float mix_lag(float z, float w, float x, bool first) 
 // z = w[0] xi_0, then z = z + w[k] xi_k in ascending k, xi_k = the white draw at counter (r - k stride) per4 + q in 64-bit unsigned
 // arithmetic.  Each product and sum is an fp32 operation of its own (no contraction), so a float32 loop over the white draws gives the
 // same bits.  The trip count is uniform over the launch and the loop stays a loop: one Philox state is live at a time.
+// With origins (the domain plan) the ONE row rows[0] serves every tile, per4 is the domain's quad count and q the quad's domain position.
 __device__ __forceinline__ f32x4 philox_rows_normal4(unsigned long long seed, unsigned long long off, const NoiseMap& m, size_t i) {
-    const unsigned long long b = i / m.per4, q = i - b * m.per4;
-    unsigned long long c = (unsigned long long)m.rows[b] * m.per4 + q;
+    unsigned long long r, q;
+    if (m.origins) {
+        r = (unsigned long long)m.rows[0];
+        q = noise_index(m, i);
+    } else {
+        const unsigned long long b = i / m.per4;
+        r = (unsigned long long)m.rows[b];
+        q = i - b * m.per4;
+    }
+    unsigned long long c = r * m.per4 + q;
     const unsigned long long back = (unsigned long long)m.stride * m.per4;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
@@ -398,13 +407,20 @@ inline int check_joint(const JointMap& jm, size_t n, const char* who) {
                who, jm.T, jm.tile_h, jm.tile_w, jm.R, n);
     return 0;
 }
-// a noise plan must describe exactly the launch's n elements (the kernel reads rows[quad / per4]) and is not composed with a tile map;
+// a noise plan must describe exactly the launch's n elements (the kernel reads rows[quad / per4]); with a tile map it is the domain plan
+// (the kernel reads rows[0] and origins[tile]): whole tiles, and a domain of whole quad rows that is at least a tile high;
 // checked on the map a kernel reads: `nm` for its own draw, `hold.nm` where it recomputes the run's draw 0 (edm_euler, edm_heun, dpmpp_2m)
 inline int check_noise(const NoiseMap& nm, size_t n, const char* who) {
     if (!nm.rows) return 0;
-    SBGM_CHECK(nm.origins == nullptr, "%s: noise rows and tile origins exclude each other", who);
     SBGM_CHECK(nm.lags >= 1 && nm.lags <= SBGM_NOISE_MAX_LAGS && nm.stride >= 1, "%s: noise rows need 1 <= lags <= %d and stride >= 1 "
                "(lags=%d, stride=%d)", who, SBGM_NOISE_MAX_LAGS, nm.lags, nm.stride);
+    if (nm.origins) {
+        SBGM_CHECK(nm.tile_h >= 1 && nm.tile_w4 >= 1 && nm.dom_w4 >= nm.tile_w4 && (n / 4) % ((size_t)nm.tile_h * nm.tile_w4) == 0 &&
+                   nm.per4 % (unsigned long long)nm.dom_w4 == 0 && nm.per4 >= (unsigned long long)nm.tile_h * nm.dom_w4,
+                   "%s: a domain noise row over %llu quads does not fit tiles of %d x %d quads in rows of %d quads (%zu elements)", who,
+                   nm.per4, nm.tile_h, nm.tile_w4, nm.dom_w4, n);
+        return 0;
+    }
     SBGM_CHECK(nm.per4 >= 1 && (n / 4) % nm.per4 == 0, "%s: noise rows over samples of %llu quads do not divide %zu elements", who, nm.per4, n);
     return 0;
 }

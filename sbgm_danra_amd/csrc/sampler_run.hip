@@ -416,7 +416,13 @@ struct SamplerRun {
         }
         if (plan && draws_noise) {
             SBGM_CHECK(per % 4 == 0, "%s: noise rows need H * W %% 4 == 0 (H=%d, W=%d)", who, H, W);
-            nm = sbgm_noise_rows_map(plan->rows, plan->stride, plan->lags, plan->w, per);
+            if (plan->domain_h > 0) {                       // the domain plan rides on the tile map set above (check_plan: origins given)
+                SBGM_CHECK(nm.origins != nullptr && plan->domain_h >= H, "%s: a domain noise row over %d rows needs tiles of at most that "
+                           "height (H=%d)", who, plan->domain_h, H);
+                nm = sbgm_noise_domain_map(nm, plan->rows, plan->domain_h, plan->stride, plan->lags, plan->w);
+            } else {
+                nm = sbgm_noise_rows_map(plan->rows, plan->stride, plan->lags, plan->w, per);
+            }
         }
         saved_ws = m->ws_bytes;
         m->ws_bytes -= keep();       // forward() must not touch the run's slabs
@@ -445,20 +451,47 @@ struct SamplerRun {
 };
 
 // A noise plan keys and mixes the in-kernel draws of independent samples: it is refused, not composed, where the run's noise is decided
-// otherwise (injected draws, domain-keyed tiles, a joint run)
-static int check_plan(const sbgm_model::NoiseRows* p, const sbgm_sampler_args& a, bool joint, const char* who) {
+// otherwise (injected draws, domain-keyed tiles, a joint run).  The domain plan (domain_h > 0) is the plan OF domain-keyed tiles: it needs
+// tile_origins, serves tiled and joint runs, and is not served by the ODE solver (`steps` false).
+static int check_plan(const sbgm_model::NoiseRows* p, const sbgm_sampler_args& a, bool joint, const char* who, bool steps = true) {
     if (!p) return 0;
     SBGM_CHECK(p->lags >= 1 && p->lags <= SBGM_NOISE_MAX_LAGS, "%s: noise rows need 1 <= lags <= %d, got %d", who, SBGM_NOISE_MAX_LAGS, p->lags);
     SBGM_CHECK(p->stride >= 1, "%s: noise row stride %d must be >= 1", who, p->stride);
     SBGM_CHECK(p->rows != nullptr, "%s: a noise plan needs its rows table", who);
     SBGM_CHECK(a.noise == nullptr, "%s: noise rows key the in-kernel noise; they cannot be combined with injected noise", who);
+    if (p->domain_h > 0) {
+        SBGM_CHECK(steps, "%s: a domain noise row is not served by the ODE solver", who);
+        SBGM_CHECK(a.tile_origins != nullptr, "%s: a domain noise row needs tile_origins (it is the row of all tiles of one domain)", who);
+        return 0;
+    }
     SBGM_CHECK(a.tile_origins == nullptr && !joint, "%s: noise rows and tile_origins (tiled or joint runs) exclude each other", who);
+    return 0;
+}
+
+// The tile table of a run that trusts it (a joint run's ramps, a domain plan's counters: a tile outside the domain would reach into the
+// counters of another row), read back once per call (a few bytes; this waits for the stream); `row`: the domain plan's device row, read
+// with it and checked against (lags - 1) * stride, or null
+static int check_origins(const sbgm_sampler_args& a, int domain_h, const int* row, int lags, int stride, const char* what, hipStream_t st) {
+    std::vector<int> org(2 * (size_t)a.B);
+    int r = 0;
+    SBGM_HIP(hipMemcpyAsync(org.data(), a.tile_origins, org.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (row) SBGM_HIP(hipMemcpyAsync(&r, row, sizeof(int), hipMemcpyDeviceToHost, st));
+    SBGM_HIP(hipStreamSynchronize(st));
+    for (int t = 0; t < a.B; ++t) {
+        const int y0 = org[2 * t], x0 = org[2 * t + 1];
+        SBGM_CHECK(y0 >= 0 && x0 >= 0 && x0 % 4 == 0 && y0 + a.H <= domain_h && x0 + a.W <= a.domain_w,
+                   "sampler: %s tile %d at (%d, %d) of %d x %d does not lie quad-aligned inside the %d x %d domain", what, t, y0, x0, a.H,
+                   a.W, domain_h, a.domain_w);
+    }
+    SBGM_CHECK(!row || (long long)r >= (long long)(lags - 1) * stride, "sampler: the domain noise row %d must be >= (lags - 1) * stride = %lld "
+               "(it would reach below row 0)", r, (long long)(lags - 1) * stride);
     return 0;
 }
 
 int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const EdmArgs* edm, const HeldArgs* held,
                         const JointArgs* joint, const DpmArgs* dpm, const NoiseRows* plan) {
     if (check_plan(plan, a, joint != nullptr, "sampler")) return 1;
+    const bool domain_plan = plan && plan->domain_h > 0;
     SBGM_CHECK(!held || (held->known && held->mask), "sampler: a constrained run needs both known and known_mask");
     if (joint) {
         SBGM_CHECK(a.tile_origins != nullptr, "sampler: a joint run needs tile_origins (its samples are the tiles of one domain)");
@@ -466,16 +499,14 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         SBGM_CHECK(!a.bn_train, "sampler: a joint run serves eval-mode BatchNorm only (bn_train must be 0)");
         SBGM_CHECK(joint->ramp_len >= 1, "sampler: joint ramp length %d must be >= 1", joint->ramp_len);
         SBGM_CHECK(a.B >= 1 && a.W >= 4 && a.W % 4 == 0, "sampler: a joint run needs B >= 1 and W %% 4 == 0 (B=%d, W=%d)", a.B, a.W);
-        // the tile table is read back once per call (a few bytes; this waits for the stream): the blend trusts it for the ramps
-        std::vector<int> org(2 * (size_t)a.B);
-        SBGM_HIP(hipMemcpyAsync(org.data(), a.tile_origins, org.size() * sizeof(int), hipMemcpyDeviceToHost, caller));
-        SBGM_HIP(hipStreamSynchronize(caller));
-        for (int t = 0; t < a.B; ++t) {
-            const int y0 = org[2 * t], x0 = org[2 * t + 1];
-            SBGM_CHECK(y0 >= 0 && x0 >= 0 && x0 % 4 == 0 && y0 + a.H <= joint->domain_h && x0 + a.W <= a.domain_w,
-                       "sampler: joint tile %d at (%d, %d) of %d x %d does not lie quad-aligned inside the %d x %d domain", t, y0, x0, a.H,
-                       a.W, joint->domain_h, a.domain_w);
-        }
+        SBGM_CHECK(!domain_plan || plan->domain_h == joint->domain_h, "sampler: the domain noise row is over %d rows, the joint run over %d",
+                   plan->domain_h, joint->domain_h);
+    }
+    if (joint || domain_plan) {
+        SBGM_CHECK(!domain_plan || (a.B >= 1 && a.W >= 4 && a.W % 4 == 0 && a.domain_w >= a.W), "sampler: a domain noise row needs B >= 1, "
+                   "W %% 4 == 0 and domain_w >= W (B=%d, W=%d, domain_w=%d)", a.B, a.W, a.domain_w);
+        if (check_origins(a, joint ? joint->domain_h : plan->domain_h, domain_plan ? plan->rows : nullptr, domain_plan ? plan->lags : 1,
+                          domain_plan ? plan->stride : 1, joint ? "joint" : "domain-row", caller)) return 1;
     }
     SBGM_CHECK(!(edm && dpm), "sampler: EDM Heun and 2M arguments exclude each other");
     // only sbgm_sampler_run_edm* pass EDM arguments, only sbgm_sampler_run_dpmpp passes 2M arguments
@@ -574,7 +605,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
         if (joint) { key.joint = 1; key.domain_h = joint->domain_h; key.ramp_len = joint->ramp_len; }
         key.rows = trows.rows; key.tbrun = trows.tbrun;
         if (plan) {                  // the rows' contents are read by every replay, like the conditions'; everything else is baked in
-            key.noise_rows = plan->rows; key.noise_stride = plan->stride; key.noise_lags = plan->lags;
+            key.noise_rows = plan->rows; key.noise_stride = plan->stride; key.noise_lags = plan->lags; key.noise_domain_h = plan->domain_h;
             std::copy(plan->w, plan->w + plan->lags, key.noise_w);
         }
         rc = run.capture(key, [&] { return step(false, false); });
@@ -597,7 +628,7 @@ int sbgm_model::sampler(const sbgm_sampler_args& a, hipStream_t caller, const Ed
 // waits for, so the device does not idle on the poll; an attempt that runs after done finds every controller frozen and changes
 // nothing.  It sets no route (set_routes).
 int sbgm_model::sampler_ode(const sbgm_sampler_args& a, hipStream_t caller, const OdeArgs& o, const NoiseRows* plan) {
-    if (check_plan(plan, a, false, "sampler_ode")) return 1;
+    if (check_plan(plan, a, false, "sampler_ode", false)) return 1;
     SBGM_CHECK(!(plan && o.x0), "sampler_ode: noise rows key the start draw; they cannot be combined with a start state x0");
     SBGM_CHECK(a.kind == SBGM_SAMPLER_RK45, "sampler_ode: kind %d is not SBGM_SAMPLER_RK45", a.kind);
     SBGM_CHECK(a.out != nullptr && o.stats_i != nullptr, "sampler_ode: out and stats_i are required");
@@ -742,8 +773,32 @@ int sbgm_sampler_set_noise_rows(sbgm_model* m, const int32_t* rows, int stride, 
     SBGM_CHECK(lags >= 1 && lags <= SBGM_NOISE_MAX_LAGS, "sampler_set_noise_rows: lags=%d must be in 1..%d", lags, SBGM_NOISE_MAX_LAGS);
     SBGM_CHECK(stride >= 1, "sampler_set_noise_rows: stride=%d must be >= 1", stride);
     SBGM_CHECK(weights != nullptr, "sampler_set_noise_rows: weights are required");
+    SBGM_CHECK(m->noise_rows.domain_h == 0, "sampler_set_noise_rows: the handle holds a domain noise row; the two plans exclude each other "
+               "(clear it with sbgm_sampler_set_noise_domain_row(m, NULL, ...))");
     sbgm_model::NoiseRows p;
     p.rows = rows; p.stride = stride; p.lags = lags;
+    std::copy(weights, weights + lags, p.w);
+    m->noise_rows = p;
+    return 0;
+}
+
+// The domain noise plan of the handle's tiled sampler runs: ONE device row for all tiles of a domain of domain_h rows (the row itself
+// stays the caller's and is read by the kernels, so a new value at the same address replays the same captured step).
+int sbgm_sampler_set_noise_domain_row(sbgm_model* m, const int32_t* row_dev, int domain_h, int stride, const float* weights, int lags) {
+    SBGM_CHECK(m, "sampler_set_noise_domain_row: null model");
+    if (row_dev == nullptr) {
+        SBGM_CHECK(lags <= 1, "sampler_set_noise_domain_row: %d lags need a row (a NULL row clears the plan)", lags);
+        m->noise_rows = sbgm_model::NoiseRows{};
+        return 0;
+    }
+    SBGM_CHECK(lags >= 1 && lags <= SBGM_NOISE_MAX_LAGS, "sampler_set_noise_domain_row: lags=%d must be in 1..%d", lags, SBGM_NOISE_MAX_LAGS);
+    SBGM_CHECK(stride >= 1, "sampler_set_noise_domain_row: stride=%d must be >= 1", stride);
+    SBGM_CHECK(domain_h >= 1, "sampler_set_noise_domain_row: domain_h=%d must be >= 1", domain_h);
+    SBGM_CHECK(weights != nullptr, "sampler_set_noise_domain_row: weights are required");
+    SBGM_CHECK(m->noise_rows.rows == nullptr || m->noise_rows.domain_h > 0, "sampler_set_noise_domain_row: the handle holds a rows plan; the "
+               "two plans exclude each other (clear it with sbgm_sampler_set_noise_rows(m, NULL, ...))");
+    sbgm_model::NoiseRows p;
+    p.rows = row_dev; p.stride = stride; p.lags = lags; p.domain_h = domain_h;
     std::copy(weights, weights + lags, p.w);
     m->noise_rows = p;
     return 0;

@@ -243,8 +243,92 @@ def _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, wh
     return rows, stride, w
 
 
+def _prep_noise_domain(noise_domain_row, domain_height, noise_weights, noise_row_stride, img_size, who, noise=None, tile_origins=None,
+                       joint_tiles=None, noise_rows=None):
+    """The domain noise plan of a tiled run as (row, stride, weights float32 numpy [K], domain_height), or None; every check needs the host
+    only (that the tiles lie inside the domain is checked by the native call, which reads the tile table)."""
+    if noise_domain_row is None:
+        if domain_height is not None:
+            raise ValueError(f"{who}: domain_height needs noise_domain_row (it is the height the domain noise row is drawn over)")
+        return None
+    if noise_rows is not None:
+        raise ValueError(f"{who}: noise_domain_row (one row for all tiles of a domain) and noise_rows (one row per sample) exclude each other")
+    if noise is not None:
+        raise ValueError(f"{who}: noise_domain_row keys and mixes the in-kernel noise; it cannot be combined with noise")
+    if tile_origins is None:
+        raise ValueError(f"{who}: noise_domain_row needs tile_origins (it is the noise row of all tiles of one domain)")
+    if isinstance(noise_domain_row, (bool, float)) or not isinstance(noise_domain_row, (int, np.integer)):
+        raise ValueError(f"{who}: noise_domain_row must be one integer (the row of the whole batch), got {noise_domain_row!r}")
+    row = int(noise_domain_row)
+    if domain_height is None and joint_tiles is not None:
+        domain_height = joint_tiles[0]
+    if domain_height is None or isinstance(domain_height, (bool, float)) or not isinstance(domain_height, (int, np.integer)):
+        raise ValueError(f"{who}: domain_height must be given with noise_domain_row as an integer (rows of the domain), got {domain_height!r}")
+    domain_height = int(domain_height)
+    if domain_height < int(img_size):
+        raise ValueError(f"{who}: domain_height={domain_height} must be >= img_size={int(img_size)} (every tile lies inside the domain)")
+    if joint_tiles is not None and int(joint_tiles[0]) != domain_height:
+        raise ValueError(f"{who}: domain_height={domain_height} differs from the joint run's domain height {int(joint_tiles[0])}")
+    w = noise_weights_f32([1.0] if noise_weights is None else noise_weights, f"{who}: noise_weights")
+    stride = int(noise_row_stride)
+    if stride < 1:
+        raise ValueError(f"{who}: noise_row_stride={noise_row_stride!r} must be >= 1")
+    if row < 0:
+        raise ValueError(f"{who}: noise_domain_row must be >= 0, got {row}")
+    if row < (w.size - 1) * stride:
+        raise ValueError(f"{who}: noise_domain_row must be >= (lags - 1) * noise_row_stride = {(w.size - 1) * stride} (row {row} would "
+                         f"reach below row 0)")
+    if row > 0x7FFFFFFF:
+        raise ValueError(f"{who}: noise_domain_row must fit int32, got {row}")
+    return row, stride, w, domain_height
+
+
+def _prep_noise_plan(noise_rows, noise_weights, noise_row_stride, batch_size, who, noise, tile_origins, joint_tiles, noise_domain_row,
+                     domain_height, img_size):
+    """The run's noise plan: the rows plan of `_prep_noise_rows` (3 entries), the domain plan of `_prep_noise_domain` (4), or None"""
+    domain = _prep_noise_domain(noise_domain_row, domain_height, noise_weights, noise_row_stride, img_size, who, noise, tile_origins,
+                                joint_tiles, noise_rows)
+    if domain is not None:
+        return domain
+    return _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, who, noise, tile_origins, joint_tiles)
+
+
 def _weights_arg(w):
     return (C.c_float * len(w))(*[float(v) for v in w])
+
+
+def temporal_noise_domain(seed, draw, row, origins, tile, domain_hw, weights=(1.0,), stride=1, scale=1.0, device="cuda"):
+    """scale * the mixed draw `draw` of the stream `seed` for the domain noise row `row`, cut into tiles: fp32 [T, tile, tile] on the
+    device, what a tiled sampler run with `tile_origins=origins, domain_width=domain_hw[1], noise_domain_row=row, domain_height=
+    domain_hw[0], noise_weights=weights, noise_row_stride=stride` uses as its draw `draw` (`sbgm_randn_domain_rows`).  `origins`:
+    T pairs (y0, x0), x0 % 4 == 0 (a sequence, or an int tensor [T, 2]); `domain_hw`: (height, padded width)."""
+    org = origins.detach().cpu().numpy() if torch.is_tensor(origins) else np.asarray(origins)
+    if org.ndim != 2 or org.shape[1] != 2 or org.shape[0] < 1 or org.dtype.kind not in "iu":
+        raise ValueError(f"temporal_noise_domain: origins must be T >= 1 integer pairs (y0, x0), got shape {tuple(org.shape)} of {org.dtype}")
+    org = org.astype(np.int64)
+    tile = int(tile)
+    if tile < 4 or tile % 4:
+        raise ValueError(f"temporal_noise_domain: tile={tile} must be a positive multiple of 4")
+    try:
+        dom_h, dom_w = (int(v) for v in domain_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"temporal_noise_domain: domain_hw must be (domain_height, domain_width), got {domain_hw!r}") from None
+    if dom_h < tile or dom_w < tile:
+        raise ValueError(f"temporal_noise_domain: domain_hw=({dom_h}, {dom_w}) must hold a tile of {tile} x {tile}")
+    if (org < 0).any() or (org[:, 1] % 4).any() or (org[:, 0] + tile > dom_h).any() or (org[:, 1] + tile > dom_w).any():
+        raise ValueError(f"temporal_noise_domain: origins must lie quad-aligned (x0 % 4 == 0) with their tiles inside the {dom_h} x {dom_w} "
+                         f"domain, got {org.tolist()}")
+    row, stride, w, _ = _prep_noise_domain(row, dom_h, weights, stride, tile, "temporal_noise_domain", tile_origins=org)
+    dev = torch.device(device) if not isinstance(device, torch.device) else device
+    if dev.type != "cuda":
+        raise N.NativeError(f"temporal_noise_domain runs on a ROCm device, got device={device!r}")
+    with torch.cuda.device(dev):
+        r_dev = torch.tensor([row], dtype=torch.int32, device=dev)
+        o_dev = torch.from_numpy(org.astype(np.int32)).to(dev).contiguous()
+        x = torch.empty(org.shape[0], tile, tile, device=dev)
+        N.check(N.lib().sbgm_randn_domain_rows(x.data_ptr(), float(scale), int(seed), int(draw), r_dev.data_ptr(), o_dev.data_ptr(),
+                                               org.shape[0], tile, tile, dom_h, dom_w, stride, _weights_arg(w), len(w), N.stream()))
+    return x
 
 
 def temporal_noise(seed, draw, rows, per_sample, weights=(1.0,), stride=1, device="cuda", scale=1.0):
@@ -276,11 +360,19 @@ class _noise_plan:
     def __enter__(self):
         if self.plan is None:
             return self
-        rows, stride, w = self.plan
         bufs = getattr(self.eng, "_noise_rows", None)
         if bufs is None:
             bufs = self.eng._noise_rows = {}
         index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()     # "cuda" is the current device
+        if len(self.plan) == 4:                          # the domain plan: ONE row at one address, whatever the day and the batch
+            row, stride, w, domain_h = self.plan
+            buf = bufs.get((index, "domain"))
+            if buf is None:
+                buf = bufs[(index, "domain")] = torch.empty(1, dtype=torch.int32, device=torch.device("cuda", index))
+            buf.copy_(torch.tensor([row], dtype=torch.int32))
+            N.check(self.eng.lib.sbgm_sampler_set_noise_domain_row(self.eng.h, buf.data_ptr(), domain_h, stride, _weights_arg(w), len(w)))
+            return self
+        rows, stride, w = self.plan
         buf = bufs.get((index, rows.size))
         if buf is None:
             buf = bufs[(index, rows.size)] = torch.empty(rows.size, dtype=torch.int32, device=torch.device("cuda", index))
@@ -373,13 +465,16 @@ def _host_start(kind, batch_size, num_steps, img_size, device, noise, seed, scal
 def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=500, device="cuda",
                            eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
                            noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None,
-                           joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1):
+                           joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1, noise_domain_row=None,
+                           domain_height=None):
     """Euler-Maruyama reverse-SDE sampler (reference score_sampling.py:63-127).  Returns the last `mean_x`.
     `known` / `known_mask` (not in the reference): hold the masked pixels at `known`, see `pc_sampler`; `joint_tiles`: see `pc_sampler`;
-    `noise_rows` / `noise_weights` / `noise_row_stride` (row-keyed, temporally correlated noise): see `pc_sampler`."""
+    `noise_rows` / `noise_weights` / `noise_row_stride` (row-keyed, temporally correlated noise) and `noise_domain_row` /
+    `domain_height` (the same for tiled runs): see `pc_sampler`."""
     seed = _fresh_seed() if seed is None else seed
     joint = _prep_joint(joint_tiles, tile_origins, noise, "Euler_Maruyama_sampler")
-    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "Euler_Maruyama_sampler", noise, tile_origins, joint_tiles)
+    plan = _prep_noise_plan(noise_rows, noise_weights, noise_row_stride, batch_size, "Euler_Maruyama_sampler", noise, tile_origins, joint_tiles,
+                            noise_domain_row, domain_height, img_size)
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "Euler_Maruyama_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_EM, score_model, batch_size, num_steps, 0.0, eps, img_size, y, cond_img, lsm_cond,
@@ -411,7 +506,7 @@ def Euler_Maruyama_sampler(score_model, marginal_prob_std, diffusion_coeff, batc
 def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=800, snr=signal_to_noise_ratio,
                device="cuda", eps=1e-3, img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *,
                noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0, known=None, known_mask=None,
-               joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1):
+               joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1, noise_domain_row=None, domain_height=None):
     """Predictor-corrector sampler: Langevin corrector with the batch-mean gradient norm, then an Euler-Maruyama
     predictor (reference score_sampling.py:136-230).  Returns the last `x_mean`.
 
@@ -437,10 +532,19 @@ def pc_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, n
     correlated with `temporal_noise_acf(noise_weights)[j]`, and a sample's noise depends on (seed, row) only, not on its place in the
     batch (this sampler's Langevin step size still uses the batch-mean score norm).  Rows 0..B-1 with the default weights reproduce the
     run without the arguments bit for bit.  Needs the native loop; refused (ValueError) with `noise`, `tile_origins` or `joint_tiles`;
-    composes with `known` / `known_mask` and guidance.  `temporal_noise_weights(rho, lags)` makes AR(1)-like weights."""
+    composes with `known` / `known_mask` and guidance.  `temporal_noise_weights(rho, lags)` makes AR(1)-like weights.
+
+    The same for a tiled or joint run: `noise_domain_row=R` (one int: all tiles of the batch are one field on one
+    day) with `domain_height`, `tile_origins`, `domain_width` and the same `noise_weights` / `noise_row_stride`.  The white draw of lag k
+    at domain row Y, quad column X4 has the counter (R - k stride) Q + Y dom_w4 + X4, Q = domain_height * ceil(domain_width / 4): R = 0
+    with the default weights is the tiled run without the arguments bit for bit, one tile that covers the domain draws what
+    `noise_rows=[R]` draws, and the copies of a domain pixel still share their draw.  Every tile must lie inside domain_height x
+    domain_width (checked by the native call).  Refused (ValueError) with `noise_rows`, `noise`, or without `tile_origins`;
+    `FullDomainTiler.sample(noise_row=...)` and `.sample_series` set it up; `temporal_noise_domain` is the draw itself."""
     seed = _fresh_seed() if seed is None else seed
     joint = _prep_joint(joint_tiles, tile_origins, noise, "pc_sampler")
-    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "pc_sampler", noise, tile_origins, joint_tiles)
+    plan = _prep_noise_plan(noise_rows, noise_weights, noise_row_stride, batch_size, "pc_sampler", noise, tile_origins, joint_tiles,
+                            noise_domain_row, domain_height, img_size)
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "pc_sampler")
     if isinstance(score_model, ScoreNet) and not (_cfg_enabled(cfg) and score_model.training):
         return _native_run(N.SAMPLER_PC, score_model, batch_size, num_steps, snr, eps, img_size, y, cond_img, lsm_cond,
@@ -592,7 +696,7 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
                      img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, sigma_min=None, sigma_max=None,
                      rho=7.0, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, noise=None, use_graph=True, seed=None,
                      tile_origins=None, domain_width=0, known=None, known_mask=None, joint_tiles=None, noise_rows=None,
-                     noise_weights=None, noise_row_stride=1):
+                     noise_weights=None, noise_row_stride=1, noise_domain_row=None, domain_height=None):
     """Heun (2nd-order) solver of the probability-flow ODE dx/dsigma = -sigma * score on the Karras sigma ladder, with optional
     stochastic churn (Karras et al. 2022, Alg. 2); works with the VE-SDE score network as trained.  `num_steps` N costs 2N-1
     network evaluations (18-64 is the intended range).  Conditions, guidance (`cfg`: both evaluations of a step use
@@ -600,7 +704,8 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     `tile_origins` behave as in `pc_sampler`.  `diffusion_coeff` is accepted for signature compatibility and unused.
     `known` / `known_mask` as in `pc_sampler`; here a held pixel follows known + sigma * (draw 0), the exact trajectory of a point mass,
     so the sampler stays deterministic in its seed.  `joint_tiles` as in `pc_sampler`: both slopes of a step use the blended score.
-    `noise_rows` / `noise_weights` / `noise_row_stride` as in `pc_sampler`: the start, the churn and the held pixels' draw 0 are mixed.
+    `noise_rows` / `noise_weights` / `noise_row_stride` as in `pc_sampler`: the start, the churn and the held pixels' draw 0 are mixed;
+    `noise_domain_row` / `domain_height` (the plan of a tiled run) as in `pc_sampler`.
     Returns x after the last step, [B,1,H,W] (no noise added at the end).  Sample quality against `pc_sampler` at 1000 steps
     has not been measured."""
     sig = float(score_model.sigma) if isinstance(score_model, ScoreNet) else _sigma_of(marginal_prob_std)
@@ -608,7 +713,8 @@ def edm_heun_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     seed = _fresh_seed() if seed is None else seed
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "edm_heun_sampler")
     joint = _prep_joint(joint_tiles, tile_origins, noise, "edm_heun_sampler")
-    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "edm_heun_sampler", noise, tile_origins, joint_tiles)
+    plan = _prep_noise_plan(noise_rows, noise_weights, noise_row_stride, batch_size, "edm_heun_sampler", noise, tile_origins, joint_tiles,
+                            noise_domain_row, domain_height, img_size)
     if isinstance(score_model, ScoreNet) and not score_model.training:
         edm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
                     float(s_churn), float(s_tmin), float(s_tmax), float(s_noise))
@@ -685,7 +791,8 @@ def dpm_sampler_kwargs(cfg) -> dict:
 def dpmpp_2m_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=64, num_steps=32, device="cuda", eps=1e-3,
                      img_size=64, y=None, cond_img=None, lsm_cond=None, topo_cond=None, cfg=None, *, sigma_min=None, sigma_max=None,
                      rho=7.0, eta=0.0, s_noise=1.0, noise=None, use_graph=True, seed=None, tile_origins=None, domain_width=0,
-                     known=None, known_mask=None, joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1):
+                     known=None, known_mask=None, joint_tiles=None, noise_rows=None, noise_weights=None, noise_row_stride=1,
+                     noise_domain_row=None, domain_height=None):
     """DPM-Solver++(2M) (Lu et al. 2022) on the Karras sigma ladder of `edm_heun_sampler`: a second-order multistep solver that reuses the
     previous step's denoised estimate, so `num_steps` N costs exactly N network evaluations (EDM Heun: 2N-1).  `eta = 0` is the
     deterministic solver of the probability-flow ODE; `eta > 0` is the SDE variant ("2M SDE", midpoint form), which adds noise of weight
@@ -694,7 +801,8 @@ def dpmpp_2m_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     step i.  `diffusion_coeff` is accepted for signature compatibility and unused.
     `known` / `known_mask` as in `pc_sampler`: after every step the held pixels are known + sigma_{i+1} z, with z the run's draw 0 when
     eta = 0 (the trajectory of a point mass, as in `edm_heun_sampler`: deterministic in the seed) and the step's own draw when eta > 0.
-    `noise_rows` / `noise_weights` / `noise_row_stride` as in `pc_sampler` (the start, and with eta > 0 every step's draw).
+    `noise_rows` / `noise_weights` / `noise_row_stride` as in `pc_sampler` (the start, and with eta > 0 every step's draw);
+    `noise_domain_row` / `domain_height` (the plan of a tiled run) as in `pc_sampler`.
     An eval-mode ScoreNet runs the native loop (`sbgm_sampler_run_dpmpp`); any other callable runs a Python loop over the same update
     kernel.  Returns x after the last step, [B,1,H,W].  On the analytic Gaussian problem it has the error of EDM Heun at the same N;
     sample quality on a trained checkpoint has not been measured."""
@@ -703,7 +811,8 @@ def dpmpp_2m_sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size
     seed = _fresh_seed() if seed is None else seed
     known, known_mask = _prep_known(known, known_mask, batch_size, img_size, device, "dpmpp_2m_sampler")
     joint = _prep_joint(joint_tiles, tile_origins, noise, "dpmpp_2m_sampler")
-    plan = _prep_noise_rows(noise_rows, noise_weights, noise_row_stride, batch_size, "dpmpp_2m_sampler", noise, tile_origins, joint_tiles)
+    plan = _prep_noise_plan(noise_rows, noise_weights, noise_row_stride, batch_size, "dpmpp_2m_sampler", noise, tile_origins, joint_tiles,
+                            noise_domain_row, domain_height, img_size)
     if isinstance(score_model, ScoreNet) and not score_model.training:
         dpm_args = (0.0 if sigma_min is None else sch["sigma_min"], 0.0 if sigma_max is None else sch["sigma_max"], float(rho),
                     float(eta), float(s_noise))

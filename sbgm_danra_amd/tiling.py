@@ -20,6 +20,10 @@ Joint sampling (`sample(..., joint=True)`): ONE diffusion over th
 tiles run as one batch and every update kernel reads the stitch-weighted blend of the tiles' scores (`joint_tiles` of the samplers),
 so all copies of a domain pixel stay bit-equal through the run and the stitch has nothing left to average: no band of smoother
 texture over the overlaps.  One rank, one batch; `pc_sampler` then uses the batch-mean Langevin step size over the tiles.
+
+Series (`sample(..., noise_row=)`, `sample_series`): the domain noise plan keys the domain-keyed noise by a noise
+row as well (one row for all tiles: they are one field on one day) and mixes it over the preceding rows, so the fields of consecutive
+days are correlated as the weights say and a day's field depends on (seed, day, member) alone.
 """
 from __future__ import annotations
 
@@ -67,6 +71,7 @@ class FullDomainTiler:
         xs = self._x_origins()
         self.origins = [(y, x) for y in ys for x in xs]
         self.origins_dev = torch.tensor(self.origins, dtype=torch.int32, device=self.device).contiguous()
+        self._origin_tables = {}
 
     def _x_origins(self):
         # x origins must be multiples of 4 (noise quads).  The last tile has to end at the domain edge, so when
@@ -76,6 +81,14 @@ class FullDomainTiler:
 
     def __len__(self):
         return len(self.origins)
+
+    def _origins_of(self, idx):
+        """the origins of the tiles `idx` as one device table, kept per batch: the captured step's key holds its address, so the days of
+        a series replay one step instead of capturing one each"""
+        key = tuple(int(i) for i in idx)
+        if key not in self._origin_tables:
+            self._origin_tables[key] = self.origins_dev[list(key)].contiguous()
+        return self._origin_tables[key]
 
     def _pad(self, dom):
         """[C, Hd, Wd] -> [C, Hd, Wd_pad], right edge replicated (only when Wd - tile is not a multiple of 4)"""
@@ -111,7 +124,7 @@ class FullDomainTiler:
 
     def sample(self, score_model, sampler, marginal_prob_std, diffusion_coeff, num_steps, cond_img=None, lsm_cond=None,
                topo_cond=None, y=None, seed=None, tiles_per_batch=None, known=None, known_mask=None, joint=False,
-               **sampler_kw) -> torch.Tensor:
+               noise_row=None, noise_weights=None, noise_row_stride=1, **sampler_kw) -> torch.Tensor:
         """Sample the whole domain: cond_img [C,Hd,Wd] / lsm_cond, topo_cond [2,Hd,Wd] / y scalar class -> [1,Hd,Wd].
         Tiles are sharded over the ranks of the process group (if any) and, per rank, run in batches of
         `tiles_per_batch`; every batch shares `seed`, so the domain-keyed noise is identical wherever tiles overlap.
@@ -119,10 +132,26 @@ class FullDomainTiler:
         the sampler; after the stitch the hold is applied once more against the domain fields, so the result equals `known` on the
         mask bit for bit and not just to the rounding of the blend.
         `joint=True`: one diffusion over the domain (the sampler's `joint_tiles`): all tiles in one batch on one rank, the tiles'
-        scores blended at every step, so the tiles agree bit for bit wherever they overlap and the stitch only assembles them."""
+        scores blended at every step, so the tiles agree bit for bit wherever they overlap and the stitch only assembles them.
+        `noise_row` (int), `noise_weights`, `noise_row_stride`: the domain noise plan (the samplers' `noise_domain_row` with
+        `domain_height = Hd`): the field is drawn as noise row `noise_row` of the stream `seed`, mixed over the rows
+        `noise_row - k * noise_row_stride` with the weights, whatever `tiles_per_batch` and `joint` are.  `sample_series` uses it."""
         import inspect
-        from .score_sampling import _fresh_seed
+        from .score_sampling import _fresh_seed, _prep_noise_domain
         _, world = parallel.world()
+        if noise_row is None:
+            if noise_weights is not None or int(noise_row_stride) != 1:
+                raise ValueError("FullDomainTiler.sample: noise_weights and noise_row_stride need noise_row (the row they mix)")
+        else:
+            if "noise_domain_row" not in inspect.signature(sampler).parameters:
+                raise ValueError(f"FullDomainTiler.sample: {getattr(sampler, '__name__', sampler)} does not take noise_row (a domain noise "
+                                 "plan is served by the step samplers)")
+            try:                                         # every host check before the first batch, under the tiler's argument name
+                _prep_noise_domain(noise_row, self.Hd, noise_weights, noise_row_stride, self.tile, "FullDomainTiler.sample", tile_origins=True)
+            except ValueError as e:
+                raise ValueError(str(e).replace("noise_domain_row", "noise_row")) from None
+            sampler_kw = dict(sampler_kw, noise_domain_row=int(noise_row), domain_height=self.Hd, noise_weights=noise_weights,
+                              noise_row_stride=noise_row_stride)
         if joint:
             if "joint_tiles" not in inspect.signature(sampler).parameters:
                 raise ValueError(f"FullDomainTiler.sample: {getattr(sampler, '__name__', sampler)} does not take joint_tiles (the per-sample "
@@ -157,7 +186,7 @@ class FullDomainTiler:
             steps = {} if num_steps is None else {"num_steps": num_steps}      # None: an adaptive sampler (rk45_sampler) has no step count
             return sampler(score_model, marginal_prob_std, diffusion_coeff, batch_size=len(idx), **steps,
                            device=self.device, img_size=self.tile, y=yb, cond_img=cut(cond_img), lsm_cond=cut(lsm_cond),
-                           topo_cond=cut(topo_cond), seed=seed, tile_origins=self.origins_dev[idx].contiguous(),
+                           topo_cond=cut(topo_cond), seed=seed, tile_origins=self._origins_of(idx),
                            domain_width=self.Wd_pad, **{k: cut(f) for k, f in held.items()}, **sampler_kw)
         out = sample_tiles_sharded(len(self), run_batch, (1, self.tile, self.tile), self.device, tiles_per_batch)
         dom = self.stitch(out)
@@ -165,6 +194,52 @@ class FullDomainTiler:
             m = known_mask.clamp(0.0, 1.0)
             dom = torch.where(m <= 0, dom, torch.where(m >= 1, known, (1.0 - m) * dom + m * known))
         return dom
+
+    def sample_series(self, score_model, sampler, marginal_prob_std, diffusion_coeff, num_steps, cond_img=None, lsm_cond=None,
+                      topo_cond=None, y=None, members=1, seed=None, temporal_noise_weights=None, first_day=0, days=None,
+                      tiles_per_batch=None, known=None, known_mask=None, joint=False, **sampler_kw) -> torch.Tensor:
+        """A series of full-domain fields: cond_img [D,C,Hd,Wd] (one condition per day; or None with `days=D`) -> [D, members, Hd, Wd].
+        The whole series runs under ONE `seed`, and member m of day d is drawn as the domain noise row (first_day + d + K - 1) * members
+        + m with stride `members` (K = len(temporal_noise_weights), default [1.0]: white in time), the row convention of the cutout
+        series (`generate_series`): consecutive days of a member share K - 1 white rows and correlate with `temporal_noise_acf(w)[1]`,
+        members are independent, and a day's field depends on (seed, first_day + d, m) only, not on the call that made it, so a series
+        can be extended (`first_day`) or one day regenerated.  `lsm_cond`, `topo_cond` [2,Hd,Wd] and a scalar `y` are shared by the
+        days; `y` may also hold D classes, `known` / `known_mask` [1,Hd,Wd] are shared or [D,1,Hd,Wd] per day; `joint`,
+        `tiles_per_batch` and the sampler's keywords act as in `sample`."""
+        from .score_sampling import _fresh_seed, noise_weights_f32
+        members, first_day = int(members), int(first_day)
+        if members < 1:
+            raise ValueError(f"FullDomainTiler.sample_series: members={members} must be >= 1")
+        if first_day < 0:
+            raise ValueError(f"FullDomainTiler.sample_series: first_day={first_day} must be >= 0")
+        if cond_img is not None:
+            if cond_img.dim() != 4 or (days is not None and int(days) != cond_img.shape[0]):
+                raise ValueError(f"FullDomainTiler.sample_series: cond_img {tuple(cond_img.shape)} must be [days, C, {self.Hd}, {self.Wd}]"
+                                 + ("" if days is None else f" with days={days}"))
+            days = cond_img.shape[0]
+        if days is None or int(days) < 1:
+            raise ValueError(f"FullDomainTiler.sample_series: days={days!r} must be >= 1 (or given through cond_img [days, C, Hd, Wd])")
+        days = int(days)
+        w = noise_weights_f32([1.0] if temporal_noise_weights is None else temporal_noise_weights,
+                              "FullDomainTiler.sample_series: temporal_noise_weights")
+        last = (first_day + days - 1 + w.size - 1) * members + members - 1
+        if last > 0x7FFFFFFF:
+            raise ValueError(f"FullDomainTiler.sample_series: first_day={first_day} puts the last noise row at {last}, beyond int32")
+        known, known_mask = (None if f is None else torch.as_tensor(f) for f in (known, known_mask))
+        per_day = lambda f, d, lead: None if f is None else (f[d] if f.dim() == lead + 1 else f)   # noqa: E731
+        if y is not None and not isinstance(y, int) and len(y) != days:
+            raise ValueError(f"FullDomainTiler.sample_series: y must be one class or {days} classes, got {len(y)}")
+        seed = _fresh_seed() if seed is None else seed
+        out = torch.empty(days, members, self.Hd, self.Wd, device=self.device)
+        for d in range(days):
+            for m in range(members):
+                out[d, m] = self.sample(score_model, sampler, marginal_prob_std, diffusion_coeff, num_steps,
+                                        cond_img=None if cond_img is None else cond_img[d], lsm_cond=lsm_cond, topo_cond=topo_cond,
+                                        y=y if y is None or isinstance(y, int) else int(y[d]), seed=seed, tiles_per_batch=tiles_per_batch,
+                                        known=per_day(known, d, 3), known_mask=per_day(known_mask, d, 3), joint=joint,
+                                        noise_row=(first_day + d + w.size - 1) * members + m, noise_weights=w, noise_row_stride=members,
+                                        **sampler_kw)[0]
+        return out
 
 
 def sample_tiles_sharded(n_tiles: int, run_batch, tile_shape, device, tiles_per_batch=None) -> torch.Tensor:
