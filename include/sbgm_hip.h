@@ -1110,6 +1110,14 @@ int sbgm_assemble_conditions(const sbgm_assemble_args* a, void* stream);
  * written as 16-byte vectors when w % 4 == 0 and every dst is 16-byte aligned.  A sample whose item or origin lies outside its stack
  * is filled with NaN.
  *
+ * sbgm_domain_gather: the whole Hd x Wd domain of B days, right-padded to Wp columns for the full-domain tiler:
+ * dst[f][b][0][y][x] = program_f(src[f][item][y][min(x, Wd - 1)]) for 0 <= y < Hd, 0 <= x < Wp, every field in ONE launch.  srcs, dsts,
+ * n_items, programs (with is_mask) and items are those of sbgm_cutout_gather; each dst is [B][1][Hd][Wp].  The column is clamped before
+ * the program runs; the program is pointwise, so the result is the replicate pad of the transformed field.  Wp >= Wd and Wp % 4 == 0
+ * (any pad width, Wp - Wd >= 4 included) and every dst 16-byte aligned: dst rows are written as 16-byte vectors throughout.  Source
+ * rows are Wd floats of any alignment, read as dwords at clamped columns, so no load reaches past its row.  A sample whose item lies
+ * outside its stack is filled with NaN.
+ *
  * sbgm_sdf_from_mask: generate_sdf + normalize_sdf (data_modules.py:93-118) of mask [B][h][w] (land = mask > 0), per sample:
  * D2 = the EXACT squared Euclidean distance in pixels to the nearest land pixel (0 on land; integer arithmetic, no search window),
  * raw = 10 land - sqrt(D2), sdf = (raw - min raw) / (max raw - min raw), sqrt and normalisation in fp64 per pixel, rounded once to fp32.
@@ -1124,6 +1132,8 @@ int sbgm_cutout_draw(uint64_t seed, uint64_t draw, int B, const int* rect, int h
 int sbgm_cutout_program_init(int32_t* words_host, int n_ops, const int* ops, const float* consts, int is_mask);
 int sbgm_cutout_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const int32_t* programs,
                        const int* items, const int* origins, int B, int Hd, int Wd, int h, int w, void* stream);
+int sbgm_domain_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const int32_t* programs,
+                       const int* items, int B, int Hd, int Wd, int Wp, void* stream);
 int64_t sbgm_sdf_workspace_bytes(int B, int h, int w);
 int sbgm_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, int B, int h, int w, void* stream);
 

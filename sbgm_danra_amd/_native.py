@@ -98,6 +98,7 @@ SIGNATURES = {
     "sbgm_cutout_draw": (_i, [_u64, _u64, _i, C.POINTER(C.c_int), _i, _i, _i, _i, _vp, _vp]),
     "sbgm_cutout_program_init": (_i, [C.POINTER(C.c_int32), _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _i]),
     "sbgm_cutout_gather": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sbgm_domain_gather": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sbgm_sdf_workspace_bytes": (_i64, [_i, _i, _i]),
     "sbgm_sdf_from_mask": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sbgm_depth_to_space2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
@@ -273,7 +274,7 @@ SIGNATURES = {
                            [_i64, _vp]),
 }
 
-ABI_VERSION = 17    # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 18    # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

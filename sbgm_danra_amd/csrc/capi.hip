@@ -33,7 +33,7 @@ const char* sbgm_get_error();
 extern "C" {
 
 const char* sbgm_last_error(void) { return sbgm_get_error(); }
-int sbgm_abi_version(void) { return 17; }
+int sbgm_abi_version(void) { return 18; }
 int sbgm_model_config_size(void) { return (int)sizeof(sbgm_model_config); }
 
 int sbgm_pack_input(const float* const* srcs, const int* src_channels, int n_src, float* dst_nhwc, int B, int H, int W,
@@ -338,6 +338,11 @@ int sbgm_cutout_gather(const float* const* srcs, float* const* dsts, const int* 
                        const int* items, const int* origins, int B, int Hd, int Wd, int h, int w, void* stream) {
     return sbgm_launch_cutout_gather(srcs, dsts, n_items, n_fields, reinterpret_cast<const CutoutProgram*>(programs), items, origins, B, Hd,
                                      Wd, h, w, ST);
+}
+int sbgm_domain_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const int32_t* programs,
+                       const int* items, int B, int Hd, int Wd, int Wp, void* stream) {
+    return sbgm_launch_domain_gather(srcs, dsts, n_items, n_fields, reinterpret_cast<const CutoutProgram*>(programs), items, B, Hd, Wd, Wp,
+                                     ST);
 }
 int64_t sbgm_sdf_workspace_bytes(int B, int h, int w) { return (int64_t)sbgm_sdf_ws_bytes(B, h, w); }
 int sbgm_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, int B, int h, int w, void* stream) {

@@ -8,6 +8,10 @@
 //     item_b = 0 for the static planes; a field flagged "mask" is then binarised to v > 0.5 ? 1 : 0 (data_modules.py:874, :909).  x0 is
 //     arbitrary, so a source row has no alignment: it is read as dwords (a wave's four loads cover the same cache lines), the output
 //     row is written as f32x4 when w % 4 == 0.  A sample whose item or origin lies outside its stack gets NaN, never a wild read.
+// K49b domain_gather_kernel  — the whole domain of a batch of days, right-padded for the tiler: out[f][b][0][y][x] =
+//     program_f(src_f[item_b][y][min(x, Wd - 1)]), 0 <= x < Wp, Wp % 4 == 0.  The column is clamped BEFORE the program (the program is
+//     pointwise, so this is the replicate pad of the transformed field).  A thread owns one output quad: four dword loads at clamped
+//     columns (source rows of Wd floats have no alignment, and no load reaches past its row, let alone the plane), one f32x4 store.
 // K50 sdf_* (three launches) — generate_sdf + normalize_sdf (data_modules.py:93-118) with an exact Euclidean distance transform:
 //     columns:   g(y, x) = distance along the column to the nearest land pixel (two sweeps; SDF_FAR when the column has none)
 //     rows:      D2(y, x) = min_x' (x - x')^2 + g(y, x')^2, the row of g held in LDS.  The search walks outwards from x and stops when
@@ -87,6 +91,43 @@ __global__ __launch_bounds__(256) void cutout_gather_kernel(GatherArgs a, const 
             const int y = (int)(i / a.w), x = (int)(i % a.w);
             dst[i] = inside ? gather_value(src[(size_t)y * a.Wd + x], p, is_mask) : nanv;
         }
+    }
+}
+
+struct DomainGatherArgs {
+    const float* src[SBGM_CUTOUT_MAX_FIELDS];
+    float* dst[SBGM_CUTOUT_MAX_FIELDS];
+    int n_items[SBGM_CUTOUT_MAX_FIELDS];          // N of a stack, 0 for a static plane
+    int Hd, Wd, Wp;
+};
+
+__global__ __launch_bounds__(256) void domain_gather_kernel(DomainGatherArgs a, const CutoutProgram* __restrict__ programs,
+                                                            const int* __restrict__ items) {
+    const int f = blockIdx.z, b = blockIdx.y;
+    const int n_items = a.n_items[f];
+    const int item = n_items > 0 ? items[b] : 0;
+    const bool inside = item >= 0 && (n_items == 0 || item < n_items);
+    const int wq = a.Wp >> 2, last = a.Wd - 1;
+    const size_t quads = (size_t)a.Hd * wq;
+    f32x4* dst = reinterpret_cast<f32x4*>(a.dst[f]) + (size_t)b * quads;
+    const float* src = a.src[f] + (size_t)(inside ? item : 0) * a.Hd * a.Wd;
+    const CutoutProgram& pg = programs[f];
+    ChainProgram p;
+    p.n_ops = pg.n_ops < SBGM_CHAIN_MAX_OPS ? pg.n_ops : SBGM_CHAIN_MAX_OPS;
+#pragma unroll
+    for (int i = 0; i < SBGM_CHAIN_MAX_OPS; ++i) { p.op[i] = pg.ops[i]; p.c[i] = pg.consts[i]; }
+    const int is_mask = pg.is_mask;
+    const float nanv = __uint_as_float(0x7FC00000u);
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += stride) {
+        const int y = (int)(q / wq), x = (int)(q % wq) << 2;
+        f32x4 v = {nanv, nanv, nanv, nanv};
+        if (inside) {
+            const float* s = src + (size_t)y * a.Wd;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = gather_value(s[x + e < last ? x + e : last], p, is_mask);
+        }
+        dst[q] = v;
     }
 }
 
@@ -199,6 +240,32 @@ int sbgm_launch_cutout_gather(const float* const* srcs, float* const* dsts, cons
     const size_t work = vec4 ? (size_t)h * w / 4 : (size_t)h * w;
     const int bx = (int)std::min<size_t>((work + 255) / 256, 256);
     hipLaunchKernelGGL(cutout_gather_kernel, dim3(bx, B, n_fields), dim3(256), 0, st, g, programs, items, origins);
+    SBGM_LAUNCH_CHECK();
+    return 0;
+}
+
+int sbgm_launch_domain_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const CutoutProgram* programs,
+                              const int* items, int B, int Hd, int Wd, int Wp, hipStream_t st) {
+    SBGM_CHECK(n_fields >= 1 && n_fields <= SBGM_CUTOUT_MAX_FIELDS, "domain_gather: %d fields (1..%d)", n_fields, SBGM_CUTOUT_MAX_FIELDS);
+    SBGM_CHECK(B >= 1 && B <= 65535 && Hd >= 1 && Wd >= 1, "domain_gather: B=%d domain %dx%d", B, Hd, Wd);
+    SBGM_CHECK(Wp >= Wd && Wp % 4 == 0, "domain_gather: padded width %d (a multiple of 4, at least the domain width %d)", Wp, Wd);
+    SBGM_CHECK(srcs && dsts && n_items && programs && items, "domain_gather: null argument");
+    DomainGatherArgs g{};
+    int stacks = 0, planes = 0;
+    for (int f = 0; f < n_fields; ++f) {
+        SBGM_CHECK(srcs[f] && dsts[f] && n_items[f] >= 0, "domain_gather: field %d is null or has a negative item count", f);
+        SBGM_CHECK((uintptr_t)dsts[f] % 16 == 0, "domain_gather: dst of field %d is not 16-byte aligned", f);
+        (n_items[f] > 0 ? stacks : planes) += 1;
+        g.src[f] = srcs[f];
+        g.dst[f] = dsts[f];
+        g.n_items[f] = n_items[f];
+    }
+    SBGM_CHECK(stacks <= 1 + SBGM_ASSEMBLE_MAX_LR && planes <= 2, "domain_gather: %d stacks (max %d), %d static planes (max 2)", stacks,
+               1 + SBGM_ASSEMBLE_MAX_LR, planes);
+    g.Hd = Hd; g.Wd = Wd; g.Wp = Wp;
+    const size_t quads = (size_t)Hd * (Wp / 4);
+    const int bx = (int)std::min<size_t>((quads + 255) / 256, 256);
+    hipLaunchKernelGGL(domain_gather_kernel, dim3(bx, B, n_fields), dim3(256), 0, st, g, programs, items);
     SBGM_LAUNCH_CHECK();
     return 0;
 }

@@ -478,6 +478,8 @@ struct CutoutProgram {                        // one row of the device program t
 };
 int sbgm_launch_cutout_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const CutoutProgram* programs,
                               const int* items, const int* origins, int B, int Hd, int Wd, int h, int w, hipStream_t st);
+int sbgm_launch_domain_gather(const float* const* srcs, float* const* dsts, const int* n_items, int n_fields, const CutoutProgram* programs,
+                              const int* items, int B, int Hd, int Wd, int Wp, hipStream_t st);
 long long sbgm_sdf_ws_bytes(int B, int h, int w);
 int sbgm_launch_sdf_from_mask(const float* mask, float* sdf, int* d2, void* ws, int B, int h, int w, hipStream_t st);
 

@@ -4,7 +4,8 @@
 are out of scope.  With an `evaluation.ensemble_products` section, `generate_repeated` also writes
 `ens_products_*`: the per-pixel mean, spread, envelope, quantile and exceedance-probability maps of its members, computed on
 the device (verification.ensemble_products).  `generate_series` (no reference counterpart) downscales the whole generation
-split in loader order, `evaluation.series.members` samples per day, into `*_series_n_<D>` files.
+split in loader order, `evaluation.series.members` samples per day, into `*_series_n_<D>` files; with an `evaluation.full_domain`
+section the days are whole domains, sampled through `tiling.FullDomainTiler.sample_series` (`_generate_domain_series`).
 
 Deliberate deviation: the reference writes `self.model.eval` without calling it, so its generation
 runs BatchNorm in training mode.  Here `eval()` IS called; pass `literal_reference_bn=True` to reproduce the
@@ -19,6 +20,7 @@ import torch
 
 from .. import parallel
 from .. import verification as V
+from ..resident_data import full_domain_config
 from ..score_sampling import (NOISE_MAX_LAGS, dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs, fresh_seed,
                               noise_weights_f32, ode_sampler_kwargs, pc_sampler, rk45_sampler, temporal_noise_acf, temporal_noise_weights)
 from ..score_unet import diffusion_coeff_fn, marginal_prob_std_fn
@@ -105,8 +107,19 @@ class SampleGenerator:
         self.output_dir = os.path.join(cfg["paths"]["sample_dir"], "generation", self.model_name_str)
         self.sample_path = os.path.join(self.output_dir, "generated_samples")
         os.makedirs(self.sample_path, exist_ok=True)
+        self.full_domain = full_domain_config(cfg)                   # raises here, at start, on what a domain series does not do
         hw = cfg["highres"]["data_size"]
-        self.constraint = constraint_mask(cfg, (hw[0], hw[0]))       # raises here, at start, on a sampler that cannot hold pixels
+        hw = (hw[0], hw[0])
+        if self.full_domain is not None:                             # the samples are whole domains: the mask has the domain's shape
+            if parallel.world()[1] > 1:
+                raise ValueError(f"evaluation.full_domain runs on one rank, got {parallel.world()[1]}: sharded days would break the "
+                                 "day order of the series")
+            hw = getattr(dataloader, "domain_hw", None)
+            if hw is None:
+                raise ValueError("evaluation.full_domain needs the loader of whole days (resident_data.ResidentDomainLoader, what "
+                                 f"get_gen_dataloader builds for the section), got {type(dataloader).__name__}")
+            self.full_domain = full_domain_config(cfg, hw)
+        self.constraint = constraint_mask(cfg, hw)                   # raises here, at start, on a sampler that cannot hold pixels
         self.products = ensemble_products_config(cfg)                # likewise on a malformed evaluation.ensemble_products section
 
     def _sample_device(self, batch_size, y, cond_img, lsm_cond, topo_cond, known=None, noise_plan=None):
@@ -235,6 +248,8 @@ class SampleGenerator:
         extended; `seed`, `weights` and `acf` go into the index file.  Rows are keyed by position in the crop: the coupling means
         something for a fixed crop (`sample_w_cutouts: false`) on consecutive days.  `pc_sampler`'s Langevin step still uses the
         batch-mean score norm, so its result, unlike its noise, depends on a day's batch-mates.  Without the two keys nothing changes."""
+        if self.full_domain is not None:
+            return self._generate_domain_series()
         members, max_days = series_config(self.cfg)
         seed, weights = series_noise_config(self.cfg)
         if weights is not None and seed is None:
@@ -278,6 +293,76 @@ class SampleGenerator:
             index.update(seed=np.int64(seed), weights=np.asarray(weights, dtype=np.float32), acf=temporal_noise_acf(weights))
         if len(points) == len(gens):
             index["hr_points"] = cat(points).numpy()
+        np.savez_compressed(os.path.join(self.sample_path, f"series_index_{suffix}.npz"), **index)
+        return gen
+
+    def _domain_sampler(self):
+        """(sampler, its keywords) of a domain series: the dispatch of `_sample_device` without rk45_sampler (refused at start)"""
+        kind = self.cfg["sampler"].get("sampler_type")
+        if kind == "edm_heun_sampler":
+            return edm_heun_sampler, edm_sampler_kwargs(self.cfg)
+        if kind == "dpmpp_2m_sampler":
+            return dpmpp_2m_sampler, dpm_sampler_kwargs(self.cfg)
+        return pc_sampler, {}
+
+    def _generate_domain_series(self):
+        """`generate_series` with an evaluation.full_domain section: the loader (`ResidentDomainLoader`) serves whole days of the
+        generation split, already padded for the tiler, and every batch of days runs through `FullDomainTiler.sample_series`: M =
+        evaluation.series.members fields per day, tiled or joint as the section says.  A domain series is always keyed by day: the ONE
+        seed and the weights are those of `series_noise_config` (a fresh seed and [1.0] without the keys), and a batch passes the absolute
+        index of its first day, so member m of day d is drawn as noise row (d + K - 1) M + m whatever evaluation.batch_size, `first_day`
+        and `max_days` are.  With a `constraint:` section the day's truth is held on the [Hd, Wd] mask.  The host arrays are allocated
+        once and filled batch by batch; the files hold the Wd real columns, the pad never leaves the device.  lsm_samples holds the one
+        static plane, [1, 2, Hd, Wd]."""
+        from ..tiling import FullDomainTiler
+        fd, loader = self.full_domain, self.dataloader
+        members, max_days = series_config(self.cfg)
+        seed, weights = series_noise_config(self.cfg)
+        weights = np.ones(1, dtype=np.float32) if weights is None else weights
+        seed = fresh_seed() if seed is None else seed
+        Hd, Wd = loader.domain_hw
+        tiler = FullDomainTiler((Hd, Wd), fd["tile"], fd["halo"], device=self.device)
+        if tiler.Wd_pad != loader.Wp or loader.first_day != fd["first_day"]:
+            raise ValueError(f"evaluation.full_domain: the loader serves width {loader.Wp} from day {loader.first_day}, the section's "
+                             f"tiler works on {tiler.Wd_pad} from day {fd['first_day']}")
+        D = loader.n_days if max_days is None else min(loader.n_days, max_days)
+        sampler, kw = self._domain_sampler()
+        back = self.cfg["evaluation"].get("transform_back", False)
+        hr_key = self.cfg["highres"]["variable"] + "_hr"
+        mask = None if self.constraint is None else torch.from_numpy(self.constraint).to(self.device)[None]
+        gen, truth = torch.empty(D, members, Hd, Wd), torch.empty(D, Hd, Wd)      # the series is held once, on the host
+        lsm_plane, seas, done = None, [], 0
+        for batch in loader:
+            if done >= D:
+                break
+            x, seasons, cond, _lsm_hr, lsm, _sdf, topo, _hp, _lp = extract_any(batch, self.device)
+            B = min(x.shape[0], D - done)
+            x = x[:B, 0, :, :Wd].contiguous()                                      # the truth, without the pad
+            out = tiler.sample_series(self.model, sampler, marginal_prob_std_fn, diffusion_coeff_fn, self.cfg["sampler"]["n_timesteps"],
+                                      cond_img=None if cond is None else cond[:B], lsm_cond=None if lsm is None else lsm[0],
+                                      topo_cond=None if topo is None else topo[0], y=None if seasons is None else seasons[:B].tolist(),
+                                      members=members, seed=seed, temporal_noise_weights=weights, first_day=fd["first_day"] + done,
+                                      days=B, tiles_per_batch=fd["tiles_per_batch"], known=None if mask is None else x[:, None],
+                                      known_mask=mask, joint=fd["joint"], **kw)
+            if back:
+                x, out = (maybe_inverse_transform(hr_key, t, self.back_transforms) for t in (x, out))
+            gen[done:done + B].copy_(out)
+            truth[done:done + B].copy_(x)
+            if seasons is not None:
+                seas.append(seasons[:B].cpu())
+            if lsm is not None and lsm_plane is None:
+                lsm_plane = lsm[:1, :, :, :Wd].cpu()
+            done += B
+        if done != D:
+            raise ValueError(f"gen_type 'series': the generation loader gave {done} of {D} days")
+        suffix = f"series_n_{D}"
+        self._save_npz({"gen_samples": gen, "eval_samples": truth, "lsm_samples": lsm_plane, "seasons": torch.cat(seas) if seas else None,
+                        "constraint_mask": self.constraint}, suffix)
+        index = {"members": np.int64(members), "seed": np.int64(seed), "weights": np.asarray(weights, dtype=np.float32),
+                 "acf": temporal_noise_acf(weights), "first_day": np.int64(fd["first_day"]), "domain_hw": np.asarray([Hd, Wd], dtype=np.int64),
+                 "tile": np.int64(fd["tile"]), "halo": np.int64(fd["halo"]), "joint": np.bool_(fd["joint"]),
+                 "tile_origins": np.asarray(tiler.origins, dtype=np.int64),
+                 "hr_points": np.tile(np.asarray([0, Hd, 0, Wd], dtype=np.int64), (D, 1))}
         np.savez_compressed(os.path.join(self.sample_path, f"series_index_{suffix}.npz"), **index)
         return gen
 

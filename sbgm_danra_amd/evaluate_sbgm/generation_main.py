@@ -1,7 +1,7 @@
 """`generation_main(cfg)` — reference sbgm/evaluate_sbgm/generation_main.py:47-181: seed, model, checkpoint
 (`network_params`, or `ema_network_params` with training.load_ema), generation loader, `SampleGenerator`, then every
 `cfg.evaluation.gen_type` (`multiple`, `single`, `repeated`, or `series`: the whole generation split in loader order, one rank
-only)."""
+only; with an `evaluation.full_domain` section the series is one of whole domains, `SampleGenerator._generate_domain_series`)."""
 from __future__ import annotations
 
 import os
@@ -13,7 +13,7 @@ from .. import parallel
 from ..ema import pick_network_params
 from ..training_utils import get_gen_dataloader, get_model, setup_logger
 from ..utils import get_model_string
-from .generation import SampleGenerator
+from .generation import SampleGenerator, full_domain_config
 
 
 def generation_main(cfg, dataloader=None, back_transforms=None):
@@ -24,6 +24,9 @@ def generation_main(cfg, dataloader=None, back_transforms=None):
     gen_dir = os.path.join(cfg["paths"]["sample_dir"], "generation", get_model_string(cfg))
     log = setup_logger(os.path.join(gen_dir, "logs"), name="gen_log")
     rank, world, local = parallel.init_distributed()
+    if full_domain_config(cfg) is not None and max(world, parallel.world()[1]) > 1:   # the section's other refusals are raised by the call
+        raise ValueError(f"evaluation.full_domain runs on one rank, got {max(world, parallel.world()[1])}: sharded days would break the "
+                         "day order of the series")
     if "series" in cfg["evaluation"]["gen_type"] and max(world, parallel.world()[1]) > 1:
         raise ValueError("gen_type 'series' runs on one rank: sharded days would interleave in the rank files and break the day order")
     if world > 1:      # one process per GPU: every rank generates from its own conditioning batch with its own noise and writes *_rank<r> files

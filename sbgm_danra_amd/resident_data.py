@@ -4,6 +4,8 @@ three native ops (csrc/cutout.hip) — what the reference's `DANRA_Dataset_cutou
 
     ResidentFields        one .npz per split, validated and uploaded once
     ResidentCutoutLoader  iterable of the reference's batch dicts, as device tensors
+    ResidentDomainLoader  iterable of whole days of a split, right-padded for `tiling.FullDomainTiler` (one `sbgm_domain_gather` per batch):
+                          what `get_gen_dataloader` returns with an `evaluation.full_domain` section (`full_domain_config`)
     resident_loaders / resident_gen_loader   what `training_utils.get_dataloader` / `get_gen_dataloader` return when the config has
                           `data_handling.resident_fields: {train: <npz>, valid: <npz>, gen: <npz>}`
 
@@ -292,6 +294,133 @@ class ResidentCutoutLoader:
             self.epoch += 1          # a loop that never calls set_epoch still sees a new order and new cutouts every epoch
 
 
+FULL_DOMAIN_KEYS = ("tile", "halo", "joint", "tiles_per_batch", "first_day")
+
+
+def full_domain_config(cfg, domain_hw=None):
+    """The optional evaluation.full_domain section as {tile, halo, joint, tiles_per_batch, first_day}, or None without it.  With the
+    section `gen_type: [series]` downscales the whole domain of `data_handling.resident_fields.gen` through `FullDomainTiler`
+    (`SampleGenerator.generate_series`).  `tile` (default highres.data_size[0]) and `halo` (default 32) are the tiler's, `joint` and
+    `tiles_per_batch` (default: all tiles of a rank in one batch) those of `FullDomainTiler.sample`; `first_day` >= 0 skips that many
+    days of the split and keeps their absolute noise rows.  Every refusal is a ValueError that names its key: an unknown key, a value of
+    the wrong type, `rk45_sampler`, a `gen_type` beside `series`, a configuration without the generation split's file and — with
+    `domain_hw` = (Hd, Wd), once the file is open — a tile or halo the tile table (`tiling.axis_origins`) refuses for that domain."""
+    ev = cfg["evaluation"]
+    sec = ev.get("full_domain") if hasattr(ev, "get") else None
+    if sec is None:
+        return None
+    if not hasattr(sec, "keys") or not set(sec.keys()) <= set(FULL_DOMAIN_KEYS):
+        raise ValueError(f"evaluation.full_domain takes the keys {list(FULL_DOMAIN_KEYS)} only, got {sec!r}")
+    integer = lambda v: isinstance(v, int) and not isinstance(v, bool)                    # noqa: E731
+    size = cfg["highres"].get("data_size")
+    tile = sec.get("tile") if sec.get("tile") is not None else (None if size is None else int(size[0]))
+    halo, joint, per, first = sec.get("halo", 32), sec.get("joint", False), sec.get("tiles_per_batch"), sec.get("first_day", 0)
+    if not integer(tile) or tile < 1:
+        raise ValueError(f"evaluation.full_domain.tile must be an integer >= 1 (default: highres.data_size[0]), got {tile!r}")
+    if not integer(halo) or not 0 <= 2 * halo < tile:
+        raise ValueError(f"evaluation.full_domain.halo must be an integer with 0 <= 2 * halo < tile = {tile}, got {halo!r}")
+    if not isinstance(joint, bool):
+        raise ValueError(f"evaluation.full_domain.joint must be true or false, got {joint!r}")
+    if per is not None and (not integer(per) or per < 1):
+        raise ValueError(f"evaluation.full_domain.tiles_per_batch must be null or an integer >= 1, got {per!r}")
+    if not integer(first) or first < 0:
+        raise ValueError(f"evaluation.full_domain.first_day must be an integer >= 0, got {first!r}")
+    if cfg["sampler"].get("sampler_type") == "rk45_sampler":
+        raise ValueError("evaluation.full_domain: sampler.sampler_type rk45_sampler does not take a domain noise plan (use pc_sampler, "
+                         "edm_heun_sampler or dpmpp_2m_sampler)")
+    kinds = list(ev.get("gen_type") or [])
+    if kinds != ["series"]:
+        raise ValueError(f"evaluation.full_domain serves evaluation.gen_type ['series'] alone, got {kinds}: the other types draw crops "
+                         "of highres.data_size from another loader")
+    paths = (cfg.get("data_handling", {}) or {}).get("resident_fields") or {}
+    if not (hasattr(paths, "get") and paths.get("gen")):
+        raise ValueError("evaluation.full_domain needs data_handling.resident_fields.gen, the .npz of the generation split")
+    if domain_hw is not None:
+        from .tiling import axis_origins, padded_width
+        try:
+            axis_origins(int(domain_hw[0]), tile, 2 * halo)
+            axis_origins(padded_width(domain_hw[1], tile), tile, 2 * halo, align=4)
+        except ValueError as e:
+            raise ValueError(f"evaluation.full_domain: tile {tile}, halo {halo} on the {domain_hw[0]}x{domain_hw[1]} domain: {e}") from None
+    return {"tile": tile, "halo": halo, "joint": joint, "tiles_per_batch": per, "first_day": first}
+
+
+class ResidentDomainLoader:
+    """Iterable over the days of `fields` in file order, `batch_size` days at a time from `first_day` on, each batch the WHOLE domain,
+    right-padded to `padded_width` (the `Wd_pad` of the `FullDomainTiler` it feeds, `tiling.padded_width`): one `sbgm_domain_gather`
+    over every field per batch, no origin draw and no shuffle.  Keys as `ResidentCutoutLoader` (`<hr_var>_hr`, `<cond>_lr`, raw
+    1-channel `lsm` / `topo`, `lsm_hr`, `classifier`, `hr_points` / `lr_points` = [0, Hd, 0, Wd]) with every field [B, 1, Hd, Wp], plus
+    `domain_hw` = (Hd, Wd).  No `sdf`: it weights the training loss.  The rectangle is the domain of the file, whatever
+    highres.data_size and cutout_domains say (they describe the training crop); the transforms are `build_transforms`'."""
+
+    def __init__(self, fields: ResidentFields, cfg, padded_width, batch_size=None, first_day=0, stats=None):
+        rf = cfg["lowres"].get("resize_factor", 1)
+        if rf not in (None, 1):
+            raise ValueError(f"lowres.resize_factor = {rf}: the resident loader does not resize (only resize_factor 1 is supported)")
+        self.fields, self.cfg = fields, cfg
+        self.batch_size = int(batch_size if batch_size is not None else cfg["evaluation"]["batch_size"])
+        self.first_day, self.Wp = int(first_day), int(padded_width)
+        self.domain_hw = (fields.Hd, fields.Wd)
+        if self.batch_size < 1 or not 0 <= self.first_day < fields.n_items:
+            raise ValueError(f"ResidentDomainLoader: batch_size={self.batch_size} (>= 1), first_day={self.first_day} of the "
+                             f"{fields.n_items} days of {fields.path}")
+        if self.Wp < fields.Wd or self.Wp % 4:
+            raise ValueError(f"ResidentDomainLoader: padded_width={self.Wp} must be a multiple of 4 and at least the domain width {fields.Wd}")
+        geo = cfg["stationary_conditions"]["geographic_conditions"]
+        geo_vars = list(geo.get("geo_variables") or []) if geo.get("sample_w_geo", False) else []
+        self.with_classes = bool(cfg["stationary_conditions"]["seasonal_conditions"].get("sample_w_cond_season", False))
+        if self.with_classes and fields.classifier is None:
+            raise ValueError(f"{fields.path}: key 'classifier' is missing, but seasonal_conditions.sample_w_cond_season is set")
+        for k in geo_vars:
+            if k in ("lsm", "topo") and k not in fields.planes:
+                raise ValueError(f"{fields.path}: key '{k}' is missing, but the geographic conditions ask for it")
+        transforms = build_transforms(cfg, fields, stats)
+        plan = [(k, fields.stacks[k], fields.n_items, 0, transforms[k]) for k in [fields.hr_key] + fields.lr_keys]
+        self.yield_lsm, self.yield_topo = "lsm" in geo_vars, "topo" in geo_vars
+        if self.yield_lsm:
+            plan.append(("lsm", fields.planes["lsm"], 0, 1, None))
+        if self.yield_topo:
+            plan.append(("topo", fields.planes["topo"], 0, 0, transforms.get("topo")))
+        self.plan = plan
+        self.programs = upload_programs([(is_mask, tr) for _k, _s, _n, is_mask, tr in plan], fields.device)   # once, not per batch
+        self._items = torch.arange(fields.n_items, dtype=torch.int32, device=fields.device)
+        self._points = torch.tensor([0, fields.Hd, 0, fields.Wd], dtype=torch.int64, device=fields.device)
+
+    @property
+    def n_days(self):
+        """the days the loader serves: those of the split from `first_day` on"""
+        return self.fields.n_items - self.first_day
+
+    def __len__(self):
+        return -(-self.n_days // self.batch_size)
+
+    def gather(self, items: torch.Tensor) -> dict:
+        """the batch of the days `items` (device int32 [B]; what __iter__ calls)"""
+        F, dev = self.fields, self.fields.device
+        B, nf = items.shape[0], len(self.plan)
+        srcs, dsts, counts, outs = (N._vp * nf)(), (N._vp * nf)(), (C.c_int * nf)(), {}
+        block = torch.empty(nf, B, 1, F.Hd, self.Wp, device=dev)           # one allocation; the batch holds views of it
+        for i, (key, src, n, _m, _t) in enumerate(self.plan):
+            outs[key] = block[i]
+            srcs[i], dsts[i], counts[i] = src.data_ptr(), outs[key].data_ptr(), n
+        N.check(N.lib().sbgm_domain_gather(srcs, dsts, counts, nf, self.programs.data_ptr(), items.data_ptr(), B, F.Hd, F.Wd, self.Wp,
+                                           N.stream()))
+        batch = {k: outs[k] for k in [F.hr_key] + F.lr_keys}
+        if self.yield_lsm:
+            batch["lsm"] = batch["lsm_hr"] = outs["lsm"]
+        if self.yield_topo:
+            batch["topo"] = outs["topo"]
+        if self.with_classes:
+            batch["classifier"] = F.classifier.index_select(0, items.long())
+        pts = self._points.expand(B, 4).contiguous()
+        batch["hr_points"], batch["lr_points"], batch["domain_hw"] = pts, pts.clone(), self.domain_hw
+        return batch
+
+    def __iter__(self):
+        for d in range(self.first_day, self.fields.n_items, self.batch_size):
+            yield self.gather(self._items[d:d + self.batch_size])
+
+
 def _split_fields(cfg, split, device):
     paths = cfg["data_handling"]["resident_fields"]
     if split not in paths or not paths[split]:
@@ -317,6 +446,20 @@ def resident_loaders(cfg, shard=None):
     return (ResidentCutoutLoader(_split_fields(cfg, "train", dev), cfg, "train", bs, seed, shard=shard, drop_last=True),
             ResidentCutoutLoader(_split_fields(cfg, "valid", dev), cfg, "valid", bs, seed),
             ResidentCutoutLoader(_split_fields(cfg, "gen", dev), cfg, "gen", n_gen, seed))
+
+
+def resident_domain_loader(cfg, shard=None):
+    """the `ResidentDomainLoader` of a configuration with an evaluation.full_domain section: evaluation.batch_size days a batch, padded
+    for the section's tile; one rank only (the days of a series keep the file's order)"""
+    from .tiling import padded_width
+    fd = full_domain_config(cfg)
+    if fd is None:
+        raise ValueError("resident_domain_loader: the configuration has no evaluation.full_domain section")
+    if shard is not None and shard[1] > 1:
+        raise ValueError(f"evaluation.full_domain runs on one rank, got {shard[1]}: sharded days would break the day order of the series")
+    fields = _split_fields(cfg, "gen", _device(cfg))
+    fd = full_domain_config(cfg, (fields.Hd, fields.Wd))
+    return ResidentDomainLoader(fields, cfg, padded_width(fields.Wd, fd["tile"]), int(cfg["evaluation"]["batch_size"]), fd["first_day"])
 
 
 def resident_gen_loader(cfg, shard=None):

@@ -58,6 +58,11 @@ def axis_origins(length: int, tile: int, overlap: int, align: int = 1):
     return out
 
 
+def padded_width(Wd: int, tile: int) -> int:
+    """the width the tile table works on: Wd padded on the right until Wd_pad - tile is a multiple of 4 (the x origins are noise quads)"""
+    return int(Wd) + (-(int(Wd) - int(tile))) % 4
+
+
 class FullDomainTiler:
     """Tile table + device gather/blend kernels for one (domain, tile, halo) geometry."""
 
@@ -76,7 +81,7 @@ class FullDomainTiler:
     def _x_origins(self):
         # x origins must be multiples of 4 (noise quads).  The last tile has to end at the domain edge, so when
         # Wd - tile is not a multiple of 4 the tile table works on a domain padded on the right to the next multiple.
-        self.Wd_pad = self.Wd + (-(self.Wd - self.tile)) % 4
+        self.Wd_pad = padded_width(self.Wd, self.tile)
         return axis_origins(self.Wd_pad, self.tile, self.overlap, align=4)
 
     def __len__(self):
@@ -97,11 +102,13 @@ class FullDomainTiler:
         return torch.nn.functional.pad(dom, (0, self.Wd_pad - self.Wd), mode="replicate")
 
     def extract(self, domain: torch.Tensor, which=None) -> torch.Tensor:
-        """domain [C, Hd, Wd] (device) -> tiles [T, C, tile, tile]; `which` = tile indices (default all)"""
+        """domain [C, Hd, Wd] (device) -> tiles [T, C, tile, tile]; `which` = tile indices (default all).  A domain that is already
+        [C, Hd, Wd_pad] (right edge replicated by its producer, `sbgm_domain_gather`) is cut as it is, without the pad's copy."""
         N.require_device(domain)
-        if domain.dim() != 3 or domain.shape[1] != self.Hd or domain.shape[2] != self.Wd:
-            raise ValueError(f"domain tensor {tuple(domain.shape)} does not match the tiler's [C, {self.Hd}, {self.Wd}]")
-        dom = N.f32c(self._pad(domain.float()))
+        if domain.dim() != 3 or domain.shape[1] != self.Hd or domain.shape[2] not in (self.Wd, self.Wd_pad):
+            raise ValueError(f"domain tensor {tuple(domain.shape)} does not match the tiler's [C, {self.Hd}, {self.Wd}]"
+                             + ("" if self.Wd_pad == self.Wd else f" or its padded [C, {self.Hd}, {self.Wd_pad}]"))
+        dom = N.f32c(domain.float() if domain.shape[2] == self.Wd_pad else self._pad(domain.float()))
         C = dom.shape[0]
         org = self.origins_dev if which is None else self.origins_dev[list(which)].contiguous()
         T = org.shape[0]
@@ -126,7 +133,8 @@ class FullDomainTiler:
                topo_cond=None, y=None, seed=None, tiles_per_batch=None, known=None, known_mask=None, joint=False,
                noise_row=None, noise_weights=None, noise_row_stride=1, **sampler_kw) -> torch.Tensor:
         """Sample the whole domain: cond_img [C,Hd,Wd] / lsm_cond, topo_cond [2,Hd,Wd] / y scalar class -> [1,Hd,Wd].
-        Tiles are sharded over the ranks of the process group (if any) and, per rank, run in batches of
+        Each condition may instead come pre-padded, [.., Hd, Wd_pad] (`extract`; what `ResidentDomainLoader` serves); `known`,
+        `known_mask` and the result are always Wd wide.  Tiles are sharded over the ranks of the process group (if any) and, per rank, run in batches of
         `tiles_per_batch`; every batch shares `seed`, so the domain-keyed noise is identical wherever tiles overlap.
         `known`, `known_mask` [1,Hd,Wd] (constrained sampling, see `pc_sampler`): cut into tiles like the conditions and passed to
         the sampler; after the stitch the hold is applied once more against the domain fields, so the result equals `known` on the

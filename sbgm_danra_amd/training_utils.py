@@ -94,6 +94,9 @@ def get_dataloader(cfg, shard=None):
 
 def get_gen_dataloader(cfg, shard=None):
     """`shard=(rank, world)`: every rank draws its OWN evaluation batch (independent units, no collective: SURVEY.md 8e)"""
+    if (cfg["evaluation"].get("full_domain") if hasattr(cfg["evaluation"], "get") else None) is not None:
+        from .resident_data import resident_domain_loader          # whole days of the generation split, padded for the tiler
+        return resident_domain_loader(cfg, shard=shard)
     if (cfg.get("data_handling", {}) or {}).get("resident_fields"):
         from .resident_data import resident_gen_loader
         return resident_gen_loader(cfg, shard=shard)
