@@ -1032,6 +1032,32 @@ int sbgm_climate_indices(const float* gen, const float* obs, const void* mask, i
                          int* days, float* stats, int* spells, int* transitions, float* quant, float* wet_quant, float* heavy,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* sbgm_climate_indices_calendar: the same indices with a calendar and with groups of days (K61, then K55 - K57 over slabs).
+ *   day_numbers: NULL, or a DEVICE int32 [N], strictly increasing (the caller checks that).  Day t is LINKED to day t - 1 iff
+ *     day_numbers[t] == day_numbers[t-1] + 1; NULL links every adjacent pair.  A broken link between day t - 1 and day t acts
+ *     exactly as one invalid day inserted between them: it ends a wet or dry run, and no transition and no lag-1 product spans
+ *     it.  It counts nowhere else: not in n, the sums, the quantiles or heavy.
+ *   groups: NULL (G = 0), or a DEVICE int32 [N] of ids in 0..G-1, 1 <= G <= 16.  The indices of group g are the calendar-aware
+ *     indices of the subsequence of the days with id g, which keeps its own day numbers (positions when day_numbers is NULL):
+ *     a link is also broken where consecutive days of the group are not consecutive days of the record.  The group has its own
+ *     mean in lag1 and its own obs wet_quant map as tau of heavy.  A day whose id lies outside 0..G-1 joins no group; a group
+ *     of 0 or 1 days follows the rules for n = 0 or n = 1.
+ * The group outputs carry a leading [G] axis on the layout of the ungrouped ones (group_days [G][HW], group_stats
+ * [G][2][7][HW], ...); they may be NULL when G = 0, the quantile ones also when their count is 0.  With day_numbers and groups
+ * NULL this is sbgm_climate_indices, bit for bit, on that function's workspace size.  The fp64 operations and their order are
+ * those of sbgm_climate_indices on the subsequence with an all-NaN day inserted at every broken link.  Cost: every group slab
+ * walks only its own days, so a grouped call sweeps the record twice where the ungrouped call sweeps it once, whatever G is
+ * (measured at 589 x 789 with four seasons: 1.45 - 1.58 times the ungrouped call). */
+#define SBGM_TEMPORAL_MAX_GROUPS 16
+int64_t sbgm_climate_calendar_workspace_bytes(int N, int H, int W, int Q, int QW, int G);
+int sbgm_climate_indices_calendar(const float* gen, const float* obs, const void* mask, int mask_is_u8, int N, int Nm, int H, int W,
+                                  float wet, const double* quantiles, int Q, const double* wet_quantiles, int QW, /* HOST arrays */
+                                  const int* day_numbers, const int* groups, int G,                      /* DEVICE int32 [N] or NULL */
+                                  int* days, float* stats, int* spells, int* transitions, float* quant, float* wet_quant,
+                                  float* heavy, int* group_days, float* group_stats, int* group_spells, int* group_transitions,
+                                  float* group_quant, float* group_wet_quant, float* group_heavy, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
+
 /* ---- pooled ensemble verification of a series (verify_series.hip) --------------------------------------
  * sbgm_series_scores: D days (1 <= D <= 4095) of M members (2 <= M <= 4095) E[d][m][p] against one truth Y[d][p] per day, pooled
  * over days x pixels.  Member (d, m) is read at ens + d * day_stride + m * member_stride (strides in elements, each >= H*W; the H*W

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import verification as V
+from .. import calendar
 from ..utils import get_model_string
 
 logger = logging.getLogger(__name__)
@@ -43,6 +44,11 @@ CLIMATE_DEFINITION = (
     "bias = mean_gen - mean_obs, rmse, Pearson pattern correlation.  cwd, cdd, transitions, p_ww, p_dw and lag1 are computed in FILE "
     "ORDER: they mean something only when the file holds consecutive days at a fixed location (a 'series' from an unshuffled loader "
     "whose cutout rectangle equals data_size)")
+CLIMATE_CALENDAR_DEFINITION = (
+    ".  With `calendar` a gap in the dates acts as one invalid day between the two days: it ends a spell, and no transition and no "
+    "lag-1 product spans it.  `groups`: the same indices over the days of each group, which keep their dates, so a spell or a pair "
+    "also ends where the group's days are not consecutive; each group has its own mean in lag1 and its own OBS wet_quantiles map in "
+    "heavy_fraction")
 PIXEL_BINS = 150                      # the reference's pixel-value histograms (evaluation.py:320)
 CRPS_DEFINITIONS = {"crps_fair": "(1/M) sum_i |x_i - y| - sum_ij |x_i - x_j| / (2 M (M - 1))",
                     "crps_standard": "(1/M) sum_i |x_i - y| - sum_ij |x_i - x_j| / (2 M^2)"}
@@ -209,6 +215,9 @@ def multivariate_scores_config(cfg):
     return energy, variogram
 
 
+CLIMATE_CALENDAR_KEYS = ("calendar", "groups")
+
+
 def climate_indices_config(cfg):
     """(wet, quantiles, wet_quantiles) of the optional evaluation.climate_indices section — `wet`: the wet-day threshold in the
     units the generated files hold (default 1.0); `quantiles`, `wet_quantiles`: at most 8 levels in [0, 1] each, either may be
@@ -217,9 +226,11 @@ def climate_indices_config(cfg):
     if sec is None:
         return None
     keys = ("wet", "quantiles", "wet_quantiles")
-    if not hasattr(sec, "keys") or not set(sec.keys()) <= set(keys):
-        unknown = sorted(set(sec.keys()) - set(keys)) if hasattr(sec, "keys") else sec
-        raise ValueError(f"evaluation.climate_indices takes the keys 'wet', 'quantiles' and 'wet_quantiles' only, got {unknown!r}")
+    if not hasattr(sec, "keys") or not set(sec.keys()) <= set(keys + CLIMATE_CALENDAR_KEYS):
+        unknown = sorted(set(sec.keys()) - set(keys + CLIMATE_CALENDAR_KEYS)) if hasattr(sec, "keys") else sec
+        raise ValueError(f"evaluation.climate_indices takes the keys 'wet', 'quantiles', 'wet_quantiles', 'calendar' and 'groups' "
+                         f"only, got {unknown!r}")
+    climate_calendar_config(cfg)
     wet = sec.get("wet", 1.0)
     if isinstance(wet, bool) or not isinstance(wet, (int, float)) or not math.isfinite(wet):
         raise ValueError(f"evaluation.climate_indices.wet must be a finite number, got {wet!r}")
@@ -235,11 +246,38 @@ def climate_indices_config(cfg):
     return float(wet), levels[0], levels[1]
 
 
+def _groups_setting(key, groups):
+    """a `groups` setting: None, "season" or "month" (from the dates of the series), a .npy path, or a list of ids in 0..15"""
+    if isinstance(groups, str):
+        if groups not in calendar.GROUPINGS and not groups.endswith(".npy"):
+            raise ValueError(f"{key}: a string must be 'season', 'month' or the path of a .npy file, got {groups!r}")
+    elif groups is not None:
+        if not isinstance(groups, (list, tuple)) or not groups or any(isinstance(g, bool) or not isinstance(g, int) or
+                                                                      not 0 <= g < V.MAX_SERIES_GROUPS for g in groups):
+            raise ValueError(f"{key} must be null, 'season', 'month', a .npy path or a list of integers in "
+                             f"0..{V.MAX_SERIES_GROUPS - 1}, one per day, got {groups!r}")
+        groups = [int(g) for g in groups]
+    return groups
+
+
+def climate_calendar_config(cfg):
+    """(calendar, groups) of the evaluation.climate_indices section — `calendar`: None (the default: true when the series has
+    dates) or a bool, whether a gap in the dates ends spells and pairs; `groups`: None, "season", "month", a list of one id in
+    0..15 per day, or a .npy path — (None, None) when the section is absent"""
+    sec = cfg["evaluation"].get("climate_indices")
+    if sec is None or not hasattr(sec, "keys"):
+        return None, None
+    cal = sec.get("calendar")
+    if cal is not None and not isinstance(cal, bool):
+        raise ValueError(f"evaluation.climate_indices.calendar must be null, true or false, got {cal!r}")
+    return cal, _groups_setting("evaluation.climate_indices.groups", sec.get("groups"))
+
+
 def series_scores_config(cfg):
     """(thresholds, climatology, groups, seed) of the optional evaluation.series_scores section — `thresholds`: up to 16 finite
     numbers in the units the generated files hold (default none); `climatology`: bool (default true), the leave-one-out
-    climatological reference and the CRPS skill score; `groups`: None, a list of one integer group id in 0..15 per day, or the
-    path of a .npy file holding one; `seed`: None (evaluation.seed) or an integer, the seed of the rank ties — or None when the
+    climatological reference and the CRPS skill score; `groups`: None, a list of one integer group id in 0..15 per day, the
+    path of a .npy file holding one, or "season" / "month" (from the dates of the series); `seed`: None (evaluation.seed) or an integer, the seed of the rank ties — or None when the
     section is absent"""
     sec = cfg["evaluation"].get("series_scores")
     if sec is None:
@@ -256,16 +294,7 @@ def series_scores_config(cfg):
     climatology = sec.get("climatology", True)
     if not isinstance(climatology, bool):
         raise ValueError(f"evaluation.series_scores.climatology must be true or false, got {climatology!r}")
-    groups = sec.get("groups")
-    if isinstance(groups, str):
-        if not groups.endswith(".npy"):
-            raise ValueError(f"evaluation.series_scores.groups: a path must name a .npy file, got {groups!r}")
-    elif groups is not None:
-        if not isinstance(groups, (list, tuple)) or not groups or any(isinstance(g, bool) or not isinstance(g, int) or
-                                                                      not 0 <= g < V.MAX_SERIES_GROUPS for g in groups):
-            raise ValueError(f"evaluation.series_scores.groups must be null, a .npy path or a list of integers in "
-                             f"0..{V.MAX_SERIES_GROUPS - 1}, one per day, got {groups!r}")
-        groups = [int(g) for g in groups]
+    groups = _groups_setting("evaluation.series_scores.groups", sec.get("groups"))
     seed = sec.get("seed")
     if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
         raise ValueError(f"evaluation.series_scores.seed must be null or an integer, got {seed!r}")
@@ -325,6 +354,7 @@ class Evaluation:
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
         logger.info(f"[INFO] Evaluating {self.label} from {files['gen_samples']}")
         self.members = None
+        self.dates = self._series_dates(files["gen_samples"]) if generated_sample_type == "series" else None
         if generated_sample_type == "series":
             # [D, M, H, W]: every per-field statistic runs on member 0, the climate indices on all members
             arrs = [np.asarray(np.load(p)["arr_0"]) for p in files["gen_samples"]]
@@ -355,6 +385,41 @@ class Evaluation:
             self.metrics.update(member=0, members=int(self.members.shape[0]))
         self.fields = {}
         self._err = None
+
+    @staticmethod
+    def _series_dates(gen_paths):
+        """int64 day numbers [D] from the `dates` of series_index_<suffix>.npz beside every gen_samples file, else None"""
+        parts = []
+        for p in gen_paths:
+            index = os.path.join(os.path.dirname(p), os.path.basename(p).replace("gen_samples_", "series_index_", 1))
+            if not os.path.exists(index):
+                return None
+            with np.load(index) as f:
+                if "dates" not in f.files:
+                    return None
+                parts.append(np.asarray(f["dates"]))
+        return calendar.day_numbers(np.concatenate(parts))
+
+    def _day_groups(self, key, groups, D):
+        """(ids list or None, names or None) of a `groups` setting for the D days of this unit"""
+        names = None
+        if isinstance(groups, str) and groups in calendar.GROUPINGS:
+            if self.dates is None:
+                raise ValueError(f"{key}: '{groups}' needs the dates of the series; {self.label} has none (no `dates` in its "
+                                 f"series_index file)")
+            groups, names = calendar.groups_from_dates(self.dates, groups)
+        elif isinstance(groups, str):
+            groups = np.load(groups)
+        if groups is None:
+            return None, None
+        groups = np.asarray(groups)
+        if groups.ndim != 1 or groups.dtype.kind not in "iu":
+            raise ValueError(f"{key} must hold one integer id per day, got shape {groups.shape} of {groups.dtype}")
+        if len(groups) != D:
+            raise ValueError(f"{key} holds {len(groups)} ids; {self.label} has {D} days")
+        groups = [int(g) for g in groups]
+        G = max(groups) + 1                                 # names of the G = largest id + 1 groups the scores have rows for
+        return groups, (names[:G] if names is not None else [str(g) for g in range(G)])
 
     def _need_ensemble(self, what):
         """the `repeated` samples are an ensemble for one condition: `what` needs them, and at least 2 members"""
@@ -601,14 +666,19 @@ class Evaluation:
         self.multivariate_fields = res
         return dict(res, metrics=out)
 
-    def climate_statistics(self, wet=None, quantiles=None, wet_quantiles=None):
+    def climate_statistics(self, wet=None, quantiles=None, wet_quantiles=None, calendar_aware=None, groups=None):
         """per-pixel climate indices along the day axis of the generated fields against their truth ('multiple' or 'series':
         one truth per day), once per member.  The maps go to a file of their own, <label>_climate.npz, which save() writes: the
         obs maps `obs_<index>`, the gen maps `gen_<index>` stacked over the members [M, ...], `days`, the levels and `wet`.  The
         metrics entry `climate` holds, per float index and level, the domain means, bias, RMSE and pattern correlation per
         member with their mean, minimum and maximum over the members.  With several members a day is valid only where every
         member is a number, so `days` and the obs maps hold for all of them.  Arguments default to the evaluation.climate_indices
-        section.  The order-dependent indices are computed in file order (see `definition`)."""
+        section.  The order-dependent indices are computed in file order (see `definition`).
+        `calendar_aware` (evaluation.climate_indices.calendar; default: true when the series has dates) makes a gap in the
+        dates end spells, transitions and lag-1 pairs; true without dates is an error.  `groups` (None, "season", "month", ids
+        or a .npy path; the two names need dates) adds the same indices per group of days: `groups`, `group_names`,
+        `group_days`, `group_obs_<index>` [G, ...] and `group_gen_<index>` [M, G, ...] in the file, and `calendar`,
+        `n_links_broken` and `groups` = [{name, n_days, indices}] in the metrics entry."""
         if self.generated_sample_type not in TIME_AXIS_TYPES:
             raise ValueError(f"climate_statistics needs one truth per day ('multiple' or 'series' samples), not "
                              f"'{self.generated_sample_type}'")
@@ -617,6 +687,13 @@ class Evaluation:
             if sec is None:
                 raise ValueError("no wet / quantiles / wet_quantiles given and the config has no evaluation.climate_indices section")
             wet, quantiles, wet_quantiles = sec
+        cfg_calendar, cfg_groups = climate_calendar_config(self.cfg)
+        calendar_aware = cfg_calendar if calendar_aware is None else bool(calendar_aware)
+        groups = cfg_groups if groups is None else groups
+        if calendar_aware and self.dates is None:
+            raise ValueError(f"evaluation.climate_indices.calendar is true but {self.label} has no dates (no `dates` in its "
+                             f"series_index file)")
+        calendar_aware = self.dates is not None if calendar_aware is None else calendar_aware
         wet = 1.0 if wet is None else float(wet)
         quantiles, wet_quantiles = [float(q) for q in (quantiles or [])], [float(q) for q in (wet_quantiles or [])]
         if self.eval_imgs.shape[0] != self.gen_imgs.shape[0]:
@@ -630,9 +707,12 @@ class Evaluation:
             finite = ~torch.isnan(members).any(dim=0)
             if not bool(finite.all()):
                 mask = (finite if mask is None else mask.bool() & finite).to(torch.uint8)
+        D = int(self.gen_imgs.shape[0])
+        gids, names = self._day_groups("evaluation.climate_indices.groups", groups, D)
+        dn = self.dates if calendar_aware else None
         runs = []
         for gen in members:
-            r = V.climate_indices(gen, self.eval_imgs, wet, quantiles, wet_quantiles, mask=mask)
+            r = V.climate_indices(gen, self.eval_imgs, wet, quantiles, wet_quantiles, mask=mask, day_numbers=dn, groups=gids)
             runs.append({k: v.cpu().numpy() for k, v in r.items()})
         res = {"days": runs[0]["days"], "wet": np.float64(wet), "quantile_levels": np.asarray(quantiles, np.float64),
                "wet_quantile_levels": np.asarray(wet_quantiles, np.float64), "members": np.int64(len(runs))}
@@ -640,23 +720,42 @@ class Evaluation:
             res[f"obs_{k}"] = runs[0][f"obs_{k}"]
             res[f"gen_{k}"] = np.stack([r[f"gen_{k}"] for r in runs])
         levels = {"quantiles": quantiles, "wet_quantiles": wet_quantiles, "heavy_fraction": wet_quantiles}
-        indices = {}
-        for k in V.CLIMATE_FLOAT_KEYS:
-            for j, name in enumerate([f"{k}_{q:g}" for q in levels[k]] if k in levels else [k]):
-                sel = (lambda a: a[j]) if k in levels else (lambda a: a)
-                per = [_pattern_summary(sel(r[f"gen_{k}"]), sel(runs[0][f"obs_{k}"])) for r in runs]
-                row = {"per_member": per}
-                for stat in ("mean_gen", "mean_obs", "bias", "rmse", "pattern_corr"):
-                    vals = np.asarray([p[stat] for p in per], np.float64)
-                    good = vals[~np.isnan(vals)]
-                    row[stat] = {"mean": float(good.mean()) if good.size else float("nan"),
-                                 "min": float(good.min()) if good.size else float("nan"),
-                                 "max": float(good.max()) if good.size else float("nan")}
-                row["pixels"] = [p["pixels"] for p in per]
-                indices[name] = row
+
+        def summary(pick):
+            """per index and level: the pattern summary of every member's map against the obs map; pick(map) selects the slab"""
+            indices = {}
+            for k in V.CLIMATE_FLOAT_KEYS:
+                for j, name in enumerate([f"{k}_{q:g}" for q in levels[k]] if k in levels else [k]):
+                    sel = (lambda a: a[j]) if k in levels else (lambda a: a)
+                    per = [_pattern_summary(sel(pick(r, f"gen_{k}")), sel(pick(runs[0], f"obs_{k}"))) for r in runs]
+                    row = {"per_member": per}
+                    for stat in ("mean_gen", "mean_obs", "bias", "rmse", "pattern_corr"):
+                        vals = np.asarray([p[stat] for p in per], np.float64)
+                        good = vals[~np.isnan(vals)]
+                        row[stat] = {"mean": float(good.mean()) if good.size else float("nan"),
+                                     "min": float(good.min()) if good.size else float("nan"),
+                                     "max": float(good.max()) if good.size else float("nan")}
+                    row["pixels"] = [p["pixels"] for p in per]
+                    indices[name] = row
+            return indices
+
         out = {"wet": wet, "quantile_levels": quantiles, "wet_quantile_levels": wet_quantiles, "members": len(runs),
-               "n_days": int(self.gen_imgs.shape[0]), "pixels": int((res["days"] > 0).sum()), "indices": indices,
+               "n_days": D, "pixels": int((res["days"] > 0).sum()), "indices": summary(lambda r, k: r[k]),
                "definition": CLIMATE_DEFINITION}
+        if self.dates is not None:
+            res["dates"] = np.asarray(self.dates, np.int64)
+        if calendar_aware or gids is not None:
+            out["calendar"] = bool(calendar_aware)
+            out["n_links_broken"] = int((~calendar.links(self.dates)[1:]).sum()) if calendar_aware else 0
+            out["definition"] = CLIMATE_DEFINITION + CLIMATE_CALENDAR_DEFINITION
+        if gids is not None:
+            res["groups"], res["group_names"] = np.asarray(gids, np.int64), np.asarray(names)
+            res["group_days"] = runs[0]["group_days"]
+            for k in V.CLIMATE_FLOAT_KEYS + V.CLIMATE_INT_KEYS:
+                res[f"group_obs_{k}"] = runs[0][f"group_obs_{k}"]
+                res[f"group_gen_{k}"] = np.stack([r[f"group_gen_{k}"] for r in runs])
+            out["groups"] = [{"name": names[g], "n_days": gids.count(g), "indices": summary(lambda r, k, g=g: r[f"group_{k}"][g])}
+                             for g in range(max(gids) + 1)]
         self.metrics["climate"] = out
         self.climate_fields = res
         return dict(res, metrics=out)
@@ -683,15 +782,7 @@ class Evaluation:
         thresholds = [float(t) for t in (thresholds or [])]
         climatology = True if climatology is None else bool(climatology)
         seed = int(self.cfg["evaluation"].get("seed", 0)) if seed is None else int(seed)
-        if isinstance(groups, str):
-            groups = np.load(groups)
-        if groups is not None:
-            groups = np.asarray(groups)
-            if groups.ndim != 1 or groups.dtype.kind not in "iu":
-                raise ValueError(f"evaluation.series_scores.groups must hold one integer id per day, got shape {groups.shape} of {groups.dtype}")
-            if len(groups) != D:
-                raise ValueError(f"evaluation.series_scores.groups holds {len(groups)} ids; {self.label} has {D} days")
-            groups = [int(g) for g in groups]
+        groups, _ = self._day_groups("evaluation.series_scores.groups", groups, D)
         r = V.series_ensemble_scores(self.members.permute(1, 0, 2, 3), self.eval_imgs, thresholds, groups=groups, mask=self.mask,
                                      seed=seed, climatology=climatology)
         res = {k: r[k].cpu().numpy() for k in V.SERIES_KEYS}

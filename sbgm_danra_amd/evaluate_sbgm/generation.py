@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from .. import parallel
+from .. import calendar, parallel
 from .. import verification as V
 from ..resident_data import full_domain_config
 from ..score_sampling import (NOISE_MAX_LAGS, dpm_sampler_kwargs, dpmpp_2m_sampler, edm_heun_sampler, edm_sampler_kwargs, fresh_seed,
@@ -54,10 +54,11 @@ def constraint_mask(cfg, hw):
 def series_config(cfg):
     """(members, max_days) of the optional evaluation.series section: `members` >= 1 samples per day (default 1), `max_days` >= 1
     or null (default: the whole generation split).  The section's other two keys, `seed` and `temporal_noise`, are read by
-    `series_noise_config`."""
+    `series_noise_config`, `calendar_origin` by `series_calendar`."""
     sec = cfg["evaluation"].get("series") or {}
-    if not hasattr(sec, "keys") or not set(sec.keys()) <= {"members", "max_days", "seed", "temporal_noise"}:
-        raise ValueError(f"evaluation.series takes the keys 'members', 'max_days', 'seed' and 'temporal_noise' only, got {sec!r}")
+    if not hasattr(sec, "keys") or not set(sec.keys()) <= {"members", "max_days", "seed", "temporal_noise", "calendar_origin"}:
+        raise ValueError(f"evaluation.series takes the keys 'members', 'max_days', 'seed', 'temporal_noise' and 'calendar_origin' only, "
+                         f"got {sec!r}")
     members, max_days = sec.get("members", 1), sec.get("max_days")
     if isinstance(members, bool) or not isinstance(members, int) or members < 1:
         raise ValueError(f"evaluation.series.members must be an integer >= 1, got {members!r}")
@@ -90,6 +91,38 @@ def series_noise_config(cfg):
     if isinstance(lags, bool) or not isinstance(lags, int) or not 1 <= lags <= NOISE_MAX_LAGS:
         raise ValueError(f"evaluation.series.temporal_noise.lags must be an integer in 1..{NOISE_MAX_LAGS}, got {lags!r}")
     return seed, temporal_noise_weights(rho, lags)
+
+
+def series_calendar(cfg, dataloader):
+    """the calendar origin (an int day number) of a series whose generation split has dates, else None: the optional
+    evaluation.series.calendar_origin (an int day number or "YYYY-MM-DD"), by default the first date of the split's file.  The key
+    without dates in the file is refused."""
+    sec = cfg["evaluation"].get("series") or {}
+    origin = sec.get("calendar_origin") if hasattr(sec, "get") else None
+    origin = None if origin is None else calendar.parse_origin(origin)
+    dates = getattr(getattr(dataloader, "fields", None), "dates", None)
+    if dates is None:
+        if origin is not None:
+            raise ValueError("evaluation.series.calendar_origin is set, but the generation split's file has no `dates`")
+        return None
+    return int(dates[0]) if origin is None else origin
+
+
+class _SeriesDates:
+    """the dates of the batches of a series, in the order served: absolute days for the noise rows, strictly increasing dates"""
+
+    def __init__(self, origin):
+        self.origin, self.dates = origin, []
+
+    def days(self, batch_dates):
+        """int64 [B] absolute days n_d = date - origin of one batch"""
+        dates = np.asarray(batch_dates, np.int64)
+        n = calendar.series_days(np.concatenate([self.dates[-1][-1:], dates]) if self.dates else dates, self.origin)
+        self.dates.append(dates)
+        return n[1:] if len(self.dates) > 1 else n
+
+    def index(self):
+        return {"dates": np.concatenate(self.dates), "calendar_origin": np.int64(self.origin)}
 
 
 def maybe_inverse_transform(k, arr, back_transforms):
@@ -245,7 +278,11 @@ class SampleGenerator:
         the loader), `noise_row_stride = M` and the K weights, so the draws of member m on day d are the moving average of the white
         draws of days d .. d-K+1 (lag-j autocorrelation `temporal_noise_acf(weights)[j]`, members mutually independent), each still
         N(0,1).  A day's noise then does not depend on the loader's batch size or on `max_days`, and a series can be reproduced or
-        extended; `seed`, `weights` and `acf` go into the index file.  Rows are keyed by position in the crop: the coupling means
+        extended; `seed`, `weights` and `acf` go into the index file.  When the generation split's file has `dates`, d is the day's
+        date minus the calendar origin (`series_calendar`) instead of its position: the day after a gap of g days is coupled to the
+        day before it at acf[g], a date's noise depends on (seed, origin, date, m) only, and `dates` and `calendar_origin` go into
+        the index file; the dates served must be strictly increasing.  With or without dates the rows come from `calendar.noise_rows`, which
+        refuses a row beyond int32 here, before the sampler would.  Rows are keyed by position in the crop: the coupling means
         something for a fixed crop (`sample_w_cutouts: false`) on consecutive days.  `pc_sampler`'s Langevin step still uses the
         batch-mean score norm, so its result, unlike its noise, depends on a day's batch-mates.  Without the two keys nothing changes."""
         if self.full_domain is not None:
@@ -257,6 +294,8 @@ class SampleGenerator:
         if parallel.world()[1] > 1:
             raise ValueError("gen_type 'series' runs on one rank: sharded days would interleave in the rank files and break the "
                              "day order")
+        origin = series_calendar(self.cfg, self.dataloader)
+        cal = None if origin is None else _SeriesDates(origin)
         gens, truths, lsms, seas, points, days = [], [], [], [], [], 0
         rep = lambda t: None if t is None else t.repeat_interleave(members, dim=0)   # noqa: E731
         for batch in self.dataloader:
@@ -268,9 +307,9 @@ class SampleGenerator:
                 x, seasons, cond, lsm, topo, hp = [None if t is None else t[:keep] for t in (x, seasons, cond, lsm, topo, hp)]
             B = x.shape[0]
             plan = None
+            absolute = np.arange(days, days + B) if cal is None else cal.days(batch["dates"][:B])
             if weights is not None:
-                first = (days + len(weights) - 1) * members
-                plan = {"seed": seed, "noise_rows": np.arange(first, first + B * members, dtype=np.int64), "noise_row_stride": members,
+                plan = {"seed": seed, "noise_rows": calendar.noise_rows(absolute, len(weights), members), "noise_row_stride": members,
                         "noise_weights": weights}
             gen = self._sample_device(B * members, rep(seasons), rep(cond), rep(lsm), rep(topo), known=rep(x), noise_plan=plan)
             if self.cfg["evaluation"].get("transform_back", False):
@@ -293,6 +332,8 @@ class SampleGenerator:
             index.update(seed=np.int64(seed), weights=np.asarray(weights, dtype=np.float32), acf=temporal_noise_acf(weights))
         if len(points) == len(gens):
             index["hr_points"] = cat(points).numpy()
+        if cal is not None:
+            index.update(cal.index())
         np.savez_compressed(os.path.join(self.sample_path, f"series_index_{suffix}.npz"), **index)
         return gen
 
@@ -311,7 +352,8 @@ class SampleGenerator:
         evaluation.series.members fields per day, tiled or joint as the section says.  A domain series is always keyed by day: the ONE
         seed and the weights are those of `series_noise_config` (a fresh seed and [1.0] without the keys), and a batch passes the absolute
         index of its first day, so member m of day d is drawn as noise row (d + K - 1) M + m whatever evaluation.batch_size, `first_day`
-        and `max_days` are.  With a `constraint:` section the day's truth is held on the [Hd, Wd] mask.  The host arrays are allocated
+        and `max_days` are; when the split's file has `dates`, d is the date minus the calendar origin (`series_calendar`) and `dates` and
+        `calendar_origin` go into the index file.  With a `constraint:` section the day's truth is held on the [Hd, Wd] mask.  The host arrays are allocated
         once and filled batch by batch; the files hold the Wd real columns, the pad never leaves the device.  lsm_samples holds the one
         static plane, [1, 2, Hd, Wd]."""
         from ..tiling import FullDomainTiler
@@ -326,6 +368,8 @@ class SampleGenerator:
             raise ValueError(f"evaluation.full_domain: the loader serves width {loader.Wp} from day {loader.first_day}, the section's "
                              f"tiler works on {tiler.Wd_pad} from day {fd['first_day']}")
         D = loader.n_days if max_days is None else min(loader.n_days, max_days)
+        origin = series_calendar(self.cfg, loader)
+        cal = None if origin is None else _SeriesDates(origin)
         sampler, kw = self._domain_sampler()
         back = self.cfg["evaluation"].get("transform_back", False)
         hr_key = self.cfg["highres"]["variable"] + "_hr"
@@ -338,11 +382,13 @@ class SampleGenerator:
             x, seasons, cond, _lsm_hr, lsm, _sdf, topo, _hp, _lp = extract_any(batch, self.device)
             B = min(x.shape[0], D - done)
             x = x[:B, 0, :, :Wd].contiguous()                                      # the truth, without the pad
+            when = (dict(first_day=fd["first_day"] + done) if cal is None
+                    else dict(day_numbers=cal.days(batch["dates"][:B]).tolist()))   # by position, or by date
             out = tiler.sample_series(self.model, sampler, marginal_prob_std_fn, diffusion_coeff_fn, self.cfg["sampler"]["n_timesteps"],
                                       cond_img=None if cond is None else cond[:B], lsm_cond=None if lsm is None else lsm[0],
                                       topo_cond=None if topo is None else topo[0], y=None if seasons is None else seasons[:B].tolist(),
-                                      members=members, seed=seed, temporal_noise_weights=weights, first_day=fd["first_day"] + done,
-                                      days=B, tiles_per_batch=fd["tiles_per_batch"], known=None if mask is None else x[:, None],
+                                      members=members, seed=seed, temporal_noise_weights=weights, days=B, **when,
+                                      tiles_per_batch=fd["tiles_per_batch"], known=None if mask is None else x[:, None],
                                       known_mask=mask, joint=fd["joint"], **kw)
             if back:
                 x, out = (maybe_inverse_transform(hr_key, t, self.back_transforms) for t in (x, out))
@@ -363,6 +409,8 @@ class SampleGenerator:
                  "tile": np.int64(fd["tile"]), "halo": np.int64(fd["halo"]), "joint": np.bool_(fd["joint"]),
                  "tile_origins": np.asarray(tiler.origins, dtype=np.int64),
                  "hr_points": np.tile(np.asarray([0, Hd, 0, Wd], dtype=np.int64), (D, 1))}
+        if cal is not None:
+            index.update(cal.index())
         np.savez_compressed(os.path.join(self.sample_path, f"series_index_{suffix}.npz"), **index)
         return gen
 

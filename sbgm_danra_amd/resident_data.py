@@ -10,7 +10,7 @@ three native ops (csrc/cutout.hip) — what the reference's `DANRA_Dataset_cutou
                           `data_handling.resident_fields: {train: <npz>, valid: <npz>, gen: <npz>}`
 
 npz layout: `<hr_var>_hr` [N, Hd, Wd]; `<cond>_lr` [N, Hd, Wd] per condition variable, already on the HR grid; `lsm`, `topo` [Hd, Wd]
-(optional); `classifier` [N] integer (optional).  Resizing is out of scope: the LR cutout must be the HR cutout and `resize_factor` 1.
+(optional); `classifier` [N] integer (optional); `dates` [N] (optional): integer days since 1970-01-01 or datetime64[D], strictly increasing.  Resizing is out of scope: the LR cutout must be the HR cutout and `resize_factor` 1.
 
 Two deliberate differences from the reference, both on crops without a coastline (include/sbgm_hip.h, sbgm_sdf_from_mask): an all-land
 crop gets sdf = 1 (reference: 0/0 = NaN, which poisons the loss) and an all-sea crop gets sdf = 0 (reference: scipy's transform of an
@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .calendar import day_numbers
 from .special_transforms import Scale, _Chain, get_transforms_from_stats
 
 SPLIT_IDS = {"train": 0, "valid": 1, "gen": 2}
@@ -43,7 +44,7 @@ def draw_number(split: str, epoch: int, batch: int, rank: int = 0) -> int:
 
 class ResidentFields:
     """The fields of one split on the device.  `stacks`: key -> fp32 [N, Hd, Wd]; `planes`: 'lsm' / 'topo' -> fp32 [Hd, Wd];
-    `classifier`: int64 [N] or None; `topo_range`: (min, max) of the topography plane, taken on the host before the upload."""
+    `classifier`: int64 [N] or None; `dates`: HOST int64 day numbers [N] or None; `topo_range`: (min, max) of the topography plane, taken on the host before the upload."""
 
     def __init__(self, path, hr_var, lr_vars=(), device="cuda", need=()):
         lr_vars = list(lr_vars or [])
@@ -85,6 +86,14 @@ class ResidentFields:
         self.stacks = {k: up(arrays[k]) for k in stack_keys}
         self.planes = {k: up(arrays[k]) for k in ("lsm", "topo") if k in arrays}
         self.classifier = None if cls is None else torch.from_numpy(cls.astype(np.int64)).to(dev)
+        self.dates = None                                   # host int64 day numbers [N] (calendar.day_numbers), or None
+        if "dates" in arrays:
+            try:
+                self.dates = day_numbers(arrays["dates"])
+            except ValueError as e:
+                raise ValueError(f"{path}: {e}") from None
+            if self.dates.shape != (self.n_items,):
+                raise ValueError(f"{path}: 'dates' holds {self.dates.shape[0]} days, the fields {self.n_items}")
 
     @staticmethod
     def _floating(arrays, key, path):
@@ -245,8 +254,10 @@ class ResidentCutoutLoader:
         return draw_number(self.split, self.epoch, batch, self.rank)
 
     # ---- one batch ------------------------------------------------------------------------------------------------------------
-    def cut(self, items: torch.Tensor, origins: torch.Tensor) -> dict:
-        """the batch for given device tensors items int32 [B] and origins int32 [B, 2] (what __iter__ calls after its draw)"""
+    def cut(self, items: torch.Tensor, origins: torch.Tensor, items_host=None) -> dict:
+        """the batch for given device tensors items int32 [B] and origins int32 [B, 2] (what __iter__ calls after its draw).
+        `items_host`: the same items as a host array, for `batch["dates"]`; without it a split with dates copies `items` to the
+        host, which synchronises (__iter__ passes its own host order, so its batches never do)"""
         F, dev, lib = self.fields, self.fields.device, N.lib()
         B = items.shape[0]
         nf = len(self.plan)
@@ -274,6 +285,8 @@ class ResidentCutoutLoader:
             batch["classifier"] = F.classifier.index_select(0, items.long())
         pts = origins.long().index_select(1, self._cols) + self._extent             # rows [r0, r1, c0, c1]
         batch["hr_points"], batch["lr_points"] = pts, pts.clone()
+        if F.dates is not None:
+            batch["dates"] = F.dates[items.cpu().numpy() if items_host is None else np.asarray(items_host, np.int64)]   # host int64 [B]
         return batch
 
     def draw_origins(self, batch: int, B: int) -> torch.Tensor:
@@ -284,12 +297,13 @@ class ResidentCutoutLoader:
 
     def __iter__(self):
         if self._items is None or self._items_epoch != self.epoch or self.shuffle:
-            self._items = torch.from_numpy(self.item_order().astype(np.int32)).to(self.fields.device)     # once per epoch
+            self._items_host = self.item_order()
+            self._items = torch.from_numpy(self._items_host.astype(np.int32)).to(self.fields.device)     # once per epoch
             self._items_epoch = self.epoch
-        items_all = self._items
+        items_all, host_all = self._items, self._items_host
         for i in range(len(self)):
             items = items_all[i * self.batch_size:(i + 1) * self.batch_size]
-            yield self.cut(items, self.draw_origins(i, items.shape[0]))
+            yield self.cut(items, self.draw_origins(i, items.shape[0]), host_all[i * self.batch_size:(i + 1) * self.batch_size])
         if self.shuffle:
             self.epoch += 1          # a loop that never calls set_epoch still sees a new order and new cutouts every epoch
 
@@ -394,8 +408,9 @@ class ResidentDomainLoader:
     def __len__(self):
         return -(-self.n_days // self.batch_size)
 
-    def gather(self, items: torch.Tensor) -> dict:
-        """the batch of the days `items` (device int32 [B]; what __iter__ calls)"""
+    def gather(self, items: torch.Tensor, items_host=None) -> dict:
+        """the batch of the days `items` (device int32 [B]; what __iter__ calls, with the same days as a host array for
+        `batch["dates"]`: without `items_host` a split with dates copies `items` to the host, which synchronises)"""
         F, dev = self.fields, self.fields.device
         B, nf = items.shape[0], len(self.plan)
         srcs, dsts, counts, outs = (N._vp * nf)(), (N._vp * nf)(), (C.c_int * nf)(), {}
@@ -414,11 +429,13 @@ class ResidentDomainLoader:
             batch["classifier"] = F.classifier.index_select(0, items.long())
         pts = self._points.expand(B, 4).contiguous()
         batch["hr_points"], batch["lr_points"], batch["domain_hw"] = pts, pts.clone(), self.domain_hw
+        if F.dates is not None:
+            batch["dates"] = F.dates[items.cpu().numpy() if items_host is None else np.asarray(items_host, np.int64)]   # host int64 [B]
         return batch
 
     def __iter__(self):
         for d in range(self.first_day, self.fields.n_items, self.batch_size):
-            yield self.gather(self._items[d:d + self.batch_size])
+            yield self.gather(self._items[d:d + self.batch_size], np.arange(d, min(d + self.batch_size, self.fields.n_items)))
 
 
 def _split_fields(cfg, split, device):

@@ -204,18 +204,23 @@ class FullDomainTiler:
         return dom
 
     def sample_series(self, score_model, sampler, marginal_prob_std, diffusion_coeff, num_steps, cond_img=None, lsm_cond=None,
-                      topo_cond=None, y=None, members=1, seed=None, temporal_noise_weights=None, first_day=0, days=None,
-                      tiles_per_batch=None, known=None, known_mask=None, joint=False, **sampler_kw) -> torch.Tensor:
+                      topo_cond=None, y=None, members=1, seed=None, temporal_noise_weights=None, first_day=None, days=None,
+                      tiles_per_batch=None, known=None, known_mask=None, joint=False, day_numbers=None, **sampler_kw) -> torch.Tensor:
         """A series of full-domain fields: cond_img [D,C,Hd,Wd] (one condition per day; or None with `days=D`) -> [D, members, Hd, Wd].
         The whole series runs under ONE `seed`, and member m of day d is drawn as the domain noise row (first_day + d + K - 1) * members
         + m with stride `members` (K = len(temporal_noise_weights), default [1.0]: white in time), the row convention of the cutout
         series (`generate_series`): consecutive days of a member share K - 1 white rows and correlate with `temporal_noise_acf(w)[1]`,
         members are independent, and a day's field depends on (seed, first_day + d, m) only, not on the call that made it, so a series
-        can be extended (`first_day`) or one day regenerated.  `lsm_cond`, `topo_cond` [2,Hd,Wd] and a scalar `y` are shared by the
+        can be extended (`first_day`) or one day regenerated.  `day_numbers` (instead of `first_day`; giving both is an error): a list
+        of `days` non-negative ints, the absolute day of each field, e.g. its date minus the calendar origin of the series; day d is
+        then drawn as row (day_numbers[d] + K - 1) * members + m, so the day after a gap of g days correlates with the day before
+        it at `temporal_noise_acf(w)[g]`.  `lsm_cond`, `topo_cond` [2,Hd,Wd] and a scalar `y` are shared by the
         days; `y` may also hold D classes, `known` / `known_mask` [1,Hd,Wd] are shared or [D,1,Hd,Wd] per day; `joint`,
         `tiles_per_batch` and the sampler's keywords act as in `sample`."""
         from .score_sampling import _fresh_seed, noise_weights_f32
-        members, first_day = int(members), int(first_day)
+        if first_day is not None and day_numbers is not None:
+            raise ValueError("FullDomainTiler.sample_series: give first_day or day_numbers, not both")
+        members, first_day = int(members), int(first_day or 0)
         if members < 1:
             raise ValueError(f"FullDomainTiler.sample_series: members={members} must be >= 1")
         if first_day < 0:
@@ -230,9 +235,15 @@ class FullDomainTiler:
         days = int(days)
         w = noise_weights_f32([1.0] if temporal_noise_weights is None else temporal_noise_weights,
                               "FullDomainTiler.sample_series: temporal_noise_weights")
-        last = (first_day + days - 1 + w.size - 1) * members + members - 1
+        what = f"day_numbers up to {max(day_numbers)}" if day_numbers is not None and len(day_numbers) else f"first_day={first_day}"
+        if day_numbers is None:
+            day_numbers = range(first_day, first_day + days)
+        day_numbers = [int(n) for n in day_numbers]
+        if len(day_numbers) != days or min(day_numbers) < 0:
+            raise ValueError(f"FullDomainTiler.sample_series: day_numbers must hold {days} non-negative integers, got {day_numbers}")
+        last = (max(day_numbers) + w.size - 1) * members + members - 1
         if last > 0x7FFFFFFF:
-            raise ValueError(f"FullDomainTiler.sample_series: first_day={first_day} puts the last noise row at {last}, beyond int32")
+            raise ValueError(f"FullDomainTiler.sample_series: {what} puts the last noise row at {last}, beyond int32")
         known, known_mask = (None if f is None else torch.as_tensor(f) for f in (known, known_mask))
         per_day = lambda f, d, lead: None if f is None else (f[d] if f.dim() == lead + 1 else f)   # noqa: E731
         if y is not None and not isinstance(y, int) and len(y) != days:
@@ -245,7 +256,7 @@ class FullDomainTiler:
                                         cond_img=None if cond_img is None else cond_img[d], lsm_cond=lsm_cond, topo_cond=topo_cond,
                                         y=y if y is None or isinstance(y, int) else int(y[d]), seed=seed, tiles_per_batch=tiles_per_batch,
                                         known=per_day(known, d, 3), known_mask=per_day(known_mask, d, 3), joint=joint,
-                                        noise_row=(first_day + d + w.size - 1) * members + m, noise_weights=w, noise_row_stride=members,
+                                        noise_row=(day_numbers[d] + w.size - 1) * members + m, noise_weights=w, noise_row_stride=members,
                                         **sampler_kw)[0]
         return out
 

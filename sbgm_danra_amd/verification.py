@@ -517,7 +517,7 @@ def _levels(levels, name):
     return qs, ((C.c_double * len(qs))(*qs) if qs else None)
 
 
-def climate_indices(gen, obs, wet=1.0, quantiles=(), wet_quantiles=(), mask=None):
+def climate_indices(gen, obs, wet=1.0, quantiles=(), wet_quantiles=(), mask=None, day_numbers=None, groups=None):
     """per-pixel climate indices along the day axis of gen [N,H,W] against obs [N,H,W], both fp32 (2 <= N <= 4095; sides 2..2048,
     H*W <= 2^20), optional mask [H,W] or [N,H,W] (uint8/bool != 0, or fp32 > 0.5).  Day t is valid at a pixel when gen and obs
     are both not NaN there and the mask admits it — paired, so both sides use the same days; a valid day is wet on a side when
@@ -531,7 +531,19 @@ def climate_indices(gen, obs, wet=1.0, quantiles=(), wet_quantiles=(), mask=None
     x > tau of x / sum over the valid wet days of x, tau the OBS side's wet_quantiles map for both sides (ETCCDI R95pTOT for
     level 0.95).  Sums are fp64 in day order (the order of axis 0), rounded to fp32 once; two calls give bit-equal results.
     At most 8 levels in [0, 1] in each list; either may be empty.  cwd, cdd, transitions, p_ww, p_dw and lag1 depend on the day
-    order and mean something only for consecutive days at a fixed location."""
+    order and mean something only for consecutive days at a fixed location.
+    `day_numbers`: one integer per day, strictly increasing (checked on the host; calendar.day_numbers gives them for dates).
+    Day t is linked to day t - 1 iff day_numbers[t] == day_numbers[t-1] + 1; None links every adjacent pair.  A broken link
+    acts exactly as one invalid day inserted between the two days: it ends a wet or dry run, and no transition and no lag-1
+    product spans it; it counts nowhere else (not in n, the sums, the quantiles or heavy_fraction).
+    `groups`: a group id in 0..15 per day (a sequence or an integer tensor; G = the largest id + 1), e.g. the season.  The
+    indices of group g are the calendar-aware indices of the subsequence of days with id g, which keeps its own day numbers
+    (positions without `day_numbers`), so a link is also broken where consecutive days of the group are not consecutive days
+    of the record; the group has its own mean in `lag1` and its own obs wet-day quantile map as tau of `heavy_fraction`.  The
+    dict then gains `group_days` int32 [G,H,W] and `group_<side>_<name>` with a leading [G] axis for every index.  A group of
+    0 or 1 days is legal: its maps follow the rules for n = 0 or n = 1.  With both None every key keeps its bits; a grouped
+    call sweeps the record twice where the plain call sweeps it once, whatever G is (measured: 1.45 - 1.58 plain calls with four
+    seasons at 589 x 789)."""
     for name, x in (("gen", gen), ("obs", obs)):
         if x.dim() != 3:
             raise ValueError(f"{name}: expected [N, H, W], got {tuple(x.shape)}")
@@ -548,31 +560,73 @@ def climate_indices(gen, obs, wet=1.0, quantiles=(), wet_quantiles=(), mask=None
     if isinstance(wet, bool) or not isinstance(wet, (int, float)) or not math.isfinite(wet) or not math.isfinite(C.c_float(wet).value):
         raise ValueError(f"climate_indices: wet must be a number finite in fp32, got {wet!r}")
     (qs, qarr), (qw, qwarr) = _levels(quantiles, "quantiles"), _levels(wet_quantiles, "wet_quantiles")
+    dn = _day_numbers(day_numbers, n)
+    gids, G = _series_groups(groups, n, "climate_indices")
     g, o = _fields(gen, "gen"), _fields(obs, "obs")
     if o.device != g.device:
         raise ValueError("gen and obs must be on the same device")
     m, u8, nm = _mask(mask, H * W, (1, n))
     Q, QW, HW, dev = len(qs), len(qw), H * W, g.device
     i32 = dict(dtype=torch.int32, device=dev)
-    days, spells, trans = torch.empty(HW, **i32), torch.empty(2, 2, HW, **i32), torch.empty(2, 4, HW, **i32)
-    stats = torch.empty(2, len(CLIMATE_STATS), HW, device=dev)
-    quant, wquant, heavy = torch.empty(2, Q, HW, device=dev), torch.empty(2, QW, HW, device=dev), torch.empty(2, QW, HW, device=dev)
-    nbytes = N.lib().sbgm_climate_indices_workspace_bytes(n, H, W, Q, QW)
-    ws = _ws(nbytes, dev)
-    N.check(N.lib().sbgm_climate_indices(g.data_ptr(), o.data_ptr(), N.ptr(m), u8, n, nm, H, W, float(wet), qarr, Q, qwarr, QW,
-                                         days.data_ptr(), stats.data_ptr(), spells.data_ptr(), trans.data_ptr(),
-                                         quant.data_ptr() if Q else None, wquant.data_ptr() if QW else None,
-                                         heavy.data_ptr() if QW else None, ws.data_ptr(), nbytes, N.stream()))
-    out = {"days": days.view(H, W)}
-    for s, side in enumerate(("gen", "obs")):
-        out.update({f"{side}_{k}": stats[s, i].view(H, W) for i, k in enumerate(CLIMATE_STATS)})
-        out.update({f"{side}_cwd": spells[s, 0].view(H, W), f"{side}_cdd": spells[s, 1].view(H, W),
-                    f"{side}_transitions": trans[s].view(4, H, W), f"{side}_quantiles": quant[s].view(Q, H, W),
-                    f"{side}_wet_quantiles": wquant[s].view(QW, H, W), f"{side}_heavy_fraction": heavy[s].view(QW, H, W)})
+    # every output as [1 + G, ...]: row 0 is the record, row 1 + g is group g
+    days, spells, trans = torch.empty(1 + G, HW, **i32), torch.empty(1 + G, 2, 2, HW, **i32), torch.empty(1 + G, 2, 4, HW, **i32)
+    stats = torch.empty(1 + G, 2, len(CLIMATE_STATS), HW, device=dev)
+    quant, wquant, heavy = (torch.empty(1 + G, 2, k, HW, device=dev) for k in (Q, QW, QW))
+    dn_dev = None if dn is None else torch.tensor(dn, dtype=torch.int32, device=dev)
+    g_dev = None if gids is None else torch.tensor(gids, dtype=torch.int32, device=dev)
+    ptr = lambda t, row, have=True: t[row].data_ptr() if have and row < 1 + G else None              # noqa: E731
+    if dn is None and gids is None:
+        nbytes = N.lib().sbgm_climate_indices_workspace_bytes(n, H, W, Q, QW)
+        ws = _ws(nbytes, dev)
+        N.check(N.lib().sbgm_climate_indices(g.data_ptr(), o.data_ptr(), N.ptr(m), u8, n, nm, H, W, float(wet), qarr, Q, qwarr, QW,
+                                             days.data_ptr(), stats.data_ptr(), spells.data_ptr(), trans.data_ptr(),
+                                             ptr(quant, 0, Q), ptr(wquant, 0, QW), ptr(heavy, 0, QW), ws.data_ptr(), nbytes,
+                                             N.stream()))
+    else:
+        nbytes = N.lib().sbgm_climate_calendar_workspace_bytes(n, H, W, Q, QW, G)
+        ws = _ws(nbytes, dev)
+        N.check(N.lib().sbgm_climate_indices_calendar(
+            g.data_ptr(), o.data_ptr(), N.ptr(m), u8, n, nm, H, W, float(wet), qarr, Q, qwarr, QW, N.ptr(dn_dev), N.ptr(g_dev), G,
+            days.data_ptr(), stats.data_ptr(), spells.data_ptr(), trans.data_ptr(), ptr(quant, 0, Q), ptr(wquant, 0, QW),
+            ptr(heavy, 0, QW), ptr(days, 1), ptr(stats, 1), ptr(spells, 1), ptr(trans, 1), ptr(quant, 1, Q), ptr(wquant, 1, QW),
+            ptr(heavy, 1, QW), ws.data_ptr(), nbytes, N.stream()))
+
+    def maps(pre, rows, lead):
+        r = {}
+        for s, side in enumerate(("gen", "obs")):
+            r.update({f"{pre}{side}_{k}": stats[rows, s, i].view(*lead, H, W) for i, k in enumerate(CLIMATE_STATS)})
+            r.update({f"{pre}{side}_cwd": spells[rows, s, 0].view(*lead, H, W), f"{pre}{side}_cdd": spells[rows, s, 1].view(*lead, H, W),
+                      f"{pre}{side}_transitions": trans[rows, s].view(*lead, 4, H, W),
+                      f"{pre}{side}_quantiles": quant[rows, s].view(*lead, Q, H, W),
+                      f"{pre}{side}_wet_quantiles": wquant[rows, s].view(*lead, QW, H, W),
+                      f"{pre}{side}_heavy_fraction": heavy[rows, s].view(*lead, QW, H, W)})
+        return r
+
+    out = {"days": days[0].view(H, W)}
+    out.update(maps("", 0, ()))
+    if G:
+        out["group_days"] = days[1:].view(G, H, W)
+        out.update(maps("group_", slice(1, None), (G,)))
     return out
 
 
-def _series_groups(groups, D):
+def _day_numbers(day_numbers, n):
+    """host int list of the optional day numbers relative to the first (they must fit int32), or None"""
+    if day_numbers is None:
+        return None
+    from .calendar import day_numbers as normalise
+    if isinstance(day_numbers, torch.Tensor):
+        day_numbers = day_numbers.cpu().numpy()
+    dn = normalise(day_numbers)
+    if dn.shape[0] != n:
+        raise ValueError(f"climate_indices: {dn.shape[0]} day numbers for N={n} days")
+    dn = dn - dn[0]
+    if int(dn[-1]) >= 2 ** 31 - 1:
+        raise ValueError(f"climate_indices: the day numbers span {int(dn[-1])} days; they must fit int32")
+    return dn.tolist()
+
+
+def _series_groups(groups, D, name="series_ensemble_scores"):
     """(host int list or None, G) of the optional group ids, one per day, each in 0..15; G = the largest id + 1"""
     if groups is None:
         return None, 0
@@ -582,12 +636,12 @@ def _series_groups(groups, D):
         groups = groups.tolist()
     groups = list(groups)
     if any(isinstance(g, bool) or int(g) != g for g in groups):
-        raise ValueError(f"series_ensemble_scores: groups must be integers, got {groups}")
+        raise ValueError(f"{name}: groups must be integers, got {groups}")
     groups = [int(g) for g in groups]
     if len(groups) != D:
-        raise ValueError(f"series_ensemble_scores: {len(groups)} group ids for D={D} days")
+        raise ValueError(f"{name}: {len(groups)} group ids for D={D} days")
     if min(groups) < 0 or max(groups) >= MAX_SERIES_GROUPS:
-        raise ValueError(f"series_ensemble_scores: group ids must lie in 0..{MAX_SERIES_GROUPS - 1} (G <= {MAX_SERIES_GROUPS}), got "
+        raise ValueError(f"{name}: group ids must lie in 0..{MAX_SERIES_GROUPS - 1} (G <= {MAX_SERIES_GROUPS}), got "
                          f"{min(groups)}..{max(groups)}")
     return groups, max(groups) + 1
 
