@@ -1058,6 +1058,54 @@ int sbgm_climate_indices_calendar(const float* gen, const float* obs, const void
                                   float* group_quant, float* group_wet_quant, float* group_heavy, void* workspace,
                                   int64_t workspace_bytes, void* stream);
 
+/* ---- period climate indices (verify_periods.hip) ------------------------------------------------------
+ * sbgm_period_indices: RxNday, RNNmm and PRCPTOT per pixel along the day axis, over the record and per period (a year, a season
+ * of a year, a month of a year), for M member series and one truth series.  Member m of day t is read at gen + m * member_stride
+ * + t * day_stride (strides in elements, day_stride >= H*W, member_stride >= H*W when M > 1; the H*W pixels of a field are
+ * dense), obs is [N][H][W]; 2 <= N <= 4095, 1 <= M <= 4095, the field limits above; mask NULL, [H][W] (Nm = 1) or [N][H][W]
+ * (Nm = N).  Series s = 0..M-1 are the members, s = M is obs: every [M+1] axis below is in that order.
+ *   Validity is paired over everything: day t is valid at pixel p when the mask admits it, obs[t][p] is not NaN and gen[m][t][p]
+ *     is not NaN for EVERY member m, so days, the period day counts and which windows exist are one map for all series.
+ *   Run length r[t] = valid[t] ? (linked[t] ? r[t-1] : 0) + 1 : 0, r[-1] = 0; linked[t] iff day_numbers[t] == day_numbers[t-1]
+ *     + 1 (DEVICE int32 [N], strictly increasing, the caller checks that; NULL: true for t > 0).  A broken link acts as one
+ *     invalid day in between, the rule of sbgm_climate_indices_calendar.
+ *   Window K ending on day t exists iff r[t] >= K.  Its sum is S = ((((+0.0 + x[t-K+1]) + x[t-K+2]) + ...) + x[t]) in fp64,
+ *     oldest day first, each fp32 value widened first, FP contraction off; starting from +0.0 makes -0 impossible.
+ *   windows: HOST int [Kw], 1 <= Kw <= 4 distinct ascending lengths in 1..32.  thresholds: HOST float [T], 0 <= T <= 8, finite.
+ *   days int32 [HW]: the valid days.
+ *   rx fp32 [M+1][Kw][HW]: the largest S over the windows that exist (best = S where best is NaN or S > best, in day order),
+ *     rounded to fp32 once; NaN where none exists.  K = 1 is Rx1day, K = 5 Rx5day.
+ *   count int32 [M+1][T][HW]: the valid days with x >= threshold_j, compared in fp32 (R10mm at 10).
+ *   prcptot fp32 [M+1][HW]: the fp64 sum in day order over the valid days with x >= wet, rounded once; 0 where there is a valid
+ *     day and no wet one, NaN where days = 0.
+ * periods: NULL (P = 0), or a DEVICE int32 [N] of ids in -1..P-1, 1 <= P <= 256, in any order; ids may recur or stay unused; -1
+ * (or any id outside 0..P-1) belongs to no period.  For period g: period_days [P][HW] counts the valid days with id g; count and
+ * prcptot run over those days; rx runs over the windows whose LAST day has id g -- a window may reach back into days of another id
+ * or of id -1 as long as its K days are linked and valid (a running sum over the record, then a maximum per year, as climdex
+ * does).  This differs from the subsequence rule of the groups of sbgm_climate_indices_calendar.  period_rx [M+1][P][Kw][HW],
+ * period_count [M+1][P][T][HW], period_prcptot [M+1][P][HW].  An id no day carries gets period_days 0, count 0 and NaN floats.
+ * Across the periods, for each index i (the Kw windows, then the T thresholds, then prcptot; I = Kw + T + 1): period g counts
+ * when period_days[g] >= min_days (>= 1) and its value is not NaN.  across_n int32 [M+1][I][HW]: the counting periods;
+ * across_mean fp32: the fp64 sum of the fp32 values (counts as exact doubles) in id order / n, rounded once, NaN for n = 0;
+ * across_std fp32: sqrt(sum (v - mean)^2 / (n - 1)) against the unrounded mean, NaN for n < 2.
+ * Every element of every output is written.  With P = 0 the period and across outputs may be NULL, with T = 0 the count maps.
+ * The workspace (size from the query, which returns 0 for arguments the call would reject) holds the validity bits, one word
+ * per day and the wet-day sums of every (series, period, pixel) in fp64: (M + 1) * P * H*W * 8 bytes of it grow with P.  No
+ * atomics: two calls give bit-equal outputs.  Cost: one pass over all series for validity, one for the sweep. */
+#define SBGM_PERIOD_MAX_WINDOWS 4
+#define SBGM_PERIOD_MAX_WINDOW 32
+#define SBGM_PERIOD_MAX_THRESHOLDS 8
+#define SBGM_PERIOD_MAX_PERIODS 256
+#define SBGM_PERIOD_MAX_MEMBERS 4095
+int64_t sbgm_period_indices_workspace_bytes(int N, int M, int H, int W, int Kw, int T, int P);
+int sbgm_period_indices(const float* gen, int64_t member_stride, int64_t day_stride, const float* obs, const void* mask,
+                        int mask_is_u8, int N, int Nm, int M, int H, int W, const int* windows /* HOST */, int Kw,
+                        const float* thresholds /* HOST */, int T, float wet, int min_days,
+                        const int* day_numbers, const int* periods, int P,                        /* DEVICE int32 [N] or NULL */
+                        int* days, float* rx, int* count, float* prcptot, int* period_days, float* period_rx, int* period_count,
+                        float* period_prcptot, int* across_n, float* across_mean, float* across_std, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 /* ---- pooled ensemble verification of a series (verify_series.hip) --------------------------------------
  * sbgm_series_scores: D days (1 <= D <= 4095) of M members (2 <= M <= 4095) E[d][m][p] against one truth Y[d][p] per day, pooled
  * over days x pixels.  Member (d, m) is read at ens + d * day_stride + m * member_stride (strides in elements, each >= H*W; the H*W

@@ -272,12 +272,15 @@ SIGNATURES = {
     "sbgm_climate_calendar_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "sbgm_climate_indices_calendar": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, C.POINTER(_d), _i, C.POINTER(_d), _i, _vp, _vp, _i] +
                                       [_vp] * 15 + [_i64, _vp]),
+    "sbgm_period_indices_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "sbgm_period_indices": (_i, [_vp, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), _i, C.POINTER(_f), _i, _f, _i, _vp,
+                                 _vp, _i] + [_vp] * 12 + [_i64, _vp]),
     "sbgm_series_scores_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i, _i64]),
     "sbgm_series_scores": (_i, [_vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, C.POINTER(_f), _i, _u64, _i] + [_vp] * 10 +
                            [_i64, _vp]),
 }
 
-ABI_VERSION = 19    # include/sbgm_hip.h: sbgm_abi_version()
+ABI_VERSION = 20   # include/sbgm_hip.h: sbgm_abi_version()
 
 _lib = None
 

@@ -11,6 +11,8 @@ import numpy as np
 SEASONS = ("DJF", "MAM", "JJA", "SON")
 MONTHS = ("Jan", "Feb", "Mar", "Apr", "May", "Jun", "Jul", "Aug", "Sep", "Oct", "Nov", "Dec")
 GROUPINGS = ("season", "month")
+PERIODS = ("year", "season_year", "month_year")
+MAX_PERIODS = 256                                 # include/sbgm_hip.h: SBGM_PERIOD_MAX_PERIODS
 
 
 def day_numbers(dates):
@@ -54,6 +56,29 @@ def groups_from_dates(dn, by):
     if by == "season":
         return [int(g) for g in (month % 12) // 3], list(SEASONS)
     return [int(g) for g in month - 1], list(MONTHS)
+
+
+def periods_from_dates(dn, by):
+    """(ids int list, names list) of the periods of a record: by="year" ("2001"), "month_year" ("2001-03") or "season_year",
+    which puts December with the following January and February and names the season by that year ("2002-DJF").  Ids count
+    from 0 at the first period present, in time order; a period without a day gets no id.  More than 256 periods is a
+    ValueError."""
+    if by not in PERIODS:
+        raise ValueError(f"periods: expected one of {PERIODS}, got {by!r}")
+    year, month, _ = civil(dn)
+    if by == "year":
+        key = year
+        name = lambda k: f"{k:04d}"                                                      # noqa: E731
+    elif by == "month_year":
+        key = year * 12 + (month - 1)
+        name = lambda k: f"{k // 12:04d}-{k % 12 + 1:02d}"                               # noqa: E731
+    else:
+        key = (year + (month == 12)) * 4 + (month % 12) // 3
+        name = lambda k: f"{k // 4:04d}-{SEASONS[k % 4]}"                                # noqa: E731
+    present = np.unique(key)                                                            # sorted: time order
+    if present.size > MAX_PERIODS:
+        raise ValueError(f"periods: {by!r} gives {present.size} periods; at most {MAX_PERIODS}")
+    return [int(g) for g in np.searchsorted(present, key)], [name(int(k)) for k in present]
 
 
 def parse_origin(x):

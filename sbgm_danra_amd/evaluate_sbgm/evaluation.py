@@ -273,6 +273,71 @@ def climate_calendar_config(cfg):
     return cal, _groups_setting("evaluation.climate_indices.groups", sec.get("groups"))
 
 
+PERIOD_KEYS = ("windows", "thresholds", "wet", "periods", "min_days", "calendar")
+
+
+def period_indices_config(cfg):
+    """(windows, thresholds, wet, periods, min_days, calendar) of the optional evaluation.period_indices section — `windows`: 1
+    to 4 distinct ascending window lengths in days, each in 1..32 (default [1, 5]: Rx1day and Rx5day); `thresholds`: up to 8
+    finite numbers in the units the generated files hold (default none; 10 gives R10mm); `wet`: the wet-day threshold of PRCPTOT
+    (default 1.0); `periods`: None, "year", "season_year" or "month_year" (from the dates of the series), a list of one id in
+    -1..255 per day (-1: no period), or a .npy path; `min_days`: the valid days a period needs at a pixel to count in the mean
+    and spread across the periods (default 1); `calendar`: None (the default: true when the series has dates) or a bool, whether
+    a gap in the dates breaks a window — or None when the section is absent"""
+    sec = cfg["evaluation"].get("period_indices")
+    if sec is None:
+        return None
+    key = "evaluation.period_indices"
+    if not hasattr(sec, "keys") or not set(sec.keys()) <= set(PERIOD_KEYS):
+        unknown = sorted(set(sec.keys()) - set(PERIOD_KEYS)) if hasattr(sec, "keys") else sec
+        raise ValueError(f"{key} takes the keys {', '.join(repr(k) for k in PERIOD_KEYS)} only, got {unknown!r}")
+    windows = sec.get("windows")
+    windows = [1, 5] if windows is None else windows
+    if (not isinstance(windows, (list, tuple)) or not 1 <= len(windows) <= V.MAX_PERIOD_WINDOWS or
+            any(isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= V.MAX_PERIOD_WINDOW for k in windows) or
+            any(b <= a for a, b in zip(windows, windows[1:]))):
+        raise ValueError(f"{key}.windows must be a list of 1..{V.MAX_PERIOD_WINDOWS} distinct ascending integers in "
+                         f"1..{V.MAX_PERIOD_WINDOW}, got {windows!r}")
+    thresholds = sec.get("thresholds")
+    thresholds = [] if thresholds is None else thresholds
+    if not isinstance(thresholds, (list, tuple)):
+        raise ValueError(f"{key}.thresholds must be a list of numbers, got {thresholds!r}")
+    if len(thresholds) > V.MAX_PERIOD_THRESHOLDS:
+        raise ValueError(f"{key}.thresholds: at most {V.MAX_PERIOD_THRESHOLDS} entries, got {len(thresholds)}")
+    thresholds = _number_list(f"{key}.thresholds", thresholds)
+    wet = sec.get("wet", 1.0)
+    if isinstance(wet, bool) or not isinstance(wet, (int, float)) or not math.isfinite(wet):
+        raise ValueError(f"{key}.wet must be a finite number, got {wet!r}")
+    periods = sec.get("periods")
+    if isinstance(periods, str):
+        if periods not in calendar.PERIODS and not periods.endswith(".npy"):
+            raise ValueError(f"{key}.periods: a string must be one of {calendar.PERIODS} or the path of a .npy file, got {periods!r}")
+    elif periods is not None:
+        if not isinstance(periods, (list, tuple)) or not periods or any(isinstance(g, bool) or not isinstance(g, int) or
+                                                                        not -1 <= g < V.MAX_PERIODS for g in periods):
+            raise ValueError(f"{key}.periods must be null, one of {calendar.PERIODS}, a .npy path or a list of integers in "
+                             f"-1..{V.MAX_PERIODS - 1}, one per day, got {periods!r}")
+        periods = [int(g) for g in periods]
+    min_days = sec.get("min_days", 1)
+    if isinstance(min_days, bool) or not isinstance(min_days, int) or min_days < 1:
+        raise ValueError(f"{key}.min_days must be an integer >= 1, got {min_days!r}")
+    cal = sec.get("calendar")
+    if cal is not None and not isinstance(cal, bool):
+        raise ValueError(f"{key}.calendar must be null, true or false, got {cal!r}")
+    return [int(k) for k in windows], thresholds, float(wet), periods, int(min_days), cal
+
+
+PERIOD_DEFINITION = (
+    "per pixel along the day axis; a day is valid where the truth and every member are not NaN and the mask admits it.  A window of "
+    "K days ending on day t exists when the K days are valid and linked (consecutive in the file, or with `calendar` consecutive "
+    "dates); rx_K = the largest window sum (K = 1: Rx1day, K = 5: Rx5day).  count_T = the valid days with value >= T (R10mm at "
+    "10).  prcptot = the sum over the valid days with value >= wet.  Per period (year, season of a year with December counted to "
+    "the following year, month of a year): count and prcptot over the period's days, rx over the windows whose last day lies in "
+    "the period (a window may begin in the period before, as in climdex).  period_mean / period_std = mean and standard deviation "
+    "(n - 1) across the periods with at least min_days valid days and a defined value.  Each entry compares the model's map with "
+    "the truth's: domain means, bias, RMSE and pattern correlation per member, with mean, minimum and maximum over the members")
+
+
 def series_scores_config(cfg):
     """(thresholds, climatology, groups, seed) of the optional evaluation.series_scores section — `thresholds`: up to 16 finite
     numbers in the units the generated files hold (default none); `climatology`: bool (default true), the leave-one-out
@@ -323,6 +388,21 @@ def _pattern_summary(gen, obs):
     den = math.sqrt(float((dg * dg).sum()) * float((do * do).sum()))
     return {"pixels": int(g.size), "mean_gen": float(g.mean()), "mean_obs": float(o.mean()), "bias": float(g.mean() - o.mean()),
             "rmse": float(np.sqrt(((g - o) ** 2).mean())), "pattern_corr": float((dg * do).sum()) / den if den > 0 else nan}
+
+
+def _members_summary(gen_maps, obs_map):
+    """the pattern summary of every member's map against the truth's map: `per_member`, each statistic as its mean, minimum and
+    maximum over the members (NaNs left out), and `pixels` per member"""
+    per = [_pattern_summary(g, obs_map) for g in gen_maps]
+    row = {"per_member": per}
+    for stat in ("mean_gen", "mean_obs", "bias", "rmse", "pattern_corr"):
+        vals = np.asarray([p[stat] for p in per], np.float64)
+        good = vals[~np.isnan(vals)]
+        row[stat] = {"mean": float(good.mean()) if good.size else float("nan"),
+                     "min": float(good.min()) if good.size else float("nan"),
+                     "max": float(good.max()) if good.size else float("nan")}
+    row["pixels"] = [p["pixels"] for p in per]
+    return row
 
 
 def _nan_quartiles(a):
@@ -727,16 +807,7 @@ class Evaluation:
             for k in V.CLIMATE_FLOAT_KEYS:
                 for j, name in enumerate([f"{k}_{q:g}" for q in levels[k]] if k in levels else [k]):
                     sel = (lambda a: a[j]) if k in levels else (lambda a: a)
-                    per = [_pattern_summary(sel(pick(r, f"gen_{k}")), sel(pick(runs[0], f"obs_{k}"))) for r in runs]
-                    row = {"per_member": per}
-                    for stat in ("mean_gen", "mean_obs", "bias", "rmse", "pattern_corr"):
-                        vals = np.asarray([p[stat] for p in per], np.float64)
-                        good = vals[~np.isnan(vals)]
-                        row[stat] = {"mean": float(good.mean()) if good.size else float("nan"),
-                                     "min": float(good.min()) if good.size else float("nan"),
-                                     "max": float(good.max()) if good.size else float("nan")}
-                    row["pixels"] = [p["pixels"] for p in per]
-                    indices[name] = row
+                    indices[name] = _members_summary([sel(pick(r, f"gen_{k}")) for r in runs], sel(pick(runs[0], f"obs_{k}")))
             return indices
 
         out = {"wet": wet, "quantile_levels": quantiles, "wet_quantile_levels": wet_quantiles, "members": len(runs),
@@ -758,6 +829,80 @@ class Evaluation:
                              for g in range(max(gids) + 1)]
         self.metrics["climate"] = out
         self.climate_fields = res
+        return dict(res, metrics=out)
+
+    def period_statistics(self, windows=None, thresholds=None, wet=None, periods=None, min_days=None, calendar_aware=None):
+        """period climate indices (RxNday, RNNmm, PRCPTOT) along the day axis of the generated fields against their truth
+        ('multiple' or 'series': one truth per day), over the record and per period, all members in one call.  The maps go to a
+        file of their own, <label>_periods.npz, which save() writes: every key of verification.period_indices with the gen maps
+        [M, ...], `windows`, `thresholds`, `wet`, `min_days`, `members` and, when there are any, `dates`, `periods` and
+        `period_names`.  The metrics entry `period_indices` holds, per index (rx_<K>, count_<T>, prcptot) the pattern summary
+        of the model's record map against the truth's and, with periods, of its period_mean and period_std maps, per member and
+        as mean, minimum and maximum over the members.  Arguments default to the evaluation.period_indices section; `periods`
+        is None, "year", "season_year", "month_year" (these need dates), ids in -1..255 or a .npy path."""
+        if self.generated_sample_type not in TIME_AXIS_TYPES:
+            raise ValueError(f"period_statistics needs one truth per day ('multiple' or 'series' samples), not "
+                             f"'{self.generated_sample_type}'")
+        sec = period_indices_config(self.cfg)
+        if sec is None and windows is None:
+            raise ValueError("no windows given and the config has no evaluation.period_indices section")
+        sec = sec if sec is not None else ([1, 5], [], 1.0, None, 1, None)
+        windows, thresholds, wet, periods, min_days, calendar_aware = (
+            d if a is None else a for a, d in zip((windows, thresholds, wet, periods, min_days, calendar_aware), sec))
+        key = "evaluation.period_indices"
+        if calendar_aware and self.dates is None:
+            raise ValueError(f"{key}.calendar is true but {self.label} has no dates (no `dates` in its series_index file)")
+        calendar_aware = self.dates is not None if calendar_aware is None else bool(calendar_aware)
+        D = int(self.gen_imgs.shape[0])
+        if self.eval_imgs.shape[0] != D:
+            raise ValueError(f"period_statistics needs as many truths as days; {self.label} has {self.eval_imgs.shape[0]} for {D}")
+        names = None
+        if isinstance(periods, str) and periods in calendar.PERIODS:
+            if self.dates is None:
+                raise ValueError(f"{key}.periods: '{periods}' needs the dates of the series; {self.label} has none (no `dates` in "
+                                 f"its series_index file)")
+            periods, names = calendar.periods_from_dates(self.dates, periods)
+        elif isinstance(periods, str):
+            periods = np.load(periods)
+        if periods is not None:
+            periods = np.asarray(periods)
+            if periods.ndim != 1 or periods.dtype.kind not in "iu":
+                raise ValueError(f"{key}.periods must hold one integer id per day, got shape {periods.shape} of {periods.dtype}")
+            if len(periods) != D:
+                raise ValueError(f"{key}.periods holds {len(periods)} ids; {self.label} has {D} days")
+            periods = [int(g) for g in periods]
+            names = names if names is not None else [str(g) for g in range(max(periods) + 1)]
+        windows, thresholds = [int(k) for k in windows], [float(t) for t in thresholds]
+        members = self.members if self.members is not None else self.gen_imgs[None]
+        r = V.period_indices(members, self.eval_imgs, windows, thresholds, float(wet), mask=self.mask,
+                             day_numbers=self.dates if calendar_aware else None, periods=periods, min_days=int(min_days))
+        res = {k: v.cpu().numpy() for k, v in r.items()}
+        M = int(members.shape[0])
+        res.update(windows=np.asarray(windows, np.int64), thresholds=np.asarray(thresholds, np.float64), wet=np.float64(wet),
+                   min_days=np.int64(min_days), members=np.int64(M))
+        if self.dates is not None:
+            res["dates"] = np.asarray(self.dates, np.int64)
+        with_periods = "period_days" in res
+        if with_periods:
+            res["periods"], res["period_names"] = np.asarray(periods, np.int64), np.asarray(names)
+
+        indices = {}
+        levels = {"rx": [f"rx_{k}" for k in windows], "count": [f"count_{t:g}" for t in thresholds], "prcptot": ["prcptot"]}
+        for k in V.PERIOD_INDICES:
+            for j, name in enumerate(levels[k]):
+                sel = (lambda a: a) if k == "prcptot" else (lambda a, j=j: a[..., j, :, :])
+                entry = {"record": _members_summary(sel(res[f"gen_{k}"]), sel(res[f"obs_{k}"]))}
+                if with_periods:
+                    for stat in ("period_mean", "period_std"):
+                        entry[stat] = _members_summary(sel(res[f"gen_{stat}_{k}"]), sel(res[f"obs_{stat}_{k}"]))
+                indices[name] = entry
+        out = {"windows": windows, "thresholds": thresholds, "wet": float(wet), "min_days": int(min_days), "members": M, "n_days": D,
+               "pixels": int((res["days"] > 0).sum()), "calendar": bool(calendar_aware),
+               "n_links_broken": int((~calendar.links(self.dates)[1:]).sum()) if calendar_aware else 0,
+               "n_periods": len(names) if with_periods else 0, "period_names": list(names) if with_periods else [],
+               "indices": indices, "definition": PERIOD_DEFINITION}
+        self.metrics["period_indices"] = out
+        self.period_fields = res
         return dict(res, metrics=out)
 
     def series_ensemble_statistics(self, thresholds=None, climatology=None, groups=None, seed=None):
@@ -818,9 +963,11 @@ class Evaluation:
     def save(self):
         """<label>_metrics.json and <label>_fields.npz under the statistics directory; returns their paths.  After
         multivariate_statistics also <label>_multivariate.npz, after climate_statistics also <label>_climate.npz, after
-        series_ensemble_statistics also <label>_series_scores.npz."""
+        series_ensemble_statistics also <label>_series_scores.npz, after period_statistics also <label>_periods.npz."""
         if getattr(self, "series_fields", None):
             np.savez(os.path.join(self.evaluation_stats_path, f"{self.label}_series_scores.npz"), **self.series_fields)
+        if getattr(self, "period_fields", None):
+            np.savez(os.path.join(self.evaluation_stats_path, f"{self.label}_periods.npz"), **self.period_fields)
         if getattr(self, "climate_fields", None):
             np.savez(os.path.join(self.evaluation_stats_path, f"{self.label}_climate.npz"), **self.climate_fields)
         if getattr(self, "multivariate_fields", None):

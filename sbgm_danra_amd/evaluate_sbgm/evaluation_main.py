@@ -10,7 +10,10 @@ every type; an `evaluation.multivariate_scores` section (energy, variogram) adds
 `evaluation.climate_indices` section (wet, quantiles, wet_quantiles) adds the per-pixel climate indices along the day axis for
 `multiple` and `series` (their maps go to `<type>_climate.npz`; for `single` and `repeated` it is logged as skipped); an
 `evaluation.series_scores` section (thresholds, climatology, groups, seed) adds the pooled ensemble verification of a `series`
-over days x pixels (its arrays go to `series_series_scores.npz`; for another type it is logged as skipped); without
+over days x pixels (its arrays go to `series_series_scores.npz`; for another type it is logged as skipped); an
+`evaluation.period_indices` section (windows, thresholds, wet, periods, min_days, calendar) adds the period climate indices
+(RxNday, RNNmm, PRCPTOT per year, season or month of a year, and their mean and spread across those) for `multiple` and `series`
+(their maps go to `<type>_periods.npz`; for `single` and `repeated` it is logged as skipped); without
 a section its statistics do not run and the output files hold what they always held."""
 from __future__ import annotations
 
@@ -21,13 +24,13 @@ import torch
 
 from ..training_utils import setup_logger
 from ..utils import get_model_string
-from .evaluation import (GEN_TYPES, TIME_AXIS_TYPES, Evaluation, climate_indices_config, ensemble_products_config, multivariate_scores_config, object_scores_config, sample_units,
-                         series_scores_config, spatial_scores_config)
+from .evaluation import (GEN_TYPES, TIME_AXIS_TYPES, Evaluation, climate_indices_config, ensemble_products_config, multivariate_scores_config, object_scores_config,
+                         period_indices_config, sample_units, series_scores_config, spatial_scores_config)
 
 # statistic -> (method of Evaluation, config function of the section that switches it on or None, for 'repeated' only).
 # Without a config function the statistic is one evaluation.eval_stat_methods may list; with one it runs, without arguments
 # (it reads its section), after those and in this order whenever the section is there.  'climate_stats' is no ensemble statistic
-# but needs one truth per day: TIME_AXIS_STATISTICS keeps it to 'multiple' and 'series'.  'series_ensemble_stats' needs days x
+# but needs one truth per day, as 'period_stats' does: TIME_AXIS_STATISTICS keeps them to 'multiple' and 'series'.  'series_ensemble_stats' needs days x
 # members: SERIES_STATISTICS keeps it to 'series'.
 STATISTICS = {
     "pixel_stats": ("full_pixel_statistics", None, False),
@@ -41,10 +44,11 @@ STATISTICS = {
     "object_stats": ("object_statistics", object_scores_config, False),
     "multivariate_stats": ("multivariate_statistics", multivariate_scores_config, True),
     "climate_stats": ("climate_statistics", climate_indices_config, False),
+    "period_stats": ("period_statistics", period_indices_config, False),
     "series_ensemble_stats": ("series_ensemble_statistics", series_scores_config, False),
 }
 # statistics along the day axis: they need one truth per day, which 'multiple' and 'series' have
-TIME_AXIS_STATISTICS = ("climate_stats",)
+TIME_AXIS_STATISTICS = ("climate_stats", "period_stats")
 # statistics over days x members: only a 'series' has both
 SERIES_STATISTICS = ("series_ensemble_stats",)
 
@@ -59,6 +63,7 @@ METHODS = _methods_of(None)
 SPATIAL_METHODS, PRODUCT_METHODS = _methods_of(spatial_scores_config), _methods_of(ensemble_products_config)
 OBJECT_METHODS, MULTIVARIATE_METHODS = _methods_of(object_scores_config), _methods_of(multivariate_scores_config)
 CLIMATE_METHODS = _methods_of(climate_indices_config)
+PERIOD_METHODS = _methods_of(period_indices_config)
 SERIES_METHODS = _methods_of(series_scores_config)
 PLOT_KEYS = ("plot_examples", "save_figs", "show_plots", "show_figs", "mask_plots", "plot_w_cond", "plot_w_lsm")
 
@@ -86,7 +91,8 @@ def unit_statistics(cfg, gen_type):
     evaluation.ensemble_products section, for 'repeated' — 'product_stats'; then — only with an evaluation.object_scores
     section — 'object_stats'; then — only with an evaluation.multivariate_scores section, for 'repeated' —
     'multivariate_stats'; then — only with an evaluation.climate_indices section, for 'multiple' and 'series' —
-    'climate_stats'; then — only with an evaluation.series_scores section, for 'series' — 'series_ensemble_stats'"""
+    'climate_stats'; then — only with an evaluation.period_indices section, for 'multiple' and 'series' — 'period_stats';
+    then — only with an evaluation.series_scores section, for 'series' — 'series_ensemble_stats'"""
     stats = eval_stat_methods(cfg)
     for name, (_, config, ensemble_only) in STATISTICS.items():
         if name in TIME_AXIS_STATISTICS and gen_type not in TIME_AXIS_TYPES:
@@ -129,6 +135,10 @@ def evaluation_main(cfg):
         for t in types:
             if t not in TIME_AXIS_TYPES:
                 log.info(f"[INFO] evaluation.climate_indices needs one truth per day ('multiple' or 'series' samples); skipped for '{t}'")
+    if period_indices_config(cfg) is not None:
+        for t in types:
+            if t not in TIME_AXIS_TYPES:
+                log.info(f"[INFO] evaluation.period_indices needs one truth per day ('multiple' or 'series' samples); skipped for '{t}'")
     if series_scores_config(cfg) is not None:
         for t in types:
             if t != "series":

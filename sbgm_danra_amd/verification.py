@@ -4,7 +4,8 @@ statistics, histograms, ensemble scores (CRPS, rank histogram, spread/skill), ra
 table, ROC area), ensemble products (per-pixel mean, spread, envelope, quantile and exceedance-probability maps) and
 object-based scores (connected objects and SAL: structure, amplitude, location) and multivariate ensemble scores (energy score,
 variogram score) and per-pixel climate indices along the day axis (wet-day frequency and intensity, spells, transitions,
-lag-1 autocorrelation, quantiles, heavy-rain fraction) and pooled ensemble scores of a series over days x pixels (csrc/verify_series.hip:
+lag-1 autocorrelation, quantiles, heavy-rain fraction), period climate indices (csrc/verify_periods.hip: RxNday, RNNmm and PRCPTOT
+over the record and per year, their mean and spread across the years) and pooled ensemble scores of a series over days x pixels (csrc/verify_series.hip:
 CRPS and spread/skill maps, rank histogram, reliability table, climatological CRPS skill score, per group of days).  Every function takes tensors on
 the ROCm device and returns tensors on the device; arguments and shapes are checked before any launch and nothing is copied
 to the host.  A pixel is valid when gen (every member) and obs are not NaN and the mask admits it (uint8/bool != 0, or float
@@ -40,6 +41,9 @@ CLIMATE_STATS = ("mean", "wet_freq", "sdii", "max", "p_ww", "p_dw", "lag1")     
 CLIMATE_FLOAT_KEYS = CLIMATE_STATS + ("quantiles", "wet_quantiles", "heavy_fraction")
 CLIMATE_INT_KEYS = ("cwd", "cdd", "transitions")
 MAX_SERIES_GROUPS, MAX_SERIES_MEMBERS = 16, 4095        # include/sbgm_hip.h: SBGM_SERIES_MAX_GROUPS; days: MAX_TEMPORAL_DAYS
+# include/sbgm_hip.h: SBGM_PERIOD_MAX_WINDOWS / _WINDOW / _THRESHOLDS / _PERIODS / _MEMBERS
+MAX_PERIOD_WINDOWS, MAX_PERIOD_WINDOW, MAX_PERIOD_THRESHOLDS, MAX_PERIODS, MAX_PERIOD_MEMBERS = 4, 32, 8, 256, 4095
+PERIOD_INDICES = ("rx", "count", "prcptot")
 SERIES_MAP_KEYS = ("crps", "spread", "skill", "ssr")
 SERIES_CLIM_MAP_KEYS = ("clim_crps", "crpss")
 SERIES_SKILL_KEYS = ("cells", "crps_fair", "crps_reference", "crpss")
@@ -721,4 +725,146 @@ def series_ensemble_scores(ens, obs, thresholds=(), groups=None, mask=None, seed
                skill_scores=skill)
     out.update({k: maps[i].view(H, W) for i, k in enumerate(SERIES_MAP_KEYS)})
     out.update({k: clim_maps[i].view(H, W) for i, k in enumerate(SERIES_CLIM_MAP_KEYS)})
+    return out
+
+
+def _period_ids(periods, n):
+    """(host int list or None, P) of the optional period ids, one per day, each in -1..255; P = the largest id + 1"""
+    if periods is None:
+        return None, 0
+    if isinstance(periods, torch.Tensor):
+        if periods.dim() != 1 or periods.is_floating_point() or periods.dtype == torch.bool:
+            raise ValueError(f"periods: expected a 1-D integer tensor, got {tuple(periods.shape)} of {periods.dtype}")
+        periods = periods.tolist()
+    periods = list(periods)
+    if any(isinstance(g, bool) or int(g) != g for g in periods):
+        raise ValueError(f"period_indices: periods must be integers, got {periods}")
+    periods = [int(g) for g in periods]
+    if len(periods) != n:
+        raise ValueError(f"period_indices: {len(periods)} period ids for N={n} days")
+    if min(periods) < -1 or max(periods) >= MAX_PERIODS:
+        raise ValueError(f"period_indices: period ids must lie in -1..{MAX_PERIODS - 1} (P <= {MAX_PERIODS}), got "
+                         f"{min(periods)}..{max(periods)}")
+    P = max(periods) + 1
+    return (periods, P) if P > 0 else (None, 0)                  # every day outside every period: as without periods
+
+
+def period_indices(gen, obs, windows=(1, 5), thresholds=(), wet=1.0, mask=None, day_numbers=None, periods=None, min_days=1):
+    """multi-day accumulation and threshold-count indices (ETCCDI RxNday, RNNmm, PRCPTOT) per pixel along the day axis, over
+    the record and per period, for gen [N,H,W] or [M,N,H,W] (M members, read by their strides: any fp32 view whose last two
+    dims are dense is not copied) against obs [N,H,W], both fp32 (2 <= N <= 4095; sides 2..2048, H*W <= 2^20), optional mask
+    [H,W] or [N,H,W] by the rules of climate_indices.  `windows`: 1 to 4 distinct ascending lengths in 1..32; `thresholds`: 0
+    to 8 values finite in fp32; `wet`: a number finite in fp32; `day_numbers` as in climate_indices.
+    Validity is paired over everything: day t is valid at pixel p when the mask admits it, obs[t,p] is not NaN and gen[m,t,p]
+    is not NaN for EVERY member m, so `days`, the period day counts and which windows exist are one map for all series.
+    Run length: r[t] = valid[t] ? (linked[t] ? r[t-1] : 0) + 1 : 0 with r[-1] = 0; linked[t] is day_numbers[t] ==
+    day_numbers[t-1] + 1, without day_numbers it is true for t > 0: a broken link acts as one invalid day in between, the
+    rule of climate_indices.  Window K ending on day t exists iff r[t] >= K; its sum is S = ((((+0.0 + x[t-K+1]) + x[t-K+2])
+    + ...) + x[t]) in fp64, oldest day first, each fp32 value widened first (starting from +0.0 makes -0 impossible).
+    Returns a dict of device tensors, for both sides as `gen_<name>` (with a leading [M] axis iff gen was 4-D) and
+    `obs_<name>`: `days` int32 [H,W] (one map); `rx` fp32 [Kw,H,W], the largest S over the windows that exist, rounded to fp32
+    once, NaN where none exists (K = 1 is Rx1day, K = 5 Rx5day); `count` int32 [T,H,W], the valid days with x >= threshold_j
+    compared in fp32 (R10mm at 10); `prcptot` fp32 [H,W], the fp64 sum in day order over the valid days with x >= wet, rounded
+    once, 0 where there is a valid day and no wet one, NaN where days == 0.
+    `periods`: one id per day in -1..255 (a sequence or an integer tensor; P = the largest id + 1); -1 belongs to no period;
+    any order, ids may recur (seasons) or stay unused (calendar.periods_from_dates gives years, seasons and months of years).
+    The dict gains `period_days` int32 [P,H,W], the valid days with id g, and `period_<side>_rx`, `period_<side>_count`,
+    `period_<side>_prcptot` with [P, ...] after the member axis: count and prcptot run over the days of the id, rx over the
+    windows whose LAST day has id g.  A window may reach back into days of another id or of id -1 as long as its K days are
+    linked and valid, which is what climdex does (a running sum over the record, then a maximum per year) and deliberately
+    differs from the subsequence rule of climate_indices' groups.  An id no day uses gives period_days 0, count 0 and NaN
+    float maps.  Across the periods, for each index (every rx window, every count threshold, prcptot) a period counts when
+    period_days[g] >= min_days (>= 1) and its value is not NaN: `<side>_period_n_<index>` int32, the counting periods;
+    `<side>_period_mean_<index>`, the fp64 sum of the fp32 values (counts as exact doubles) in id order / n, rounded once;
+    `<side>_period_std_<index>` = sqrt(sum (v - mean)^2 / (n - 1)) against the unrounded mean for n >= 2, else NaN; index in
+    rx, count, prcptot, shaped as the index.  Every element of every output is written; two calls give bit-equal results,
+    whatever the strides of gen."""
+    name = "period_indices"
+    if gen.dim() not in (3, 4):
+        raise ValueError(f"gen: expected [N, H, W] or [M, N, H, W], got {tuple(gen.shape)}")
+    if obs.dim() != 3:
+        raise ValueError(f"obs: expected [N, H, W], got {tuple(obs.shape)}")
+    for what, x in (("gen", gen), ("obs", obs)):
+        if x.dtype != torch.float32:
+            raise TypeError(f"{what}: expected a float32 tensor, got {x.dtype}")
+    members = gen.dim() == 4
+    M = gen.shape[0] if members else 1
+    n, H, W = gen.shape[-3:]
+    if not (2 <= H <= MAX_FIELD_SIDE and 2 <= W <= MAX_FIELD_SIDE) or H * W > MAX_FIELD_PIXELS:
+        raise ValueError(f"{name}: field size {H}x{W}; sides must be 2..{MAX_FIELD_SIDE} and H*W <= 2^20")
+    if not 2 <= n <= MAX_TEMPORAL_DAYS:
+        raise ValueError(f"{name}: N={n} days; need 2..{MAX_TEMPORAL_DAYS}")
+    if not 1 <= M <= MAX_PERIOD_MEMBERS:
+        raise ValueError(f"{name}: M={M} members; need 1..{MAX_PERIOD_MEMBERS}")
+    if tuple(obs.shape) != (n, H, W):
+        raise ValueError(f"obs: shape {tuple(obs.shape)} does not match gen days and fields {(n, H, W)}")
+    _shape_rows(mask, "mask", (H, W), (1, n))
+    if mask is not None and not (mask.dtype in (torch.uint8, torch.bool) or mask.is_floating_point()):
+        raise TypeError(f"mask: expected uint8, bool or float, got {mask.dtype}")
+    win = list(windows)
+    if not 1 <= len(win) <= MAX_PERIOD_WINDOWS:
+        raise ValueError(f"{name}: {len(win)} windows; need 1..{MAX_PERIOD_WINDOWS}")
+    if any(isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_PERIOD_WINDOW for k in win):
+        raise ValueError(f"{name}: windows must be integers in 1..{MAX_PERIOD_WINDOW}, got {win}")
+    win = [int(k) for k in win]
+    if any(b <= a for a, b in zip(win, win[1:])):
+        raise ValueError(f"{name}: windows must be distinct and ascending, got {win}")
+    thr = [float(t) for t in thresholds]
+    if len(thr) > MAX_PERIOD_THRESHOLDS:
+        raise ValueError(f"{name}: {len(thr)} thresholds; at most {MAX_PERIOD_THRESHOLDS}")
+    tarr = (C.c_float * len(thr))(*thr) if thr else None
+    if thr and not all(math.isfinite(t) and math.isfinite(a) for t, a in zip(thr, tarr)):
+        raise ValueError(f"{name}: thresholds must be finite in fp32, got {thr}")
+    if isinstance(wet, bool) or not isinstance(wet, (int, float)) or not math.isfinite(wet) or not math.isfinite(C.c_float(wet).value):
+        raise ValueError(f"{name}: wet must be a number finite in fp32, got {wet!r}")
+    if isinstance(min_days, bool) or not isinstance(min_days, int) or not 1 <= min_days < 2 ** 31:
+        raise ValueError(f"{name}: min_days must be an integer >= 1, got {min_days!r}")
+    dn = _day_numbers(day_numbers, n)
+    pids, P = _period_ids(periods, n)
+    N.require_device(gen, obs)
+    if obs.device != gen.device:
+        raise ValueError("gen and obs must be on the same device")
+    HW = H * W
+    if members:
+        g = gen
+        if g.stride(3) != 1 or g.stride(2) != W or g.stride(1) < HW or (M > 1 and g.stride(0) < HW):
+            g = g.contiguous()
+        mstride, dstride = (g.stride(0) if M > 1 else 0), g.stride(1)
+    else:
+        g = gen.contiguous()
+        mstride, dstride = 0, HW
+    o = obs.contiguous()
+    m, u8, nm = _mask(mask, HW, (1, n))
+    Kw, T, S, dev = len(win), len(thr), M + 1, g.device
+    I = Kw + T + 1
+    i32 = dict(dtype=torch.int32, device=dev)
+    days, rx, count, prc = torch.empty(HW, **i32), torch.empty(S, Kw, HW, device=dev), torch.empty(S, T, HW, **i32), torch.empty(S, HW, device=dev)
+    pdays, prx, pcount = torch.empty(P, HW, **i32), torch.empty(S, P, Kw, HW, device=dev), torch.empty(S, P, T, HW, **i32)
+    pprc = torch.empty(S, P, HW, device=dev)
+    an, amean, astd = torch.empty(S, I, HW, **i32), torch.empty(S, I, HW, device=dev), torch.empty(S, I, HW, device=dev)
+    dn_dev = None if dn is None else torch.tensor(dn, dtype=torch.int32, device=dev)
+    p_dev = None if pids is None else torch.tensor(pids, dtype=torch.int32, device=dev)
+    nbytes = N.lib().sbgm_period_indices_workspace_bytes(n, M, H, W, Kw, T, P)
+    ws = _ws(nbytes, dev)
+    have = lambda t, on=True: t.data_ptr() if on and t.numel() else None                          # noqa: E731
+    N.check(N.lib().sbgm_period_indices(
+        g.data_ptr(), mstride, dstride, o.data_ptr(), N.ptr(m), u8, n, nm, M, H, W, (C.c_int * Kw)(*win), Kw, tarr, T, float(wet),
+        min_days, N.ptr(dn_dev), N.ptr(p_dev), P, days.data_ptr(), rx.data_ptr(), have(count), prc.data_ptr(), have(pdays), have(prx),
+        have(pcount), have(pprc), have(an, P), have(amean, P), have(astd, P), ws.data_ptr(), nbytes, N.stream()))
+
+    def sides(t):
+        """t [M + 1, ..., HW] -> (the member rows, without their axis for a 3-D gen; the obs row), each [..., H, W]"""
+        v = t.unflatten(-1, (H, W))
+        return (v[:M] if members else v[0]), v[M]
+
+    out = {"days": days.view(H, W)}
+    for key, t in (("rx", rx), ("count", count), ("prcptot", prc)):
+        out[f"gen_{key}"], out[f"obs_{key}"] = sides(t)
+    if P:
+        out["period_days"] = pdays.view(P, H, W)
+        for key, t in (("rx", prx), ("count", pcount), ("prcptot", pprc)):
+            out[f"period_gen_{key}"], out[f"period_obs_{key}"] = sides(t)
+        for stat, t in (("n", an), ("mean", amean), ("std", astd)):
+            for key, sl in (("rx", slice(0, Kw)), ("count", slice(Kw, Kw + T)), ("prcptot", Kw + T)):
+                out[f"gen_period_{stat}_{key}"], out[f"obs_period_{stat}_{key}"] = sides(t[:, sl])
     return out
